@@ -15,7 +15,13 @@ then top-k) over this rank's resident library. Workloads (BASELINE.json `configs
 * `--pockets 16 --ligands 1253376`: the per-GPU shard of configs[3] (16 pockets x one shared library);
 * `--model stress64`: configs[4] - the 64-node model against 64-conformer ligands (100 352 of them by default).
 
-Rank 0 prints ONE JSON line. `value` is measured with the library already resident in HBM.
+Rank 0 prints ONE JSON line. `value` is measured with the library already resident in HBM; `ms_per_step` is one
+timed step. A plain run sets up, warms up, times the `--steps` steps and prints that line. `--dump-outputs DIR` writes
+what the last timed step handed back (scores, status, top-k) as DIR/<name>.npy; the inputs are seeded, so two builds can
+be compared output for output.
+
+`--full` adds the side measurements, each of which costs runs of its own: `roofline`, `issue` and `work` (one extra
+profiled pass), `parity_sample`, `cpu_baseline`, `end_to_end` and `survey_library` (the `--no-*` switches trim them).
 `roofline.achieved` prices the dominant kernel (the one with the largest HIP-event time per chunk) at the
 ALGORITHMIC bytes of the path (packed ligand bytes + 8-byte offset in, 4-byte score + 4-byte status out, per
 ligand it processes) over its HIP-event duration; this path is not HBM-bound, the fraction is
@@ -40,6 +46,8 @@ sys.path.insert(0, str(REPO))
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s HBM3E spec
 PROFILE_TAG = "r6"  # the committed rocprofv3 --pmc summaries (profiles/<tag>_*.json) the static blocks of the line are read from
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files of all ranks together
+DUMP_SAMPLE_SEED = 20240601   # the ligands kept when the per-ligand arrays do not fit the budget
 
 # name -> (model file under tests/golden, conformers, ligands on one GPU, topologies, fraction of ligands drawn on the model's nodes,
 #          (seed of the topologies | None = tools.synthetic.BASE_SEED, offset of the perturbation stream's seed))
@@ -571,6 +579,44 @@ def issue_block(n_lig, pass_ms):
             "note": "instruction counts are NOT measured in this run: they come from the committed rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_VALU pass of the same build of csrc/ (checked by content hash), priced at this run's pass time"}
 
 
+def dump_outputs(out_dir, results, rank=0, world=1, budget=DUMP_BUDGET_BYTES):
+    """`--dump-outputs`: what the timed path handed back in its last step - per pocket the scores and status of this rank's ligands
+    and the (merged) top-k - as out_dir/<name>.npy in float32 (scores, status) or float64 (top-k indices, exact below 2^53).
+    Names carry `_pocketNN` with several pockets and `_rankR` with several ranks. When the per-ligand arrays of all pockets and ranks
+    exceed the budget, every array keeps the same seeded sample of ligand positions, written as `ligand_index` (float64)."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = results[0][0].scores.numel()
+    topk_bytes = sum(t[0].numel() * 12 for _, t in results)
+    per_ligand = 8 * len(results)  # float32 score + float32 status per pocket
+    room = budget // max(world, 1) - topk_bytes - 256 * (1 + 4 * len(results))  # (a .npy header is 128 bytes)
+    index = None
+    if n * per_ligand > room:
+        m = max(0, room // (per_ligand + 8))  # (+ the float64 index itself)
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=min(m, n), replace=False))
+    suffix_rank = f"_rank{rank}" if world > 1 else ""
+    written = {}
+
+    def save(name, t, dtype):
+        a = t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        path = os.path.join(out_dir, f"{name}{suffix_rank}.npy")
+        np.save(path, a.astype(dtype))
+        written[os.path.basename(path)] = list(a.shape)
+
+    if index is not None:
+        save("ligand_index", index, np.float64)
+        index_dev = torch.from_numpy(index).to(results[0][0].scores.device)
+    for p, (res, top) in enumerate(results):
+        tag = f"_pocket{p:02d}" if len(results) > 1 else ""
+        scores, status = (res.scores, res.status) if index is None else (res.scores[index_dev], res.status[index_dev])
+        save("scores" + tag, scores, np.float64 if scores.dtype == torch.float64 else np.float32)
+        save("status" + tag, status, np.float32)
+        save("topk_scores" + tag, top[0], np.float32)
+        save("topk_indices" + tag, top[1], np.float64)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -584,12 +630,18 @@ def main():
     ap.add_argument("--library", choices=("expanded", "survey"), default="expanded",
                     help="expanded: molecule topologies x jittered copies (tools/synthetic.py; the default line); survey: SURVEY.md 8d-2's generator, every ligand an independent draw (tools/survey_library.py)")
     ap.add_argument("--pockets", type=int, default=1, help="score this many distinct pockets (1..16) against the shared library (BASELINE configs[3])")
+    ap.add_argument("--full", action="store_true", help="also the side measurements: profiled pass (roofline, issue, work), parity sample, CPU baseline, "
+                                                         "end-to-end legs, survey-library leg; without it the run times the steps and prints the headline line only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-serial-leg", action="store_true", help="skip the end-to-end (pack + copy) side measurement")
-    ap.add_argument("--no-survey-leg", action="store_true", help="skip the side measurement on SURVEY 8d-2's own library (the default line carries it as `survey_library`)")
+    ap.add_argument("--no-survey-leg", action="store_true", help="skip the side measurement on SURVEY 8d-2's own library (the --full line carries it as `survey_library`)")
     ap.add_argument("--no-parity-sample", action="store_true")
     ap.add_argument("--dump-dir", default=None, help="every rank writes its shard's scores and rank 0 the merged top-k here (tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help=f"write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most {DUMP_BUDGET_BYTES >> 20} MB: a seeded sample of the ligands beyond that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         start_ranks(args)  # does not return
@@ -650,8 +702,12 @@ def main():
     n_conf_total = lib.total_conformers
     index_base = rank * n_lig
 
+    keep_all = args.dump_outputs is not None
+
     def step():
-        for pocket in pockets:  # pocket-outer / ligand-inner: the library stays resident, every pocket makes one pass
+        # (result, ranking) of the last pocket; of every pocket with --dump-outputs (what a caller of the path receives)
+        results = []
+        for p, pocket in enumerate(pockets):  # pocket-outer / ligand-inner: the library stays resident, every pocket makes one pass
             res = engine.screen(pocket, lib, topk=args.topk, index_base=index_base)
             if world > 1:
                 if exchange is not None:  # RCCL all-gather + merge on the device through libpmx's C ABI; the ranking stays on the device
@@ -660,7 +716,9 @@ def main():
                     top = allgather_topk_device(res.topk_scores, res.topk_indices, args.topk)  # rehearsal transport, the device merge of the RCCL path
             else:
                 top = (res.topk_scores, res.topk_indices)
-        return res, top
+            if keep_all or p == len(pockets) - 1:
+                results.append((res, top))
+        return results
 
     def barrier():
         if world > 1:
@@ -673,9 +731,15 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        res, top = step()
+        if keep_all:
+            results = None  # (a step that keeps every pocket's results does not also hold the previous step's)
+        results = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    res, top = results[-1]
+    if args.dump_outputs:
+        written = dump_outputs(args.dump_outputs, results, rank, world)
+        log(f"[rank {rank}] outputs of the last timed step in {args.dump_outputs}: {written}")
     if args.dump_dir:
         os.makedirs(args.dump_dir, exist_ok=True)
         np.savez(os.path.join(args.dump_dir, f"rank{rank}.npz"), scores=res.scores.cpu().numpy(), index_base=index_base,
@@ -683,7 +747,7 @@ def main():
     # One more, untimed pass with HIP events around the phases (pmx_set_profiling: event records only) and the device
     # counters read back: the kernel durations behind the roofline block.
     prof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         engine.set_profiling(True)
         try:
             engine.screen(pockets[-1], lib, topk=args.topk, index_base=index_base)
@@ -701,26 +765,7 @@ def main():
     if rank == 0:
         ms_per_step = elapsed * 1e3 / max(args.steps, 1)
         value = world * n_conf_total * len(pockets) * args.steps / elapsed
-        # algorithmic bytes: records + 8 B offset in, 4 B score + 4 B status out, per ligand
-        alg_bytes_per_ligand = lib.num_bytes / n_lig + 8 + 4 + 4
-        kernels = {
-            "ligand_kernel (score tables in per-wavefront slices + tree search within the pass budget; 3 launches: slices, large slices, arena)": prof["ms_ligand"],
-            "task_kernel (queued subtrees of over-budget trees; all rounds) + finalize": prof["ms_tasks"],
-        }
-        dominant = max(kernels, key=kernels.get)
-        dom_ms = kernels[dominant]
-        ligands_per_launch = prof["ligands_last"]
-        achieved = (alg_bytes_per_ligand * ligands_per_launch) / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        # HBM traffic per launch from the committed PMC passes (FETCH_SIZE / WRITE_SIZE, collected separately with
-        # rocprofv3 --pmc and corrected as MI355X_MICROARCH.md prescribes), scaled to this launch's ligands - quoted only
-        # when the summary was taken on this build of csrc/ and on this workload
         bench_shape = args.model == "6oim" and args.conformers == 8 and len(pockets) == 1 and args.library == "expanded"
-        traffic, traffic_src = None, "profiled on the 6OIM-like model at 8 conformers only: not quoted for this workload"
-        if bench_shape:
-            pmc, traffic_src = committed_profile("hbm_traffic")
-            if pmc is not None:
-                key = "ligand_kernel" if dominant.startswith("ligand_kernel") else "task_kernel"
-                traffic = pmc["kernels"][key]["hbm_bytes_per_ligand"] * ligands_per_launch
         model_words = {"6oim": "6OIM-like model (37 nodes, 11 clusters)", "stress64": "stress model (64 nodes, 54 clusters)"}[args.model]
         out = {
             "metric": f"ligand-conformers scored/sec ({len(pockets)} pocket{'s' if len(pockets) > 1 else ''})",
@@ -755,90 +800,113 @@ def main():
                 "exchange": None if world == 1 else ({"collective": "ncclAllGather of per-rank top-k (pmx_topk_allgather, merge on the device)", "rccl_ranks": exchange.rccl_ranks, "control_plane": control}
                                                      if exchange is not None else {"collective": f"{backend} all_gather of per-rank top-k (rehearsal transport) + the device merge of pmx_topk_allgather (pmx_topk over the gathered lists)", "ranks": world}),
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": dominant,
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_from_profile": traffic_src,
-                "traffic_note": "NOT measured in this run: HBM bytes per ligand of that kernel from the committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same build of csrc/ (content hash checked; separate runs, read side doubled per MI355X_MICROARCH.md), scaled to this launch's ligands; null if no summary of this build and workload is committed",
-                "algorithmic_bytes_per_ligand": alg_bytes_per_ligand,
-                "ligands_per_launch": ligands_per_launch,
-                "kernel_ms_per_launch": kernels,
-                "profiled_pass_ms": prof["ms_total"],
-                "note": "HIP-event times of one extra, untimed pass with pmx_set_profiling(1) (event records on the call's stream, no synchronisation); "
-                        "the timed steps run with profiling off. The path is not HBM-bound (SURVEY.md section 0, DESIGN.md section 4): what binds is "
-                        "instruction issue and memory latency, see `issue` (DESIGN.md section 4).",
-            },
-            # The resource that is busiest on this path: the CU's scalar unit, one wave-instruction per cycle.
-            "issue": issue_block(n_lig, prof["ms_total"]) if bench_shape else None,
-            # what the kernels do per ligand
-            "work": {
-                "tree_frames_per_ligand": prof["n_frames"] / max(n_lig, 1),
-                "walker_passes_per_ligand": prof["n_passes"] / max(n_lig, 1),
-                "table_items_per_ligand_conformer": prof["n_items"] * (64 // max(1, 1 << (args.conformers - 1).bit_length())) / max(n_lig, 1),  # (wave-iterations x slots of a wavefront)
-                "queued_subtrees_per_ligand": prof["n_tasks"] / max(n_lig, 1),
-                "path_bound_tests_per_ligand": prof["n_path_bounds"] / max(n_lig, 1),
-                "children_dropped_by_path_bound_per_ligand": prof["n_path_drops"] / max(n_lig, 1),
-                "probe_passes_per_ligand": prof["n_probe_passes"] / max(n_lig, 1),
-                "walks_over_budget_per_ligand": prof["n_heavy"] / max(n_lig, 1),
-                "ligands_with_tables_beyond_a_slice": prof["n_slice_overflow"],
-                "longest_walk_passes": prof["max_passes"],
-                # (above 1: split trees found the table arena full and were walked by one wavefront each - exact, slow: PMX_SUPER / PMX_ARENA_MB)
-                "arena_asked_over_capacity": prof["arena_bytes"] / max(prof.get("arena_capacity", 0), 1),
-                "wave_time_share": {k: prof["ticks_" + k] / max(prof["ticks_alive"], 1) for k in ("scan", "tables", "bounds", "walk")},
-            },
             "csrc_sha16": csrc_digest(),
+            "full": args.full,
         }
-        if not args.no_parity_sample:
-            try:
-                out["parity_sample"] = parity_sample(pockets[-1], res.scores, offsets, data)
-            except Exception as e:  # never lose the bench line over the check - but say so
-                out["parity_sample"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"], work = cpu_baseline(pockets, offsets, data, args.conformers)
-            # Gaussian terms as the reference evaluates them (counted by the oracle on the same ligands) per second: the
-            # table phase replaces each group of |A||B| terms by one tabulated pair function, so this is an equivalent rate
-            terms_per_conf = work["gaussian_terms_per_ligand_conformer"]
-            out["work"].update(work)
-            out["work"]["reference_equivalent_gaussian_terms_per_s"] = terms_per_conf * value
-            out["work"]["reference_terms_per_table_item"] = terms_per_conf / max(out["work"]["table_items_per_ligand_conformer"], 1e-9)
-        else:
-            out["cpu_baseline"] = None
-        if world == 1 and not args.no_serial_leg and molecules is not None:
-            try:
-                out["end_to_end"] = end_to_end(molecules, lib, data, ms_per_step, n_conf_total * len(pockets))
-                if len(pockets) == 1:
-                    out["end_to_end"].update(end_to_end_overlapped(molecules, pockets[0], n_lig, args.topk, device))
-                    out["end_to_end"].update(end_to_end_device_packed(molecules, pockets[0], n_lig, args.topk, device))
-            except Exception as e:  # never lose the bench line over the side measurement
-                out["end_to_end"] = {**(out.get("end_to_end") or {}), "error": repr(e)}
-        # The same pass on SURVEY.md 8d-2's OWN generator (`--library survey` makes it the line's workload): a side block of the default line, so that
-        # one driver run carries both libraries. Untimed for `value`; its own warm-up, two timed passes, its own parity sample.
-        if world == 1 and bench_shape and not args.no_survey_leg and args.ligands >= 1_000_000:
-            try:
-                slib, soff, sdata, sstats = build_survey_library(model, 1_000_000, args.conformers, 0, device, wl_active)
-                engine.screen(model, slib, topk=args.topk)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(2):
-                    sres = engine.screen(model, slib, topk=args.topk)
-                torch.cuda.synchronize()
-                sdt = (time.perf_counter() - t0) / 2
-                out["survey_library"] = {
-                    "value": slib.total_conformers / sdt, "unit": "ligand-conformers/s", "ms_per_step": sdt * 1e3, "ligands": len(slib),
-                    "library_stats": sstats, "command": "python bench.py --library survey",
-                    "parity_sample": None if args.no_parity_sample else parity_sample(model, sres.scores, soff, sdata),
-                    "note": "tools/survey_library.py: every ligand an independent draw (n ~ clip(N(20, 6), 4, 32), conformer sigma 0.5 A, 10 % on the model's nodes at 0.7 A); "
-                            "5.5 x the tree search per ligand of the default library",
-                }
-                slib.close()
-                del soff, sdata
-            except Exception as e:  # never lose the bench line over the side measurement
-                out["survey_library"] = {"error": repr(e)}
+        if args.full:  # the side measurements: an extra profiled pass, the oracle, the host legs, a second library
+            # algorithmic bytes: records + 8 B offset in, 4 B score + 4 B status out, per ligand
+            alg_bytes_per_ligand = lib.num_bytes / n_lig + 8 + 4 + 4
+            kernels = {
+                "ligand_kernel (score tables in per-wavefront slices + tree search within the pass budget; 3 launches: slices, large slices, arena)": prof["ms_ligand"],
+                "task_kernel (queued subtrees of over-budget trees; all rounds) + finalize": prof["ms_tasks"],
+            }
+            dominant = max(kernels, key=kernels.get)
+            dom_ms = kernels[dominant]
+            ligands_per_launch = prof["ligands_last"]
+            achieved = (alg_bytes_per_ligand * ligands_per_launch) / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+            # HBM traffic per launch from the committed PMC passes (FETCH_SIZE / WRITE_SIZE, collected separately with
+            # rocprofv3 --pmc, read side doubled by tools/collect_profiles.py), scaled to this launch's ligands - quoted only
+            # when the summary was taken on this build of csrc/ and on this workload
+            traffic, traffic_src = None, "profiled on the 6OIM-like model at 8 conformers only: not quoted for this workload"
+            if bench_shape:
+                pmc, traffic_src = committed_profile("hbm_traffic")
+                if pmc is not None:
+                    key = "ligand_kernel" if dominant.startswith("ligand_kernel") else "task_kernel"
+                    traffic = pmc["kernels"][key]["hbm_bytes_per_ligand"] * ligands_per_launch
+            out.update({
+                "roofline": {
+                    "bound": "hbm",
+                    "kernel": dominant,
+                    "achieved": achieved,
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": traffic,
+                    "traffic_from_profile": traffic_src,
+                    "traffic_note": "NOT measured in this run: HBM bytes per ligand of that kernel from the committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same build of csrc/ (content hash checked; separate runs, read side doubled by tools/collect_profiles.py), scaled to this launch's ligands; null if no summary of this build and workload is committed",
+                    "algorithmic_bytes_per_ligand": alg_bytes_per_ligand,
+                    "ligands_per_launch": ligands_per_launch,
+                    "kernel_ms_per_launch": kernels,
+                    "profiled_pass_ms": prof["ms_total"],
+                    "note": "HIP-event times of one extra, untimed pass with pmx_set_profiling(1) (event records on the call's stream, no synchronisation); "
+                            "the timed steps run with profiling off. The path is not HBM-bound (SURVEY.md section 0, DESIGN.md section 4): what binds is "
+                            "instruction issue and memory latency, see `issue` (DESIGN.md section 4).",
+                },
+                # The resource that is busiest on this path: the CU's scalar unit, one wave-instruction per cycle.
+                "issue": issue_block(n_lig, prof["ms_total"]) if bench_shape else None,
+                # what the kernels do per ligand
+                "work": {
+                    "tree_frames_per_ligand": prof["n_frames"] / max(n_lig, 1),
+                    "walker_passes_per_ligand": prof["n_passes"] / max(n_lig, 1),
+                    "table_items_per_ligand_conformer": prof["n_items"] * (64 // max(1, 1 << (args.conformers - 1).bit_length())) / max(n_lig, 1),  # (wave-iterations x slots of a wavefront)
+                    "queued_subtrees_per_ligand": prof["n_tasks"] / max(n_lig, 1),
+                    "path_bound_tests_per_ligand": prof["n_path_bounds"] / max(n_lig, 1),
+                    "children_dropped_by_path_bound_per_ligand": prof["n_path_drops"] / max(n_lig, 1),
+                    "probe_passes_per_ligand": prof["n_probe_passes"] / max(n_lig, 1),
+                    "walks_over_budget_per_ligand": prof["n_heavy"] / max(n_lig, 1),
+                    "ligands_with_tables_beyond_a_slice": prof["n_slice_overflow"],
+                    "longest_walk_passes": prof["max_passes"],
+                    # (above 1: split trees found the table arena full and were walked by one wavefront each - exact, slow: PMX_SUPER / PMX_ARENA_MB)
+                    "arena_asked_over_capacity": prof["arena_bytes"] / max(prof.get("arena_capacity", 0), 1),
+                    "wave_time_share": {k: prof["ticks_" + k] / max(prof["ticks_alive"], 1) for k in ("scan", "tables", "bounds", "walk")},
+                },
+            })
+            if not args.no_parity_sample:
+                try:
+                    out["parity_sample"] = parity_sample(pockets[-1], res.scores, offsets, data)
+                except Exception as e:  # never lose the bench line over the check - but say so
+                    out["parity_sample"] = {"error": repr(e)}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"], work = cpu_baseline(pockets, offsets, data, args.conformers)
+                # Gaussian terms as the reference evaluates them (counted by the oracle on the same ligands) per second: the
+                # table phase replaces each group of |A||B| terms by one tabulated pair function, so this is an equivalent rate
+                terms_per_conf = work["gaussian_terms_per_ligand_conformer"]
+                out["work"].update(work)
+                out["work"]["reference_equivalent_gaussian_terms_per_s"] = terms_per_conf * value
+                out["work"]["reference_terms_per_table_item"] = terms_per_conf / max(out["work"]["table_items_per_ligand_conformer"], 1e-9)
+            else:
+                out["cpu_baseline"] = None
+            if world == 1 and not args.no_serial_leg and molecules is not None:
+                try:
+                    out["end_to_end"] = end_to_end(molecules, lib, data, ms_per_step, n_conf_total * len(pockets))
+                    if len(pockets) == 1:
+                        out["end_to_end"].update(end_to_end_overlapped(molecules, pockets[0], n_lig, args.topk, device))
+                        out["end_to_end"].update(end_to_end_device_packed(molecules, pockets[0], n_lig, args.topk, device))
+                except Exception as e:  # never lose the bench line over the side measurement
+                    out["end_to_end"] = {**(out.get("end_to_end") or {}), "error": repr(e)}
+            # The same pass on SURVEY.md 8d-2's OWN generator (`--library survey` makes it the line's workload): a side block of the default line, so that
+            # one driver run carries both libraries. Untimed for `value`; its own warm-up, two timed passes, its own parity sample.
+            if world == 1 and bench_shape and not args.no_survey_leg and args.ligands >= 1_000_000:
+                try:
+                    slib, soff, sdata, sstats = build_survey_library(model, 1_000_000, args.conformers, 0, device, wl_active)
+                    engine.screen(model, slib, topk=args.topk)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(2):
+                        sres = engine.screen(model, slib, topk=args.topk)
+                    torch.cuda.synchronize()
+                    sdt = (time.perf_counter() - t0) / 2
+                    out["survey_library"] = {
+                        "value": slib.total_conformers / sdt, "unit": "ligand-conformers/s", "ms_per_step": sdt * 1e3, "ligands": len(slib),
+                        "library_stats": sstats, "command": "python bench.py --library survey",
+                        "parity_sample": None if args.no_parity_sample else parity_sample(model, sres.scores, soff, sdata),
+                        "note": "tools/survey_library.py: every ligand an independent draw (n ~ clip(N(20, 6), 4, 32), conformer sigma 0.5 A, 10 % on the model's nodes at 0.7 A); "
+                                "5.5 x the tree search per ligand of the default library",
+                    }
+                    slib.close()
+                    del soff, sdata
+                except Exception as e:  # never lose the bench line over the side measurement
+                    out["survey_library"] = {"error": repr(e)}
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -44,3 +44,50 @@ def test_reference_rate_file_is_what_bench_quotes():
     assert ref is not None and ref["kind"] == "reference" and ref["cores"] == 1 and ref["value"] > 0
     for row in ref["sets"].values():
         assert row["ligand_conformers"] == 8 * row["ligands"]
+
+
+def _fake_results(n, pockets, k, seed):
+    """What bench.py's step() returns, on the CPU: per pocket (result with scores / status, (top-k scores, top-k indices))."""
+    from types import SimpleNamespace
+
+    import torch
+
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(pockets):
+        scores = torch.from_numpy(rng.random(n, dtype=np.float32))
+        status = torch.from_numpy(rng.integers(0, 2, n).astype(np.int32))
+        top = torch.topk(scores, k)
+        out.append((SimpleNamespace(scores=scores, status=status), (top.values, top.indices.to(torch.int64) + 10**9)))
+    return out
+
+
+def test_dump_outputs_writes_every_array_in_float(tmp_path):
+    import bench
+
+    results = _fake_results(5000, 2, 7, seed=1)
+    written = bench.dump_outputs(tmp_path, results)
+    assert sorted(written) == sorted(f"{a}_pocket{p:02d}.npy" for a in ("scores", "status", "topk_scores", "topk_indices") for p in (0, 1))
+    for p, (res, top) in enumerate(results):
+        s = np.load(tmp_path / f"scores_pocket{p:02d}.npy")
+        assert s.dtype == np.float32 and np.array_equal(s, res.scores.numpy())
+        st = np.load(tmp_path / f"status_pocket{p:02d}.npy")
+        assert st.dtype == np.float32 and np.array_equal(st, res.status.numpy())
+        ti = np.load(tmp_path / f"topk_indices_pocket{p:02d}.npy")
+        assert ti.dtype == np.float64 and ti.astype(np.int64).tolist() == top[1].tolist()
+
+
+def test_dump_outputs_keeps_a_fixed_sample_within_the_budget(tmp_path):
+    import bench
+
+    n, budget = 100_000, 200_000
+    results = _fake_results(n, 1, 5, seed=2)
+    bench.dump_outputs(tmp_path / "a", results, rank=1, world=2, budget=budget)
+    bench.dump_outputs(tmp_path / "b", results, rank=1, world=2, budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(f"{a}_rank1.npy" for a in ("ligand_index", "scores", "status", "topk_scores", "topk_indices"))
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= budget // 2  # (this rank's share of the budget)
+    index = np.load(tmp_path / "a" / "ligand_index_rank1.npy")
+    assert index.dtype == np.float64 and 0 < len(index) < n and np.all(np.diff(index) > 0)
+    np.testing.assert_array_equal(index, np.load(tmp_path / "b" / "ligand_index_rank1.npy"))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "scores_rank1.npy"), results[0][0].scores.numpy()[index.astype(np.int64)])

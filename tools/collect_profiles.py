@@ -4,7 +4,7 @@
   python tools/collect_profiles.py <bench.json> <kernel_stats.csv> <fetch_dir> <write_dir> <sq_dir> [ligands_in_pmc_run]
 
 The PMC passes are separate runs (`--pmc FETCH_SIZE`, `--pmc WRITE_SIZE`, one SQ pass) of
-`bench.py --ligands 200000 --steps 1 --warmup 0`; FETCH_SIZE / WRITE_SIZE are KiB and the read side is
+`bench.py --full --ligands 200000 --steps 1 --warmup 0`; FETCH_SIZE / WRITE_SIZE are KiB and the read side is
 doubled as MI355X_MICROARCH.md prescribes for gfx950.
 """
 import collections
@@ -58,7 +58,7 @@ def main():
                 cnt[k] += 1
         res[ctr] = (tot, cnt)
     out = {
-        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of bench.py --ligands 200000 --steps 1 --warmup 0",
+        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of bench.py --full --ligands 200000 --steps 1 --warmup 0",
         "note": "FETCH_SIZE / WRITE_SIZE in KiB; hbm_bytes_per_ligand = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 / (ligands * passes) for the engine's kernels "
                 "(`passes` engine passes ran under the profiler: the timed step and bench.py's profiled pass; the summaries of rounds 3 "
                 "and of the first round-4 sets divided by ligands only and are 2x too high), the read side doubled per MI355X_MICROARCH.md (gfx950 reports half of wide coalesced reads; narrow accesses are "
@@ -102,7 +102,7 @@ def main():
         if cyc and ms:
             clock = {"GRBM_GUI_ACTIVE": cyc, "kernel_ms": ms, "kernel": "ligand_kernel launches of the same command under --pmc GRBM_GUI_ACTIVE --kernel-trace", "xcds": 8,
                      "clock_hz": cyc / 8 / (ms * 1e-3), "note": "GRBM_GUI_ACTIVE summed over the 8 XCDs / kernel time: an upper estimate of the shader clock under this load"}
-    json.dump({**({"clock": clock} if clock else {}), "source": "rocprofv3 --pmc SQ_* (one profiler run) of bench.py --ligands 200000 --steps 1 --warmup 0; SQ_WAVE_CYCLES, "
+    json.dump({**({"clock": clock} if clock else {}), "source": "rocprofv3 --pmc SQ_* (one profiler run) of bench.py --full --ligands 200000 --steps 1 --warmup 0; SQ_WAVE_CYCLES, "
                          "SQ_WAIT_* and SQ_ACTIVE_* count quad-cycles; totals over the run's engine passes (SQ_WAVES / 18432 = passes)",
                "ligands": n_lig, "passes": n_pass, "csrc_sha16": sha, "counters": sq},
               open(PROF / f"{TAG}_pmc_sq_summary.json", "w"), indent=1)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timeline of the last device-packed end-to-end run from a rocprofv3 trace (kernel + memory-copy CSVs of `bench.py`):
 
-    rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d DIR -o t -- python bench.py --no-survey-leg --no-cpu-baseline --no-parity-sample
+    rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d DIR -o t -- python bench.py --full --no-survey-leg --no-cpu-baseline --no-parity-sample
     python tools/e2e_timeline.py DIR/t
 
 Prints, for the last window that holds three record_kernel launches, every kernel family and copy direction with first start / last end (ms from the window's start) and busy time."""

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L > $OUT/avail.txt 2>&1
 grep -o -E "\b(SQ_[A-Z_0-9]*IFETCH[A-Z_0-9]*|SQC_[A-Z_0-9]+|SQ_INSTS_SMEM[A-Z_0-9]*|SQ_WAIT_INST_[A-Z_0-9]+|SQ_INST_CYCLES_[A-Z_0-9]+|SQ_BUSY_CYCLES|SQ_ACTIVE_INST_[A-Z_0-9]+|SQ_INSTS_BRANCH|SQ_INSTS_SENDMSG|SQ_INSTS_VSKIPPED|SQ_INSTS_FLAT[A-Z_0-9]*|SQ_INSTS_VMEM[A-Z_0-9]*)\b" $OUT/avail.txt | sort -u > $OUT/names.txt
 cat $OUT/names.txt | tr '\n' ' '
-run() { tag=$1; shift; timeout 240 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$tag -o p -- python $ROOT/bench.py --ligands 200000 --steps 1 --warmup 0 --no-cpu-baseline --no-serial-leg --no-parity-sample > $OUT/$tag.log 2>&1; echo "$tag rc=$?"; }
+run() { tag=$1; shift; timeout 240 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$tag -o p -- python $ROOT/bench.py --full --ligands 200000 --steps 1 --warmup 0 --no-cpu-baseline --no-serial-leg --no-parity-sample > $OUT/$tag.log 2>&1; echo "$tag rc=$?"; }
 run ic SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_WAIT_IFETCH SQ_WAVE_CYCLES
 run dc SQC_DCACHE_REQ SQC_DCACHE_HITS SQC_DCACHE_MISSES SQ_INSTS_SMEM SQ_WAVE_CYCLES
 run act SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_MISC SQ_INSTS_BRANCH SQ_WAVE_CYCLES SQ_BUSY_CYCLES

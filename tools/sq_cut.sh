@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-.}; OUT=$ROOT/gpurun_out/sq_cut; mkdir -p $OUT; cd /tmp;
 for name in product "$@"; do
   if [ "$name" = product ]; then unset PMX_LIBPMX; else export PMX_LIBPMX=$ROOT/variants/libpmx_$name.so; fi
   rm -rf $OUT/$name
-  PMX_TREE_FLAGS=16384 timeout 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $OUT/$name -o p -- python $ROOT/bench.py --ligands 200000 --steps 1 --warmup 0 --no-cpu-baseline --no-serial-leg --no-parity-sample > $OUT/$name.log 2>&1
+  PMX_TREE_FLAGS=16384 timeout 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $OUT/$name -o p -- python $ROOT/bench.py --full --ligands 200000 --steps 1 --warmup 0 --no-cpu-baseline --no-serial-leg --no-parity-sample > $OUT/$name.log 2>&1
   python3 - "$OUT/$name" "$name" <<'P'
 import csv, glob, collections, sys
 acc = collections.defaultdict(float); n = 0

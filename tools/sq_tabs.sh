@@ -1,5 +1,5 @@
 ROOT=$GRAFT_REPO_ROOT; OUT=$ROOT/gpurun_out/sq_tabs; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-run() { tag=$1; shift; timeout 200 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$tag -o p -- python $ROOT/bench.py --ligands 200000 --steps 1 --warmup 0 --no-cpu-baseline --no-serial-leg --no-parity-sample > $OUT/$tag.log 2>&1; echo "$tag rc=$?"; }
+run() { tag=$1; shift; timeout 200 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$tag -o p -- python $ROOT/bench.py --full --ligands 200000 --steps 1 --warmup 0 --no-cpu-baseline --no-serial-leg --no-parity-sample > $OUT/$tag.log 2>&1; echo "$tag rc=$?"; }
 PMX_TREE_FLAGS=16384 run tabs SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_BRANCH SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES
 run clk GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_INSTS_SALU
 python3 - <<'P'

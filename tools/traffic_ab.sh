@@ -8,7 +8,7 @@ for name in product "$@"; do
   if [ "$name" = product ]; then unset PMX_LIBPMX; else export PMX_LIBPMX=$ROOT/variants/libpmx_$name.so; fi
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf $OUT/${name}_$c
-    rocprofv3 --pmc $c --output-format csv -d $OUT/${name}_$c -o p -- python $ROOT/bench.py --ligands 200000 --steps 1 --warmup 0 ${TRAFFIC_ARGS:-} --no-cpu-baseline --no-serial-leg --no-parity-sample > $OUT/${name}_$c.log 2>&1
+    rocprofv3 --pmc $c --output-format csv -d $OUT/${name}_$c -o p -- python $ROOT/bench.py --full --ligands 200000 --steps 1 --warmup 0 ${TRAFFIC_ARGS:-} --no-cpu-baseline --no-serial-leg --no-parity-sample > $OUT/${name}_$c.log 2>&1
   done
   python - "$OUT" "$name" <<'PY'
 import collections, csv, sys
