@@ -44,6 +44,8 @@ typedef enum {
 #define PMX_LIGAND_OK 0
 #define PMX_LIGAND_UNSUPPORTED 1 /* record exceeds a structural limit; score is NaN */
 #define PMX_LIGAND_TOO_LARGE 2   /* the ligand's score tables exceed the whole table arena (PMX_ARENA_MB); score is NaN */
+#define PMX_LIGAND_EXPLAIN_MISS 3 /* pmx_explain: a conformer's maximum was not met by any leaf (reserved: the explain walker records the
+                                     leaf that sets each maximum, so it cannot occur; a caller that sees it has found a bug) */
 
 typedef struct pmx_model pmx_model;
 typedef struct pmx_library pmx_library;
@@ -307,6 +309,30 @@ int pmx_density_labels(pmx_density *d, int32_t *labels_out);
 int pmx_density_order(pmx_density *d, int32_t n_components, const int32_t *comp_map, const int32_t *comp_seed,
                       const int32_t *comp_offset, int32_t *members_out);
 int pmx_density_destroy(pmx_density *d);
+
+/*
+ * What a score is made of, for a list of ligands (a ranked screen's hits): per conformer c < C the float64 maximum over the leaves
+ * of the reference's tree (`scores` inside GraphMatcher._run_average, graph_match.py:103-109 - their mean is what pmx_score_f64
+ * returns, bit for bit the same values) and the key of the leaf that reaches it (ClusterMatchTree.key, tree.py:129-137): per
+ * tree level the model cluster (its index in model.node_clusters) that the level's ligand cluster is matched to, or 0xFF for
+ * None. Ties: the FIRST leaf in `root_tree.iteration()` order with that score - the one a strict `>` update keeps; children
+ * are in ascending model-cluster order with None last (tree.py:88-101), so this is the lexicographically smallest key with None
+ * after every cluster.
+ *   ligands_dev[n]        library indices, any order, repeats allowed; an index outside the library is reported PMX_LIGAND_UNSUPPORTED
+ *   conf_max_dev          double [n][PMX_MAX_CONFORMERS]: the maxima (0 where no leaf holds the conformer with a score > 0), lanes >= C are 0
+ *   match_dev             uint8 [n][PMX_MAX_CONFORMERS][PMX_MAX_LEVELS]: the keys; 0xFF throughout for a conformer whose maximum is 0 and
+ *                         for levels >= nl
+ *   levels_dev            uint8 [n][PMX_MAX_LEVELS]: the ligand cluster of tree level l (its index in the record's priority-ordered cluster
+ *                         list: clusters without a candidate are skipped, at most PMX_MAX_LEVELS, graph_match.py:87-88,124-137); 0xFE for l >= nl
+ *   best_conformer_dev    int32 [n]: the smallest c with the largest maximum (-1 for a ligand with a non-zero status)
+ *   status_dev            int32 [n]: PMX_LIGAND_* as pmx_score reports it; an unsupported or too large ligand has NaN maxima
+ * n <= PMX_EXPLAIN_MAX. The call is stream-ordered like pmx_score (enqueued, no synchronisation) and uses the same workspace of
+ * (device, stream). Each listed ligand's tables are built as pmx_score builds them and its tree is walked to its end by one
+ * wavefront (pmx_explain.hip): no pass budget, no task queue - the call costs about its largest tree.
+ */
+#define PMX_EXPLAIN_MAX 65536
+int pmx_explain(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev, uint32_t n,
+                double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev, int32_t *status_dev, void *stream);
 
 /* Frees the scoring workspaces libpmx keeps between calls on `device` (synchronises the device first). */
 int pmx_release_workspaces(int device);

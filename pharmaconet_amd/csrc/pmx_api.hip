@@ -21,6 +21,7 @@
 #include "pmx.h"
 #include "pmx_screen.hip"
 #include "pmx_debug.h"
+#include "pmx_explain.h"
 
 using namespace pmx;
 
@@ -617,8 +618,9 @@ struct ScreenWs {
                 if (e) (void)hipEventDestroy(e);
             c = ChunkSet{};
         }
-        for (void *q : {(void *)slices, (void *)big, (void *)totbuf, (void *)pabuf})
+        for (void *q : {(void *)slices, (void *)big, (void *)totbuf, (void *)pabuf, (void *)xctl})
             if (q) (void)hipFree(q);
+        xctl = nullptr;
         slices = big = totbuf = pabuf = nullptr;
         slices_bytes = big_bytes = totbuf_bytes = pabuf_bytes = 0;
         for (auto &e : ev) {
@@ -630,6 +632,7 @@ struct ScreenWs {
         ev_valid = false;
         ctl_used[0] = ctl_used[1] = false;
     }
+    Ctl *xctl = nullptr;   // pmx_explain's control block (its own: the statistics of the last pmx_score stay what that call left)
     uint64_t stamp = 0;    // last use (ensure_screen): the least recently used workspace of a device goes first
     bool released = false; // pmx_release_workspaces (or the cap on workspaces per device) took the buffers: a caller that was waiting on `mu` asks for a new workspace
 };
@@ -721,29 +724,56 @@ struct PocketPlan {
     uint32_t pa_bytes = 0; // path_bound()'s buffer per wavefront
 };
 
+// Events, side stream and control blocks of a workspace, on its first call (num_cu is set last: a workspace whose events, stream or
+// control blocks could not be made stays uninitialised).
+static int init_workspace(ScreenWs &ws, int device) {
+    if (ws.num_cu) return PMX_OK;
+    auto init = [&]() -> int {
+        hipDeviceProp_t prop;
+        HIPCHECK(hipGetDeviceProperties(&prop, device));
+        for (auto &e : ws.ev) HIPCHECK(hipEventCreate(&e));
+        HIPCHECK(hipStreamCreateWithFlags(&ws.side, hipStreamNonBlocking));
+        for (ChunkSet &c : ws.set) {
+            HIPCHECK(hipMalloc((void **)&c.ctl, sizeof(Ctl)));
+            HIPCHECK(hipEventCreateWithFlags(&c.lig_done, hipEventDisableTiming));
+            HIPCHECK(hipEventCreateWithFlags(&c.tasks_done, hipEventDisableTiming));
+        }
+        ws.num_cu = prop.multiProcessorCount;
+        return PMX_OK;
+    };
+    const int irc = init();
+    if (irc) ws.free_buffers();
+    return irc;
+}
+
+// Type weights further apart than PMX_TAILS_RATIO (default 8 = the ratio of the reference's own defaults, graph_match.py:32-40: any override that spreads the weights further takes the exact tails): pair items
+// evaluate rough cells term by term like self items do (item_finish<TAILS>, pmx_screen.hip) - slower, and only then.
+// PMX_PAIR_TAILS = 0 / 1 forces it off / on. Decided over all models of a call (pmx_score_multi: the pockets' types together).
+static bool pair_tails(const pmx_model *const *models, int n_models, const Weights &W) {
+    float wmin = INFINITY, wmax = 0.f;
+    bool present[PMX_NUM_TYPES] = {};
+    for (int m = 0; m < n_models; ++m)
+        for (int i = 0; i < models[m]->dm.Nm; ++i) present[models[m]->node_type[i]] = true; // (only the types the pockets hold can meet in an entry)
+    for (int t = 0; t < PMX_NUM_TYPES; ++t) {
+        const float a = std::fabs(W.w[t]);
+        if (present[t] && a > 0.f && std::isfinite(a)) wmin = std::min(wmin, a), wmax = std::max(wmax, a);
+    }
+    const char *rs = std::getenv("PMX_TAILS_RATIO");
+    const double ratio = (rs && *rs) ? std::atof(rs) : 8.0;
+    bool tails = wmax > 0.f && (double)wmax > ratio * (double)wmin;
+    const long force = env_long("PMX_PAIR_TAILS", -1);
+    if (force == 0) tails = false;
+    if (force > 0) tails = true;
+    return tails;
+}
+
 template <int G>
 static int score_screen(const pmx_model *const *models, int n_models, const pmx_library *lib, const Weights &W, uint64_t first, uint64_t count,
                         void *scores_dev, bool scores_f64, int32_t *status_dev, hipStream_t stream, ScreenWs &ws) {
     if (count > 0xfffffff0ull) return fail(PMX_ERR_INVALID, "more than 2^32 ligands in one call");
-    if (!ws.num_cu) { // (num_cu is set last: a workspace whose events, stream or control blocks could not be made stays uninitialised)
-        auto init = [&]() -> int {
-            hipDeviceProp_t prop;
-            HIPCHECK(hipGetDeviceProperties(&prop, lib->device));
-            for (auto &e : ws.ev) HIPCHECK(hipEventCreate(&e));
-            HIPCHECK(hipStreamCreateWithFlags(&ws.side, hipStreamNonBlocking));
-            for (ChunkSet &c : ws.set) {
-                HIPCHECK(hipMalloc((void **)&c.ctl, sizeof(Ctl)));
-                HIPCHECK(hipEventCreateWithFlags(&c.lig_done, hipEventDisableTiming));
-                HIPCHECK(hipEventCreateWithFlags(&c.tasks_done, hipEventDisableTiming));
-            }
-            ws.num_cu = prop.multiProcessorCount;
-            return PMX_OK;
-        };
-        const int irc = init();
-        if (irc) {
-            ws.free_buffers();
-            return irc;
-        }
+    {
+        const int irc = init_workspace(ws, lib->device);
+        if (irc) return irc;
     }
     const uint32_t flags = (uint32_t)env_long("PMX_TREE_FLAGS", 0);
     const uint32_t max_nodes = (uint32_t)std::max(4, std::min(lib->info.max_nodes, PMX_MAX_LIGAND_NODES));
@@ -759,26 +789,7 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
     // any validation switch: the kernels of pmx_screen_debug.hip (libpmx's own read those bits as zero, pmx_screen.hip PMX_WFLAGS)
     const bool debug_kernels = (flags & ~PMX_PRODUCT_FLAGS) != 0;
     bool debug_ok = true;
-    // Type weights further apart than PMX_TAILS_RATIO (default 8 = the ratio of the reference's own defaults, graph_match.py:32-40: any override that spreads the weights further takes the exact tails): pair items
-    // evaluate rough cells term by term like self items do (item_finish<TAILS>, pmx_screen.hip) - slower, and only then.
-    // PMX_PAIR_TAILS = 0 / 1 forces it off / on.
-    bool tails = false;
-    {
-        float wmin = INFINITY, wmax = 0.f;
-        bool present[PMX_NUM_TYPES] = {};
-        for (int m = 0; m < n_models; ++m)
-            for (int i = 0; i < models[m]->dm.Nm; ++i) present[models[m]->node_type[i]] = true; // (only the types the pockets hold can meet in an entry)
-        for (int t = 0; t < PMX_NUM_TYPES; ++t) {
-            const float a = std::fabs(W.w[t]);
-            if (present[t] && a > 0.f && std::isfinite(a)) wmin = std::min(wmin, a), wmax = std::max(wmax, a);
-        }
-        const char *rs = std::getenv("PMX_TAILS_RATIO");
-        const double ratio = (rs && *rs) ? std::atof(rs) : 8.0;
-        tails = wmax > 0.f && (double)wmax > ratio * (double)wmin;
-        const long force = env_long("PMX_PAIR_TAILS", -1);
-        if (force == 0) tails = false;
-        if (force > 0) tails = true;
-    }
+    const bool tails = pair_tails(models, n_models, W); // (term-by-term tails for widely spread type weights, see pair_tails)
     // arena passes over the ligands an arena pass had no room for, each with the arena to itself (a pass with an empty list exits at
     // once): a ligand is reported PMX_LIGAND_TOO_LARGE when its tables exceed the whole arena - or when the arena-class ligands of a
     // chunk need more than 1 + PMX_ARENA_RETRIES arenas
@@ -1189,3 +1200,156 @@ extern "C" int pmx_release_workspaces(int device) {
 
 // error hook for pmx_topk.hip (keeps the thread-local message in one translation unit)
 int pmx_topk_fail(int code, const char *msg) { return fail(code, "%s", msg); }
+
+// ------------------------------------------------------------------------------------ explain (pmx_explain.hip)
+// The listed ligands' tables are built as pmx_score builds them - per-wave slices, then large slices, then the arena with its
+// retries - and each is walked to its end by one wavefront of the explain kernel: no budget, no task queue.
+template <int G>
+static int explain_screen(const pmx_model *model, const pmx_library *lib, const Weights &W, const pmx_xpl::Args &a, hipStream_t stream, ScreenWs &ws) {
+    {
+        const int irc = init_workspace(ws, lib->device);
+        if (irc) return irc;
+    }
+    const bool tails = pair_tails(&model, 1, W); // (as pmx_score / pmx_score_f64 decide it for this model)
+    const uint32_t max_nodes = (uint32_t)std::max(4, std::min(lib->info.max_nodes, PMX_MAX_LIGAND_NODES));
+    ScreenParams p{};
+    p.M = model->dm;
+    int rc = pair_functions(const_cast<pmx_model *>(model), W, stream, &p.F);
+    if (rc) return rc;
+    p.lib = lib->dl;
+    p.sidtab = model->sidtab;
+    p.sub_off = model->sub_off;
+    p.sub_nodes = model->sub_nodes;
+    p.W = W;
+    p.flags = PMX_SCORES_F64;
+    p.max_nodes = max_nodes;
+    p.bound_cost = (uint32_t)std::max<long>(0, env_long("PMX_BOUND_COST", 8192));
+    p.dead_min_entries = (uint32_t)std::max<long>(1, env_long("PMX_DEAD_MIN_ENTRIES", 32));
+    p.status = a.status;
+    // the per-wave buffers as score_screen sizes them (the same workspace serves both)
+    const WaveShape<G> shape = wave_shape<G>(model->dm.K, (int)max_nodes);
+    const size_t lds = pmx_xpl::lds_bytes(G, model->dm.K, (int)max_nodes);
+    const uint32_t waves_per_cu = (uint32_t)std::max<long>(2, std::min<long>({(long)(kLdsPerCu / shape.bytes), 4L * PMX_SCREEN_WAVES, env_long("PMX_WAVES_PER_CU", 32)}));
+    const uint32_t task_waves_per_cu = (uint32_t)std::max<long>(2, std::min<long>({(long)(kLdsPerCu / shape.bytes), 4L * PMX_TASK_WAVES, env_long("PMX_TASK_WAVES_PER_CU", 32)}));
+    const uint32_t grid = (uint32_t)ws.num_cu * std::max(waves_per_cu, task_waves_per_cu);
+    const long k_scale = std::max(1L, std::min(16L, ((long)model->dm.K * model->dm.K + 60) / 121));
+    const uint32_t slice_bytes = (uint32_t)std::max<long>(4, env_long("PMX_SLICE_KB", (cand_bounds<G>() ? 112L : 80L) * std::max(1, G / 8) * k_scale)) * 1024u;
+    const uint64_t nlmax = (uint64_t)std::min<int>(PMX_MAX_LEVELS, std::max(1, lib->info.max_clusters));
+    const uint64_t K = (uint64_t)std::max(1, std::min(model->dm.K, PMX_MAX_LEVEL_CANDIDATES));
+    const uint64_t worst = rec_bytes<G>((uint32_t)(nlmax * K), (uint32_t)(nlmax * (nlmax - 1) / 2 * K * K), (uint32_t)nlmax);
+    const uint64_t cap = (uint64_t)std::max<long>(1, env_long("PMX_BIG_SLICE_MB", G >= 32 ? 4 : 32)) << 20;
+    const uint32_t big_bytes = (uint32_t)std::max<uint64_t>(slice_bytes, (std::min(worst, cap) + 4095) & ~4095ull);
+    const uint64_t big_total = (uint64_t)std::max<long>(64, env_long("PMX_BIG_TOTAL_MB", G >= 32 ? 16384 : 4096)) << 20;
+    const uint32_t big_grid = (uint32_t)std::max<uint64_t>(16, std::min<uint64_t>(grid, big_total / big_bytes));
+    uint32_t pa_bytes = 0;
+    size_t pabuf_need = 0;
+    if (cand_bounds<G>()) {
+        const uint64_t need = (nlmax + 1) * nlmax * K * G * 4;
+        pa_bytes = (uint32_t)std::min<uint64_t>((need + 255) & ~255ull, (uint64_t)std::max<long>(1, env_long("PMX_PATH_KB", 1024)) << 10);
+        pabuf_need = (size_t)grid * pa_bytes * 2u;
+    }
+    rc = grow(&ws.slices, &ws.slices_bytes, (size_t)grid * slice_bytes, stream, ws.side);
+    if (rc) return rc;
+    rc = grow(&ws.big, &ws.big_bytes, (size_t)big_grid * big_bytes, stream, ws.side);
+    if (rc) return rc;
+    if (pabuf_need) {
+        rc = grow(&ws.pabuf, &ws.pabuf_bytes, pabuf_need, stream, ws.side);
+        if (rc) return rc;
+    }
+    if (!totals_in_lds<G>()) { // (the table phase stages node distances and chain lengths there at 32 / 64 lanes)
+        rc = grow(&ws.totbuf, &ws.totbuf_bytes, (size_t)ws.num_cu * 4u * std::max(PMX_SCREEN_WAVES, PMX_TASK_WAVES) * kTotBufBytes * 2u, stream, ws.side);
+        if (rc) return rc;
+    }
+    ChunkSet &c = ws.set[0];
+    if (!c.arena) { // (an arena made by pmx_score is taken as it is)
+        size_t arena_want = (size_t)std::max<long>(1, env_long("PMX_ARENA_MB", G >= 32 ? 32768 : 65536)) << 20;
+        if (!std::getenv("PMX_ARENA_MB")) {
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b / 3 < arena_want) {
+                arena_want = std::max<size_t>((size_t)1 << 30, (free_b / 3) & ~(((size_t)1 << 20) - 1));
+                c.arena_shrunk_to = arena_want;
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+        const size_t asked = arena_want;
+        rc = grow(&c.arena, &c.arena_bytes, arena_want, stream, ws.side, std::min<size_t>((size_t)1 << 30, arena_want));
+        if (rc) return rc;
+        if (c.arena_bytes < asked) c.arena_shrunk_to = c.arena_bytes;
+    }
+    rc = grow(&c.lists, &c.lists_bytes, (size_t)a.n * 12, stream, ws.side);
+    if (rc) return rc;
+    if (!ws.xctl) HIPCHECK(hipMalloc((void **)&ws.xctl, sizeof(Ctl)));
+    p.ctl = ws.xctl;
+    p.arena = c.arena;
+    p.arena_bytes = std::min<unsigned long long>(c.arena_bytes, (1ull << 36) - 4096);
+    p.ovf_list = c.lists;
+    p.carry_list = c.lists + a.n;
+    p.heavy_list = c.lists + 2 * (size_t)a.n;
+    p.list_cap = a.n;
+    p.pabuf = ws.pabuf;
+    p.pa_bytes = pa_bytes;
+    p.totbuf = ws.totbuf;
+    p.hi = a.n;
+
+    pmx_xpl::launch_init(a, stream);
+    ctl_clear_kernel<<<dim3((sizeof(Ctl) / 4 + 255) / 256), dim3(256), 0, stream>>>(ws.xctl, 1);
+    const uint32_t full = (uint32_t)ws.num_cu * waves_per_cu;
+    bool ok = true;
+    auto launch = [&](int mode, uint32_t blocks) { ok &= pmx_xpl::launch(G, tails, mode, std::max(1u, blocks), (unsigned)lds, stream, &p, sizeof p, a); };
+    p.slices = ws.slices;
+    p.slice_bytes = slice_bytes;
+    launch(0, std::min(full, a.n));
+    p.slices = ws.big;
+    p.slice_bytes = big_bytes;
+    launch(1, std::min(big_grid, full));
+    p.retry_out = c.lists;
+    p.retry_slot = 0;
+    launch(2, std::min(big_grid, full));
+    if (worst > big_bytes) {
+        const int arena_retries = (int)std::max<long>(1, env_long("PMX_ARENA_RETRIES", 4));
+        for (int t = 0; t < arena_retries; ++t) {
+            retry_prep_kernel<<<dim3(1), dim3(64), 0, stream>>>(ws.xctl, (uint32_t)(t + 1) & 1u);
+            p.retry_in = (t & 1) == 0 ? c.lists : c.lists + a.n;
+            p.retry_out = t + 1 == arena_retries ? nullptr : ((t & 1) == 0 ? c.lists + a.n : c.lists);
+            p.retry_slot = (uint32_t)(t + 1) & 1u;
+            launch(3, std::min(big_grid, full));
+        }
+    }
+    pmx_xpl::launch_fixup(a, stream);
+    HIPCHECK(hipGetLastError());
+    if (!ok) return fail(PMX_ERR_INVALID, "the explain kernels (pmx_explain.hip) do not match this build's parameter block");
+    return PMX_OK;
+}
+
+extern "C" int pmx_explain(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev, uint32_t n,
+                           double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev, int32_t *status_dev, void *stream_) {
+    if (!model || !lib || !weights) return fail(PMX_ERR_INVALID, "null argument");
+    if (n > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "more than %d ligands in one explain call", PMX_EXPLAIN_MAX);
+    if (n == 0) return PMX_OK;
+    if (!ligands_dev || !conf_max_dev || !match_dev || !levels_dev || !best_conformer_dev || !status_dev) return fail(PMX_ERR_INVALID, "null argument");
+    if (model->device != lib->device) return fail(PMX_ERR_INVALID, "model and library live on different devices");
+    HIPCHECK(hipSetDevice(lib->device));
+    Weights W;
+    for (int t = 0; t < PMX_NUM_TYPES; ++t) W.w[t] = weights[t];
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    pmx_xpl::Args a{ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev};
+    const int G = next_pow2(std::max(1, std::min(lib->info.max_conformers, PMX_MAX_CONFORMERS)));
+    std::shared_ptr<ScreenWs> ws;
+    std::unique_lock<std::mutex> lock;
+    for (;;) {
+        ws = ensure_screen(lib->device, stream);
+        lock = std::unique_lock<std::mutex>(ws->mu);
+        if (!ws->released) break;
+        lock.unlock();
+    }
+    switch (G) {
+    case 1: return explain_screen<1>(model, lib, W, a, stream, *ws);
+    case 2: return explain_screen<2>(model, lib, W, a, stream, *ws);
+    case 4: return explain_screen<4>(model, lib, W, a, stream, *ws);
+    case 8: return explain_screen<8>(model, lib, W, a, stream, *ws);
+    case 16: return explain_screen<16>(model, lib, W, a, stream, *ws);
+    case 32: return explain_screen<32>(model, lib, W, a, stream, *ws);
+    default: return explain_screen<64>(model, lib, W, a, stream, *ws);
+    }
+}

@@ -1,0 +1,350 @@
+// pmx_explain.hip - what a score is made of, on gfx950: for listed ligands the per-conformer maxima that pmx_score averages
+// (graph_match.py:103-109, `scores` inside _run_average) and, per conformer, the leaf of the reference's tree that reaches
+// its maximum (ClusterMatchTree.key, tree.py:129-137).
+//
+// pmx_screen.hip is compiled here once more, as namespace pmx_x: the explain kernel builds a ligand's tables with the product's
+// own prepare_ligand (same slices, large slices and arena passes, same statuses) and walks them with a walker of its own. The
+// product kernels of libpmx (namespace pmx, pmx_api.hip) are not instantiated in this translation unit and do not change.
+//
+// The explaining leaf of conformer c is the first leaf in `root_tree.iteration()` order whose score for c equals the maximum -
+// the leaf a strict `>` update in _run_average keeps. This walker visits the tree in that order (candidates in ascending
+// model-cluster order, the skip child last, tree.py:88-101) and updates with a strict `>`, so the first leaf it records at the
+// final maximum IS that leaf. A child is dropped only when no leaf below it can reach the running maximum of any of its
+// conformers ((total + R) * kBoundSlack < running maximum, strictly; the running maximum is never above the final one), so
+// no leaf that ties the maximum is ever dropped, and only children with >= 5 matches are dropped at all: their existence alone
+// settles every skip decision above them (tree.py:98, see walk() in pmx_screen.hip). Leaf totals are summed as the product
+// walker sums them - (parent + self) + (pair entries of the matched ancestors, shallowest first) in float64 - so the maxima
+// are bit for bit the ones pmx_score averages.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstring>
+
+#define PMX_NS pmx_x
+#include "pmx_screen.hip"
+#include "pmx_explain.h"
+
+namespace pmx_x {
+
+constexpr uint8_t kNoMatch = 0xFF, kNoLevel = 0xFE;
+
+// The explain walker's LDS, behind the product's per-wave layout.
+template <int G>
+struct ExplainLds {
+    uint32_t tot, key, frame, mrow, path, cb, bytes;
+};
+template <int G>
+__host__ __device__ inline ExplainLds<G> explain_lds(const WaveShape<G> &ws) {
+    ExplainLds<G> e;
+    uint32_t o = (ws.bytes + 15u) & ~15u;
+    e.tot = o; // double [frame][G]: the total of each frame's tree node (frame f = the node whose children are the candidates of level f)
+    o += (PMX_MAX_LEVELS + 1) * G * 8;
+    e.key = o; // u8 [G][PMX_MAX_LEVELS]: the key of the leaf holding conformer c's maximum, as candidate numbers
+    o += (uint32_t)round16((uint64_t)G * PMX_MAX_LEVELS);
+    e.frame = o; // int [PMX_MAX_LEVELS + 1]: nb | mx << 8 | any << 16 | matched << 17 | nm << 24
+    o += 4 * 24;
+    e.mrow = o; // int [PMX_MAX_LEVELS]: pair entry of match q against candidate x = mrow[q] + x
+    o += 4 * PMX_MAX_LEVELS;
+    e.path = o; // u8 [PMX_MAX_LEVELS]: the candidate taken at each level of the current path (kNoMatch: the skip child)
+    o += 32;
+    e.cb = o; // u64 [PMX_MAX_LEVELS][2]: model clusters that are candidates of each level
+    o += 16 * PMX_MAX_LEVELS;
+    e.bytes = o;
+    return e;
+}
+
+// The tree of one prepared ligand (tables at `rec`), maxima and keys into row li of the output. Lane c < G is conformer c.
+template <int G>
+__device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const ExplainLds<G> &E, const unsigned char *rec, uint64_t lig, uint32_t li,
+                             const pmx_xpl::Args &a) {
+    const int lane = lane_id();
+    const int c = lane & (G - 1);
+    const bool mine = lane < G; // (lanes >= G idle)
+    const RecHeader *H = reinterpret_cast<const RecHeader *>(rec);
+    const int nl = uni((int)H->nl), C = uni((int)H->C);
+    const uint32_t ksumtot = (uint32_t)uni((int)H->ksumtot), T = (uint32_t)uni((int)H->T);
+    const float *S = reinterpret_cast<const float *>(rec + rec_s_off<G>());
+    const float *P = reinterpret_cast<const float *>(rec + rec_p_off<G>(ksumtot));
+    const double *R = reinterpret_cast<const double *>(rec + rec_r_off<G>(ksumtot, T));
+    double *tot = reinterpret_cast<double *>(lds + E.tot);
+    uint8_t *key = lds + E.key;
+    int *frame = reinterpret_cast<int *>(lds + E.frame);
+    int *mrow = reinterpret_cast<int *>(lds + E.mrow);
+    uint8_t *path = lds + E.path;
+    unsigned long long *cbl = reinterpret_cast<unsigned long long *>(lds + E.cb);
+
+    uint32_t vbits = (mine && c < C) ? 1u : 0u; // bit f: conformer c is in the pair_scores of frame f's node (tree.py:78-84)
+    double best = 0.0;                           // running maximum of conformer c (graph_match.py:105-108)
+    if (mine) {
+        tot[c] = 0.0;
+        for (int l = 0; l < PMX_MAX_LEVELS; ++l) key[c * PMX_MAX_LEVELS + l] = kNoMatch;
+    }
+    if (lane == 0) frame[0] = 0;
+    wave_sync();
+    const double slack = kBoundSlack;
+    int f = 0;
+    for (;;) {
+        if (f == nl) { // a leaf: its pair_scores are the frame's totals over the frame's conformers
+            if (mine && ((vbits >> f) & 1u)) {
+                const double t = tot[f * G + c];
+                if (t > best) {
+                    best = t;
+                    for (int l = 0; l < nl; ++l) key[c * PMX_MAX_LEVELS + l] = path[l];
+                }
+            }
+            const int ret = (uni(frame[f]) >> 17) & 1;
+            --f;
+            const int st = uni(frame[f]);
+            const int mx = max((st >> 8) & 255, ret);
+            wave_sync();
+            if (lane == 0) frame[f] = (st & ~0xff00) | (mx << 8);
+            wave_sync();
+            continue;
+        }
+        const int st = uni(frame[f]);
+        int nb = st & 255, mx = (st >> 8) & 255, any = (st >> 16) & 1;
+        const int matched = (st >> 17) & 1, nm = (st >> 24) & 255;
+        const int kf = uni((int)H->k[f]), ksf = uni((int)H->ksum[f]);
+        if (nb < kf) { // candidate nb of level f: does the child exist, and what are its totals (tree.py:33-41, 78-84)
+            const int b = nb++;
+            const uint32_t x = (uint32_t)(ksf + b);
+            bool valid = false;
+            double t = 0.0;
+            if (mine) {
+                const float self = S[(size_t)x * G + c];
+                float lo = 1.f;
+                double sum = 0.0;
+                for (int q = 0; q < nm; ++q) {
+                    const float v = P[(size_t)(uint32_t)(uni(mrow[q]) + (int)x) * G + c];
+                    lo = fminf(lo, v);
+                    sum += (double)v;
+                }
+                valid = ((vbits >> f) & 1u) && lo > 0.f && sum == sum; // (NaN entry: not > 0, see walk())
+                t = (tot[f * G + c] + (double)self) + sum;
+            }
+            if (__ballot(valid) == 0ull) {
+                wave_sync();
+                if (lane == 0) frame[f] = (st & ~0xff) | nb;
+                wave_sync();
+                continue;
+            }
+            any = 1;
+            if (nm + 1 >= 5) { // a child whose existence settles every skip decision above it: may be dropped on its bound
+                const double r = mine ? R[(size_t)(f + 1) * G + c] : 0.0;
+                if (__ballot(valid && (t + r) * slack >= best) == 0ull) {
+                    mx = max(mx, 1); // (it returns >= 1 match: all the frames above need to know, see the note at the top)
+                    wave_sync();
+                    if (lane == 0) frame[f] = nb | (mx << 8) | (any << 16) | (matched << 17) | (nm << 24);
+                    wave_sync();
+                    continue;
+                }
+            }
+            wave_sync();
+            if (lane == 0) {
+                frame[f] = nb | (mx << 8) | (any << 16) | (matched << 17) | (nm << 24);
+                frame[f + 1] = (1 << 17) | ((nm + 1) << 24);
+                path[f] = (uint8_t)b;
+                const int k1 = (int)H->ksum[f + 1];
+                mrow[nm] = (int)H->rowbase[f] + b * ((int)ksumtot - k1) - k1; // entry((f, b) -> x) = rowbase[f] + b nd_f + (x - ksum[f + 1])
+            }
+            if (mine) tot[(f + 1) * G + c] = t;
+            vbits = (vbits & ~(1u << (f + 1))) | ((valid ? 1u : 0u) << (f + 1));
+            wave_sync();
+            ++f;
+            continue;
+        }
+        if (nb == kf) { // the candidates are done: the skip child (tree.py:98-101)
+            wave_sync();
+            if (lane == 0) frame[f] = (st & ~0xff) | (kf + 1);
+            wave_sync();
+            if (any && nm + mx >= 5) continue;
+            const bool valid = mine && ((vbits >> f) & 1u);
+            const double t = mine ? tot[f * G + c] : 0.0;
+            if (nm >= 5) {
+                const double r = mine ? R[(size_t)(f + 1) * G + c] : 0.0;
+                if (__ballot(valid && (t + r) * slack >= best) == 0ull) continue;
+            }
+            if (lane == 0) {
+                frame[f + 1] = nm << 24;
+                path[f] = kNoMatch;
+            }
+            if (mine) tot[(f + 1) * G + c] = t;
+            vbits = (vbits & ~(1u << (f + 1))) | ((valid ? 1u : 0u) << (f + 1));
+            wave_sync();
+            ++f;
+            continue;
+        }
+        // the frame is done: it returns its own match and the most its children returned (tree.py:102)
+        if (f == 0) break;
+        const int ret = matched + mx;
+        --f;
+        const int sp = uni(frame[f]);
+        const int mxp = max((sp >> 8) & 255, ret);
+        wave_sync();
+        if (lane == 0) frame[f] = (sp & ~0xff00) | (mxp << 8);
+        wave_sync();
+    }
+
+    // ---- the row: levels, maxima, keys as model clusters, best conformer
+    const Record r = parse_record(p.lib.data + p.lib.offsets[lig]);
+    {
+        unsigned long long cb0 = 0, cb1 = 0;
+        if (lane < r.ncl) {
+            const int cs = lane ? r.cluster_end[lane - 1] : 0, ce = r.cluster_end[lane];
+            unsigned lm = 0;
+            for (int u = cs; u < ce; ++u) lm |= r.typemask[u];
+            cb0 = p.M.tclus[2u * (lm & 127u)];
+            cb1 = p.M.tclus[2u * (lm & 127u) + 1u];
+        }
+        const bool has = (cb0 | cb1) != 0ull;
+        const unsigned long long bal = __ballot(has);
+        const int lev = __popcll(bal & ((1ull << lane) - 1ull));
+        if (has && lev < nl) { // (scan_ligand's levels: clusters with a candidate, in priority order, at most PMX_MAX_LEVELS)
+            a.levels[(size_t)li * PMX_MAX_LEVELS + lev] = (uint8_t)lane;
+            cbl[2 * lev] = cb0;
+            cbl[2 * lev + 1] = cb1;
+        }
+    }
+    wave_sync();
+    const bool live = mine && c < C;
+    a.conf_max[(size_t)li * PMX_MAX_CONFORMERS + lane] = live ? best : 0.0;
+    if (live) {
+        uint8_t *out = a.match + ((size_t)li * PMX_MAX_CONFORMERS + c) * PMX_MAX_LEVELS;
+        for (int l = 0; l < nl; ++l) {
+            const int b = key[c * PMX_MAX_LEVELS + l];
+            uint8_t m = kNoMatch;
+            if (b != kNoMatch) {
+                const unsigned long long w0 = cbl[2 * l], w1 = cbl[2 * l + 1];
+                const int n0 = __popcll(w0);
+                unsigned long long xw = b < n0 ? w0 : w1;
+                for (int j = b < n0 ? b : b - n0; j > 0; --j) xw &= xw - 1ull;
+                m = (uint8_t)((b < n0 ? 0 : 64) + __ffsll(xw) - 1);
+            }
+            out[l] = m;
+        }
+    }
+    // smallest conformer with the largest maximum
+    double m = live ? best : -1.0;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double o = __shfl_xor(m, d);
+        m = o > m ? o : m;
+    }
+    const unsigned long long at = __ballot(live && best == m);
+    if (lane == 0) a.best[li] = at ? __ffsll(at) - 1 : 0;
+    wave_sync();
+}
+
+// Persistent wavefronts over the call's list (mode 0) or over the ligands an earlier pass handed on (modes 1 - 3): the tables
+// as the product builds them (prepare_ligand, which also writes the status), then the explain walk.
+template <int G, bool TAILS>
+__global__ __launch_bounds__(64) void explain_kernel(const ScreenParams p, const pmx_xpl::Args a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int lane0 = lane_id();
+    const uint32_t wave_id = blockIdx.x;
+    const WaveShape<G> ws = wave_shape<G>(p.M.K, (int)p.max_nodes);
+    const ExplainLds<G> E = explain_lds<G>(ws);
+    const uint32_t todo = p.mode == 0 ? a.n
+                                      : min(p.mode == 1 ? p.ctl->ovf_count : (p.mode == 2 ? p.ctl->carry_count : p.ctl->retry_count[p.retry_slot ^ 1u]), p.list_cap);
+    const uint32_t *list = p.mode == 1 ? p.ovf_list : (p.mode == 2 ? p.carry_list : p.retry_in);
+    WaveStats *stat = reinterpret_cast<WaveStats *>(lds + ws.off_stat);
+    if (lane0 < (int)(sizeof(WaveStats) / 8)) reinterpret_cast<unsigned long long *>(stat)[lane0] = 0ull;
+    wave_sync();
+    for (;;) {
+        const int lane = lane_id();
+        uint32_t next = 0;
+        if (lane == 0) next = atomicAdd(&p.ctl->cursor[p.mode], 1u);
+        next = (uint32_t)uni((int)next);
+        if (next >= todo) break;
+        const uint32_t li = p.mode == 0 ? next : (uint32_t)uni((int)list[next]);
+        const uint64_t lig = uni64(a.ligands[li]);
+        if (lig >= p.lib.n) { // (not a ligand of the library: reported unsupported, nothing is read)
+            if (lane == 0) a.status[li] = PMX_LIGAND_UNSUPPORTED;
+            continue;
+        }
+        // row li of the call is library ligand `lig`: prepare_ligand reads record first + li and writes status[li] and scores[li]
+        // (a NaN or the 0 of a ligand without levels: written into the row's first maximum, which it is)
+        ScreenParams q = p;
+        q.first = lig - (uint64_t)li;
+        q.status = a.status;
+        q.scores = reinterpret_cast<float *>(a.conf_max + (size_t)li * (PMX_MAX_CONFORMERS - 1));
+        q.flags = PMX_SCORES_F64;
+        unsigned char *rec = prepare_ligand<G, false, TAILS>(q, lds, ws, li, wave_id, stat);
+        if (!rec) continue;
+        explain_walk<G>(q, lds, E, rec, lig, li, a);
+    }
+}
+
+__global__ void explain_init_kernel(const pmx_xpl::Args a) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n = a.n;
+    if (i < n * PMX_MAX_CONFORMERS) a.conf_max[i] = 0.0;
+    if (i < n * PMX_MAX_LEVELS) a.levels[i] = kNoLevel;
+    if (i < n) a.best[i] = 0;
+    for (size_t j = i; j < n * PMX_MAX_CONFORMERS * PMX_MAX_LEVELS; j += (size_t)gridDim.x * blockDim.x) a.match[j] = kNoMatch;
+}
+
+__global__ void explain_fixup_kernel(const pmx_xpl::Args a) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)a.n * PMX_MAX_CONFORMERS) return;
+    const size_t li = i / PMX_MAX_CONFORMERS;
+    if (a.status[li] == PMX_LIGAND_OK) return;
+    a.conf_max[i] = __builtin_nan("");
+    if (i % PMX_MAX_CONFORMERS == 0) a.best[li] = -1;
+}
+
+} // namespace pmx_x
+
+namespace pmx_xpl {
+
+template <int G>
+static size_t lds_g(int K, int max_nodes) {
+    return pmx_x::explain_lds<G>(pmx_x::wave_shape<G>(K, max_nodes)).bytes;
+}
+size_t lds_bytes(int G, int K, int max_nodes) {
+    switch (G) {
+    case 1: return lds_g<1>(K, max_nodes);
+    case 2: return lds_g<2>(K, max_nodes);
+    case 4: return lds_g<4>(K, max_nodes);
+    case 8: return lds_g<8>(K, max_nodes);
+    case 16: return lds_g<16>(K, max_nodes);
+    case 32: return lds_g<32>(K, max_nodes);
+    default: return lds_g<64>(K, max_nodes);
+    }
+}
+
+template <int G>
+static void launch_g(bool tails, unsigned blocks, unsigned lds, hipStream_t stream, const pmx_x::ScreenParams &p, const Args &a) {
+    if (tails) pmx_x::explain_kernel<G, true><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+    else pmx_x::explain_kernel<G, false><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+}
+
+bool launch(int G, bool tails, int mode, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes, const Args &a) {
+    if (bytes != sizeof(pmx_x::ScreenParams)) return false;
+    pmx_x::ScreenParams p;
+    std::memcpy(&p, params, sizeof p);
+    p.mode = mode;
+    switch (G) {
+    case 1: launch_g<1>(tails, blocks, lds, stream, p, a); break;
+    case 2: launch_g<2>(tails, blocks, lds, stream, p, a); break;
+    case 4: launch_g<4>(tails, blocks, lds, stream, p, a); break;
+    case 8: launch_g<8>(tails, blocks, lds, stream, p, a); break;
+    case 16: launch_g<16>(tails, blocks, lds, stream, p, a); break;
+    case 32: launch_g<32>(tails, blocks, lds, stream, p, a); break;
+    case 64: launch_g<64>(tails, blocks, lds, stream, p, a); break;
+    default: return false;
+    }
+    return true;
+}
+
+void launch_init(const Args &a, hipStream_t stream) {
+    const size_t n = (size_t)a.n * PMX_MAX_CONFORMERS;
+    const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 65535);
+    pmx_x::explain_init_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(a);
+}
+
+void launch_fixup(const Args &a, hipStream_t stream) {
+    const size_t n = (size_t)a.n * PMX_MAX_CONFORMERS;
+    pmx_x::explain_fixup_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(a);
+}
+
+} // namespace pmx_xpl

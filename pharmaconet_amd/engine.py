@@ -15,7 +15,7 @@ from . import _ffi
 from .constants import weights_vector
 from .library import PackedLibrary, as_packed_library
 
-__all__ = ["DeviceLibrary", "ScreeningResult", "score_one", "screen", "topk", "device_model", "last_score_stats"]
+__all__ = ["DeviceLibrary", "Explanation", "ScreeningResult", "explain", "score_one", "screen", "topk", "device_model", "last_score_stats"]
 
 
 def _torch():
@@ -86,6 +86,7 @@ class DeviceLibrary:
         self.device = _device_index(device)
         offsets = np.ascontiguousarray(library.offsets, dtype=np.uint64)
         data = np.ascontiguousarray(library.data, dtype=np.uint8)
+        self._n_conf = library.headers()[:, 1].copy() if len(library) else np.zeros(0, np.uint16)  # (what `explain` cuts its rows to)
         view = _ffi.LibraryView(len(library), offsets.ctypes.data, data.ctypes.data if data.size else None, 0)
         handle = ctypes.c_void_p()
         _ffi.check(lib.pmx_library_upload(ctypes.byref(view), self.device, ctypes.byref(handle)))
@@ -220,6 +221,10 @@ class ScreeningResult:
     first: int
     topk_scores: "object | None" = None  # torch.float32 [k]
     topk_indices: "object | None" = None  # torch.int64 [k], global ligand indices (first + position)
+    model: "object | None" = None  # what `screen` scored (for `explain`): the model, the library when it was a DeviceLibrary or a PackedLibrary
+    library: "object | None" = None
+    weights: "dict | None" = None
+    index_base: int = 0  # added to library indices in topk_indices
 
     def scores_numpy(self) -> np.ndarray:
         return self.scores.cpu().numpy()
@@ -230,6 +235,24 @@ class ScreeningResult:
         idx = self.topk_indices.cpu().numpy()
         sc = self.topk_scores.cpu().numpy()
         return [(int(i), float(s)) for i, s in zip(idx, sc) if i >= 0]
+
+    def explain(self, k: int, model=None, library=None, weights: dict[str, float] | None = None) -> "Explanation":
+        """`explain` of this screen's k best ligands (best first), without scoring the library again. `model`, `library` and `weights`
+        default to what `screen` was called with."""
+        model = model if model is not None else self.model
+        library = library if library is not None else self.library
+        weights = self.weights if weights is None else weights
+        if model is None or library is None:
+            raise ValueError("this result does not know its library (it was not given as a DeviceLibrary or a PackedLibrary): pass it")
+        if self.topk_indices is not None and int(self.topk_indices.numel()) >= k:
+            top = self.topk_indices.cpu().numpy()[:k]
+            idx = top[top >= 0] - self.index_base  # (global indices of a sharded screen -> library indices)
+        else:
+            sc = self.scores.cpu().numpy().astype(np.float64)
+            key = np.where(self.status.cpu().numpy() != 0, -np.inf, np.nan_to_num(sc, nan=-np.inf))
+            idx = np.lexsort((np.arange(len(sc)), -key))[:k] + self.first
+        idx = np.asarray([i for i in idx if i >= 0], dtype=np.uint64)
+        return explain(model, library, idx, weights=weights)
 
 
 def _weights_array(weights):
@@ -280,6 +303,7 @@ def screen(
     torch = _torch()
     lib = _ffi.load()
     owned = None
+    given = library
     if not isinstance(library, DeviceLibrary):
         owned = library = DeviceLibrary(as_packed_library(library), device)
     dev = library.device
@@ -299,7 +323,8 @@ def screen(
                 scores.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream),
             )
         )
-        result = ScreeningResult(scores=scores, status=status, first=first)
+        result = ScreeningResult(scores=scores, status=status, first=first, model=model, library=given if isinstance(given, (DeviceLibrary, PackedLibrary)) else None,
+                                  weights=weights, index_base=index_base)
         if topk is not None:
             result.topk_scores, result.topk_indices = globals()["topk"](scores, int(topk), base_index=index_base + first)
     finally:
@@ -323,6 +348,140 @@ def score_one(model, ligand, weights: dict[str, float] | None = None, device=Non
             f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h"
         )
     return float(result.scores.cpu()[0])
+
+
+NO_MATCH = 0xFF  # include/pmx.h pmx_explain: a level matched to None
+NO_LEVEL = 0xFE
+
+
+@dataclass
+class Explanation:
+    """What `explain` returns: one row per listed ligand, cut to that ligand's conformers C and tree levels nl.
+
+    conf_max[i]        float64 [C]: per conformer the maximum over the tree's leaves (`scores` inside `_run_average`; its mean is the
+                       ligand's score); NaN for a ligand with a non-zero status
+    best_conformer[i]  the smallest conformer with the largest maximum (-1 with a non-zero status)
+    levels[i]          int [nl]: the ligand cluster (index in the record's priority-ordered cluster list) behind each tree level
+    match[i]           int [C, nl]: per conformer the key of the first leaf (in `root_tree.iteration()` order) that reaches its
+                       maximum - the model cluster (index in `model.node_clusters`) each level is matched to, -1 for None; all -1 where the
+                       maximum is 0 (no leaf explains it)
+    status[i]          PMX_LIGAND_* as `screen` reports it"""
+
+    indices: np.ndarray
+    conf_max: list
+    best_conformer: np.ndarray
+    levels: list
+    match: list
+    status: np.ndarray
+
+    def __len__(self) -> int:
+        return len(self.indices)
+
+    @property
+    def max(self) -> np.ndarray:
+        """Per ligand the largest conformer maximum (`GraphMatcher._run_max`, graph_match.py:111-112)."""
+        return np.array([float(m.max()) if m.size else 0.0 for m in self.conf_max])
+
+    def pairs(self, i: int, model, library, conformer: int | None = None) -> list[dict]:
+        """Row i as readable pairs for one conformer (default: the best one): per tree level the ligand cluster (index, types, node count,
+        centre in that conformer) and the model cluster it is matched to (index, type, centre), or None. (A packed record holds typed
+        nodes, not atoms: the atom indices of a ligand cluster are those of its nodes in the `LigandGraph` the record was packed from.)"""
+        from .constants import TYPE_NAMES
+
+        packed = library if isinstance(library, PackedLibrary) else as_packed_library(library)
+        c = int(self.best_conformer[i]) if conformer is None else int(conformer)
+        if c < 0 or self.status[i] != 0:
+            return []
+        rec = packed.unpack(int(self.indices[i]))
+        ends = rec["cluster_end"]
+        flat = model.flat
+        out = []
+        for lev, lc in enumerate(self.levels[i]):
+            lc = int(lc)
+            s0 = int(ends[lc - 1]) if lc > 0 else 0
+            s1 = int(ends[lc])
+            tm = int(np.bitwise_or.reduce(rec["typemask"][s0:s1])) if s1 > s0 else 0
+            centre = rec["xyz"][s0:s1, :, c].astype(np.float64).mean(axis=0) if s1 > s0 else np.zeros(3)
+            m = int(self.match[i][c, lev])
+            out.append(dict(
+                level=lev,
+                ligand_cluster=lc,
+                ligand_types=[TYPE_NAMES[t] for t in range(len(TYPE_NAMES)) if tm >> t & 1],
+                ligand_nodes=s1 - s0,
+                ligand_center=tuple(float(x) for x in centre),
+                model_cluster=None if m < 0 else m,
+                model_type=None if m < 0 else flat.cluster_type[m],
+                model_center=None if m < 0 else tuple(float(x) for x in flat.cluster_center[m]),
+            ))
+        return out
+
+
+def _conformer_counts(library: "DeviceLibrary", idx: np.ndarray) -> np.ndarray:
+    """Conformer counts of library ligands `idx` (0 outside the library): kept per ligand when the library was uploaded from the host, read
+    from the adopted device records otherwise."""
+    ok = idx < len(library)
+    j = np.where(ok, idx, 0)
+    if getattr(library, "_n_conf", None) is not None:
+        return np.where(ok, library._n_conf[j].astype(np.int64) if len(library._n_conf) else 0, 0)
+    src = getattr(library, "_adopted", None)
+    if src is None:
+        raise ValueError("explain needs the conformer counts of this DeviceLibrary: make it from a PackedLibrary or adopt the device buffers")
+    torch = _torch()
+    offsets, data = src
+    starts = offsets.view(torch.int64)[torch.from_numpy(j).to(offsets.device)]
+    c = data[starts + 2].to(torch.int64) | (data[starts + 3].to(torch.int64) << 8)
+    return np.where(ok, c.cpu().numpy(), 0)
+
+
+def explain(model, library, indices, weights: dict[str, float] | None = None, device=None) -> Explanation:
+    """Per-conformer maxima and the leaf that reaches each (`pmx_explain`, csrc/pmx_explain.hip) for the library ligands `indices`
+    (any order, repeats allowed, at most 65536). `library` is a `DeviceLibrary` or anything `as_packed_library` accepts. Runs on torch's
+    current stream of the device and waits for it."""
+    torch = _torch()
+    lib = _ffi.load()
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+    if (idx < 0).any():
+        raise ValueError("negative ligand index")
+    n = len(idx)
+    if n > 65536:
+        raise ValueError("at most 65536 ligands per explain call (PMX_EXPLAIN_MAX)")
+    owned = None
+    if not isinstance(library, DeviceLibrary):
+        owned = library = DeviceLibrary(as_packed_library(library), device)
+    dev = library.device
+    mh = device_model(model, dev)
+    tdev = torch.device("cuda", dev)
+    L, CM = 20, 64  # PMX_MAX_LEVELS, PMX_MAX_CONFORMERS
+    m = max(n, 1)
+    lig = torch.from_numpy(idx).to(tdev)
+    conf_max = torch.empty((m, CM), dtype=torch.float64, device=tdev)
+    match = torch.empty((m, CM, L), dtype=torch.uint8, device=tdev)
+    levels = torch.empty((m, L), dtype=torch.uint8, device=tdev)
+    best = torch.empty(m, dtype=torch.int32, device=tdev)
+    status = torch.empty(m, dtype=torch.int32, device=tdev)
+    try:
+        with torch.cuda.device(tdev):
+            stream = torch.cuda.current_stream(tdev)
+            _ffi.check(lib.pmx_explain(mh.handle, library.handle, _weights_array(weights), lig.data_ptr(), n, conf_max.data_ptr(),
+                                       match.data_ptr(), levels.data_ptr(), best.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+            stream.synchronize()
+    finally:
+        if owned is not None:
+            torch.cuda.synchronize(tdev)
+            owned.close()
+    cm, mt, lv = conf_max.cpu().numpy()[:n], match.cpu().numpy()[:n], levels.cpu().numpy()[:n]
+    st, bc = status.cpu().numpy()[:n].astype(np.int32), best.cpu().numpy()[:n].astype(np.int64)
+    conf = _conformer_counts(library, idx)
+    out_cm, out_lv, out_mt = [], [], []
+    for i in range(n):
+        nl = int(np.count_nonzero(lv[i] != NO_LEVEL))
+        C = int(conf[i]) if st[i] == 0 else 0
+        out_cm.append(cm[i, :C].copy() if st[i] == 0 else np.full(1, np.nan))
+        out_lv.append(lv[i, :nl].astype(np.int64))
+        key = mt[i, :C, :nl].astype(np.int64)
+        key[key == NO_MATCH] = -1
+        out_mt.append(key)
+    return Explanation(indices=idx.astype(np.int64), conf_max=out_cm, best_conformer=bc, levels=out_lv, match=out_mt, status=st)
 
 
 def last_score_stats() -> dict:

@@ -333,6 +333,33 @@ class PharmacophoreModel:
 
         return score_one(self, ligand, weights)
 
+    def scoring_detail(self, ligand, weights: dict[str, float] | None = None) -> dict:
+        """`_scoring` with what the score is made of: `score` (the mean of `conf_max`, graph_match.py:109), `max` (`GraphMatcher._run_max`,
+        graph_match.py:111-112), `conf_max` (the per-conformer maxima whose mean is the score), `best_conformer`, `levels` and `match`
+        (the key of the leaf that reaches each conformer's maximum), `pairs` (the best conformer's match, readable). Takes what
+        `_scoring` takes."""
+        from .engine import explain
+        from .library import as_packed_library
+
+        packed = as_packed_library(ligand)
+        if len(packed) != 1:
+            raise ValueError("scoring_detail takes exactly one ligand")
+        ex = explain(self, packed, [0], weights=weights)
+        if int(ex.status[0]) != 0:
+            n, c, _ = packed.header(0)
+            raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+        cm = ex.conf_max[0]
+        n, c, ncl = packed.header(0)
+        score = 0 if (ncl == 0 and n == 0 and c > 0) else float(np.mean(cm))  # (graph_match.py:95-96 returns the int 0)
+        return dict(score=score, max=float(cm.max()) if cm.size else 0.0, conf_max=cm, best_conformer=int(ex.best_conformer[0]),
+                    levels=ex.levels[0], match=ex.match[0], pairs=ex.pairs(0, self, packed))
+
+    def explain(self, library, indices, weights: dict[str, float] | None = None, **kwargs):
+        """Per-conformer maxima and explaining matches of library ligands `indices` (`engine.explain`)."""
+        from .engine import explain
+
+        return explain(self, library, indices, weights=weights, **kwargs)
+
     def screen(self, library, weights: dict[str, float] | None = None, topk: int | None = None, **kwargs):
         """Batched `screening.py:46-75`: score every ligand of a packed library on the GPU.
 

@@ -29,6 +29,8 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("-d", "--library_dir", type=str, required=True, help="molecular library directory, or a packed .pmxlib file")
         cfg.add_argument("-o", "--out", type=str, required=True, help="result file path")
         cfg.add_argument("--cpus", type=int, default=1, help="host processes for reading / packing molecule files")
+        cfg.add_argument("--explain", type=int, default=0, metavar="K", help="also explain the K best hits (best conformer and its cluster matches)")
+        cfg.add_argument("--explain_out", type=str, default=None, help="CSV of the explained hits (default: <out>.explain.csv)")
         par = self.add_argument_group("parameter")
         par.add_argument("--hydrophobic", type=float, default=1.0, help="weight for hydrophobic carbon")
         par.add_argument("--aromatic", type=float, default=4.0, help="weight for aromatic ring")
@@ -121,7 +123,29 @@ def main(argv=None) -> None:
     )
     names, lib = load_library(Path(args.library_dir), args.cpus, on_device=True)
     result = model.screen(lib, weights=weight, float64=True)  # (the reference writes the float64 `GraphMatcher.run()` returns)
-    write_csv(Path(args.out), names, result.scores.cpu().numpy(), result.status.cpu().numpy())
+    scores, status = result.scores.cpu().numpy(), result.status.cpu().numpy()
+    write_csv(Path(args.out), names, scores, status)
+    if args.explain > 0:
+        out = Path(args.explain_out) if args.explain_out else Path(str(args.out) + ".explain.csv")
+        write_explain_csv(out, names, scores, status, model, lib, weight, args.explain)
+
+
+def write_explain_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int) -> None:
+    """The k best hits of a screen, in the order of the main CSV, with the best conformer, its maximum and its matched pairs
+    `ligand cluster -> model cluster:type` (ligand clusters as indices of the record's priority-ordered cluster list, model clusters as
+    indices of `model.node_clusters`; levels matched to None are left out): `engine.explain` on those k ligands only."""
+    from .engine import explain
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    ex = explain(model, lib, order, weights=weights)
+    types = model.flat.cluster_type
+    with open(out, "w") as w:
+        w.write("rank,path,score,best_conformer,conformer_max,matches\n")
+        for r, i in enumerate(order):
+            c = int(ex.best_conformer[r])
+            pairs = [f"{lc}->{int(m)}:{types[int(m)]}" for lc, m in zip(ex.levels[r], ex.match[r][c]) if m >= 0] if c >= 0 else []
+            w.write(f"{r + 1},{names[i]},{float(scores[i])},{c},{float(ex.conf_max[r][c])},{' '.join(pairs)}\n")
 
 
 if __name__ == "__main__":
