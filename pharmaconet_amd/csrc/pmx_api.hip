@@ -610,6 +610,9 @@ struct ScreenWs {
     bool ctl_used[2] = {false, false};
     hipStream_t last_stream = nullptr;
     std::mutex mu; // held while a call enqueues (the workspace belongs to one call at a time, in stream order)
+    Ctl *xctl = nullptr;   // pmx_explain's control block (its own: the statistics of the last pmx_score stay what that call left)
+    uint64_t stamp = 0;    // last use (ensure_screen): the least recently used workspace of a device goes first
+    bool released = false; // pmx_release_workspaces (or the cap on workspaces per device) took the buffers: a caller that was waiting on `mu` asks for a new workspace
     void free_buffers() {
         for (ChunkSet &c : set) {
             for (void *q : {(void *)c.ctl, (void *)c.arena, (void *)c.queue, (void *)c.lists})
@@ -632,9 +635,6 @@ struct ScreenWs {
         ev_valid = false;
         ctl_used[0] = ctl_used[1] = false;
     }
-    Ctl *xctl = nullptr;   // pmx_explain's control block (its own: the statistics of the last pmx_score stay what that call left)
-    uint64_t stamp = 0;    // last use (ensure_screen): the least recently used workspace of a device goes first
-    bool released = false; // pmx_release_workspaces (or the cap on workspaces per device) took the buffers: a caller that was waiting on `mu` asks for a new workspace
 };
 // Workspaces are shared: the map, a call in progress and the thread that asks for the last call's statistics each hold a
 // reference, so pmx_release_workspaces can take a workspace out of the map and free its buffers while none of them is left
@@ -713,16 +713,58 @@ static int grow(T **ptr, size_t *have, size_t want, hipStream_t stream, hipStrea
     return PMX_OK;
 }
 
-// What one pocket of a call needs: kernel parameters, launch shapes, chunk size.
-struct PocketPlan {
-    ScreenParams p;
-    size_t lds = 0;
-    uint32_t waves_per_cu = 0, task_waves_per_cu = 0;
-    uint32_t slice_bytes = 0, big_bytes = 0, big_grid = 0;
-    uint64_t worst_bytes = 0;
-    uint32_t super = 0;
-    uint32_t pa_bytes = 0; // path_bound()'s buffer per wavefront
+// The per-wavefront buffers of a workspace, in bytes (a call grows them to the largest need of its pockets).
+struct BufferNeeds {
+    size_t slices = 0, big = 0, totbuf = 0, pabuf = 0;
+    void cover(const BufferNeeds &o) { slices = std::max(slices, o.slices), big = std::max(big, o.big), totbuf = std::max(totbuf, o.totbuf), pabuf = std::max(pabuf, o.pabuf); }
 };
+
+static int grow_buffers(ScreenWs &ws, const BufferNeeds &need, hipStream_t stream) {
+    int rc = grow(&ws.slices, &ws.slices_bytes, need.slices, stream, ws.side);
+    if (!rc) rc = grow(&ws.big, &ws.big_bytes, need.big, stream, ws.side);
+    if (!rc) rc = grow(&ws.totbuf, &ws.totbuf_bytes, need.totbuf, stream, ws.side);
+    if (!rc) rc = grow(&ws.pabuf, &ws.pabuf_bytes, need.pabuf, stream, ws.side);
+    return rc;
+}
+
+// The table arena of a chunk set. (PMX_ARENA_MB is per set; a smaller arena than asked for is slower - more trees walked by one
+// wavefront alone - never wrong, so it shrinks when memory is short: several streams each keep a workspace. A size that was
+// accepted after shrinking stands until the workspace is released: asking for the full size again on every call would
+// synchronise, free and fail again each time)
+// (32 / 64 conformer lanes: records of megabytes - 16 GB held the split trees of a 16 384-ligand chunk of the stress configuration
+// to within 3 %, and every tree past the end is walked by one wavefront alone)
+// ([MI355X] round 6: 64 GB at up to 16 lanes. SURVEY 8d-2's library puts 29 GB of split trees' tables into the arena per 1 M-ligand chunk at the old
+// budget, 17 GB at the new one; with a 16 GB arena 200 000 trees found it full and were walked by one wavefront each - the longest for 1.2 M
+// passes, the pass 3.4 s instead of 0.54 s. The part has 288 GB.)
+template <int G>
+static int ensure_arena(ChunkSet &c, hipStream_t stream, hipStream_t side) {
+    size_t arena_want = (size_t)std::max<long>(1, env_long("PMX_ARENA_MB", G >= 32 ? 32768 : 65536)) << 20;
+    if (!c.arena && !std::getenv("PMX_ARENA_MB")) { // first allocation, no explicit size: at most a third of what the device has free
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b / 3 < arena_want) {
+            arena_want = std::max<size_t>((size_t)1 << 30, (free_b / 3) & ~(((size_t)1 << 20) - 1));
+            c.arena_shrunk_to = arena_want;
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    const size_t arena_min = std::min<size_t>((size_t)1 << 30, arena_want);
+    if (c.arena_shrunk_to) arena_want = std::min(arena_want, std::max(c.arena_shrunk_to, arena_min));
+    const size_t asked = arena_want;
+    const int rc = grow(&c.arena, &c.arena_bytes, arena_want, stream, side, arena_min);
+    if (rc) return rc;
+    if (c.arena_bytes < asked) c.arena_shrunk_to = c.arena_bytes;
+    return PMX_OK;
+}
+
+// Arena pass t + 2 (mode 3) over the ligands the arena pass before had no room for: it reads the list that pass wrote and lists
+// what it has no room for in the other half of `lists` - the last one lists nothing, it reports them.
+static void prepare_retry(ScreenParams &p, Ctl *ctl, uint32_t *lists, uint32_t cap, int t, int retries, hipStream_t stream) {
+    retry_prep_kernel<<<dim3(1), dim3(64), 0, stream>>>(ctl, (uint32_t)(t + 1) & 1u);
+    p.retry_in = (t & 1) == 0 ? lists : lists + cap;
+    p.retry_out = t + 1 == retries ? nullptr : ((t & 1) == 0 ? lists + cap : lists);
+    p.retry_slot = (uint32_t)(t + 1) & 1u;
+}
 
 // Events, side stream and control blocks of a workspace, on its first call (num_cu is set last: a workspace whose events, stream or
 // control blocks could not be made stays uninitialised).
@@ -767,6 +809,75 @@ static bool pair_tails(const pmx_model *const *models, int n_models, const Weigh
     return tails;
 }
 
+// What one pocket of a call needs: kernel parameters, launch shapes, buffers and chunk size. pmx_score and pmx_explain both plan
+// here: the same workspace serves both, and explain promises the score pass's slices, large slices, arena passes and statuses.
+// `p` holds what the model and the library decide; what one call decides (flags, range, budget, outputs, lists, control block)
+// its caller sets.
+struct PocketPlan {
+    ScreenParams p;
+    size_t lds = 0;
+    uint32_t waves_per_cu = 0, task_waves_per_cu = 0;
+    uint32_t slice_bytes = 0, big_bytes = 0, big_grid = 0;
+    uint32_t super = 0;
+    int arena_retries = 0; // arena passes after the first (0: no table of this model and library can exceed a large slice)
+    BufferNeeds need;
+};
+
+template <int G>
+static int plan_pocket(const pmx_model *model, const pmx_library *lib, const Weights &W, int num_cu, hipStream_t stream, PocketPlan &pl) {
+    pl = PocketPlan{};
+    ScreenParams &p = pl.p;
+    p.M = model->dm;
+    const int rc = pair_functions(const_cast<pmx_model *>(model), W, stream, &p.F);
+    if (rc) return rc;
+    p.lib = lib->dl;
+    p.sidtab = model->sidtab;
+    p.sub_off = model->sub_off;
+    p.sub_nodes = model->sub_nodes;
+    p.W = W;
+    p.max_nodes = (uint32_t)std::max(4, std::min(lib->info.max_nodes, PMX_MAX_LIGAND_NODES));
+    p.bound_cost = (uint32_t)std::max<long>(0, env_long("PMX_BOUND_COST", 8192));
+    p.dead_min_entries = (uint32_t)std::max<long>(1, env_long("PMX_DEAD_MIN_ENTRIES", 32));
+    const WaveShape<G> shape = wave_shape<G>(model->dm.K, (int)p.max_nodes);
+    pl.lds = shape.bytes;
+    pl.waves_per_cu = (uint32_t)std::max<long>(2, std::min<long>({(long)(kLdsPerCu / shape.bytes), 4L * PMX_SCREEN_WAVES, env_long("PMX_WAVES_PER_CU", 32)}));
+    // the task kernel is the walker alone: it may be built for more waves per SIMD than the ligand kernel (PMX_TASK_WAVES)
+    pl.task_waves_per_cu = (uint32_t)std::max<long>(2, std::min<long>({(long)(kLdsPerCu / shape.bytes), 4L * PMX_TASK_WAVES, env_long("PMX_TASK_WAVES_PER_CU", 32)}));
+    const uint32_t grid = (uint32_t)num_cu * std::max(pl.waves_per_cu, pl.task_waves_per_cu); // (sizes the per-wavefront buffers of both kernels)
+    // per-wavefront slice: 112 KB at 8 conformer lanes (every ligand of the bench library fits, path_bound()'s table included), scaled with the lanes
+    // (table bytes grow with the square of the model's cluster count: the 11-cluster 6OIM-like model is the reference point)
+    const long k_scale = std::max(1L, std::min(16L, ((long)model->dm.K * model->dm.K + 60) / 121));
+    pl.slice_bytes = (uint32_t)std::max<long>(4, env_long("PMX_SLICE_KB", (cand_bounds<G>() ? 112L : 80L) * std::max(1, G / 8) * k_scale)) * 1024u;
+    pl.need.slices = (size_t)grid * pl.slice_bytes;
+    // large slices for the ligands whose tables exceed a slice: as large as a table of this model and library can get, at most
+    // PMX_BIG_SLICE_MB each, PMX_BIG_TOTAL_MB together (what is larger still goes to the arena)
+    const uint64_t nlmax = (uint64_t)std::min<int>(PMX_MAX_LEVELS, std::max(1, lib->info.max_clusters));
+    const uint64_t K = (uint64_t)std::max(1, std::min(model->dm.K, PMX_MAX_LEVEL_CANDIDATES)); // (candidates per level)
+    const uint64_t worst = rec_bytes<G>((uint32_t)(nlmax * K), (uint32_t)(nlmax * (nlmax - 1) / 2 * K * K), (uint32_t)nlmax);
+    const uint64_t cap = (uint64_t)std::max<long>(1, env_long("PMX_BIG_SLICE_MB", G >= 32 ? 4 : 32)) << 20;
+    pl.big_bytes = (uint32_t)std::max<uint64_t>(pl.slice_bytes, (std::min(worst, cap) + 4095) & ~4095ull);
+    const uint64_t total = (uint64_t)std::max<long>(64, env_long("PMX_BIG_TOTAL_MB", G >= 32 ? 16384 : 4096)) << 20;
+    pl.big_grid = (uint32_t)std::max<uint64_t>(16, std::min<uint64_t>(grid, total / pl.big_bytes));
+    pl.need.big = (size_t)pl.big_grid * pl.big_bytes;
+    if (cand_bounds<G>()) { // float[matches <= levels][candidates of all levels][G], at most 1 MB per wavefront (larger jobs do without)
+        const uint64_t need = (nlmax + 1) * nlmax * K * G * 4;
+        p.pa_bytes = (uint32_t)std::min<uint64_t>((need + 255) & ~255ull, (uint64_t)std::max<long>(1, env_long("PMX_PATH_KB", 1024)) << 10);
+        pl.need.pabuf = (size_t)grid * p.pa_bytes * 2u; // ligand kernel | task kernel
+    }
+    // (the table phase stages node distances and chain lengths there at 32 / 64 lanes)
+    if (!totals_in_lds<G>()) pl.need.totbuf = (size_t)num_cu * 4u * std::max(PMX_SCREEN_WAVES, PMX_TASK_WAVES) * kTotBufBytes * 2u; // ligand kernel | task kernel
+    // arena passes over the ligands an arena pass had no room for, each with the arena to itself (a pass with an empty list exits at
+    // once): a ligand is reported PMX_LIGAND_TOO_LARGE when its tables exceed the whole arena - or when the arena-class ligands of a
+    // chunk need more than 1 + PMX_ARENA_RETRIES arenas
+    if (worst > pl.big_bytes) pl.arena_retries = (int)std::max<long>(1, env_long("PMX_ARENA_RETRIES", 4));
+    // chunk: what the arena has to hold at a time are the tables of the chunk's split trees. (Cutting a pocket's pass into more
+    // chunks than the arena asks for does not pay: every chunk ends in a dozen rounds with a tail each - 1 M ligands in 8
+    // chunks: 258 ms back to back, 234 ms with the rounds beside the next chunk's ligand kernel, 207 ms in one chunk.)
+    const long super_dflt = std::max(16384L, (1L << 20) * 8 / std::max(G, 8) / k_scale);
+    pl.super = (uint32_t)std::max<long>(1024, std::min<long>(env_long("PMX_SUPER", super_dflt), 1 << 24));
+    return PMX_OK;
+}
+
 template <int G>
 static int score_screen(const pmx_model *const *models, int n_models, const pmx_library *lib, const Weights &W, uint64_t first, uint64_t count,
                         void *scores_dev, bool scores_f64, int32_t *status_dev, hipStream_t stream, ScreenWs &ws) {
@@ -776,7 +887,6 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
         if (irc) return irc;
     }
     const uint32_t flags = (uint32_t)env_long("PMX_TREE_FLAGS", 0);
-    const uint32_t max_nodes = (uint32_t)std::max(4, std::min(lib->info.max_nodes, PMX_MAX_LIGAND_NODES));
     // [MI355X] round 6, passes a walk may take before it splits. On the bench library (92 passes per ligand, 7 % of the walks over 384) 384 / 384
     // and 768 / 384 are the same 99.1 ms; on SURVEY 8d-2's own library (800 passes per ligand) 384 sends 57-74 % of the ligands to the arena and
     // the queue (714 ms with a 64 GB arena, queue full), 768 a third of them (539 ms). A queued subtree keeps the smaller budget: the rounds' tail.
@@ -790,87 +900,29 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
     const bool debug_kernels = (flags & ~PMX_PRODUCT_FLAGS) != 0;
     bool debug_ok = true;
     const bool tails = pair_tails(models, n_models, W); // (term-by-term tails for widely spread type weights, see pair_tails)
-    // arena passes over the ligands an arena pass had no room for, each with the arena to itself (a pass with an empty list exits at
-    // once): a ligand is reported PMX_LIGAND_TOO_LARGE when its tables exceed the whole arena - or when the arena-class ligands of a
-    // chunk need more than 1 + PMX_ARENA_RETRIES arenas
-    const int arena_retries = (int)std::max<long>(1, env_long("PMX_ARENA_RETRIES", 4));
 
     // ---- per pocket: parameters and launch shapes
     std::vector<PocketPlan> plan((size_t)n_models);
-    size_t slices_need = 0, big_need = 0, totbuf_need = 0, pabuf_need = 0;
+    BufferNeeds need;
     uint32_t super_max = 0;
     bool retry_possible = false;
     for (int m = 0; m < n_models; ++m) {
-        const pmx_model *model = models[m];
         PocketPlan &pl = plan[(size_t)m];
-        ScreenParams &p = pl.p;
-        p = ScreenParams{};
-        p.M = model->dm;
-        int rc = pair_functions(const_cast<pmx_model *>(model), W, stream, &p.F);
+        const int rc = plan_pocket<G>(models[m], lib, W, ws.num_cu, stream, pl);
         if (rc) return rc;
-        p.lib = lib->dl;
-        p.sidtab = model->sidtab;
-        p.sub_off = model->sub_off;
-        p.sub_nodes = model->sub_nodes;
-        p.W = W;
+        ScreenParams &p = pl.p;
         p.first = first;
         p.flags = flags | (scores_f64 ? PMX_SCORES_F64 : 0u);
-        p.max_nodes = max_nodes;
         p.budget = lig_budget;
         p.min_levels = (uint32_t)std::max<long>(0, env_long("PMX_MIN_LEVELS", 3));
-        p.bound_cost = (uint32_t)std::max<long>(0, env_long("PMX_BOUND_COST", 8192));
-        p.dead_min_entries = (uint32_t)std::max<long>(1, env_long("PMX_DEAD_MIN_ENTRIES", 32));
         p.scores = scores_f64 ? reinterpret_cast<float *>(static_cast<double *>(scores_dev) + (size_t)m * count) : static_cast<float *>(scores_dev) + (size_t)m * count;
         p.status = m == 0 ? status_dev : nullptr;
-        const WaveShape<G> shape = wave_shape<G>(model->dm.K, (int)max_nodes);
-        pl.lds = shape.bytes;
-        pl.waves_per_cu = (uint32_t)std::max<long>(2, std::min<long>({(long)(kLdsPerCu / shape.bytes), 4L * PMX_SCREEN_WAVES, env_long("PMX_WAVES_PER_CU", 32)}));
-        // the task kernel is the walker alone: it may be built for more waves per SIMD than the ligand kernel (PMX_TASK_WAVES)
-        pl.task_waves_per_cu = (uint32_t)std::max<long>(2, std::min<long>({(long)(kLdsPerCu / shape.bytes), 4L * PMX_TASK_WAVES, env_long("PMX_TASK_WAVES_PER_CU", 32)}));
-        const uint32_t grid = (uint32_t)ws.num_cu * std::max(pl.waves_per_cu, pl.task_waves_per_cu); // (sizes the per-wavefront buffers of both kernels)
-        // per-wavefront slice: 112 KB at 8 conformer lanes (every ligand of the bench library fits, path_bound()'s table included), scaled with the lanes
-        // (table bytes grow with the square of the model's cluster count: the 11-cluster 6OIM-like model is the reference point)
-        const long k_scale = std::max(1L, std::min(16L, ((long)model->dm.K * model->dm.K + 60) / 121));
-        pl.slice_bytes = (uint32_t)std::max<long>(4, env_long("PMX_SLICE_KB", (cand_bounds<G>() ? 112L : 80L) * std::max(1, G / 8) * k_scale)) * 1024u;
-        slices_need = std::max(slices_need, (size_t)grid * pl.slice_bytes);
-        // large slices for the ligands whose tables exceed a slice: as large as a table of this model and library can get, at most
-        // PMX_BIG_SLICE_MB each, PMX_BIG_TOTAL_MB together (what is larger still goes to the arena)
-        {
-            const uint64_t nlmax = (uint64_t)std::min<int>(PMX_MAX_LEVELS, std::max(1, lib->info.max_clusters));
-            const uint64_t K = (uint64_t)std::max(1, std::min(model->dm.K, PMX_MAX_LEVEL_CANDIDATES)); // (candidates per level)
-            const uint64_t worst = rec_bytes<G>((uint32_t)(nlmax * K), (uint32_t)(nlmax * (nlmax - 1) / 2 * K * K), (uint32_t)nlmax);
-            const uint64_t cap = (uint64_t)std::max<long>(1, env_long("PMX_BIG_SLICE_MB", G >= 32 ? 4 : 32)) << 20;
-            pl.worst_bytes = worst;
-            pl.big_bytes = (uint32_t)std::max<uint64_t>(pl.slice_bytes, (std::min(worst, cap) + 4095) & ~4095ull);
-            const uint64_t total = (uint64_t)std::max<long>(64, env_long("PMX_BIG_TOTAL_MB", G >= 32 ? 16384 : 4096)) << 20;
-            pl.big_grid = (uint32_t)std::max<uint64_t>(16, std::min<uint64_t>(grid, total / pl.big_bytes));
-        }
-        big_need = std::max(big_need, (size_t)pl.big_grid * pl.big_bytes);
-        if (cand_bounds<G>()) { // float[matches <= levels][candidates of all levels][G], at most 1 MB per wavefront (larger jobs do without)
-            const uint64_t nlmax = (uint64_t)std::min<int>(PMX_MAX_LEVELS, std::max(1, lib->info.max_clusters));
-            const uint64_t need = (nlmax + 1) * nlmax * (uint64_t)std::max(1, std::min(model->dm.K, PMX_MAX_LEVEL_CANDIDATES)) * G * 4;
-            pl.pa_bytes = (uint32_t)std::min<uint64_t>((need + 255) & ~255ull, (uint64_t)std::max<long>(1, env_long("PMX_PATH_KB", 1024)) << 10);
-            pabuf_need = std::max(pabuf_need, (size_t)grid * pl.pa_bytes * 2u); // ligand kernel | task kernel
-        }
-        retry_possible = retry_possible || pl.worst_bytes > pl.big_bytes;
-        if (!totals_in_lds<G>()) totbuf_need = (size_t)ws.num_cu * 4u * std::max(PMX_SCREEN_WAVES, PMX_TASK_WAVES) * kTotBufBytes * 2u; // ligand kernel | task kernel
-        // chunk: what the arena has to hold at a time are the tables of the chunk's split trees. (Cutting a pocket's pass into more
-        // chunks than the arena asks for does not pay: every chunk ends in a dozen rounds with a tail each - 1 M ligands in 8
-        // chunks: 258 ms back to back, 234 ms with the rounds beside the next chunk's ligand kernel, 207 ms in one chunk.)
-        const long super_dflt = std::max(16384L, (1L << 20) * 8 / std::max(G, 8) / k_scale);
-        pl.super = (uint32_t)std::max<long>(1024, std::min<long>(env_long("PMX_SUPER", super_dflt), 1 << 24));
+        need.cover(pl.need);
+        retry_possible = retry_possible || pl.arena_retries > 0;
         super_max = std::max(super_max, pl.super);
     }
-    int rc = grow(&ws.slices, &ws.slices_bytes, slices_need, stream, ws.side);
-    if (rc) return rc;
-    rc = grow(&ws.big, &ws.big_bytes, big_need, stream, ws.side);
-    if (rc) return rc;
-    if (totbuf_need) {
-        rc = grow(&ws.totbuf, &ws.totbuf_bytes, totbuf_need, stream, ws.side);
-        if (rc) return rc;
-    }
-    if (pabuf_need) {
-        rc = grow(&ws.pabuf, &ws.pabuf_bytes, pabuf_need, stream, ws.side);
+    {
+        const int rc = grow_buffers(ws, need, stream);
         if (rc) return rc;
     }
     uint64_t n_chunks = 0;
@@ -893,37 +945,13 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
     // (PMX_OVERLAP, off by default): in order on one stream a chunk is through with them when the next one starts.
     for (int ci = 0; ci < (overlap ? 2 : 1); ++ci) {
         ChunkSet &c = ws.set[ci];
-        // (PMX_ARENA_MB / PMX_TASKQ_MB are per set; a smaller arena than asked for is slower - more trees walked by one
-        // wavefront alone - never wrong, so it shrinks when memory is short: several streams each keep a workspace. A size that was
-        // accepted after shrinking stands until the workspace is released: asking for the full size again on every call would
-        // synchronise, free and fail again each time)
-        // (32 / 64 conformer lanes: records of megabytes - 16 GB held the split trees of a 16 384-ligand chunk of the stress configuration
-        // to within 3 %, and every tree past the end is walked by one wavefront alone)
-        // ([MI355X] round 6: 64 GB at up to 16 lanes. SURVEY 8d-2's library puts 29 GB of split trees' tables into the arena per 1 M-ligand chunk at the old
-        // budget, 17 GB at the new one; with a 16 GB arena 200 000 trees found it full and were walked by one wavefront each - the longest for 1.2 M
-        // passes, the pass 3.4 s instead of 0.54 s. The part has 288 GB.)
-        size_t arena_want = (size_t)std::max<long>(1, env_long("PMX_ARENA_MB", G >= 32 ? 32768 : 65536)) << 20;
-        if (!c.arena && !std::getenv("PMX_ARENA_MB")) { // first allocation, no explicit size: at most a third of what the device has free
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b / 3 < arena_want) {
-                arena_want = std::max<size_t>((size_t)1 << 30, (free_b / 3) & ~(((size_t)1 << 20) - 1));
-                c.arena_shrunk_to = arena_want;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        const size_t arena_min = std::min<size_t>((size_t)1 << 30, arena_want);
-        if (c.arena_shrunk_to) arena_want = std::min(arena_want, std::max(c.arena_shrunk_to, arena_min));
-        const size_t asked = arena_want;
-        int rc2 = grow(&c.arena, &c.arena_bytes, arena_want, stream, ws.side, arena_min);
-        if (rc2) return rc2;
-        if (c.arena_bytes < asked) c.arena_shrunk_to = c.arena_bytes;
-        rc2 = grow(&c.queue, &c.queue_bytes, (size_t)std::max<long>(1, env_long("PMX_TASKQ_MB", (G >= 32 ? 1024L : 2048L) * std::max(1, G / 8))) << 20, stream, ws.side);
-        if (rc2) return rc2;
-        rc2 = grow(&c.lists, &c.lists_bytes, (size_t)super_max * 12, stream, ws.side);
-        if (rc2) return rc2;
+        int rc = ensure_arena<G>(c, stream, ws.side);
+        if (!rc) rc = grow(&c.queue, &c.queue_bytes, (size_t)std::max<long>(1, env_long("PMX_TASKQ_MB", (G >= 32 ? 1024L : 2048L) * std::max(1, G / 8))) << 20, stream, ws.side);
+        if (!rc) rc = grow(&c.lists, &c.lists_bytes, (size_t)super_max * 12, stream, ws.side);
+        if (rc) return rc;
     }
-    const double lig_share = std::min(0.9, std::max(0.1, std::atof(std::getenv("PMX_LIG_SHARE") ? std::getenv("PMX_LIG_SHARE") : "0.5")));
+    const char *lig_share_env = std::getenv("PMX_LIG_SHARE");
+    const double lig_share = std::min(0.9, std::max(0.1, std::atof(lig_share_env ? lig_share_env : "0.5")));
 
     if (g_profiling) HIPCHECK(hipEventRecord(ws.ev[0], stream));
     ws.ctl_used[0] = ws.ctl_used[1] = false;
@@ -954,7 +982,6 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
             p.qcap = (uint32_t)std::min<size_t>(c.queue_bytes / task_rec_bytes<G>() / kShards, 0x3fffffffu / kShards);
             p.totbuf = ws.totbuf;
             p.pabuf = ws.pabuf;
-            p.pa_bytes = pl.pa_bytes;
             // this set's last chunk (two chunks ago) has to be through its rounds
             if (overlap && c.pending) HIPCHECK(hipStreamWaitEvent(stream, c.tasks_done, 0));
             if (overlap && !overlap_pockets && lo == 0 && seq > 0 && ws.set[(seq - 1) & 1].pending) // (the rounds of the pocket before)
@@ -1013,23 +1040,17 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
             };
             rounds_and_finalize();
             // Ligands the arena pass had no room for, with the arena to themselves (only models and libraries whose largest tables
-            // exceed a large slice ever get here; `side` is the caller's stream then): PMX_ARENA_RETRIES times, the last time reporting what
-            // still does not fit.
-            if (pl.worst_bytes > pl.big_bytes) {
-                for (int t = 0; t < arena_retries; ++t) {
-                    retry_prep_kernel<<<dim3(1), dim3(64), 0, side>>>(c.ctl, (uint32_t)(t + 1) & 1u);
-                    p.retry_in = (t & 1) == 0 ? c.lists : c.lists + super;
-                    p.retry_out = t + 1 == arena_retries ? nullptr : ((t & 1) == 0 ? c.lists + super : c.lists);
-                    p.retry_slot = (uint32_t)(t + 1) & 1u;
-                    p.totbuf = ws.totbuf;
-                    p.pabuf = ws.pabuf;
-                    launch(3, std::min(pl.big_grid, lig_grid), side);
-                    if (!totals_in_lds<G>()) p.totbuf = ws.totbuf + ws.totbuf_bytes / 2;
-                    if (ws.pabuf) p.pabuf = ws.pabuf + ws.pabuf_bytes / 2;
-                    rounds_and_finalize();
-                }
-                p.retry_in = nullptr;
+            // exceed a large slice have such passes; `side` is the caller's stream then), the last pass reporting what still does not fit.
+            for (int t = 0; t < pl.arena_retries; ++t) {
+                prepare_retry(p, c.ctl, c.lists, super, t, pl.arena_retries, side);
+                p.totbuf = ws.totbuf;
+                p.pabuf = ws.pabuf;
+                launch(3, std::min(pl.big_grid, lig_grid), side);
+                if (!totals_in_lds<G>()) p.totbuf = ws.totbuf + ws.totbuf_bytes / 2;
+                if (ws.pabuf) p.pabuf = ws.pabuf + ws.pabuf_bytes / 2;
+                rounds_and_finalize();
             }
+            p.retry_in = nullptr;
             if (g_profiling && last_of_call) HIPCHECK(hipEventRecord(ws.ev[5], side));
             if (overlap) {
                 HIPCHECK(hipEventRecord(c.tasks_done, side));
@@ -1099,10 +1120,30 @@ static int screen_stats(pmx_score_stats *out) {
     return PMX_OK;
 }
 
-static int next_pow2(int x) {
+// Conformer lanes per slot for a library: its most conformers, rounded up to a power of two.
+static int lanes_of(const pmx_library *lib) {
     int g = 1;
-    while (g < x) g <<= 1;
+    while (g < std::min(lib->info.max_conformers, PMX_MAX_CONFORMERS)) g <<= 1;
     return g;
+}
+
+static Weights to_weights(const float weights[PMX_NUM_TYPES]) {
+    Weights W;
+    for (int t = 0; t < PMX_NUM_TYPES; ++t) W.w[t] = weights[t];
+    return W;
+}
+
+// The workspace of (device, stream), held: one call at a time enqueues on it. (lock is released before ws goes)
+struct HeldWs {
+    std::shared_ptr<ScreenWs> ws;
+    std::unique_lock<std::mutex> lock;
+};
+static HeldWs hold_screen(int device, hipStream_t stream) {
+    for (;;) {
+        HeldWs h{ensure_screen(device, stream), {}};
+        h.lock = std::unique_lock<std::mutex>(h.ws->mu);
+        if (!h.ws->released) return h; // (released while this call waited: the map holds a fresh one, or will make one)
+    }
 }
 
 static int score_any(const pmx_model *const *models, int n_models, const pmx_library *lib, const float weights[PMX_NUM_TYPES], uint64_t first,
@@ -1117,29 +1158,13 @@ static int score_any(const pmx_model *const *models, int n_models, const pmx_lib
     g_last_screen.reset();
     if (count == 0 || n_models == 0) return PMX_OK;
     HIPCHECK(hipSetDevice(lib->device));
-    Weights W;
-    for (int t = 0; t < PMX_NUM_TYPES; ++t) W.w[t] = weights[t];
+    const Weights W = to_weights(weights);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int G = next_pow2(std::max(1, std::min(lib->info.max_conformers, PMX_MAX_CONFORMERS)));
+    const HeldWs held = hold_screen(lib->device, stream);
     int rc = PMX_OK;
-    std::shared_ptr<ScreenWs> ws;
-    std::unique_lock<std::mutex> lock;
-    for (;;) { // one call at a time enqueues on a (device, stream) workspace
-        ws = ensure_screen(lib->device, stream);
-        lock = std::unique_lock<std::mutex>(ws->mu);
-        if (!ws->released) break;
-        lock.unlock(); // released while this call waited: the map holds a fresh one (or will make one)
-    }
-    switch (G) {
-    case 1: rc = score_screen<1>(models, n_models, lib, W, first, count, scores_dev, scores_f64, status_dev, stream, *ws); break;
-    case 2: rc = score_screen<2>(models, n_models, lib, W, first, count, scores_dev, scores_f64, status_dev, stream, *ws); break;
-    case 4: rc = score_screen<4>(models, n_models, lib, W, first, count, scores_dev, scores_f64, status_dev, stream, *ws); break;
-    case 8: rc = score_screen<8>(models, n_models, lib, W, first, count, scores_dev, scores_f64, status_dev, stream, *ws); break;
-    case 16: rc = score_screen<16>(models, n_models, lib, W, first, count, scores_dev, scores_f64, status_dev, stream, *ws); break;
-    case 32: rc = score_screen<32>(models, n_models, lib, W, first, count, scores_dev, scores_f64, status_dev, stream, *ws); break;
-    default: rc = score_screen<64>(models, n_models, lib, W, first, count, scores_dev, scores_f64, status_dev, stream, *ws); break;
-    }
-    g_last_screen = ws;
+    if (!with_lanes(lanes_of(lib), [&](auto g) { rc = score_screen<decltype(g)::value>(models, n_models, lib, W, first, count, scores_dev, scores_f64, status_dev, stream, *held.ws); }))
+        rc = fail(PMX_ERR_INVALID, "no kernels for %d conformer lanes", lanes_of(lib));
+    g_last_screen = held.ws;
     g_last_device = lib->device;
     return rc;
 }
@@ -1206,80 +1231,20 @@ int pmx_topk_fail(int code, const char *msg) { return fail(code, "%s", msg); }
 // retries - and each is walked to its end by one wavefront of the explain kernel: no budget, no task queue.
 template <int G>
 static int explain_screen(const pmx_model *model, const pmx_library *lib, const Weights &W, const pmx_xpl::Args &a, hipStream_t stream, ScreenWs &ws) {
-    {
-        const int irc = init_workspace(ws, lib->device);
-        if (irc) return irc;
-    }
+    int rc = init_workspace(ws, lib->device);
+    if (rc) return rc;
     const bool tails = pair_tails(&model, 1, W); // (as pmx_score / pmx_score_f64 decide it for this model)
-    const uint32_t max_nodes = (uint32_t)std::max(4, std::min(lib->info.max_nodes, PMX_MAX_LIGAND_NODES));
-    ScreenParams p{};
-    p.M = model->dm;
-    int rc = pair_functions(const_cast<pmx_model *>(model), W, stream, &p.F);
-    if (rc) return rc;
-    p.lib = lib->dl;
-    p.sidtab = model->sidtab;
-    p.sub_off = model->sub_off;
-    p.sub_nodes = model->sub_nodes;
-    p.W = W;
-    p.flags = PMX_SCORES_F64;
-    p.max_nodes = max_nodes;
-    p.bound_cost = (uint32_t)std::max<long>(0, env_long("PMX_BOUND_COST", 8192));
-    p.dead_min_entries = (uint32_t)std::max<long>(1, env_long("PMX_DEAD_MIN_ENTRIES", 32));
-    p.status = a.status;
-    // the per-wave buffers as score_screen sizes them (the same workspace serves both)
-    const WaveShape<G> shape = wave_shape<G>(model->dm.K, (int)max_nodes);
-    const size_t lds = pmx_xpl::lds_bytes(G, model->dm.K, (int)max_nodes);
-    const uint32_t waves_per_cu = (uint32_t)std::max<long>(2, std::min<long>({(long)(kLdsPerCu / shape.bytes), 4L * PMX_SCREEN_WAVES, env_long("PMX_WAVES_PER_CU", 32)}));
-    const uint32_t task_waves_per_cu = (uint32_t)std::max<long>(2, std::min<long>({(long)(kLdsPerCu / shape.bytes), 4L * PMX_TASK_WAVES, env_long("PMX_TASK_WAVES_PER_CU", 32)}));
-    const uint32_t grid = (uint32_t)ws.num_cu * std::max(waves_per_cu, task_waves_per_cu);
-    const long k_scale = std::max(1L, std::min(16L, ((long)model->dm.K * model->dm.K + 60) / 121));
-    const uint32_t slice_bytes = (uint32_t)std::max<long>(4, env_long("PMX_SLICE_KB", (cand_bounds<G>() ? 112L : 80L) * std::max(1, G / 8) * k_scale)) * 1024u;
-    const uint64_t nlmax = (uint64_t)std::min<int>(PMX_MAX_LEVELS, std::max(1, lib->info.max_clusters));
-    const uint64_t K = (uint64_t)std::max(1, std::min(model->dm.K, PMX_MAX_LEVEL_CANDIDATES));
-    const uint64_t worst = rec_bytes<G>((uint32_t)(nlmax * K), (uint32_t)(nlmax * (nlmax - 1) / 2 * K * K), (uint32_t)nlmax);
-    const uint64_t cap = (uint64_t)std::max<long>(1, env_long("PMX_BIG_SLICE_MB", G >= 32 ? 4 : 32)) << 20;
-    const uint32_t big_bytes = (uint32_t)std::max<uint64_t>(slice_bytes, (std::min(worst, cap) + 4095) & ~4095ull);
-    const uint64_t big_total = (uint64_t)std::max<long>(64, env_long("PMX_BIG_TOTAL_MB", G >= 32 ? 16384 : 4096)) << 20;
-    const uint32_t big_grid = (uint32_t)std::max<uint64_t>(16, std::min<uint64_t>(grid, big_total / big_bytes));
-    uint32_t pa_bytes = 0;
-    size_t pabuf_need = 0;
-    if (cand_bounds<G>()) {
-        const uint64_t need = (nlmax + 1) * nlmax * K * G * 4;
-        pa_bytes = (uint32_t)std::min<uint64_t>((need + 255) & ~255ull, (uint64_t)std::max<long>(1, env_long("PMX_PATH_KB", 1024)) << 10);
-        pabuf_need = (size_t)grid * pa_bytes * 2u;
-    }
-    rc = grow(&ws.slices, &ws.slices_bytes, (size_t)grid * slice_bytes, stream, ws.side);
-    if (rc) return rc;
-    rc = grow(&ws.big, &ws.big_bytes, (size_t)big_grid * big_bytes, stream, ws.side);
-    if (rc) return rc;
-    if (pabuf_need) {
-        rc = grow(&ws.pabuf, &ws.pabuf_bytes, pabuf_need, stream, ws.side);
-        if (rc) return rc;
-    }
-    if (!totals_in_lds<G>()) { // (the table phase stages node distances and chain lengths there at 32 / 64 lanes)
-        rc = grow(&ws.totbuf, &ws.totbuf_bytes, (size_t)ws.num_cu * 4u * std::max(PMX_SCREEN_WAVES, PMX_TASK_WAVES) * kTotBufBytes * 2u, stream, ws.side);
-        if (rc) return rc;
-    }
+    PocketPlan pl;
+    rc = plan_pocket<G>(model, lib, W, ws.num_cu, stream, pl);
+    if (!rc) rc = grow_buffers(ws, pl.need, stream);
     ChunkSet &c = ws.set[0];
-    if (!c.arena) { // (an arena made by pmx_score is taken as it is)
-        size_t arena_want = (size_t)std::max<long>(1, env_long("PMX_ARENA_MB", G >= 32 ? 32768 : 65536)) << 20;
-        if (!std::getenv("PMX_ARENA_MB")) {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b / 3 < arena_want) {
-                arena_want = std::max<size_t>((size_t)1 << 30, (free_b / 3) & ~(((size_t)1 << 20) - 1));
-                c.arena_shrunk_to = arena_want;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        const size_t asked = arena_want;
-        rc = grow(&c.arena, &c.arena_bytes, arena_want, stream, ws.side, std::min<size_t>((size_t)1 << 30, arena_want));
-        if (rc) return rc;
-        if (c.arena_bytes < asked) c.arena_shrunk_to = c.arena_bytes;
-    }
-    rc = grow(&c.lists, &c.lists_bytes, (size_t)a.n * 12, stream, ws.side);
+    if (!rc && !c.arena) rc = ensure_arena<G>(c, stream, ws.side); // (an arena made by pmx_score is taken as it is)
+    if (!rc) rc = grow(&c.lists, &c.lists_bytes, (size_t)a.n * 12, stream, ws.side);
     if (rc) return rc;
     if (!ws.xctl) HIPCHECK(hipMalloc((void **)&ws.xctl, sizeof(Ctl)));
+    ScreenParams &p = pl.p;
+    p.flags = PMX_SCORES_F64; // (never PMX_TREE_FLAGS)
+    p.status = a.status;
     p.ctl = ws.xctl;
     p.arena = c.arena;
     p.arena_bytes = std::min<unsigned long long>(c.arena_bytes, (1ull << 36) - 4096);
@@ -1288,33 +1253,27 @@ static int explain_screen(const pmx_model *model, const pmx_library *lib, const 
     p.heavy_list = c.lists + 2 * (size_t)a.n;
     p.list_cap = a.n;
     p.pabuf = ws.pabuf;
-    p.pa_bytes = pa_bytes;
     p.totbuf = ws.totbuf;
     p.hi = a.n;
 
     pmx_xpl::launch_init(a, stream);
     ctl_clear_kernel<<<dim3((sizeof(Ctl) / 4 + 255) / 256), dim3(256), 0, stream>>>(ws.xctl, 1);
-    const uint32_t full = (uint32_t)ws.num_cu * waves_per_cu;
+    const size_t lds = pmx_xpl::lds_bytes(G, model->dm.K, (int)p.max_nodes);
+    const uint32_t full = (uint32_t)ws.num_cu * pl.waves_per_cu;
     bool ok = true;
     auto launch = [&](int mode, uint32_t blocks) { ok &= pmx_xpl::launch(G, tails, mode, std::max(1u, blocks), (unsigned)lds, stream, &p, sizeof p, a); };
     p.slices = ws.slices;
-    p.slice_bytes = slice_bytes;
+    p.slice_bytes = pl.slice_bytes;
     launch(0, std::min(full, a.n));
     p.slices = ws.big;
-    p.slice_bytes = big_bytes;
-    launch(1, std::min(big_grid, full));
+    p.slice_bytes = pl.big_bytes;
+    launch(1, std::min(pl.big_grid, full));
     p.retry_out = c.lists;
     p.retry_slot = 0;
-    launch(2, std::min(big_grid, full));
-    if (worst > big_bytes) {
-        const int arena_retries = (int)std::max<long>(1, env_long("PMX_ARENA_RETRIES", 4));
-        for (int t = 0; t < arena_retries; ++t) {
-            retry_prep_kernel<<<dim3(1), dim3(64), 0, stream>>>(ws.xctl, (uint32_t)(t + 1) & 1u);
-            p.retry_in = (t & 1) == 0 ? c.lists : c.lists + a.n;
-            p.retry_out = t + 1 == arena_retries ? nullptr : ((t & 1) == 0 ? c.lists + a.n : c.lists);
-            p.retry_slot = (uint32_t)(t + 1) & 1u;
-            launch(3, std::min(big_grid, full));
-        }
+    launch(2, std::min(pl.big_grid, full));
+    for (int t = 0; t < pl.arena_retries; ++t) {
+        prepare_retry(p, ws.xctl, c.lists, a.n, t, pl.arena_retries, stream);
+        launch(3, std::min(pl.big_grid, full));
     }
     pmx_xpl::launch_fixup(a, stream);
     HIPCHECK(hipGetLastError());
@@ -1330,26 +1289,12 @@ extern "C" int pmx_explain(const pmx_model *model, const pmx_library *lib, const
     if (!ligands_dev || !conf_max_dev || !match_dev || !levels_dev || !best_conformer_dev || !status_dev) return fail(PMX_ERR_INVALID, "null argument");
     if (model->device != lib->device) return fail(PMX_ERR_INVALID, "model and library live on different devices");
     HIPCHECK(hipSetDevice(lib->device));
-    Weights W;
-    for (int t = 0; t < PMX_NUM_TYPES; ++t) W.w[t] = weights[t];
+    const Weights W = to_weights(weights);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    pmx_xpl::Args a{ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev};
-    const int G = next_pow2(std::max(1, std::min(lib->info.max_conformers, PMX_MAX_CONFORMERS)));
-    std::shared_ptr<ScreenWs> ws;
-    std::unique_lock<std::mutex> lock;
-    for (;;) {
-        ws = ensure_screen(lib->device, stream);
-        lock = std::unique_lock<std::mutex>(ws->mu);
-        if (!ws->released) break;
-        lock.unlock();
-    }
-    switch (G) {
-    case 1: return explain_screen<1>(model, lib, W, a, stream, *ws);
-    case 2: return explain_screen<2>(model, lib, W, a, stream, *ws);
-    case 4: return explain_screen<4>(model, lib, W, a, stream, *ws);
-    case 8: return explain_screen<8>(model, lib, W, a, stream, *ws);
-    case 16: return explain_screen<16>(model, lib, W, a, stream, *ws);
-    case 32: return explain_screen<32>(model, lib, W, a, stream, *ws);
-    default: return explain_screen<64>(model, lib, W, a, stream, *ws);
-    }
+    const pmx_xpl::Args a{ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev};
+    const HeldWs held = hold_screen(lib->device, stream);
+    int rc = PMX_OK;
+    if (!with_lanes(lanes_of(lib), [&](auto g) { rc = explain_screen<decltype(g)::value>(model, lib, W, a, stream, *held.ws); }))
+        rc = fail(PMX_ERR_INVALID, "no kernels for %d conformer lanes", lanes_of(lib));
+    return rc;
 }

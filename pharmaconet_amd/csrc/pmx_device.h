@@ -1,7 +1,9 @@
-// pmx_device.h - device-side layouts shared by the kernels of libpmx (gfx950 only).
+// pmx_device.h - device-side layouts shared by the kernels of libpmx (gfx950 only), and the host's dispatch on their lane count.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "pmx.h"
 
@@ -60,6 +62,21 @@ __device__ inline Record parse_record(const uint8_t *rec) {
 
 __device__ inline bool record_supported(const Record &r) {
     return r.C >= 1 && r.C <= PMX_MAX_CONFORMERS && r.n <= PMX_MAX_LIGAND_NODES && r.ncl <= PMX_MAX_LIGAND_CLUSTERS;
+}
+
+// Host: f(std::integral_constant<int, G>{}) for a conformer lane count the kernels are built for (1, 2, 4, ..., 64); false for any other G.
+template <class F>
+inline bool with_lanes(int G, F &&f) {
+    switch (G) {
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    case 8: f(std::integral_constant<int, 8>{}); return true;
+    case 16: f(std::integral_constant<int, 16>{}); return true;
+    case 32: f(std::integral_constant<int, 32>{}); return true;
+    case 64: f(std::integral_constant<int, 64>{}); return true;
+    default: return false;
+    }
 }
 
 } // namespace pmx

@@ -15,7 +15,8 @@ struct Args {
     int32_t *best;     // [n]
     int32_t *status;   // [n]
 };
-// Dynamic LDS of the explain kernel of shape G for a model of K clusters and a library of at most max_nodes nodes per ligand.
+// Dynamic LDS of the explain kernel of shape G for a model of K clusters and a library of at most max_nodes nodes per ligand
+// (0 for a G this side does not know).
 size_t lds_bytes(int G, int K, int max_nodes);
 // `params`: the caller's pmx::ScreenParams (same source and layout; `bytes` is checked against this side's sizeof). mode as
 // ScreenParams::mode: 0 the listed ligands with tables in per-wave slices, 1 the large-slice pass, 2 / 3 the arena passes.

@@ -296,26 +296,10 @@ __global__ void explain_fixup_kernel(const pmx_xpl::Args a) {
 
 namespace pmx_xpl {
 
-template <int G>
-static size_t lds_g(int K, int max_nodes) {
-    return pmx_x::explain_lds<G>(pmx_x::wave_shape<G>(K, max_nodes)).bytes;
-}
 size_t lds_bytes(int G, int K, int max_nodes) {
-    switch (G) {
-    case 1: return lds_g<1>(K, max_nodes);
-    case 2: return lds_g<2>(K, max_nodes);
-    case 4: return lds_g<4>(K, max_nodes);
-    case 8: return lds_g<8>(K, max_nodes);
-    case 16: return lds_g<16>(K, max_nodes);
-    case 32: return lds_g<32>(K, max_nodes);
-    default: return lds_g<64>(K, max_nodes);
-    }
-}
-
-template <int G>
-static void launch_g(bool tails, unsigned blocks, unsigned lds, hipStream_t stream, const pmx_x::ScreenParams &p, const Args &a) {
-    if (tails) pmx_x::explain_kernel<G, true><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
-    else pmx_x::explain_kernel<G, false><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+    size_t bytes = 0;
+    pmx::with_lanes(G, [&](auto g) { bytes = pmx_x::explain_lds<decltype(g)::value>(pmx_x::wave_shape<decltype(g)::value>(K, max_nodes)).bytes; });
+    return bytes;
 }
 
 bool launch(int G, bool tails, int mode, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes, const Args &a) {
@@ -323,17 +307,10 @@ bool launch(int G, bool tails, int mode, unsigned blocks, unsigned lds, hipStrea
     pmx_x::ScreenParams p;
     std::memcpy(&p, params, sizeof p);
     p.mode = mode;
-    switch (G) {
-    case 1: launch_g<1>(tails, blocks, lds, stream, p, a); break;
-    case 2: launch_g<2>(tails, blocks, lds, stream, p, a); break;
-    case 4: launch_g<4>(tails, blocks, lds, stream, p, a); break;
-    case 8: launch_g<8>(tails, blocks, lds, stream, p, a); break;
-    case 16: launch_g<16>(tails, blocks, lds, stream, p, a); break;
-    case 32: launch_g<32>(tails, blocks, lds, stream, p, a); break;
-    case 64: launch_g<64>(tails, blocks, lds, stream, p, a); break;
-    default: return false;
-    }
-    return true;
+    return pmx::with_lanes(G, [&](auto g) {
+        if (tails) pmx_x::explain_kernel<decltype(g)::value, true><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+        else pmx_x::explain_kernel<decltype(g)::value, false><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+    });
 }
 
 void launch_init(const Args &a, hipStream_t stream) {

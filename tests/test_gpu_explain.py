@@ -153,12 +153,12 @@ def test_consistent_with_the_score_pass_on_4096_ligands(which):
     assert (ex.status == 0).all()
 
 
-def test_invariance_and_two_streams():
+def test_invariance_and_two_streams(monkeypatch):
     import threading
 
     import torch
 
-    from pharmaconet_amd.engine import DeviceLibrary, explain
+    from pharmaconet_amd.engine import DeviceLibrary, explain, last_score_stats, screen
 
     model, lib, weights, _ = load_golden("set_c21_c8")
     dlib = DeviceLibrary(lib)
@@ -168,6 +168,16 @@ def test_invariance_and_two_streams():
         for r, i in enumerate(rows):
             assert np.array_equal(ex.conf_max[r], base.conf_max[i]) and np.array_equal(ex.match[r], base.match[i])
             assert np.array_equal(ex.levels[r], base.levels[i]) and ex.best_conformer[r] == base.best_conformer[i]
+            assert ex.status[r] == base.status[i]
+
+    # the overflow passes: tables that do not fit an 8 KB slice, then also large slices of 1 MB (as test_gpu_api.py cuts the score pass)
+    for env in ({"PMX_SLICE_KB": "8"}, {"PMX_SLICE_KB": "8", "PMX_BIG_SLICE_MB": "1", "PMX_BIG_TOTAL_MB": "64"}):
+        with monkeypatch.context() as mp:
+            for k, v in env.items():
+                mp.setenv(k, v)
+            same(explain(model, dlib, np.arange(len(lib)), weights=weights), np.arange(len(lib)))
+            screen(model, dlib, weights=weights, float64=True)
+            assert last_score_stats()["n_slice_overflow"] > 0, env  # the setting does reach the overflow passes
 
     rng = np.random.default_rng(3)
     perm = rng.permutation(len(lib))
