@@ -118,14 +118,12 @@ int pmx_library_destroy(pmx_library *lib);
  * Everything is enqueued and the call returns: no device-to-host read, no synchronisation, no helper thread (a
  * synchronisation happens only when a cached work buffer has to grow). The work is ordered on `stream`: per chunk of ligands
  * (PMX_SUPER) the ligand kernel (score tables in per-wavefront slices + tree search within a pass budget), the same for
- * ligands with larger tables, a fixed number of task rounds for the subtrees of over-budget trees, finalize. With
- * PMX_OVERLAP set and more than one chunk, the rounds of a chunk run on a side stream that the workspace owns, beside the
- * next chunk's ligand kernel: they start behind an event recorded on `stream` and `stream` waits for their last event before
- * the call's work counts as done, so a caller sees one stream-ordered operation either way. Work buffers are kept per (device, stream) for at most PMX_MAX_WORKSPACES (default 4) streams per device - the least recently used idle workspace is
+ * ligands with larger tables, a fixed number of task rounds for the subtrees of over-budget trees, finalize - one in-order
+ * sequence on `stream`, no other stream, no event to wait for. Work buffers are kept per (device, stream) for at most PMX_MAX_WORKSPACES (default 4) streams per device - the least recently used idle workspace is
  * freed when one more stream appears. At the defaults: about 73 GB for libraries of up to 8 conformers and an 11-cluster model (64 GB table arena,
  * 2 GB task queue, <= 4 GB large slices, 0.7 GB slices, 1.8 GB path sums), about 70 GB at 32 / 64 conformer lanes (32 GB arena, 8 GB queue, <= 16 GB
- * large slices, slices that grow with the square of the model's cluster count); PMX_ARENA_MB, PMX_TASKQ_MB size one buffer set, and a second
- * set exists only while PMX_OVERLAP is in use. Without PMX_ARENA_MB the table arena takes at most a third of the device memory that is free when it is first allocated, and it shrinks when device memory is short - a smaller arena is slower, never
+ * large slices, slices that grow with the square of the model's cluster count); PMX_ARENA_MB, PMX_TASKQ_MB size the arena and
+ * the queue of a workspace. Without PMX_ARENA_MB the table arena takes at most a third of the device memory that is free when it is first allocated, and it shrinks when device memory is short - a smaller arena is slower, never
  * wrong - and keeps the size it got until pmx_release_workspaces. PMX_LIGAND_TOO_LARGE is reported for a ligand whose tables exceed a whole
  * arena; a ligand that merely found the arena full of other ligands' tables is taken again with the arena empty, in up to PMX_ARENA_RETRIES
  * (default 4) further passes (only models whose largest possible tables exceed a large slice have such passes).
@@ -145,8 +143,8 @@ int pmx_score_multi_f64(const pmx_model *const *models, int n_models, const pmx_
                         const float weights[PMX_NUM_TYPES], uint64_t first, uint64_t count, double *scores_dev,
                         int32_t *status_dev, void *stream);
 
-/* The same for several models over one library: the pockets' chunks are one sequence of one call (one pocket after the other
- * on `stream` by default; PMX_OVERLAP=2 lets a pocket's last task rounds run beside the next pocket's ligand kernel);
+/* The same for several models over one library: the pockets' chunks are one sequence of one call, one pocket after the other
+ * on `stream`;
  * scores_dev is [n_models][count], status_dev[count] is written once. */
 int pmx_score_multi(const pmx_model *const *models, int n_models, const pmx_library *lib,
                     const float weights[PMX_NUM_TYPES], uint64_t first, uint64_t count, float *scores_dev,

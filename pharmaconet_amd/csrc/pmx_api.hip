@@ -1,4 +1,4 @@
-// pmx_api.hip - host side of libpmx.so: the C ABI of include/pmx.h over the kernels of pmx_screen.hip.
+// pmx_api.hip - the host half of libpmx.so: the C ABI of include/pmx.h over the kernels of pmx_screen.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -267,7 +267,7 @@ static int build_pair_functions(pmx_model *m, const pmx_model_desc *d, const std
 // Cells whose polynomial deviates from the function by more than this, relative to the function, are flagged (FnCell) and
 // evaluated term by term where a self entry meets them. 2e-7 is just above what the float32 coefficients themselves cost
 // (each rounded to 6e-8 of its value) and leaves room for the reference's own float32 rounding of z and z^2 (about
-// 1e-7 z^2 / 2 relative) inside the 2e-6 the parity tests allow; on the bench library 1-3 self items per ligand are flagged.
+// 1e-7 z^2 / 2 relative) within the 2e-6 the parity tests allow; on the bench library 1-3 self items per ligand are flagged.
 static double fn_rel_tol() {
     const char *s = std::getenv("PMX_FN_RELTOL");
     const double v = (s && *s) ? std::atof(s) : 2e-7;
@@ -573,67 +573,35 @@ static bool trace_on() {
 // A call is cut into chunks of <= PMX_SUPER ligands (per pocket); a chunk is: clear the control block; ligand_kernel over the
 // range (tables in per-wave slices); ligand_kernel over the ligands whose tables need larger slices / the arena; a fixed
 // number of task rounds (each a snapshot of the queue + one persistent launch that exits at once when the round is empty; the
-// last round never queues); finalize. The ligand kernels of all chunks go out on the caller's stream; the task rounds of a
-// chunk go out on a side stream of the workspace, behind an event of the chunk's ligand kernels, and so run *next to* the
-// ligand kernels of the following chunk (of the same pocket or the next one): two sets of control block / arena / queue /
-// lists alternate, a set is reused when its chunk's rounds are done (event), and the caller's stream waits for the side
-// stream at the end - everything stays ordered on the caller's stream, nothing is read back, no host thread. The two kernels
-// share the wave slots of a CU (PMX_LIG_SHARE): the walkers of the task rounds are bound by scalar issue, the table phase
-// of the ligand kernel by vector issue and memory, so side by side they fill what the other leaves idle.
-struct ChunkSet {
-    Ctl *ctl = nullptr;
-    uint8_t *arena = nullptr;
-    size_t arena_bytes = 0;
-    uint8_t *queue = nullptr;
-    size_t queue_bytes = 0;
-    uint32_t *lists = nullptr; // ovf | carry | heavy
-    size_t lists_bytes = 0;
-    hipEvent_t lig_done = nullptr, tasks_done = nullptr;
-    bool pending = false; // tasks_done was recorded by the call in progress
-    size_t arena_shrunk_to = 0; // the arena size that was accepted when memory was short (0: never shrunk)
-};
+// last round never queues); finalize; the arena retries. Everything goes out on the caller's stream, in order: a chunk is
+// through with the control block, arena, queue and lists when the next one starts, so a workspace holds one of each. Nothing
+// is read back, no host thread.
 struct ScreenWs {
-    ChunkSet set[2];
-    uint8_t *slices = nullptr;
-    size_t slices_bytes = 0;
-    uint8_t *big = nullptr;
-    size_t big_bytes = 0;
-    uint8_t *totbuf = nullptr;
-    size_t totbuf_bytes = 0;
-    uint8_t *pabuf = nullptr; // path_bound()'s pair sums: ligand kernel's wavefronts | task kernel's
-    size_t pabuf_bytes = 0;
+    DevBuf ctl;                      // Ctl: pmx_score's control block
+    DevBuf xctl;                     // Ctl: pmx_explain's (its own: the statistics of the last pmx_score stay what that call left)
+    DevBuf slices, big;              // per-wavefront table slices, large slices
+    DevBuf totbuf;                   // ligand kernel's wavefronts | task kernel's
+    DevBuf pabuf;                    // path_bound()'s pair sums: ligand kernel's wavefronts | task kernel's
+    DevBuf arena, queue;
+    DevBuf lists;                    // uint32: ovf | carry | heavy
+    size_t arena_shrunk_to = 0;      // the arena size that was accepted when memory was short (0: never shrunk)
     int num_cu = 0;
-    hipStream_t side = nullptr; // the task rounds' stream
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // profiling: call start | last chunk: ligand kernels start, done | end | last chunk: rounds start, done
     uint64_t ligands_last = 0;
     bool ev_valid = false;
-    bool ctl_used[2] = {false, false};
+    bool ctl_used = false; // the call in progress has cleared `ctl`
     hipStream_t last_stream = nullptr;
     std::mutex mu; // held while a call enqueues (the workspace belongs to one call at a time, in stream order)
-    Ctl *xctl = nullptr;   // pmx_explain's control block (its own: the statistics of the last pmx_score stay what that call left)
     uint64_t stamp = 0;    // last use (ensure_screen): the least recently used workspace of a device goes first
     bool released = false; // pmx_release_workspaces (or the cap on workspaces per device) took the buffers: a caller that was waiting on `mu` asks for a new workspace
     void free_buffers() {
-        for (ChunkSet &c : set) {
-            for (void *q : {(void *)c.ctl, (void *)c.arena, (void *)c.queue, (void *)c.lists})
-                if (q) (void)hipFree(q);
-            for (hipEvent_t e : {c.lig_done, c.tasks_done})
-                if (e) (void)hipEventDestroy(e);
-            c = ChunkSet{};
-        }
-        for (void *q : {(void *)slices, (void *)big, (void *)totbuf, (void *)pabuf, (void *)xctl})
-            if (q) (void)hipFree(q);
-        xctl = nullptr;
-        slices = big = totbuf = pabuf = nullptr;
-        slices_bytes = big_bytes = totbuf_bytes = pabuf_bytes = 0;
+        for (DevBuf *b : {&ctl, &xctl, &slices, &big, &totbuf, &pabuf, &arena, &queue, &lists}) b->release();
         for (auto &e : ev) {
             if (e) (void)hipEventDestroy(e);
             e = nullptr;
         }
-        if (side) (void)hipStreamDestroy(side);
-        side = nullptr;
-        ev_valid = false;
-        ctl_used[0] = ctl_used[1] = false;
+        arena_shrunk_to = 0;
+        ev_valid = ctl_used = false;
     }
 };
 // Workspaces are shared: the map, a call in progress and the thread that asks for the last call's statistics each hold a
@@ -689,30 +657,6 @@ static std::shared_ptr<ScreenWs> ensure_screen(int device, hipStream_t stream) {
     return out;
 }
 
-// (a buffer only ever grows; queued work may still use the old one, on the caller's stream or on the side stream)
-template <typename T>
-static int grow(T **ptr, size_t *have, size_t want, hipStream_t stream, hipStream_t side, size_t min_bytes = 0) {
-    if (*have >= want) return PMX_OK;
-    if (*ptr) {
-        HIPCHECK(hipStreamSynchronize(stream));
-        if (side) HIPCHECK(hipStreamSynchronize(side));
-        (void)hipFree(*ptr);
-        *ptr = nullptr;
-        *have = 0;
-    }
-    // min_bytes: the buffer is a cache (the table arena) - a smaller one is slower, never wrong: halve on out-of-memory
-    for (;;) {
-        const hipError_t e = hipMalloc((void **)ptr, want);
-        if (e == hipSuccess) break;
-        (void)hipGetLastError();
-        if (e != hipErrorOutOfMemory || min_bytes == 0 || want / 2 < min_bytes)
-            return fail(e == hipErrorOutOfMemory ? PMX_ERR_OOM : PMX_ERR_HIP, "hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e));
-        want /= 2;
-    }
-    *have = want;
-    return PMX_OK;
-}
-
 // The per-wavefront buffers of a workspace, in bytes (a call grows them to the largest need of its pockets).
 struct BufferNeeds {
     size_t slices = 0, big = 0, totbuf = 0, pabuf = 0;
@@ -720,14 +664,14 @@ struct BufferNeeds {
 };
 
 static int grow_buffers(ScreenWs &ws, const BufferNeeds &need, hipStream_t stream) {
-    int rc = grow(&ws.slices, &ws.slices_bytes, need.slices, stream, ws.side);
-    if (!rc) rc = grow(&ws.big, &ws.big_bytes, need.big, stream, ws.side);
-    if (!rc) rc = grow(&ws.totbuf, &ws.totbuf_bytes, need.totbuf, stream, ws.side);
-    if (!rc) rc = grow(&ws.pabuf, &ws.pabuf_bytes, need.pabuf, stream, ws.side);
-    return rc;
+    HIPCHECK(ws.slices.grow(need.slices, stream));
+    HIPCHECK(ws.big.grow(need.big, stream));
+    HIPCHECK(ws.totbuf.grow(need.totbuf, stream));
+    HIPCHECK(ws.pabuf.grow(need.pabuf, stream));
+    return PMX_OK;
 }
 
-// The table arena of a chunk set. (PMX_ARENA_MB is per set; a smaller arena than asked for is slower - more trees walked by one
+// The table arena of a workspace. (A smaller arena than asked for with PMX_ARENA_MB is slower - more trees walked by one
 // wavefront alone - never wrong, so it shrinks when memory is short: several streams each keep a workspace. A size that was
 // accepted after shrinking stands until the workspace is released: asking for the full size again on every call would
 // synchronise, free and fail again each time)
@@ -737,23 +681,21 @@ static int grow_buffers(ScreenWs &ws, const BufferNeeds &need, hipStream_t strea
 // budget, 17 GB at the new one; with a 16 GB arena 200 000 trees found it full and were walked by one wavefront each - the longest for 1.2 M
 // passes, the pass 3.4 s instead of 0.54 s. The part has 288 GB.)
 template <int G>
-static int ensure_arena(ChunkSet &c, hipStream_t stream, hipStream_t side) {
+static int ensure_arena(ScreenWs &ws, hipStream_t stream) {
     size_t arena_want = (size_t)std::max<long>(1, env_long("PMX_ARENA_MB", G >= 32 ? 32768 : 65536)) << 20;
-    if (!c.arena && !std::getenv("PMX_ARENA_MB")) { // first allocation, no explicit size: at most a third of what the device has free
+    if (!ws.arena.ptr && !std::getenv("PMX_ARENA_MB")) { // first allocation, no explicit size: at most a third of what the device has free
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b / 3 < arena_want) {
             arena_want = std::max<size_t>((size_t)1 << 30, (free_b / 3) & ~(((size_t)1 << 20) - 1));
-            c.arena_shrunk_to = arena_want;
+            ws.arena_shrunk_to = arena_want;
         } else {
             (void)hipGetLastError();
         }
     }
     const size_t arena_min = std::min<size_t>((size_t)1 << 30, arena_want);
-    if (c.arena_shrunk_to) arena_want = std::min(arena_want, std::max(c.arena_shrunk_to, arena_min));
-    const size_t asked = arena_want;
-    const int rc = grow(&c.arena, &c.arena_bytes, arena_want, stream, side, arena_min);
-    if (rc) return rc;
-    if (c.arena_bytes < asked) c.arena_shrunk_to = c.arena_bytes;
+    if (ws.arena_shrunk_to) arena_want = std::min(arena_want, std::max(ws.arena_shrunk_to, arena_min));
+    HIPCHECK(ws.arena.grow(arena_want, stream, arena_min));
+    if (ws.arena.bytes < arena_want) ws.arena_shrunk_to = ws.arena.bytes;
     return PMX_OK;
 }
 
@@ -766,20 +708,15 @@ static void prepare_retry(ScreenParams &p, Ctl *ctl, uint32_t *lists, uint32_t c
     p.retry_slot = (uint32_t)(t + 1) & 1u;
 }
 
-// Events, side stream and control blocks of a workspace, on its first call (num_cu is set last: a workspace whose events, stream or
-// control blocks could not be made stays uninitialised).
-static int init_workspace(ScreenWs &ws, int device) {
+// Events and control block of a workspace, on its first call (num_cu is set last: a workspace whose events or control block
+// could not be made stays uninitialised).
+static int init_workspace(ScreenWs &ws, int device, hipStream_t stream) {
     if (ws.num_cu) return PMX_OK;
     auto init = [&]() -> int {
         hipDeviceProp_t prop;
         HIPCHECK(hipGetDeviceProperties(&prop, device));
         for (auto &e : ws.ev) HIPCHECK(hipEventCreate(&e));
-        HIPCHECK(hipStreamCreateWithFlags(&ws.side, hipStreamNonBlocking));
-        for (ChunkSet &c : ws.set) {
-            HIPCHECK(hipMalloc((void **)&c.ctl, sizeof(Ctl)));
-            HIPCHECK(hipEventCreateWithFlags(&c.lig_done, hipEventDisableTiming));
-            HIPCHECK(hipEventCreateWithFlags(&c.tasks_done, hipEventDisableTiming));
-        }
+        HIPCHECK(ws.ctl.grow(sizeof(Ctl), stream));
         ws.num_cu = prop.multiProcessorCount;
         return PMX_OK;
     };
@@ -872,7 +809,7 @@ static int plan_pocket(const pmx_model *model, const pmx_library *lib, const Wei
     if (worst > pl.big_bytes) pl.arena_retries = (int)std::max<long>(1, env_long("PMX_ARENA_RETRIES", 4));
     // chunk: what the arena has to hold at a time are the tables of the chunk's split trees. (Cutting a pocket's pass into more
     // chunks than the arena asks for does not pay: every chunk ends in a dozen rounds with a tail each - 1 M ligands in 8
-    // chunks: 258 ms back to back, 234 ms with the rounds beside the next chunk's ligand kernel, 207 ms in one chunk.)
+    // chunks: 258 ms, 207 ms in one chunk.)
     const long super_dflt = std::max(16384L, (1L << 20) * 8 / std::max(G, 8) / k_scale);
     pl.super = (uint32_t)std::max<long>(1024, std::min<long>(env_long("PMX_SUPER", super_dflt), 1 << 24));
     return PMX_OK;
@@ -882,10 +819,7 @@ template <int G>
 static int score_screen(const pmx_model *const *models, int n_models, const pmx_library *lib, const Weights &W, uint64_t first, uint64_t count,
                         void *scores_dev, bool scores_f64, int32_t *status_dev, hipStream_t stream, ScreenWs &ws) {
     if (count > 0xfffffff0ull) return fail(PMX_ERR_INVALID, "more than 2^32 ligands in one call");
-    {
-        const int irc = init_workspace(ws, lib->device);
-        if (irc) return irc;
-    }
+    // ---- knobs
     const uint32_t flags = (uint32_t)env_long("PMX_TREE_FLAGS", 0);
     // [MI355X] round 6, passes a walk may take before it splits. On the bench library (92 passes per ligand, 7 % of the walks over 384) 384 / 384
     // and 768 / 384 are the same 99.1 ms; on SURVEY 8d-2's own library (800 passes per ligand) 384 sends 57-74 % of the ligands to the arena and
@@ -901,11 +835,14 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
     bool debug_ok = true;
     const bool tails = pair_tails(models, n_models, W); // (term-by-term tails for widely spread type weights, see pair_tails)
 
-    // ---- per pocket: parameters and launch shapes
+    // ---- plan: per pocket, parameters and launch shapes
+    {
+        const int irc = init_workspace(ws, lib->device, stream);
+        if (irc) return irc;
+    }
     std::vector<PocketPlan> plan((size_t)n_models);
     BufferNeeds need;
     uint32_t super_max = 0;
-    bool retry_possible = false;
     for (int m = 0; m < n_models; ++m) {
         PocketPlan &pl = plan[(size_t)m];
         const int rc = plan_pocket<G>(models[m], lib, W, ws.num_cu, stream, pl);
@@ -918,151 +855,105 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
         p.scores = scores_f64 ? reinterpret_cast<float *>(static_cast<double *>(scores_dev) + (size_t)m * count) : static_cast<float *>(scores_dev) + (size_t)m * count;
         p.status = m == 0 ? status_dev : nullptr;
         need.cover(pl.need);
-        retry_possible = retry_possible || pl.arena_retries > 0;
         super_max = std::max(super_max, pl.super);
     }
-    {
-        const int rc = grow_buffers(ws, need, stream);
-        if (rc) return rc;
-    }
-    uint64_t n_chunks = 0;
-    for (const PocketPlan &pl : plan) n_chunks += (count + pl.super - 1) / pl.super;
-    // The rounds go to the side stream when there is something to run them next to. (Not when an arena pass may have to be
-    // retried: the retry's ligand kernels use the large slices, as the next chunk's do.)
-    // [MI355X] history of this switch. With the round-3 search (task rounds = 47 % of a pass, scalar-bound) the rounds beside the
-    // next chunk's ligand kernel gained 3.6 % on the 12.5 M-ligand shard (2.39 s against 2.47 s) and lost wherever chunks were
-    // small (16 pockets: 24.5 s against 22.2 s). With the path-aware bound the rounds are 22 % of a pass and mostly tail: the
-    // same shard takes 2.15 s with them beside the next ligand kernel (which then has half the wave slots) and 1.66 s back to
-    // back. So PMX_OVERLAP = 0 (default): everything on the caller's stream; 1: beside each other within a pocket whose chunks
-    // hold >= 2^19 ligands; 2: always, across pockets as well.
-    const long overlap_mode = env_long("PMX_OVERLAP", 0);
-    uint32_t super_min = ~0u;
-    for (const PocketPlan &pl : plan) super_min = std::min(super_min, pl.super);
-    const bool overlap = n_chunks >= 2 && !retry_possible && overlap_mode != 0 && (overlap_mode >= 2 || super_min >= (1u << 19));
-    const bool overlap_pockets = overlap_mode >= 2;
-    hipStream_t side = overlap ? ws.side : stream;
-    // Arena, task queue and lists: one set - a second one only where the rounds of a chunk run beside the next chunk's ligand kernel
-    // (PMX_OVERLAP, off by default): in order on one stream a chunk is through with them when the next one starts.
-    for (int ci = 0; ci < (overlap ? 2 : 1); ++ci) {
-        ChunkSet &c = ws.set[ci];
-        int rc = ensure_arena<G>(c, stream, ws.side);
-        if (!rc) rc = grow(&c.queue, &c.queue_bytes, (size_t)std::max<long>(1, env_long("PMX_TASKQ_MB", (G >= 32 ? 1024L : 2048L) * std::max(1, G / 8))) << 20, stream, ws.side);
-        if (!rc) rc = grow(&c.lists, &c.lists_bytes, (size_t)super_max * 12, stream, ws.side);
-        if (rc) return rc;
-    }
-    const char *lig_share_env = std::getenv("PMX_LIG_SHARE");
-    const double lig_share = std::min(0.9, std::max(0.1, std::atof(lig_share_env ? lig_share_env : "0.5")));
 
+    // ---- buffers
+    {
+        int rc = grow_buffers(ws, need, stream);
+        if (!rc) rc = ensure_arena<G>(ws, stream);
+        if (rc) return rc;
+        HIPCHECK(ws.queue.grow((size_t)std::max<long>(1, env_long("PMX_TASKQ_MB", (G >= 32 ? 1024L : 2048L) * std::max(1, G / 8))) << 20, stream));
+        HIPCHECK(ws.lists.grow((size_t)super_max * 12, stream));
+    }
+    Ctl *const ctl = ws.ctl.as<Ctl>();
+    uint32_t *const lists = ws.lists.as<uint32_t>();
+    uint8_t *const totbuf = ws.totbuf.as<uint8_t>(), *const pabuf = ws.pabuf.as<uint8_t>();
+
+    // ---- pockets and their chunks
     if (g_profiling) HIPCHECK(hipEventRecord(ws.ev[0], stream));
-    ws.ctl_used[0] = ws.ctl_used[1] = false;
-    ws.set[0].pending = ws.set[1].pending = false;
-    uint64_t seq = 0;
+    ws.ctl_used = false;
     for (int m = 0; m < n_models; ++m) {
-        PocketPlan &pl = plan[(size_t)m];
+        const PocketPlan &pl = plan[(size_t)m];
         ScreenParams p = pl.p;
         const uint32_t super = pl.super;
-        const uint32_t full = pl.waves_per_cu;
-        const uint32_t lig_waves = std::min(full - 1, std::max(1u, (uint32_t)(full * lig_share + 0.5)));
-        for (uint64_t lo = 0; lo < count; lo += super, ++seq) {
-            const bool last_of_call = seq + 1 == n_chunks;
-            // a chunk that has the device to itself: the call's first / last, or (by default) a pocket's first / last
-            const bool first_chunk = seq == 0 || (!overlap_pockets && lo == 0), last_chunk = last_of_call || (!overlap_pockets && lo + super >= count);
-            const int ci = overlap ? (int)(seq & 1) : 0;
-            ChunkSet &c = ws.set[ci];
-            p.lo = (uint32_t)lo;
-            p.hi = (uint32_t)std::min<uint64_t>(count, lo + super);
-            p.ctl = c.ctl;
-            p.arena = c.arena;
-            p.arena_bytes = std::min<unsigned long long>(c.arena_bytes, (1ull << 36) - 4096);
-            p.ovf_list = c.lists;
-            p.carry_list = c.lists + super;
-            p.heavy_list = c.lists + 2 * (size_t)super;
-            p.list_cap = super;
-            p.queue = c.queue;
-            p.qcap = (uint32_t)std::min<size_t>(c.queue_bytes / task_rec_bytes<G>() / kShards, 0x3fffffffu / kShards);
-            p.totbuf = ws.totbuf;
-            p.pabuf = ws.pabuf;
-            // this set's last chunk (two chunks ago) has to be through its rounds
-            if (overlap && c.pending) HIPCHECK(hipStreamWaitEvent(stream, c.tasks_done, 0));
-            if (overlap && !overlap_pockets && lo == 0 && seq > 0 && ws.set[(seq - 1) & 1].pending) // (the rounds of the pocket before)
-                HIPCHECK(hipStreamWaitEvent(stream, ws.set[(seq - 1) & 1].tasks_done, 0));
-            if (g_profiling && last_of_call) HIPCHECK(hipEventRecord(ws.ev[1], stream));
-            ws.ligands_last = p.hi - p.lo;
-            ctl_clear_kernel<<<dim3((sizeof(Ctl) / 4 + 255) / 256), dim3(256), 0, stream>>>(c.ctl, ws.ctl_used[ci] ? 0 : 1);
-            ws.ctl_used[ci] = true;
-            // the first chunk's ligand kernel has the device to itself, the others share it with the rounds of the chunk before
-            const uint32_t lig_grid = (uint32_t)ws.num_cu * ((overlap && !first_chunk) ? lig_waves : full);
-            const uint32_t task_grid = (uint32_t)ws.num_cu * ((overlap && !last_chunk) ? std::min<uint32_t>(pl.task_waves_per_cu, full - lig_waves) : pl.task_waves_per_cu);
-            auto launch = [&](int mode, uint32_t blocks, hipStream_t on) {
-                p.mode = mode;
-                if (debug_kernels) debug_ok &= pmx_debug::launch_ligand(G, exact, tails, blocks, pl.lds, on, &p, sizeof p);
-                else if (tails) ligand_kernel<G, false, true><<<dim3(blocks), dim3(64), pl.lds, on>>>(p);
-                else ligand_kernel<G, false, false><<<dim3(blocks), dim3(64), pl.lds, on>>>(p);
-            };
+        const uint32_t lig_grid = (uint32_t)ws.num_cu * pl.waves_per_cu, task_grid = (uint32_t)ws.num_cu * pl.task_waves_per_cu;
+        p.ctl = ctl;
+        p.arena = ws.arena.as<uint8_t>();
+        p.arena_bytes = std::min<unsigned long long>(ws.arena.bytes, (1ull << 36) - 4096);
+        p.ovf_list = lists;
+        p.carry_list = lists + super;
+        p.heavy_list = lists + 2 * (size_t)super;
+        p.list_cap = super;
+        p.queue = ws.queue.as<uint8_t>();
+        p.qcap = (uint32_t)std::min<size_t>(ws.queue.bytes / task_rec_bytes<G>() / kShards, 0x3fffffffu / kShards);
+        p.totbuf = totbuf; // (the ligand kernel's halves; rounds_and_finalize switches to the task kernel's and back)
+        p.pabuf = pabuf;
+        auto launch = [&](int mode, uint32_t blocks) {
+            p.mode = mode;
+            if (debug_kernels) debug_ok &= pmx_debug::launch_ligand(G, exact, tails, blocks, pl.lds, stream, &p, sizeof p);
+            else if (tails) ligand_kernel<G, false, true><<<dim3(blocks), dim3(64), pl.lds, stream>>>(p);
+            else ligand_kernel<G, false, false><<<dim3(blocks), dim3(64), pl.lds, stream>>>(p);
+        };
+        // the subtrees the over-budget walkers queued, and the ones those queue in turn: a fixed number of rounds, each a snapshot of
+        // the queue and one persistent launch (an empty round exits at once); the last round walks everything to its end
+        auto rounds_and_finalize = [&]() {
+            if (!totals_in_lds<G>()) p.totbuf = totbuf + ws.totbuf.bytes / 2;
+            if (pabuf) p.pabuf = pabuf + ws.pabuf.bytes / 2;
+            for (int r = 0; r < rounds; ++r) {
+                // Late rounds hold few subtrees (fewer than wavefronts): what they cost is their longest walk, i.e. the budget. Halving
+                // it from round PMX_TASK_DECAY_FROM on spreads a deep subtree over the idle wavefronts sooner.
+                p.budget = r < task_decay_from ? task_budget : std::max<uint32_t>(task_budget_min, task_budget >> std::min(r - task_decay_from + 1, 16));
+                p.last_round = r + 1 == rounds ? 1u : 0u;
+                round_kernel<<<dim3(1), dim3(64), 0, stream>>>(ctl, p.qcap);
+                if (debug_kernels) debug_ok &= pmx_debug::launch_task(G, task_grid, pl.lds, stream, &p, sizeof p);
+                else task_kernel<G><<<dim3(task_grid), dim3(64), pl.lds, stream>>>(p);
+            }
+            finalize_kernel<G><<<dim3((super + 255) / 256), dim3(256), 0, stream>>>(p);
             p.last_round = 0;
             p.budget = lig_budget;
+            p.totbuf = totbuf;
+            p.pabuf = pabuf;
+        };
+        for (uint64_t lo = 0; lo < count; lo += super) {
+            const bool last_of_call = m + 1 == n_models && lo + super >= count;
+            p.lo = (uint32_t)lo;
+            p.hi = (uint32_t)std::min<uint64_t>(count, lo + super);
+            if (g_profiling && last_of_call) HIPCHECK(hipEventRecord(ws.ev[1], stream));
+            ws.ligands_last = p.hi - p.lo;
+            ctl_clear_kernel<<<dim3((sizeof(Ctl) / 4 + 255) / 256), dim3(256), 0, stream>>>(ctl, ws.ctl_used ? 0 : 1);
+            ws.ctl_used = true;
             // every ligand whose tables fit a slice
-            p.slices = ws.slices;
+            p.slices = ws.slices.as<uint8_t>();
             p.slice_bytes = pl.slice_bytes;
-            launch(0, lig_grid, stream);
+            launch(0, lig_grid);
             // the others with large slices (fewer wavefronts)
-            p.slices = ws.big;
+            p.slices = ws.big.as<uint8_t>();
             p.slice_bytes = pl.big_bytes;
-            launch(1, std::min(pl.big_grid, lig_grid), stream);
+            launch(1, std::min(pl.big_grid, lig_grid));
             // and what exceeds those from the arena; ligands that find it full (of the tables of over-budget trees, or of each
             // other) are listed in the storage of the overflow list, which is done with
-            p.retry_out = c.lists;
+            p.retry_out = lists;
             p.retry_slot = 0;
-            launch(2, std::min(pl.big_grid, lig_grid), stream);
-            if (g_profiling && last_of_call) HIPCHECK(hipEventRecord(ws.ev[2], stream));
-            if (overlap) {
-                HIPCHECK(hipEventRecord(c.lig_done, stream));
-                HIPCHECK(hipStreamWaitEvent(side, c.lig_done, 0));
+            launch(2, std::min(pl.big_grid, lig_grid));
+            if (g_profiling && last_of_call) {
+                HIPCHECK(hipEventRecord(ws.ev[2], stream));
+                HIPCHECK(hipEventRecord(ws.ev[4], stream));
             }
-            if (g_profiling && last_of_call) HIPCHECK(hipEventRecord(ws.ev[4], side));
-            // the subtrees the over-budget walkers queued, and the ones those queue in turn: a fixed number of rounds, each a snapshot of
-            // the queue and one persistent launch (an empty round exits at once); the last round walks everything to its end
-            if (!totals_in_lds<G>()) p.totbuf = ws.totbuf + ws.totbuf_bytes / 2;
-            if (ws.pabuf) p.pabuf = ws.pabuf + ws.pabuf_bytes / 2;
-            auto rounds_and_finalize = [&]() {
-                for (int r = 0; r < rounds; ++r) {
-                    // Late rounds hold few subtrees (fewer than wavefronts): what they cost is their longest walk, i.e. the budget. Halving
-                    // it from round PMX_TASK_DECAY_FROM on spreads a deep subtree over the idle wavefronts sooner.
-                    p.budget = r < task_decay_from ? task_budget : std::max<uint32_t>(task_budget_min, task_budget >> std::min(r - task_decay_from + 1, 16));
-                    p.last_round = r + 1 == rounds ? 1u : 0u;
-                    round_kernel<<<dim3(1), dim3(64), 0, side>>>(c.ctl, p.qcap);
-                    if (debug_kernels) debug_ok &= pmx_debug::launch_task(G, task_grid, pl.lds, side, &p, sizeof p);
-                    else task_kernel<G><<<dim3(task_grid), dim3(64), pl.lds, side>>>(p);
-                }
-                finalize_kernel<G><<<dim3((super + 255) / 256), dim3(256), 0, side>>>(p);
-                p.last_round = 0;
-                p.budget = lig_budget;
-            };
             rounds_and_finalize();
             // Ligands the arena pass had no room for, with the arena to themselves (only models and libraries whose largest tables
-            // exceed a large slice have such passes; `side` is the caller's stream then), the last pass reporting what still does not fit.
+            // exceed a large slice have such passes), the last pass reporting what still does not fit.
             for (int t = 0; t < pl.arena_retries; ++t) {
-                prepare_retry(p, c.ctl, c.lists, super, t, pl.arena_retries, side);
-                p.totbuf = ws.totbuf;
-                p.pabuf = ws.pabuf;
-                launch(3, std::min(pl.big_grid, lig_grid), side);
-                if (!totals_in_lds<G>()) p.totbuf = ws.totbuf + ws.totbuf_bytes / 2;
-                if (ws.pabuf) p.pabuf = ws.pabuf + ws.pabuf_bytes / 2;
+                prepare_retry(p, ctl, lists, super, t, pl.arena_retries, stream);
+                launch(3, std::min(pl.big_grid, lig_grid));
                 rounds_and_finalize();
             }
             p.retry_in = nullptr;
-            if (g_profiling && last_of_call) HIPCHECK(hipEventRecord(ws.ev[5], side));
-            if (overlap) {
-                HIPCHECK(hipEventRecord(c.tasks_done, side));
-                c.pending = true;
-            }
+            if (g_profiling && last_of_call) HIPCHECK(hipEventRecord(ws.ev[5], stream));
         }
     }
     HIPCHECK(hipGetLastError());
     if (!debug_ok) return fail(PMX_ERR_INVALID, "the validation kernels (pmx_screen_debug.hip) do not match this build's parameter block");
-    if (overlap) // the call ends on the caller's stream
-        for (ChunkSet &c : ws.set)
-            if (c.pending) HIPCHECK(hipStreamWaitEvent(stream, c.tasks_done, 0));
     if (g_profiling) HIPCHECK(hipEventRecord(ws.ev[3], stream));
     ws.ev_valid = g_profiling != 0;
     ws.last_stream = stream;
@@ -1080,15 +971,14 @@ static int screen_stats(pmx_score_stats *out) {
     unsigned long long st[kStatWords] = {0};
     std::vector<unsigned char> host(sizeof(Ctl));
     *out = pmx_score_stats{};
-    for (int ci = 0; ci < 2; ++ci) {
-        if (!w->ctl_used[ci]) continue;
-        HIPCHECK(hipMemcpy(host.data(), w->set[ci].ctl, sizeof(Ctl), hipMemcpyDeviceToHost));
+    if (w->ctl_used) {
+        HIPCHECK(hipMemcpy(host.data(), w->ctl.ptr, sizeof(Ctl), hipMemcpyDeviceToHost));
         const Ctl *c = reinterpret_cast<const Ctl *>(host.data());
         for (int sh = 0; sh < kScreenStatShards; ++sh)
             for (int i = 0; i < kStatWords; ++i) st[i] = (i == 5) ? std::max(st[i], c->stats[sh][i]) : st[i] + c->stats[sh][i];
-        out->queue_overflow |= c->qflag;
-        out->arena_bytes = std::max<uint64_t>(out->arena_bytes, c->arena_top);
-        out->arena_capacity = std::max<uint64_t>(out->arena_capacity, w->set[ci].arena_bytes);
+        out->queue_overflow = c->qflag;
+        out->arena_bytes = c->arena_top;
+        out->arena_capacity = w->arena.bytes;
     }
     out->n_frames = st[0];
     out->n_passes = st[1];
@@ -1199,6 +1089,7 @@ extern "C" int pmx_score_f64(const pmx_model *model, const pmx_library *lib, con
 // grown on demand and kept between calls, which is what a screening loop wants and what a long-lived host program that
 // is done screening does not.
 int pmx_topk_release(int device);
+int pmx_pack_release(int device);
 extern "C" int pmx_release_workspaces(int device) {
     HIPCHECK(hipSetDevice(device));
     HIPCHECK(hipDeviceSynchronize());
@@ -1220,7 +1111,8 @@ extern "C" int pmx_release_workspaces(int device) {
         w->free_buffers();
         w->released = true;
     }
-    return pmx_topk_release(device);
+    const int rc = pmx_topk_release(device);
+    return rc ? rc : pmx_pack_release(device);
 }
 
 // error hook for pmx_topk.hip (keeps the thread-local message in one translation unit)
@@ -1231,48 +1123,49 @@ int pmx_topk_fail(int code, const char *msg) { return fail(code, "%s", msg); }
 // retries - and each is walked to its end by one wavefront of the explain kernel: no budget, no task queue.
 template <int G>
 static int explain_screen(const pmx_model *model, const pmx_library *lib, const Weights &W, const pmx_xpl::Args &a, hipStream_t stream, ScreenWs &ws) {
-    int rc = init_workspace(ws, lib->device);
+    int rc = init_workspace(ws, lib->device, stream);
     if (rc) return rc;
     const bool tails = pair_tails(&model, 1, W); // (as pmx_score / pmx_score_f64 decide it for this model)
     PocketPlan pl;
     rc = plan_pocket<G>(model, lib, W, ws.num_cu, stream, pl);
     if (!rc) rc = grow_buffers(ws, pl.need, stream);
-    ChunkSet &c = ws.set[0];
-    if (!rc && !c.arena) rc = ensure_arena<G>(c, stream, ws.side); // (an arena made by pmx_score is taken as it is)
-    if (!rc) rc = grow(&c.lists, &c.lists_bytes, (size_t)a.n * 12, stream, ws.side);
+    if (!rc && !ws.arena.ptr) rc = ensure_arena<G>(ws, stream); // (an arena made by pmx_score is taken as it is)
     if (rc) return rc;
-    if (!ws.xctl) HIPCHECK(hipMalloc((void **)&ws.xctl, sizeof(Ctl)));
+    HIPCHECK(ws.lists.grow((size_t)a.n * 12, stream));
+    HIPCHECK(ws.xctl.grow(sizeof(Ctl), stream));
+    Ctl *const xctl = ws.xctl.as<Ctl>();
+    uint32_t *const lists = ws.lists.as<uint32_t>();
     ScreenParams &p = pl.p;
     p.flags = PMX_SCORES_F64; // (never PMX_TREE_FLAGS)
     p.status = a.status;
-    p.ctl = ws.xctl;
-    p.arena = c.arena;
-    p.arena_bytes = std::min<unsigned long long>(c.arena_bytes, (1ull << 36) - 4096);
-    p.ovf_list = c.lists;
-    p.carry_list = c.lists + a.n;
-    p.heavy_list = c.lists + 2 * (size_t)a.n;
+    p.ctl = xctl;
+    p.arena = ws.arena.as<uint8_t>();
+    p.arena_bytes = std::min<unsigned long long>(ws.arena.bytes, (1ull << 36) - 4096);
+    p.ovf_list = lists;
+    p.carry_list = lists + a.n;
+    p.heavy_list = lists + 2 * (size_t)a.n;
     p.list_cap = a.n;
-    p.pabuf = ws.pabuf;
-    p.totbuf = ws.totbuf;
+    p.pabuf = ws.pabuf.as<uint8_t>();
+    p.totbuf = ws.totbuf.as<uint8_t>();
     p.hi = a.n;
 
     pmx_xpl::launch_init(a, stream);
-    ctl_clear_kernel<<<dim3((sizeof(Ctl) / 4 + 255) / 256), dim3(256), 0, stream>>>(ws.xctl, 1);
+    ctl_clear_kernel<<<dim3((sizeof(Ctl) / 4 + 255) / 256), dim3(256), 0, stream>>>(xctl, 1);
     const size_t lds = pmx_xpl::lds_bytes(G, model->dm.K, (int)p.max_nodes);
     const uint32_t full = (uint32_t)ws.num_cu * pl.waves_per_cu;
     bool ok = true;
     auto launch = [&](int mode, uint32_t blocks) { ok &= pmx_xpl::launch(G, tails, mode, std::max(1u, blocks), (unsigned)lds, stream, &p, sizeof p, a); };
-    p.slices = ws.slices;
+    p.slices = ws.slices.as<uint8_t>();
     p.slice_bytes = pl.slice_bytes;
     launch(0, std::min(full, a.n));
-    p.slices = ws.big;
+    p.slices = ws.big.as<uint8_t>();
     p.slice_bytes = pl.big_bytes;
     launch(1, std::min(pl.big_grid, full));
-    p.retry_out = c.lists;
+    p.retry_out = lists;
     p.retry_slot = 0;
     launch(2, std::min(pl.big_grid, full));
     for (int t = 0; t < pl.arena_retries; ++t) {
-        prepare_retry(p, ws.xctl, c.lists, a.n, t, pl.arena_retries, stream);
+        prepare_retry(p, xctl, lists, a.n, t, pl.arena_retries, stream);
         launch(3, std::min(pl.big_grid, full));
     }
     pmx_xpl::launch_fixup(a, stream);

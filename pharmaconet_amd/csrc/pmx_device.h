@@ -1,4 +1,5 @@
-// pmx_device.h - device-side layouts shared by the kernels of libpmx (gfx950 only), and the host's dispatch on their lane count.
+// pmx_device.h - device-side layouts shared by the kernels of libpmx (gfx950 only), and two host-only helpers: the dispatch on
+// their lane count (with_lanes) and the owner of a cached device buffer (DevBuf).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -78,5 +79,42 @@ inline bool with_lanes(int G, F &&f) {
     default: return false;
     }
 }
+
+// Host: a device buffer that is kept from call to call and has this one owner. It only ever grows. Work queued on `stream` may still
+// use the old buffer, so a reallocation waits for that stream first. min_bytes: the buffer is a cache (the table arena) - a smaller
+// one is slower, never wrong: the size asked for is halved on out-of-memory, down to min_bytes, and `bytes` says what it got.
+// No destructor: buffers are freed by release(), while the HIP runtime is alive and the right device is current.
+struct DevBuf {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    template <class T>
+    T *as() const { return static_cast<T *>(ptr); }
+    hipError_t grow(size_t want, hipStream_t stream, size_t min_bytes = 0) {
+        if (bytes >= want) return hipSuccess;
+        if (ptr) {
+            const hipError_t e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) return e;
+            release();
+        }
+        for (;;) {
+            const hipError_t e = hipMalloc(&ptr, want);
+            if (e == hipSuccess) break;
+            (void)hipGetLastError();
+            ptr = nullptr;
+            if (e != hipErrorOutOfMemory || min_bytes == 0 || want / 2 < min_bytes) return e;
+            want /= 2;
+        }
+        bytes = want;
+        return hipSuccess;
+    }
+    void release() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+    }
+};
 
 } // namespace pmx

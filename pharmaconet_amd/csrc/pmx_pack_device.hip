@@ -28,6 +28,7 @@
 #include <mutex>
 
 #include "pmx.h"
+#include "pmx_device.h"
 
 int pmx_topk_fail(int code, const char *msg); // error hook in pmx_api.hip
 
@@ -737,27 +738,17 @@ __global__ void close_offsets_kernel(const uint64_t *sizes, uint64_t *offsets, u
     if (threadIdx.x == 0 && blockIdx.x == 0) offsets[n] = n ? offsets[n - 1] + sizes[n - 1] : 0;
 }
 
-// Work buffers (descriptors, sizes, scan scratch) kept per device from call to call; a call holds the lock while it runs.
+// Work buffers (descriptors, sizes, scan scratch) kept from call to call, one set per device: a call touches its own device's
+// entry only, and holds that entry's lock while it runs.
 struct PackWork {
     std::mutex mu;
-    int device = -1;
-    void *desc = nullptr, *sizes = nullptr, *scan = nullptr, *status = nullptr;
-    size_t desc_bytes = 0, sizes_bytes = 0, scan_bytes = 0, status_bytes = 0;
+    pmx::DevBuf desc, sizes, scan, status;
     hipEvent_t done = nullptr;     // behind the last call's record writer (it reads `desc` after the call has returned)
     hipStream_t last = nullptr;    // the stream that call was made on
     bool pending = false;
 };
-PackWork g_work;
-
-bool grow(void **p, size_t *have, size_t need) {
-    if (*have >= need) return true;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    if (hipMalloc(p, need) != hipSuccess) return false;
-    *have = need;
-    return true;
-}
+constexpr int kMaxDevices = 64;
+PackWork g_work[kMaxDevices];
 
 } // namespace
 
@@ -773,38 +764,29 @@ extern "C" int pmx_pack_features_device(const pmx_feature_batch *b, int device, 
         return PMX_OK;
     }
     if (n > 0x7fffffffull) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_pack_features_device: more than 2^31 - 1 molecules in one call");
-    std::lock_guard<std::mutex> lock(g_work.mu);
-    if (g_work.device != device) { // (buffers belong to the device they were allocated on)
-        if (g_work.device >= 0) {
-            (void)hipSetDevice(g_work.device);
-            (void)hipFree(g_work.desc), (void)hipFree(g_work.sizes), (void)hipFree(g_work.scan), (void)hipFree(g_work.status);
-            (void)hipSetDevice(device);
-        }
-        g_work.desc = g_work.sizes = g_work.scan = g_work.status = nullptr;
-        g_work.desc_bytes = g_work.sizes_bytes = g_work.scan_bytes = g_work.status_bytes = 0;
-        if (g_work.done) (void)hipEventDestroy(g_work.done);
-        g_work.done = nullptr;
-        g_work.pending = false;
-        g_work.device = device;
-    }
-    // The buffers are shared by all calls: one made on another stream than the last starts behind that call's record writer.
-    if (!g_work.done && hipEventCreateWithFlags(&g_work.done, hipEventDisableTiming) != hipSuccess) return pmx_topk_fail(PMX_ERR_HIP, "pmx_pack_features_device: hipEventCreate failed");
-    if (g_work.pending && g_work.last != stream && hipStreamWaitEvent(stream, g_work.done, 0) != hipSuccess)
+    if (device < 0 || device >= kMaxDevices) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_pack_features_device: device index out of range");
+    PackWork &w = g_work[device];
+    std::lock_guard<std::mutex> lock(w.mu);
+    // The buffers are shared by all calls on the device: one made on another stream than the last starts behind that call's record writer.
+    if (!w.done && hipEventCreateWithFlags(&w.done, hipEventDisableTiming) != hipSuccess) return pmx_topk_fail(PMX_ERR_HIP, "pmx_pack_features_device: hipEventCreate failed");
+    if (w.pending && w.last != stream && hipStreamWaitEvent(stream, w.done, 0) != hipSuccess)
         return pmx_topk_fail(PMX_ERR_HIP, "pmx_pack_features_device: hipStreamWaitEvent failed");
     size_t scan_need = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_need, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)n, stream);
-    if (!grow(&g_work.desc, &g_work.desc_bytes, n * sizeof(PackDesc)) || !grow(&g_work.sizes, &g_work.sizes_bytes, n * 8) ||
-        !grow(&g_work.scan, &g_work.scan_bytes, scan_need ? scan_need : 8) || (!status_out_dev && !grow(&g_work.status, &g_work.status_bytes, n * 4)))
-        return pmx_topk_fail(PMX_ERR_OOM, "pmx_pack_features_device: out of device memory");
+    hipError_t e = w.desc.grow(n * sizeof(PackDesc), stream);
+    if (e == hipSuccess) e = w.sizes.grow(n * 8, stream);
+    if (e == hipSuccess) e = w.scan.grow(scan_need ? scan_need : 8, stream);
+    if (e == hipSuccess && !status_out_dev) e = w.status.grow(n * 4, stream);
+    if (e != hipSuccess) return pmx_topk_fail(e == hipErrorOutOfMemory ? PMX_ERR_OOM : PMX_ERR_HIP, hipGetErrorString(e));
     DevBatch d{n, b->atom_off, b->atomic_num, b->nbr_off, b->nbr, b->feat_off, b->feat_type, b->feat_flags, b->feat_atom_off, b->feat_atoms,
                b->feat_center_off, b->feat_centers, b->n_conf, b->pos_off, b->positions};
-    PackDesc *desc = static_cast<PackDesc *>(g_work.desc);
-    uint64_t *sizes = static_cast<uint64_t *>(g_work.sizes);
-    int32_t *status = status_out_dev ? status_out_dev : static_cast<int32_t *>(g_work.status);
+    PackDesc *desc = w.desc.as<PackDesc>();
+    uint64_t *sizes = w.sizes.as<uint64_t>();
+    int32_t *status = status_out_dev ? status_out_dev : w.status.as<int32_t>();
     graph_wave_kernel<<<dim3((unsigned)n), dim3(64), 0, stream>>>(d, desc, sizes, status);
     graph_kernel<<<dim3((unsigned)n), dim3(64), 0, stream>>>(d, desc, sizes, status); // (a block whose molecule is done returns at once)
-    size_t scan_bytes = g_work.scan_bytes;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(g_work.scan, scan_bytes, sizes, offsets_out_dev, (int)n, stream);
+    size_t scan_bytes = w.scan.bytes;
+    e = hipcub::DeviceScan::ExclusiveSum(w.scan.ptr, scan_bytes, sizes, offsets_out_dev, (int)n, stream);
     if (e == hipSuccess) {
         close_offsets_kernel<<<1, 64, 0, stream>>>(sizes, offsets_out_dev, n);
         e = hipGetLastError();
@@ -818,9 +800,22 @@ extern "C" int pmx_pack_features_device(const pmx_feature_batch *b, int device, 
     if (total > data_cap) return pmx_topk_fail(PMX_ERR_INVALID, "data_out too small (data_bytes holds the size needed)");
     record_kernel<<<dim3((unsigned)n), dim3(64), 0, stream>>>(d, desc, offsets_out_dev, data_out_dev);
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(g_work.done, stream);
+    if (e == hipSuccess) e = hipEventRecord(w.done, stream);
     if (e != hipSuccess) return pmx_topk_fail(PMX_ERR_HIP, hipGetErrorString(e));
-    g_work.last = stream;
-    g_work.pending = true;
+    w.last = stream;
+    w.pending = true;
+    return PMX_OK;
+}
+
+// pmx_release_workspaces: the packer's buffers of `device` (the device is current).
+int pmx_pack_release(int device) {
+    if (device < 0 || device >= kMaxDevices) return PMX_OK;
+    PackWork &w = g_work[device];
+    std::lock_guard<std::mutex> lock(w.mu); // a call that is packing finishes first
+    (void)hipDeviceSynchronize();           // ... and the record writer it left behind
+    for (pmx::DevBuf *b : {&w.desc, &w.sizes, &w.scan, &w.status}) b->release();
+    if (w.done) (void)hipEventDestroy(w.done);
+    w.done = nullptr;
+    w.pending = false;
     return PMX_OK;
 }

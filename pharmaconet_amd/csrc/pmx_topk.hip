@@ -20,6 +20,7 @@
 #include <utility>
 
 #include "pmx.h"
+#include "pmx_device.h"
 
 int pmx_topk_fail(int code, const char *msg); // defined in pmx_api.hip
 
@@ -158,11 +159,8 @@ __global__ void sel_sort_emit(const float *scores, const uint64_t *index, uint64
 // Workspace per (device, stream), of fixed size (it depends on the largest k only), allocated once under the lock; the
 // lock is held while a call enqueues, so two host threads ranking on one stream are serialised like the stream itself.
 namespace {
-struct TopkWs {
-    unsigned char *buf = nullptr;
-};
 constexpr size_t kWsBytes = 256 + kBins * 4 + (size_t)kMaxK * 8;
-std::map<std::pair<int, hipStream_t>, TopkWs> g_topk_ws;
+std::map<std::pair<int, hipStream_t>, pmx::DevBuf> g_topk_ws;
 std::mutex g_topk_mu;
 } // namespace
 
@@ -175,11 +173,12 @@ extern "C" int pmx_topk(const float *scores_dev, const uint64_t *index_dev, uint
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     TK_CHECK(hipSetDevice(device));
     std::lock_guard<std::mutex> lock(g_topk_mu);
-    TopkWs &ws = g_topk_ws[std::make_pair(device, stream)];
-    if (!ws.buf) TK_CHECK(hipMalloc((void **)&ws.buf, kWsBytes));
-    SelState *st = reinterpret_cast<SelState *>(ws.buf);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(ws.buf + 256);
-    uint2 *cand = reinterpret_cast<uint2 *>(ws.buf + 256 + kBins * 4);
+    pmx::DevBuf &ws = g_topk_ws[std::make_pair(device, stream)];
+    TK_CHECK(ws.grow(kWsBytes, stream));
+    unsigned char *buf = ws.as<unsigned char>();
+    SelState *st = reinterpret_cast<SelState *>(buf);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(buf + 256);
+    uint2 *cand = reinterpret_cast<uint2 *>(buf + 256 + kBins * 4);
     uint32_t m = 2;
     while (m < (uint32_t)k) m <<= 1;
     const uint32_t n32 = (uint32_t)n;
@@ -208,7 +207,7 @@ int pmx_topk_release(int device) {
     std::lock_guard<std::mutex> lock(g_topk_mu);
     for (auto it = g_topk_ws.begin(); it != g_topk_ws.end();) {
         if (it->first.first == device) {
-            if (it->second.buf) (void)hipFree(it->second.buf);
+            it->second.release();
             it = g_topk_ws.erase(it);
         } else {
             ++it;
@@ -224,9 +223,7 @@ int pmx_topk_release(int device) {
 struct pmx_comm {
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1, device = 0;
-    float *gs = nullptr;     // [nranks * kcap]
-    uint64_t *gi = nullptr;
-    int kcap = 0;
+    pmx::DevBuf gs, gi; // float, uint64 [nranks * k], grown to the largest k asked for
 };
 
 extern "C" int pmx_comm_unique_id(char id_out[PMX_COMM_ID_BYTES]) {
@@ -275,8 +272,8 @@ extern "C" int pmx_comm_destroy(pmx_comm *c) {
     if (!c) return PMX_OK;
     (void)hipSetDevice(c->device);
     if (c->comm) (void)ncclCommDestroy(c->comm);
-    if (c->gs) (void)hipFree(c->gs);
-    if (c->gi) (void)hipFree(c->gi);
+    c->gs.release();
+    c->gi.release();
     delete c;
     return PMX_OK;
 }
@@ -287,25 +284,15 @@ extern "C" int pmx_topk_allgather(pmx_comm *c, const float *scores_k_dev, const 
     if (k == 0) return PMX_OK;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     TK_CHECK(hipSetDevice(c->device));
-    if (c->kcap < k) {
-        if (c->gs) {
-            TK_CHECK(hipStreamSynchronize(stream));
-            (void)hipFree(c->gs);
-            (void)hipFree(c->gi);
-            c->gs = nullptr;
-            c->gi = nullptr;
-        }
-        TK_CHECK(hipMalloc((void **)&c->gs, (size_t)c->nranks * k * sizeof(float)));
-        TK_CHECK(hipMalloc((void **)&c->gi, (size_t)c->nranks * k * sizeof(uint64_t)));
-        c->kcap = k;
-    }
+    TK_CHECK(c->gs.grow((size_t)c->nranks * k * sizeof(float), stream));
+    TK_CHECK(c->gi.grow((size_t)c->nranks * k * sizeof(uint64_t), stream));
     ncclResult_t r = ncclGroupStart();
-    if (r == ncclSuccess) r = ncclAllGather(scores_k_dev, c->gs, (size_t)k, ncclFloat32, c->comm, stream);
-    if (r == ncclSuccess) r = ncclAllGather(index_k_dev, c->gi, (size_t)k, ncclUint64, c->comm, stream);
+    if (r == ncclSuccess) r = ncclAllGather(scores_k_dev, c->gs.ptr, (size_t)k, ncclFloat32, c->comm, stream);
+    if (r == ncclSuccess) r = ncclAllGather(index_k_dev, c->gi.ptr, (size_t)k, ncclUint64, c->comm, stream);
     if (r == ncclSuccess) r = ncclGroupEnd();
     if (r != ncclSuccess) return pmx_topk_fail(PMX_ERR_HIP, ncclGetErrorString(r));
     // ranks hold contiguous ascending shards, so position order in the gathered array is global index order: ties on the score
     // go by position = by global index; NaN entries (unsupported ligands, real indices) rank after every real score, and
     // padding entries (index UINT64_MAX, from ranks with fewer than k ligands) after those
-    return pmx_topk(c->gs, c->gi, (uint64_t)c->nranks * (uint64_t)k, 0, k, out_scores_dev, out_index_dev, c->device, stream_);
+    return pmx_topk(c->gs.as<float>(), c->gi.as<uint64_t>(), (uint64_t)c->nranks * (uint64_t)k, 0, k, out_scores_dev, out_index_dev, c->device, stream_);
 }

@@ -82,12 +82,16 @@ class DeviceLibrary:
     """A packed ligand library resident in HBM (upload once, score against many models / weights)."""
 
     def __init__(self, library: PackedLibrary, device=None):
-        lib = _ffi.load()
         self.device = _device_index(device)
         offsets = np.ascontiguousarray(library.offsets, dtype=np.uint64)
         data = np.ascontiguousarray(library.data, dtype=np.uint8)
         self._n_conf = library.headers()[:, 1].copy() if len(library) else np.zeros(0, np.uint16)  # (what `explain` cuts its rows to)
         view = _ffi.LibraryView(len(library), offsets.ctypes.data, data.ctypes.data if data.size else None, 0)
+        self._upload(view)
+
+    def _upload(self, view) -> None:
+        """pmx_library_upload of `view` on self.device: the handle and what the library says about itself."""
+        lib = _ffi.load()
         handle = ctypes.c_void_p()
         _ffi.check(lib.pmx_library_upload(ctypes.byref(view), self.device, ctypes.byref(handle)))
         self.handle = handle
@@ -106,7 +110,6 @@ class DeviceLibrary:
         """A library already in device memory: `offsets` int64/uint64 [N + 1] and `data` uint8 torch tensors - copied, or with `adopt` used in
         place (the tensors are kept alive by the object and must not be written to while it lives)."""
         torch = _torch()
-        lib = _ffi.load()
         self = cls.__new__(cls)
         self.device = _device_index(device if device is not None else offsets.device)
         torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()  # (pmx_library_upload reads a complete view, on the default stream)
@@ -116,18 +119,7 @@ class DeviceLibrary:
                 raise ValueError("adopted buffers must be contiguous")
             self._adopted = (offsets, data)
         view = _ffi.LibraryView(int(offsets.numel()) - 1, offsets.data_ptr(), data.data_ptr(), 2 if adopt else 1)
-        handle = ctypes.c_void_p()
-        _ffi.check(lib.pmx_library_upload(ctypes.byref(view), self.device, ctypes.byref(handle)))
-        self.handle = handle
-        info = _ffi.LibraryInfo()
-        _ffi.check(lib.pmx_library_info_get(self.handle, ctypes.byref(info)))
-        self.num_ligands = int(info.n_ligands)
-        self.num_bytes = int(info.n_bytes)
-        self.total_conformers = int(info.total_conformers)
-        self.max_nodes = int(info.max_nodes)
-        self.max_conformers = int(info.max_conformers)
-        self.max_clusters = int(info.max_clusters)
-        self.num_unsupported = int(info.n_unsupported)
+        self._upload(view)
         return self
 
     @classmethod

@@ -252,8 +252,7 @@ def test_scores_do_not_depend_on_how_the_work_is_cut(monkeypatch):
     assert stats_default["n_tasks"] > 0  # the default run does split trees
     for env in (
         {"PMX_SUPER": "4001"},                       # 8 super-chunks: control block, queue and arena restart eight times
-        {"PMX_SUPER": "4001", "PMX_OVERLAP": "2"},   # ... with every chunk's task rounds on the side stream beside the next chunk's ligand kernel
-        {"PMX_SUPER": "7000", "PMX_OVERLAP": "2", "PMX_LIG_SHARE": "0.3", "PMX_BUDGET": "32"},
+        {"PMX_SUPER": "7000", "PMX_BUDGET": "32"},    # ... five, with trees split early: every chunk's rounds and queue are busy
         {"PMX_WAVES_PER_CU": "2"},                   # few persistent wavefronts: each builds and walks many ligands
         {"PMX_SLICE_KB": "8"},                       # most tables overflow the slices: large-slice pass
         {"PMX_SLICE_KB": "8", "PMX_BIG_SLICE_MB": "1", "PMX_BIG_TOTAL_MB": "64"},
