@@ -358,7 +358,7 @@ typedef struct {
     uint64_t ticks_scan, ticks_tables, ticks_bounds, ticks_walk, ticks_alive; /* s_memtime ticks summed over wavefronts, by phase */
     uint64_t n_exact_values;    /* self-table items evaluated term by term because their cell of the tabulated function is not accurate relative
                                    to the function's own (tail) value there, per lane */
-    uint64_t dbg[8];            /* walker counters of instrumented builds (-DPMX_COUNTERS, see csrc/pmx_screen.hip walk()); 0 otherwise */
+    uint64_t dbg[8];            /* walker counters of instrumented builds (-DPMX_COUNTERS, _TABLE_TICKS, _WALK_TICKS, _TABLE_FILL: see the list in csrc/pmx_screen_tables.h); 0 otherwise */
     uint64_t n_path_bounds, n_path_drops; /* children tested against the bound their actual path gives (path_bound()), and dropped by it */
     uint64_t n_dead_entries;    /* pair-table entries settled as -1 without computing their items: more than half of their node pairs lie
                                    outside every 2-sigma window of the two model clusters, for every conformer */

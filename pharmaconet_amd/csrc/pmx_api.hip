@@ -76,7 +76,7 @@ struct pmx_model {
     DevModel dm;
     void *blob;
     uint8_t node_type[PMX_MAX_MODEL_NODES]; // host copy
-    // node subsets and tabulated pair functions (pmx_screen.hip)
+    // node subsets and tabulated pair functions (pmx_screen_layout.h FnTable, pmx_screen_tables.h fn_build_kernel)
     uint32_t NS = 0, NF = 0, ncell = 0;
     float h = 0.f;
     uint16_t *sidtab = nullptr;  // device [K * 128]
@@ -726,7 +726,7 @@ static int init_workspace(ScreenWs &ws, int device, hipStream_t stream) {
 }
 
 // Type weights further apart than PMX_TAILS_RATIO (default 8 = the ratio of the reference's own defaults, graph_match.py:32-40: any override that spreads the weights further takes the exact tails): pair items
-// evaluate rough cells term by term like self items do (item_finish<TAILS>, pmx_screen.hip) - slower, and only then.
+// evaluate rough cells term by term like self items do (item_finish<TAILS>, pmx_screen_tables.h) - slower, and only then.
 // PMX_PAIR_TAILS = 0 / 1 forces it off / on. Decided over all models of a call (pmx_score_multi: the pockets' types together).
 static bool pair_tails(const pmx_model *const *models, int n_models, const Weights &W) {
     float wmin = INFINITY, wmax = 0.f;
@@ -830,7 +830,7 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
     const int task_decay_from = (int)std::max<long>(1, env_long("PMX_TASK_DECAY_FROM", 99));
     const uint32_t task_budget_min = (uint32_t)std::max<long>(8, env_long("PMX_TASK_BUDGET_MIN", 48));
     const bool exact = (flags & 8) != 0;
-    // any validation switch: the kernels of pmx_screen_debug.hip (libpmx's own read those bits as zero, pmx_screen.hip PMX_WFLAGS)
+    // any validation switch: the kernels of pmx_screen_debug.hip (libpmx's own read those bits as zero, pmx_screen_layout.h PMX_WFLAGS)
     const bool debug_kernels = (flags & ~PMX_PRODUCT_FLAGS) != 0;
     bool debug_ok = true;
     const bool tails = pair_tails(models, n_models, W); // (term-by-term tails for widely spread type weights, see pair_tails)

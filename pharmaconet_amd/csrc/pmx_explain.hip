@@ -2,9 +2,10 @@
 // (graph_match.py:103-109, `scores` inside _run_average) and, per conformer, the leaf of the reference's tree that reaches
 // its maximum (ClusterMatchTree.key, tree.py:129-137).
 //
-// pmx_screen.hip is compiled here once more, as namespace pmx_x: the explain kernel builds a ligand's tables with the product's
-// own prepare_ligand (same slices, large slices and arena passes, same statuses) and walks them with a walker of its own. The
-// product kernels of libpmx (namespace pmx, pmx_api.hip) are not instantiated in this translation unit and do not change.
+// The table phase of the screening path (pmx_screen_tables.h) is compiled here once more, as namespace pmx_x: the explain kernel builds
+// a ligand's tables with the product's own prepare_ligand (same slices, large slices and arena passes, same statuses) and walks them with
+// a walker of its own. Neither the product walker (pmx_screen_walk.h) nor the product kernels (pmx_screen.hip) are part of this
+// translation unit.
 //
 // The explaining leaf of conformer c is the first leaf in `root_tree.iteration()` order whose score for c equals the maximum -
 // the leaf a strict `>` update in _run_average keeps. This walker visits the tree in that order (candidates in ascending
@@ -12,7 +13,7 @@
 // final maximum IS that leaf. A child is dropped only when no leaf below it can reach the running maximum of any of its
 // conformers ((total + R) * kBoundSlack < running maximum, strictly; the running maximum is never above the final one), so
 // no leaf that ties the maximum is ever dropped, and only children with >= 5 matches are dropped at all: their existence alone
-// settles every skip decision above them (tree.py:98, see walk() in pmx_screen.hip). Leaf totals are summed as the product
+// settles every skip decision above them (tree.py:98, see walk() in pmx_screen_walk.h). Leaf totals are summed as the product
 // walker sums them - (parent + self) + (pair entries of the matched ancestors, shallowest first) in float64 - so the maxima
 // are bit for bit the ones pmx_score averages.
 #include <hip/hip_runtime.h>
@@ -20,7 +21,7 @@
 #include <cstring>
 
 #define PMX_NS pmx_x
-#include "pmx_screen.hip"
+#include "pmx_screen_tables.h"
 #include "pmx_explain.h"
 
 namespace pmx_x {

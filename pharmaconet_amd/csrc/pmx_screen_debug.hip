@@ -1,6 +1,6 @@
 // pmx_screen_debug.hip - pmx_screen.hip once more, as namespace pmx_dbg, with every PMX_TREE_FLAGS switch compiled in: the kernels
 // behind the validation settings of the tests (no bounds, no fused levels, no cache, term-by-term items, ...) and the phase studies
-// of tools/. libpmx's own kernels (namespace pmx) carry none of these switches; see the note at the top of pmx_screen.hip.
+// of tools/. libpmx's own kernels (namespace pmx) carry none of these switches; see the note on PMX_NS in pmx_screen_layout.h.
 #include <hip/hip_runtime.h>
 #include <cstring>
 

@@ -39,6 +39,29 @@ def test_binding_covers_the_header(libpmx):
     assert libpmx.pmx_version() >= 100
 
 
+def csrc_include_closure(csrc, units):
+    """Every file under csrc/ that the units #include "..." directly or through another such file."""
+    seen, todo = set(), list(units)
+    while todo:
+        for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', (csrc / todo.pop()).read_text(), flags=re.M):
+            if (csrc / inc).is_file() and inc not in seen:
+                seen.add(inc)
+                todo.append(inc)
+    return seen
+
+
+def test_build_digest_covers_every_included_source():
+    """A header that a unit includes and build.py's DEPS does not list would leave libpmx.so, its stamp and bench.py's csrc_sha16 stale
+    after an edit, with no error."""
+    from pharmaconet_amd import build
+
+    closure = csrc_include_closure(build.CSRC, build.SOURCES)
+    assert "pmx_screen_layout.h" in closure and "pmx_device.h" in closure  # (the scan itself finds nested includes)
+    listed = set(build.SOURCES + build.DEPS)
+    assert closure <= listed, f"included under csrc/ but not in build.py's SOURCES + DEPS: {sorted(closure - listed)}"
+    assert all((build.CSRC / f).is_file() for f in listed), "build.py lists a file that is not there"
+
+
 def test_struct_sizes_match_the_header():
     from pharmaconet_amd import _ffi
 

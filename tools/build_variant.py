@@ -22,15 +22,15 @@ def main():
     procs = []
     for src in SOURCES:
         obj = out / f"{name}_{src.rsplit('.', 1)[0]}.o"
-        # (the two translation units that include pmx_screen.hip - the product kernels and the validation kernels - are always compiled
-        # with the variant's flags: a debug kernel built with the base macros under a host side built with the variant's would have
-        # another LDS layout and other launch bounds)
-        screening = src in ("pmx_api.hip", "pmx_screen_debug.hip")
+        # (the three translation units that include the screening headers - the product kernels, the validation kernels and the explain
+        # kernel, which builds its tables with the same code - are always compiled with the variant's flags: a kernel built with the base
+        # macros under a host side built with the variant's would have another LDS layout and other launch bounds)
+        screening = src in ("pmx_api.hip", "pmx_screen_debug.hip", "pmx_explain.hip")
         base_obj = out / f"base_{src.rsplit('.', 1)[0]}.o"
         fresh = base_obj.exists() and base_obj.stat().st_mtime > max((CSRC / src).stat().st_mtime, (REPO / "include" / "pmx.h").stat().st_mtime)
         if src.endswith(".hip") and not screening and fresh and name != "base":
             obj = out / f"base_{src.rsplit('.', 1)[0]}.o"
-        else:  # (the compiles run side by side: the two screening units take a minute each)
+        else:  # (the compiles run side by side: the screening units take a minute each)
             procs.append(subprocess.Popen([hipcc(), *FLAGS, *extra, f"-I{REPO / 'include'}", f"-I{CSRC}", "-c", str(CSRC / src), "-o", str(obj)]))
         objs.append(str(obj))
     if any(pr.wait() != 0 for pr in procs):
