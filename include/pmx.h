@@ -46,6 +46,7 @@ typedef enum {
 #define PMX_LIGAND_TOO_LARGE 2   /* the ligand's score tables exceed the whole table arena (PMX_ARENA_MB); score is NaN */
 #define PMX_LIGAND_EXPLAIN_MISS 3 /* pmx_explain: a conformer's maximum was not met by any leaf (reserved: the explain walker records the
                                      leaf that sets each maximum, so it cannot occur; a caller that sees it has found a bug) */
+#define PMX_LIGAND_KEY_INVALID 4  /* pmx_attribute: the row's conformer or key is not one of the ligand's tree (see there); total and node shares are NaN */
 
 typedef struct pmx_model pmx_model;
 typedef struct pmx_library pmx_library;
@@ -331,6 +332,45 @@ int pmx_density_destroy(pmx_density *d);
 #define PMX_EXPLAIN_MAX 65536
 int pmx_explain(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev, uint32_t n,
                 double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev, int32_t *status_dev, void *stream);
+
+/*
+ * Which ligand nodes carry a leaf's total: row i takes library ligand ligands_dev[i], conformer conformer_dev[i] and a key key_dev[i] -
+ * per tree level a model cluster or 0xFF for None, the format of pmx_explain's match_dev rows - and answers with the entries the
+ * reference's tree adds up for that leaf, term by term. All values are for that conformer c; lines of match_utils.py, graph_match.py, tree.py.
+ *   levels[l]      the ligand cluster behind tree level l, as pmx_explain reports it (0xFE for l >= nl).
+ *   match list     of a matched level l (k[l] != 0xFF; q = levels[l], a = k[l]): the nodes u of cluster q, in record order, whose type mask shares
+ *                  a type with at least one node of model cluster a (graph_match.py:139-172).
+ *   term(u, v)     likelihood * normalize_coeff * score_coeff of match_utils.py:29-69, in the reference's float32 operations;
+ *   fail(u, v)     num_pass < num_match * 0.5 (:56-61).
+ *   entry[l][l]    the float32 sum of term over itertools.combinations of level l's list, in that order (:87-120; no majority test).
+ *   entry[l1][l2]  l1 < l2, both matched: the float32 sum of term over itertools.product of the two lists; fails[l1][l2] the number of
+ *                  failing node pairs. The entry is -1 (no match) when the cluster-distance prefilter of graph_match.py:263-268 fails (it
+ *                  fails only if it fails for EVERY conformer of the ligand) or when fails > n1 * n2 * 0.5; otherwise the sum.
+ *   valid          c < C, every k[l] != 0xFF is a candidate of level l, and every off-diagonal entry between matched levels is > 0 (tree.py:81).
+ *   total          the float64 sum in the product walker's order: per matched level, shallowest first,
+ *                  (running + self) + (pair entries with the matched ancestors, shallowest first).
+ *   node[u]        float64: half of every term(u, v) / term(v, u) that enters an entry above, each weighted by its entry's
+ *                  (float32 sum) / (float64 sum of the same terms) - 1 to within float32 rounding - so that sum_u node[u] = sum of the entries =
+ *                  total to float64 rounding. 0 for nodes of unmatched clusters, of clusters beyond the PMX_MAX_LEVELS levels, or outside
+ *                  their cluster's match list.
+ * Outputs, per row:
+ *   total_dev     double [n]                                     NaN when the row is not valid
+ *   node_dev      double [n][PMX_MAX_LIGAND_NODES]               NaN throughout when the row is not valid
+ *   entry_dev     float  [n][PMX_MAX_LEVELS][PMX_MAX_LEVELS]     upper triangle and diagonal; 0 elsewhere and for unmatched levels, -1 as defined
+ *                                                                above. Written for an invalid row too (the answer to "why not this mode"); a
+ *                                                                match that is not a candidate of its level counts as None there, and a row
+ *                                                                whose conformer is not one of the ligand's has no entries (all 0).
+ *   fails_dev     uint16 [n][PMX_MAX_LEVELS][PMX_MAX_LEVELS]     counted in full, also where the entry is -1; 0 on the diagonal
+ *   levels_dev    uint8  [n][PMX_MAX_LEVELS]
+ *   status_dev    int32  [n]  PMX_LIGAND_OK; PMX_LIGAND_UNSUPPORTED for an index outside the library, a header-only record or a ligand
+ *                             pmx_score reports unsupported; PMX_LIGAND_KEY_INVALID for a row that is not valid
+ * A key of all 0xFF, or a ligand without levels, is valid with total 0. n <= PMX_EXPLAIN_MAX; n = 0 succeeds. The call is stream-ordered
+ * like pmx_explain (enqueued, no synchronisation). One wavefront per row (pmx_attribute.hip); no score table, no tabulated pair function,
+ * no table arena: any weights, and no dependence on PMX_TAILS_RATIO. The same call gives the same bits on every run.
+ */
+int pmx_attribute(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev,
+                  const int32_t *conformer_dev, const uint8_t *key_dev /* [n][PMX_MAX_LEVELS] */, uint32_t n, double *total_dev, double *node_dev,
+                  float *entry_dev, uint16_t *fails_dev, uint8_t *levels_dev, int32_t *status_dev, void *stream);
 
 /* Frees the scoring workspaces libpmx keeps between calls on `device` (synchronises the device first). */
 int pmx_release_workspaces(int device);

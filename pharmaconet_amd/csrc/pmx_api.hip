@@ -22,6 +22,7 @@
 #include "pmx_screen.hip"
 #include "pmx_debug.h"
 #include "pmx_explain.h"
+#include "pmx_attribute.h"
 
 using namespace pmx;
 
@@ -584,6 +585,7 @@ struct ScreenWs {
     DevBuf pabuf;                    // path_bound()'s pair sums: ligand kernel's wavefronts | task kernel's
     DevBuf arena, queue;
     DevBuf lists;                    // uint32: ovf | carry | heavy
+    DevBuf acur;                     // uint32: pmx_attribute's row cursor
     size_t arena_shrunk_to = 0;      // the arena size that was accepted when memory was short (0: never shrunk)
     int num_cu = 0;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // profiling: call start | last chunk: ligand kernels start, done | end | last chunk: rounds start, done
@@ -595,7 +597,7 @@ struct ScreenWs {
     uint64_t stamp = 0;    // last use (ensure_screen): the least recently used workspace of a device goes first
     bool released = false; // pmx_release_workspaces (or the cap on workspaces per device) took the buffers: a caller that was waiting on `mu` asks for a new workspace
     void free_buffers() {
-        for (DevBuf *b : {&ctl, &xctl, &slices, &big, &totbuf, &pabuf, &arena, &queue, &lists}) b->release();
+        for (DevBuf *b : {&ctl, &xctl, &slices, &big, &totbuf, &pabuf, &arena, &queue, &lists, &acur}) b->release();
         for (auto &e : ev) {
             if (e) (void)hipEventDestroy(e);
             e = nullptr;
@@ -1190,4 +1192,39 @@ extern "C" int pmx_explain(const pmx_model *model, const pmx_library *lib, const
     if (!with_lanes(lanes_of(lib), [&](auto g) { rc = explain_screen<decltype(g)::value>(model, lib, W, a, stream, *held.ws); }))
         rc = fail(PMX_ERR_INVALID, "no kernels for %d conformer lanes", lanes_of(lib));
     return rc;
+}
+
+// ------------------------------------------------------------------------------------ attribution (pmx_attribute.hip)
+// One kernel over the call's rows: no tables, no slices, no arena. Of the workspace of (device, stream) it takes the CU count and four
+// bytes for its row cursor, cleared in stream order in front of the launch.
+extern "C" int pmx_attribute(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev,
+                             const int32_t *conformer_dev, const uint8_t *key_dev, uint32_t n, double *total_dev, double *node_dev, float *entry_dev,
+                             uint16_t *fails_dev, uint8_t *levels_dev, int32_t *status_dev, void *stream_) {
+    if (!model || !lib || !weights) return fail(PMX_ERR_INVALID, "null argument");
+    if (n > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "more than %d rows in one attribute call", PMX_EXPLAIN_MAX);
+    if (n == 0) return PMX_OK;
+    if (!ligands_dev || !conformer_dev || !key_dev || !total_dev || !node_dev || !entry_dev || !fails_dev || !levels_dev || !status_dev)
+        return fail(PMX_ERR_INVALID, "null argument");
+    if (model->device != lib->device) return fail(PMX_ERR_INVALID, "model and library live on different devices");
+    HIPCHECK(hipSetDevice(lib->device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const HeldWs held = hold_screen(lib->device, stream);
+    ScreenWs &ws = *held.ws;
+    const int rc = init_workspace(ws, lib->device, stream);
+    if (rc) return rc;
+    HIPCHECK(ws.acur.grow(256, stream));
+    HIPCHECK(hipMemsetAsync(ws.acur.ptr, 0, 4, stream));
+    ScreenParams p{};
+    p.M = model->dm;
+    p.lib = lib->dl;
+    p.sidtab = model->sidtab;
+    p.sub_off = model->sub_off;
+    p.sub_nodes = model->sub_nodes;
+    p.W = to_weights(weights);
+    const pmx_attr::Args a{ligands_dev, conformer_dev, key_dev, n, total_dev, node_dev, entry_dev, fails_dev, levels_dev, status_dev, ws.acur.as<uint32_t>()};
+    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(kLdsPerCu / pmx_attr::lds_bytes(), 8));
+    const unsigned blocks = std::min<unsigned>(n, (unsigned)ws.num_cu * per_cu);
+    if (!pmx_attr::launch(blocks, stream, &p, sizeof p, a)) return fail(PMX_ERR_INVALID, "the attribution kernel (pmx_attribute.hip) does not match this build's parameter block");
+    HIPCHECK(hipGetLastError());
+    return PMX_OK;
 }

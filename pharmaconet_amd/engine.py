@@ -15,7 +15,7 @@ from . import _ffi
 from .constants import weights_vector
 from .library import PackedLibrary, as_packed_library
 
-__all__ = ["DeviceLibrary", "Explanation", "ScreeningResult", "explain", "score_one", "screen", "topk", "device_model", "last_score_stats"]
+__all__ = ["Attribution", "DeviceLibrary", "Explanation", "ScreeningResult", "attribute", "explain", "score_one", "screen", "topk", "device_model", "last_score_stats"]
 
 
 def _torch():
@@ -86,6 +86,7 @@ class DeviceLibrary:
         offsets = np.ascontiguousarray(library.offsets, dtype=np.uint64)
         data = np.ascontiguousarray(library.data, dtype=np.uint8)
         self._n_conf = library.headers()[:, 1].copy() if len(library) else np.zeros(0, np.uint16)  # (what `explain` cuts its rows to)
+        self._n_nodes = library.headers()[:, 0].copy() if len(library) else np.zeros(0, np.uint16)  # (... and `attribute`)
         view = _ffi.LibraryView(len(library), offsets.ctypes.data, data.ctypes.data if data.size else None, 0)
         self._upload(view)
 
@@ -408,6 +409,38 @@ class Explanation:
         return out
 
 
+    def attribution(self, model, library, conformer: int | None = None, weights: dict[str, float] | None = None) -> "Attribution":
+        """`attribute` of every row with status 0, at its best conformer (or `conformer`) under that conformer's own key: which nodes
+        carry the explained maximum. `rows` of the result says which row of this explanation each of its rows is."""
+        rows = [i for i in range(len(self)) if self.status[i] == 0]
+        conf = [int(self.best_conformer[i]) if conformer is None else int(conformer) for i in rows]
+        keys = []
+        for i, c in zip(rows, conf):
+            m = self.match[i]
+            keys.append(m[c] if 0 <= c < m.shape[0] else np.full(len(self.levels[i]), -1, np.int64))  # (not a conformer of the ligand: reported by the row's status)
+        out = attribute(model, library, self.indices[rows], conf, keys, weights=weights)
+        out.rows = np.asarray(rows, dtype=np.int64)
+        return out
+
+
+def _record_counts(library: "DeviceLibrary", idx: np.ndarray, field: int) -> np.ndarray:
+    """Header field `field` (0: nodes, 1: conformers) of library ligands `idx` (0 outside the library): kept per ligand when the library was
+    uploaded from the host, read from the adopted device records otherwise."""
+    ok = idx < len(library)
+    j = np.where(ok, idx, 0)
+    kept = getattr(library, "_n_conf" if field == 1 else "_n_nodes", None)
+    if kept is not None:
+        return np.where(ok, kept[j].astype(np.int64) if len(kept) else 0, 0)
+    src = getattr(library, "_adopted", None)
+    if src is None:
+        raise ValueError("this DeviceLibrary does not know its records' sizes: make it from a PackedLibrary or adopt the device buffers")
+    torch = _torch()
+    offsets, data = src
+    starts = offsets.view(torch.int64)[torch.from_numpy(j).to(offsets.device)] + 2 * field
+    v = data[starts].to(torch.int64) | (data[starts + 1].to(torch.int64) << 8)
+    return np.where(ok, v.cpu().numpy(), 0)
+
+
 def _conformer_counts(library: "DeviceLibrary", idx: np.ndarray) -> np.ndarray:
     """Conformer counts of library ligands `idx` (0 outside the library): kept per ligand when the library was uploaded from the host, read
     from the adopted device records otherwise."""
@@ -474,6 +507,116 @@ def explain(model, library, indices, weights: dict[str, float] | None = None, de
         key[key == NO_MATCH] = -1
         out_mt.append(key)
     return Explanation(indices=idx.astype(np.int64), conf_max=out_cm, best_conformer=bc, levels=out_lv, match=out_mt, status=st)
+
+
+KEY_INVALID = 4  # include/pmx.h PMX_LIGAND_KEY_INVALID
+
+
+@dataclass
+class Attribution:
+    """What `attribute` returns: one row per (ligand, conformer, key), cut to that ligand's nodes n and tree levels nl (definitions:
+    `pmx_attribute` in include/pmx.h).
+
+    total[i]   float64: the leaf's total for the conformer; NaN when the row is not valid (status 4) or the ligand unsupported (status 1)
+    node[i]    float64 [n]: the share of each node of the packed record, in record order; they add up to total[i]; NaN like total
+    entry[i]   float32 [nl, nl]: self entries on the diagonal, pair entries above it (-1: no match), 0 elsewhere and for unmatched levels;
+               also given for an invalid row
+    fails[i]   int [nl, nl]: failing node pairs of each pair entry
+    levels[i]  int [nl]: the ligand cluster behind each tree level
+    status[i]  0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID)"""
+
+    indices: np.ndarray
+    conformers: np.ndarray
+    total: np.ndarray
+    node: list
+    entry: list
+    fails: list
+    levels: list
+    status: np.ndarray
+    rows: "np.ndarray | None" = None  # `Explanation.attribution`: the explanation's row behind each row
+
+    def __len__(self) -> int:
+        return len(self.indices)
+
+    def atom_scores(self, i: int, lig) -> np.ndarray:
+        """Row i per atom of `lig` (the `LigandFeatures` the record was packed from): a node's share goes to its atoms in equal parts,
+        an atom adds up what it gets from its nodes. float64 [n_atoms]; its sum is total[i]."""
+        from .library import record_node_atoms
+
+        atoms = record_node_atoms(lig)
+        if len(atoms) != len(self.node[i]):
+            raise ValueError(f"the ligand has {len(atoms)} nodes, row {i} has {len(self.node[i])}")
+        out = np.zeros(lig.num_atoms, dtype=np.float64)
+        for share, at in zip(self.node[i], atoms):
+            out[list(at)] += float(share) / len(at)
+        return out
+
+
+def attribute(model, library, indices, conformers, keys, weights: dict[str, float] | None = None, device=None) -> Attribution:
+    """Entries, total and node shares (`pmx_attribute`, csrc/pmx_attribute.hip) of the leaf `keys[i]` of library ligand `indices[i]` for its
+    conformer `conformers[i]`. A key is an int array with a model cluster per tree level and -1 for None - the form `Explanation.match[i][c]`
+    has; shorter keys are filled with None. At most 65536 rows; any order, repeats allowed. `library` is a `DeviceLibrary` or anything
+    `as_packed_library` accepts. Runs on torch's current stream of the device and waits for it."""
+    torch = _torch()
+    lib = _ffi.load()
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+    conf = np.ascontiguousarray(np.asarray(conformers, dtype=np.int64).reshape(-1))
+    n = len(idx)
+    if (idx < 0).any():
+        raise ValueError("negative ligand index")
+    if len(conf) != n or len(keys) != n:
+        raise ValueError("indices, conformers and keys differ in length")
+    if n > 65536:
+        raise ValueError("at most 65536 rows per attribute call (PMX_EXPLAIN_MAX)")
+    L, NN = 20, 64  # PMX_MAX_LEVELS, PMX_MAX_LIGAND_NODES
+    kb = np.full((max(n, 1), L), NO_MATCH, dtype=np.uint8)
+    for i, k in enumerate(keys):
+        k = np.asarray(k, dtype=np.int64).reshape(-1)
+        if len(k) > L:
+            raise ValueError(f"key {i} has more than {L} levels")
+        if ((k < -1) | (k >= NO_LEVEL)).any():
+            raise ValueError(f"key {i}: a model cluster index or -1 per level")
+        kb[i, : len(k)] = np.where(k < 0, NO_MATCH, k).astype(np.uint8)
+    owned = None
+    if not isinstance(library, DeviceLibrary):
+        owned = library = DeviceLibrary(as_packed_library(library), device)
+    dev = library.device
+    mh = device_model(model, dev)
+    tdev = torch.device("cuda", dev)
+    m = max(n, 1)
+    lig = torch.from_numpy(idx).to(tdev)
+    cf = torch.from_numpy(np.clip(conf, -1, 2**31 - 1).astype(np.int32)).to(tdev)
+    key = torch.from_numpy(kb).to(tdev)
+    total = torch.empty(m, dtype=torch.float64, device=tdev)
+    node = torch.empty((m, NN), dtype=torch.float64, device=tdev)
+    entry = torch.empty((m, L, L), dtype=torch.float32, device=tdev)
+    fails = torch.empty((m, L, L), dtype=torch.int16, device=tdev)
+    levels = torch.empty((m, L), dtype=torch.uint8, device=tdev)
+    status = torch.empty(m, dtype=torch.int32, device=tdev)
+    try:
+        with torch.cuda.device(tdev):
+            stream = torch.cuda.current_stream(tdev)
+            _ffi.check(lib.pmx_attribute(mh.handle, library.handle, _weights_array(weights), lig.data_ptr(), cf.data_ptr(), key.data_ptr(), n,
+                                         total.data_ptr(), node.data_ptr(), entry.data_ptr(), fails.data_ptr(), levels.data_ptr(), status.data_ptr(),
+                                         ctypes.c_void_p(stream.cuda_stream)))
+            stream.synchronize()
+    finally:
+        if owned is not None:
+            torch.cuda.synchronize(tdev)
+            owned.close()
+    tt, nd, en = total.cpu().numpy()[:n], node.cpu().numpy()[:n], entry.cpu().numpy()[:n]
+    fl, lv, st = fails.cpu().numpy()[:n].view(np.uint16), levels.cpu().numpy()[:n], status.cpu().numpy()[:n].astype(np.int32)
+    nn = _record_counts(library, idx, 0)
+    out_nd, out_en, out_fl, out_lv = [], [], [], []
+    for i in range(n):
+        nl = int(np.count_nonzero(lv[i] != NO_LEVEL))
+        k = int(nn[i]) if st[i] != 1 else 0
+        out_nd.append(nd[i, :k].copy())
+        out_en.append(en[i, :nl, :nl].copy())
+        out_fl.append(fl[i, :nl, :nl].astype(np.int64))
+        out_lv.append(lv[i, :nl].astype(np.int64))
+    return Attribution(indices=idx.astype(np.int64), conformers=conf.astype(np.int64), total=tt.copy() if n else np.zeros(0), node=out_nd, entry=out_en,
+                       fails=out_fl, levels=out_lv, status=st)
 
 
 def last_score_stats() -> dict:

@@ -46,6 +46,7 @@ __all__ = [
     "PackedLibrary",
     "cluster_ligand",
     "pack_clustered_ligand",
+    "record_node_atoms",
     "pack_ligand",
     "pack_ligand_or_marker",
     "pack_features_native",
@@ -95,6 +96,7 @@ class ClusteredLigand:
     clusters: list[list[int]]  # node indices in cluster iteration order
     cluster_types: list[str]  # "Aromatic" | "Cation" | "Anion" | "HBond" | "Halogen" | "Hydrophobic"
     cluster_key_atom: list[int]  # min(cluster.nodes[0].atom_indices)  (graph_match.py:46)
+    node_atoms: list[tuple[int, ...]] | None = None  # per node its atom indices, ascending (`cluster_ligand` fills it; `record_node_atoms`)
 
 
 # ------------------------------------------------------------- LigandGraph restated
@@ -249,7 +251,7 @@ def cluster_ligand(lig: LigandFeatures) -> ClusteredLigand:
         else:
             positions[node.index] = np.mean(atom_positions[list(node.center_indices), :], axis=0, dtype=np.float32)
     key_atom = [min(nodes[c[0]].atom_indices) for c in clusters]
-    return ClusteredLigand(typemask, positions, clusters, cluster_types, key_atom)
+    return ClusteredLigand(typemask, positions, clusters, cluster_types, key_atom, [tuple(sorted(node.atom_indices)) for node in nodes])
 
 
 # ----------------------------------------------------------------------- packing
@@ -257,9 +259,8 @@ class LigandTooLarge(ValueError):
     """The ligand exceeds a structural limit of the GPU engine (include/pmx.h)."""
 
 
-def pack_clustered_ligand(cl: ClusteredLigand) -> bytes:
-    """Sort clusters by `priority_fn` (`graph_match.py:43-60`, stable like `sorted`, `:87`),
-    renumber nodes cluster by cluster and emit one record."""
+def _record_order(cl: ClusteredLigand) -> tuple[list[int], list[int], list[int]]:
+    """A record's cluster order (`priority_fn`, stable), the node order that follows from it and each cluster's end in that order."""
     order = sorted(
         range(len(cl.clusters)),
         key=lambda i: (
@@ -274,6 +275,22 @@ def pack_clustered_ligand(cl: ClusteredLigand) -> bytes:
     for i in order:
         node_order.extend(cl.clusters[i])
         cluster_end.append(len(node_order))
+    return order, node_order, cluster_end
+
+
+def record_node_atoms(lig: LigandFeatures) -> list[tuple[int, ...]]:
+    """The atom indices (ascending) of each node of the ligand's packed record, in the record's node order - the order
+    `pack_clustered_ligand` writes; the native and device packers write byte-identical records, so it holds for theirs too. What turns
+    the node shares of `engine.attribute` into atom shares (`Attribution.atom_scores`)."""
+    cl = cluster_ligand(lig)
+    _, node_order, _ = _record_order(cl)
+    return [cl.node_atoms[u] for u in node_order]
+
+
+def pack_clustered_ligand(cl: ClusteredLigand) -> bytes:
+    """Sort clusters by `priority_fn` (`graph_match.py:43-60`, stable like `sorted`, `:87`),
+    renumber nodes cluster by cluster and emit one record."""
+    order, node_order, cluster_end = _record_order(cl)
     if len(set(node_order)) != len(node_order):
         raise ValueError("a ligand node may belong to one cluster only")
     n = len(node_order)

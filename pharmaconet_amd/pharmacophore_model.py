@@ -354,6 +354,35 @@ class PharmacophoreModel:
         return dict(score=score, max=float(cm.max()) if cm.size else 0.0, conf_max=cm, best_conformer=int(ex.best_conformer[0]),
                     levels=ex.levels[0], match=ex.match[0], pairs=ex.pairs(0, self, packed))
 
+    def scoring_attribution(self, ligand, weights: dict[str, float] | None = None, conformer: int | None = None, key=None) -> dict:
+        """Which nodes of one ligand carry a leaf's total (`engine.attribute`): by default the explaining leaf of the best conformer, else
+        `conformer` and / or `key` (a model cluster or -1 per tree level). `conformer`, `key`, `levels`, `total`, `node` (share per node of the
+        packed record), `entry`, `fails` and `status` (0, or 4 when the key is not a leaf of the ligand's tree for that conformer: total
+        and node are then NaN, `entry` says which pair stands in the way). Takes what `_scoring` takes."""
+        from .engine import attribute, explain
+        from .library import as_packed_library
+
+        packed = as_packed_library(ligand)
+        if len(packed) != 1:
+            raise ValueError("scoring_attribution takes exactly one ligand")
+        if conformer is None or key is None:
+            ex = explain(self, packed, [0], weights=weights)
+            if int(ex.status[0]) != 0:
+                n, c, _ = packed.header(0)
+                raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+            if conformer is None:
+                conformer = int(ex.best_conformer[0])
+            if key is None:
+                if not 0 <= int(conformer) < ex.match[0].shape[0]:
+                    raise ValueError(f"the ligand has {ex.match[0].shape[0]} conformers")
+                key = ex.match[0][int(conformer)]
+        at = attribute(self, packed, [0], [int(conformer)], [key], weights=weights)
+        if int(at.status[0]) == 1:
+            n, c, _ = packed.header(0)
+            raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+        return dict(conformer=int(conformer), key=np.asarray(key, dtype=np.int64), levels=at.levels[0], total=float(at.total[0]), node=at.node[0],
+                    entry=at.entry[0], fails=at.fails[0], status=int(at.status[0]))
+
     def explain(self, library, indices, weights: dict[str, float] | None = None, **kwargs):
         """Per-conformer maxima and explaining matches of library ligands `indices` (`engine.explain`)."""
         from .engine import explain

@@ -31,6 +31,7 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--cpus", type=int, default=1, help="host processes for reading / packing molecule files")
         cfg.add_argument("--explain", type=int, default=0, metavar="K", help="also explain the K best hits (best conformer and its cluster matches)")
         cfg.add_argument("--explain_out", type=str, default=None, help="CSV of the explained hits (default: <out>.explain.csv)")
+        cfg.add_argument("--explain_nodes", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per pharmacophore node of each explained hit and the node's share of the hit's best conformer maximum")
         par = self.add_argument_group("parameter")
         par.add_argument("--hydrophobic", type=float, default=1.0, help="weight for hydrophobic carbon")
         par.add_argument("--aromatic", type=float, default=4.0, help="weight for aromatic ring")
@@ -110,7 +111,10 @@ def write_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarra
 
 
 def main(argv=None) -> None:
-    args = Screening_ArgParser().parse_args(argv)
+    parser = Screening_ArgParser()
+    args = parser.parse_args(argv)
+    if args.explain_nodes and args.explain <= 0:
+        parser.error("--explain_nodes needs --explain K")
     model = PharmacophoreModel.load(args.pharmacophore_model)
     weight = dict(
         Cation=args.cation,
@@ -128,6 +132,8 @@ def main(argv=None) -> None:
     if args.explain > 0:
         out = Path(args.explain_out) if args.explain_out else Path(str(args.out) + ".explain.csv")
         write_explain_csv(out, names, scores, status, model, lib, weight, args.explain)
+        if args.explain_nodes:
+            write_explain_nodes_csv(Path(args.explain_nodes), names, scores, status, model, lib, weight, args.explain)
 
 
 def write_explain_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int) -> None:
@@ -146,6 +152,42 @@ def write_explain_csv(out: Path, names: list[str], scores: np.ndarray, status: n
             c = int(ex.best_conformer[r])
             pairs = [f"{lc}->{int(m)}:{types[int(m)]}" for lc, m in zip(ex.levels[r], ex.match[r][c]) if m >= 0] if c >= 0 else []
             w.write(f"{r + 1},{names[i]},{float(scores[i])},{c},{float(ex.conf_max[r][c])},{' '.join(pairs)}\n")
+
+
+def _record_of(lib, i: int) -> dict:
+    """Record i of a packed library, or of a device-resident one made from features (its buffers are read back for that record)."""
+    if isinstance(lib, PackedLibrary):
+        return lib.unpack(i)
+    offsets, data = lib._adopted
+    lo, hi = (int(x) for x in offsets[i : i + 2].cpu())
+    return PackedLibrary.from_records([data[lo:hi].cpu().numpy().tobytes()]).unpack(0)
+
+
+def write_explain_nodes_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int) -> None:
+    """One row per (hit, node) of the k best hits, in the order of the main CSV: the node's index in the packed record, its types, its
+    ligand cluster, the model cluster that cluster is matched to in the explaining leaf of the hit's best conformer (empty for None and
+    for clusters outside the tree), the node's share of that conformer's maximum (`engine.attribute`) and the share as a fraction of it."""
+    from .constants import TYPE_NAMES
+    from .engine import explain
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    ex = explain(model, lib, order, weights=weights)
+    at = ex.attribution(model, lib, weights=weights)
+    with open(out, "w") as w:
+        w.write("rank,index,path,conformer,node,node_types,ligand_cluster,model_cluster,node_score,share\n")
+        for r, row in enumerate(at.rows):
+            i = order[int(row)]
+            rec = _record_of(lib, i)
+            ends = rec["cluster_end"]
+            matched = {int(lc): int(m) for lc, m in zip(ex.levels[row], ex.match[row][int(at.conformers[r])]) if m >= 0}
+            total = float(at.total[r])
+            for u, share in enumerate(at.node[r]):
+                lc = int(np.searchsorted(ends, u, side="right"))
+                tm = int(rec["typemask"][u])
+                types = "|".join(TYPE_NAMES[t] for t in range(len(TYPE_NAMES)) if tm >> t & 1)
+                frac = float(share) / total if total > 0 else 0.0
+                w.write(f"{int(row) + 1},{i},{names[i]},{int(at.conformers[r])},{u},{types},{lc},{matched.get(lc, '')},{float(share)},{frac}\n")
 
 
 if __name__ == "__main__":

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Time of `engine.explain` for the top hits of a screen (the cost of inspecting them, include/pmx.h pmx_explain).
 
-    python tools/explain_bench.py [--ligands 1000000] [--hits 1000] [--library bench|survey|stress] [--repeat 3]
+    python tools/explain_bench.py [--ligands 1000000] [--hits 1000] [--library bench|survey|stress] [--repeat 3] [--attribute]
 
 Scores the library once (pmx_score_f64), ranks it on the host and times explain of the `--hits` best ligands on a resident library,
-best of `--repeat` calls after one warm-up call. Prints one JSON line."""
+best of `--repeat` calls after one warm-up call. With `--attribute` also `engine.attribute` of the same hits at their best conformer under
+their own key (`Explanation.attribution`), and - the host's packing and cutting of 65 536 rows being most of either wall time - the device
+time of the two C calls alone between HIP events. Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--hits", type=int, default=1000)
     ap.add_argument("--library", choices=("bench", "survey", "stress"), default="bench")
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--attribute", action="store_true", help="also time engine.attribute of the same hits")
     a = ap.parse_args()
     import torch
 
@@ -57,11 +60,67 @@ def main():
         t0 = time.perf_counter()
         ex = explain(model, dlib, top, weights=weights)
         times.append(time.perf_counter() - t0)
+    extra = {}
+    if a.attribute:
+        at = ex.attribution(model, dlib, weights=weights)  # warm-up
+        wall = []
+        for _ in range(a.repeat):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            at = ex.attribution(model, dlib, weights=weights)
+            wall.append(time.perf_counter() - t0)
+        extra = dict(attribute_rows=len(at), attribute_ms=round(1e3 * min(wall), 3), attribute_invalid=int((at.status != 0).sum()), **device_times(model, dlib, weights, ex, a.repeat))
     means = np.array([m.mean() for m in ex.conf_max])
-    print(json.dumps(dict(library=a.library, ligands=dlib.num_ligands, hits=len(top), explain_ms=round(1e3 * min(times), 3),
+    print(json.dumps(dict(**extra, library=a.library, ligands=dlib.num_ligands, hits=len(top), explain_ms=round(1e3 * min(times), 3),
                           explain_ms_all=[round(1e3 * t, 3) for t in times], max_abs_diff_vs_score=float(np.abs(means - sc[top]).max()),
                           misses=int((ex.status == 3).sum()),
                           score_pass_longest_walk=int(stats["max_passes"]), score_pass_split_trees=int(stats["n_heavy"]))))
+
+
+def device_times(model, dlib, weights, ex, repeat):
+    """pmx_explain and pmx_attribute of the explanation's OK rows between HIP events on the current stream: best of `repeat`, in ms."""
+    import ctypes
+
+    import torch
+
+    from pharmaconet_amd import _ffi
+    from pharmaconet_amd.engine import _weights_array, device_model
+
+    lib = _ffi.load()
+    dev = torch.device("cuda", dlib.device)
+    rows = [i for i in range(len(ex)) if ex.status[i] == 0]
+    n = len(rows)
+    keys = np.full((n, 20), 0xFF, np.uint8)
+    for r, i in enumerate(rows):
+        k = ex.match[i][int(ex.best_conformer[i])]
+        keys[r, : len(k)] = np.where(k < 0, 0xFF, k)
+    lig = torch.from_numpy(ex.indices[rows].astype(np.int64)).to(dev)
+    conf = torch.from_numpy(ex.best_conformer[rows].astype(np.int32)).to(dev)
+    key = torch.from_numpy(keys).to(dev)
+    f64, u8, i32 = torch.float64, torch.uint8, torch.int32
+    cm, mt, lv = torch.empty((n, 64), dtype=f64, device=dev), torch.empty((n, 64, 20), dtype=u8, device=dev), torch.empty((n, 20), dtype=u8, device=dev)
+    best, st = torch.empty(n, dtype=i32, device=dev), torch.empty(n, dtype=i32, device=dev)
+    tot, nd = torch.empty(n, dtype=f64, device=dev), torch.empty((n, 64), dtype=f64, device=dev)
+    en, fl = torch.empty((n, 20, 20), dtype=torch.float32, device=dev), torch.empty((n, 20, 20), dtype=torch.int16, device=dev)
+    mh, w = device_model(model, dlib.device), _weights_array(weights)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    calls = dict(
+        explain_device_ms=lambda: lib.pmx_explain(mh.handle, dlib.handle, w, lig.data_ptr(), n, cm.data_ptr(), mt.data_ptr(), lv.data_ptr(), best.data_ptr(), st.data_ptr(), stream),
+        attribute_device_ms=lambda: lib.pmx_attribute(mh.handle, dlib.handle, w, lig.data_ptr(), conf.data_ptr(), key.data_ptr(), n, tot.data_ptr(), nd.data_ptr(),
+                                                      en.data_ptr(), fl.data_ptr(), lv.data_ptr(), st.data_ptr(), stream),
+    )
+    out = {}
+    for name, call in calls.items():
+        times = []
+        for _ in range(repeat + 1):  # (the first is a warm-up)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _ffi.check(call())
+            e1.record()
+            e1.synchronize()
+            times.append(e0.elapsed_time(e1))
+        out[name] = round(min(times[1:]), 3)
+    return out
 
 
 if __name__ == "__main__":
