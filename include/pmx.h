@@ -328,10 +328,35 @@ int pmx_density_destroy(pmx_density *d);
  * n <= PMX_EXPLAIN_MAX. The call is stream-ordered like pmx_score (enqueued, no synchronisation) and uses the same workspace of
  * (device, stream). Each listed ligand's tables are built as pmx_score builds them and its tree is walked to its end by one
  * wavefront (pmx_explain.hip): no pass budget, no task queue - the call costs about its largest tree.
+ *
+ * Constrained matching (pmx_explain_constrained): the same answers over the leaves that QUALIFY under a constraint. A constraint is up
+ * to PMX_MAX_REQUIRE_GROUPS require groups - each a non-empty set of model clusters (indices into model.node_clusters) - and one
+ * exclude set. A leaf qualifies when its key holds at least one cluster of every require group and no cluster of the exclude set (a
+ * group of several clusters says "any cluster that holds this hotspot node"). The tree is the reference's, unchanged: which children
+ * exist and when the skip child exists (`nm + mx < 5`, tree.py:98-101) do not depend on the constraint; only the set of leaves that may
+ * update a conformer's maximum does. Per conformer the constrained maximum is the maximum over qualifying leaves that hold the
+ * conformer with a score > 0 (0 if there is none, keys 0xFF), the key that of the first qualifying leaf in iteration order that
+ * reaches it - the rule above. A constrained maximum is never above the unconstrained one. Outputs, limits, statuses, stream ordering
+ * and workspace use are pmx_explain's; pmx_explain is this call without a constraint (constraint = NULL).
+ *   PMX_ERR_INVALID       n_require outside 0 .. PMX_MAX_REQUIRE_GROUPS; an empty group among the first n_require; a bit at or above the
+ *                         model's cluster count
+ * A constraint that no leaf can satisfy (a cluster required alone and excluded, say) is no error: status 0, maxima 0, keys 0xFF, best
+ * conformer 0.
  */
 #define PMX_EXPLAIN_MAX 65536
 int pmx_explain(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev, uint32_t n,
                 double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev, int32_t *status_dev, void *stream);
+
+#define PMX_MAX_REQUIRE_GROUPS 8
+typedef struct {
+    int32_t n_require;                           /* 0 .. PMX_MAX_REQUIRE_GROUPS */
+    uint64_t require[PMX_MAX_REQUIRE_GROUPS][2]; /* bit (a % 64) of word a / 64: model cluster a */
+    uint64_t exclude[2];
+} pmx_match_constraint; /* host struct, copied by the call; NULL = no constraint */
+
+int pmx_explain_constrained(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES],
+                            const pmx_match_constraint *constraint, const uint64_t *ligands_dev, uint32_t n, double *conf_max_dev,
+                            uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev, int32_t *status_dev, void *stream);
 
 /*
  * Which ligand nodes carry a leaf's total: row i takes library ligand ligands_dev[i], conformer conformer_dev[i] and a key key_dev[i] -

@@ -89,6 +89,19 @@ class ScoreStats(ctypes.Structure):
     )
 
 
+MAX_REQUIRE_GROUPS = 8
+
+
+class MatchConstraint(ctypes.Structure):
+    """pmx_match_constraint: bit (a % 64) of word a / 64 is model cluster a."""
+
+    _fields_ = [
+        ("n_require", ctypes.c_int32),
+        ("require", (ctypes.c_uint64 * 2) * MAX_REQUIRE_GROUPS),
+        ("exclude", ctypes.c_uint64 * 2),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/pmx.h declares
 SIGNATURES = {
     "pmx_last_error": (ctypes.c_char_p, []),
@@ -163,6 +176,11 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "pmx_explain_constrained": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(MatchConstraint), ctypes.c_void_p, ctypes.c_uint32,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     ),
     "pmx_attribute": (
         ctypes.c_int,

@@ -52,7 +52,7 @@ static int fail(int code, const char *fmt, ...) {
     } while (0)
 
 extern "C" const char *pmx_last_error(void) { return g_err; }
-extern "C" int pmx_version(void) { return 100; }
+extern "C" int pmx_version(void) { return 101; }
 extern "C" int pmx_set_profiling(int enabled) {
     g_profiling = enabled;
     return PMX_OK;
@@ -1124,7 +1124,8 @@ int pmx_topk_fail(int code, const char *msg) { return fail(code, "%s", msg); }
 // The listed ligands' tables are built as pmx_score builds them - per-wave slices, then large slices, then the arena with its
 // retries - and each is walked to its end by one wavefront of the explain kernel: no budget, no task queue.
 template <int G>
-static int explain_screen(const pmx_model *model, const pmx_library *lib, const Weights &W, const pmx_xpl::Args &a, hipStream_t stream, ScreenWs &ws) {
+static int explain_screen(const pmx_model *model, const pmx_library *lib, const Weights &W, const pmx_xpl::Args &a, bool constrained, hipStream_t stream,
+                          ScreenWs &ws) {
     int rc = init_workspace(ws, lib->device, stream);
     if (rc) return rc;
     const bool tails = pair_tails(&model, 1, W); // (as pmx_score / pmx_score_f64 decide it for this model)
@@ -1153,10 +1154,10 @@ static int explain_screen(const pmx_model *model, const pmx_library *lib, const 
 
     pmx_xpl::launch_init(a, stream);
     ctl_clear_kernel<<<dim3((sizeof(Ctl) / 4 + 255) / 256), dim3(256), 0, stream>>>(xctl, 1);
-    const size_t lds = pmx_xpl::lds_bytes(G, model->dm.K, (int)p.max_nodes);
+    const size_t lds = pmx_xpl::lds_bytes(G, model->dm.K, (int)p.max_nodes, constrained);
     const uint32_t full = (uint32_t)ws.num_cu * pl.waves_per_cu;
     bool ok = true;
-    auto launch = [&](int mode, uint32_t blocks) { ok &= pmx_xpl::launch(G, tails, mode, std::max(1u, blocks), (unsigned)lds, stream, &p, sizeof p, a); };
+    auto launch = [&](int mode, uint32_t blocks) { ok &= pmx_xpl::launch(G, tails, constrained, mode, std::max(1u, blocks), (unsigned)lds, stream, &p, sizeof p, a); };
     p.slices = ws.slices.as<uint8_t>();
     p.slice_bytes = pl.slice_bytes;
     launch(0, std::min(full, a.n));
@@ -1176,9 +1177,32 @@ static int explain_screen(const pmx_model *model, const pmx_library *lib, const 
     return PMX_OK;
 }
 
-extern "C" int pmx_explain(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev, uint32_t n,
-                           double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev, int32_t *status_dev, void *stream_) {
+// pmx_explain and pmx_explain_constrained: one driver; without a constraint the kernels are the ones that never look at one.
+static int explain_call(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const pmx_match_constraint *constraint,
+                        const uint64_t *ligands_dev, uint32_t n, double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev,
+                        int32_t *status_dev, void *stream_) {
     if (!model || !lib || !weights) return fail(PMX_ERR_INVALID, "null argument");
+    pmx_match_constraint con;
+    std::memset(&con, 0, sizeof con);
+    if (constraint) {
+        const int K = model->dm.K;
+        const auto beyond = [K](const uint64_t w[2]) { // a bit at or above the model's cluster count
+            const uint64_t m0 = K >= 64 ? ~0ull : (1ull << K) - 1ull, m1 = K >= 128 ? ~0ull : (K > 64 ? (1ull << (K - 64)) - 1ull : 0ull);
+            return ((w[0] & ~m0) | (w[1] & ~m1)) != 0ull;
+        };
+        if (constraint->n_require < 0 || constraint->n_require > PMX_MAX_REQUIRE_GROUPS)
+            return fail(PMX_ERR_INVALID, "constraint: %d require groups (0 to %d)", (int)constraint->n_require, PMX_MAX_REQUIRE_GROUPS);
+        con.n_require = constraint->n_require;
+        for (int g = 0; g < con.n_require; ++g) {
+            if ((constraint->require[g][0] | constraint->require[g][1]) == 0ull) return fail(PMX_ERR_INVALID, "constraint: require group %d is empty", g);
+            if (beyond(constraint->require[g])) return fail(PMX_ERR_INVALID, "constraint: require group %d names a cluster outside the model's %d", g, K);
+            con.require[g][0] = constraint->require[g][0];
+            con.require[g][1] = constraint->require[g][1];
+        }
+        if (beyond(constraint->exclude)) return fail(PMX_ERR_INVALID, "constraint: the exclude set names a cluster outside the model's %d", K);
+        con.exclude[0] = constraint->exclude[0];
+        con.exclude[1] = constraint->exclude[1];
+    }
     if (n > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "more than %d ligands in one explain call", PMX_EXPLAIN_MAX);
     if (n == 0) return PMX_OK;
     if (!ligands_dev || !conf_max_dev || !match_dev || !levels_dev || !best_conformer_dev || !status_dev) return fail(PMX_ERR_INVALID, "null argument");
@@ -1186,12 +1210,24 @@ extern "C" int pmx_explain(const pmx_model *model, const pmx_library *lib, const
     HIPCHECK(hipSetDevice(lib->device));
     const Weights W = to_weights(weights);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const pmx_xpl::Args a{ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev};
+    const pmx_xpl::Args a{ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, con};
+    const bool constrained = constraint != nullptr;
     const HeldWs held = hold_screen(lib->device, stream);
     int rc = PMX_OK;
-    if (!with_lanes(lanes_of(lib), [&](auto g) { rc = explain_screen<decltype(g)::value>(model, lib, W, a, stream, *held.ws); }))
+    if (!with_lanes(lanes_of(lib), [&](auto g) { rc = explain_screen<decltype(g)::value>(model, lib, W, a, constrained, stream, *held.ws); }))
         rc = fail(PMX_ERR_INVALID, "no kernels for %d conformer lanes", lanes_of(lib));
     return rc;
+}
+
+extern "C" int pmx_explain(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev, uint32_t n,
+                           double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev, int32_t *status_dev, void *stream) {
+    return explain_call(model, lib, weights, nullptr, ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, stream);
+}
+
+extern "C" int pmx_explain_constrained(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const pmx_match_constraint *constraint,
+                                       const uint64_t *ligands_dev, uint32_t n, double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev,
+                                       int32_t *best_conformer_dev, int32_t *status_dev, void *stream) {
+    return explain_call(model, lib, weights, constraint, ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, stream);
 }
 
 // ------------------------------------------------------------------------------------ attribution (pmx_attribute.hip)

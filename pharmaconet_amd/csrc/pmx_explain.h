@@ -1,8 +1,10 @@
-// pmx_explain.h - launchers of the explain kernels (pmx_explain.hip), called by pmx_explain() in pmx_api.hip.
+// pmx_explain.h - launchers of the explain kernels (pmx_explain.hip), called by pmx_explain() and pmx_explain_constrained() in pmx_api.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <stdint.h>
+
+#include "pmx.h"
 
 namespace pmx_xpl {
 // Where one call's answers go (device pointers, see pmx_explain in include/pmx.h); row i belongs to ligands[i].
@@ -14,14 +16,16 @@ struct Args {
     uint8_t *levels;   // [n][PMX_MAX_LEVELS]
     int32_t *best;     // [n]
     int32_t *status;   // [n]
+    pmx_match_constraint con; // which leaves may hold a maximum (read by the constrained kernels only)
 };
 // Dynamic LDS of the explain kernel of shape G for a model of K clusters and a library of at most max_nodes nodes per ligand
-// (0 for a G this side does not know).
-size_t lds_bytes(int G, int K, int max_nodes);
+// (0 for a G this side does not know); the constrained kernels keep two more 128-bit words per tree level.
+size_t lds_bytes(int G, int K, int max_nodes, bool constrained);
 // `params`: the caller's pmx::ScreenParams (same source and layout; `bytes` is checked against this side's sizeof). mode as
 // ScreenParams::mode: 0 the listed ligands with tables in per-wave slices, 1 the large-slice pass, 2 / 3 the arena passes.
-// Returns false when G or the size is not one this side knows.
-bool launch(int G, bool tails, int mode, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes, const Args &a);
+// `constrained`: the kernels that test every leaf against a.con; without it a.con is not read. Returns false when G or the size is not
+// one this side knows.
+bool launch(int G, bool tails, bool constrained, int mode, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes, const Args &a);
 void launch_init(const Args &a, hipStream_t stream);  // rows as for a ligand without levels: maxima 0, no match, no levels
 void launch_fixup(const Args &a, hipStream_t stream); // rows of ligands with a non-zero status: maxima NaN, best conformer -1
 } // namespace pmx_xpl

@@ -16,6 +16,13 @@
 // settles every skip decision above them (tree.py:98, see walk() in pmx_screen_walk.h). Leaf totals are summed as the product
 // walker sums them - (parent + self) + (pair entries of the matched ancestors, shallowest first) in float64 - so the maxima
 // are bit for bit the ones pmx_score averages.
+//
+// Constrained matching (pmx_explain_constrained): the same tree - which children exist and when the skip child exists do not depend on
+// the constraint - but only a leaf whose key qualifies (a cluster of every require group, none of the exclude set) may update a
+// conformer's maximum. The constrained instantiation keeps, per frame, the 128-bit set of model clusters matched on the path; the
+// bound test above holds with the constrained running maximum, and a child with >= 5 matches is also dropped when no leaf below it can
+// qualify (an excluded cluster on its path, or a require group with no cluster on the path or among the candidates of the levels
+// below). A subtree with fewer matches that cannot qualify is walked for its match count alone.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstring>
@@ -31,10 +38,10 @@ constexpr uint8_t kNoMatch = 0xFF, kNoLevel = 0xFE;
 // The explain walker's LDS, behind the product's per-wave layout.
 template <int G>
 struct ExplainLds {
-    uint32_t tot, key, frame, mrow, path, cb, bytes;
+    uint32_t tot, key, frame, mrow, path, cb, pm, sfx, bytes;
 };
 template <int G>
-__host__ __device__ inline ExplainLds<G> explain_lds(const WaveShape<G> &ws) {
+__host__ __device__ inline ExplainLds<G> explain_lds(const WaveShape<G> &ws, bool constrained) {
     ExplainLds<G> e;
     uint32_t o = (ws.bytes + 15u) & ~15u;
     e.tot = o; // double [frame][G]: the total of each frame's tree node (frame f = the node whose children are the candidates of level f)
@@ -49,12 +56,39 @@ __host__ __device__ inline ExplainLds<G> explain_lds(const WaveShape<G> &ws) {
     o += 32;
     e.cb = o; // u64 [PMX_MAX_LEVELS][2]: model clusters that are candidates of each level
     o += 16 * PMX_MAX_LEVELS;
+    e.pm = e.sfx = o;
+    if (constrained) {
+        e.pm = o; // u64 [PMX_MAX_LEVELS + 1][2]: model clusters matched on the path to each frame's node
+        o += 16 * (PMX_MAX_LEVELS + 1);
+        e.sfx = o; // u64 [PMX_MAX_LEVELS + 1][2]: model clusters that are candidates of level f or of a level below it
+        o += 16 * (PMX_MAX_LEVELS + 1);
+    }
     e.bytes = o;
     return e;
 }
 
+// Can a key whose matched model clusters are (m0, m1), and that may still gain clusters of (s0, s1), qualify: no excluded cluster matched,
+// and every require group has a cluster matched or still to come. With s = 0: does the key qualify. Wave-uniform.
+__device__ inline bool con_feasible(const pmx_match_constraint &k, unsigned long long m0, unsigned long long m1, unsigned long long s0, unsigned long long s1) {
+    if (((m0 & k.exclude[0]) | (m1 & k.exclude[1])) != 0ull) return false;
+    for (int g = 0; g < k.n_require; ++g)
+        if ((((m0 | s0) & k.require[g][0]) | ((m1 | s1) & k.require[g][1])) == 0ull) return false;
+    return true;
+}
+
+// Candidate b of a level whose candidates are the model clusters (w0, w1), as a one-bit set: candidates are in ascending cluster order.
+__device__ inline void candidate_bit(unsigned long long w0, unsigned long long w1, int b, unsigned long long &b0, unsigned long long &b1) {
+    const int n0 = __popcll(w0);
+    unsigned long long xw = b < n0 ? w0 : w1;
+    for (int j = b < n0 ? b : b - n0; j > 0; --j) xw &= xw - 1ull;
+    xw &= 0ull - xw;
+    b0 = b < n0 ? xw : 0ull;
+    b1 = b < n0 ? 0ull : xw;
+}
+
 // The tree of one prepared ligand (tables at `rec`), maxima and keys into row li of the output. Lane c < G is conformer c.
-template <int G>
+// CONSTRAINED: only leaves whose key qualifies under a.con update a maximum (see the note at the top).
+template <int G, bool CONSTRAINED>
 __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const ExplainLds<G> &E, const unsigned char *rec, uint64_t lig, uint32_t li,
                              const pmx_xpl::Args &a) {
     const int lane = lane_id();
@@ -72,6 +106,46 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
     int *mrow = reinterpret_cast<int *>(lds + E.mrow);
     uint8_t *path = lds + E.path;
     unsigned long long *cbl = reinterpret_cast<unsigned long long *>(lds + E.cb);
+    unsigned long long *pm = reinterpret_cast<unsigned long long *>(lds + E.pm);
+    unsigned long long *sfx = reinterpret_cast<unsigned long long *>(lds + E.sfx);
+
+    // ---- the levels of the row and the model clusters that are candidates of each
+    const Record r = parse_record(p.lib.data + p.lib.offsets[lig]);
+    {
+        unsigned long long cb0 = 0, cb1 = 0;
+        if (lane < r.ncl) {
+            const int cs = lane ? r.cluster_end[lane - 1] : 0, ce = r.cluster_end[lane];
+            unsigned lm = 0;
+            for (int u = cs; u < ce; ++u) lm |= r.typemask[u];
+            cb0 = p.M.tclus[2u * (lm & 127u)];
+            cb1 = p.M.tclus[2u * (lm & 127u) + 1u];
+        }
+        const bool has = (cb0 | cb1) != 0ull;
+        const unsigned long long bal = __ballot(has);
+        const int lev = __popcll(bal & ((1ull << lane) - 1ull));
+        if (has && lev < nl) { // (scan_ligand's levels: clusters with a candidate, in priority order, at most PMX_MAX_LEVELS)
+            a.levels[(size_t)li * PMX_MAX_LEVELS + lev] = (uint8_t)lane;
+            cbl[2 * lev] = cb0;
+            cbl[2 * lev + 1] = cb1;
+        }
+    }
+    bool go = true; // (no leaf can qualify when a require group has no cluster among the candidates of any level)
+    if constexpr (CONSTRAINED) {
+        wave_sync();
+        if (lane == 0) {
+            unsigned long long s0 = 0, s1 = 0;
+            sfx[2 * nl] = sfx[2 * nl + 1] = 0ull;
+            for (int l = nl - 1; l >= 0; --l) {
+                s0 |= cbl[2 * l];
+                s1 |= cbl[2 * l + 1];
+                sfx[2 * l] = s0;
+                sfx[2 * l + 1] = s1;
+            }
+            pm[0] = pm[1] = 0ull;
+        }
+        wave_sync();
+        go = con_feasible(a.con, 0ull, 0ull, uni64(sfx[0]), uni64(sfx[1]));
+    }
 
     uint32_t vbits = (mine && c < C) ? 1u : 0u; // bit f: conformer c is in the pair_scores of frame f's node (tree.py:78-84)
     double best = 0.0;                           // running maximum of conformer c (graph_match.py:105-108)
@@ -83,9 +157,11 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
     wave_sync();
     const double slack = kBoundSlack;
     int f = 0;
-    for (;;) {
+    while (go) {
         if (f == nl) { // a leaf: its pair_scores are the frame's totals over the frame's conformers
-            if (mine && ((vbits >> f) & 1u)) {
+            bool qualifies = true;
+            if constexpr (CONSTRAINED) qualifies = con_feasible(a.con, uni64(pm[2 * f]), uni64(pm[2 * f + 1]), 0ull, 0ull);
+            if (qualifies && mine && ((vbits >> f) & 1u)) {
                 const double t = tot[f * G + c];
                 if (t > best) {
                     best = t;
@@ -129,9 +205,20 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
                 continue;
             }
             any = 1;
+            unsigned long long m0 = 0, m1 = 0; // the child's matched model clusters
+            if constexpr (CONSTRAINED) {
+                candidate_bit(uni64(cbl[2 * f]), uni64(cbl[2 * f + 1]), b, m0, m1);
+                m0 |= uni64(pm[2 * f]);
+                m1 |= uni64(pm[2 * f + 1]);
+            }
             if (nm + 1 >= 5) { // a child whose existence settles every skip decision above it: may be dropped on its bound
-                const double r = mine ? R[(size_t)(f + 1) * G + c] : 0.0;
-                if (__ballot(valid && (t + r) * slack >= best) == 0ull) {
+                bool drop = false; // (or when no leaf below it can qualify)
+                if constexpr (CONSTRAINED) drop = !con_feasible(a.con, m0, m1, uni64(sfx[2 * (f + 1)]), uni64(sfx[2 * (f + 1) + 1]));
+                if (!drop) {
+                    const double rb = mine ? R[(size_t)(f + 1) * G + c] : 0.0;
+                    drop = __ballot(valid && (t + rb) * slack >= best) == 0ull;
+                }
+                if (drop) {
                     mx = max(mx, 1); // (it returns >= 1 match: all the frames above need to know, see the note at the top)
                     wave_sync();
                     if (lane == 0) frame[f] = nb | (mx << 8) | (any << 16) | (matched << 17) | (nm << 24);
@@ -146,6 +233,10 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
                 path[f] = (uint8_t)b;
                 const int k1 = (int)H->ksum[f + 1];
                 mrow[nm] = (int)H->rowbase[f] + b * ((int)ksumtot - k1) - k1; // entry((f, b) -> x) = rowbase[f] + b nd_f + (x - ksum[f + 1])
+                if constexpr (CONSTRAINED) {
+                    pm[2 * (f + 1)] = m0;
+                    pm[2 * (f + 1) + 1] = m1;
+                }
             }
             if (mine) tot[(f + 1) * G + c] = t;
             vbits = (vbits & ~(1u << (f + 1))) | ((valid ? 1u : 0u) << (f + 1));
@@ -161,12 +252,22 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
             const bool valid = mine && ((vbits >> f) & 1u);
             const double t = mine ? tot[f * G + c] : 0.0;
             if (nm >= 5) {
-                const double r = mine ? R[(size_t)(f + 1) * G + c] : 0.0;
-                if (__ballot(valid && (t + r) * slack >= best) == 0ull) continue;
+                bool drop = false;
+                if constexpr (CONSTRAINED)
+                    drop = !con_feasible(a.con, uni64(pm[2 * f]), uni64(pm[2 * f + 1]), uni64(sfx[2 * (f + 1)]), uni64(sfx[2 * (f + 1) + 1]));
+                if (!drop) {
+                    const double rb = mine ? R[(size_t)(f + 1) * G + c] : 0.0;
+                    drop = __ballot(valid && (t + rb) * slack >= best) == 0ull;
+                }
+                if (drop) continue;
             }
             if (lane == 0) {
                 frame[f + 1] = nm << 24;
                 path[f] = kNoMatch;
+                if constexpr (CONSTRAINED) {
+                    pm[2 * (f + 1)] = pm[2 * f];
+                    pm[2 * (f + 1) + 1] = pm[2 * f + 1];
+                }
             }
             if (mine) tot[(f + 1) * G + c] = t;
             vbits = (vbits & ~(1u << (f + 1))) | ((valid ? 1u : 0u) << (f + 1));
@@ -185,26 +286,7 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
         wave_sync();
     }
 
-    // ---- the row: levels, maxima, keys as model clusters, best conformer
-    const Record r = parse_record(p.lib.data + p.lib.offsets[lig]);
-    {
-        unsigned long long cb0 = 0, cb1 = 0;
-        if (lane < r.ncl) {
-            const int cs = lane ? r.cluster_end[lane - 1] : 0, ce = r.cluster_end[lane];
-            unsigned lm = 0;
-            for (int u = cs; u < ce; ++u) lm |= r.typemask[u];
-            cb0 = p.M.tclus[2u * (lm & 127u)];
-            cb1 = p.M.tclus[2u * (lm & 127u) + 1u];
-        }
-        const bool has = (cb0 | cb1) != 0ull;
-        const unsigned long long bal = __ballot(has);
-        const int lev = __popcll(bal & ((1ull << lane) - 1ull));
-        if (has && lev < nl) { // (scan_ligand's levels: clusters with a candidate, in priority order, at most PMX_MAX_LEVELS)
-            a.levels[(size_t)li * PMX_MAX_LEVELS + lev] = (uint8_t)lane;
-            cbl[2 * lev] = cb0;
-            cbl[2 * lev + 1] = cb1;
-        }
-    }
+    // ---- the row: maxima, keys as model clusters, best conformer
     wave_sync();
     const bool live = mine && c < C;
     a.conf_max[(size_t)li * PMX_MAX_CONFORMERS + lane] = live ? best : 0.0;
@@ -237,13 +319,13 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
 
 // Persistent wavefronts over the call's list (mode 0) or over the ligands an earlier pass handed on (modes 1 - 3): the tables
 // as the product builds them (prepare_ligand, which also writes the status), then the explain walk.
-template <int G, bool TAILS>
+template <int G, bool TAILS, bool CONSTRAINED>
 __global__ __launch_bounds__(64) void explain_kernel(const ScreenParams p, const pmx_xpl::Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int lane0 = lane_id();
     const uint32_t wave_id = blockIdx.x;
     const WaveShape<G> ws = wave_shape<G>(p.M.K, (int)p.max_nodes);
-    const ExplainLds<G> E = explain_lds<G>(ws);
+    const ExplainLds<G> E = explain_lds<G>(ws, CONSTRAINED);
     const uint32_t todo = p.mode == 0 ? a.n
                                       : min(p.mode == 1 ? p.ctl->ovf_count : (p.mode == 2 ? p.ctl->carry_count : p.ctl->retry_count[p.retry_slot ^ 1u]), p.list_cap);
     const uint32_t *list = p.mode == 1 ? p.ovf_list : (p.mode == 2 ? p.carry_list : p.retry_in);
@@ -271,7 +353,7 @@ __global__ __launch_bounds__(64) void explain_kernel(const ScreenParams p, const
         q.flags = PMX_SCORES_F64;
         unsigned char *rec = prepare_ligand<G, false, TAILS>(q, lds, ws, li, wave_id, stat);
         if (!rec) continue;
-        explain_walk<G>(q, lds, E, rec, lig, li, a);
+        explain_walk<G, CONSTRAINED>(q, lds, E, rec, lig, li, a);
     }
 }
 
@@ -297,20 +379,26 @@ __global__ void explain_fixup_kernel(const pmx_xpl::Args a) {
 
 namespace pmx_xpl {
 
-size_t lds_bytes(int G, int K, int max_nodes) {
+size_t lds_bytes(int G, int K, int max_nodes, bool constrained) {
     size_t bytes = 0;
-    pmx::with_lanes(G, [&](auto g) { bytes = pmx_x::explain_lds<decltype(g)::value>(pmx_x::wave_shape<decltype(g)::value>(K, max_nodes)).bytes; });
+    pmx::with_lanes(G, [&](auto g) { bytes = pmx_x::explain_lds<decltype(g)::value>(pmx_x::wave_shape<decltype(g)::value>(K, max_nodes), constrained).bytes; });
     return bytes;
 }
 
-bool launch(int G, bool tails, int mode, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes, const Args &a) {
+template <int G, bool CONSTRAINED>
+static void launch_shape(bool tails, unsigned blocks, unsigned lds, hipStream_t stream, const pmx_x::ScreenParams &p, const Args &a) {
+    if (tails) pmx_x::explain_kernel<G, true, CONSTRAINED><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+    else pmx_x::explain_kernel<G, false, CONSTRAINED><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+}
+
+bool launch(int G, bool tails, bool constrained, int mode, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes, const Args &a) {
     if (bytes != sizeof(pmx_x::ScreenParams)) return false;
     pmx_x::ScreenParams p;
     std::memcpy(&p, params, sizeof p);
     p.mode = mode;
     return pmx::with_lanes(G, [&](auto g) {
-        if (tails) pmx_x::explain_kernel<decltype(g)::value, true><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
-        else pmx_x::explain_kernel<decltype(g)::value, false><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+        if (constrained) launch_shape<decltype(g)::value, true>(tails, blocks, lds, stream, p, a);
+        else launch_shape<decltype(g)::value, false>(tails, blocks, lds, stream, p, a);
     });
 }
 

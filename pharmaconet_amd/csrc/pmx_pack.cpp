@@ -33,7 +33,7 @@ static int pmx_topk_fail(int code, const char *msg) {
     return code;
 }
 extern "C" const char *pmx_last_error(void) { return g_pack_err; }
-extern "C" int pmx_version(void) { return 100; }
+extern "C" int pmx_version(void) { return 101; }
 #else
 int pmx_topk_fail(int code, const char *msg); // error hook in pmx_api.hip
 #endif

@@ -358,7 +358,8 @@ class Explanation:
     match[i]           int [C, nl]: per conformer the key of the first leaf (in `root_tree.iteration()` order) that reaches its
                        maximum - the model cluster (index in `model.node_clusters`) each level is matched to, -1 for None; all -1 where the
                        maximum is 0 (no leaf explains it)
-    status[i]          PMX_LIGAND_* as `screen` reports it"""
+    status[i]          PMX_LIGAND_* as `screen` reports it
+    require, exclude   the constraint it was made with (`explain`): maxima and keys are then over the qualifying leaves only; None without"""
 
     indices: np.ndarray
     conf_max: list
@@ -366,9 +367,17 @@ class Explanation:
     levels: list
     match: list
     status: np.ndarray
+    require: "tuple | None" = None  # normalised: a tuple of groups, each a sorted tuple of model cluster indices
+    exclude: "tuple | None" = None  # a sorted tuple of model cluster indices
 
     def __len__(self) -> int:
         return len(self.indices)
+
+    @property
+    def scores(self) -> np.ndarray:
+        """Per ligand the mean of `conf_max` - the ligand's score (graph_match.py:109), the constrained score of a constrained
+        explanation; NaN for a ligand with a non-zero status."""
+        return np.array([float(np.mean(m)) if st == 0 and m.size else (np.nan if st != 0 else 0.0) for m, st in zip(self.conf_max, self.status)])
 
     @property
     def max(self) -> np.ndarray:
@@ -411,7 +420,8 @@ class Explanation:
 
     def attribution(self, model, library, conformer: int | None = None, weights: dict[str, float] | None = None) -> "Attribution":
         """`attribute` of every row with status 0, at its best conformer (or `conformer`) under that conformer's own key: which nodes
-        carry the explained maximum. `rows` of the result says which row of this explanation each of its rows is."""
+        carry the explained maximum. `rows` of the result says which row of this explanation each of its rows is. A constrained
+        explanation needs nothing more: the reported keys are attributed, and they are the qualifying leaves' keys."""
         rows = [i for i in range(len(self)) if self.status[i] == 0]
         conf = [int(self.best_conformer[i]) if conformer is None else int(conformer) for i in rows]
         keys = []
@@ -458,10 +468,63 @@ def _conformer_counts(library: "DeviceLibrary", idx: np.ndarray) -> np.ndarray:
     return np.where(ok, c.cpu().numpy(), 0)
 
 
-def explain(model, library, indices, weights: dict[str, float] | None = None, device=None) -> Explanation:
+def normalize_constraint(require=None, exclude=None, num_clusters: int | None = None):
+    """`require` (a sequence of groups, each an int or a sequence of ints) and `exclude` (a sequence of ints) as (tuple of sorted tuples,
+    sorted tuple) of model cluster indices. ValueError for a negative index or, with `num_clusters`, an index outside the model; an
+    empty group and a ninth group are kept as they are (`pmx_explain_constrained` refuses them)."""
+    def one(v, what):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}: a model cluster index, not {v!r}")
+        if v < 0 or (num_clusters is not None and v >= num_clusters):
+            raise ValueError(f"{what}: model cluster {int(v)} is outside the model" + (f"'s {num_clusters} clusters" if num_clusters is not None else ""))
+        return int(v)
+
+    groups = []
+    for g in ([] if require is None else require):
+        members = [g] if isinstance(g, (int, np.integer)) else list(g)
+        groups.append(tuple(sorted({one(v, "require") for v in members})))
+    if exclude is not None and isinstance(exclude, (int, np.integer)):
+        exclude = [exclude]
+    return tuple(groups), tuple(sorted({one(v, "exclude") for v in ([] if exclude is None else exclude)}))
+
+
+def _constraint_struct(groups, excluded) -> "_ffi.MatchConstraint":
+    con = _ffi.MatchConstraint()
+    con.n_require = len(groups)
+    for g, members in enumerate(groups[: _ffi.MAX_REQUIRE_GROUPS]):
+        for a in members:
+            con.require[g][a // 64] |= 1 << (a % 64)
+    for a in excluded:
+        con.exclude[a // 64] |= 1 << (a % 64)
+    return con
+
+
+def key_qualifies(key, require, exclude) -> bool:
+    """Does a key (a model cluster or -1 per level) hold a cluster of every group of `require` and none of `exclude` (both normalised)."""
+    have = {int(m) for m in key if m >= 0}
+    return all(have & set(g) for g in require) and not (have & set(exclude))
+
+
+def explain(model, library, indices, weights: dict[str, float] | None = None, device=None, require=None, exclude=None) -> Explanation:
     """Per-conformer maxima and the leaf that reaches each (`pmx_explain`, csrc/pmx_explain.hip) for the library ligands `indices`
     (any order, repeats allowed, at most 65536). `library` is a `DeviceLibrary` or anything `as_packed_library` accepts. Runs on torch's
-    current stream of the device and waits for it."""
+    current stream of the device and waits for it.
+
+    `require` / `exclude`: constrained matching (`pmx_explain_constrained`). `require` is a sequence of groups, each a model cluster
+    index or a sequence of them; `exclude` a sequence of indices (`PharmacophoreModel.clusters_with_nodes` makes either from hotspot
+    nodes). Only leaves whose key holds a cluster of every group and none of `exclude` count: `conf_max`, `scores` and `match` are over
+    those leaves. With both None the call is `pmx_explain` as before."""
+    if require is None and exclude is None:
+        return _run_explain(model, library, indices, weights, device, None)
+    groups, excluded = normalize_constraint(require, exclude)
+    if any(a >= 128 for g in groups for a in g) or any(a >= 128 for a in excluded):
+        raise _ffi.PmxError("constraint: a model has at most 128 clusters (PMX_MAX_MODEL_CLUSTERS)")
+    return _run_explain(model, library, indices, weights, device, (groups, excluded))
+
+
+def _run_explain(model, library, indices, weights, device, constraint, entry: str | None = None) -> Explanation:
+    """`explain`'s call: `constraint` None (`pmx_explain`, or `entry="pmx_explain_constrained"` with a NULL constraint) or normalised
+    (groups, excluded)."""
     torch = _torch()
     lib = _ffi.load()
     idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
@@ -487,8 +550,13 @@ def explain(model, library, indices, weights: dict[str, float] | None = None, de
     try:
         with torch.cuda.device(tdev):
             stream = torch.cuda.current_stream(tdev)
-            _ffi.check(lib.pmx_explain(mh.handle, library.handle, _weights_array(weights), lig.data_ptr(), n, conf_max.data_ptr(),
-                                       match.data_ptr(), levels.data_ptr(), best.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+            outs = (lig.data_ptr(), n, conf_max.data_ptr(), match.data_ptr(), levels.data_ptr(), best.data_ptr(), status.data_ptr(),
+                    ctypes.c_void_p(stream.cuda_stream))
+            if constraint is None and entry != "pmx_explain_constrained":
+                _ffi.check(lib.pmx_explain(mh.handle, library.handle, _weights_array(weights), *outs))
+            else:
+                con = ctypes.byref(_constraint_struct(*constraint)) if constraint is not None else None
+                _ffi.check(lib.pmx_explain_constrained(mh.handle, library.handle, _weights_array(weights), con, *outs))
             stream.synchronize()
     finally:
         if owned is not None:
@@ -506,7 +574,98 @@ def explain(model, library, indices, weights: dict[str, float] | None = None, de
         key = mt[i, :C, :nl].astype(np.int64)
         key[key == NO_MATCH] = -1
         out_mt.append(key)
-    return Explanation(indices=idx.astype(np.int64), conf_max=out_cm, best_conformer=bc, levels=out_lv, match=out_mt, status=st)
+    return Explanation(indices=idx.astype(np.int64), conf_max=out_cm, best_conformer=bc, levels=out_lv, match=out_mt, status=st,
+                       require=constraint[0] if constraint is not None else None, exclude=constraint[1] if constraint is not None else None)
+
+
+def concat_explanations(parts: list) -> Explanation:
+    """Rows of several explanations made with one constraint, in the order given."""
+    first = parts[0]
+    return Explanation(indices=np.concatenate([p.indices for p in parts]), conf_max=[m for p in parts for m in p.conf_max],
+                       best_conformer=np.concatenate([p.best_conformer for p in parts]), levels=[v for p in parts for v in p.levels],
+                       match=[m for p in parts for m in p.match], status=np.concatenate([p.status for p in parts]),
+                       require=first.require, exclude=first.exclude)
+
+
+def _take_rows(ex: Explanation, rows) -> Explanation:
+    rows = [int(r) for r in rows]
+    return Explanation(indices=ex.indices[rows], conf_max=[ex.conf_max[r] for r in rows], best_conformer=ex.best_conformer[rows],
+                       levels=[ex.levels[r] for r in rows], match=[ex.match[r] for r in rows], status=ex.status[rows],
+                       require=ex.require, exclude=ex.exclude)
+
+
+@dataclass
+class ConstrainedScreeningResult:
+    """What `screen_constrained` returns: the k best ligands by constrained score, best first (ties by ascending index).
+
+    indices        int64 [<= k]: library indices of the hits (only ligands with a constrained score > 0 are hits)
+    scores         float64: their constrained scores (the mean over conformers of the best qualifying leaf)
+    unconstrained  float32: their scores in the ordinary screen
+    explanation    the constrained `Explanation` of the hits, in the same order
+    pool           how many ligands, taken in the order of the ordinary screen, were explained under the constraint
+    exact          True when no ligand outside the pool can belong to (or tie with) the hits"""
+
+    indices: np.ndarray
+    scores: np.ndarray
+    unconstrained: np.ndarray
+    explanation: Explanation
+    pool: int
+    exact: bool
+    screen: "ScreeningResult | None" = None  # the ordinary screen it started from
+
+
+def screen_constrained(model, library, topk: int, require=None, exclude=None, weights: dict[str, float] | None = None, pool: int | None = None,
+                       max_pool: int | None = None, device=None) -> ConstrainedScreeningResult:
+    """The exact top-k of the whole library by CONSTRAINED score, from one ordinary screen plus constrained explanations of a pool of its
+    best ligands. A constrained maximum never exceeds the unconstrained one, so with the ligands ordered by the screen's float32 score
+    (descending, ties by index, non-zero status last), u the score of the first ligand outside the pool and c_k the k-th best
+    constrained score inside it, the pool's top-k is the library's as soon as c_k > float64(nextafter(float32(u), +inf)): the one-ulp step
+    covers the float32 rounding of the screen's score and its summation order, the strict `>` a tie from outside. Until then the pool
+    doubles (only the new ligands are explained), from `pool` (default max(4 topk, 4096)) up to the library or `max_pool`, where the
+    result comes back with `exact` False."""
+    torch = _torch()
+    topk = int(topk)
+    if topk <= 0:
+        raise ValueError("topk must be positive")
+    groups, excluded = normalize_constraint(require, exclude)
+    owned = None
+    if not isinstance(library, DeviceLibrary):
+        owned = library = DeviceLibrary(as_packed_library(library), device)
+    try:
+        res = screen(model, library, weights=weights)
+        sc, st = res.scores.cpu().numpy(), res.status.cpu().numpy()
+        total = len(sc)
+        rank = np.where(st != 0, -np.inf, np.nan_to_num(sc.astype(np.float64), nan=-np.inf))
+        order = np.lexsort((np.arange(total), -rank))  # (the order of ScreeningResult.explain)
+        n = min(total, max(4 * topk, 4096) if pool is None else max(int(pool), 1))
+        if max_pool is not None:
+            n = min(n, max(int(max_pool), 1))
+        parts, done, con = [], 0, []
+        while True:
+            for lo in range(done, n, 65536):
+                parts.append(explain(model, library, order[lo : min(lo + 65536, n)], weights=weights, require=groups, exclude=excluded))
+                con.append(parts[-1].scores)
+            done = n
+            cs = np.nan_to_num(np.concatenate(con) if con else np.zeros(0), nan=0.0)
+            hits = np.flatnonzero(cs > 0)
+            best = hits[np.lexsort((order[hits], -cs[hits]))][:topk]  # rows of the pool: descending constrained score, ascending index
+            if n >= total:
+                exact = True
+            elif len(best) < topk or st[order[n]] != 0:
+                exact = st[order[n]] != 0  # (nothing scored is left outside the pool)
+            else:
+                u = np.float32(sc[order[n]])
+                exact = bool(cs[best[-1]] > np.float64(np.nextafter(u, np.float32(np.inf))))
+            if exact or (max_pool is not None and n >= int(max_pool)):
+                break
+            n = min(total, 2 * n if max_pool is None else min(2 * n, int(max_pool)))
+        ex = concat_explanations(parts) if parts else explain(model, library, [], weights=weights, require=groups, exclude=excluded)
+    finally:
+        if owned is not None:
+            torch.cuda.synchronize(torch.device("cuda", owned.device))
+            owned.close()
+    return ConstrainedScreeningResult(indices=order[best].astype(np.int64), scores=cs[best].astype(np.float64), unconstrained=sc[order[best]].astype(np.float32),
+                                      explanation=_take_rows(ex, best), pool=int(n), exact=bool(exact), screen=res if owned is None else None)
 
 
 KEY_INVALID = 4  # include/pmx.h PMX_LIGAND_KEY_INVALID

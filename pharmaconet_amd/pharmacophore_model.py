@@ -333,18 +333,29 @@ class PharmacophoreModel:
 
         return score_one(self, ligand, weights)
 
-    def scoring_detail(self, ligand, weights: dict[str, float] | None = None) -> dict:
+    def clusters_with_nodes(self, nodes) -> list[int]:
+        """The model clusters (indices into `node_clusters`) that contain any of the model nodes `nodes` (an index or a sequence of
+        them): a ready-made require group ("any cluster that holds this hotspot node") or exclude list for `explain`."""
+        flat = self.flat
+        wanted = 0
+        for m in ([nodes] if isinstance(nodes, (int, np.integer)) else nodes):
+            if not 0 <= int(m) < flat.num_nodes:
+                raise ValueError(f"model node {int(m)} is outside the model's {flat.num_nodes} nodes")
+            wanted |= 1 << int(m)
+        return [a for a, members in enumerate(cluster_node_sets(flat)) if members & wanted]
+
+    def scoring_detail(self, ligand, weights: dict[str, float] | None = None, require=None, exclude=None) -> dict:
         """`_scoring` with what the score is made of: `score` (the mean of `conf_max`, graph_match.py:109), `max` (`GraphMatcher._run_max`,
         graph_match.py:111-112), `conf_max` (the per-conformer maxima whose mean is the score), `best_conformer`, `levels` and `match`
         (the key of the leaf that reaches each conformer's maximum), `pairs` (the best conformer's match, readable). Takes what
-        `_scoring` takes."""
+        `_scoring` takes. With `require` / `exclude` (see `engine.explain`) all of it is over the qualifying leaves: the constrained score."""
         from .engine import explain
         from .library import as_packed_library
 
         packed = as_packed_library(ligand)
         if len(packed) != 1:
             raise ValueError("scoring_detail takes exactly one ligand")
-        ex = explain(self, packed, [0], weights=weights)
+        ex = explain(self, packed, [0], weights=weights, require=require, exclude=exclude)
         if int(ex.status[0]) != 0:
             n, c, _ = packed.header(0)
             raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
@@ -388,6 +399,12 @@ class PharmacophoreModel:
         from .engine import explain
 
         return explain(self, library, indices, weights=weights, **kwargs)
+
+    def screen_constrained(self, library, topk: int, require=None, exclude=None, weights: dict[str, float] | None = None, **kwargs):
+        """The exact top-k by constrained score (`engine.screen_constrained`)."""
+        from .engine import screen_constrained
+
+        return screen_constrained(self, library, topk, require=require, exclude=exclude, weights=weights, **kwargs)
 
     def screen(self, library, weights: dict[str, float] | None = None, topk: int | None = None, **kwargs):
         """Batched `screening.py:46-75`: score every ligand of a packed library on the GPU.

@@ -32,6 +32,10 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--explain", type=int, default=0, metavar="K", help="also explain the K best hits (best conformer and its cluster matches)")
         cfg.add_argument("--explain_out", type=str, default=None, help="CSV of the explained hits (default: <out>.explain.csv)")
         cfg.add_argument("--explain_nodes", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per pharmacophore node of each explained hit and the node's share of the hit's best conformer maximum")
+        cfg.add_argument("--require", action="append", default=[], metavar="LIST", help="constrained matching: comma-separated model cluster indices, one of which a hit's match must hold (repeatable: one group each)")
+        cfg.add_argument("--exclude", type=str, default=None, metavar="LIST", help="constrained matching: comma-separated model cluster indices that a hit's match must not hold")
+        cfg.add_argument("--constrained_out", type=str, default=None, metavar="PATH", help="CSV of the best hits by constrained score (needed with --require / --exclude)")
+        cfg.add_argument("--constrained_k", type=int, default=100, metavar="K", help="hits in --constrained_out")
         par = self.add_argument_group("parameter")
         par.add_argument("--hydrophobic", type=float, default=1.0, help="weight for hydrophobic carbon")
         par.add_argument("--aromatic", type=float, default=4.0, help="weight for aromatic ring")
@@ -115,6 +119,15 @@ def main(argv=None) -> None:
     args = parser.parse_args(argv)
     if args.explain_nodes and args.explain <= 0:
         parser.error("--explain_nodes needs --explain K")
+    if (args.require or args.exclude is not None) and not args.constrained_out:
+        parser.error("--require / --exclude need --constrained_out PATH")
+    if args.constrained_out and args.constrained_k <= 0:
+        parser.error("--constrained_k must be positive")
+    try:
+        require = [[int(v) for v in g.split(",")] for g in args.require]
+        exclude = [int(v) for v in args.exclude.split(",")] if args.exclude else []
+    except ValueError:
+        parser.error("--require / --exclude take comma-separated model cluster indices")
     model = PharmacophoreModel.load(args.pharmacophore_model)
     weight = dict(
         Cation=args.cation,
@@ -134,6 +147,27 @@ def main(argv=None) -> None:
         write_explain_csv(out, names, scores, status, model, lib, weight, args.explain)
         if args.explain_nodes:
             write_explain_nodes_csv(Path(args.explain_nodes), names, scores, status, model, lib, weight, args.explain)
+    if args.constrained_out:
+        write_constrained_csv(Path(args.constrained_out), names, model, lib, weight, args.constrained_k, require, exclude)
+
+
+def write_constrained_csv(out: Path, names: list[str], model, lib, weights, k: int, require, exclude) -> None:
+    """The k best ligands by constrained score (`engine.screen_constrained`: only matches that hold a cluster of every `require` group
+    and none of `exclude` count), best first: the constrained score, the ordinary score, the best conformer under the constraint and its
+    matched pairs in the format of the explain CSV."""
+    from .engine import screen_constrained
+
+    res = screen_constrained(model, lib, k, require=require, exclude=exclude, weights=weights)
+    if not res.exact:
+        print("warning: the constrained hits are not certified exact (the pool of examined ligands was capped)", file=sys.stderr)
+    ex = res.explanation
+    types = model.flat.cluster_type
+    with open(out, "w") as w:
+        w.write("rank,path,constrained_score,score,best_conformer,matches\n")
+        for r, i in enumerate(res.indices):
+            c = int(ex.best_conformer[r])
+            pairs = [f"{lc}->{int(m)}:{types[int(m)]}" for lc, m in zip(ex.levels[r], ex.match[r][c]) if m >= 0] if c >= 0 else []
+            w.write(f"{r + 1},{names[int(i)]},{float(res.scores[r])},{float(res.unconstrained[r])},{c},{' '.join(pairs)}\n")
 
 
 def write_explain_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int) -> None:
