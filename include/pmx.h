@@ -359,6 +359,31 @@ int pmx_explain_constrained(const pmx_model *model, const pmx_library *lib, cons
                             uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev, int32_t *status_dev, void *stream);
 
 /*
+ * The other good binding modes: per listed ligand, per conformer c and per mode m < n_modes, the m-th entry of that conformer's ranked
+ * leaf list - the leaves of the reference's tree (`root_tree.iteration()`) that hold c with a score > 0 (and qualify, when a constraint
+ * is given), by descending score, equal scores in iteration order (the rule that makes pmx_explain's key "the first leaf"). Values are
+ * the float64 leaf totals as the product walker sums them, so mode 0 is bit for bit pmx_explain (constraint = NULL) or
+ * pmx_explain_constrained: maxima, keys, levels, best conformer and status.
+ *   mode_max_dev          double [n][n_modes][PMX_MAX_CONFORMERS]: the totals, non-increasing in m; 0 for entries beyond the number of such
+ *                         leaves and for lanes >= C
+ *   mode_match_dev        uint8 [n][n_modes][PMX_MAX_CONFORMERS][PMX_MAX_LEVELS]: their keys in match_dev's format; 0xFF throughout where the
+ *                         value is 0
+ *   levels_dev, status_dev  as pmx_explain's
+ *   best_conformer_dev    defined on mode 0: the smallest c with the largest mode_max[.][0][c] (-1 for a ligand with a non-zero status)
+ * A ligand with a non-zero status has NaN in every mode. 1 <= n_modes <= PMX_MAX_MODES and n * n_modes <= PMX_EXPLAIN_MAX, otherwise
+ * PMX_ERR_INVALID; the constraint is checked as pmx_explain_constrained checks it; n = 0 succeeds. Statuses, stream ordering and
+ * workspace use are pmx_explain's, its slice, large-slice and arena passes included. One wavefront walks a ligand's tree once for all
+ * modes (pmx_explain.hip, the MODES kernels): a subtree is left out only when no leaf in it can enter any conformer's list, so the call
+ * costs more than pmx_explain the further the n_modes-th value lies below the maximum. There is no ranking of modes across conformers: a
+ * leaf holds a subset of the conformers, and the reference defines none.
+ */
+#define PMX_MAX_MODES 8
+int pmx_explain_modes(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES],
+                      const pmx_match_constraint *constraint /* NULL = none */, int n_modes, const uint64_t *ligands_dev, uint32_t n,
+                      double *mode_max_dev, uint8_t *mode_match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev, int32_t *status_dev,
+                      void *stream);
+
+/*
  * Which ligand nodes carry a leaf's total: row i takes library ligand ligands_dev[i], conformer conformer_dev[i] and a key key_dev[i] -
  * per tree level a model cluster or 0xFF for None, the format of pmx_explain's match_dev rows - and answers with the entries the
  * reference's tree adds up for that leaf, term by term. All values are for that conformer c; lines of match_utils.py, graph_match.py, tree.py.

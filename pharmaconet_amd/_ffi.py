@@ -90,6 +90,7 @@ class ScoreStats(ctypes.Structure):
 
 
 MAX_REQUIRE_GROUPS = 8
+MAX_MODES = 8  # include/pmx.h PMX_MAX_MODES
 
 
 class MatchConstraint(ctypes.Structure):
@@ -180,6 +181,11 @@ SIGNATURES = {
     "pmx_explain_constrained": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(MatchConstraint), ctypes.c_void_p, ctypes.c_uint32,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "pmx_explain_modes": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(MatchConstraint), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     ),
     "pmx_attribute": (

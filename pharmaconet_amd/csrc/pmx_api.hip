@@ -1154,7 +1154,7 @@ static int explain_screen(const pmx_model *model, const pmx_library *lib, const 
 
     pmx_xpl::launch_init(a, stream);
     ctl_clear_kernel<<<dim3((sizeof(Ctl) / 4 + 255) / 256), dim3(256), 0, stream>>>(xctl, 1);
-    const size_t lds = pmx_xpl::lds_bytes(G, model->dm.K, (int)p.max_nodes, constrained);
+    const size_t lds = pmx_xpl::lds_bytes(G, model->dm.K, (int)p.max_nodes, constrained, (int)a.n_modes);
     const uint32_t full = (uint32_t)ws.num_cu * pl.waves_per_cu;
     bool ok = true;
     auto launch = [&](int mode, uint32_t blocks) { ok &= pmx_xpl::launch(G, tails, constrained, mode, std::max(1u, blocks), (unsigned)lds, stream, &p, sizeof p, a); };
@@ -1177,9 +1177,10 @@ static int explain_screen(const pmx_model *model, const pmx_library *lib, const 
     return PMX_OK;
 }
 
-// pmx_explain and pmx_explain_constrained: one driver; without a constraint the kernels are the ones that never look at one.
+// pmx_explain, pmx_explain_constrained and pmx_explain_modes: one driver; without a constraint the kernels are the ones that never look at
+// one. n_modes 0: one maximum and one key per conformer; otherwise pmx_explain_modes' outputs, n_modes of each.
 static int explain_call(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const pmx_match_constraint *constraint,
-                        const uint64_t *ligands_dev, uint32_t n, double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev,
+                        int n_modes, const uint64_t *ligands_dev, uint32_t n, double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev,
                         int32_t *status_dev, void *stream_) {
     if (!model || !lib || !weights) return fail(PMX_ERR_INVALID, "null argument");
     pmx_match_constraint con;
@@ -1204,13 +1205,14 @@ static int explain_call(const pmx_model *model, const pmx_library *lib, const fl
         con.exclude[1] = constraint->exclude[1];
     }
     if (n > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "more than %d ligands in one explain call", PMX_EXPLAIN_MAX);
+    if ((uint64_t)n * (uint64_t)n_modes > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "%u ligands x %d modes: more than %d in one call", n, n_modes, PMX_EXPLAIN_MAX);
     if (n == 0) return PMX_OK;
     if (!ligands_dev || !conf_max_dev || !match_dev || !levels_dev || !best_conformer_dev || !status_dev) return fail(PMX_ERR_INVALID, "null argument");
     if (model->device != lib->device) return fail(PMX_ERR_INVALID, "model and library live on different devices");
     HIPCHECK(hipSetDevice(lib->device));
     const Weights W = to_weights(weights);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const pmx_xpl::Args a{ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, con};
+    const pmx_xpl::Args a{ligands_dev, n, (uint32_t)n_modes, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, con};
     const bool constrained = constraint != nullptr;
     const HeldWs held = hold_screen(lib->device, stream);
     int rc = PMX_OK;
@@ -1221,13 +1223,20 @@ static int explain_call(const pmx_model *model, const pmx_library *lib, const fl
 
 extern "C" int pmx_explain(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev, uint32_t n,
                            double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev, int32_t *status_dev, void *stream) {
-    return explain_call(model, lib, weights, nullptr, ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, stream);
+    return explain_call(model, lib, weights, nullptr, 0, ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, stream);
 }
 
 extern "C" int pmx_explain_constrained(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const pmx_match_constraint *constraint,
                                        const uint64_t *ligands_dev, uint32_t n, double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev,
                                        int32_t *best_conformer_dev, int32_t *status_dev, void *stream) {
-    return explain_call(model, lib, weights, constraint, ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, stream);
+    return explain_call(model, lib, weights, constraint, 0, ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, stream);
+}
+
+extern "C" int pmx_explain_modes(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const pmx_match_constraint *constraint,
+                                 int n_modes, const uint64_t *ligands_dev, uint32_t n, double *mode_max_dev, uint8_t *mode_match_dev, uint8_t *levels_dev,
+                                 int32_t *best_conformer_dev, int32_t *status_dev, void *stream) {
+    if (n_modes < 1 || n_modes > PMX_MAX_MODES) return fail(PMX_ERR_INVALID, "%d modes (1 to %d)", n_modes, PMX_MAX_MODES);
+    return explain_call(model, lib, weights, constraint, n_modes, ligands_dev, n, mode_max_dev, mode_match_dev, levels_dev, best_conformer_dev, status_dev, stream);
 }
 
 // ------------------------------------------------------------------------------------ attribution (pmx_attribute.hip)

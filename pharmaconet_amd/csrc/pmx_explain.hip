@@ -23,6 +23,17 @@
 // bound test above holds with the constrained running maximum, and a child with >= 5 matches is also dropped when no leaf below it can
 // qualify (an excluded cluster on its path, or a require group with no cluster on the path or among the candidates of the levels
 // below). A subtree with fewer matches that cannot qualify is walked for its match count alone.
+//
+// Modes (pmx_explain_modes): per conformer the M = n_modes best leaves instead of the best one - the leaves that hold the conformer with
+// a score > 0 (and qualify, under a constraint), by descending total, equal totals in iteration order. The MODES instantiation keeps per
+// lane the M totals, sorted, in LDS and the M keys (as candidate numbers) in the row's own output block, turned into model clusters in
+// place at the end. A leaf enters the list iff its total is strictly above the lane's M-th value, behind every entry >= it: a later leaf
+// never overtakes an equal earlier one, so the list is the stable order above and its head, updated by the same strict `>`, is
+// pmx_explain's answer bit for bit. The bound follows the M-th value: a child with >= 5 matches is dropped when
+// (total + R) * kBoundSlack < the running M-th value, strictly, for every conformer it holds. The running M-th value of a conformer never
+// exceeds its final one (entries only rise), so every leaf below a dropped child is strictly below the final M-th value of every conformer
+// it holds and belongs to no list; a leaf that ties the M-th value is never dropped, and the walked leaves arrive in iteration order, so the
+// lists are those of the full tree. The feasibility drops of the constrained walker do not look at values and are unchanged.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstring>
@@ -63,7 +74,7 @@ __host__ __device__ inline ExplainLds<G> explain_lds(const WaveShape<G> &ws, boo
         e.sfx = o; // u64 [PMX_MAX_LEVELS + 1][2]: model clusters that are candidates of level f or of a level below it
         o += 16 * (PMX_MAX_LEVELS + 1);
     }
-    e.bytes = o;
+    e.bytes = o; // (the MODES walker's totals lie behind: double [n_modes][G], conformer c's descending; its keys live in the row's output block)
     return e;
 }
 
@@ -86,9 +97,18 @@ __device__ inline void candidate_bit(unsigned long long w0, unsigned long long w
     b1 = b < n0 ? 0ull : xw;
 }
 
+// Candidate b of such a level as a model cluster.
+__device__ inline uint8_t candidate_cluster(unsigned long long w0, unsigned long long w1, int b) {
+    const int n0 = __popcll(w0);
+    unsigned long long xw = b < n0 ? w0 : w1;
+    for (int j = b < n0 ? b : b - n0; j > 0; --j) xw &= xw - 1ull;
+    return (uint8_t)((b < n0 ? 0 : 64) + __ffsll(xw) - 1);
+}
+
 // The tree of one prepared ligand (tables at `rec`), maxima and keys into row li of the output. Lane c < G is conformer c.
 // CONSTRAINED: only leaves whose key qualifies under a.con update a maximum (see the note at the top).
-template <int G, bool CONSTRAINED>
+// MODES: the a.n_modes best leaves per conformer; a.conf_max and a.match are then [n][n_modes][...] (see the note at the top).
+template <int G, bool CONSTRAINED, bool MODES>
 __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const ExplainLds<G> &E, const unsigned char *rec, uint64_t lig, uint32_t li,
                              const pmx_xpl::Args &a) {
     const int lane = lane_id();
@@ -108,6 +128,11 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
     unsigned long long *cbl = reinterpret_cast<unsigned long long *>(lds + E.cb);
     unsigned long long *pm = reinterpret_cast<unsigned long long *>(lds + E.pm);
     unsigned long long *sfx = reinterpret_cast<unsigned long long *>(lds + E.sfx);
+    // MODES: conformer c's totals at mv[m * G + c], mode m's key at mkey + m * kModeKeys
+    const int M = MODES ? uni((int)a.n_modes) : 1;
+    double *mv = MODES ? reinterpret_cast<double *>(lds + E.bytes) : nullptr;
+    constexpr size_t kModeKeys = (size_t)PMX_MAX_CONFORMERS * PMX_MAX_LEVELS;
+    uint8_t *mkey = MODES ? a.match + ((size_t)li * M * PMX_MAX_CONFORMERS + c) * PMX_MAX_LEVELS : nullptr;
 
     // ---- the levels of the row and the model clusters that are candidates of each
     const Record r = parse_record(p.lib.data + p.lib.offsets[lig]);
@@ -148,10 +173,14 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
     }
 
     uint32_t vbits = (mine && c < C) ? 1u : 0u; // bit f: conformer c is in the pair_scores of frame f's node (tree.py:78-84)
-    double best = 0.0;                           // running maximum of conformer c (graph_match.py:105-108)
+    double best = 0.0;                           // running maximum of conformer c (graph_match.py:105-108); MODES: its running M-th value
     if (mine) {
         tot[c] = 0.0;
-        for (int l = 0; l < PMX_MAX_LEVELS; ++l) key[c * PMX_MAX_LEVELS + l] = kNoMatch;
+        if constexpr (MODES) {
+            for (int m = 0; m < M; ++m) mv[m * G + c] = 0.0; // (the keys are the row's: 0xFF throughout, explain_modes_init_kernel)
+        } else {
+            for (int l = 0; l < PMX_MAX_LEVELS; ++l) key[c * PMX_MAX_LEVELS + l] = kNoMatch;
+        }
     }
     if (lane == 0) frame[0] = 0;
     wave_sync();
@@ -164,8 +193,19 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
             if (qualifies && mine && ((vbits >> f) & 1u)) {
                 const double t = tot[f * G + c];
                 if (t > best) {
-                    best = t;
-                    for (int l = 0; l < nl; ++l) key[c * PMX_MAX_LEVELS + l] = path[l];
+                    if constexpr (MODES) { // behind every entry >= t; the entries below move down one place, the last one leaves
+                        int at = M - 1;
+                        for (; at > 0 && mv[(at - 1) * G + c] < t; --at) {
+                            mv[at * G + c] = mv[(at - 1) * G + c];
+                            for (int l = 0; l < nl; ++l) mkey[at * kModeKeys + l] = mkey[(at - 1) * kModeKeys + l];
+                        }
+                        mv[at * G + c] = t;
+                        for (int l = 0; l < nl; ++l) mkey[at * kModeKeys + l] = path[l];
+                        best = mv[(M - 1) * G + c];
+                    } else {
+                        best = t;
+                        for (int l = 0; l < nl; ++l) key[c * PMX_MAX_LEVELS + l] = path[l];
+                    }
                 }
             }
             const int ret = (uni(frame[f]) >> 17) & 1;
@@ -289,20 +329,33 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
     // ---- the row: maxima, keys as model clusters, best conformer
     wave_sync();
     const bool live = mine && c < C;
-    a.conf_max[(size_t)li * PMX_MAX_CONFORMERS + lane] = live ? best : 0.0;
-    if (live) {
-        uint8_t *out = a.match + ((size_t)li * PMX_MAX_CONFORMERS + c) * PMX_MAX_LEVELS;
-        for (int l = 0; l < nl; ++l) {
-            const int b = key[c * PMX_MAX_LEVELS + l];
-            uint8_t m = kNoMatch;
-            if (b != kNoMatch) {
-                const unsigned long long w0 = cbl[2 * l], w1 = cbl[2 * l + 1];
-                const int n0 = __popcll(w0);
-                unsigned long long xw = b < n0 ? w0 : w1;
-                for (int j = b < n0 ? b : b - n0; j > 0; --j) xw &= xw - 1ull;
-                m = (uint8_t)((b < n0 ? 0 : 64) + __ffsll(xw) - 1);
+    if constexpr (MODES) {
+        for (int m = 0; m < M; ++m) {
+            const double v = live ? mv[m * G + c] : 0.0;
+            a.conf_max[((size_t)li * M + m) * PMX_MAX_CONFORMERS + lane] = v;
+            if (v > 0.0) // (a place no leaf took keeps its 0xFF)
+                for (int l = 0; l < nl; ++l) {
+                    uint8_t &k = mkey[m * kModeKeys + l];
+                    if (k != kNoMatch) k = candidate_cluster(cbl[2 * l], cbl[2 * l + 1], k);
+                }
+        }
+        best = live ? mv[c] : 0.0; // (the best conformer is mode 0's)
+    } else {
+        a.conf_max[(size_t)li * PMX_MAX_CONFORMERS + lane] = live ? best : 0.0;
+        if (live) {
+            uint8_t *out = a.match + ((size_t)li * PMX_MAX_CONFORMERS + c) * PMX_MAX_LEVELS;
+            for (int l = 0; l < nl; ++l) {
+                const int b = key[c * PMX_MAX_LEVELS + l];
+                uint8_t m = kNoMatch;
+                if (b != kNoMatch) {
+                    const unsigned long long w0 = cbl[2 * l], w1 = cbl[2 * l + 1];
+                    const int n0 = __popcll(w0);
+                    unsigned long long xw = b < n0 ? w0 : w1;
+                    for (int j = b < n0 ? b : b - n0; j > 0; --j) xw &= xw - 1ull;
+                    m = (uint8_t)((b < n0 ? 0 : 64) + __ffsll(xw) - 1);
+                }
+                out[l] = m;
             }
-            out[l] = m;
         }
     }
     // smallest conformer with the largest maximum
@@ -319,7 +372,7 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
 
 // Persistent wavefronts over the call's list (mode 0) or over the ligands an earlier pass handed on (modes 1 - 3): the tables
 // as the product builds them (prepare_ligand, which also writes the status), then the explain walk.
-template <int G, bool TAILS, bool CONSTRAINED>
+template <int G, bool TAILS, bool CONSTRAINED, bool MODES>
 __global__ __launch_bounds__(64) void explain_kernel(const ScreenParams p, const pmx_xpl::Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int lane0 = lane_id();
@@ -349,11 +402,12 @@ __global__ __launch_bounds__(64) void explain_kernel(const ScreenParams p, const
         ScreenParams q = p;
         q.first = lig - (uint64_t)li;
         q.status = a.status;
-        q.scores = reinterpret_cast<float *>(a.conf_max + (size_t)li * (PMX_MAX_CONFORMERS - 1));
+        if constexpr (MODES) q.scores = reinterpret_cast<float *>(a.conf_max + (size_t)li * (a.n_modes * PMX_MAX_CONFORMERS - 1));
+        else q.scores = reinterpret_cast<float *>(a.conf_max + (size_t)li * (PMX_MAX_CONFORMERS - 1));
         q.flags = PMX_SCORES_F64;
         unsigned char *rec = prepare_ligand<G, false, TAILS>(q, lds, ws, li, wave_id, stat);
         if (!rec) continue;
-        explain_walk<G, CONSTRAINED>(q, lds, E, rec, lig, li, a);
+        explain_walk<G, CONSTRAINED, MODES>(q, lds, E, rec, lig, li, a);
     }
 }
 
@@ -375,20 +429,40 @@ __global__ void explain_fixup_kernel(const pmx_xpl::Args a) {
     if (i % PMX_MAX_CONFORMERS == 0) a.best[li] = -1;
 }
 
+// The same for the rows of pmx_explain_modes: a.conf_max is [n][n_modes][PMX_MAX_CONFORMERS], a.match [n][n_modes][PMX_MAX_CONFORMERS][PMX_MAX_LEVELS].
+__global__ void explain_modes_init_kernel(const pmx_xpl::Args a) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n = a.n, nm = n * a.n_modes;
+    if (i < nm * PMX_MAX_CONFORMERS) a.conf_max[i] = 0.0;
+    if (i < n * PMX_MAX_LEVELS) a.levels[i] = kNoLevel;
+    if (i < n) a.best[i] = 0;
+    for (size_t j = i; j < nm * PMX_MAX_CONFORMERS * PMX_MAX_LEVELS; j += (size_t)gridDim.x * blockDim.x) a.match[j] = kNoMatch;
+}
+
+__global__ void explain_modes_fixup_kernel(const pmx_xpl::Args a) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t row = (size_t)a.n_modes * PMX_MAX_CONFORMERS;
+    if (i >= (size_t)a.n * row) return;
+    const size_t li = i / row;
+    if (a.status[li] == PMX_LIGAND_OK) return;
+    a.conf_max[i] = __builtin_nan("");
+    if (i % row == 0) a.best[li] = -1;
+}
+
 } // namespace pmx_x
 
 namespace pmx_xpl {
 
-size_t lds_bytes(int G, int K, int max_nodes, bool constrained) {
+size_t lds_bytes(int G, int K, int max_nodes, bool constrained, int n_modes) {
     size_t bytes = 0;
-    pmx::with_lanes(G, [&](auto g) { bytes = pmx_x::explain_lds<decltype(g)::value>(pmx_x::wave_shape<decltype(g)::value>(K, max_nodes), constrained).bytes; });
+    pmx::with_lanes(G, [&](auto g) { bytes = pmx_x::explain_lds<decltype(g)::value>(pmx_x::wave_shape<decltype(g)::value>(K, max_nodes), constrained).bytes + (size_t)n_modes * decltype(g)::value * 8; });
     return bytes;
 }
 
-template <int G, bool CONSTRAINED>
+template <int G, bool CONSTRAINED, bool MODES>
 static void launch_shape(bool tails, unsigned blocks, unsigned lds, hipStream_t stream, const pmx_x::ScreenParams &p, const Args &a) {
-    if (tails) pmx_x::explain_kernel<G, true, CONSTRAINED><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
-    else pmx_x::explain_kernel<G, false, CONSTRAINED><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+    if (tails) pmx_x::explain_kernel<G, true, CONSTRAINED, MODES><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+    else pmx_x::explain_kernel<G, false, CONSTRAINED, MODES><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
 }
 
 bool launch(int G, bool tails, bool constrained, int mode, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes, const Args &a) {
@@ -396,21 +470,25 @@ bool launch(int G, bool tails, bool constrained, int mode, unsigned blocks, unsi
     pmx_x::ScreenParams p;
     std::memcpy(&p, params, sizeof p);
     p.mode = mode;
+    const bool modes = a.n_modes > 0;
     return pmx::with_lanes(G, [&](auto g) {
-        if (constrained) launch_shape<decltype(g)::value, true>(tails, blocks, lds, stream, p, a);
-        else launch_shape<decltype(g)::value, false>(tails, blocks, lds, stream, p, a);
+        constexpr int L = decltype(g)::value;
+        if (modes) constrained ? launch_shape<L, true, true>(tails, blocks, lds, stream, p, a) : launch_shape<L, false, true>(tails, blocks, lds, stream, p, a);
+        else constrained ? launch_shape<L, true, false>(tails, blocks, lds, stream, p, a) : launch_shape<L, false, false>(tails, blocks, lds, stream, p, a);
     });
 }
 
 void launch_init(const Args &a, hipStream_t stream) {
-    const size_t n = (size_t)a.n * PMX_MAX_CONFORMERS;
+    const size_t n = (size_t)a.n * std::max<uint32_t>(a.n_modes, 1) * PMX_MAX_CONFORMERS;
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 65535);
-    pmx_x::explain_init_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(a);
+    if (a.n_modes > 0) pmx_x::explain_modes_init_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(a);
+    else pmx_x::explain_init_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(a);
 }
 
 void launch_fixup(const Args &a, hipStream_t stream) {
-    const size_t n = (size_t)a.n * PMX_MAX_CONFORMERS;
-    pmx_x::explain_fixup_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(a);
+    const size_t n = (size_t)a.n * std::max<uint32_t>(a.n_modes, 1) * PMX_MAX_CONFORMERS;
+    if (a.n_modes > 0) pmx_x::explain_modes_fixup_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(a);
+    else pmx_x::explain_fixup_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(a);
 }
 
 } // namespace pmx_xpl

@@ -232,11 +232,19 @@ class ScreeningResult:
     def explain(self, k: int, model=None, library=None, weights: dict[str, float] | None = None) -> "Explanation":
         """`explain` of this screen's k best ligands (best first), without scoring the library again. `model`, `library` and `weights`
         default to what `screen` was called with."""
+        model, library, weights = self._scored(model, library, weights)
+        return explain(model, library, self._best(k), weights=weights)
+
+    def _scored(self, model, library, weights):
         model = model if model is not None else self.model
         library = library if library is not None else self.library
         weights = self.weights if weights is None else weights
         if model is None or library is None:
             raise ValueError("this result does not know its library (it was not given as a DeviceLibrary or a PackedLibrary): pass it")
+        return model, library, weights
+
+    def _best(self, k: int) -> np.ndarray:
+        """Library indices of this screen's k best ligands, best first."""
         if self.topk_indices is not None and int(self.topk_indices.numel()) >= k:
             top = self.topk_indices.cpu().numpy()[:k]
             idx = top[top >= 0] - self.index_base  # (global indices of a sharded screen -> library indices)
@@ -244,8 +252,12 @@ class ScreeningResult:
             sc = self.scores.cpu().numpy().astype(np.float64)
             key = np.where(self.status.cpu().numpy() != 0, -np.inf, np.nan_to_num(sc, nan=-np.inf))
             idx = np.lexsort((np.arange(len(sc)), -key))[:k] + self.first
-        idx = np.asarray([i for i in idx if i >= 0], dtype=np.uint64)
-        return explain(model, library, idx, weights=weights)
+        return np.asarray([i for i in idx if i >= 0], dtype=np.uint64)
+
+    def modes(self, k: int, modes: int = 4, model=None, library=None, weights: dict[str, float] | None = None, require=None, exclude=None) -> "ModeSet":
+        """`explain_modes` of this screen's k best ligands (the rows of `explain(k)`): the `modes` best binding modes per conformer."""
+        model, library, weights = self._scored(model, library, weights)
+        return explain_modes(model, library, self._best(k), modes=modes, weights=weights, require=require, exclude=exclude)
 
 
 def _weights_array(weights):
@@ -592,6 +604,124 @@ def _take_rows(ex: Explanation, rows) -> Explanation:
     return Explanation(indices=ex.indices[rows], conf_max=[ex.conf_max[r] for r in rows], best_conformer=ex.best_conformer[rows],
                        levels=[ex.levels[r] for r in rows], match=[ex.match[r] for r in rows], status=ex.status[rows],
                        require=ex.require, exclude=ex.exclude)
+
+
+@dataclass
+class ModeSet:
+    """What `explain_modes` returns: per listed ligand and conformer the `modes` best leaves of the reference's tree - those that hold the
+    conformer with a score > 0 (and qualify under `require` / `exclude`), by descending score, equal scores in `root_tree.iteration()`
+    order. Row i is cut to that ligand's conformers C and tree levels nl.
+
+    values[i]          float64 [modes, C]: the leaf totals, non-increasing along the modes; 0 where the conformer has fewer such leaves;
+                       values[i][0] is `Explanation.conf_max[i]`; NaN [modes, 1] for a ligand with a non-zero status
+    match[i]           int [modes, C, nl]: their keys (`Explanation.match`), all -1 where the value is 0
+    levels, best_conformer, status, indices, require, exclude   as `Explanation`'s; the best conformer is mode 0's"""
+
+    indices: np.ndarray
+    modes: int
+    values: list
+    match: list
+    levels: list
+    best_conformer: np.ndarray
+    status: np.ndarray
+    require: "tuple | None" = None
+    exclude: "tuple | None" = None
+
+    def __len__(self) -> int:
+        return len(self.indices)
+
+    def count(self, i: int) -> np.ndarray:
+        """Per conformer of row i the modes found (at most `modes`)."""
+        return np.count_nonzero(np.nan_to_num(self.values[i], nan=0.0) > 0, axis=0)
+
+    def gap(self, i: int, c: int | None = None, m: int = 0) -> float:
+        """(mode m - mode m + 1) / mode m of conformer c (default: the best one): how far the next mode lies below. 1.0 when there is no
+        next mode (or no mode m). The last mode asked for has no known successor: ValueError for m + 1 >= `modes`."""
+        if not 0 <= m < self.modes - 1:
+            raise ValueError(f"the gap behind mode {m} needs modes >= {m + 2}")
+        c = int(self.best_conformer[i]) if c is None else int(c)
+        if c < 0 or self.status[i] != 0:
+            return float("nan")
+        v, nxt = float(self.values[i][m, c]), float(self.values[i][m + 1, c])
+        return 1.0 if v <= 0 or nxt <= 0 else (v - nxt) / v
+
+    def explanation(self, m: int = 0) -> Explanation:
+        """Mode m of every row as an ordinary `Explanation` (`pairs`, `attribution`): its values as `conf_max`, its keys as `match`. The
+        best conformer stays mode 0's, so `pairs(i, ...)` of several m compares the modes of one conformer."""
+        if not 0 <= m < self.modes:
+            raise ValueError(f"mode {m} of {self.modes}")
+        return Explanation(indices=self.indices, conf_max=[v[m].copy() for v in self.values], best_conformer=self.best_conformer, levels=self.levels,
+                           match=[k[m] for k in self.match], status=self.status, require=self.require, exclude=self.exclude)
+
+
+def explain_modes(model, library, indices, modes: int = 4, weights: dict[str, float] | None = None, device=None, require=None, exclude=None) -> ModeSet:
+    """The `modes` (1 to 8) best binding modes per conformer of the library ligands `indices` (`pmx_explain_modes`, csrc/pmx_explain.hip):
+    mode 0 is `explain`'s answer bit for bit, the others are the runners-up in the order a `ModeSet` describes. Any number of ligands
+    (calls of at most 65536 // modes rows each); `library`, `require`, `exclude`, stream and waiting as `explain`."""
+    modes = int(modes)
+    if not 1 <= modes <= _ffi.MAX_MODES:
+        raise _ffi.PmxError(f"{modes} modes (1 to {_ffi.MAX_MODES}, PMX_MAX_MODES)")
+    constraint = None
+    if require is not None or exclude is not None:
+        constraint = normalize_constraint(require, exclude)
+        if any(a >= 128 for g in constraint[0] for a in g) or any(a >= 128 for a in constraint[1]):
+            raise _ffi.PmxError("constraint: a model has at most 128 clusters (PMX_MAX_MODEL_CLUSTERS)")
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    owned = None
+    if not isinstance(library, DeviceLibrary):
+        owned = library = DeviceLibrary(as_packed_library(library), device)
+    try:
+        step = 65536 // modes
+        parts = [_run_modes(model, library, idx[lo : lo + step], modes, weights, constraint) for lo in range(0, max(len(idx), 1), step)]
+    finally:
+        if owned is not None:
+            _torch().cuda.synchronize(_torch().device("cuda", owned.device))
+            owned.close()
+    return ModeSet(indices=np.concatenate([p.indices for p in parts]), modes=modes, values=[v for p in parts for v in p.values],
+                   match=[m for p in parts for m in p.match], levels=[v for p in parts for v in p.levels],
+                   best_conformer=np.concatenate([p.best_conformer for p in parts]), status=np.concatenate([p.status for p in parts]),
+                   require=parts[0].require, exclude=parts[0].exclude)
+
+
+def _run_modes(model, library: "DeviceLibrary", idx, modes: int, weights, constraint) -> ModeSet:
+    """One `pmx_explain_modes` call (its limits are the call's to enforce)."""
+    torch = _torch()
+    lib = _ffi.load()
+    idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).reshape(-1))
+    if (idx < 0).any():
+        raise ValueError("negative ligand index")
+    n = len(idx)
+    mh = device_model(model, library.device)
+    tdev = torch.device("cuda", library.device)
+    L, CM = 20, 64  # PMX_MAX_LEVELS, PMX_MAX_CONFORMERS
+    m = max(n, 1)
+    rows = m if n * modes > 65536 else m * modes  # (a call the library refuses writes nothing)
+    lig = torch.from_numpy(idx).to(tdev)
+    values = torch.empty((rows, CM), dtype=torch.float64, device=tdev)
+    match = torch.empty((rows, CM, L), dtype=torch.uint8, device=tdev)
+    levels = torch.empty((m, L), dtype=torch.uint8, device=tdev)
+    best = torch.empty(m, dtype=torch.int32, device=tdev)
+    status = torch.empty(m, dtype=torch.int32, device=tdev)
+    with torch.cuda.device(tdev):
+        stream = torch.cuda.current_stream(tdev)
+        con = ctypes.byref(_constraint_struct(*constraint)) if constraint is not None else None
+        _ffi.check(lib.pmx_explain_modes(mh.handle, library.handle, _weights_array(weights), con, modes, lig.data_ptr(), n, values.data_ptr(), match.data_ptr(),
+                                         levels.data_ptr(), best.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+    vl, mt, lv = values.cpu().numpy().reshape(-1, modes, CM)[:n], match.cpu().numpy().reshape(-1, modes, CM, L)[:n], levels.cpu().numpy()[:n]
+    st, bc = status.cpu().numpy()[:n].astype(np.int32), best.cpu().numpy()[:n].astype(np.int64)
+    conf = _conformer_counts(library, idx)
+    out_vl, out_lv, out_mt = [], [], []
+    for i in range(n):
+        nl = int(np.count_nonzero(lv[i] != NO_LEVEL))
+        C = int(conf[i]) if st[i] == 0 else 0
+        out_vl.append(vl[i, :, :C].copy() if st[i] == 0 else np.full((modes, 1), np.nan))
+        out_lv.append(lv[i, :nl].astype(np.int64))
+        key = mt[i, :, :C, :nl].astype(np.int64)
+        key[key == NO_MATCH] = -1
+        out_mt.append(key)
+    return ModeSet(indices=idx.astype(np.int64), modes=modes, values=out_vl, match=out_mt, levels=out_lv, best_conformer=bc, status=st,
+                   require=constraint[0] if constraint is not None else None, exclude=constraint[1] if constraint is not None else None)
 
 
 @dataclass

@@ -400,6 +400,31 @@ class PharmacophoreModel:
 
         return explain(self, library, indices, weights=weights, **kwargs)
 
+    def scoring_modes(self, ligand, modes: int = 4, weights: dict[str, float] | None = None, require=None, exclude=None) -> dict:
+        """`scoring_detail` with the runners-up: per conformer the `modes` best leaves of one ligand's tree (`engine.explain_modes`). `values`
+        [modes, C] and `match` [modes, C, nl] (mode 0 is `scoring_detail`'s `conf_max` and `match`), `count` [C] the modes found, `best_conformer`,
+        `levels`, and `pairs`: per mode found at the best conformer its readable match. Takes what `_scoring` takes."""
+        from .engine import explain_modes
+        from .library import as_packed_library
+
+        packed = as_packed_library(ligand)
+        if len(packed) != 1:
+            raise ValueError("scoring_modes takes exactly one ligand")
+        ms = explain_modes(self, packed, [0], modes=modes, weights=weights, require=require, exclude=exclude)
+        if int(ms.status[0]) != 0:
+            n, c, _ = packed.header(0)
+            raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+        c = int(ms.best_conformer[0])
+        found = int(ms.count(0)[c]) if ms.values[0].shape[1] else 0
+        return dict(values=ms.values[0], match=ms.match[0], count=ms.count(0), best_conformer=c, levels=ms.levels[0],
+                    pairs=[ms.explanation(m).pairs(0, self, packed) for m in range(found)])
+
+    def explain_modes(self, library, indices, modes: int = 4, weights: dict[str, float] | None = None, **kwargs):
+        """The `modes` best binding modes per conformer of library ligands `indices` (`engine.explain_modes`)."""
+        from .engine import explain_modes
+
+        return explain_modes(self, library, indices, modes=modes, weights=weights, **kwargs)
+
     def screen_constrained(self, library, topk: int, require=None, exclude=None, weights: dict[str, float] | None = None, **kwargs):
         """The exact top-k by constrained score (`engine.screen_constrained`)."""
         from .engine import screen_constrained

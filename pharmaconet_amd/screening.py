@@ -32,6 +32,8 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--explain", type=int, default=0, metavar="K", help="also explain the K best hits (best conformer and its cluster matches)")
         cfg.add_argument("--explain_out", type=str, default=None, help="CSV of the explained hits (default: <out>.explain.csv)")
         cfg.add_argument("--explain_nodes", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per pharmacophore node of each explained hit and the node's share of the hit's best conformer maximum")
+        cfg.add_argument("--modes", type=int, default=None, metavar="M", help="with --explain K: also list the M (1 to 8) best binding modes of each explained hit's best conformer")
+        cfg.add_argument("--modes_out", type=str, default=None, metavar="PATH", help="CSV of the modes (default: <out>.modes.csv)")
         cfg.add_argument("--require", action="append", default=[], metavar="LIST", help="constrained matching: comma-separated model cluster indices, one of which a hit's match must hold (repeatable: one group each)")
         cfg.add_argument("--exclude", type=str, default=None, metavar="LIST", help="constrained matching: comma-separated model cluster indices that a hit's match must not hold")
         cfg.add_argument("--constrained_out", type=str, default=None, metavar="PATH", help="CSV of the best hits by constrained score (needed with --require / --exclude)")
@@ -119,6 +121,12 @@ def main(argv=None) -> None:
     args = parser.parse_args(argv)
     if args.explain_nodes and args.explain <= 0:
         parser.error("--explain_nodes needs --explain K")
+    if args.modes is not None and args.explain <= 0:
+        parser.error("--modes needs --explain K")
+    if args.modes is not None and not 1 <= args.modes <= 8:
+        parser.error("--modes takes 1 to 8")
+    if args.modes_out and args.modes is None:
+        parser.error("--modes_out needs --modes M")
     if (args.require or args.exclude is not None) and not args.constrained_out:
         parser.error("--require / --exclude need --constrained_out PATH")
     if args.constrained_out and args.constrained_k <= 0:
@@ -147,6 +155,9 @@ def main(argv=None) -> None:
         write_explain_csv(out, names, scores, status, model, lib, weight, args.explain)
         if args.explain_nodes:
             write_explain_nodes_csv(Path(args.explain_nodes), names, scores, status, model, lib, weight, args.explain)
+        if args.modes is not None:
+            out = Path(args.modes_out) if args.modes_out else Path(str(args.out) + ".modes.csv")
+            write_modes_csv(out, names, scores, status, model, lib, weight, args.explain, args.modes)
     if args.constrained_out:
         write_constrained_csv(Path(args.constrained_out), names, model, lib, weight, args.constrained_k, require, exclude)
 
@@ -186,6 +197,26 @@ def write_explain_csv(out: Path, names: list[str], scores: np.ndarray, status: n
             c = int(ex.best_conformer[r])
             pairs = [f"{lc}->{int(m)}:{types[int(m)]}" for lc, m in zip(ex.levels[r], ex.match[r][c]) if m >= 0] if c >= 0 else []
             w.write(f"{r + 1},{names[i]},{float(scores[i])},{c},{float(ex.conf_max[r][c])},{' '.join(pairs)}\n")
+
+
+def write_modes_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, modes: int) -> None:
+    """One row per (hit, mode) of the k best hits, in the order of the explain CSV: the `modes` best leaves of the hit's best conformer
+    (`engine.explain_modes`), best first - the leaf's total, the total as a fraction of mode 0's (the explain CSV's conformer_max), and
+    its matched pairs in the explain CSV's format. Modes the conformer does not have are left out."""
+    from .engine import explain_modes
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    ms = explain_modes(model, lib, order, modes=modes, weights=weights)
+    types = model.flat.cluster_type
+    with open(out, "w") as w:
+        w.write("rank,path,mode,mode_score,fraction_of_best,matches\n")
+        for r, i in enumerate(order):
+            c = int(ms.best_conformer[r])
+            for m in range(int(ms.count(r)[c]) if c >= 0 and ms.values[r].shape[1] else 0):
+                v = float(ms.values[r][m, c])
+                pairs = [f"{lc}->{int(a)}:{types[int(a)]}" for lc, a in zip(ms.levels[r], ms.match[r][m, c]) if a >= 0]
+                w.write(f"{r + 1},{names[i]},{m},{v},{v / float(ms.values[r][0, c])},{' '.join(pairs)}\n")
 
 
 def _record_of(lib, i: int) -> dict:
