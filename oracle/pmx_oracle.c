@@ -17,6 +17,10 @@
  * accumulation of the likelihood, `sigma_sq < 4.0` for the 2-sigma test, weight sums W1 * W2. It is NOT pinned against
  * reference output (Numba cannot be run here; `fastmath=True` may further reassociate): it bounds the spread between
  * the reference's own two code paths, see tests/test_oracle_golden.py::test_numba_variant_spread.
+ *
+ * oracle_explain keeps what the same walk sees at its leaves instead of the mean alone: per conformer the best leaf totals and their
+ * keys, over all leaves or over those that qualify under a constraint. It is pinned against the reference's own leaves by
+ * tests/test_oracle_explain.py (tests/golden/explain_*.npz, constrained_*.npz, modes_*.npz).
  */
 #include <math.h>
 #include <stdint.h>
@@ -75,6 +79,25 @@ typedef struct {
     int64_t n_terms; /* Gaussian terms evaluated per conformer (model node pairs over all ligand node pairs): work measure */
 } oracle_result;
 
+/* include/pmx.h pmx_match_constraint: bit a % 64 of word a / 64 is model cluster a */
+#define MAX_REQUIRE 8
+#define MAX_MODES 8
+typedef struct {
+    int32_t n_require;
+    uint64_t require[MAX_REQUIRE][2];
+    uint64_t exclude[2];
+} oracle_constraint;
+
+/* what oracle_explain keeps of one ligand's leaves */
+typedef struct {
+    const oracle_constraint *con; /* NULL: every leaf qualifies */
+    int n_modes;
+    uint8_t *levels;     /* [MAX_LEVELS]: lev_cluster, 0xFE past nl */
+    double *values;      /* [n_modes][MAX_C]: per conformer the best totals, descending, equal totals in arrival order; 0 past the list's end */
+    uint8_t *keys;       /* [n_modes][MAX_C][MAX_LEVELS]: their keys as model clusters, 0xFF for the skip child and for absent entries */
+    int64_t *n_positive; /* [MAX_C]: qualifying leaves that hold the conformer with a total > 0 */
+} explain_out;
+
 typedef struct {
     int n, C, ncl;
     const uint8_t *typemask;
@@ -110,6 +133,7 @@ typedef struct {
     /* DFS path */
     int sel[MAX_LEVELS];
     int variant; /* 0: NumPy kernels, 1: Numba kernels */
+    explain_out *xo; /* oracle_explain: where the leaves go (NULL: the maxima alone) */
 } ctx_t;
 
 static float edge_distance(const ligand_t *L, int u, int v, int c) {
@@ -306,6 +330,43 @@ static void build_tables(ctx_t *X, oracle_result *R) {
     }
 }
 
+/* A leaf of the walk below, kept for oracle_explain: its key is the path sel[] as model clusters (ClusterMatchTree.key,
+ * tree.py:129-137). A leaf that qualifies counts for every conformer it holds with a total > 0 and enters that conformer's list only
+ * when strictly above the list's last entry, behind every entry at or above it - the strict `>` of graph_match.py:105-108 kept for
+ * n_modes entries, so the list's head is what best[] holds when there is no constraint. */
+static void keep_leaf(ctx_t *X, const uint8_t *alive, const double *total) {
+    explain_out *O = X->xo;
+    const int C = X->L.C, M = O->n_modes;
+    uint8_t key[MAX_LEVELS];
+    uint64_t have[2] = {0, 0};
+    for (int l = 0; l < X->nl; ++l) {
+        if (X->sel[l] < 0) {
+            key[l] = 0xFF;
+            continue;
+        }
+        const int a = X->cand[l][X->sel[l]];
+        key[l] = (uint8_t)a;
+        have[a >> 6] |= (uint64_t)1 << (a & 63);
+    }
+    if (O->con) {
+        if ((have[0] & O->con->exclude[0]) | (have[1] & O->con->exclude[1])) return;
+        for (int g = 0; g < O->con->n_require; ++g)
+            if (!((have[0] & O->con->require[g][0]) | (have[1] & O->con->require[g][1]))) return;
+    }
+    for (int c = 0; c < C; ++c) {
+        if (!alive[c] || !(total[c] > 0.0)) continue;
+        O->n_positive[c]++;
+        if (!(total[c] > O->values[(size_t)(M - 1) * MAX_C + c])) continue;
+        int at = M - 1;
+        for (; at > 0 && O->values[(size_t)(at - 1) * MAX_C + c] < total[c]; --at) {
+            O->values[(size_t)at * MAX_C + c] = O->values[(size_t)(at - 1) * MAX_C + c];
+            memcpy(O->keys + ((size_t)at * MAX_C + c) * MAX_LEVELS, O->keys + ((size_t)(at - 1) * MAX_C + c) * MAX_LEVELS, MAX_LEVELS);
+        }
+        O->values[(size_t)at * MAX_C + c] = total[c];
+        memcpy(O->keys + ((size_t)at * MAX_C + c) * MAX_LEVELS, key, (size_t)X->nl);
+    }
+}
+
 /* ClusterMatchTree.dfs_run, scoring/tree.py:55-104, with the per-candidate filtering of :69-85
  * evaluated when the candidate is reached instead of being carried down in `match_dict` (same sets,
  * same float64 sums in the same order: accumulated pair score top-down, then parent + self + pair,
@@ -316,6 +377,7 @@ static int dfs(ctx_t *X, int level, int matched, int num_matches, const uint8_t 
         X->n_leaf++;
         for (int c = 0; c < C; ++c)
             if (alive[c] && total[c] > X->best[c]) X->best[c] = total[c];
+        if (X->xo) keep_leaf(X, alive, total);
         return matched;
     }
     int f = level + 1;
@@ -355,12 +417,13 @@ static int dfs(ctx_t *X, int level, int matched, int num_matches, const uint8_t 
     return max_num + matched; /* tree.py:102 */
 }
 
-static void score_ligand(const oracle_model *M, const uint8_t *rec, const float w[7], oracle_result *R, int variant) {
+static void score_ligand(const oracle_model *M, const uint8_t *rec, const float w[7], oracle_result *R, int variant, explain_out *xo) {
     arena_reset();
     ctx_t *X = (ctx_t *)arena_calloc(1, sizeof(ctx_t));
     memset(R, 0, sizeof(*R));
     X->M = M;
     X->variant = variant;
+    X->xo = xo;
     ligand_t *L = &X->L;
     L->n = rec[0] | (rec[1] << 8);
     L->C = rec[2] | (rec[3] << 8);
@@ -385,6 +448,8 @@ static void score_ligand(const oracle_model *M, const uint8_t *rec, const float 
         X->nl++;
     }
     R->n_levels = X->nl;
+    if (xo)
+        for (int l = 0; l < X->nl; ++l) xo->levels[l] = (uint8_t)X->lev_cluster[l];
     if (X->nl > 0) { /* graph_match.py:98-99 */
         build_node_matches(X, w);
         build_tables(X, R);
@@ -414,25 +479,67 @@ int oracle_score(const oracle_model *M, const uint64_t *offsets, const uint8_t *
     return oracle_score_variant(M, offsets, data, first, count, weights, scores, results, num_threads, 0);
 }
 
+/* 0 for a model this restatement's fixed-size tables hold */
+static int model_fits(const oracle_model *M) {
+    if (M->n_clusters > MAX_K || M->n_nodes > 256) return 2;
+    const int nw = M->n_nodes > 64 ? (M->n_nodes + 63) / 64 : 1;
+    for (int a = 0; a < M->n_clusters; ++a) { /* node_match holds 64 model nodes */
+        int cnt = 0;
+        for (int w = 0; w < nw; ++w) cnt += __builtin_popcountll(M->cluster_nodes[(size_t)a * nw + w]);
+        if (cnt > 64) return 3;
+    }
+    return 0;
+}
+
 int oracle_score_variant(const oracle_model *M, const uint64_t *offsets, const uint8_t *data, uint64_t first, uint64_t count,
                          const float weights[7], double *scores, oracle_result *results, int num_threads, int variant) {
     if (num_threads < 1) num_threads = 1;
-    if (M->n_clusters > MAX_K || M->n_nodes > 256) return 2; /* fixed-size tables of this restatement */
-    {
-        const int nw = M->n_nodes > 64 ? (M->n_nodes + 63) / 64 : 1;
-        for (int a = 0; a < M->n_clusters; ++a) { /* node_match holds 64 model nodes */
-            int cnt = 0;
-            for (int w = 0; w < nw; ++w) cnt += __builtin_popcountll(M->cluster_nodes[(size_t)a * nw + w]);
-            if (cnt > 64) return 3;
-        }
-    }
+    const int fits = model_fits(M);
+    if (fits) return fits;
     int64_t n = (int64_t)count;
 #pragma omp parallel for schedule(dynamic, 16) num_threads(num_threads)
     for (int64_t i = 0; i < n; ++i) {
         oracle_result r;
-        score_ligand(M, data + offsets[first + (uint64_t)i], weights, &r, variant);
+        score_ligand(M, data + offsets[first + (uint64_t)i], weights, &r, variant, NULL);
         scores[i] = r.score;
         if (results) results[i] = r;
+    }
+    return 0;
+}
+
+/* The leaves of ligands [first, first+count): per ligand i the tree levels, per conformer the n_modes (1 .. 8) best leaf totals with their
+ * keys, and how many leaves count. `con` is NULL (every leaf qualifies), one constraint for all ligands (per_ligand = 0) or an array of
+ * `count` constraints (per_ligand = 1). Outputs, all written in full: levels uint8 [count][20] (0xFE past nl), values double
+ * [count][n_modes][64], keys uint8 [count][n_modes][64][20] (0xFF for the skip child and wherever no leaf is held), n_positive int64
+ * [count][64]; `scores` (may be NULL) is oracle_score's answer for the same ligands, from the same walk. Returns 0; 4 for n_modes or a
+ * constraint out of range. */
+int oracle_explain(const oracle_model *M, const uint64_t *offsets, const uint8_t *data, uint64_t first, uint64_t count, const float weights[7],
+                   const oracle_constraint *con, int per_ligand, int n_modes, uint8_t *levels, double *values, uint8_t *keys, int64_t *n_positive,
+                   double *scores, int num_threads) {
+    if (num_threads < 1) num_threads = 1;
+    const int fits = model_fits(M);
+    if (fits) return fits;
+    if (n_modes < 1 || n_modes > MAX_MODES) return 4;
+    for (uint64_t i = 0; con && i < (per_ligand ? count : 1); ++i)
+        if (con[i].n_require < 0 || con[i].n_require > MAX_REQUIRE) return 4;
+    const int64_t n = (int64_t)count;
+    const size_t nv = (size_t)n_modes * MAX_C;
+    memset(levels, 0xFE, (size_t)n * MAX_LEVELS);
+    memset(values, 0, (size_t)n * nv * sizeof(double));
+    memset(keys, 0xFF, (size_t)n * nv * MAX_LEVELS);
+    memset(n_positive, 0, (size_t)n * MAX_C * sizeof(int64_t));
+#pragma omp parallel for schedule(dynamic, 4) num_threads(num_threads)
+    for (int64_t i = 0; i < n; ++i) {
+        oracle_result r;
+        explain_out o;
+        o.con = con ? con + (per_ligand ? i : 0) : NULL;
+        o.n_modes = n_modes;
+        o.levels = levels + (size_t)i * MAX_LEVELS;
+        o.values = values + (size_t)i * nv;
+        o.keys = keys + (size_t)i * nv * MAX_LEVELS;
+        o.n_positive = n_positive + (size_t)i * MAX_C;
+        score_ligand(M, data + offsets[first + (uint64_t)i], weights, &r, 0, &o);
+        if (scores) scores[i] = r.score;
     }
     return 0;
 }
