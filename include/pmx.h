@@ -373,7 +373,7 @@ int pmx_explain_constrained(const pmx_model *model, const pmx_library *lib, cons
  * A ligand with a non-zero status has NaN in every mode. 1 <= n_modes <= PMX_MAX_MODES and n * n_modes <= PMX_EXPLAIN_MAX, otherwise
  * PMX_ERR_INVALID; the constraint is checked as pmx_explain_constrained checks it; n = 0 succeeds. Statuses, stream ordering and
  * workspace use are pmx_explain's, its slice, large-slice and arena passes included. One wavefront walks a ligand's tree once for all
- * modes (pmx_explain.hip, the MODES kernels): a subtree is left out only when no leaf in it can enter any conformer's list, so the call
+ * modes (pmx_explain.hip: the one walker, of which pmx_explain is n_modes = 1): a subtree is left out only when no leaf in it can enter any conformer's list, so the call
  * costs more than pmx_explain the further the n_modes-th value lies below the maximum. There is no ranking of modes across conformers: a
  * leaf holds a subset of the conformers, and the reference defines none.
  */

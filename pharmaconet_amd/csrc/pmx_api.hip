@@ -1178,7 +1178,7 @@ static int explain_screen(const pmx_model *model, const pmx_library *lib, const 
 }
 
 // pmx_explain, pmx_explain_constrained and pmx_explain_modes: one driver; without a constraint the kernels are the ones that never look at
-// one. n_modes 0: one maximum and one key per conformer; otherwise pmx_explain_modes' outputs, n_modes of each.
+// one. n_modes leaves per conformer, 1 for pmx_explain and pmx_explain_constrained: the outputs are [n][n_modes][...].
 static int explain_call(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const pmx_match_constraint *constraint,
                         int n_modes, const uint64_t *ligands_dev, uint32_t n, double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev,
                         int32_t *status_dev, void *stream_) {
@@ -1223,13 +1223,13 @@ static int explain_call(const pmx_model *model, const pmx_library *lib, const fl
 
 extern "C" int pmx_explain(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev, uint32_t n,
                            double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev, int32_t *status_dev, void *stream) {
-    return explain_call(model, lib, weights, nullptr, 0, ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, stream);
+    return explain_call(model, lib, weights, nullptr, 1, ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, stream);
 }
 
 extern "C" int pmx_explain_constrained(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const pmx_match_constraint *constraint,
                                        const uint64_t *ligands_dev, uint32_t n, double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev,
                                        int32_t *best_conformer_dev, int32_t *status_dev, void *stream) {
-    return explain_call(model, lib, weights, constraint, 0, ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, stream);
+    return explain_call(model, lib, weights, constraint, 1, ligands_dev, n, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, stream);
 }
 
 extern "C" int pmx_explain_modes(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const pmx_match_constraint *constraint,

@@ -24,13 +24,15 @@
 // qualify (an excluded cluster on its path, or a require group with no cluster on the path or among the candidates of the levels
 // below). A subtree with fewer matches that cannot qualify is walked for its match count alone.
 //
-// Modes (pmx_explain_modes): per conformer the M = n_modes best leaves instead of the best one - the leaves that hold the conformer with
-// a score > 0 (and qualify, under a constraint), by descending total, equal totals in iteration order. The MODES instantiation keeps per
-// lane the M totals, sorted, in LDS and the M keys (as candidate numbers) in the row's own output block, turned into model clusters in
-// place at the end. A leaf enters the list iff its total is strictly above the lane's M-th value, behind every entry >= it: a later leaf
-// never overtakes an equal earlier one, so the list is the stable order above and its head, updated by the same strict `>`, is
-// pmx_explain's answer bit for bit. The bound follows the M-th value: a child with >= 5 matches is dropped when
-// (total + R) * kBoundSlack < the running M-th value, strictly, for every conformer it holds. The running M-th value of a conformer never
+// Modes: there is one walker, and it keeps per conformer the M = n_modes best leaves - the leaves that hold the conformer with a score
+// > 0 (and qualify, under a constraint), by descending total, equal totals in iteration order. pmx_explain and pmx_explain_constrained
+// are M = 1 (the list is the running maximum and its key, the outputs [n][1][...] are the layouts they document), pmx_explain_modes any M
+// up to PMX_MAX_MODES. A lane keeps its M totals, sorted, in LDS and its M keys (as candidate numbers) in the row's own output block,
+// turned into model clusters in place at the end. A leaf enters the list iff its total is strictly above the lane's M-th value, behind
+// every entry >= it: a later leaf never overtakes an equal earlier one, so the list is the stable order above and its head is the first
+// leaf at the maximum, as the strict `>` of _run_average keeps it. The bound follows the M-th value (with M = 1 the running maximum of
+// the note above): a child with >= 5 matches is dropped when (total + R) * kBoundSlack < the running M-th value, strictly, for every
+// conformer it holds. The running M-th value of a conformer never
 // exceeds its final one (entries only rise), so every leaf below a dropped child is strictly below the final M-th value of every conformer
 // it holds and belongs to no list; a leaf that ties the M-th value is never dropped, and the walked leaves arrive in iteration order, so the
 // lists are those of the full tree. The feasibility drops of the constrained walker do not look at values and are unchanged.
@@ -49,7 +51,7 @@ constexpr uint8_t kNoMatch = 0xFF, kNoLevel = 0xFE;
 // The explain walker's LDS, behind the product's per-wave layout.
 template <int G>
 struct ExplainLds {
-    uint32_t tot, key, frame, mrow, path, cb, pm, sfx, bytes;
+    uint32_t tot, frame, mrow, path, cb, pm, sfx, bytes;
 };
 template <int G>
 __host__ __device__ inline ExplainLds<G> explain_lds(const WaveShape<G> &ws, bool constrained) {
@@ -57,8 +59,6 @@ __host__ __device__ inline ExplainLds<G> explain_lds(const WaveShape<G> &ws, boo
     uint32_t o = (ws.bytes + 15u) & ~15u;
     e.tot = o; // double [frame][G]: the total of each frame's tree node (frame f = the node whose children are the candidates of level f)
     o += (PMX_MAX_LEVELS + 1) * G * 8;
-    e.key = o; // u8 [G][PMX_MAX_LEVELS]: the key of the leaf holding conformer c's maximum, as candidate numbers
-    o += (uint32_t)round16((uint64_t)G * PMX_MAX_LEVELS);
     e.frame = o; // int [PMX_MAX_LEVELS + 1]: nb | mx << 8 | any << 16 | matched << 17 | nm << 24
     o += 4 * 24;
     e.mrow = o; // int [PMX_MAX_LEVELS]: pair entry of match q against candidate x = mrow[q] + x
@@ -74,7 +74,7 @@ __host__ __device__ inline ExplainLds<G> explain_lds(const WaveShape<G> &ws, boo
         e.sfx = o; // u64 [PMX_MAX_LEVELS + 1][2]: model clusters that are candidates of level f or of a level below it
         o += 16 * (PMX_MAX_LEVELS + 1);
     }
-    e.bytes = o; // (the MODES walker's totals lie behind: double [n_modes][G], conformer c's descending; its keys live in the row's output block)
+    e.bytes = o; // (the mode totals lie behind: double [n_modes][G], conformer c's descending; the keys live in the row's output block)
     return e;
 }
 
@@ -105,10 +105,10 @@ __device__ inline uint8_t candidate_cluster(unsigned long long w0, unsigned long
     return (uint8_t)((b < n0 ? 0 : 64) + __ffsll(xw) - 1);
 }
 
-// The tree of one prepared ligand (tables at `rec`), maxima and keys into row li of the output. Lane c < G is conformer c.
-// CONSTRAINED: only leaves whose key qualifies under a.con update a maximum (see the note at the top).
-// MODES: the a.n_modes best leaves per conformer; a.conf_max and a.match are then [n][n_modes][...] (see the note at the top).
-template <int G, bool CONSTRAINED, bool MODES>
+// The tree of one prepared ligand (tables at `rec`): the a.n_modes best leaves per conformer, totals and keys into row li of the output
+// (a.conf_max and a.match are [n][n_modes][...]). Lane c < G is conformer c.
+// CONSTRAINED: only leaves whose key qualifies under a.con enter a list (see the note at the top).
+template <int G, bool CONSTRAINED>
 __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const ExplainLds<G> &E, const unsigned char *rec, uint64_t lig, uint32_t li,
                              const pmx_xpl::Args &a) {
     const int lane = lane_id();
@@ -121,18 +121,17 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
     const float *P = reinterpret_cast<const float *>(rec + rec_p_off<G>(ksumtot));
     const double *R = reinterpret_cast<const double *>(rec + rec_r_off<G>(ksumtot, T));
     double *tot = reinterpret_cast<double *>(lds + E.tot);
-    uint8_t *key = lds + E.key;
     int *frame = reinterpret_cast<int *>(lds + E.frame);
     int *mrow = reinterpret_cast<int *>(lds + E.mrow);
     uint8_t *path = lds + E.path;
     unsigned long long *cbl = reinterpret_cast<unsigned long long *>(lds + E.cb);
     unsigned long long *pm = reinterpret_cast<unsigned long long *>(lds + E.pm);
     unsigned long long *sfx = reinterpret_cast<unsigned long long *>(lds + E.sfx);
-    // MODES: conformer c's totals at mv[m * G + c], mode m's key at mkey + m * kModeKeys
-    const int M = MODES ? uni((int)a.n_modes) : 1;
-    double *mv = MODES ? reinterpret_cast<double *>(lds + E.bytes) : nullptr;
+    // conformer c's totals at mv[m * G + c], mode m's key at mkey + m * kModeKeys
+    const int M = uni((int)a.n_modes);
+    double *mv = reinterpret_cast<double *>(lds + E.bytes);
     constexpr size_t kModeKeys = (size_t)PMX_MAX_CONFORMERS * PMX_MAX_LEVELS;
-    uint8_t *mkey = MODES ? a.match + ((size_t)li * M * PMX_MAX_CONFORMERS + c) * PMX_MAX_LEVELS : nullptr;
+    uint8_t *mkey = a.match + ((size_t)li * M * PMX_MAX_CONFORMERS + c) * PMX_MAX_LEVELS;
 
     // ---- the levels of the row and the model clusters that are candidates of each
     const Record r = parse_record(p.lib.data + p.lib.offsets[lig]);
@@ -173,14 +172,10 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
     }
 
     uint32_t vbits = (mine && c < C) ? 1u : 0u; // bit f: conformer c is in the pair_scores of frame f's node (tree.py:78-84)
-    double best = 0.0;                           // running maximum of conformer c (graph_match.py:105-108); MODES: its running M-th value
+    double best = 0.0;                           // running M-th value of conformer c (M = 1: its running maximum, graph_match.py:105-108)
     if (mine) {
         tot[c] = 0.0;
-        if constexpr (MODES) {
-            for (int m = 0; m < M; ++m) mv[m * G + c] = 0.0; // (the keys are the row's: 0xFF throughout, explain_modes_init_kernel)
-        } else {
-            for (int l = 0; l < PMX_MAX_LEVELS; ++l) key[c * PMX_MAX_LEVELS + l] = kNoMatch;
-        }
+        for (int m = 0; m < M; ++m) mv[m * G + c] = 0.0; // (the keys are the row's: 0xFF throughout, explain_init_kernel)
     }
     if (lane == 0) frame[0] = 0;
     wave_sync();
@@ -192,20 +187,15 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
             if constexpr (CONSTRAINED) qualifies = con_feasible(a.con, uni64(pm[2 * f]), uni64(pm[2 * f + 1]), 0ull, 0ull);
             if (qualifies && mine && ((vbits >> f) & 1u)) {
                 const double t = tot[f * G + c];
-                if (t > best) {
-                    if constexpr (MODES) { // behind every entry >= t; the entries below move down one place, the last one leaves
-                        int at = M - 1;
-                        for (; at > 0 && mv[(at - 1) * G + c] < t; --at) {
-                            mv[at * G + c] = mv[(at - 1) * G + c];
-                            for (int l = 0; l < nl; ++l) mkey[at * kModeKeys + l] = mkey[(at - 1) * kModeKeys + l];
-                        }
-                        mv[at * G + c] = t;
-                        for (int l = 0; l < nl; ++l) mkey[at * kModeKeys + l] = path[l];
-                        best = mv[(M - 1) * G + c];
-                    } else {
-                        best = t;
-                        for (int l = 0; l < nl; ++l) key[c * PMX_MAX_LEVELS + l] = path[l];
+                if (t > best) { // behind every entry >= t; the entries below move down one place, the last one leaves
+                    int at = M - 1;
+                    for (; at > 0 && mv[(at - 1) * G + c] < t; --at) {
+                        mv[at * G + c] = mv[(at - 1) * G + c];
+                        for (int l = 0; l < nl; ++l) mkey[at * kModeKeys + l] = mkey[(at - 1) * kModeKeys + l];
                     }
+                    mv[at * G + c] = t;
+                    for (int l = 0; l < nl; ++l) mkey[at * kModeKeys + l] = path[l];
+                    best = mv[(M - 1) * G + c];
                 }
             }
             const int ret = (uni(frame[f]) >> 17) & 1;
@@ -329,35 +319,16 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
     // ---- the row: maxima, keys as model clusters, best conformer
     wave_sync();
     const bool live = mine && c < C;
-    if constexpr (MODES) {
-        for (int m = 0; m < M; ++m) {
-            const double v = live ? mv[m * G + c] : 0.0;
-            a.conf_max[((size_t)li * M + m) * PMX_MAX_CONFORMERS + lane] = v;
-            if (v > 0.0) // (a place no leaf took keeps its 0xFF)
-                for (int l = 0; l < nl; ++l) {
-                    uint8_t &k = mkey[m * kModeKeys + l];
-                    if (k != kNoMatch) k = candidate_cluster(cbl[2 * l], cbl[2 * l + 1], k);
-                }
-        }
-        best = live ? mv[c] : 0.0; // (the best conformer is mode 0's)
-    } else {
-        a.conf_max[(size_t)li * PMX_MAX_CONFORMERS + lane] = live ? best : 0.0;
-        if (live) {
-            uint8_t *out = a.match + ((size_t)li * PMX_MAX_CONFORMERS + c) * PMX_MAX_LEVELS;
+    for (int m = 0; m < M; ++m) {
+        const double v = live ? mv[m * G + c] : 0.0;
+        a.conf_max[((size_t)li * M + m) * PMX_MAX_CONFORMERS + lane] = v;
+        if (v > 0.0) // (a place no leaf took keeps its 0xFF)
             for (int l = 0; l < nl; ++l) {
-                const int b = key[c * PMX_MAX_LEVELS + l];
-                uint8_t m = kNoMatch;
-                if (b != kNoMatch) {
-                    const unsigned long long w0 = cbl[2 * l], w1 = cbl[2 * l + 1];
-                    const int n0 = __popcll(w0);
-                    unsigned long long xw = b < n0 ? w0 : w1;
-                    for (int j = b < n0 ? b : b - n0; j > 0; --j) xw &= xw - 1ull;
-                    m = (uint8_t)((b < n0 ? 0 : 64) + __ffsll(xw) - 1);
-                }
-                out[l] = m;
+                uint8_t &k = mkey[m * kModeKeys + l];
+                if (k != kNoMatch) k = candidate_cluster(cbl[2 * l], cbl[2 * l + 1], k);
             }
-        }
     }
+    best = live ? mv[c] : 0.0; // (the best conformer is mode 0's)
     // smallest conformer with the largest maximum
     double m = live ? best : -1.0;
 #pragma unroll
@@ -372,7 +343,7 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
 
 // Persistent wavefronts over the call's list (mode 0) or over the ligands an earlier pass handed on (modes 1 - 3): the tables
 // as the product builds them (prepare_ligand, which also writes the status), then the explain walk.
-template <int G, bool TAILS, bool CONSTRAINED, bool MODES>
+template <int G, bool TAILS, bool CONSTRAINED>
 __global__ __launch_bounds__(64) void explain_kernel(const ScreenParams p, const pmx_xpl::Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int lane0 = lane_id();
@@ -402,35 +373,16 @@ __global__ __launch_bounds__(64) void explain_kernel(const ScreenParams p, const
         ScreenParams q = p;
         q.first = lig - (uint64_t)li;
         q.status = a.status;
-        if constexpr (MODES) q.scores = reinterpret_cast<float *>(a.conf_max + (size_t)li * (a.n_modes * PMX_MAX_CONFORMERS - 1));
-        else q.scores = reinterpret_cast<float *>(a.conf_max + (size_t)li * (PMX_MAX_CONFORMERS - 1));
+        q.scores = reinterpret_cast<float *>(a.conf_max + (size_t)li * (a.n_modes * PMX_MAX_CONFORMERS - 1));
         q.flags = PMX_SCORES_F64;
         unsigned char *rec = prepare_ligand<G, false, TAILS>(q, lds, ws, li, wave_id, stat);
         if (!rec) continue;
-        explain_walk<G, CONSTRAINED, MODES>(q, lds, E, rec, lig, li, a);
+        explain_walk<G, CONSTRAINED>(q, lds, E, rec, lig, li, a);
     }
 }
 
+// a.conf_max is [n][n_modes][PMX_MAX_CONFORMERS], a.match [n][n_modes][PMX_MAX_CONFORMERS][PMX_MAX_LEVELS].
 __global__ void explain_init_kernel(const pmx_xpl::Args a) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t n = a.n;
-    if (i < n * PMX_MAX_CONFORMERS) a.conf_max[i] = 0.0;
-    if (i < n * PMX_MAX_LEVELS) a.levels[i] = kNoLevel;
-    if (i < n) a.best[i] = 0;
-    for (size_t j = i; j < n * PMX_MAX_CONFORMERS * PMX_MAX_LEVELS; j += (size_t)gridDim.x * blockDim.x) a.match[j] = kNoMatch;
-}
-
-__global__ void explain_fixup_kernel(const pmx_xpl::Args a) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)a.n * PMX_MAX_CONFORMERS) return;
-    const size_t li = i / PMX_MAX_CONFORMERS;
-    if (a.status[li] == PMX_LIGAND_OK) return;
-    a.conf_max[i] = __builtin_nan("");
-    if (i % PMX_MAX_CONFORMERS == 0) a.best[li] = -1;
-}
-
-// The same for the rows of pmx_explain_modes: a.conf_max is [n][n_modes][PMX_MAX_CONFORMERS], a.match [n][n_modes][PMX_MAX_CONFORMERS][PMX_MAX_LEVELS].
-__global__ void explain_modes_init_kernel(const pmx_xpl::Args a) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t n = a.n, nm = n * a.n_modes;
     if (i < nm * PMX_MAX_CONFORMERS) a.conf_max[i] = 0.0;
@@ -439,7 +391,7 @@ __global__ void explain_modes_init_kernel(const pmx_xpl::Args a) {
     for (size_t j = i; j < nm * PMX_MAX_CONFORMERS * PMX_MAX_LEVELS; j += (size_t)gridDim.x * blockDim.x) a.match[j] = kNoMatch;
 }
 
-__global__ void explain_modes_fixup_kernel(const pmx_xpl::Args a) {
+__global__ void explain_fixup_kernel(const pmx_xpl::Args a) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t row = (size_t)a.n_modes * PMX_MAX_CONFORMERS;
     if (i >= (size_t)a.n * row) return;
@@ -459,10 +411,10 @@ size_t lds_bytes(int G, int K, int max_nodes, bool constrained, int n_modes) {
     return bytes;
 }
 
-template <int G, bool CONSTRAINED, bool MODES>
+template <int G, bool CONSTRAINED>
 static void launch_shape(bool tails, unsigned blocks, unsigned lds, hipStream_t stream, const pmx_x::ScreenParams &p, const Args &a) {
-    if (tails) pmx_x::explain_kernel<G, true, CONSTRAINED, MODES><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
-    else pmx_x::explain_kernel<G, false, CONSTRAINED, MODES><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+    if (tails) pmx_x::explain_kernel<G, true, CONSTRAINED><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
+    else pmx_x::explain_kernel<G, false, CONSTRAINED><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
 }
 
 bool launch(int G, bool tails, bool constrained, int mode, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes, const Args &a) {
@@ -470,25 +422,21 @@ bool launch(int G, bool tails, bool constrained, int mode, unsigned blocks, unsi
     pmx_x::ScreenParams p;
     std::memcpy(&p, params, sizeof p);
     p.mode = mode;
-    const bool modes = a.n_modes > 0;
     return pmx::with_lanes(G, [&](auto g) {
         constexpr int L = decltype(g)::value;
-        if (modes) constrained ? launch_shape<L, true, true>(tails, blocks, lds, stream, p, a) : launch_shape<L, false, true>(tails, blocks, lds, stream, p, a);
-        else constrained ? launch_shape<L, true, false>(tails, blocks, lds, stream, p, a) : launch_shape<L, false, false>(tails, blocks, lds, stream, p, a);
+        constrained ? launch_shape<L, true>(tails, blocks, lds, stream, p, a) : launch_shape<L, false>(tails, blocks, lds, stream, p, a);
     });
 }
 
 void launch_init(const Args &a, hipStream_t stream) {
-    const size_t n = (size_t)a.n * std::max<uint32_t>(a.n_modes, 1) * PMX_MAX_CONFORMERS;
+    const size_t n = (size_t)a.n * a.n_modes * PMX_MAX_CONFORMERS;
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 65535);
-    if (a.n_modes > 0) pmx_x::explain_modes_init_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(a);
-    else pmx_x::explain_init_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(a);
+    pmx_x::explain_init_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(a);
 }
 
 void launch_fixup(const Args &a, hipStream_t stream) {
-    const size_t n = (size_t)a.n * std::max<uint32_t>(a.n_modes, 1) * PMX_MAX_CONFORMERS;
-    if (a.n_modes > 0) pmx_x::explain_modes_fixup_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(a);
-    else pmx_x::explain_fixup_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(a);
+    const size_t n = (size_t)a.n * a.n_modes * PMX_MAX_CONFORMERS;
+    pmx_x::explain_fixup_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(a);
 }
 
 } // namespace pmx_xpl

@@ -6,6 +6,7 @@ PyTorch is used for what it is good at here - device buffers, the current HIP st
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from dataclasses import dataclass
 
@@ -149,6 +150,22 @@ class DeviceLibrary:
             self.close()
         except Exception:
             pass
+
+
+@contextlib.contextmanager
+def _resident(library, device=None):
+    """`library` in HBM for the length of the block: a `DeviceLibrary` as it is, anything else `as_packed_library` accepts uploaded for the
+    block and closed behind it, once the device is done with it."""
+    if isinstance(library, DeviceLibrary):
+        yield library
+        return
+    owned = DeviceLibrary(as_packed_library(library), device)
+    try:
+        yield owned
+    finally:
+        torch = _torch()
+        torch.cuda.synchronize(torch.device("cuda", owned.device))
+        owned.close()
 
 
 FEATURE_FIELDS = ("atom_off", "atomic_num", "nbr_off", "nbr", "feat_off", "feat_type", "feat_flags", "feat_atom_off", "feat_atoms",
@@ -307,35 +324,27 @@ def screen(
     rounding; the device top-k ranks float32 values, so it is not offered together with `topk`."""
     torch = _torch()
     lib = _ffi.load()
-    owned = None
-    given = library
-    if not isinstance(library, DeviceLibrary):
-        owned = library = DeviceLibrary(as_packed_library(library), device)
-    dev = library.device
-    mh = device_model(model, dev)
-    if count is None:
-        count = len(library) - first
-    tdev = torch.device("cuda", dev)
     if float64 and topk is not None:
         raise ValueError("float64 scores are ranked by the caller (the device top-k ranks float32 values)")
-    scores = torch.empty(count, dtype=torch.float64 if float64 else torch.float32, device=tdev)
-    status = torch.empty(count, dtype=torch.int32, device=tdev)
-    stream = torch.cuda.current_stream(tdev).cuda_stream
-    try:
+    with _resident(library, device) as dlib:
+        dev = dlib.device
+        mh = device_model(model, dev)
+        if count is None:
+            count = len(dlib) - first
+        tdev = torch.device("cuda", dev)
+        scores = torch.empty(count, dtype=torch.float64 if float64 else torch.float32, device=tdev)
+        status = torch.empty(count, dtype=torch.int32, device=tdev)
+        stream = torch.cuda.current_stream(tdev).cuda_stream
         _ffi.check(
             (lib.pmx_score_f64 if float64 else lib.pmx_score)(
-                mh.handle, library.handle, _weights_array(weights), first, count,
+                mh.handle, dlib.handle, _weights_array(weights), first, count,
                 scores.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream),
             )
         )
-        result = ScreeningResult(scores=scores, status=status, first=first, model=model, library=given if isinstance(given, (DeviceLibrary, PackedLibrary)) else None,
+        result = ScreeningResult(scores=scores, status=status, first=first, model=model, library=library if isinstance(library, (DeviceLibrary, PackedLibrary)) else None,
                                   weights=weights, index_base=index_base)
         if topk is not None:
             result.topk_scores, result.topk_indices = globals()["topk"](scores, int(topk), base_index=index_base + first)
-    finally:
-        if owned is not None:
-            torch.cuda.synchronize(tdev)
-            owned.close()
     return result
 
 
@@ -463,23 +472,6 @@ def _record_counts(library: "DeviceLibrary", idx: np.ndarray, field: int) -> np.
     return np.where(ok, v.cpu().numpy(), 0)
 
 
-def _conformer_counts(library: "DeviceLibrary", idx: np.ndarray) -> np.ndarray:
-    """Conformer counts of library ligands `idx` (0 outside the library): kept per ligand when the library was uploaded from the host, read
-    from the adopted device records otherwise."""
-    ok = idx < len(library)
-    j = np.where(ok, idx, 0)
-    if getattr(library, "_n_conf", None) is not None:
-        return np.where(ok, library._n_conf[j].astype(np.int64) if len(library._n_conf) else 0, 0)
-    src = getattr(library, "_adopted", None)
-    if src is None:
-        raise ValueError("explain needs the conformer counts of this DeviceLibrary: make it from a PackedLibrary or adopt the device buffers")
-    torch = _torch()
-    offsets, data = src
-    starts = offsets.view(torch.int64)[torch.from_numpy(j).to(offsets.device)]
-    c = data[starts + 2].to(torch.int64) | (data[starts + 3].to(torch.int64) << 8)
-    return np.where(ok, c.cpu().numpy(), 0)
-
-
 def normalize_constraint(require=None, exclude=None, num_clusters: int | None = None):
     """`require` (a sequence of groups, each an int or a sequence of ints) and `exclude` (a sequence of ints) as (tuple of sorted tuples,
     sorted tuple) of model cluster indices. ValueError for a negative index or, with `num_clusters`, an index outside the model; an
@@ -526,68 +518,66 @@ def explain(model, library, indices, weights: dict[str, float] | None = None, de
     index or a sequence of them; `exclude` a sequence of indices (`PharmacophoreModel.clusters_with_nodes` makes either from hotspot
     nodes). Only leaves whose key holds a cluster of every group and none of `exclude` count: `conf_max`, `scores` and `match` are over
     those leaves. With both None the call is `pmx_explain` as before."""
+    n = int(np.size(indices))
+    if n > 65536:
+        raise ValueError("at most 65536 ligands per explain call (PMX_EXPLAIN_MAX)")
+    constraint = _constraint(require, exclude)
+    with _resident(library, device) as dlib:
+        return _explain_rows(model, dlib, indices, 1, weights, constraint, "pmx_explain" if constraint is None else "pmx_explain_constrained").explanation()
+
+
+def _constraint(require, exclude):
+    """`require` / `exclude` of `explain` and `explain_modes` normalised to (groups, excluded), None when both are None."""
     if require is None and exclude is None:
-        return _run_explain(model, library, indices, weights, device, None)
+        return None
     groups, excluded = normalize_constraint(require, exclude)
     if any(a >= 128 for g in groups for a in g) or any(a >= 128 for a in excluded):
         raise _ffi.PmxError("constraint: a model has at most 128 clusters (PMX_MAX_MODEL_CLUSTERS)")
-    return _run_explain(model, library, indices, weights, device, (groups, excluded))
+    return groups, excluded
 
 
-def _run_explain(model, library, indices, weights, device, constraint, entry: str | None = None) -> Explanation:
-    """`explain`'s call: `constraint` None (`pmx_explain`, or `entry="pmx_explain_constrained"` with a NULL constraint) or normalised
-    (groups, excluded)."""
+def _explain_rows(model, library: "DeviceLibrary", indices, modes: int, weights, constraint, entry: str) -> "ModeSet":
+    """One call of `entry` (its limits are the call's to enforce) and its rows cut to each ligand's conformers and levels, as a `ModeSet`:
+    `pmx_explain` (no constraint) and `pmx_explain_constrained` (`constraint` None - a NULL constraint - or normalised (groups, excluded))
+    answer with one mode, `pmx_explain_modes` with `modes`."""
     torch = _torch()
     lib = _ffi.load()
     idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
     if (idx < 0).any():
         raise ValueError("negative ligand index")
     n = len(idx)
-    if n > 65536:
-        raise ValueError("at most 65536 ligands per explain call (PMX_EXPLAIN_MAX)")
-    owned = None
-    if not isinstance(library, DeviceLibrary):
-        owned = library = DeviceLibrary(as_packed_library(library), device)
-    dev = library.device
-    mh = device_model(model, dev)
-    tdev = torch.device("cuda", dev)
+    mh = device_model(model, library.device)
+    tdev = torch.device("cuda", library.device)
     L, CM = 20, 64  # PMX_MAX_LEVELS, PMX_MAX_CONFORMERS
     m = max(n, 1)
+    rows = m if n * modes > 65536 else m * modes  # (a call the library refuses writes nothing)
     lig = torch.from_numpy(idx).to(tdev)
-    conf_max = torch.empty((m, CM), dtype=torch.float64, device=tdev)
-    match = torch.empty((m, CM, L), dtype=torch.uint8, device=tdev)
+    values = torch.empty((rows, CM), dtype=torch.float64, device=tdev)
+    match = torch.empty((rows, CM, L), dtype=torch.uint8, device=tdev)
     levels = torch.empty((m, L), dtype=torch.uint8, device=tdev)
     best = torch.empty(m, dtype=torch.int32, device=tdev)
     status = torch.empty(m, dtype=torch.int32, device=tdev)
-    try:
-        with torch.cuda.device(tdev):
-            stream = torch.cuda.current_stream(tdev)
-            outs = (lig.data_ptr(), n, conf_max.data_ptr(), match.data_ptr(), levels.data_ptr(), best.data_ptr(), status.data_ptr(),
-                    ctypes.c_void_p(stream.cuda_stream))
-            if constraint is None and entry != "pmx_explain_constrained":
-                _ffi.check(lib.pmx_explain(mh.handle, library.handle, _weights_array(weights), *outs))
-            else:
-                con = ctypes.byref(_constraint_struct(*constraint)) if constraint is not None else None
-                _ffi.check(lib.pmx_explain_constrained(mh.handle, library.handle, _weights_array(weights), con, *outs))
-            stream.synchronize()
-    finally:
-        if owned is not None:
-            torch.cuda.synchronize(tdev)
-            owned.close()
-    cm, mt, lv = conf_max.cpu().numpy()[:n], match.cpu().numpy()[:n], levels.cpu().numpy()[:n]
+    with torch.cuda.device(tdev):
+        stream = torch.cuda.current_stream(tdev)
+        con = ctypes.byref(_constraint_struct(*constraint)) if constraint is not None else None
+        which = {"pmx_explain": (), "pmx_explain_constrained": (con,), "pmx_explain_modes": (con, modes)}[entry]
+        _ffi.check(getattr(lib, entry)(mh.handle, library.handle, _weights_array(weights), *which, lig.data_ptr(), n, values.data_ptr(), match.data_ptr(),
+                                       levels.data_ptr(), best.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+    vl, mt, lv = values.cpu().numpy().reshape(-1, modes, CM)[:n], match.cpu().numpy().reshape(-1, modes, CM, L)[:n], levels.cpu().numpy()[:n]
     st, bc = status.cpu().numpy()[:n].astype(np.int32), best.cpu().numpy()[:n].astype(np.int64)
-    conf = _conformer_counts(library, idx)
-    out_cm, out_lv, out_mt = [], [], []
+    conf = _record_counts(library, idx, 1)
+    out_vl, out_lv, out_mt = [], [], []
     for i in range(n):
         nl = int(np.count_nonzero(lv[i] != NO_LEVEL))
         C = int(conf[i]) if st[i] == 0 else 0
-        out_cm.append(cm[i, :C].copy() if st[i] == 0 else np.full(1, np.nan))
+        out_vl.append(vl[i, :, :C].copy() if st[i] == 0 else np.full((modes, 1), np.nan))
         out_lv.append(lv[i, :nl].astype(np.int64))
-        key = mt[i, :C, :nl].astype(np.int64)
+        key = mt[i, :, :C, :nl].astype(np.int64)
         key[key == NO_MATCH] = -1
         out_mt.append(key)
-    return Explanation(indices=idx.astype(np.int64), conf_max=out_cm, best_conformer=bc, levels=out_lv, match=out_mt, status=st,
-                       require=constraint[0] if constraint is not None else None, exclude=constraint[1] if constraint is not None else None)
+    return ModeSet(indices=idx.astype(np.int64), modes=modes, values=out_vl, match=out_mt, levels=out_lv, best_conformer=bc, status=st,
+                   require=constraint[0] if constraint is not None else None, exclude=constraint[1] if constraint is not None else None)
 
 
 def concat_explanations(parts: list) -> Explanation:
@@ -661,67 +651,15 @@ def explain_modes(model, library, indices, modes: int = 4, weights: dict[str, fl
     modes = int(modes)
     if not 1 <= modes <= _ffi.MAX_MODES:
         raise _ffi.PmxError(f"{modes} modes (1 to {_ffi.MAX_MODES}, PMX_MAX_MODES)")
-    constraint = None
-    if require is not None or exclude is not None:
-        constraint = normalize_constraint(require, exclude)
-        if any(a >= 128 for g in constraint[0] for a in g) or any(a >= 128 for a in constraint[1]):
-            raise _ffi.PmxError("constraint: a model has at most 128 clusters (PMX_MAX_MODEL_CLUSTERS)")
+    constraint = _constraint(require, exclude)
     idx = np.asarray(indices, dtype=np.int64).reshape(-1)
-    owned = None
-    if not isinstance(library, DeviceLibrary):
-        owned = library = DeviceLibrary(as_packed_library(library), device)
-    try:
-        step = 65536 // modes
-        parts = [_run_modes(model, library, idx[lo : lo + step], modes, weights, constraint) for lo in range(0, max(len(idx), 1), step)]
-    finally:
-        if owned is not None:
-            _torch().cuda.synchronize(_torch().device("cuda", owned.device))
-            owned.close()
+    step = 65536 // modes
+    with _resident(library, device) as dlib:
+        parts = [_explain_rows(model, dlib, idx[lo : lo + step], modes, weights, constraint, "pmx_explain_modes") for lo in range(0, max(len(idx), 1), step)]
     return ModeSet(indices=np.concatenate([p.indices for p in parts]), modes=modes, values=[v for p in parts for v in p.values],
                    match=[m for p in parts for m in p.match], levels=[v for p in parts for v in p.levels],
                    best_conformer=np.concatenate([p.best_conformer for p in parts]), status=np.concatenate([p.status for p in parts]),
                    require=parts[0].require, exclude=parts[0].exclude)
-
-
-def _run_modes(model, library: "DeviceLibrary", idx, modes: int, weights, constraint) -> ModeSet:
-    """One `pmx_explain_modes` call (its limits are the call's to enforce)."""
-    torch = _torch()
-    lib = _ffi.load()
-    idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).reshape(-1))
-    if (idx < 0).any():
-        raise ValueError("negative ligand index")
-    n = len(idx)
-    mh = device_model(model, library.device)
-    tdev = torch.device("cuda", library.device)
-    L, CM = 20, 64  # PMX_MAX_LEVELS, PMX_MAX_CONFORMERS
-    m = max(n, 1)
-    rows = m if n * modes > 65536 else m * modes  # (a call the library refuses writes nothing)
-    lig = torch.from_numpy(idx).to(tdev)
-    values = torch.empty((rows, CM), dtype=torch.float64, device=tdev)
-    match = torch.empty((rows, CM, L), dtype=torch.uint8, device=tdev)
-    levels = torch.empty((m, L), dtype=torch.uint8, device=tdev)
-    best = torch.empty(m, dtype=torch.int32, device=tdev)
-    status = torch.empty(m, dtype=torch.int32, device=tdev)
-    with torch.cuda.device(tdev):
-        stream = torch.cuda.current_stream(tdev)
-        con = ctypes.byref(_constraint_struct(*constraint)) if constraint is not None else None
-        _ffi.check(lib.pmx_explain_modes(mh.handle, library.handle, _weights_array(weights), con, modes, lig.data_ptr(), n, values.data_ptr(), match.data_ptr(),
-                                         levels.data_ptr(), best.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
-        stream.synchronize()
-    vl, mt, lv = values.cpu().numpy().reshape(-1, modes, CM)[:n], match.cpu().numpy().reshape(-1, modes, CM, L)[:n], levels.cpu().numpy()[:n]
-    st, bc = status.cpu().numpy()[:n].astype(np.int32), best.cpu().numpy()[:n].astype(np.int64)
-    conf = _conformer_counts(library, idx)
-    out_vl, out_lv, out_mt = [], [], []
-    for i in range(n):
-        nl = int(np.count_nonzero(lv[i] != NO_LEVEL))
-        C = int(conf[i]) if st[i] == 0 else 0
-        out_vl.append(vl[i, :, :C].copy() if st[i] == 0 else np.full((modes, 1), np.nan))
-        out_lv.append(lv[i, :nl].astype(np.int64))
-        key = mt[i, :, :C, :nl].astype(np.int64)
-        key[key == NO_MATCH] = -1
-        out_mt.append(key)
-    return ModeSet(indices=idx.astype(np.int64), modes=modes, values=out_vl, match=out_mt, levels=out_lv, best_conformer=bc, status=st,
-                   require=constraint[0] if constraint is not None else None, exclude=constraint[1] if constraint is not None else None)
 
 
 @dataclass
@@ -753,16 +691,12 @@ def screen_constrained(model, library, topk: int, require=None, exclude=None, we
     covers the float32 rounding of the screen's score and its summation order, the strict `>` a tie from outside. Until then the pool
     doubles (only the new ligands are explained), from `pool` (default max(4 topk, 4096)) up to the library or `max_pool`, where the
     result comes back with `exact` False."""
-    torch = _torch()
     topk = int(topk)
     if topk <= 0:
         raise ValueError("topk must be positive")
     groups, excluded = normalize_constraint(require, exclude)
-    owned = None
-    if not isinstance(library, DeviceLibrary):
-        owned = library = DeviceLibrary(as_packed_library(library), device)
-    try:
-        res = screen(model, library, weights=weights)
+    with _resident(library, device) as dlib:
+        res = screen(model, dlib, weights=weights)
         sc, st = res.scores.cpu().numpy(), res.status.cpu().numpy()
         total = len(sc)
         rank = np.where(st != 0, -np.inf, np.nan_to_num(sc.astype(np.float64), nan=-np.inf))
@@ -773,7 +707,7 @@ def screen_constrained(model, library, topk: int, require=None, exclude=None, we
         parts, done, con = [], 0, []
         while True:
             for lo in range(done, n, 65536):
-                parts.append(explain(model, library, order[lo : min(lo + 65536, n)], weights=weights, require=groups, exclude=excluded))
+                parts.append(explain(model, dlib, order[lo : min(lo + 65536, n)], weights=weights, require=groups, exclude=excluded))
                 con.append(parts[-1].scores)
             done = n
             cs = np.nan_to_num(np.concatenate(con) if con else np.zeros(0), nan=0.0)
@@ -789,13 +723,9 @@ def screen_constrained(model, library, topk: int, require=None, exclude=None, we
             if exact or (max_pool is not None and n >= int(max_pool)):
                 break
             n = min(total, 2 * n if max_pool is None else min(2 * n, int(max_pool)))
-        ex = concat_explanations(parts) if parts else explain(model, library, [], weights=weights, require=groups, exclude=excluded)
-    finally:
-        if owned is not None:
-            torch.cuda.synchronize(torch.device("cuda", owned.device))
-            owned.close()
+        ex = concat_explanations(parts) if parts else explain(model, dlib, [], weights=weights, require=groups, exclude=excluded)
     return ConstrainedScreeningResult(indices=order[best].astype(np.int64), scores=cs[best].astype(np.float64), unconstrained=sc[order[best]].astype(np.float32),
-                                      explanation=_take_rows(ex, best), pool=int(n), exact=bool(exact), screen=res if owned is None else None)
+                                      explanation=_take_rows(ex, best), pool=int(n), exact=bool(exact), screen=res if dlib is library else None)
 
 
 KEY_INVALID = 4  # include/pmx.h PMX_LIGAND_KEY_INVALID
@@ -866,36 +796,29 @@ def attribute(model, library, indices, conformers, keys, weights: dict[str, floa
         if ((k < -1) | (k >= NO_LEVEL)).any():
             raise ValueError(f"key {i}: a model cluster index or -1 per level")
         kb[i, : len(k)] = np.where(k < 0, NO_MATCH, k).astype(np.uint8)
-    owned = None
-    if not isinstance(library, DeviceLibrary):
-        owned = library = DeviceLibrary(as_packed_library(library), device)
-    dev = library.device
-    mh = device_model(model, dev)
-    tdev = torch.device("cuda", dev)
-    m = max(n, 1)
-    lig = torch.from_numpy(idx).to(tdev)
-    cf = torch.from_numpy(np.clip(conf, -1, 2**31 - 1).astype(np.int32)).to(tdev)
-    key = torch.from_numpy(kb).to(tdev)
-    total = torch.empty(m, dtype=torch.float64, device=tdev)
-    node = torch.empty((m, NN), dtype=torch.float64, device=tdev)
-    entry = torch.empty((m, L, L), dtype=torch.float32, device=tdev)
-    fails = torch.empty((m, L, L), dtype=torch.int16, device=tdev)
-    levels = torch.empty((m, L), dtype=torch.uint8, device=tdev)
-    status = torch.empty(m, dtype=torch.int32, device=tdev)
-    try:
+    with _resident(library, device) as dlib:
+        dev = dlib.device
+        mh = device_model(model, dev)
+        tdev = torch.device("cuda", dev)
+        m = max(n, 1)
+        lig = torch.from_numpy(idx).to(tdev)
+        cf = torch.from_numpy(np.clip(conf, -1, 2**31 - 1).astype(np.int32)).to(tdev)
+        key = torch.from_numpy(kb).to(tdev)
+        total = torch.empty(m, dtype=torch.float64, device=tdev)
+        node = torch.empty((m, NN), dtype=torch.float64, device=tdev)
+        entry = torch.empty((m, L, L), dtype=torch.float32, device=tdev)
+        fails = torch.empty((m, L, L), dtype=torch.int16, device=tdev)
+        levels = torch.empty((m, L), dtype=torch.uint8, device=tdev)
+        status = torch.empty(m, dtype=torch.int32, device=tdev)
         with torch.cuda.device(tdev):
             stream = torch.cuda.current_stream(tdev)
-            _ffi.check(lib.pmx_attribute(mh.handle, library.handle, _weights_array(weights), lig.data_ptr(), cf.data_ptr(), key.data_ptr(), n,
+            _ffi.check(lib.pmx_attribute(mh.handle, dlib.handle, _weights_array(weights), lig.data_ptr(), cf.data_ptr(), key.data_ptr(), n,
                                          total.data_ptr(), node.data_ptr(), entry.data_ptr(), fails.data_ptr(), levels.data_ptr(), status.data_ptr(),
                                          ctypes.c_void_p(stream.cuda_stream)))
             stream.synchronize()
-    finally:
-        if owned is not None:
-            torch.cuda.synchronize(tdev)
-            owned.close()
+        nn = _record_counts(dlib, idx, 0)
     tt, nd, en = total.cpu().numpy()[:n], node.cpu().numpy()[:n], entry.cpu().numpy()[:n]
     fl, lv, st = fails.cpu().numpy()[:n].view(np.uint16), levels.cpu().numpy()[:n], status.cpu().numpy()[:n].astype(np.int32)
-    nn = _record_counts(library, idx, 0)
     out_nd, out_en, out_fl, out_lv = [], [], [], []
     for i in range(n):
         nl = int(np.count_nonzero(lv[i] != NO_LEVEL))

@@ -1,6 +1,6 @@
 """Binding modes restated for the tests (`pmx_explain_modes`): per conformer the M best leaves of `explain_ref.tree_leaves` - those that
 hold the conformer with a score > 0 and qualify under a constraint - by descending score, equal scores in iteration order; a CPU model
-of the MODES walker of csrc/pmx_explain.hip with its drops; and the reading of tests/golden/modes_<set>.npz
+of the walker of csrc/pmx_explain.hip (M = 1: `pmx_explain`) with its drops; and the reading of tests/golden/modes_<set>.npz
 (tests/golden/make_golden_modes.py)."""
 
 from __future__ import annotations
@@ -117,7 +117,7 @@ def completion_bounds(model, record, tables):
 
 
 def walk_modes_with_drops(model, record, weights7, M: int, require=(), exclude=(), tables=None, bounds=None):
-    """The MODES walker restated: per conformer M values, descending, and their keys; a leaf enters iff its total is strictly above the
+    """The explain walker restated for M modes: per conformer M values, descending, and their keys; a leaf enters iff its total is strictly above the
     M-th value, behind every entry >= it; a subtree at a drop site is left out when no conformer it holds can reach its M-th value
     ((total + R) * slack < M-th, strictly) or - the constrained walker's rule - when no leaf below can qualify. Returns (values [M, C],
     keys [M][C], nodes walked): values and keys must be `ranked_modes` of the full tree."""

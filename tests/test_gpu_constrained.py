@@ -67,14 +67,14 @@ def test_reference_constrained_fixtures(name):
 def test_empty_constraint_is_pmx_explain(name):
     """No constraint through pmx_explain_constrained (a NULL constraint: the unconstrained kernels; an empty one: the constrained
     kernels with nothing to test) is bit for bit pmx_explain, on every row of the set."""
-    from pharmaconet_amd.engine import DeviceLibrary, _run_explain, explain
+    from pharmaconet_amd.engine import DeviceLibrary, _explain_rows, explain
 
     model, lib, weights, _ = load_golden(name)
     dlib = DeviceLibrary(lib)
     idx = np.arange(len(lib))
     base = explain(model, dlib, idx, weights=weights)
     assert base.require is None and base.exclude is None
-    null = _run_explain(model, dlib, idx, weights, None, None, entry="pmx_explain_constrained")
+    null = _explain_rows(model, dlib, idx, 1, weights, None, "pmx_explain_constrained").explanation()
     empty = explain(model, dlib, idx, weights=weights, require=[], exclude=[])
     assert empty.require == () and empty.exclude == ()
     for r in idx:

@@ -259,3 +259,55 @@ def test_screening_result_explain_and_cli(tmp_path):
             lc, mc = pair.split("->")
             assert 0 <= int(lc) < lib.header(int(f[1].split("#")[-1]))[2]
             assert 0 <= int(mc.split(":")[0]) < K and mc.split(":")[1] == model.flat.cluster_type[int(mc.split(":")[0])]
+
+
+def test_three_entry_points_write_their_rows_and_no_more():
+    """The three C entry points on raw buffers with one sentinel row (0xA5 bytes) behind what each call owns: pmx_explain and
+    pmx_explain_constrained fill [n][64] and [n][64][20] - one mode of the one walker - and pmx_explain_modes [n][3][64] and
+    [n][3][64][20]; the sentinel rows stay, and the owned rows are what `explain` and `explain_modes` cut their answers from."""
+    import ctypes
+
+    import torch
+
+    from pharmaconet_amd import _ffi
+    from pharmaconet_amd.engine import DeviceLibrary, _weights_array, device_model, explain, explain_modes
+
+    model, lib, weights, _ = load_golden("set_c21_c8")
+    dlib = DeviceLibrary(lib)
+    idx = np.array([5, 0, len(lib) - 1, len(lib) + 7], dtype=np.int64)  # (the last one is outside the library)
+    n, L, CM = len(idx), 20, 64
+    dev = torch.device("cuda", dlib.device)
+    head = (device_model(model, dlib.device).handle, dlib.handle, _weights_array(weights))
+    lig = torch.from_numpy(idx).to(dev)
+    empty = _ffi.MatchConstraint()
+    calls = (("pmx_explain", (), 1, explain(model, dlib, idx, weights=weights)),
+             ("pmx_explain_constrained", (ctypes.byref(empty),), 1, explain(model, dlib, idx, weights=weights, require=[], exclude=[])),
+             ("pmx_explain_modes", (None, 3), 3, explain_modes(model, dlib, idx, modes=3, weights=weights)))
+    for entry, which, M, want in calls:
+        row = dict(values=M * CM * 8, match=M * CM * L, levels=L, best=4, status=4)  # bytes per ligand
+        buf = {k: torch.full(((n + 1) * b,), 0xA5, dtype=torch.uint8, device=dev) for k, b in row.items()}
+        stream = torch.cuda.current_stream(dev)
+        _ffi.check(getattr(_ffi.load(), entry)(*head, *which, lig.data_ptr(), n, buf["values"].data_ptr(), buf["match"].data_ptr(), buf["levels"].data_ptr(),
+                                               buf["best"].data_ptr(), buf["status"].data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+        raw = {k: v.cpu().numpy() for k, v in buf.items()}
+        for k, b in row.items():
+            assert (raw[k][n * b :] == 0xA5).all(), (entry, k)
+        values = raw["values"][: n * row["values"]].view(np.float64).reshape(n, M, CM)
+        match = raw["match"][: n * row["match"]].reshape(n, M, CM, L)
+        levels = raw["levels"][: n * L].reshape(n, L)
+        best, status = raw["best"][: n * 4].view(np.int32), raw["status"][: n * 4].view(np.int32)
+        ms = want if M > 1 else None
+        assert status.tolist() == want.status.tolist() == [0, 0, 0, 1] and best.tolist() == want.best_conformer.tolist(), entry
+        assert np.isnan(values[3]).all() and best[3] == -1, entry
+        for r in range(3):
+            C, nl = lib.header(int(idx[r]))[1], len(want.levels[r])
+            assert levels[r, :nl].tolist() == want.levels[r].tolist() and (levels[r, nl:] == 0xFE).all(), (entry, r)
+            got_v = values[r, :, :C]
+            got_k = match[r, :, :C, :nl].astype(np.int64)
+            got_k[got_k == 0xFF] = -1
+            if ms is not None:
+                assert np.array_equal(got_v, ms.values[r]) and np.array_equal(got_k, ms.match[r]), (entry, r)
+            else:
+                assert np.array_equal(got_v[0], want.conf_max[r]) and np.array_equal(got_k[0], want.match[r]), (entry, r)
+            assert (values[r, :, C:] == 0).all() and (match[r, :, C:] == 0xFF).all() and (match[r, :, :, nl:] == 0xFF).all(), (entry, r)

@@ -1,4 +1,4 @@
-"""`pmx_explain_modes` on the GPU (csrc/pmx_explain.hip, the MODES walker): per conformer the best leaves of the reference's tree, checked
+"""`pmx_explain_modes` on the GPU (csrc/pmx_explain.hip: the one explain walker, here with M modes): per conformer the best leaves of the reference's tree, checked
 against the reference's own ranked leaves (tests/golden/modes_<set>.npz), `explain` (mode 0, bit for bit), the NumPy restatement
 (tests/modes_ref.py) and `attribute`."""
 
@@ -228,7 +228,7 @@ def test_invariance_and_two_streams(monkeypatch):
 def test_edge_cases():
     from pharmaconet_amd import PackedLibrary
     from pharmaconet_amd._ffi import PmxError
-    from pharmaconet_amd.engine import DeviceLibrary, _run_modes, explain, explain_modes
+    from pharmaconet_amd.engine import DeviceLibrary, _explain_rows, explain, explain_modes
     from pharmaconet_amd.library import UNSUPPORTED_RECORD, LigandFeatures, pack_ligand
 
     model, lib, _, _ = load_golden("set_c21_c8")
@@ -244,7 +244,7 @@ def test_edge_cases():
     # n * modes beyond PMX_EXPLAIN_MAX: the engine cuts the list, the call itself refuses
     many = np.full(65536 // 8 + 5, 3)
     with pytest.raises(PmxError):
-        _run_modes(model, dsmall, many, 8, None, None)
+        _explain_rows(model, dsmall, many, 8, None, None, "pmx_explain_modes")
     ms = explain_modes(model, dsmall, many, modes=8)
     assert len(ms) == len(many) and all(same_mode(ms, r, m, ms, 0) for r in (1, len(many) // 2, len(many) - 1) for m in range(8))
     plain = explain(model, dsmall, [3])

@@ -120,6 +120,7 @@ def device_times(model, dlib, weights, ex, repeat):
             e1.synchronize()
             times.append(e0.elapsed_time(e1))
         out[name] = round(min(times[1:]), 3)
+        out[name + "_all"] = [round(t, 3) for t in times[1:]]
     return out
 
 
