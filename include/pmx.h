@@ -422,6 +422,49 @@ int pmx_attribute(const pmx_model *model, const pmx_library *lib, const float we
                   const int32_t *conformer_dev, const uint8_t *key_dev /* [n][PMX_MAX_LEVELS] */, uint32_t n, double *total_dev, double *node_dev,
                   float *entry_dev, uint16_t *fails_dev, uint8_t *levels_dev, int32_t *status_dev, void *stream);
 
+/*
+ * Where a binding mode sits in the pocket: row i takes library ligand ligands_dev[i], conformer c = conformer_dev[i] and a key key_dev[i],
+ * in the format of pmx_attribute's rows, and answers with the rigid motion that brings the matched ligand nodes onto the pharmacophore
+ * points of the model nodes they are matched to. The reference has no counterpart (it scores distances only); float64 throughout.
+ *   pairs      for every matched level l (k[l] != 0xFF; q = levels[l], a = k[l]) and every node u of q in the level's match list (as
+ *              pmx_attribute defines it, graph_match.py:139-172): every model node m of cluster a whose type is in u's type mask forms a
+ *              pair (u, m) of weight w = weights[node_type[m]]; pairs with w <= 0 are left out. x_u is u's float32 position for
+ *              conformer c, widened; y_m = node_center_dev[m], the model node's `center`.
+ *   R, t       the proper rotation and the translation that minimise sum_pairs w |R x_u + t - y_m|^2: W = sum w, weighted centroids xbar
+ *              and ybar, S = sum w (x_u - xbar)(y_m - ybar)^T, Horn's symmetric 4x4 matrix N of S, its eigenvalues by cyclic Jacobi, the
+ *              quaternion q of the largest (the lowest index on equal eigenvalues: N = 0 gives q = (1, 0, 0, 0), R = I), R from q,
+ *              t = ybar - R xbar. Never a reflection: a mirrored ligand gets the best proper rotation and a residual. With one fitted
+ *              node S is taken as 0: R = I exactly and t = ybar - xbar.
+ *   fit[0]     W
+ *   fit[1]     sse = sum_pairs w |R x_u + t - y_m|^2, summed from the posed points
+ *   fit[2]     rmsd = sqrt(sse / W)
+ *   fit[3]     rmsd_nodes = sqrt(sum_u W_u |R x_u + t - ybar_u|^2 / W), W_u and ybar_u node u's weight sum and weighted target centroid
+ *              (sse = rmsd_nodes^2 W + sum_u sum_m w |y_m - ybar_u|^2: several targets per node add a constant the fit cannot change)
+ *   fit[4]     E0 = sum_pairs w (|x_u - xbar|^2 + |y_m - ybar|^2)
+ *   fit[5]     gap = lambda_1 - lambda_2 of N: the rotation is unique only where gap / E0 is not tiny (fitted nodes in one point or on a
+ *              line leave a rotation free); the caller decides
+ *   fit[6, 7]  0
+ * Outputs, per row:
+ *   rot_dev     double [n][9]  R, row-major          trans_dev  double [n][3]  t          fit_dev  double [n][8]
+ *   node_dev    double [n][PMX_MAX_LIGAND_NODES]  |R x_u + t - ybar_u| of a fitted node (one with a pair); -1 for every other node of the
+ *                                                 record and for the lanes beyond it
+ *   count_dev   int32  [n][2]  {fitted nodes, pairs}
+ *   levels_dev  uint8  [n][PMX_MAX_LEVELS]  as pmx_attribute writes it
+ *   status_dev  int32  [n]  PMX_LIGAND_OK; PMX_LIGAND_UNSUPPORTED as pmx_attribute reports it; PMX_LIGAND_KEY_INVALID when c is not a
+ *                           conformer of the ligand or some k[l] != 0xFF is not a candidate of level l. The key need not be a leaf of
+ *                           the tree: no score is computed, so "what would this mode look like" is allowed.
+ * A row that is not OK has NaN in rot, trans, fit and node, and counts of 0. A valid row without pairs (a key of all 0xFF, a ligand without
+ * levels, W = 0) has R = I, t = 0 and all fit values 0. n <= PMX_EXPLAIN_MAX; n = 0 succeeds; a NULL node_center_dev with n > 0 is
+ * PMX_ERR_INVALID. Stream-ordered like pmx_attribute (enqueued, no synchronisation). One wavefront per row (pmx_align.hip), fixed-order
+ * sums, no floating-point atomic: the same call gives the same bits on every run.
+ */
+int pmx_align(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES],
+              const double *node_center_dev /* [n_nodes][3], model node m's `center` */,
+              const uint64_t *ligands_dev, const int32_t *conformer_dev, const uint8_t *key_dev /* [n][PMX_MAX_LEVELS] */, uint32_t n,
+              double *rot_dev /* [n][9] row-major R */, double *trans_dev /* [n][3] t */, double *fit_dev /* [n][8] */,
+              double *node_dev /* [n][PMX_MAX_LIGAND_NODES] */, int32_t *count_dev /* [n][2] */,
+              uint8_t *levels_dev /* [n][PMX_MAX_LEVELS] */, int32_t *status_dev, void *stream);
+
 /* Frees the scoring workspaces libpmx keeps between calls on `device` (synchronises the device first). */
 int pmx_release_workspaces(int device);
 

@@ -23,6 +23,7 @@
 #include "pmx_debug.h"
 #include "pmx_explain.h"
 #include "pmx_attribute.h"
+#include "pmx_align.h"
 
 using namespace pmx;
 
@@ -585,7 +586,7 @@ struct ScreenWs {
     DevBuf pabuf;                    // path_bound()'s pair sums: ligand kernel's wavefronts | task kernel's
     DevBuf arena, queue;
     DevBuf lists;                    // uint32: ovf | carry | heavy
-    DevBuf acur;                     // uint32: pmx_attribute's row cursor
+    DevBuf acur;                     // uint32: the row cursor of pmx_attribute and pmx_align
     size_t arena_shrunk_to = 0;      // the arena size that was accepted when memory was short (0: never shrunk)
     int num_cu = 0;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // profiling: call start | last chunk: ligand kernels start, done | end | last chunk: rounds start, done
@@ -1270,6 +1271,40 @@ extern "C" int pmx_attribute(const pmx_model *model, const pmx_library *lib, con
     const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(kLdsPerCu / pmx_attr::lds_bytes(), 8));
     const unsigned blocks = std::min<unsigned>(n, (unsigned)ws.num_cu * per_cu);
     if (!pmx_attr::launch(blocks, stream, &p, sizeof p, a)) return fail(PMX_ERR_INVALID, "the attribution kernel (pmx_attribute.hip) does not match this build's parameter block");
+    HIPCHECK(hipGetLastError());
+    return PMX_OK;
+}
+
+// ------------------------------------------------------------------------------------ rigid fit of a binding mode (pmx_align.hip)
+// As pmx_attribute: one kernel over the call's rows; of the workspace of (device, stream) the CU count and the row cursor.
+extern "C" int pmx_align(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const double *node_center_dev,
+                         const uint64_t *ligands_dev, const int32_t *conformer_dev, const uint8_t *key_dev, uint32_t n, double *rot_dev, double *trans_dev,
+                         double *fit_dev, double *node_dev, int32_t *count_dev, uint8_t *levels_dev, int32_t *status_dev, void *stream_) {
+    if (!model || !lib || !weights) return fail(PMX_ERR_INVALID, "null argument");
+    if (n > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "more than %d rows in one align call", PMX_EXPLAIN_MAX);
+    if (n == 0) return PMX_OK;
+    if (!node_center_dev || !ligands_dev || !conformer_dev || !key_dev || !rot_dev || !trans_dev || !fit_dev || !node_dev || !count_dev || !levels_dev || !status_dev)
+        return fail(PMX_ERR_INVALID, "null argument");
+    if (model->device != lib->device) return fail(PMX_ERR_INVALID, "model and library live on different devices");
+    HIPCHECK(hipSetDevice(lib->device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const HeldWs held = hold_screen(lib->device, stream);
+    ScreenWs &ws = *held.ws;
+    const int rc = init_workspace(ws, lib->device, stream);
+    if (rc) return rc;
+    HIPCHECK(ws.acur.grow(256, stream));
+    HIPCHECK(hipMemsetAsync(ws.acur.ptr, 0, 4, stream));
+    ScreenParams p{};
+    p.M = model->dm;
+    p.lib = lib->dl;
+    p.sidtab = model->sidtab;
+    p.sub_off = model->sub_off;
+    p.sub_nodes = model->sub_nodes;
+    p.W = to_weights(weights);
+    const pmx_aln::Args a{ligands_dev, conformer_dev, key_dev, n, node_center_dev, rot_dev, trans_dev, fit_dev, node_dev, count_dev, levels_dev, status_dev, ws.acur.as<uint32_t>()};
+    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(kLdsPerCu / pmx_aln::lds_bytes(), 8));
+    const unsigned blocks = std::min<unsigned>(n, (unsigned)ws.num_cu * per_cu);
+    if (!pmx_aln::launch(blocks, stream, &p, sizeof p, a)) return fail(PMX_ERR_INVALID, "the fit kernel (pmx_align.hip) does not match this build's parameter block");
     HIPCHECK(hipGetLastError());
     return PMX_OK;
 }

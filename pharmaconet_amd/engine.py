@@ -16,7 +16,7 @@ from . import _ffi
 from .constants import weights_vector
 from .library import PackedLibrary, as_packed_library
 
-__all__ = ["Attribution", "DeviceLibrary", "Explanation", "ScreeningResult", "attribute", "explain", "score_one", "screen", "topk", "device_model", "last_score_stats"]
+__all__ = ["Alignment", "Attribution", "DeviceLibrary", "Explanation", "ScreeningResult", "align", "attribute", "explain", "score_one", "screen", "topk", "device_model", "last_score_stats"]
 
 
 def _torch():
@@ -57,6 +57,16 @@ class _ModelHandle:
         handle = ctypes.c_void_p()
         _ffi.check(lib.pmx_model_create(ctypes.byref(desc), device, ctypes.byref(handle)))
         self.handle = handle
+        self._node_centers = None
+
+    def node_centers(self, model):
+        """The model nodes' `center` as a float64 [Nm, 3] tensor on the handle's device (`pmx_align`'s targets): uploaded on first use, kept."""
+        if self._node_centers is None:
+            torch = _torch()
+            host = np.zeros((max(model.num_nodes, 1), 3), dtype=np.float64)  # (never an empty buffer: a model without nodes has no pairs either)
+            host[: model.num_nodes] = model.node_centers
+            self._node_centers = torch.from_numpy(host).to(torch.device("cuda", self.device))
+        return self._node_centers
 
     def __del__(self):
         try:
@@ -443,15 +453,28 @@ class Explanation:
         """`attribute` of every row with status 0, at its best conformer (or `conformer`) under that conformer's own key: which nodes
         carry the explained maximum. `rows` of the result says which row of this explanation each of its rows is. A constrained
         explanation needs nothing more: the reported keys are attributed, and they are the qualifying leaves' keys."""
+        rows, conf, keys = self._own_rows(conformer)
+        out = attribute(model, library, self.indices[rows], conf, keys, weights=weights)
+        out.rows = np.asarray(rows, dtype=np.int64)
+        return out
+
+    def poses(self, model, library, conformer: int | None = None, weights: dict[str, float] | None = None) -> "Alignment":
+        """`align` of every row with status 0, at its best conformer (or `conformer`) under that conformer's own key: where the explained
+        match puts the ligand in the pocket. `rows` of the result says which row of this explanation each of its rows is."""
+        rows, conf, keys = self._own_rows(conformer)
+        out = align(model, library, self.indices[rows], conf, keys, weights=weights)
+        out.rows = np.asarray(rows, dtype=np.int64)
+        return out
+
+    def _own_rows(self, conformer):
+        """The rows with status 0, the conformer each is looked at (its best one, or `conformer`) and that conformer's own key."""
         rows = [i for i in range(len(self)) if self.status[i] == 0]
         conf = [int(self.best_conformer[i]) if conformer is None else int(conformer) for i in rows]
         keys = []
         for i, c in zip(rows, conf):
             m = self.match[i]
             keys.append(m[c] if 0 <= c < m.shape[0] else np.full(len(self.levels[i]), -1, np.int64))  # (not a conformer of the ligand: reported by the row's status)
-        out = attribute(model, library, self.indices[rows], conf, keys, weights=weights)
-        out.rows = np.asarray(rows, dtype=np.int64)
-        return out
+        return rows, conf, keys
 
 
 def _record_counts(library: "DeviceLibrary", idx: np.ndarray, field: int) -> np.ndarray:
@@ -731,6 +754,33 @@ def screen_constrained(model, library, topk: int, require=None, exclude=None, we
 KEY_INVALID = 4  # include/pmx.h PMX_LIGAND_KEY_INVALID
 
 
+_MAX_LEVELS, _MAX_NODES = 20, 64  # PMX_MAX_LEVELS, PMX_MAX_LIGAND_NODES
+
+
+def _listed_rows(indices, conformers, keys, what: str):
+    """The (ligand, conformer, key) rows of an `attribute` / `align` call as the arrays the C ABI takes: int64 indices, int64 conformers and
+    uint8 keys [max(n, 1), PMX_MAX_LEVELS] with 0xFF for None (shorter keys are filled with None)."""
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+    conf = np.ascontiguousarray(np.asarray(conformers, dtype=np.int64).reshape(-1))
+    n = len(idx)
+    if (idx < 0).any():
+        raise ValueError("negative ligand index")
+    if len(conf) != n or len(keys) != n:
+        raise ValueError("indices, conformers and keys differ in length")
+    if n > 65536:
+        raise ValueError(f"at most 65536 rows per {what} call (PMX_EXPLAIN_MAX)")
+    L = _MAX_LEVELS
+    kb = np.full((max(n, 1), L), NO_MATCH, dtype=np.uint8)
+    for i, k in enumerate(keys):
+        k = np.asarray(k, dtype=np.int64).reshape(-1)
+        if len(k) > L:
+            raise ValueError(f"key {i} has more than {L} levels")
+        if ((k < -1) | (k >= NO_LEVEL)).any():
+            raise ValueError(f"key {i}: a model cluster index or -1 per level")
+        kb[i, : len(k)] = np.where(k < 0, NO_MATCH, k).astype(np.uint8)
+    return idx, conf, kb
+
+
 @dataclass
 class Attribution:
     """What `attribute` returns: one row per (ligand, conformer, key), cut to that ligand's nodes n and tree levels nl (definitions:
@@ -778,24 +828,9 @@ def attribute(model, library, indices, conformers, keys, weights: dict[str, floa
     `as_packed_library` accepts. Runs on torch's current stream of the device and waits for it."""
     torch = _torch()
     lib = _ffi.load()
-    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
-    conf = np.ascontiguousarray(np.asarray(conformers, dtype=np.int64).reshape(-1))
+    idx, conf, kb = _listed_rows(indices, conformers, keys, "attribute")
     n = len(idx)
-    if (idx < 0).any():
-        raise ValueError("negative ligand index")
-    if len(conf) != n or len(keys) != n:
-        raise ValueError("indices, conformers and keys differ in length")
-    if n > 65536:
-        raise ValueError("at most 65536 rows per attribute call (PMX_EXPLAIN_MAX)")
-    L, NN = 20, 64  # PMX_MAX_LEVELS, PMX_MAX_LIGAND_NODES
-    kb = np.full((max(n, 1), L), NO_MATCH, dtype=np.uint8)
-    for i, k in enumerate(keys):
-        k = np.asarray(k, dtype=np.int64).reshape(-1)
-        if len(k) > L:
-            raise ValueError(f"key {i} has more than {L} levels")
-        if ((k < -1) | (k >= NO_LEVEL)).any():
-            raise ValueError(f"key {i}: a model cluster index or -1 per level")
-        kb[i, : len(k)] = np.where(k < 0, NO_MATCH, k).astype(np.uint8)
+    L, NN = _MAX_LEVELS, _MAX_NODES
     with _resident(library, device) as dlib:
         dev = dlib.device
         mh = device_model(model, dev)
@@ -829,6 +864,87 @@ def attribute(model, library, indices, conformers, keys, weights: dict[str, floa
         out_lv.append(lv[i, :nl].astype(np.int64))
     return Attribution(indices=idx.astype(np.int64), conformers=conf.astype(np.int64), total=tt.copy() if n else np.zeros(0), node=out_nd, entry=out_en,
                        fails=out_fl, levels=out_lv, status=st)
+
+
+@dataclass
+class Alignment:
+    """What `align` returns: one row per (ligand, conformer, key) - the rigid motion that puts the matched nodes of the conformer onto the
+    pharmacophore points of the model nodes they are matched to, and how well (definitions: `pmx_align` in include/pmx.h). All float64.
+
+    rotation[i]     [3, 3] proper rotation R        translation[i]  [3] t: a point x of the conformer sits at R x + t in the pocket
+    weight[i]       W, the sum of the pair weights  sse[i]          sum over pairs of w |R x_u + t - y_m|^2
+    rmsd[i]         sqrt(sse / W)                   rmsd_nodes[i]   the same with every node's targets replaced by their weighted centroid
+    scale[i]        E0 = sum w (|x_u - xbar|^2 + |y_m - ybar|^2)
+    gap[i]          lambda_1 - lambda_2 of Horn's matrix: where gap / scale is tiny (one fitted node, nodes on a line) the rotation is not unique
+    node[i]         [n]: per node of the packed record its distance from its targets' centroid after the fit, -1 for a node without a pair
+    n_nodes[i], n_pairs[i]  fitted nodes and pairs  levels[i]       int [nl]: the ligand cluster behind each tree level
+    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer of the ligand, or a match that is no candidate
+                    of its level); every float of such a row is NaN. A valid row without pairs has R = I, t = 0 and zeros."""
+
+    indices: np.ndarray
+    conformers: np.ndarray
+    rotation: np.ndarray
+    translation: np.ndarray
+    rmsd: np.ndarray
+    rmsd_nodes: np.ndarray
+    weight: np.ndarray
+    sse: np.ndarray
+    scale: np.ndarray
+    gap: np.ndarray
+    node: list
+    n_nodes: np.ndarray
+    n_pairs: np.ndarray
+    levels: list
+    status: np.ndarray
+    rows: "np.ndarray | None" = None  # `Explanation.poses`: the explanation's row behind each row
+
+    def __len__(self) -> int:
+        return len(self.indices)
+
+    def transform(self, i: int, positions) -> np.ndarray:
+        """Row i's motion applied to any [..., 3] array of points of the conformer's frame - a whole molecule's atoms, say: positions @ R.T + t."""
+        return np.asarray(positions, dtype=np.float64) @ self.rotation[i].T + self.translation[i]
+
+
+def align(model, library, indices, conformers, keys, weights: dict[str, float] | None = None, device=None) -> Alignment:
+    """The rigid fit (`pmx_align`, csrc/pmx_align.hip) of library ligand `indices[i]`'s conformer `conformers[i]` under the match `keys[i]`, rows as
+    `attribute` takes them. The key need not be a leaf of the ligand's tree. At most 65536 rows; any order, repeats allowed. `library` is a
+    `DeviceLibrary` or anything `as_packed_library` accepts. Runs on torch's current stream of the device and waits for it."""
+    torch = _torch()
+    lib = _ffi.load()
+    idx, conf, kb = _listed_rows(indices, conformers, keys, "align")
+    n = len(idx)
+    L, NN = _MAX_LEVELS, _MAX_NODES
+    with _resident(library, device) as dlib:
+        dev = dlib.device
+        mh = device_model(model, dev)
+        tdev = torch.device("cuda", dev)
+        m = max(n, 1)
+        with torch.cuda.device(tdev):
+            centers = mh.node_centers(model)
+            lig = torch.from_numpy(idx).to(tdev)
+            cf = torch.from_numpy(np.clip(conf, -1, 2**31 - 1).astype(np.int32)).to(tdev)
+            key = torch.from_numpy(kb).to(tdev)
+            rot = torch.empty((m, 3, 3), dtype=torch.float64, device=tdev)
+            trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
+            fit = torch.empty((m, 8), dtype=torch.float64, device=tdev)
+            node = torch.empty((m, NN), dtype=torch.float64, device=tdev)
+            count = torch.empty((m, 2), dtype=torch.int32, device=tdev)
+            levels = torch.empty((m, L), dtype=torch.uint8, device=tdev)
+            status = torch.empty(m, dtype=torch.int32, device=tdev)
+            stream = torch.cuda.current_stream(tdev)
+            _ffi.check(lib.pmx_align(mh.handle, dlib.handle, _weights_array(weights), centers.data_ptr(), lig.data_ptr(), cf.data_ptr(),
+                                     key.data_ptr(), n, rot.data_ptr(), trans.data_ptr(), fit.data_ptr(), node.data_ptr(), count.data_ptr(), levels.data_ptr(),
+                                     status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+            stream.synchronize()
+        nn = _record_counts(dlib, idx, 0)
+    ft, nd, cn = fit.cpu().numpy()[:n], node.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
+    lv, st = levels.cpu().numpy()[:n], status.cpu().numpy()[:n].astype(np.int32)
+    out_nd = [nd[i, : int(nn[i]) if st[i] != 1 else 0].copy() for i in range(n)]
+    out_lv = [lv[i, : int(np.count_nonzero(lv[i] != NO_LEVEL))].astype(np.int64) for i in range(n)]
+    return Alignment(indices=idx.astype(np.int64), conformers=conf.astype(np.int64), rotation=rot.cpu().numpy()[:n].copy(), translation=trans.cpu().numpy()[:n].copy(),
+                     rmsd=ft[:, 2].copy(), rmsd_nodes=ft[:, 3].copy(), weight=ft[:, 0].copy(), sse=ft[:, 1].copy(), scale=ft[:, 4].copy(), gap=ft[:, 5].copy(),
+                     node=out_nd, n_nodes=cn[:, 0].copy(), n_pairs=cn[:, 1].copy(), levels=out_lv, status=st)
 
 
 def last_score_stats() -> dict:

@@ -242,6 +242,12 @@ class PharmacophoreModel:
     def num_nodes(self) -> int:
         return self.flat.num_nodes
 
+    @property
+    def node_centers(self) -> np.ndarray:
+        """float64 [Nm, 3]: `nodes[m].center`, the pharmacophore point of every model node (what `engine.align` fits ligand nodes onto)."""
+        assert self._state is not None, "empty model"
+        return np.array([[float(v) for v in node["center"]] for node in self._state["nodes"]], dtype=np.float64).reshape(-1, 3)
+
     # The reference's object graph (`pharmacophore_model.py:191-204,207-365`), built on first use from the state dict: code
     # written against `model.nodes / .edges / .node_dict / .node_cluster_dict / .node_clusters` keeps working. Read-only views -
     # scoring never touches them (the device tables come from `flat`).
@@ -393,6 +399,42 @@ class PharmacophoreModel:
             raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
         return dict(conformer=int(conformer), key=np.asarray(key, dtype=np.int64), levels=at.levels[0], total=float(at.total[0]), node=at.node[0],
                     entry=at.entry[0], fails=at.fails[0], status=int(at.status[0]))
+
+    def scoring_pose(self, ligand, weights: dict[str, float] | None = None, conformer: int | None = None, key=None) -> dict:
+        """One ligand put into the pocket (`engine.align`): by default its best conformer under the explaining leaf's match, else `conformer`
+        and / or `key` (a model cluster or -1 per tree level; it need not be a leaf of the tree). `positions` [n_atoms, 3] are the
+        conformer's atom positions after the fit (None when `ligand` is a packed record, which holds nodes, not atoms), `node_positions` [n, 3]
+        those of the record's nodes; `rotation`, `translation`, `rmsd`, `rmsd_nodes`, `weight`, `sse`, `scale`, `gap`, `node`, `n_nodes`,
+        `n_pairs`, `levels` and `status` as `engine.Alignment` has them, with `conformer` and `key`. Takes what `_scoring` takes."""
+        from .engine import align, explain
+        from .library import as_packed_library
+
+        packed = as_packed_library(ligand)
+        if len(packed) != 1:
+            raise ValueError("scoring_pose takes exactly one ligand")
+        if conformer is None or key is None:
+            ex = explain(self, packed, [0], weights=weights)
+            if int(ex.status[0]) != 0:
+                n, c, _ = packed.header(0)
+                raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+            if conformer is None:
+                conformer = int(ex.best_conformer[0])
+            if key is None:
+                if not 0 <= int(conformer) < ex.match[0].shape[0]:
+                    raise ValueError(f"the ligand has {ex.match[0].shape[0]} conformers")
+                key = ex.match[0][int(conformer)]
+        al = align(self, packed, [0], [int(conformer)], [key], weights=weights)
+        if int(al.status[0]) == 1:
+            n, c, _ = packed.header(0)
+            raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+        ok = int(al.status[0]) == 0
+        atoms = getattr(ligand, "atom_positions", None)  # [n_atoms, C, 3] of a `Ligand` / `LigandFeatures`
+        positions = al.transform(0, np.asarray(atoms, dtype=np.float64)[:, int(conformer)]) if ok and atoms is not None else None
+        node_positions = al.transform(0, packed.unpack(0)["xyz"][:, :, int(conformer)].astype(np.float64)) if ok else None
+        return dict(conformer=int(conformer), key=np.asarray(key, dtype=np.int64), positions=positions, node_positions=node_positions,
+                    rotation=al.rotation[0], translation=al.translation[0], rmsd=float(al.rmsd[0]), rmsd_nodes=float(al.rmsd_nodes[0]),
+                    weight=float(al.weight[0]), sse=float(al.sse[0]), scale=float(al.scale[0]), gap=float(al.gap[0]), node=al.node[0],
+                    n_nodes=int(al.n_nodes[0]), n_pairs=int(al.n_pairs[0]), levels=al.levels[0], status=int(al.status[0]))
 
     def explain(self, library, indices, weights: dict[str, float] | None = None, **kwargs):
         """Per-conformer maxima and explaining matches of library ligands `indices` (`engine.explain`)."""

@@ -32,6 +32,7 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--explain", type=int, default=0, metavar="K", help="also explain the K best hits (best conformer and its cluster matches)")
         cfg.add_argument("--explain_out", type=str, default=None, help="CSV of the explained hits (default: <out>.explain.csv)")
         cfg.add_argument("--explain_nodes", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per pharmacophore node of each explained hit and the node's share of the hit's best conformer maximum")
+        cfg.add_argument("--poses", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit and the rigid motion (rotation, translation) that puts its best conformer onto the matched pharmacophore points")
         cfg.add_argument("--modes", type=int, default=None, metavar="M", help="with --explain K: also list the M (1 to 8) best binding modes of each explained hit's best conformer")
         cfg.add_argument("--modes_out", type=str, default=None, metavar="PATH", help="CSV of the modes (default: <out>.modes.csv)")
         cfg.add_argument("--require", action="append", default=[], metavar="LIST", help="constrained matching: comma-separated model cluster indices, one of which a hit's match must hold (repeatable: one group each)")
@@ -121,6 +122,8 @@ def main(argv=None) -> None:
     args = parser.parse_args(argv)
     if args.explain_nodes and args.explain <= 0:
         parser.error("--explain_nodes needs --explain K")
+    if args.poses and args.explain <= 0:
+        parser.error("--poses needs --explain K")
     if args.modes is not None and args.explain <= 0:
         parser.error("--modes needs --explain K")
     if args.modes is not None and not 1 <= args.modes <= 8:
@@ -155,6 +158,8 @@ def main(argv=None) -> None:
         write_explain_csv(out, names, scores, status, model, lib, weight, args.explain)
         if args.explain_nodes:
             write_explain_nodes_csv(Path(args.explain_nodes), names, scores, status, model, lib, weight, args.explain)
+        if args.poses:
+            write_poses_csv(Path(args.poses), names, scores, status, model, lib, weight, args.explain)
         if args.modes is not None:
             out = Path(args.modes_out) if args.modes_out else Path(str(args.out) + ".modes.csv")
             write_modes_csv(out, names, scores, status, model, lib, weight, args.explain, args.modes)
@@ -253,6 +258,23 @@ def write_explain_nodes_csv(out: Path, names: list[str], scores: np.ndarray, sta
                 types = "|".join(TYPE_NAMES[t] for t in range(len(TYPE_NAMES)) if tm >> t & 1)
                 frac = float(share) / total if total > 0 else 0.0
                 w.write(f"{int(row) + 1},{i},{names[i]},{int(at.conformers[r])},{u},{types},{lc},{matched.get(lc, '')},{float(share)},{frac}\n")
+
+
+def write_poses_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int) -> None:
+    """One row per hit of the k best, in the order of the explain CSV: the fit of the hit's best conformer under its explaining match
+    (`engine.align`) - the two RMSDs, the fitted nodes and the motion `x -> R x + t` (R row by row) that poses the conformer in the
+    pocket. Every number is the `repr` of the float64 the GPU returned."""
+    from .engine import explain
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
+    with open(out, "w") as w:
+        w.write("rank,path,conformer,rmsd,rmsd_nodes,fitted_nodes," + ",".join(f"r{i}{j}" for i in range(3) for j in range(3)) + ",tx,ty,tz\n")
+        for r, row in enumerate(al.rows):
+            nums = [al.rmsd[r], al.rmsd_nodes[r]], [*al.rotation[r].reshape(-1), *al.translation[r]]
+            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{','.join(repr(float(v)) for v in nums[0])},{int(al.n_nodes[r])},"
+                    f"{','.join(repr(float(v)) for v in nums[1])}\n")
 
 
 if __name__ == "__main__":

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Time of `engine.explain` for the top hits of a screen (the cost of inspecting them, include/pmx.h pmx_explain).
 
-    python tools/explain_bench.py [--ligands 1000000] [--hits 1000] [--library bench|survey|stress] [--repeat 3] [--attribute]
+    python tools/explain_bench.py [--ligands 1000000] [--hits 1000] [--library bench|survey|stress] [--repeat 3] [--attribute] [--align]
 
 Scores the library once (pmx_score_f64), ranks it on the host and times explain of the `--hits` best ligands on a resident library,
 best of `--repeat` calls after one warm-up call. With `--attribute` also `engine.attribute` of the same hits at their best conformer under
 their own key (`Explanation.attribution`), and - the host's packing and cutting of 65 536 rows being most of either wall time - the device
-time of the two C calls alone between HIP events. Prints one JSON line."""
+time of the two C calls alone between HIP events. With `--align` the same for `engine.align` (`Explanation.poses`, pmx_align). Prints one JSON line."""
 import argparse
 import json
 import sys
@@ -27,6 +27,7 @@ def main():
     ap.add_argument("--library", choices=("bench", "survey", "stress"), default="bench")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--attribute", action="store_true", help="also time engine.attribute of the same hits")
+    ap.add_argument("--align", action="store_true", help="also time engine.align of the same hits")
     a = ap.parse_args()
     import torch
 
@@ -70,6 +71,16 @@ def main():
             at = ex.attribution(model, dlib, weights=weights)
             wall.append(time.perf_counter() - t0)
         extra = dict(attribute_rows=len(at), attribute_ms=round(1e3 * min(wall), 3), attribute_invalid=int((at.status != 0).sum()), **device_times(model, dlib, weights, ex, a.repeat))
+    if a.align:
+        al = ex.poses(model, dlib, weights=weights)  # warm-up (the node centres go to the device)
+        wall = []
+        for _ in range(a.repeat):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            al = ex.poses(model, dlib, weights=weights)
+            wall.append(time.perf_counter() - t0)
+        extra.update(align_rows=len(al), align_ms=round(1e3 * min(wall), 3), align_invalid=int((al.status != 0).sum()),
+                     **device_times(model, dlib, weights, ex, a.repeat, ("explain_device_ms", "align_device_ms")))
     means = np.array([m.mean() for m in ex.conf_max])
     print(json.dumps(dict(**extra, library=a.library, ligands=dlib.num_ligands, hits=len(top), explain_ms=round(1e3 * min(times), 3),
                           explain_ms_all=[round(1e3 * t, 3) for t in times], max_abs_diff_vs_score=float(np.abs(means - sc[top]).max()),
@@ -77,8 +88,9 @@ def main():
                           score_pass_longest_walk=int(stats["max_passes"]), score_pass_split_trees=int(stats["n_heavy"]))))
 
 
-def device_times(model, dlib, weights, ex, repeat):
-    """pmx_explain and pmx_attribute of the explanation's OK rows between HIP events on the current stream: best of `repeat`, in ms."""
+def device_times(model, dlib, weights, ex, repeat, which=("explain_device_ms", "attribute_device_ms")):
+    """pmx_explain, pmx_attribute and pmx_align (those of `which`) of the explanation's OK rows between HIP events on the current stream:
+    best of `repeat`, in ms."""
     import ctypes
 
     import torch
@@ -102,15 +114,22 @@ def device_times(model, dlib, weights, ex, repeat):
     best, st = torch.empty(n, dtype=i32, device=dev), torch.empty(n, dtype=i32, device=dev)
     tot, nd = torch.empty(n, dtype=f64, device=dev), torch.empty((n, 64), dtype=f64, device=dev)
     en, fl = torch.empty((n, 20, 20), dtype=torch.float32, device=dev), torch.empty((n, 20, 20), dtype=torch.int16, device=dev)
+    rot, tr, fit = torch.empty((n, 9), dtype=f64, device=dev), torch.empty((n, 3), dtype=f64, device=dev), torch.empty((n, 8), dtype=f64, device=dev)
+    cnt = torch.empty((n, 2), dtype=i32, device=dev)
     mh, w = device_model(model, dlib.device), _weights_array(weights)
+    ctr = mh.node_centers(model)
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     calls = dict(
         explain_device_ms=lambda: lib.pmx_explain(mh.handle, dlib.handle, w, lig.data_ptr(), n, cm.data_ptr(), mt.data_ptr(), lv.data_ptr(), best.data_ptr(), st.data_ptr(), stream),
         attribute_device_ms=lambda: lib.pmx_attribute(mh.handle, dlib.handle, w, lig.data_ptr(), conf.data_ptr(), key.data_ptr(), n, tot.data_ptr(), nd.data_ptr(),
                                                       en.data_ptr(), fl.data_ptr(), lv.data_ptr(), st.data_ptr(), stream),
+        align_device_ms=lambda: lib.pmx_align(mh.handle, dlib.handle, w, ctr.data_ptr(), lig.data_ptr(), conf.data_ptr(), key.data_ptr(), n, rot.data_ptr(), tr.data_ptr(),
+                                              fit.data_ptr(), nd.data_ptr(), cnt.data_ptr(), lv.data_ptr(), st.data_ptr(), stream),
     )
     out = {}
     for name, call in calls.items():
+        if name not in which:
+            continue
         times = []
         for _ in range(repeat + 1):  # (the first is a warm-up)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
