@@ -415,7 +415,7 @@ int pmx_explain_modes(const pmx_model *model, const pmx_library *lib, const floa
  *   status_dev    int32  [n]  PMX_LIGAND_OK; PMX_LIGAND_UNSUPPORTED for an index outside the library, a header-only record or a ligand
  *                             pmx_score reports unsupported; PMX_LIGAND_KEY_INVALID for a row that is not valid
  * A key of all 0xFF, or a ligand without levels, is valid with total 0. n <= PMX_EXPLAIN_MAX; n = 0 succeeds. The call is stream-ordered
- * like pmx_explain (enqueued, no synchronisation). One wavefront per row (pmx_attribute.hip); no score table, no tabulated pair function,
+ * like pmx_explain (enqueued, no synchronisation). One wavefront per row (pmx_rows.hip); no score table, no tabulated pair function,
  * no table arena: any weights, and no dependence on PMX_TAILS_RATIO. The same call gives the same bits on every run.
  */
 int pmx_attribute(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev,
@@ -455,7 +455,7 @@ int pmx_attribute(const pmx_model *model, const pmx_library *lib, const float we
  *                           the tree: no score is computed, so "what would this mode look like" is allowed.
  * A row that is not OK has NaN in rot, trans, fit and node, and counts of 0. A valid row without pairs (a key of all 0xFF, a ligand without
  * levels, W = 0) has R = I, t = 0 and all fit values 0. n <= PMX_EXPLAIN_MAX; n = 0 succeeds; a NULL node_center_dev with n > 0 is
- * PMX_ERR_INVALID. Stream-ordered like pmx_attribute (enqueued, no synchronisation). One wavefront per row (pmx_align.hip), fixed-order
+ * PMX_ERR_INVALID. Stream-ordered like pmx_attribute (enqueued, no synchronisation). One wavefront per row (pmx_rows.hip), fixed-order
  * sums, no floating-point atomic: the same call gives the same bits on every run.
  */
 int pmx_align(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES],

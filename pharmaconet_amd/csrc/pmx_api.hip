@@ -22,8 +22,7 @@
 #include "pmx_screen.hip"
 #include "pmx_debug.h"
 #include "pmx_explain.h"
-#include "pmx_attribute.h"
-#include "pmx_align.h"
+#include "pmx_rows.h"
 
 using namespace pmx;
 
@@ -1240,20 +1239,19 @@ extern "C" int pmx_explain_modes(const pmx_model *model, const pmx_library *lib,
     return explain_call(model, lib, weights, constraint, n_modes, ligands_dev, n, mode_max_dev, mode_match_dev, levels_dev, best_conformer_dev, status_dev, stream);
 }
 
-// ------------------------------------------------------------------------------------ attribution (pmx_attribute.hip)
-// One kernel over the call's rows: no tables, no slices, no arena. Of the workspace of (device, stream) it takes the CU count and four
-// bytes for its row cursor, cleared in stream order in front of the launch.
-extern "C" int pmx_attribute(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev,
-                             const int32_t *conformer_dev, const uint8_t *key_dev, uint32_t n, double *total_dev, double *node_dev, float *entry_dev,
-                             uint16_t *fails_dev, uint8_t *levels_dev, int32_t *status_dev, void *stream_) {
+// ------------------------------------------------------------------------------------ the row kernels (pmx_rows.hip)
+// pmx_attribute and pmx_align: one kernel over the call's rows; no tables, no slices, no arena. Of the workspace of (device, stream) it
+// takes the CU count and four bytes for its row cursor, cleared in stream order in front of the launch. `what`: the call's name in a
+// message; null_out: one of the caller's own device pointers is null; launch(blocks, p, cursor) starts the caller's kernel.
+template <class Launch>
+static int row_call(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], uint32_t n, const char *what, bool null_out,
+                    pmx_rows::Kind kind, hipStream_t stream, Launch launch) {
     if (!model || !lib || !weights) return fail(PMX_ERR_INVALID, "null argument");
-    if (n > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "more than %d rows in one attribute call", PMX_EXPLAIN_MAX);
+    if (n > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "more than %d rows in one %s call", PMX_EXPLAIN_MAX, what);
     if (n == 0) return PMX_OK;
-    if (!ligands_dev || !conformer_dev || !key_dev || !total_dev || !node_dev || !entry_dev || !fails_dev || !levels_dev || !status_dev)
-        return fail(PMX_ERR_INVALID, "null argument");
+    if (null_out) return fail(PMX_ERR_INVALID, "null argument");
     if (model->device != lib->device) return fail(PMX_ERR_INVALID, "model and library live on different devices");
     HIPCHECK(hipSetDevice(lib->device));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     const HeldWs held = hold_screen(lib->device, stream);
     ScreenWs &ws = *held.ws;
     const int rc = init_workspace(ws, lib->device, stream);
@@ -1267,44 +1265,31 @@ extern "C" int pmx_attribute(const pmx_model *model, const pmx_library *lib, con
     p.sub_off = model->sub_off;
     p.sub_nodes = model->sub_nodes;
     p.W = to_weights(weights);
-    const pmx_attr::Args a{ligands_dev, conformer_dev, key_dev, n, total_dev, node_dev, entry_dev, fails_dev, levels_dev, status_dev, ws.acur.as<uint32_t>()};
-    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(kLdsPerCu / pmx_attr::lds_bytes(), 8));
+    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(kLdsPerCu / pmx_rows::lds_bytes(kind), 8));
     const unsigned blocks = std::min<unsigned>(n, (unsigned)ws.num_cu * per_cu);
-    if (!pmx_attr::launch(blocks, stream, &p, sizeof p, a)) return fail(PMX_ERR_INVALID, "the attribution kernel (pmx_attribute.hip) does not match this build's parameter block");
+    if (!launch(blocks, p, ws.acur.as<uint32_t>())) return fail(PMX_ERR_INVALID, "the %s kernel (pmx_rows.hip) does not match this build's parameter block", what);
     HIPCHECK(hipGetLastError());
     return PMX_OK;
 }
 
-// ------------------------------------------------------------------------------------ rigid fit of a binding mode (pmx_align.hip)
-// As pmx_attribute: one kernel over the call's rows; of the workspace of (device, stream) the CU count and the row cursor.
+extern "C" int pmx_attribute(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev,
+                             const int32_t *conformer_dev, const uint8_t *key_dev, uint32_t n, double *total_dev, double *node_dev, float *entry_dev,
+                             uint16_t *fails_dev, uint8_t *levels_dev, int32_t *status_dev, void *stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const bool null_out = !ligands_dev || !conformer_dev || !key_dev || !total_dev || !node_dev || !entry_dev || !fails_dev || !levels_dev || !status_dev;
+    return row_call(model, lib, weights, n, "attribute", null_out, pmx_rows::kAttribute, stream, [&](unsigned blocks, const ScreenParams &p, uint32_t *cursor) {
+        const pmx_rows::AttributeArgs a{{ligands_dev, conformer_dev, key_dev, n, levels_dev, status_dev, cursor}, total_dev, node_dev, entry_dev, fails_dev};
+        return pmx_rows::launch(pmx_rows::kAttribute, blocks, stream, &p, sizeof p, &a);
+    });
+}
+
 extern "C" int pmx_align(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const double *node_center_dev,
                          const uint64_t *ligands_dev, const int32_t *conformer_dev, const uint8_t *key_dev, uint32_t n, double *rot_dev, double *trans_dev,
                          double *fit_dev, double *node_dev, int32_t *count_dev, uint8_t *levels_dev, int32_t *status_dev, void *stream_) {
-    if (!model || !lib || !weights) return fail(PMX_ERR_INVALID, "null argument");
-    if (n > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "more than %d rows in one align call", PMX_EXPLAIN_MAX);
-    if (n == 0) return PMX_OK;
-    if (!node_center_dev || !ligands_dev || !conformer_dev || !key_dev || !rot_dev || !trans_dev || !fit_dev || !node_dev || !count_dev || !levels_dev || !status_dev)
-        return fail(PMX_ERR_INVALID, "null argument");
-    if (model->device != lib->device) return fail(PMX_ERR_INVALID, "model and library live on different devices");
-    HIPCHECK(hipSetDevice(lib->device));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const HeldWs held = hold_screen(lib->device, stream);
-    ScreenWs &ws = *held.ws;
-    const int rc = init_workspace(ws, lib->device, stream);
-    if (rc) return rc;
-    HIPCHECK(ws.acur.grow(256, stream));
-    HIPCHECK(hipMemsetAsync(ws.acur.ptr, 0, 4, stream));
-    ScreenParams p{};
-    p.M = model->dm;
-    p.lib = lib->dl;
-    p.sidtab = model->sidtab;
-    p.sub_off = model->sub_off;
-    p.sub_nodes = model->sub_nodes;
-    p.W = to_weights(weights);
-    const pmx_aln::Args a{ligands_dev, conformer_dev, key_dev, n, node_center_dev, rot_dev, trans_dev, fit_dev, node_dev, count_dev, levels_dev, status_dev, ws.acur.as<uint32_t>()};
-    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(kLdsPerCu / pmx_aln::lds_bytes(), 8));
-    const unsigned blocks = std::min<unsigned>(n, (unsigned)ws.num_cu * per_cu);
-    if (!pmx_aln::launch(blocks, stream, &p, sizeof p, a)) return fail(PMX_ERR_INVALID, "the fit kernel (pmx_align.hip) does not match this build's parameter block");
-    HIPCHECK(hipGetLastError());
-    return PMX_OK;
+    const bool null_out = !node_center_dev || !ligands_dev || !conformer_dev || !key_dev || !rot_dev || !trans_dev || !fit_dev || !node_dev || !count_dev || !levels_dev || !status_dev;
+    return row_call(model, lib, weights, n, "align", null_out, pmx_rows::kAlign, stream, [&](unsigned blocks, const ScreenParams &p, uint32_t *cursor) {
+        const pmx_rows::AlignArgs a{{ligands_dev, conformer_dev, key_dev, n, levels_dev, status_dev, cursor}, node_center_dev, rot_dev, trans_dev, fit_dev, node_dev, count_dev};
+        return pmx_rows::launch(pmx_rows::kAlign, blocks, stream, &p, sizeof p, &a);
+    });
 }

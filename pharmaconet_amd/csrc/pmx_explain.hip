@@ -136,21 +136,12 @@ __device__ void explain_walk(const ScreenParams &p, unsigned char *lds, const Ex
     // ---- the levels of the row and the model clusters that are candidates of each
     const Record r = parse_record(p.lib.data + p.lib.offsets[lig]);
     {
-        unsigned long long cb0 = 0, cb1 = 0;
-        if (lane < r.ncl) {
-            const int cs = lane ? r.cluster_end[lane - 1] : 0, ce = r.cluster_end[lane];
-            unsigned lm = 0;
-            for (int u = cs; u < ce; ++u) lm |= r.typemask[u];
-            cb0 = p.M.tclus[2u * (lm & 127u)];
-            cb1 = p.M.tclus[2u * (lm & 127u) + 1u];
-        }
-        const bool has = (cb0 | cb1) != 0ull;
-        const unsigned long long bal = __ballot(has);
-        const int lev = __popcll(bal & ((1ull << lane) - 1ull));
-        if (has && lev < nl) { // (scan_ligand's levels: clusters with a candidate, in priority order, at most PMX_MAX_LEVELS)
-            a.levels[(size_t)li * PMX_MAX_LEVELS + lev] = (uint8_t)lane;
-            cbl[2 * lev] = cb0;
-            cbl[2 * lev + 1] = cb1;
+        const ClusterCand k = cluster_candidates(p, r, r.ncl, lane, [&r](int u) { return (unsigned)r.typemask[u]; });
+        const LevelSlot s = level_slot(k, lane);
+        if (s.has && s.lev < nl) { // (nl is the record header's: prepare_ligand has refused a ligand with too many candidates at a level)
+            a.levels[(size_t)li * PMX_MAX_LEVELS + s.lev] = (uint8_t)lane;
+            cbl[2 * s.lev] = k.cb0;
+            cbl[2 * s.lev + 1] = k.cb1;
         }
     }
     bool go = true; // (no leaf can qualify when a require group has no cluster among the candidates of any level)

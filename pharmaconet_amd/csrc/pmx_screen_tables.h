@@ -1,7 +1,8 @@
 // pmx_screen_tables.h - the table phase of the screening path (device): from a packed ligand record to its score tables and search
 // bounds in a wave's slice or in the arena. The wave helpers, the pair-function builder (fn_build_kernel), the table items, scan_ligand,
 // build_tables, chain_lengths, build_bounds and prepare_ligand, which strings them together. The product walker (pmx_screen_walk.h)
-// and the explain walker (pmx_explain.hip) both start from what prepare_ligand leaves. Layouts: pmx_screen_layout.h.
+// and the explain walker (pmx_explain.hip) both start from what prepare_ligand leaves; the row kernels (pmx_rows.hip) take parse_record and the
+// level rule (cluster_candidates, level_slot) only. Layouts: pmx_screen_layout.h.
 #pragma once
 #include <type_traits>
 
@@ -545,6 +546,46 @@ __device__ __forceinline__ LevelInfo scan_ligand(const ScreenParams &p, unsigned
     L.ksumtot = (uint32_t)uni((int)scal[0]);
     L.T = (uint32_t)uni((int)scal[1]);
     return L;
+}
+
+// The same level rule for the kernels that open one listed ligand outside the score pass (pmx_rows.hip, explain_walk): which tree a key
+// talks about. scan_ligand keeps its own lines - the score pass is bound by instruction issue and tuned as it stands - so a change of the
+// rule is made there and here.
+// What lane `lane` knows about ligand cluster `lane` (< ncl) of the record: its nodes [cs, ce) and the model clusters that share a type
+// with one of them (PMX_MAX_MODEL_CLUSTERS bits); zeros in the other lanes. tm(u): type mask of node u.
+struct ClusterCand {
+    int cs, ce;
+    unsigned long long cb0, cb1;
+};
+template <class TypeMask>
+__device__ __forceinline__ ClusterCand cluster_candidates(const ScreenParams &p, const Record &r, int ncl, int lane, TypeMask tm) {
+    ClusterCand k{0, 0, 0ull, 0ull};
+    if (lane < ncl) {
+        k.cs = lane ? r.cluster_end[lane - 1] : 0;
+        k.ce = r.cluster_end[lane];
+        unsigned lm = 0;
+        for (int u = k.cs; u < k.ce; ++u) lm |= tm(u);
+        k.cb0 = p.M.tclus[2u * (lm & 127u)];
+        k.cb1 = p.M.tclus[2u * (lm & 127u) + 1u];
+    }
+    return k;
+}
+// The ballot over the wavefront's clusters: `has` a candidate, then level `lev` of the tree when lev < nl (priority order, at most
+// PMX_MAX_LEVELS); too_many: a level has more than PMX_MAX_LEVEL_CANDIDATES candidates, which makes the ligand unsupported.
+struct LevelSlot {
+    bool has;
+    int lev, nl;
+    bool too_many;
+};
+__device__ __forceinline__ LevelSlot level_slot(const ClusterCand &k, int lane) {
+    LevelSlot s;
+    s.has = (k.cb0 | k.cb1) != 0ull;
+    const int kc = (int)__popcll(k.cb0) + (int)__popcll(k.cb1);
+    const unsigned long long bal = __ballot(s.has);
+    s.lev = __popcll(bal & ((1ull << lane) - 1ull));
+    s.nl = min((int)__popcll(bal), PMX_MAX_LEVELS);
+    s.too_many = __ballot(s.has && s.lev < PMX_MAX_LEVELS && kc > PMX_MAX_LEVEL_CANDIDATES) != 0ull;
+    return s;
 }
 
 struct Pos3 {

@@ -781,6 +781,34 @@ def _listed_rows(indices, conformers, keys, what: str):
     return idx, conf, kb
 
 
+def _row_call(model, library, indices, conformers, keys, what: str, device, call):
+    """The part `attribute` and `align` share: the rows (`_listed_rows`) go to the resident library's device, `call(lib, mh, dlib, m, ptrs)` -
+    m = max(n, 1) rows to allocate, ptrs = (ligands, conformers, keys, n, levels, status, stream) as the C ABI takes them - allocates the call's
+    own outputs and invokes the C function on torch's current stream; this waits for the stream. Returns idx, conf, what `call` returned, and per
+    row the levels cut to the ligand's, the node count (0 for status 1) and the status."""
+    torch = _torch()
+    lib = _ffi.load()
+    idx, conf, kb = _listed_rows(indices, conformers, keys, what)
+    n = len(idx)
+    with _resident(library, device) as dlib:
+        mh = device_model(model, dlib.device)
+        tdev = torch.device("cuda", dlib.device)
+        m = max(n, 1)
+        with torch.cuda.device(tdev):
+            lig = torch.from_numpy(idx).to(tdev)
+            cf = torch.from_numpy(np.clip(conf, -1, 2**31 - 1).astype(np.int32)).to(tdev)
+            key = torch.from_numpy(kb).to(tdev)
+            levels = torch.empty((m, _MAX_LEVELS), dtype=torch.uint8, device=tdev)
+            status = torch.empty(m, dtype=torch.int32, device=tdev)
+            stream = torch.cuda.current_stream(tdev)
+            out = call(lib, mh, dlib, m, (lig.data_ptr(), cf.data_ptr(), key.data_ptr(), n, levels.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+            stream.synchronize()
+        nn = _record_counts(dlib, idx, 0)
+    lv, st = levels.cpu().numpy()[:n], status.cpu().numpy()[:n].astype(np.int32)
+    out_lv = [lv[i, : int(np.count_nonzero(lv[i] != NO_LEVEL))].astype(np.int64) for i in range(n)]
+    return idx.astype(np.int64), conf.astype(np.int64), out, out_lv, [int(nn[i]) if st[i] != 1 else 0 for i in range(n)], st
+
+
 @dataclass
 class Attribution:
     """What `attribute` returns: one row per (ligand, conformer, key), cut to that ligand's nodes n and tree levels nl (definitions:
@@ -822,48 +850,31 @@ class Attribution:
 
 
 def attribute(model, library, indices, conformers, keys, weights: dict[str, float] | None = None, device=None) -> Attribution:
-    """Entries, total and node shares (`pmx_attribute`, csrc/pmx_attribute.hip) of the leaf `keys[i]` of library ligand `indices[i]` for its
+    """Entries, total and node shares (`pmx_attribute`, csrc/pmx_rows.hip) of the leaf `keys[i]` of library ligand `indices[i]` for its
     conformer `conformers[i]`. A key is an int array with a model cluster per tree level and -1 for None - the form `Explanation.match[i][c]`
     has; shorter keys are filled with None. At most 65536 rows; any order, repeats allowed. `library` is a `DeviceLibrary` or anything
     `as_packed_library` accepts. Runs on torch's current stream of the device and waits for it."""
     torch = _torch()
-    lib = _ffi.load()
-    idx, conf, kb = _listed_rows(indices, conformers, keys, "attribute")
-    n = len(idx)
     L, NN = _MAX_LEVELS, _MAX_NODES
-    with _resident(library, device) as dlib:
-        dev = dlib.device
-        mh = device_model(model, dev)
-        tdev = torch.device("cuda", dev)
-        m = max(n, 1)
-        lig = torch.from_numpy(idx).to(tdev)
-        cf = torch.from_numpy(np.clip(conf, -1, 2**31 - 1).astype(np.int32)).to(tdev)
-        key = torch.from_numpy(kb).to(tdev)
+
+    def call(lib, mh, dlib, m, ptrs):
+        lig, cf, key, n, levels, status, stream = ptrs
+        tdev = torch.device("cuda", dlib.device)
         total = torch.empty(m, dtype=torch.float64, device=tdev)
         node = torch.empty((m, NN), dtype=torch.float64, device=tdev)
         entry = torch.empty((m, L, L), dtype=torch.float32, device=tdev)
         fails = torch.empty((m, L, L), dtype=torch.int16, device=tdev)
-        levels = torch.empty((m, L), dtype=torch.uint8, device=tdev)
-        status = torch.empty(m, dtype=torch.int32, device=tdev)
-        with torch.cuda.device(tdev):
-            stream = torch.cuda.current_stream(tdev)
-            _ffi.check(lib.pmx_attribute(mh.handle, dlib.handle, _weights_array(weights), lig.data_ptr(), cf.data_ptr(), key.data_ptr(), n,
-                                         total.data_ptr(), node.data_ptr(), entry.data_ptr(), fails.data_ptr(), levels.data_ptr(), status.data_ptr(),
-                                         ctypes.c_void_p(stream.cuda_stream)))
-            stream.synchronize()
-        nn = _record_counts(dlib, idx, 0)
-    tt, nd, en = total.cpu().numpy()[:n], node.cpu().numpy()[:n], entry.cpu().numpy()[:n]
-    fl, lv, st = fails.cpu().numpy()[:n].view(np.uint16), levels.cpu().numpy()[:n], status.cpu().numpy()[:n].astype(np.int32)
-    out_nd, out_en, out_fl, out_lv = [], [], [], []
-    for i in range(n):
-        nl = int(np.count_nonzero(lv[i] != NO_LEVEL))
-        k = int(nn[i]) if st[i] != 1 else 0
-        out_nd.append(nd[i, :k].copy())
-        out_en.append(en[i, :nl, :nl].copy())
-        out_fl.append(fl[i, :nl, :nl].astype(np.int64))
-        out_lv.append(lv[i, :nl].astype(np.int64))
-    return Attribution(indices=idx.astype(np.int64), conformers=conf.astype(np.int64), total=tt.copy() if n else np.zeros(0), node=out_nd, entry=out_en,
-                       fails=out_fl, levels=out_lv, status=st)
+        _ffi.check(lib.pmx_attribute(mh.handle, dlib.handle, _weights_array(weights), lig, cf, key, n, total.data_ptr(), node.data_ptr(), entry.data_ptr(),
+                                     fails.data_ptr(), levels, status, stream))
+        return total, node, entry, fails
+
+    idx, conf, (total, node, entry, fails), out_lv, nn, st = _row_call(model, library, indices, conformers, keys, "attribute", device, call)
+    n = len(idx)
+    tt, nd, en, fl = total.cpu().numpy()[:n], node.cpu().numpy()[:n], entry.cpu().numpy()[:n], fails.cpu().numpy()[:n].view(np.uint16)
+    nls = [len(v) for v in out_lv]
+    return Attribution(indices=idx, conformers=conf, total=tt.copy() if n else np.zeros(0), node=[nd[i, : nn[i]].copy() for i in range(n)],
+                       entry=[en[i, : nls[i], : nls[i]].copy() for i in range(n)], fails=[fl[i, : nls[i], : nls[i]].astype(np.int64) for i in range(n)],
+                       levels=out_lv, status=st)
 
 
 @dataclass
@@ -907,44 +918,30 @@ class Alignment:
 
 
 def align(model, library, indices, conformers, keys, weights: dict[str, float] | None = None, device=None) -> Alignment:
-    """The rigid fit (`pmx_align`, csrc/pmx_align.hip) of library ligand `indices[i]`'s conformer `conformers[i]` under the match `keys[i]`, rows as
+    """The rigid fit (`pmx_align`, csrc/pmx_rows.hip) of library ligand `indices[i]`'s conformer `conformers[i]` under the match `keys[i]`, rows as
     `attribute` takes them. The key need not be a leaf of the ligand's tree. At most 65536 rows; any order, repeats allowed. `library` is a
     `DeviceLibrary` or anything `as_packed_library` accepts. Runs on torch's current stream of the device and waits for it."""
     torch = _torch()
-    lib = _ffi.load()
-    idx, conf, kb = _listed_rows(indices, conformers, keys, "align")
+
+    def call(lib, mh, dlib, m, ptrs):
+        lig, cf, key, n, levels, status, stream = ptrs
+        tdev = torch.device("cuda", dlib.device)
+        centers = mh.node_centers(model)
+        rot = torch.empty((m, 3, 3), dtype=torch.float64, device=tdev)
+        trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
+        fit = torch.empty((m, 8), dtype=torch.float64, device=tdev)
+        node = torch.empty((m, _MAX_NODES), dtype=torch.float64, device=tdev)
+        count = torch.empty((m, 2), dtype=torch.int32, device=tdev)
+        _ffi.check(lib.pmx_align(mh.handle, dlib.handle, _weights_array(weights), centers.data_ptr(), lig, cf, key, n, rot.data_ptr(), trans.data_ptr(),
+                                 fit.data_ptr(), node.data_ptr(), count.data_ptr(), levels, status, stream))
+        return rot, trans, fit, node, count
+
+    idx, conf, (rot, trans, fit, node, count), out_lv, nn, st = _row_call(model, library, indices, conformers, keys, "align", device, call)
     n = len(idx)
-    L, NN = _MAX_LEVELS, _MAX_NODES
-    with _resident(library, device) as dlib:
-        dev = dlib.device
-        mh = device_model(model, dev)
-        tdev = torch.device("cuda", dev)
-        m = max(n, 1)
-        with torch.cuda.device(tdev):
-            centers = mh.node_centers(model)
-            lig = torch.from_numpy(idx).to(tdev)
-            cf = torch.from_numpy(np.clip(conf, -1, 2**31 - 1).astype(np.int32)).to(tdev)
-            key = torch.from_numpy(kb).to(tdev)
-            rot = torch.empty((m, 3, 3), dtype=torch.float64, device=tdev)
-            trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
-            fit = torch.empty((m, 8), dtype=torch.float64, device=tdev)
-            node = torch.empty((m, NN), dtype=torch.float64, device=tdev)
-            count = torch.empty((m, 2), dtype=torch.int32, device=tdev)
-            levels = torch.empty((m, L), dtype=torch.uint8, device=tdev)
-            status = torch.empty(m, dtype=torch.int32, device=tdev)
-            stream = torch.cuda.current_stream(tdev)
-            _ffi.check(lib.pmx_align(mh.handle, dlib.handle, _weights_array(weights), centers.data_ptr(), lig.data_ptr(), cf.data_ptr(),
-                                     key.data_ptr(), n, rot.data_ptr(), trans.data_ptr(), fit.data_ptr(), node.data_ptr(), count.data_ptr(), levels.data_ptr(),
-                                     status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
-            stream.synchronize()
-        nn = _record_counts(dlib, idx, 0)
     ft, nd, cn = fit.cpu().numpy()[:n], node.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
-    lv, st = levels.cpu().numpy()[:n], status.cpu().numpy()[:n].astype(np.int32)
-    out_nd = [nd[i, : int(nn[i]) if st[i] != 1 else 0].copy() for i in range(n)]
-    out_lv = [lv[i, : int(np.count_nonzero(lv[i] != NO_LEVEL))].astype(np.int64) for i in range(n)]
-    return Alignment(indices=idx.astype(np.int64), conformers=conf.astype(np.int64), rotation=rot.cpu().numpy()[:n].copy(), translation=trans.cpu().numpy()[:n].copy(),
+    return Alignment(indices=idx, conformers=conf, rotation=rot.cpu().numpy()[:n].copy(), translation=trans.cpu().numpy()[:n].copy(),
                      rmsd=ft[:, 2].copy(), rmsd_nodes=ft[:, 3].copy(), weight=ft[:, 0].copy(), sse=ft[:, 1].copy(), scale=ft[:, 4].copy(), gap=ft[:, 5].copy(),
-                     node=out_nd, n_nodes=cn[:, 0].copy(), n_pairs=cn[:, 1].copy(), levels=out_lv, status=st)
+                     node=[nd[i, : nn[i]].copy() for i in range(n)], n_nodes=cn[:, 0].copy(), n_pairs=cn[:, 1].copy(), levels=out_lv, status=st)
 
 
 def last_score_stats() -> dict:

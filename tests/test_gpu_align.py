@@ -1,4 +1,4 @@
-"""`pmx_align` on the GPU (csrc/pmx_align.hip): the rigid fit of listed (ligand, conformer, key) rows against the NumPy restatement of
+"""`pmx_align` on the GPU (csrc/pmx_rows.hip): the rigid fit of listed (ligand, conformer, key) rows against the NumPy restatement of
 tests/align_ref.py (an SVD fit, where the kernel diagonalises Horn's matrix), a planted pose and its mirror image, degenerate and invalid
 rows, repeatability, and the Python layer on top of it.
 
@@ -242,6 +242,49 @@ def test_degenerate_and_invalid_rows_in_one_call():
         assert al.n_nodes[r] == 0 and al.n_pairs[r] == 0
     assert len(al.node[3]) == rec0["n_nodes"] and len(al.node[5]) == 0 and len(al.levels[5]) == 0
     assert al.levels[4].tolist() == ex.levels[i0].tolist()
+
+
+def test_row_calls_agree_on_what_a_row_is():
+    """`pmx_attribute` and `pmx_align` open a row with one front end (open_row in csrc/pmx_rows.hip) and `pmx_explain` finds the levels by the
+    same rule (pmx_screen_tables.h): the same rows, good and bad, through both calls give the same status, levels and node count, and the
+    levels are `explain`'s. With the 22-cluster ligand of test_gpu_attribution.py::test_level_cap: 20 levels in every answer."""
+    from pharmaconet_amd import PackedLibrary
+    from pharmaconet_amd.engine import align, attribute, explain
+    from pharmaconet_amd.library import LigandFeatures, pack_ligand
+
+    model, lib, weights, ex, _ = posed("set_6oim_c8")
+    i0 = next(i for i in range(len(ex)) if ex.status[i] == 0 and 2 <= len(ex.levels[i]) < 20)  # (below 20: a key has room for a match at level nl)
+    pos = (np.asarray(model.flat.cluster_center).mean(axis=0) + np.random.default_rng(11).uniform(-5, 5, (22, 3, 3))).astype(np.float32)
+    capped = None
+    for ftype in ("Halogen", "Cation", "Anion", "HBond_acceptor", "HBond_donor"):
+        one = PackedLibrary.from_records([pack_ligand(LigandFeatures([9] * 22, [[] for _ in range(22)], [(ftype, a, a) for a in range(22)], pos))])
+        if one.header(0)[2] == 22 and candidates(model, one.unpack(0), 0):
+            capped = one.record(0)
+            break
+    assert capped is not None
+    both = PackedLibrary.from_records([lib.record(int(ex.indices[i0])), capped])
+    ex2 = explain(model, both, [0, 1], weights=weights)
+    assert ex2.status.tolist() == [0, 0] and ex2.levels[0].tolist() == ex.levels[i0].tolist() and len(ex2.levels[1]) == 20
+    rec0 = both.unpack(0)
+    nl, C = len(ex2.levels[0]), len(ex2.conf_max[0])
+    c0, c1 = int(ex2.best_conformer[0]), int(ex2.best_conformer[1])
+    key = ex2.match[0][c0]
+    assert 2 <= nl < 20 and (key >= 0).any()
+    l0 = int(np.flatnonzero(key >= 0)[0])
+    stranger = key.copy()
+    stranger[l0] = next(m for m in range(model.flat.num_clusters) if m not in candidates(model, rec0, int(ex2.levels[0][l0])))
+    beyond = np.append(key, key[l0])  # a match at level nl
+    none = np.full(nl, NONE, dtype=np.int64)
+    rows = [(0, c0, key), (0, c0, none), (0, C, key), (0, -1, key), (0, c0, stranger), (0, c0, beyond), (len(both), 0, none), (1, c1, ex2.match[1][c1])]
+    args = ([r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows])
+    at = attribute(model, both, *args, weights=weights)
+    al = align(model, both, *args, weights=weights)
+    assert at.status.tolist() == al.status.tolist() == [0, 0, 4, 4, 4, 4, 1, 0]
+    for r, (lig, _, _) in enumerate(rows):
+        assert at.levels[r].tolist() == al.levels[r].tolist() and len(at.node[r]) == len(al.node[r]), r
+        if at.status[r] != 1:
+            assert at.levels[r].tolist() == ex2.levels[lig].tolist() and len(at.node[r]) == both.header(lig)[0], r
+    assert len(at.levels[6]) == len(at.node[6]) == 0 and len(at.levels[7]) == len(al.levels[7]) == 20
 
 
 def test_limits_and_keys_that_are_no_leaf():

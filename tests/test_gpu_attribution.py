@@ -1,4 +1,4 @@
-"""`pmx_attribute` on the GPU (csrc/pmx_attribute.hip): entries, node shares and totals of listed leaves, checked against the reference's
+"""`pmx_attribute` on the GPU (csrc/pmx_rows.hip): entries, node shares and totals of listed leaves, checked against the reference's
 recorded numbers (tests/golden/attribution_<set>.npz), against `pmx_explain`'s maxima, against the NumPy restatement of
 tests/attribution_ref.py, and for what it does with keys that are no leaf of the tree."""
 
