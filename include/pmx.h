@@ -233,6 +233,32 @@ int pmx_pack_features_device(const pmx_feature_batch *batch, int device, void *s
                              uint64_t data_cap, uint64_t *data_bytes, int32_t *status_out);
 
 /*
+ * A sub-library on the device (pmx_select.hip): the records of the listed ligands, gathered into a new library without leaving HBM.
+ * The reference has no counterpart - its library is a list of files, and a list of hits is a Python slice of it (screening.py:66-75);
+ * here it is what turns "the best 10^5 hits", "the survivors of a filter" or "these hits, for the next campaign" back into something
+ * pmx_score / pmx_score_multi take, which score a contiguous range and nothing else.
+ *   indices_dev[n]        library indices, any order, repeats allowed; record i of the new library is a byte copy of record indices_dev[i]
+ *   offsets_out_dev       uint64 [n + 1], written in full by every call that gets as far as the device (offsets_out_dev[0] = 0)
+ *   data_out_dev          the records; data_cap its size in bytes. Must not overlap the source library's buffers (PMX_ERR_INVALID)
+ *   *data_bytes           (host) the exact size of the new library's data
+ * The conventions are pmx_pack_features_device's: the kernels run on `stream`, the host waits once - for one 24-byte read: the total and
+ * the count and first position of indices outside the library - and the record copy is enqueued behind it; offsets_out_dev and
+ * data_out_dev are complete in stream order. A call with data_out_dev = NULL only sizes (offsets and *data_bytes; data_cap must be 0);
+ * a call with data_out_dev does the same and then copies; with a data_cap that is too small it fails with PMX_ERR_INVALID, *data_bytes
+ * holds the need and nothing is copied. An index >= n_ligands fails the call with PMX_ERR_INVALID - the message gives how many there
+ * are and the first position that holds one - and no record is written (*data_bytes is 0). n = 0 succeeds: offsets_out_dev[0] = 0,
+ * *data_bytes = 0. n > 2^31 - 1 is PMX_ERR_INVALID (the scan's limit, as in pmx_pack_features_device). The source may be a library of
+ * any origin (uploaded, copied on the device, adopted); the new buffers are the caller's - pmx_library_upload with on_device = 2 makes
+ * them a library. Work buffers (8 bytes per index, the scan's scratch, three counters) are kept per device, grow only when a call needs
+ * more, are shared by calls on all streams (a call holds them until its host wait has ended) and are freed by pmx_release_workspaces.
+ */
+int pmx_library_select(const pmx_library *lib, const uint64_t *indices_dev, uint64_t n, uint64_t *offsets_out_dev /* [n + 1] */,
+                       uint8_t *data_out_dev, uint64_t data_cap, uint64_t *data_bytes, void *stream);
+/* The device buffers a library reads (owned, copied or adopted) - offsets uint64 [n_ligands + 1], data [n_bytes] - for reading it back.
+ * Valid until pmx_library_destroy (an adopted library's for as long as their owner keeps them); not to be written to. */
+int pmx_library_buffers(const pmx_library *lib, const uint64_t **offsets_dev, const uint8_t **data_dev);
+
+/*
  * The rule half of ligand perception in native code (pmx_perceive.cpp): get_pharmacophore_nodes of
  * src/pmnet/scoring/ligand_utils.py:25-184 for a batch of molecules. The reference asks OpenBabel per atom inside Python
  * predicates, one molecule at a time; here what only the chemistry toolkit can say comes in as flat per-atom answers, taken on the

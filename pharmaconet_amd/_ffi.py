@@ -112,6 +112,11 @@ SIGNATURES = {
     "pmx_library_upload": (ctypes.c_int, [ctypes.POINTER(LibraryView), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     "pmx_library_info_get": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LibraryInfo)]),
     "pmx_library_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "pmx_library_select": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p],
+    ),
+    "pmx_library_buffers": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]),
     "pmx_score": (
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_uint64, ctypes.c_uint64,

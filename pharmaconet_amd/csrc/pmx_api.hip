@@ -545,6 +545,15 @@ extern "C" int pmx_library_info_get(const pmx_library *lib, pmx_library_info *in
     return PMX_OK;
 }
 
+extern "C" int pmx_library_buffers(const pmx_library *lib, const uint64_t **offsets_dev, const uint8_t **data_dev) {
+    if (!lib || !offsets_dev || !data_dev) return fail(PMX_ERR_INVALID, "null argument");
+    *offsets_dev = lib->offsets;
+    *data_dev = lib->data;
+    return PMX_OK;
+}
+
+int pmx_library_device(const pmx_library *lib) { return lib->device; } // for pmx_select.hip (the struct stays in this translation unit)
+
 extern "C" int pmx_library_destroy(pmx_library *lib) {
     if (!lib) return PMX_OK;
     (void)hipSetDevice(lib->device);
@@ -1092,6 +1101,7 @@ extern "C" int pmx_score_f64(const pmx_model *model, const pmx_library *lib, con
 // is done screening does not.
 int pmx_topk_release(int device);
 int pmx_pack_release(int device);
+int pmx_select_release(int device);
 extern "C" int pmx_release_workspaces(int device) {
     HIPCHECK(hipSetDevice(device));
     HIPCHECK(hipDeviceSynchronize());
@@ -1113,8 +1123,9 @@ extern "C" int pmx_release_workspaces(int device) {
         w->free_buffers();
         w->released = true;
     }
-    const int rc = pmx_topk_release(device);
-    return rc ? rc : pmx_pack_release(device);
+    int rc = pmx_topk_release(device);
+    if (!rc) rc = pmx_pack_release(device);
+    return rc ? rc : pmx_select_release(device);
 }
 
 // error hook for pmx_topk.hip (keeps the thread-local message in one translation unit)

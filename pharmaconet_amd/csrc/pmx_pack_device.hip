@@ -29,6 +29,7 @@
 
 #include "pmx.h"
 #include "pmx_device.h"
+#include "pmx_scan.h"
 
 int pmx_topk_fail(int code, const char *msg); // error hook in pmx_api.hip
 
@@ -734,10 +735,6 @@ __global__ __launch_bounds__(64) void record_kernel(DevBatch b, const PackDesc *
     }
 }
 
-__global__ void close_offsets_kernel(const uint64_t *sizes, uint64_t *offsets, uint64_t n) { // offsets[n] = offsets[n - 1] + sizes[n - 1]
-    if (threadIdx.x == 0 && blockIdx.x == 0) offsets[n] = n ? offsets[n - 1] + sizes[n - 1] : 0;
-}
-
 // Work buffers (descriptors, sizes, scan scratch) kept from call to call, one set per device: a call touches its own device's
 // entry only, and holds that entry's lock while it runs.
 struct PackWork {
@@ -788,7 +785,7 @@ extern "C" int pmx_pack_features_device(const pmx_feature_batch *b, int device, 
     size_t scan_bytes = w.scan.bytes;
     e = hipcub::DeviceScan::ExclusiveSum(w.scan.ptr, scan_bytes, sizes, offsets_out_dev, (int)n, stream);
     if (e == hipSuccess) {
-        close_offsets_kernel<<<1, 64, 0, stream>>>(sizes, offsets_out_dev, n);
+        pmx::close_offsets_kernel<<<1, 64, 0, stream>>>(sizes, offsets_out_dev, n, nullptr); // (pmx_scan.h)
         e = hipGetLastError();
     }
     uint64_t total = 0;

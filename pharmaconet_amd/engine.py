@@ -16,7 +16,8 @@ from . import _ffi
 from .constants import weights_vector
 from .library import PackedLibrary, as_packed_library
 
-__all__ = ["Alignment", "Attribution", "DeviceLibrary", "Explanation", "ScreeningResult", "align", "attribute", "explain", "score_one", "screen", "topk", "device_model", "last_score_stats"]
+__all__ = ["Alignment", "Attribution", "DeviceLibrary", "Explanation", "PanelResult", "ScreeningResult", "align", "attribute", "explain", "score_one", "screen", "screen_multi", "topk",
+           "device_model", "last_score_stats"]
 
 
 def _torch():
@@ -149,6 +150,51 @@ class DeviceLibrary:
     def __len__(self) -> int:
         return self.num_ligands
 
+    def select(self, indices) -> "DeviceLibrary":
+        """The records of ligands `indices` (any order, repeats allowed) as a resident library of their own, gathered on the device
+        (`pmx_library_select`, csrc/pmx_select.hip): record i is a byte copy of record `indices[i]`, as `PackedLibrary.select` makes it on
+        the host. `indices`: a list, a NumPy array, or an int64 torch tensor on the device (which stays there). Runs on torch's current
+        stream; the new library's buffers are torch's, adopted, so `explain`, `attribute`, `align` and `download` work on it. An index outside
+        the library is a `PmxError` that says how many there are and where the first is (IndexError for a negative one in a host list)."""
+        torch = _torch()
+        lib = _ffi.load()
+        tdev = torch.device("cuda", self.device)
+        idx = _listed_indices(indices, tdev)
+        n = int(idx.numel())
+        with torch.cuda.device(tdev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(tdev).cuda_stream)
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=tdev)
+            nbytes = ctypes.c_uint64(0)
+            _ffi.check(lib.pmx_library_select(self.handle, idx.data_ptr() if n else None, n, offsets.data_ptr(), None, 0, ctypes.byref(nbytes), stream))
+            data = torch.empty(int(nbytes.value), dtype=torch.uint8, device=tdev)
+            if data.numel():
+                _ffi.check(lib.pmx_library_select(self.handle, idx.data_ptr(), n, offsets.data_ptr(), data.data_ptr(), data.numel(), ctypes.byref(nbytes), stream))
+            return DeviceLibrary.from_device_buffers(offsets, data, tdev, adopt=True)  # (waits for the stream: `idx` may go)
+
+    def buffers(self):
+        """(offsets int64 [N + 1], data uint8 [bytes]): the device buffers this library reads, as torch tensors - the adopted ones, or views of
+        the library's own (`pmx_library_buffers`), valid until `close`. Not to be written to."""
+        src = getattr(self, "_adopted", None)
+        if src is not None:
+            return src
+        torch = _torch()
+        po, pd = ctypes.c_void_p(), ctypes.c_void_p()
+        _ffi.check(_ffi.load().pmx_library_buffers(self.handle, ctypes.byref(po), ctypes.byref(pd)))
+        tdev = torch.device("cuda", self.device)
+
+        class _View:  # (torch reads foreign device memory through the CUDA array interface)
+            def __init__(self, ptr, count, typestr):
+                self.__cuda_array_interface__ = dict(shape=(count,), typestr=typestr, data=(int(ptr), False), version=2, strides=None)
+
+        offsets = torch.as_tensor(_View(po.value, self.num_ligands + 1, "<i8"), device=tdev)
+        data = torch.as_tensor(_View(pd.value, self.num_bytes, "|u1"), device=tdev) if self.num_bytes else torch.empty(0, dtype=torch.uint8, device=tdev)
+        return offsets, data
+
+    def download(self) -> PackedLibrary:
+        """The library as a host `PackedLibrary`, whatever it was made from (waits for torch's current stream)."""
+        offsets, data = self.buffers()
+        return PackedLibrary(offsets.cpu().numpy().view(np.uint64).copy(), data[: self.num_bytes].cpu().numpy().copy())
+
     def close(self) -> None:
         if getattr(self, "handle", None):
             _ffi.load().pmx_library_destroy(self.handle)
@@ -160,6 +206,19 @@ class DeviceLibrary:
             self.close()
         except Exception:
             pass
+
+
+def _listed_indices(indices, tdev):
+    """A list of ligand indices as a flat int64 tensor on `tdev`: a list or a NumPy array is uploaded, a device tensor stays where it is."""
+    torch = _torch()
+    if isinstance(indices, torch.Tensor):
+        if indices.dtype != torch.int64:
+            raise TypeError("ligand indices as a tensor: int64")
+        return indices.to(tdev).reshape(-1).contiguous()
+    host = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+    if (host < 0).any():
+        raise IndexError("negative ligand index")
+    return torch.from_numpy(host).to(tdev)
 
 
 @contextlib.contextmanager
@@ -245,6 +304,7 @@ class ScreeningResult:
     library: "object | None" = None
     weights: "dict | None" = None
     index_base: int = 0  # added to library indices in topk_indices
+    indices: "object | None" = None  # a listed screen (`screen(..., indices=)`): torch.int64 [count] on the device, the library ligand behind each score
 
     def scores_numpy(self) -> np.ndarray:
         return self.scores.cpu().numpy()
@@ -279,7 +339,15 @@ class ScreeningResult:
             sc = self.scores.cpu().numpy().astype(np.float64)
             key = np.where(self.status.cpu().numpy() != 0, -np.inf, np.nan_to_num(sc, nan=-np.inf))
             idx = np.lexsort((np.arange(len(sc)), -key))[:k] + self.first
+            if self.indices is not None:  # (a listed screen: positions of the list -> library indices)
+                idx = self.indices.cpu().numpy()[idx]
         return np.asarray([i for i in idx if i >= 0], dtype=np.uint64)
+
+    def panel(self, k: int, models, library=None) -> "PanelResult":
+        """This screen's k best ligands (best first) against other pockets: a `PanelResult` whose column 0 is this screen's own model and whose
+        further columns are `models`, under this screen's weights and in its precision - `DeviceLibrary.select` of the hits, then `screen_multi`."""
+        model, library, weights = self._scored(None, library, None)
+        return screen_multi([model, *models], library, weights=weights, indices=self._best(k).astype(np.int64), float64=str(self.scores.dtype).endswith("float64"))
 
     def modes(self, k: int, modes: int = 4, model=None, library=None, weights: dict[str, float] | None = None, require=None, exclude=None) -> "ModeSet":
         """`explain_modes` of this screen's k best ligands (the rows of `explain(k)`): the `modes` best binding modes per conformer."""
@@ -325,22 +393,25 @@ def screen(
     count: int | None = None,
     index_base: int = 0,
     float64: bool = False,
+    indices=None,
 ) -> ScreeningResult:
     """Score ligands `[first, first + count)` of `library` against `model` on the GPU.
 
     `library` is a `DeviceLibrary` (already in HBM) or anything `as_packed_library` accepts.
     `index_base` is added to positions when reporting top-k indices (the shard's global offset).
+    `indices` (instead of `first` / `count`): a listed screen - the ligands `indices` (a list, a NumPy array or an int64 device tensor; any
+    order, repeats allowed), gathered on the device (`DeviceLibrary.select`) and scored as a library of their own. Scores and status
+    come back in list order, `topk_indices` are indices of `library` (ties in list order), and the result's `explain` / `modes` explain
+    against `library`.
     `float64`: scores as the float64 the reference returns (`pmx_score_f64`; `graph_match.py:109`) instead of its float32
     rounding; the device top-k ranks float32 values, so it is not offered together with `topk`."""
     torch = _torch()
     lib = _ffi.load()
     if float64 and topk is not None:
         raise ValueError("float64 scores are ranked by the caller (the device top-k ranks float32 values)")
-    with _resident(library, device) as dlib:
+    with _resident(library, device) as whole, _listed(whole, indices, first, count) as (dlib, listed, first, count):
         dev = dlib.device
         mh = device_model(model, dev)
-        if count is None:
-            count = len(dlib) - first
         tdev = torch.device("cuda", dev)
         scores = torch.empty(count, dtype=torch.float64 if float64 else torch.float32, device=tdev)
         status = torch.empty(count, dtype=torch.int32, device=tdev)
@@ -352,10 +423,87 @@ def screen(
             )
         )
         result = ScreeningResult(scores=scores, status=status, first=first, model=model, library=library if isinstance(library, (DeviceLibrary, PackedLibrary)) else None,
-                                  weights=weights, index_base=index_base)
-        if topk is not None:
+                                  weights=weights, index_base=index_base, indices=listed)
+        if topk is not None and listed is not None:  # (pmx_topk breaks ties by position: list order)
+            result.topk_scores, result.topk_indices = globals()["topk"](scores, int(topk), indices=listed + index_base if index_base else listed)
+        elif topk is not None:
             result.topk_scores, result.topk_indices = globals()["topk"](scores, int(topk), base_index=index_base + first)
     return result
+
+
+@contextlib.contextmanager
+def _listed(dlib: "DeviceLibrary", indices, first: int, count: int | None):
+    """What a scoring call scores: (library, None, first, count) for the range `[first, first + count)` of `dlib`; for a list of ligands
+    (`indices`) the selection as a library of its own with the list on the device and the range that covers it, closed behind the block. The
+    selection's buffers are torch's, allocated on the stream the scoring call is enqueued on, so they may be given back while it still runs."""
+    if indices is None:
+        yield dlib, None, first, (len(dlib) - first if count is None else count)
+        return
+    if first != 0 or count is not None:
+        raise ValueError("`indices` and `first` / `count` are mutually exclusive")
+    torch = _torch()
+    listed = _listed_indices(indices, torch.device("cuda", dlib.device))
+    sub = dlib.select(listed)
+    try:
+        yield sub, listed, 0, len(sub)
+    finally:
+        sub.close()
+
+
+@dataclass
+class PanelResult:
+    """What `screen_multi` returns: one library (or one list of its ligands) against several pockets.
+
+    scores   torch.float32 (float64 with `float64=True`) [n_models, count] on the device: row m is what `screen(models[m], ...)` gives
+    status   torch.int32 [count]: PMX_LIGAND_*, the same for every pocket
+    indices  torch.int64 [count] on the device for a listed call (the library ligand behind each column), else None: column j is ligand first + j"""
+
+    scores: "object"
+    status: "object"
+    first: int = 0
+    indices: "object | None" = None
+    models: "list | None" = None
+    library: "object | None" = None
+    weights: "dict | None" = None
+
+    def ligands(self) -> np.ndarray:
+        """int64 [count]: the library ligand behind each column."""
+        return self.indices.cpu().numpy() if self.indices is not None else np.arange(int(self.status.numel()), dtype=np.int64) + self.first
+
+    def best(self, m: int, k: int) -> tuple[np.ndarray, np.ndarray]:
+        """(library indices, scores) of pocket m's k best ligands, best first; ties in column order, ligands with a non-zero status left out."""
+        sc, st = self.scores[m].cpu().numpy(), self.status.cpu().numpy()
+        key = np.where(st != 0, -np.inf, np.nan_to_num(sc.astype(np.float64), nan=-np.inf))
+        cols = [int(j) for j in np.lexsort((np.arange(len(sc)), -key))[:k] if st[j] == 0]
+        return self.ligands()[cols], sc[cols]
+
+    def margin(self, target: int):
+        """[count] on the device: the target pocket's score minus the best score of the other pockets - how selective each ligand is for it."""
+        n = int(self.scores.shape[0])
+        if n < 2 or not 0 <= target < n:
+            raise ValueError(f"margin of pocket {target} among {n}: needs a pocket of the panel and at least one other")
+        others = [m for m in range(n) if m != target]
+        return self.scores[target] - self.scores[others].max(dim=0).values
+
+
+def screen_multi(models, library, weights: dict[str, float] | None = None, first: int = 0, count: int | None = None, indices=None, float64: bool = False,
+                 device=None) -> PanelResult:
+    """Score ligands `[first, first + count)` of `library`, or the ligands `indices`, against every model of `models` in one call
+    (`pmx_score_multi` / `pmx_score_multi_f64`: one pocket after the other on torch's current stream, the library read from HBM each time).
+    `library`, `indices` and `float64` as `screen` takes them; each row of the result's scores is bit for bit that pocket's `screen`."""
+    torch = _torch()
+    lib = _ffi.load()
+    models = list(models)
+    with _resident(library, device) as whole, _listed(whole, indices, first, count) as (dlib, listed, first, count):
+        tdev = torch.device("cuda", dlib.device)
+        handles = (ctypes.c_void_p * max(len(models), 1))(*(device_model(m, dlib.device).handle.value for m in models))
+        scores = torch.empty((len(models), count), dtype=torch.float64 if float64 else torch.float32, device=tdev)
+        status = torch.empty(count, dtype=torch.int32, device=tdev)
+        stream = torch.cuda.current_stream(tdev).cuda_stream
+        _ffi.check((lib.pmx_score_multi_f64 if float64 else lib.pmx_score_multi)(handles, len(models), dlib.handle, _weights_array(weights), first, count,
+                                                                                   scores.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream)))
+    return PanelResult(scores=scores, status=status, first=first, indices=listed, models=models,
+                       library=library if isinstance(library, (DeviceLibrary, PackedLibrary)) else None, weights=weights)
 
 
 def score_one(model, ligand, weights: dict[str, float] | None = None, device=None) -> float:
@@ -479,17 +627,14 @@ class Explanation:
 
 def _record_counts(library: "DeviceLibrary", idx: np.ndarray, field: int) -> np.ndarray:
     """Header field `field` (0: nodes, 1: conformers) of library ligands `idx` (0 outside the library): kept per ligand when the library was
-    uploaded from the host, read from the adopted device records otherwise."""
+    uploaded from the host, read from the library's device records (`DeviceLibrary.buffers`) otherwise."""
     ok = idx < len(library)
     j = np.where(ok, idx, 0)
     kept = getattr(library, "_n_conf" if field == 1 else "_n_nodes", None)
     if kept is not None:
         return np.where(ok, kept[j].astype(np.int64) if len(kept) else 0, 0)
-    src = getattr(library, "_adopted", None)
-    if src is None:
-        raise ValueError("this DeviceLibrary does not know its records' sizes: make it from a PackedLibrary or adopt the device buffers")
     torch = _torch()
-    offsets, data = src
+    offsets, data = library.buffers()
     starts = offsets.view(torch.int64)[torch.from_numpy(j).to(offsets.device)] + 2 * field
     v = data[starts].to(torch.int64) | (data[starts + 1].to(torch.int64) << 8)
     return np.where(ok, v.cpu().numpy(), 0)

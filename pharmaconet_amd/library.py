@@ -435,6 +435,24 @@ class PackedLibrary:
         lo, hi = int(self.offsets[first]), int(self.offsets[first + count])
         return PackedLibrary(self.offsets[first : first + count + 1] - np.uint64(lo), self.data[lo:hi])
 
+    def select(self, indices) -> "PackedLibrary":
+        """The records of ligands `indices` (any order, repeats allowed) as a library of their own: record i is a byte copy of record
+        `indices[i]`. The host counterpart of `engine.DeviceLibrary.select` (`pmx_library_select`). IndexError for an index outside the library."""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= len(self)):
+            bad = np.flatnonzero((idx < 0) | (idx >= len(self)))
+            raise IndexError(f"{len(bad)} of {len(idx)} indices are outside the library's {len(self)} ligands, the first at position {int(bad[0])}")
+        data = np.ascontiguousarray(self.data[: int(self.offsets[-1])])
+        if np.any(self.offsets % RECORD_ALIGN):
+            raise ValueError("records must start on 16-byte boundaries")
+        starts = self.offsets[idx].astype(np.int64) // RECORD_ALIGN  # in 16-byte units, like the device copy
+        sizes = self.offsets[idx + 1].astype(np.int64) // RECORD_ALIGN - starts
+        ends = np.cumsum(sizes)
+        offsets = np.zeros(len(idx) + 1, dtype=np.uint64)
+        offsets[1:] = ends * RECORD_ALIGN
+        src = np.repeat(starts - (ends - sizes), sizes) + np.arange(int(ends[-1]) if len(idx) else 0, dtype=np.int64)
+        return PackedLibrary(offsets, data.view(f"V{RECORD_ALIGN}")[src].view(np.uint8))
+
     def unpack(self, i: int) -> dict:
         """Decode record i (for tests and debugging)."""
         n, c, k = self.header(i)

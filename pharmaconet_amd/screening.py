@@ -5,6 +5,7 @@ type weights. `--library_dir` may be a directory of `.sdf` / `.mol2` files (perc
 processes; needs OpenBabel like the reference) or a packed library file (`.pmxlib`, see
 `pharmaconet_amd.library`) with an optional `<library>.names` text file giving one path per ligand.
 Output: `path,score` CSV, best first, ties in library order (`screening.py:70-75`). Scoring runs on the GPU.
+`--panel MODEL ... --panel_out PATH` scores the best hits against other pockets; `--save_top K PATH` keeps them as a packed library.
 """
 
 from __future__ import annotations
@@ -39,6 +40,10 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--exclude", type=str, default=None, metavar="LIST", help="constrained matching: comma-separated model cluster indices that a hit's match must not hold")
         cfg.add_argument("--constrained_out", type=str, default=None, metavar="PATH", help="CSV of the best hits by constrained score (needed with --require / --exclude)")
         cfg.add_argument("--constrained_k", type=int, default=100, metavar="K", help="hits in --constrained_out")
+        cfg.add_argument("--panel", action="append", default=[], metavar="MODEL", help="selectivity panel: another pharmacophore model (.pm | .json) the best hits are also scored against (repeatable)")
+        cfg.add_argument("--panel_k", type=int, default=100, metavar="K", help="hits in --panel_out")
+        cfg.add_argument("--panel_out", type=str, default=None, metavar="PATH", help="CSV of the K best hits with their score against every --panel model and the margin over the best of them (needed with --panel)")
+        cfg.add_argument("--save_top", nargs=2, default=None, metavar=("K", "PATH"), help="keep the K best hits as a packed library PATH (.pmxlib, with PATH.names) that -d takes")
         par = self.add_argument_group("parameter")
         par.add_argument("--hydrophobic", type=float, default=1.0, help="weight for hydrophobic carbon")
         par.add_argument("--aromatic", type=float, default=4.0, help="weight for aromatic ring")
@@ -134,6 +139,19 @@ def main(argv=None) -> None:
         parser.error("--require / --exclude need --constrained_out PATH")
     if args.constrained_out and args.constrained_k <= 0:
         parser.error("--constrained_k must be positive")
+    if args.panel and not args.panel_out:
+        parser.error("--panel needs --panel_out PATH")
+    if args.panel_out and not args.panel:
+        parser.error("--panel_out needs --panel MODEL")
+    if args.panel_out and args.panel_k <= 0:
+        parser.error("--panel_k must be positive")
+    if args.save_top:
+        try:
+            save_k = int(args.save_top[0])
+        except ValueError:
+            save_k = 0
+        if save_k <= 0:
+            parser.error("--save_top takes a positive K and a path")
     try:
         require = [[int(v) for v in g.split(",")] for g in args.require]
         exclude = [int(v) for v in args.exclude.split(",")] if args.exclude else []
@@ -165,6 +183,45 @@ def main(argv=None) -> None:
             write_modes_csv(out, names, scores, status, model, lib, weight, args.explain, args.modes)
     if args.constrained_out:
         write_constrained_csv(Path(args.constrained_out), names, model, lib, weight, args.constrained_k, require, exclude)
+    if args.panel_out or args.save_top:
+        from .engine import DeviceLibrary
+
+        dlib = lib if isinstance(lib, DeviceLibrary) else DeviceLibrary(lib)  # (resident once for both)
+        if args.panel_out:
+            write_panel_csv(Path(args.panel_out), names, scores, status, model, args.panel, dlib, weight, args.panel_k)
+        if args.save_top:
+            save_top(Path(args.save_top[1]), names, scores, status, dlib, save_k)
+
+
+def _best_hits(scores: np.ndarray, status: np.ndarray, k: int) -> list[int]:
+    """The k best scored ligands in the order of the main CSV."""
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    return [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+
+
+def write_panel_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, panel: list[str], lib, weights, k: int) -> None:
+    """The k best hits of a screen, in the order of the main CSV, against a panel of other pockets (`engine.screen_multi` on those k ligands
+    only, gathered on the device): the hit's score, its float64 score against every panel model (a column named by the model file's stem) and
+    the margin - the score minus the best panel score: what the hit has over its best off-target."""
+    from .engine import screen_multi
+
+    order = _best_hits(scores, status, k)
+    res = screen_multi([model] + [PharmacophoreModel.load(m) for m in panel], lib, weights=weights, indices=order, float64=True)
+    sc, margin = res.scores.cpu().numpy(), res.margin(0).cpu().numpy()
+    with open(out, "w") as w:
+        w.write("rank,path,score," + ",".join(Path(m).stem for m in panel) + ",margin\n")
+        for r, i in enumerate(order):
+            w.write(f"{r + 1},{names[i]},{float(sc[0, r])}," + ",".join(str(float(v)) for v in sc[1:, r]) + f",{float(margin[r])}\n")
+
+
+def save_top(path: Path, names: list[str], scores: np.ndarray, status: np.ndarray, lib, k: int) -> None:
+    """The k best hits of a screen, in the order of the main CSV, as a packed library file of their own (`DeviceLibrary.select`, read back with
+    `download`) and its `.names` file: what `--library_dir` takes for the next campaign."""
+    order = _best_hits(scores, status, k)
+    sub = lib.select(order)
+    sub.download().save(path)
+    sub.close()
+    Path(str(path) + ".names").write_text("".join(f"{names[i]}\n" for i in order))
 
 
 def write_constrained_csv(out: Path, names: list[str], model, lib, weights, k: int, require, exclude) -> None:
@@ -225,10 +282,10 @@ def write_modes_csv(out: Path, names: list[str], scores: np.ndarray, status: np.
 
 
 def _record_of(lib, i: int) -> dict:
-    """Record i of a packed library, or of a device-resident one made from features (its buffers are read back for that record)."""
+    """Record i of a packed library, or of a device-resident one of any origin (its buffers are read back for that record)."""
     if isinstance(lib, PackedLibrary):
         return lib.unpack(i)
-    offsets, data = lib._adopted
+    offsets, data = lib.buffers()
     lo, hi = (int(x) for x in offsets[i : i + 2].cpu())
     return PackedLibrary.from_records([data[lo:hi].cpu().numpy().tobytes()]).unpack(0)
 
