@@ -491,6 +491,67 @@ int pmx_align(const pmx_model *model, const pmx_library *lib, const float weight
               double *node_dev /* [n][PMX_MAX_LIGAND_NODES] */, int32_t *count_dev /* [n][2] */,
               uint8_t *levels_dev /* [n][PMX_MAX_LEVELS] */, int32_t *status_dev, void *stream);
 
+/*
+ * Which model nodes - the hotspots of the pocket - carry a leaf's total: rows (ligand, conformer c, key) exactly as pmx_attribute takes them,
+ * and the same leaf. pmx_attribute splits every term(u, v) between the two ligand nodes; the same term is a sum over model node pairs
+ * (match_utils.py:29-69), and this call splits it among those. All values are for the row's conformer c.
+ *   node pair      (u, v) that enters an entry of pmx_attribute: itertools.combinations of one matched level's match list, or
+ *                  itertools.product of two matched levels' lists; u is the earlier node in record order.
+ *   inner term     (m, m') for m in u's node subset (the model nodes of u's level's match whose type is in u's type mask) and m' in v's:
+ *                  the float32 addend g = (w_m w_m' / std) expf(-0.5 z^2), z = (d(u, v) - mean) / std of the model edge (m, m'), formed
+ *                  as match_utils.py:50-69 forms it; it passes when |z| < 2 (:56-60).
+ *   G(u, v)        the float64 sum of the pair's g in the order of itertools.product(u's subset, v's subset), both ascending.
+ *   term(u, v), scale[e]   pmx_attribute's: the float32 term, and entry / (float64 sum of the entry's terms) of the pair's entry e.
+ *   hotspot[m]     float64: the sum of 1/2 (g / G(u, v)) term(u, v) scale[e] over every inner term of every node pair in which m is one
+ *                  of the two sides; a term (m, m) gives both halves to m; a pair with G = 0 gives nothing. Summed per node pair, pairs
+ *                  in ascending (u, v), per pair the side of u first, per side in ascending order of the other model node. 0 for
+ *                  m >= n_nodes and for nodes in no term, so sum_m hotspot[m] = sum of the entries = total to float64 rounding.
+ *   terms[m], pass[m]   the inner terms, and the passing ones, counted once for each of their sides that is m.
+ *   fingerprint    bit (m % 64) of word m / 64 is set iff terms[m] > 0 and 2 pass[m] >= terms[m]: the majority rule of
+ *                  match_utils.py:56-61 read per hotspot - the ligand puts most of what it puts near m at a distance the model expects.
+ * Outputs, per row:
+ *   total_dev        double [n]                            pmx_attribute's total, bit for bit; NaN when the row is not valid
+ *   hotspot_dev      double [n][PMX_MAX_MODEL_NODES]       NaN throughout when the row is not valid
+ *   terms_dev        uint32 [n][PMX_MAX_MODEL_NODES]       0 throughout when the row is not valid
+ *   pass_dev         uint32 [n][PMX_MAX_MODEL_NODES]       0 throughout when the row is not valid
+ *   fingerprint_dev  uint64 [n][PMX_FINGERPRINT_WORDS]     0 when the row is not valid
+ *   levels_dev, status_dev   as pmx_attribute writes them, with its validity rule: a key that is no leaf for c gives PMX_LIGAND_KEY_INVALID
+ * A key of all 0xFF, or a ligand without levels, is valid with total 0 and everything else 0. n <= PMX_EXPLAIN_MAX; n = 0 succeeds. The call
+ * is stream-ordered like pmx_attribute (enqueued, no synchronisation). One wavefront per row (pmx_rows.hip): pmx_attribute's steps, then a
+ * lane per model node; fixed-order sums, no floating-point atomic: the same call gives the same bits on every run.
+ */
+#define PMX_FINGERPRINT_WORDS (PMX_MAX_MODEL_NODES / 64) /* 4 */
+int pmx_hotspots(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev,
+                 const int32_t *conformer_dev, const uint8_t *key_dev /* [n][PMX_MAX_LEVELS] */, uint32_t n, double *total_dev,
+                 double *hotspot_dev /* [n][PMX_MAX_MODEL_NODES] */, uint32_t *terms_dev /* [n][PMX_MAX_MODEL_NODES] */,
+                 uint32_t *pass_dev /* [n][PMX_MAX_MODEL_NODES] */, uint64_t *fingerprint_dev /* [n][PMX_FINGERPRINT_WORDS] */,
+                 uint8_t *levels_dev /* [n][PMX_MAX_LEVELS] */, int32_t *status_dev, void *stream);
+
+/*
+ * Fingerprints compared: a_dev [na][PMX_FINGERPRINT_WORDS] against b_dev [nb][PMX_FINGERPRINT_WORDS] (rows of pmx_hotspots'
+ * fingerprint_dev, or any bit sets of that size), out_dev [na][nb] float.
+ *   sim(x, y) = (float)popcount(x & y) / (float)popcount(x | y), one float32 division; 1.0f when both are empty.
+ * na, nb <= PMX_EXPLAIN_MAX (otherwise PMX_ERR_INVALID); na = 0 or nb = 0 succeeds and writes nothing; a_dev == b_dev is allowed. The
+ * pointers are memory of `device`. Stream-ordered, no synchronisation.
+ */
+int pmx_fingerprint_tanimoto(const uint64_t *a_dev, uint32_t na, const uint64_t *b_dev, uint32_t nb, float *out_dev /* [na][nb] */, int device, void *stream);
+
+/*
+ * Sphere exclusion in row order (the rows are the caller's ranking, best first): row i joins the FIRST earlier leader l with
+ * sim(fp[i], fp[l]) >= threshold, compared in float32 - leader_of[i] = l; otherwise it becomes a leader, leader_of[i] = i. Once max_leaders
+ * leaders exist a row that joins none gets UINT32_MAX. Row 0 is always a leader when n > 0. Similarity is not transitive and the rule does
+ * not pretend it is: a row similar to a member of a leader's cluster but not to the leader does not join it.
+ *   leader_of_dev  uint32 [n]            leaders_dev  uint32 [max_leaders]: the leaders' rows, ascending; the first *n_leaders_dev are written
+ *   n_leaders_dev  uint32 [1]
+ * PMX_ERR_INVALID: threshold outside (0, 1]; max_leaders 0 or above PMX_MAX_LEADERS; n > PMX_EXPLAIN_MAX. n = 0 succeeds with
+ * *n_leaders_dev = 0. The result is defined by the rule alone. One work-group with the leaders' fingerprints in LDS
+ * (pmx_fingerprint.hip). Stream-ordered, no synchronisation.
+ */
+#define PMX_MAX_LEADERS 2048
+int pmx_fingerprint_leaders(const uint64_t *fp_dev /* [n][PMX_FINGERPRINT_WORDS] */, uint32_t n, float threshold, uint32_t max_leaders,
+                            uint32_t *leader_of_dev /* [n] */, uint32_t *leaders_dev /* [max_leaders] */, uint32_t *n_leaders_dev /* [1] */,
+                            int device, void *stream);
+
 /* Frees the scoring workspaces libpmx keeps between calls on `device` (synchronises the device first). */
 int pmx_release_workspaces(int device);
 

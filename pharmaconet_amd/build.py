@@ -16,7 +16,7 @@ REPO = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libpmx.so"
 PACK_LIB = PKG / "libpmx_pack.so"  # the packer alone, host-only (no HIP / RCCL runtime)
-SOURCES = ("pmx_api.hip", "pmx_screen_debug.hip", "pmx_explain.hip", "pmx_rows.hip", "pmx_topk.hip", "pmx_density.hip", "pmx_pack_device.hip", "pmx_select.hip", "pmx_pack.cpp", "pmx_sdf.cpp", "pmx_perceive.cpp")
+SOURCES = ("pmx_api.hip", "pmx_screen_debug.hip", "pmx_explain.hip", "pmx_rows.hip", "pmx_fingerprint.hip", "pmx_topk.hip", "pmx_density.hip", "pmx_pack_device.hip", "pmx_select.hip", "pmx_pack.cpp", "pmx_sdf.cpp", "pmx_perceive.cpp")
 # every file under csrc/ that a unit of SOURCES #includes, directly or not (tests/test_cabi.py checks the closure): with SOURCES, what the
 # digest of the stamp covers
 DEPS = ("pmx_screen.hip", "pmx_screen_walk.h", "pmx_screen_tables.h", "pmx_screen_layout.h", "pmx_device.h", "pmx_debug.h", "pmx_explain.h", "pmx_rows.h", "pmx_scan.h")

@@ -1251,7 +1251,7 @@ extern "C" int pmx_explain_modes(const pmx_model *model, const pmx_library *lib,
 }
 
 // ------------------------------------------------------------------------------------ the row kernels (pmx_rows.hip)
-// pmx_attribute and pmx_align: one kernel over the call's rows; no tables, no slices, no arena. Of the workspace of (device, stream) it
+// pmx_attribute, pmx_align and pmx_hotspots: one kernel over the call's rows; no tables, no slices, no arena. Of the workspace of (device, stream) it
 // takes the CU count and four bytes for its row cursor, cleared in stream order in front of the launch. `what`: the call's name in a
 // message; null_out: one of the caller's own device pointers is null; launch(blocks, p, cursor) starts the caller's kernel.
 template <class Launch>
@@ -1291,6 +1291,17 @@ extern "C" int pmx_attribute(const pmx_model *model, const pmx_library *lib, con
     return row_call(model, lib, weights, n, "attribute", null_out, pmx_rows::kAttribute, stream, [&](unsigned blocks, const ScreenParams &p, uint32_t *cursor) {
         const pmx_rows::AttributeArgs a{{ligands_dev, conformer_dev, key_dev, n, levels_dev, status_dev, cursor}, total_dev, node_dev, entry_dev, fails_dev};
         return pmx_rows::launch(pmx_rows::kAttribute, blocks, stream, &p, sizeof p, &a);
+    });
+}
+
+extern "C" int pmx_hotspots(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const uint64_t *ligands_dev,
+                            const int32_t *conformer_dev, const uint8_t *key_dev, uint32_t n, double *total_dev, double *hotspot_dev, uint32_t *terms_dev,
+                            uint32_t *pass_dev, uint64_t *fingerprint_dev, uint8_t *levels_dev, int32_t *status_dev, void *stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const bool null_out = !ligands_dev || !conformer_dev || !key_dev || !total_dev || !hotspot_dev || !terms_dev || !pass_dev || !fingerprint_dev || !levels_dev || !status_dev;
+    return row_call(model, lib, weights, n, "hotspots", null_out, pmx_rows::kHotspots, stream, [&](unsigned blocks, const ScreenParams &p, uint32_t *cursor) {
+        const pmx_rows::HotspotArgs a{{ligands_dev, conformer_dev, key_dev, n, levels_dev, status_dev, cursor}, total_dev, hotspot_dev, terms_dev, pass_dev, fingerprint_dev};
+        return pmx_rows::launch(pmx_rows::kHotspots, blocks, stream, &p, sizeof p, &a);
     });
 }
 

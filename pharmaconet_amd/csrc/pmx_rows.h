@@ -1,5 +1,5 @@
-// pmx_rows.h - launcher of the row kernels (pmx_rows.hip): attribution and rigid fit of listed (ligand, conformer, key) rows, called by
-// pmx_attribute() and pmx_align() in pmx_api.hip.
+// pmx_rows.h - launcher of the row kernels (pmx_rows.hip): attribution, rigid fit and hotspot shares of listed (ligand, conformer, key) rows, called by
+// pmx_attribute(), pmx_align() and pmx_hotspots() in pmx_api.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -34,11 +34,20 @@ struct AlignArgs {
     double *node;         // [n][PMX_MAX_LIGAND_NODES]
     int32_t *count;       // [n][2]
 };
-enum Kind { kAttribute, kAlign };
+// Where the answers of pmx_hotspots go (include/pmx.h).
+struct HotspotArgs {
+    Rows rows;
+    double *total;         // [n]
+    double *hotspot;       // [n][PMX_MAX_MODEL_NODES]
+    uint32_t *terms;       // [n][PMX_MAX_MODEL_NODES]
+    uint32_t *pass;        // [n][PMX_MAX_MODEL_NODES]
+    uint64_t *fingerprint; // [n][PMX_FINGERPRINT_WORDS]
+};
+enum Kind { kAttribute, kAlign, kHotspots };
 // Static LDS of one wavefront of the kernel: how many fit a compute unit.
 size_t lds_bytes(Kind kind);
 // `params`: the caller's pmx::ScreenParams with the model, the library, the node subsets and the weights filled in (same source and
-// layout; `bytes` is checked against this side's sizeof). `args`: the AttributeArgs or AlignArgs of `kind`. Returns false when the size
+// layout; `bytes` is checked against this side's sizeof). `args`: the AttributeArgs, AlignArgs or HotspotArgs of `kind`. Returns false when the size
 // is not the one this side knows.
 bool launch(Kind kind, unsigned blocks, hipStream_t stream, const void *params, size_t bytes, const void *args);
 } // namespace pmx_rows

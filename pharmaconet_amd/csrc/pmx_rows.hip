@@ -1,5 +1,5 @@
-// pmx_rows.hip - the kernels that answer a question about listed (ligand, conformer, key) rows, on gfx950: pmx_attribute and pmx_align
-// (include/pmx.h). One wavefront handles one row, and both kernels open a row the same way (open_row): the ligand's record, its type masks,
+// pmx_rows.hip - the kernels that answer a question about listed (ligand, conformer, key) rows, on gfx950: pmx_attribute, pmx_hotspots and
+// pmx_align (include/pmx.h). One wavefront handles one row, and all kernels open a row the same way (open_row): the ligand's record, its type masks,
 // its tree levels with the candidates of each (the level rule of pmx_screen_tables.h), and the key checked against them.
 //
 // pmx_screen_tables.h is compiled here once more, as namespace pmx_r, for parse_record, the level rule, the wavefront helpers, center_size
@@ -10,7 +10,7 @@
 // (match_utils.py:9-122 behind graph_match.py:139-172, :263-268), the number of failing node pairs per pair entry, the leaf's total in the
 // product walker's order, and the share of every ligand node. Every node-pair term is evaluated one by one in the reference's float32
 // operations (exact_value), so the answer does not depend on PMX_TAILS_RATIO or on the rough-cell flags of the tabulated functions. Five
-// steps after open_row, which hand over through the wavefront's LDS:
+// steps after open_row, which hand over through the wavefront's LDS (all but `nodes` are leaf_steps, which hotspots_row runs too):
 //   centres   lane c = conformer c: centre and size of every matched level's cluster, then the cluster-distance prefilter of every
 //             pair of matched levels (it fails only when it fails for every conformer: one ballot)
 //   terms     lane u = node u: term(u, v) and fail(u, v) for every later listed node v, into term[u][v] and one fail mask per node
@@ -36,7 +36,10 @@
 // Several targets per node: sum_m w |p - y_m|^2 = W_u |p - ybar_u|^2 + sum_m w |y_m - ybar_u|^2 for any point p, so the fit sees node u
 // as one point ybar_u of weight W_u and the second sum is a constant of the row (sse - rmsd_nodes^2 W).
 //
-// In neither kernel does a lane add to another lane's sum, and there is no floating-point atomic: the same call gives the same bits.
+// hotspots_row - which model nodes carry the same total: attribute_row's steps up to the entries and the total (leaf_steps, shared), then
+// the model-side step described where it stands.
+//
+// In no kernel does a lane add to another lane's sum, and there is no floating-point atomic: the same call gives the same bits.
 #include <hip/hip_runtime.h>
 #include <cstring>
 
@@ -188,20 +191,73 @@ constexpr uint32_t kAttributeLds = kAtNlv + kN;
 static_assert(kAtScale % 8 == 0 && kAtFailm % 8 == 0 && kAtRow % 8 == 0 && kAtEnt % 4 == 0 && kAtPf % 4 == 0 && kAtFc % 2 == 0 && kAtSid % 2 == 0, "LDS alignment");
 static_assert(kAttributeLds <= 64 * 1024, "LDS of a work-group");
 
-// Row li of the call.
-__device__ void attribute_row(const ScreenParams &p, const pmx_rows::AttributeArgs &a, unsigned char *lds, uint32_t li) {
+// The wavefront's LDS as the steps below see it.
+struct LeafLds {
+    float4 *ctr;
+    float *term;
+    float4 *pos;
+    double *scale;
+    unsigned long long *failm;
+    RowLds &L;
+    float *ent;
+    uint32_t *pf;
+    uint16_t *fc, *sid;
+    uint8_t *nlv;
+    __device__ explicit LeafLds(unsigned char *lds)
+        : ctr(reinterpret_cast<float4 *>(lds + kAtR)), term(reinterpret_cast<float *>(lds + kAtR)), pos(reinterpret_cast<float4 *>(lds + kAtPos)),
+          scale(reinterpret_cast<double *>(lds + kAtScale)), failm(reinterpret_cast<unsigned long long *>(lds + kAtFailm)),
+          L(*reinterpret_cast<RowLds *>(lds + kAtRow)), ent(reinterpret_cast<float *>(lds + kAtEnt)), pf(reinterpret_cast<uint32_t *>(lds + kAtPf)),
+          fc(reinterpret_cast<uint16_t *>(lds + kAtFc)), sid(reinterpret_cast<uint16_t *>(lds + kAtSid)), nlv(lds + kAtNlv) {}
+};
+
+// What the shared steps leave behind them, next to the LDS: the row, the lane's own node, and the leaf's verdict and total.
+struct Leaf {
+    Row w;
+    int mylev;      // tree level of node `lane`
+    uint32_t mysid; // its node subset under its level's match (0: not in a match list)
+    bool dead;      // some pair entry between matched levels is not > 0
+    double total;
+};
+
+// Index of (u, v), u < v < kN, in a triangular array of kN (kN - 1) / 2.
+__device__ __forceinline__ int tri_index(int u, int v) { return ((u * (2 * kN - u - 1)) >> 1) + (v - u - 1); }
+
+// G(u, v) of pmx_hotspots: the float64 sum, in the order of itertools.product, of the float32 addends exact_value forms for the node pair.
+__device__ __forceinline__ double inner_sum(const ScreenParams &p, uint32_t sidu, uint32_t sidv, float d) {
+    const uint8_t *A = p.sub_nodes + p.sub_off[sidu], *B = p.sub_nodes + p.sub_off[sidv];
+    const int nA = (int)(p.sub_off[sidu + 1] - p.sub_off[sidu]), nB = (int)(p.sub_off[sidv + 1] - p.sub_off[sidv]);
+    double G = 0.0;
+    for (int ia = 0; ia < nA; ++ia) {
+        const int m = A[ia];
+        const float wa = p.W.w[p.M.node_type[m]];
+        for (int ib = 0; ib < nB; ++ib) {
+            const int n = B[ib];
+            const float4 e = p.M.edge[m * p.M.Nm + n]; // {mean, s, T, std}
+            const float z = (d - e.x) / e.w;
+            const float wos = (wa * p.W.w[p.M.node_type[n]]) / e.w;
+            const float g = wos * expf(-0.5f * (z * z));
+            G = G + (double)g;
+        }
+    }
+    return G;
+}
+
+// Row li of the call through open_row and the steps centres, terms, entries and total: what pmx_attribute and pmx_hotspots share. With
+// `gsum` (pmx_hotspots) the terms step also leaves G(u, v) of every evaluated node pair in gsum[tri_index(u, v)].
+template <bool WITH_G>
+__device__ __forceinline__ Leaf leaf_steps(const ScreenParams &p, const Rows &rows, const LeafLds &S, double *gsum, uint32_t li) {
     const int lane = lane_id();
-    float4 *ctr = reinterpret_cast<float4 *>(lds + kAtR);
-    float *term = reinterpret_cast<float *>(lds + kAtR);
-    float4 *pos = reinterpret_cast<float4 *>(lds + kAtPos);
-    double *scale = reinterpret_cast<double *>(lds + kAtScale);
-    unsigned long long *failm = reinterpret_cast<unsigned long long *>(lds + kAtFailm);
-    RowLds &L = *reinterpret_cast<RowLds *>(lds + kAtRow);
-    float *ent = reinterpret_cast<float *>(lds + kAtEnt);
-    uint32_t *pf = reinterpret_cast<uint32_t *>(lds + kAtPf);
-    uint16_t *fc = reinterpret_cast<uint16_t *>(lds + kAtFc);
-    uint16_t *sid = reinterpret_cast<uint16_t *>(lds + kAtSid);
-    uint8_t *nlv = lds + kAtNlv;
+    float4 *ctr = S.ctr;
+    float *term = S.term;
+    float4 *pos = S.pos;
+    double *scale = S.scale;
+    unsigned long long *failm = S.failm;
+    RowLds &L = S.L;
+    float *ent = S.ent;
+    uint32_t *pf = S.pf;
+    uint16_t *fc = S.fc;
+    uint16_t *sid = S.sid;
+    uint8_t *nlv = S.nlv;
     const uint8_t *ls = L.ls, *le = L.le, *keyl = L.key;
 
     // ---- the row as for a ligand without levels
@@ -211,19 +267,21 @@ __device__ void attribute_row(const ScreenParams &p, const pmx_rows::AttributeAr
     }
     sid[lane] = 0;
     nlv[lane] = kNoMatch;
-    const Row w = open_row(p, a.rows, L, li);
+    Leaf f;
+    f.w = open_row(p, rows, L, li);
+    f.mylev = -1, f.mysid = 0u, f.dead = false, f.total = 0.0;
+    const Row &w = f.w;
     const Record &r = w.r;
     const int n = w.n, C = w.C, nl = w.nl, c = w.c;
 
     // (entries are reported for a key with a match that is no candidate, too: that match counts as None; the row is invalid)
-    bool dead = false;
-    double share = 0.0, total = 0.0;
     if (w.compute) {
         GlobalFloats xyz = (GlobalFloats)uniptr(r.xyz);
         // ---- nodes: level, subset under the level's match, position in conformer c
         const NodeSubset me = row_node_subset(p, w, L, lane);
         const int mylev = me.lev;
         const uint32_t mysid = me.sid;
+        f.mylev = mylev, f.mysid = mysid;
         float px = 0.f, py = 0.f, pz = 0.f;
         if (lane < n) {
             const uint32_t o = (uint32_t)(lane * 3 * C + c);
@@ -275,6 +333,7 @@ __device__ void attribute_row(const ScreenParams &p, const pmx_rows::AttributeAr
                 int np, mn;
                 term[lane * kTS + v] = exact_value(p, mysid, sv, d, np, mn);
                 fm |= 2 * np < mn ? 1ull << v : 0ull; // match_utils.py:56-61
+                if (WITH_G) gsum[tri_index(lane, v)] = inner_sum(p, mysid, sv, d);
             }
         }
         failm[lane] = fm;
@@ -313,22 +372,11 @@ __device__ void attribute_row(const ScreenParams &p, const pmx_rows::AttributeAr
             ent[e] = value;
             scale[e] = accd != 0.0 ? (double)value / accd : 0.0;
         }
-        dead = __ballot(dead_pair) != 0ull;
+        f.dead = __ballot(dead_pair) != 0ull;
         wave_sync();
 
-        // ---- node shares
-        if (mysid != 0u) {
-            for (int v = 0; v < n; ++v) {
-                const int lv = uni((int)nlv[v]);
-                if (lv == kNoMatch) continue;
-                if (v != lane) {
-                    const float t = v > lane ? term[lane * kTS + v] : term[v * kTS + lane];
-                    share += (double)t * scale[min(mylev, lv) * kL + max(mylev, lv)];
-                }
-            }
-            share *= 0.5;
-        }
         // ---- the total as the product walker sums it: (running + self) + (pair entries with the matched ancestors, shallowest first)
+        double total = 0.0;
         for (int l = 0; l < nl; ++l) {
             if (uni((int)keyl[l]) == kNoMatch) continue;
             double sum = 0.0;
@@ -336,24 +384,170 @@ __device__ void attribute_row(const ScreenParams &p, const pmx_rows::AttributeAr
                 if (uni((int)keyl[l0]) != kNoMatch) sum += (double)ent[l0 * kL + l];
             total = (total + (double)ent[l * kL + l]) + sum;
         }
+        f.total = total;
+    }
+    return f;
+}
+
+// Row li of the call.
+__device__ void attribute_row(const ScreenParams &p, const pmx_rows::AttributeArgs &a, unsigned char *lds, uint32_t li) {
+    const int lane = lane_id();
+    const LeafLds S(lds);
+    const Leaf f = leaf_steps<false>(p, a.rows, S, nullptr, li);
+    const float *term = S.term, *ent = S.ent;
+    const double *scale = S.scale;
+
+    // ---- node shares
+    double share = 0.0;
+    if (f.w.compute && f.mysid != 0u) {
+        for (int v = 0; v < f.w.n; ++v) {
+            const int lv = uni((int)S.nlv[v]);
+            if (lv == kNoMatch) continue;
+            if (v != lane) {
+                const float t = v > lane ? term[lane * kTS + v] : term[v * kTS + lane];
+                share += (double)t * scale[min(f.mylev, lv) * kL + max(f.mylev, lv)];
+            }
+        }
+        share *= 0.5;
     }
 
     // ---- the row
-    const int status = row_status(w, dead);
+    const int status = row_status(f.w, f.dead);
     const double nan = __builtin_nan("");
     a.node[(size_t)li * kN + lane] = status == PMX_LIGAND_OK ? share : nan;
     for (int e = lane; e < kL * kL; e += 64) {
         a.entry[(size_t)li * kL * kL + e] = ent[e];
-        a.fails[(size_t)li * kL * kL + e] = fc[e];
+        a.fails[(size_t)li * kL * kL + e] = S.fc[e];
     }
-    if (lane == 0) a.total[li] = status == PMX_LIGAND_OK ? total : nan;
-    write_row_header(a.rows, L, li, status);
+    if (lane == 0) a.total[li] = status == PMX_LIGAND_OK ? f.total : nan;
+    write_row_header(a.rows, S.L, li, status);
     wave_sync(); // (the next row starts by clearing this LDS)
 }
 
 __global__ __launch_bounds__(64) void attribute_kernel(const ScreenParams p, const pmx_rows::AttributeArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[kAttributeLds];
     for_each_row(a.rows, [&](uint32_t li) { attribute_row(p, a, lds, li); });
+}
+
+// ------------------------------------------------------------------------------------------------ hotspots
+// hotspots_row - which model nodes carry a leaf's total: leaf_steps as above, with G(u, v) kept per node pair, then the model-side step.
+//   masks     lane u = node u: its node subset as a bit per model node, PMX_FINGERPRINT_WORDS words
+//   hotspots  lane = model node m = lane + 64 j (a register set per node word j): the listed node pairs (u, v) are walked wave-uniformly, in
+//             ascending (u, v); a lane whose m is in u's subset walks v's subset in ascending order and adds up the pair's inner terms
+//             (m, m') in float64, a lane whose m is in v's subset walks u's; the sums are weighted by term(u, v) scale[e] / (2 G(u, v)).
+//             Every inner term is evaluated once from each side, and no lane adds to another lane's sum.
+constexpr int kW = PMX_FINGERPRINT_WORDS;
+static_assert(kW * 64 == PMX_MAX_MODEL_NODES && kW == 4, "a lane per model node and node word");
+constexpr uint32_t kHsG = (kAttributeLds + 7u) & ~7u;             // double [kN (kN - 1) / 2]: G(u, v), tri_index
+constexpr uint32_t kHsMask = kHsG + (kN * (kN - 1) / 2) * 8;      // u64 [kN][kW]: the model nodes of each listed node's subset
+constexpr uint32_t kHotspotsLds = kHsMask + kN * kW * 8;
+static_assert(kHotspotsLds <= 64 * 1024, "LDS of a work-group");
+
+// The inner terms of one side: model node m (in one node's subset) against the other node's subset `other` (ascending). SWAP: m is the
+// second index of the model edge (m is on v's side). Adds the float32 addends to `sum` in float64 and counts terms and passes.
+template <bool SWAP>
+__device__ __forceinline__ void inner_side(const ScreenParams &p, int m, const unsigned long long *other, int nw, float d, double &sum, uint32_t &terms, uint32_t &pass) {
+    const float wm = p.W.w[p.M.node_type[m]];
+    for (int j = 0; j < nw; ++j) {
+        unsigned long long bits = other[j];
+        while (bits != 0ull) {
+            const int o = 64 * j + (int)__builtin_ctzll(bits);
+            bits &= bits - 1ull;
+            const float wo = p.W.w[p.M.node_type[o]];
+            const float4 e = SWAP ? p.M.edge[o * p.M.Nm + m] : p.M.edge[m * p.M.Nm + o]; // {mean, s, T, std}
+            const float t = d - e.x, z = t / e.w;
+            const float wos = (SWAP ? wo * wm : wm * wo) / e.w;
+            const float g = wos * expf(-0.5f * (z * z));
+            sum = sum + (double)g;
+            terms += 1u;
+            pass += fabsf(t) <= e.z ? 1u : 0u; // == abs(z) < 2 (pmx_device.h)
+        }
+    }
+}
+
+// Row li of the call.
+__device__ void hotspots_row(const ScreenParams &p, const pmx_rows::HotspotArgs &a, unsigned char *lds, uint32_t li) {
+    const int lane = lane_id();
+    const LeafLds S(lds);
+    double *gsum = reinterpret_cast<double *>(lds + kHsG);
+    unsigned long long *mask = reinterpret_cast<unsigned long long *>(lds + kHsMask);
+    const Leaf f = leaf_steps<true>(p, a.rows, S, gsum, li);
+    const int status = row_status(f.w, f.dead);
+    const int Nm = p.M.Nm, nw = (Nm + 63) >> 6; // (a model has at most PMX_MAX_MODEL_NODES nodes: nw <= kW)
+
+    double hs[kW] = {0.0, 0.0, 0.0, 0.0};
+    uint32_t tc[kW] = {0u, 0u, 0u, 0u}, pc[kW] = {0u, 0u, 0u, 0u};
+    if (status == PMX_LIGAND_OK) {
+        // ---- masks
+        unsigned long long mw[kW] = {0ull, 0ull, 0ull, 0ull};
+        if (f.mysid != 0u) {
+            for (uint32_t k = p.sub_off[f.mysid]; k < p.sub_off[f.mysid + 1u]; ++k) {
+                const int m = p.sub_nodes[k];
+#pragma unroll
+                for (int j = 0; j < kW; ++j) mw[j] |= (m >> 6) == j ? 1ull << (m & 63) : 0ull;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kW; ++j) mask[lane * kW + j] = mw[j];
+        wave_sync();
+
+        // ---- hotspots
+        const int n = f.w.n;
+        for (int u = 0; u + 1 < n; ++u) {
+            const int lu = uni((int)S.nlv[u]);
+            if (lu == kNoMatch) continue;
+            const float4 P = S.pos[u];
+            const unsigned long long *mu = mask + u * kW;
+            for (int v = u + 1; v < n; ++v) {
+                const int lv = uni((int)S.nlv[v]);
+                if (lv == kNoMatch) continue;
+                const float4 Q = S.pos[v];
+                const float d = norm3f(P.x - Q.x, P.y - Q.y, P.z - Q.z); // (the operands and the operations of the terms step)
+                const double G = gsum[tri_index(u, v)];
+                const double coef = G != 0.0 ? (0.5 * ((double)S.term[u * kTS + v] * S.scale[min(lu, lv) * kL + max(lu, lv)])) / G : 0.0;
+                const unsigned long long *mv = mask + v * kW;
+#pragma unroll
+                for (int j = 0; j < kW; ++j) {
+                    if (j >= nw) continue;
+                    const int m = lane + 64 * j;
+                    if ((mu[j] >> lane) & 1ull) {
+                        double sum = 0.0;
+                        inner_side<false>(p, m, mv, nw, d, sum, tc[j], pc[j]);
+                        hs[j] = hs[j] + coef * sum;
+                    }
+                    if ((mv[j] >> lane) & 1ull) {
+                        double sum = 0.0;
+                        inner_side<true>(p, m, mu, nw, d, sum, tc[j], pc[j]);
+                        hs[j] = hs[j] + coef * sum;
+                    }
+                }
+            }
+        }
+    }
+
+    // ---- the row
+    const double nan = __builtin_nan("");
+    unsigned long long fp[kW];
+#pragma unroll
+    for (int j = 0; j < kW; ++j) {
+        const size_t o = (size_t)li * PMX_MAX_MODEL_NODES + (size_t)(lane + 64 * j);
+        a.hotspot[o] = status == PMX_LIGAND_OK ? hs[j] : nan;
+        a.terms[o] = tc[j];
+        a.pass[o] = pc[j];
+        fp[j] = __ballot(tc[j] > 0u && 2u * pc[j] >= tc[j]); // match_utils.py:56-61, per hotspot
+    }
+    if (lane == 0) {
+        a.total[li] = status == PMX_LIGAND_OK ? f.total : nan;
+#pragma unroll
+        for (int j = 0; j < kW; ++j) a.fingerprint[(size_t)li * kW + j] = fp[j];
+    }
+    write_row_header(a.rows, S.L, li, status);
+    wave_sync(); // (the next row starts by clearing this LDS)
+}
+
+__global__ __launch_bounds__(64) void hotspots_kernel(const ScreenParams p, const pmx_rows::HotspotArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kHotspotsLds];
+    for_each_row(a.rows, [&](uint32_t li) { hotspots_row(p, a, lds, li); });
 }
 
 // ------------------------------------------------------------------------------------------------ rigid fit
@@ -597,13 +791,14 @@ __global__ __launch_bounds__(64) void align_kernel(const ScreenParams p, const p
 
 namespace pmx_rows {
 
-size_t lds_bytes(Kind kind) { return kind == kAttribute ? (size_t)pmx_r::kAttributeLds : sizeof(pmx_r::RowLds); }
+size_t lds_bytes(Kind kind) { return kind == kAttribute ? (size_t)pmx_r::kAttributeLds : (kind == kHotspots ? (size_t)pmx_r::kHotspotsLds : sizeof(pmx_r::RowLds)); }
 
 bool launch(Kind kind, unsigned blocks, hipStream_t stream, const void *params, size_t bytes, const void *args) {
     if (bytes != sizeof(pmx_r::ScreenParams)) return false;
     pmx_r::ScreenParams p;
     std::memcpy(&p, params, sizeof p);
     if (kind == kAttribute) pmx_r::attribute_kernel<<<dim3(blocks), dim3(64), 0, stream>>>(p, *static_cast<const AttributeArgs *>(args));
+    else if (kind == kHotspots) pmx_r::hotspots_kernel<<<dim3(blocks), dim3(64), 0, stream>>>(p, *static_cast<const HotspotArgs *>(args));
     else pmx_r::align_kernel<<<dim3(blocks), dim3(64), 0, stream>>>(p, *static_cast<const AlignArgs *>(args));
     return true;
 }

@@ -355,6 +355,25 @@ class ScreeningResult:
         return explain_modes(model, library, self._best(k), modes=modes, weights=weights, require=require, exclude=exclude)
 
 
+    def diverse(self, k: int, pool: int | None = None, threshold: float = 0.7, model=None, library=None, weights: dict[str, float] | None = None) -> "DiverseHits":
+        """The k first hits of this screen that are not the same binding mode again: the best `pool` hits (default
+        min(len, max(8 k, 1024), 65536)) are explained, fingerprinted at their best conformer (`Explanation.hotspots`) and run through
+        `HotspotProfile.leaders(threshold)` in rank order. Hits with a non-zero status are left out of the pool."""
+        if k <= 0:
+            raise ValueError("k must be positive")
+        model, library, weights = self._scored(model, library, weights)
+        n = int(self.scores.numel())
+        pool = min(n, max(8 * k, 1024), 65536) if pool is None else int(pool)
+        if not 0 < pool <= 65536:
+            raise ValueError("pool: 1 to 65536 hits")
+        ex = explain(model, library, self._best(pool), weights=weights)
+        prof = ex.hotspots(model, library, weights=weights)
+        leaders, leader_of = prof.leaders(threshold=threshold, max_leaders=min(k, 2048))
+        sizes = np.bincount(leader_of[leader_of >= 0], minlength=len(prof)).astype(np.int64)
+        return DiverseHits(indices=prof.indices[leaders], scores=ex.scores[prof.rows[leaders]], cluster_size=sizes[leaders],
+                           leaders=leaders, leader_of=leader_of, pool=prof.indices, profile=prof)
+
+
 def _weights_array(weights):
     return (ctypes.c_float * _ffi.NUM_TYPES)(*weights_vector(weights))
 
@@ -611,6 +630,15 @@ class Explanation:
         match puts the ligand in the pocket. `rows` of the result says which row of this explanation each of its rows is."""
         rows, conf, keys = self._own_rows(conformer)
         out = align(model, library, self.indices[rows], conf, keys, weights=weights)
+        out.rows = np.asarray(rows, dtype=np.int64)
+        return out
+
+    def hotspots(self, model, library, conformer: int | None = None, weights: dict[str, float] | None = None) -> "HotspotProfile":
+        """`hotspots` of every row with status 0, at its best conformer (or `conformer`) under that conformer's own key: which model nodes
+        carry the explained maximum, and the row's interaction fingerprint. `rows` of the result says which row of this explanation each
+        of its rows is."""
+        rows, conf, keys = self._own_rows(conformer)
+        out = hotspots(model, library, self.indices[rows], conf, keys, weights=weights)
         out.rows = np.asarray(rows, dtype=np.int64)
         return out
 
@@ -1087,6 +1115,167 @@ def align(model, library, indices, conformers, keys, weights: dict[str, float] |
     return Alignment(indices=idx, conformers=conf, rotation=rot.cpu().numpy()[:n].copy(), translation=trans.cpu().numpy()[:n].copy(),
                      rmsd=ft[:, 2].copy(), rmsd_nodes=ft[:, 3].copy(), weight=ft[:, 0].copy(), sse=ft[:, 1].copy(), scale=ft[:, 4].copy(), gap=ft[:, 5].copy(),
                      node=[nd[i, : nn[i]].copy() for i in range(n)], n_nodes=cn[:, 0].copy(), n_pairs=cn[:, 1].copy(), levels=out_lv, status=st)
+
+
+_MAX_MODEL_NODES, _FP_WORDS, _MAX_LEADERS = 256, 4, 2048  # PMX_MAX_MODEL_NODES, PMX_FINGERPRINT_WORDS, PMX_MAX_LEADERS
+
+
+def _fingerprint_tensor(fp, tdev):
+    torch = _torch()
+    fp = np.ascontiguousarray(np.asarray(fp, dtype=np.uint64).reshape(-1, _FP_WORDS))
+    if len(fp) > 65536:
+        raise ValueError("at most 65536 fingerprints per call (PMX_EXPLAIN_MAX)")
+    return torch.from_numpy(np.ascontiguousarray(fp.view(np.int64).reshape(max(len(fp), 0), _FP_WORDS))).to(tdev), len(fp)
+
+
+def fingerprint_similarity(a, b=None, device=None) -> np.ndarray:
+    """Tanimoto similarity (`pmx_fingerprint_tanimoto`, csrc/pmx_fingerprint.hip) of the uint64 [n, 4] fingerprints `a` against `b` (default:
+    `a` itself): float32 [n, m], popcount(x & y) / popcount(x | y) and 1 where both are empty. Waits for the stream."""
+    torch = _torch()
+    lib = _ffi.load()
+    dev = _device_index(device)
+    tdev = torch.device("cuda", dev)
+    with torch.cuda.device(tdev):
+        ta, na = _fingerprint_tensor(a, tdev)
+        tb, nb = (ta, na) if b is None else _fingerprint_tensor(b, tdev)
+        out = torch.empty((na, nb), dtype=torch.float32, device=tdev)
+        stream = torch.cuda.current_stream(tdev)
+        _ffi.check(lib.pmx_fingerprint_tanimoto(ta.data_ptr(), na, tb.data_ptr(), nb, out.data_ptr(), dev, ctypes.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+    return out.cpu().numpy()
+
+
+def fingerprint_leaders(fp, threshold: float = 0.7, max_leaders: int = _MAX_LEADERS, device=None):
+    """Sphere exclusion in row order (`pmx_fingerprint_leaders`): (leaders, leader_of) - the rows that became leaders, ascending, and per row
+    the leader it joined (itself for a leader; -1 for a row that joined none after `max_leaders` leaders existed). A row joins the first
+    earlier leader it is at least `threshold` similar to. Waits for the stream."""
+    torch = _torch()
+    lib = _ffi.load()
+    dev = _device_index(device)
+    tdev = torch.device("cuda", dev)
+    with torch.cuda.device(tdev):
+        t, n = _fingerprint_tensor(fp, tdev)
+        leader_of = torch.empty(max(n, 1), dtype=torch.int32, device=tdev)
+        leaders = torch.empty(max(int(max_leaders), 1), dtype=torch.int32, device=tdev)
+        count = torch.zeros(1, dtype=torch.int32, device=tdev)
+        stream = torch.cuda.current_stream(tdev)
+        _ffi.check(lib.pmx_fingerprint_leaders(t.data_ptr(), n, float(threshold), int(max_leaders), leader_of.data_ptr(), leaders.data_ptr(), count.data_ptr(), dev,
+                                               ctypes.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+    nl = int(count.cpu()[0])
+    lo = leader_of.cpu().numpy()[:n].view(np.uint32).astype(np.int64)
+    lo[lo == 0xFFFFFFFF] = -1
+    return leaders.cpu().numpy()[:nl].view(np.uint32).astype(np.int64), lo
+
+
+@dataclass
+class HotspotProfile:
+    """What `hotspots` returns: one row per (ligand, conformer, key), cut to the model's nodes Nm (definitions: `pmx_hotspots` in
+    include/pmx.h).
+
+    total[i]        float64: the leaf's total, `Attribution.total` bit for bit; NaN when the row is not valid or the ligand unsupported
+    share[i]        float64 [Nm]: what each model node - each hotspot of the pocket - carries of it; they add up to total[i]; NaN like total
+    terms[i], passes[i]  int [Nm]: the inner terms a node is a side of, and those within two sigma
+    fingerprint     uint64 [n, 4]: bit m % 64 of word m // 64 says node m is engaged (it has terms and at least half of them pass)
+    levels[i]       int [nl]: the ligand cluster behind each tree level
+    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID)"""
+
+    indices: np.ndarray
+    conformers: np.ndarray
+    total: np.ndarray
+    share: list
+    terms: list
+    passes: list
+    fingerprint: np.ndarray
+    levels: list
+    status: np.ndarray
+    rows: "np.ndarray | None" = None  # `Explanation.hotspots`: the explanation's row behind each row
+    device: "int | None" = None  # where `similarity` and `leaders` run
+
+    def __len__(self) -> int:
+        return len(self.indices)
+
+    def nodes(self, i: int) -> np.ndarray:
+        """The engaged model nodes of row i: the set bits of its fingerprint, ascending."""
+        bits = np.unpackbits(self.fingerprint[i].view(np.uint8), bitorder="little")
+        return np.flatnonzero(bits).astype(np.int64)
+
+    def cluster_share(self, i: int, model) -> np.ndarray:
+        """Row i's shares summed per model cluster (index in `model.node_clusters`): float64 [K]. A node that belongs to several clusters
+        counts in each of them, so the sum over the clusters can exceed total[i]."""
+        flat = model.flat
+        cn = np.asarray(flat.cluster_nodes, dtype=np.uint64)
+        cn = cn.reshape(cn.shape[0], -1)
+        member = np.unpackbits(np.ascontiguousarray(cn).view(np.uint8), axis=1, bitorder="little")[:, : len(self.share[i])].astype(bool)
+        return np.array([float(self.share[i][member[a]].sum()) for a in range(member.shape[0])])
+
+    def usage(self) -> np.ndarray:
+        """Which hotspots this list of hits lives off: the mean of share / total over the rows with status 0 and total > 0. float64 [Nm];
+        zeros when there is no such row."""
+        rows = [i for i in range(len(self)) if self.status[i] == 0 and self.total[i] > 0]
+        if not rows:
+            return np.zeros(len(self.share[0]) if len(self) else 0)
+        return np.mean([self.share[i] / self.total[i] for i in rows], axis=0)
+
+    def similarity(self, other: "HotspotProfile | None" = None) -> np.ndarray:
+        """Tanimoto similarity of the fingerprints, on the GPU: float32 [n, m] against `other`'s rows (default: this profile's own)."""
+        return fingerprint_similarity(self.fingerprint, None if other is None else other.fingerprint, device=self.device)
+
+    def leaders(self, threshold: float = 0.7, max_leaders: int = _MAX_LEADERS):
+        """Sphere exclusion over the rows in their order, which is the caller's ranking (`fingerprint_leaders`): (leaders, leader_of)."""
+        return fingerprint_leaders(self.fingerprint, threshold=threshold, max_leaders=max_leaders, device=self.device)
+
+
+@dataclass
+class DiverseHits:
+    """What `ScreeningResult.diverse` returns.
+
+    indices, scores  the first k leaders of the pool, best first: indices in the library that was screened, and the hits' scores
+    cluster_size     per leader the hits of the pool that joined it, itself included
+    leaders          the leaders' rows in the pool
+    leader_of        per hit of the pool the pool row of its leader (-1: it joined none of the k)
+    pool             the pooled hits' indices, best first;  profile  their `HotspotProfile`"""
+
+    indices: np.ndarray
+    scores: np.ndarray
+    cluster_size: np.ndarray
+    leaders: np.ndarray
+    leader_of: np.ndarray
+    pool: np.ndarray
+    profile: "HotspotProfile"
+
+    def __len__(self) -> int:
+        return len(self.indices)
+
+
+def hotspots(model, library, indices, conformers, keys, weights: dict[str, float] | None = None, device=None) -> HotspotProfile:
+    """Total, model-node shares, term counts and interaction fingerprint (`pmx_hotspots`, csrc/pmx_rows.hip) of the leaf `keys[i]` of library
+    ligand `indices[i]` for its conformer `conformers[i]`, rows as `attribute` takes them. At most 65536 rows; any order, repeats allowed.
+    Runs on torch's current stream of the device and waits for it."""
+    torch = _torch()
+    NM, FW = _MAX_MODEL_NODES, _FP_WORDS
+    where = []
+
+    def call(lib, mh, dlib, m, ptrs):
+        lig, cf, key, n, levels, status, stream = ptrs
+        tdev = torch.device("cuda", dlib.device)
+        where.append(dlib.device)
+        total = torch.empty(m, dtype=torch.float64, device=tdev)
+        share = torch.empty((m, NM), dtype=torch.float64, device=tdev)
+        terms = torch.empty((m, NM), dtype=torch.int32, device=tdev)
+        passes = torch.empty((m, NM), dtype=torch.int32, device=tdev)
+        fp = torch.empty((m, FW), dtype=torch.int64, device=tdev)
+        _ffi.check(lib.pmx_hotspots(mh.handle, dlib.handle, _weights_array(weights), lig, cf, key, n, total.data_ptr(), share.data_ptr(), terms.data_ptr(),
+                                    passes.data_ptr(), fp.data_ptr(), levels, status, stream))
+        return total, share, terms, passes, fp
+
+    idx, conf, (total, share, terms, passes, fp), out_lv, _, st = _row_call(model, library, indices, conformers, keys, "hotspots", device, call)
+    n, nm = len(idx), int(model.flat.num_nodes)
+    tt, sh = total.cpu().numpy()[:n], share.cpu().numpy()[:n]
+    tc, pc = terms.cpu().numpy()[:n].view(np.uint32), passes.cpu().numpy()[:n].view(np.uint32)
+    return HotspotProfile(indices=idx, conformers=conf, total=tt.copy() if n else np.zeros(0), share=[sh[i, :nm].copy() for i in range(n)],
+                          terms=[tc[i, :nm].astype(np.int64) for i in range(n)], passes=[pc[i, :nm].astype(np.int64) for i in range(n)],
+                          fingerprint=fp.cpu().numpy()[:n].view(np.uint64).copy().reshape(n, FW), levels=out_lv, status=st, device=where[0])
 
 
 def last_score_stats() -> dict:

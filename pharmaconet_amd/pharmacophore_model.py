@@ -400,6 +400,35 @@ class PharmacophoreModel:
         return dict(conformer=int(conformer), key=np.asarray(key, dtype=np.int64), levels=at.levels[0], total=float(at.total[0]), node=at.node[0],
                     entry=at.entry[0], fails=at.fails[0], status=int(at.status[0]))
 
+    def scoring_hotspots(self, ligand, weights: dict[str, float] | None = None, conformer: int | None = None, key=None) -> dict:
+        """Which model nodes - hotspots of the pocket - carry a leaf's total for one ligand (`engine.hotspots`): by default the explaining leaf
+        of the best conformer, else `conformer` and / or `key` (a model cluster or -1 per tree level). `conformer`, `key`, `levels`, `total`,
+        `share` (per model node), `terms`, `passes`, `fingerprint` (uint64 [4]), `nodes` (the engaged model nodes) and `status` (0, or 4 when
+        the key is not a leaf of the ligand's tree for that conformer: total and share are then NaN). Takes what `_scoring` takes."""
+        from .engine import explain, hotspots
+        from .library import as_packed_library
+
+        packed = as_packed_library(ligand)
+        if len(packed) != 1:
+            raise ValueError("scoring_hotspots takes exactly one ligand")
+        if conformer is None or key is None:
+            ex = explain(self, packed, [0], weights=weights)
+            if int(ex.status[0]) != 0:
+                n, c, _ = packed.header(0)
+                raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+            if conformer is None:
+                conformer = int(ex.best_conformer[0])
+            if key is None:
+                if not 0 <= int(conformer) < ex.match[0].shape[0]:
+                    raise ValueError(f"the ligand has {ex.match[0].shape[0]} conformers")
+                key = ex.match[0][int(conformer)]
+        hs = hotspots(self, packed, [0], [int(conformer)], [key], weights=weights)
+        if int(hs.status[0]) == 1:
+            n, c, _ = packed.header(0)
+            raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+        return dict(conformer=int(conformer), key=np.asarray(key, dtype=np.int64), levels=hs.levels[0], total=float(hs.total[0]), share=hs.share[0],
+                    terms=hs.terms[0], passes=hs.passes[0], fingerprint=hs.fingerprint[0], nodes=hs.nodes(0), status=int(hs.status[0]))
+
     def scoring_pose(self, ligand, weights: dict[str, float] | None = None, conformer: int | None = None, key=None) -> dict:
         """One ligand put into the pocket (`engine.align`): by default its best conformer under the explaining leaf's match, else `conformer`
         and / or `key` (a model cluster or -1 per tree level; it need not be a leaf of the tree). `positions` [n_atoms, 3] are the

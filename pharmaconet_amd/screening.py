@@ -34,6 +34,11 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--explain_out", type=str, default=None, help="CSV of the explained hits (default: <out>.explain.csv)")
         cfg.add_argument("--explain_nodes", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per pharmacophore node of each explained hit and the node's share of the hit's best conformer maximum")
         cfg.add_argument("--poses", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit and the rigid motion (rotation, translation) that puts its best conformer onto the matched pharmacophore points")
+        cfg.add_argument("--hotspots", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per (explained hit, model node it has terms with): the node's share of the hit's best conformer maximum and whether the hit engages it")
+        cfg.add_argument("--diverse", type=int, default=None, metavar="K", help="list the K first hits that are not the same binding mode again (leaders by interaction fingerprint, in rank order)")
+        cfg.add_argument("--diverse_pool", type=int, default=None, metavar="P", help="best hits that --diverse looks at (default: max(8 K, 1024), at most 65536)")
+        cfg.add_argument("--diverse_threshold", type=float, default=0.7, metavar="T", help="Tanimoto similarity from which a hit joins an earlier leader")
+        cfg.add_argument("--diverse_out", type=str, default=None, metavar="PATH", help="CSV of the diverse hits (needed with --diverse)")
         cfg.add_argument("--modes", type=int, default=None, metavar="M", help="with --explain K: also list the M (1 to 8) best binding modes of each explained hit's best conformer")
         cfg.add_argument("--modes_out", type=str, default=None, metavar="PATH", help="CSV of the modes (default: <out>.modes.csv)")
         cfg.add_argument("--require", action="append", default=[], metavar="LIST", help="constrained matching: comma-separated model cluster indices, one of which a hit's match must hold (repeatable: one group each)")
@@ -129,6 +134,18 @@ def main(argv=None) -> None:
         parser.error("--explain_nodes needs --explain K")
     if args.poses and args.explain <= 0:
         parser.error("--poses needs --explain K")
+    if args.hotspots and args.explain <= 0:
+        parser.error("--hotspots needs --explain K")
+    if args.diverse is not None and args.diverse <= 0:
+        parser.error("--diverse takes a positive K")
+    if args.diverse is not None and not args.diverse_out:
+        parser.error("--diverse needs --diverse_out PATH")
+    if args.diverse is None and (args.diverse_out or args.diverse_pool is not None):
+        parser.error("--diverse_out / --diverse_pool need --diverse K")
+    if args.diverse_pool is not None and not 1 <= args.diverse_pool <= 65536:
+        parser.error("--diverse_pool takes 1 to 65536")
+    if not 0.0 < args.diverse_threshold <= 1.0:
+        parser.error("--diverse_threshold takes a similarity in (0, 1]")
     if args.modes is not None and args.explain <= 0:
         parser.error("--modes needs --explain K")
     if args.modes is not None and not 1 <= args.modes <= 8:
@@ -178,9 +195,13 @@ def main(argv=None) -> None:
             write_explain_nodes_csv(Path(args.explain_nodes), names, scores, status, model, lib, weight, args.explain)
         if args.poses:
             write_poses_csv(Path(args.poses), names, scores, status, model, lib, weight, args.explain)
+        if args.hotspots:
+            write_hotspots_csv(Path(args.hotspots), names, scores, status, model, lib, weight, args.explain)
         if args.modes is not None:
             out = Path(args.modes_out) if args.modes_out else Path(str(args.out) + ".modes.csv")
             write_modes_csv(out, names, scores, status, model, lib, weight, args.explain, args.modes)
+    if args.diverse is not None:
+        write_diverse_csv(Path(args.diverse_out), names, result, args.diverse, args.diverse_pool, args.diverse_threshold)
     if args.constrained_out:
         write_constrained_csv(Path(args.constrained_out), names, model, lib, weight, args.constrained_k, require, exclude)
     if args.panel_out or args.save_top:
@@ -315,6 +336,39 @@ def write_explain_nodes_csv(out: Path, names: list[str], scores: np.ndarray, sta
                 types = "|".join(TYPE_NAMES[t] for t in range(len(TYPE_NAMES)) if tm >> t & 1)
                 frac = float(share) / total if total > 0 else 0.0
                 w.write(f"{int(row) + 1},{i},{names[i]},{int(at.conformers[r])},{u},{types},{lc},{matched.get(lc, '')},{float(share)},{frac}\n")
+
+
+def write_hotspots_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int) -> None:
+    """One row per (hit, model node the hit has terms with) of the k best hits, in the order of the explain CSV: the node's index in the
+    model, its type, its share of the hit's best conformer maximum (`engine.hotspots`), the share as a fraction of it, and 1 where the
+    hit engages the node (the node's bit of the hit's interaction fingerprint)."""
+    from .constants import TYPE_NAMES
+    from .engine import explain
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    hs = explain(model, lib, order, weights=weights).hotspots(model, lib, weights=weights)
+    node_type = model.flat.node_type
+    with open(out, "w") as w:
+        w.write("rank,path,node,type,share,fraction,engaged\n")
+        for r, row in enumerate(hs.rows):
+            total = float(hs.total[r])
+            engaged = set(hs.nodes(r).tolist())
+            for m in np.flatnonzero(hs.terms[r] > 0):
+                share = float(hs.share[r][m])
+                w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(m)},{TYPE_NAMES[int(node_type[m])]},{share},{share / total if total > 0 else 0.0},{int(int(m) in engaged)}\n")
+
+
+def write_diverse_csv(out: Path, names: list[str], result, k: int, pool: int | None, threshold: float) -> None:
+    """The k first hits of the screen that are not the same binding mode again (`ScreeningResult.diverse`), best first: the hit's rank
+    in the main CSV, its score, how many hits of the pool joined it (itself included) and the model nodes it engages."""
+    dv = result.diverse(k, pool=pool, threshold=threshold)
+    pool_rows = dv.profile.rows
+    scores = result.scores.cpu().numpy()  # (the main CSV's numbers)
+    with open(out, "w") as w:
+        w.write("rank,path,score,cluster_size,engaged_nodes\n")
+        for r, row in enumerate(dv.leaders):
+            w.write(f"{int(pool_rows[row]) + 1},{names[int(dv.indices[r])]},{float(scores[int(dv.indices[r])])},{int(dv.cluster_size[r])},{' '.join(str(int(m)) for m in dv.profile.nodes(int(row)))}\n")
 
 
 def write_poses_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int) -> None:
