@@ -15,11 +15,13 @@ PKG = Path(__file__).resolve().parent
 REPO = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libpmx.so"
-PACK_LIB = PKG / "libpmx_pack.so"  # the packer alone, host-only (no HIP / RCCL runtime)
-SOURCES = ("pmx_api.hip", "pmx_screen_debug.hip", "pmx_explain.hip", "pmx_rows.hip", "pmx_fingerprint.hip", "pmx_topk.hip", "pmx_density.hip", "pmx_pack_device.hip", "pmx_select.hip", "pmx_pack.cpp", "pmx_sdf.cpp", "pmx_perceive.cpp")
+PACK_LIB = PKG / "libpmx_pack.so"  # the host-only units alone (no HIP / RCCL runtime)
+SOURCES = ("pmx_api.hip", "pmx_screen_debug.hip", "pmx_explain.hip", "pmx_rows.hip", "pmx_fingerprint.hip", "pmx_topk.hip", "pmx_density.hip", "pmx_pack_device.hip", "pmx_select.hip", "pmx_pack.cpp", "pmx_sdf.cpp", "pmx_perceive.cpp", "pmx_model_tables.cpp", "pmx_error.cpp")
+# the host-only units: libpmx_pack.so is these alone (the packer, the readers, the model tables and the error hook)
+HOST_SOURCES = tuple(s for s in SOURCES if s.endswith(".cpp"))
 # every file under csrc/ that a unit of SOURCES #includes, directly or not (tests/test_cabi.py checks the closure): with SOURCES, what the
 # digest of the stamp covers
-DEPS = ("pmx_screen.hip", "pmx_screen_walk.h", "pmx_screen_tables.h", "pmx_screen_layout.h", "pmx_device.h", "pmx_debug.h", "pmx_explain.h", "pmx_rows.h", "pmx_scan.h")
+DEPS = ("pmx_screen.hip", "pmx_screen_walk.h", "pmx_screen_tables.h", "pmx_screen_layout.h", "pmx_device.h", "pmx_debug.h", "pmx_explain.h", "pmx_rows.h", "pmx_scan.h", "pmx_error.h", "pmx_model_tables.h")
 FLAGS = (
     "--offload-arch=gfx950",
     "-O3",
@@ -140,8 +142,9 @@ def _build(verbose: bool) -> Path:
     os.replace(tmp, LIB)
     # the host-only packer library
     tmp = PACK_LIB.with_suffix(".so.tmp")
-    cmd = [os.environ.get("CXX", "g++"), "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-DPMX_PACK_STANDALONE", f"-I{REPO / 'include'}",
-           str(CSRC / "pmx_pack.cpp"), str(CSRC / "pmx_sdf.cpp"), str(CSRC / "pmx_perceive.cpp"), "-o", str(tmp)]
+    # (-ffp-contract=off: pmx_model_tables.cpp must round like the reference's float32 NumPy code in this library too)
+    cmd = [os.environ.get("CXX", "g++"), "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-ffp-contract=off", f"-I{REPO / 'include'}",
+           *(str(CSRC / s) for s in HOST_SOURCES), "-o", str(tmp)]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)

@@ -3,7 +3,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
@@ -23,11 +22,11 @@
 #include "pmx_debug.h"
 #include "pmx_explain.h"
 #include "pmx_rows.h"
+#include "pmx_model_tables.h"
 
 using namespace pmx;
 
-// ------------------------------------------------------------------------------------- errors
-static thread_local char g_err[512] = "";
+// -------------------------------------------------------------------------------------- state
 static thread_local pmx_score_stats g_stats = {};
 static int g_profiling = 0;
 struct ScreenWs;
@@ -35,30 +34,12 @@ static thread_local std::shared_ptr<ScreenWs> g_last_screen;
 static thread_local int g_last_device = 0;
 static int screen_stats(pmx_score_stats *out);
 
-static int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIPCHECK(expr)                                                                                         \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess)                                                                                  \
-            return fail(e_ == hipErrorOutOfMemory ? PMX_ERR_OOM : PMX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, \
-                        hipGetErrorString(e_), __FILE__, __LINE__);                                            \
-    } while (0)
-
-extern "C" const char *pmx_last_error(void) { return g_err; }
-extern "C" int pmx_version(void) { return 101; }
 extern "C" int pmx_set_profiling(int enabled) {
     g_profiling = enabled;
     return PMX_OK;
 }
 extern "C" int pmx_score_stats_get(pmx_score_stats *out) {
-    if (!out) return fail(PMX_ERR_INVALID, "null stats");
+    if (!out) return pmx_fail(PMX_ERR_INVALID, "null stats");
     *out = g_stats;
     if (g_last_screen) return screen_stats(out);
     return PMX_OK;
@@ -72,6 +53,7 @@ struct FnEntry { // tabulated pair functions for one set of type weights
     uint64_t stamp = 0;
 };
 
+// The tables of pmx_model_tables.cpp in one device allocation; every pointer below and in `dm` points into `blob`.
 struct pmx_model {
     int device;
     DevModel dm;
@@ -80,190 +62,19 @@ struct pmx_model {
     // node subsets and tabulated pair functions (pmx_screen_layout.h FnTable, pmx_screen_tables.h fn_build_kernel)
     uint32_t NS = 0, NF = 0, ncell = 0;
     float h = 0.f;
-    uint16_t *sidtab = nullptr;  // device [K * 128]
-    uint32_t *sub_off = nullptr;  // device [NS + 1]: the nodes of subset s are sub_nodes[sub_off[s] .. sub_off[s + 1]), ascending
-    uint8_t *sub_nodes = nullptr; // device
-    float2 *win = nullptr;        // device [NS * NS * ncell] exact pass windows
-    uint64_t n_complex_cells = 0;
+    const uint16_t *sidtab = nullptr;  // [K * 128]
+    const uint32_t *sub_off = nullptr;  // [NS + 1]: the nodes of subset s are sub_nodes[sub_off[s] .. sub_off[s + 1]), ascending
+    const uint8_t *sub_nodes = nullptr;
+    const float2 *win = nullptr;        // [NF * ncell] exact pass windows
     std::mutex fn_mu;
     std::vector<FnEntry> fn;
     uint64_t fn_stamp = 0;
 };
 
-// A set of model nodes (PMX_MAX_MODEL_NODES bits).
-struct NodeSet {
-    static constexpr int W = PMX_MAX_MODEL_NODES / 64;
-    uint64_t w[W] = {};
-    bool any() const { for (int i = 0; i < W; ++i) if (w[i]) return true; return false; }
-    int count() const { int c = 0; for (int i = 0; i < W; ++i) c += __builtin_popcountll(w[i]); return c; }
-    void set(int m) { w[m >> 6] |= 1ull << (m & 63); }
-    bool operator==(const NodeSet &o) const { return std::memcmp(w, o.w, sizeof(w)) == 0; }
-    NodeSet operator&(const NodeSet &o) const { NodeSet r; for (int i = 0; i < W; ++i) r.w[i] = w[i] & o.w[i]; return r; }
-    std::vector<int> list() const { // ascending
-        std::vector<int> v;
-        for (int i = 0; i < W; ++i)
-            for (uint64_t x = w[i]; x; x &= x - 1) v.push_back(i * 64 + __builtin_ctzll(x));
-        return v;
-    }
-};
-
-// Largest float T with fl(T / std) < 2 under round-to-nearest-even float32 division: the quotient
-// rounds below 2 exactly when T / std < 2 - 2^-24, and std * (2 - 2^-24) is exact in double.
-static float pass_threshold(float std) {
-    const double bound = (double)std * (2.0 - std::ldexp(1.0, -24));
-    float t = (float)bound;
-    if ((double)t >= bound) t = std::nextafterf(t, -INFINITY);
-    return t;
-}
-
-
-// ---------------------------------------------------------------------------- pair functions: subsets and pass windows
-// The floats d >= 0 with |fl(d - mean)| <= T, i.e. abs((d - mean) / std) < 2 in the reference's float32 arithmetic
-// (match_utils.py:55-57; T = pass_threshold(std)). fl(d - mean) is monotonic in d, so the set is an interval of floats;
-// its ends are found by bisection on the bit patterns (non-negative floats order like their bits).
-static bool edge_window(float mean, float T, float &lo, float &hi) {
-    auto f32 = [](uint32_t b) { float f; std::memcpy(&f, &b, 4); return f; };
-    auto ge = [&](uint32_t b) { volatile float x = f32(b) - mean; return x >= -T; };
-    auto le = [&](uint32_t b) { volatile float x = f32(b) - mean; return x <= T; };
-    const uint32_t top = 0x7f7fffffu;
-    if (!le(0u) || !ge(top)) return false;
-    uint32_t a = 0, b = top; // smallest b with ge
-    if (ge(0u)) b = 0;
-    else {
-        while (b - a > 1) {
-            const uint32_t m = a + (b - a) / 2;
-            if (ge(m)) b = m; else a = m;
-        }
-    }
-    const uint32_t lo_b = b;
-    a = 0, b = top; // largest a with le
-    if (le(top)) a = top;
-    else {
-        while (b - a > 1) {
-            const uint32_t m = a + (b - a) / 2;
-            if (le(m)) a = m; else b = m;
-        }
-    }
-    const uint32_t hi_b = a;
-    if (lo_b > hi_b) return false;
-    lo = f32(lo_b);
-    hi = f32(hi_b);
-    return true;
-}
-
-static int build_pair_functions(pmx_model *m, const pmx_model_desc *d, const std::vector<NodeSet> &cnodes, const NodeSet *tnodes) {
-    const int Nm = m->dm.Nm, K = m->dm.K;
-    // node subsets: (model cluster, ligand type mask) -> the cluster's nodes of those types (graph_match.py:148-150)
-    std::vector<NodeSet> subs(1);
-    std::vector<uint16_t> sidtab((size_t)std::max(K, 1) * 128, 0);
-    for (int a = 0; a < K; ++a)
-        for (int mask = 0; mask < 128; ++mask) {
-            const NodeSet nodes = cnodes[a] & tnodes[mask];
-            if (!nodes.any()) continue;
-            size_t id = 1;
-            for (; id < subs.size(); ++id)
-                if (subs[id] == nodes) break;
-            if (id == subs.size()) subs.push_back(nodes);
-            sidtab[(size_t)a * 128 + mask] = (uint16_t)id;
-        }
-    const uint32_t NS = (uint32_t)subs.size();
-    if (NS > 65535u) return fail(PMX_ERR_INVALID, "model has %u distinct node subsets (max 65535)", NS);
-    std::vector<std::vector<int>> sublist(NS);
-    std::vector<uint32_t> sub_off(NS + 1, 0);
-    std::vector<uint8_t> sub_nodes;
-    for (uint32_t s = 0; s < NS; ++s) {
-        sublist[s] = subs[s].list();
-        sub_off[s] = (uint32_t)sub_nodes.size();
-        for (int x : sublist[s]) sub_nodes.push_back((uint8_t)x);
-    }
-    sub_off[NS] = (uint32_t)sub_nodes.size();
-    if (sub_nodes.empty()) sub_nodes.push_back(0);
-    // grid: h = the largest power of two <= std_min / 4 (quintic Hermite error < 6e-8 of the peak, measured), range to mean + 7 std
-    float std_min = 1e30f, dmax = 1.f;
-    for (int i = 0; i < Nm * Nm; ++i) {
-        std_min = std::min(std_min, d->edge_std[i]);
-        dmax = std::max(dmax, d->edge_mean[i] + 7.0f * d->edge_std[i]);
-    }
-    if (Nm == 0) std_min = 1.f;
-    float h = 0.5f;
-    while (h > std_min / 4.f && h > 1.f / 64.f) h *= 0.5f;
-    const uint32_t ncell = (uint32_t)std::ceil((double)dmax / (double)h) + 1;
-    if (ncell > 16384 || (uint64_t)NS * NS * ncell * sizeof(FnCell) >= (4ull << 30)) // (the kernels address the table with 32-bit byte offsets)
-        return fail(PMX_ERR_INVALID, "pair-function tables of this model would take %llu cells x %u x %u subsets", (unsigned long long)ncell, NS, NS);
-    // exact pass window of every model edge
-    std::vector<float> wlo((size_t)Nm * Nm), whi((size_t)Nm * Nm);
-    std::vector<uint8_t> wok((size_t)Nm * Nm);
-    for (int i = 0; i < Nm * Nm; ++i) wok[i] = edge_window(d->edge_mean[i], pass_threshold(d->edge_std[i]), wlo[i], whi[i]) ? 1 : 0;
-    const float INF = INFINITY;
-    // a symmetric model (edge[m][n] == edge[n][m]: distances are) has F_(A,B) == F_(B,A): the pair (lo, hi) is stored once
-    const bool tri = m->dm.symmetric != 0;
-    const uint32_t NF = tri ? NS * (NS + 1) / 2 : NS * NS;
-    std::vector<float2> win((size_t)NF * ncell);
-    uint64_t n_complex = 0;
-    std::vector<std::pair<float, int>> ev;
-    std::vector<std::pair<float, float>> pass;
-    for (uint32_t sa = 0; sa < NS; ++sa)
-        for (uint32_t sb = 0; sb < NS; ++sb) {
-            if (tri && sb > sa) continue;
-            float2 *out = win.data() + (size_t)(tri ? sa * (sa + 1) / 2 + sb : sa * NS + sb) * ncell;
-            const std::vector<int> &A = sublist[sa], &B = sublist[sb];
-            if (A.empty() || B.empty()) { // no item: never a fail
-                for (uint32_t i = 0; i < ncell; ++i) out[i] = make_float2(-INF, INF);
-                continue;
-            }
-            const int mn = (int)(A.size() * B.size());
-            ev.clear();
-            for (const int am : A)
-                for (const int bm : B) {
-                    const int e = am * Nm + bm;
-                    if (!wok[e]) continue;
-                    ev.emplace_back(wlo[e], +1);
-                    ev.emplace_back(std::nextafterf(whi[e], INF), -1); // first float after the window
-                }
-            std::sort(ev.begin(), ev.end());
-            pass.clear();
-            int cnt = 0;
-            bool in = false;
-            float start = 0.f;
-            for (size_t i = 0; i < ev.size();) {
-                const float x = ev[i].first;
-                for (; i < ev.size() && ev[i].first == x; ++i) cnt += ev[i].second;
-                const bool ok = 2 * cnt >= mn; // num_pass >= num_match * 0.5 (match_utils.py:61)
-                if (ok && !in) { in = true; start = x; }
-                else if (!ok && in) { in = false; pass.emplace_back(start, std::nextafterf(x, -INF)); }
-            }
-            if (in) pass.emplace_back(start, INF);
-            for (uint32_t i = 0; i < ncell; ++i) {
-                const float x0 = (float)i * h, x1 = (i + 1 == ncell) ? INF : (float)(i + 1) * h;
-                int hits = 0;
-                float2 w = make_float2(INF, INF); // never passes (no distance is >= INF; written so that lo <= hi holds for every window: the device's median-of-three test)
-                for (const auto &pr : pass)
-                    if (pr.first < x1 && pr.second >= x0) {
-                        ++hits;
-                        w = make_float2(pr.first, pr.second);
-                    }
-                if (hits > 1) {
-                    w = make_float2(NAN, NAN);
-                    ++n_complex;
-                }
-                out[i] = w;
-            }
-        }
-    HIPCHECK(hipMalloc((void **)&m->sidtab, sidtab.size() * 2));
-    HIPCHECK(hipMalloc((void **)&m->sub_off, (size_t)(NS + 1) * 4));
-    HIPCHECK(hipMalloc((void **)&m->sub_nodes, sub_nodes.size()));
-    HIPCHECK(hipMalloc((void **)&m->win, win.size() * sizeof(float2)));
-    HIPCHECK(hipMemcpy(m->sidtab, sidtab.data(), sidtab.size() * 2, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(m->sub_off, sub_off.data(), (size_t)(NS + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(m->sub_nodes, sub_nodes.data(), sub_nodes.size(), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(m->win, win.data(), win.size() * sizeof(float2), hipMemcpyHostToDevice));
-    m->NS = NS;
-    m->NF = NF;
-    m->ncell = ncell;
-    m->h = h;
-    m->n_complex_cells = n_complex;
-    return PMX_OK;
-}
+static_assert(sizeof(F2) == sizeof(float2) && offsetof(F2, y) == offsetof(float2, y), "F2 is float2");
+static_assert(sizeof(F4) == sizeof(float4) && offsetof(F4, y) == offsetof(float4, y) && offsetof(F4, z) == offsetof(float4, z) && offsetof(F4, w) == offsetof(float4, w),
+              "F4 is float4");
+static_assert(sizeof(FnCell) == kFnCellBytes, "the size limit of build_model_tables");
 
 // Cells whose polynomial deviates from the function by more than this, relative to the function, are flagged (FnCell) and
 // evaluated term by term where a self entry meets them. 2e-7 is just above what the float32 coefficients themselves cost
@@ -295,11 +106,11 @@ static int pair_functions(pmx_model *m, const Weights &W, hipStream_t stream, Fn
     if (!hit) {
         if (m->fn.size() < 4) {
             FnEntry fresh; // (enters the cache only once its buffer and event exist)
-            HIPCHECK(hipMalloc((void **)&fresh.cells, (size_t)m->NF * m->ncell * sizeof(FnCell)));
+            PMX_HIPCHECK(hipMalloc((void **)&fresh.cells, (size_t)m->NF * m->ncell * sizeof(FnCell)));
             const hipError_t ee = hipEventCreateWithFlags(&fresh.ready, hipEventDisableTiming);
             if (ee != hipSuccess) {
                 (void)hipFree(fresh.cells);
-                return fail(PMX_ERR_HIP, "hipEventCreateWithFlags failed: %s", hipGetErrorString(ee));
+                return pmx_fail(PMX_ERR_HIP, "hipEventCreateWithFlags failed: %s", hipGetErrorString(ee));
             }
             m->fn.push_back(fresh);
             hit = &m->fn.back();
@@ -307,14 +118,14 @@ static int pair_functions(pmx_model *m, const Weights &W, hipStream_t stream, Fn
             hit = &m->fn[0];
             for (FnEntry &e : m->fn)
                 if (e.stamp < hit->stamp) hit = &e;
-            HIPCHECK(hipDeviceSynchronize());
+            PMX_HIPCHECK(hipDeviceSynchronize());
         }
         hit->W = W;
         fn_build_kernel<<<dim3(m->NF), dim3(128), 0, stream>>>(m->dm, W, m->sub_off, m->sub_nodes, m->NS, m->ncell, m->h, m->win, hit->cells, fn_rel_tol(), fn_max_exponent());
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipEventRecord(hit->ready, stream));
+        PMX_HIPCHECK(hipGetLastError());
+        PMX_HIPCHECK(hipEventRecord(hit->ready, stream));
     } else {
-        HIPCHECK(hipStreamWaitEvent(stream, hit->ready, 0));
+        PMX_HIPCHECK(hipStreamWaitEvent(stream, hit->ready, 0));
     }
     hit->stamp = ++m->fn_stamp;
     out->cells = hit->cells;
@@ -326,118 +137,54 @@ static int pair_functions(pmx_model *m, const Weights &W, hipStream_t stream, Fn
     return PMX_OK;
 }
 
+// The model's tables (build_model_tables), uploaded: one allocation of 16-byte aligned sections, one copy.
 extern "C" int pmx_model_create(const pmx_model_desc *d, int device, pmx_model **out) {
-    if (!d || !out) return fail(PMX_ERR_INVALID, "null argument");
-    const int Nm = d->n_nodes, K = d->n_clusters;
-    if (Nm < 0 || Nm > PMX_MAX_MODEL_NODES) return fail(PMX_ERR_INVALID, "model has %d nodes (max %d)", Nm, PMX_MAX_MODEL_NODES);
-    if (K < 0 || K > PMX_MAX_MODEL_CLUSTERS) return fail(PMX_ERR_INVALID, "model has %d clusters (max %d)", K, PMX_MAX_MODEL_CLUSTERS);
-    for (int i = 0; i < Nm; ++i)
-        if (d->node_type[i] >= PMX_NUM_TYPES) return fail(PMX_ERR_INVALID, "node %d has type id %d", i, d->node_type[i]);
-    HIPCHECK(hipSetDevice(device));
+    if (!d || !out) return pmx_fail(PMX_ERR_INVALID, "null argument");
+    ModelTables t;
+    const int rc = build_model_tables(d, &t);
+    if (rc != PMX_OK) return rc;
+    PMX_HIPCHECK(hipSetDevice(device));
 
-    const size_t n_edge = (size_t)Nm * Nm, n_pair = (size_t)K * K;
-    const size_t off_edge = 0;
-    const size_t off_type = off_edge + round16(n_edge * sizeof(float4));
-    const size_t off_tclus = off_type + PMX_MAX_MODEL_NODES;
-    const size_t off_cpair = off_tclus + 128 * 16;
-    const size_t off_cwin = off_cpair + round16(n_pair * sizeof(float2));
-    const size_t total = off_cwin + round16(n_pair * sizeof(float2)) + 16;
-    std::vector<unsigned char> host(total, 0);
-    float4 *edge = reinterpret_cast<float4 *>(host.data() + off_edge);
-    uint8_t *ntype = host.data() + off_type;
-    uint64_t *tclus = reinterpret_cast<uint64_t *>(host.data() + off_tclus); // [128][2]
-    std::vector<NodeSet> cnodes((size_t)std::max(K, 1));
-    NodeSet tnodes[128];
-    float2 *cpair = reinterpret_cast<float2 *>(host.data() + off_cpair);
-    float2 *cwin = reinterpret_cast<float2 *>(host.data() + off_cwin);
-
-    const double s_const = std::sqrt(0.5 * 1.4426950408889634074); // sqrt(0.5 * log2(e))
-    for (size_t i = 0; i < n_edge; ++i) {
-        const float mean = d->edge_mean[i], sd = d->edge_std[i];
-        if (!(sd > 0.f)) return fail(PMX_ERR_INVALID, "edge %zu has distance_std %g", i, (double)sd);
-        edge[i] = make_float4(mean, (float)(s_const / (double)sd), pass_threshold(sd), sd);
-    }
-    NodeSet type_nodes[PMX_NUM_TYPES];
-    for (int m = 0; m < Nm; ++m) {
-        ntype[m] = d->node_type[m];
-        type_nodes[d->node_type[m]].set(m);
-    }
-    const int NW = std::max(1, (Nm + 63) / 64); // words per cluster in cluster_nodes
-    for (int a = 0; a < K; ++a)
-        for (int m = 0; m < Nm; ++m)
-            if (d->cluster_nodes[(size_t)a * NW + (m >> 6)] >> (m & 63) & 1) cnodes[a].set(m);
-    for (int mask = 0; mask < 128; ++mask) {
-        NodeSet nodes;
-        uint64_t clus[2] = {0, 0};
-        for (int t = 0; t < PMX_NUM_TYPES; ++t)
-            if (mask >> t & 1)
-                for (int i = 0; i < NodeSet::W; ++i) nodes.w[i] |= type_nodes[t].w[i];
-        for (int a = 0; a < K; ++a)
-            if (d->cluster_typemask[a] & mask) clus[a >> 6] |= 1ull << (a & 63);
-        tnodes[mask] = nodes;
-        tclus[2 * mask] = clus[0];
-        tclus[2 * mask + 1] = clus[1];
-    }
-    for (int a = 0; a < K; ++a)
-        for (int b = 0; b < K; ++b) {
-            const double *ca = d->cluster_center + 3 * a, *cb = d->cluster_center + 3 * b;
-            const double dist = std::sqrt((ca[0] - cb[0]) * (ca[0] - cb[0]) + (ca[1] - cb[1]) * (ca[1] - cb[1]) +
-                                          (ca[2] - cb[2]) * (ca[2] - cb[2])); // graph_match.py:263-264
-            cpair[a * K + b] = make_float2((float)dist, (float)(d->cluster_size[a] + d->cluster_size[b])); // :265
-        }
-    // hull of the exact 2-sigma windows of a cluster pair's node pairs (the dead-entry test of build_tables)
-    {
-        std::vector<float> wlo(n_edge), whi(n_edge);
-        std::vector<uint8_t> wok(n_edge);
-        for (size_t i = 0; i < n_edge; ++i) wok[i] = edge_window(d->edge_mean[i], pass_threshold(d->edge_std[i]), wlo[i], whi[i]) ? 1 : 0;
-        for (int a = 0; a < K; ++a)
-            for (int b = 0; b < K; ++b) {
-                float lo = INFINITY, hi = -INFINITY;
-                for (const int am : cnodes[a].list())
-                    for (const int bm : cnodes[b].list()) {
-                        const size_t e = (size_t)am * Nm + bm;
-                        if (!wok[e]) continue;
-                        lo = std::min(lo, wlo[e]);
-                        hi = std::max(hi, whi[e]);
-                    }
-                cwin[a * K + b] = make_float2(lo, hi);
-            }
-    }
+    std::vector<unsigned char> host;
+    auto section = [&host](const auto &v) { // appends a table, returns its offset
+        const size_t off = host.size(), bytes = v.size() * sizeof(v[0]);
+        host.resize(off + round16(bytes), 0);
+        if (bytes) std::memcpy(host.data() + off, v.data(), bytes);
+        return off;
+    };
+    const size_t off_edge = section(t.edge), off_type = section(t.node_type), off_tclus = section(t.tclus), off_cpair = section(t.cpair), off_cwin = section(t.cwin);
+    const size_t off_sidtab = section(t.sidtab), off_sub_off = section(t.sub_off), off_sub_nodes = section(t.sub_nodes), off_win = section(t.win);
+    host.resize(host.size() + 16, 0);
 
     void *blob = nullptr;
-    HIPCHECK(hipMalloc(&blob, total));
-    hipError_t e = hipMemcpy(blob, host.data(), total, hipMemcpyHostToDevice);
+    PMX_HIPCHECK(hipMalloc(&blob, host.size()));
+    const hipError_t e = hipMemcpy(blob, host.data(), host.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         (void)hipFree(blob);
-        return fail(PMX_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
+        return pmx_fail(PMX_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
     }
+    const unsigned char *b8 = static_cast<const unsigned char *>(blob);
     pmx_model *m = new pmx_model();
     m->device = device;
     m->blob = blob;
-    std::memcpy(m->node_type, ntype, sizeof(m->node_type));
-    unsigned char *b8 = static_cast<unsigned char *>(blob);
-    m->dm.Nm = Nm;
-    m->dm.K = K;
-    m->dm.symmetric = 1;
-    for (int a = 0; a < Nm && m->dm.symmetric; ++a)
-        for (int b = 0; b < a; ++b)
-            if (std::memcmp(&d->edge_mean[a * Nm + b], &d->edge_mean[b * Nm + a], 4) || std::memcmp(&d->edge_std[a * Nm + b], &d->edge_std[b * Nm + a], 4)) {
-                m->dm.symmetric = 0;
-                break;
-            }
+    std::memcpy(m->node_type, t.node_type.data(), sizeof(m->node_type));
+    m->dm.Nm = t.Nm;
+    m->dm.K = t.K;
+    m->dm.symmetric = t.symmetric;
     m->dm.pad_ = 0;
     m->dm.edge = reinterpret_cast<const float4 *>(b8 + off_edge);
     m->dm.node_type = b8 + off_type;
     m->dm.tclus = reinterpret_cast<const uint64_t *>(b8 + off_tclus);
     m->dm.cpair = reinterpret_cast<const float2 *>(b8 + off_cpair);
     m->dm.cwin = reinterpret_cast<const float2 *>(b8 + off_cwin);
-    {
-        const int rc = build_pair_functions(m, d, cnodes, tnodes);
-        if (rc != PMX_OK) {
-            pmx_model_destroy(m);
-            return rc;
-        }
-    }
+    m->NS = t.NS;
+    m->NF = t.NF;
+    m->ncell = t.ncell;
+    m->h = t.h;
+    m->sidtab = reinterpret_cast<const uint16_t *>(b8 + off_sidtab);
+    m->sub_off = reinterpret_cast<const uint32_t *>(b8 + off_sub_off);
+    m->sub_nodes = b8 + off_sub_nodes;
+    m->win = reinterpret_cast<const float2 *>(b8 + off_win);
     *out = m;
     return PMX_OK;
 }
@@ -446,10 +193,6 @@ extern "C" int pmx_model_destroy(pmx_model *m) {
     if (!m) return PMX_OK;
     (void)hipSetDevice(m->device);
     (void)hipFree(m->blob);
-    if (m->sidtab) (void)hipFree(m->sidtab);
-    if (m->sub_off) (void)hipFree(m->sub_off);
-    if (m->sub_nodes) (void)hipFree(m->sub_nodes);
-    if (m->win) (void)hipFree(m->win);
     for (FnEntry &e : m->fn) {
         if (e.cells) (void)hipFree(e.cells);
         if (e.ready) (void)hipEventDestroy(e.ready);
@@ -469,19 +212,19 @@ struct pmx_library {
 };
 
 extern "C" int pmx_library_upload(const pmx_library_view *v, int device, pmx_library **out) {
-    if (!v || !out) return fail(PMX_ERR_INVALID, "null argument");
-    if (!v->offsets) return fail(PMX_ERR_INVALID, "null offsets");
-    HIPCHECK(hipSetDevice(device));
+    if (!v || !out) return pmx_fail(PMX_ERR_INVALID, "null argument");
+    if (!v->offsets) return pmx_fail(PMX_ERR_INVALID, "null offsets");
+    PMX_HIPCHECK(hipSetDevice(device));
     const uint64_t n = v->n_ligands;
     const hipMemcpyKind kind = v->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     uint64_t nbytes = 0;
     if (v->on_device) {
-        HIPCHECK(hipMemcpy(&nbytes, v->offsets + n, 8, hipMemcpyDeviceToHost));
+        PMX_HIPCHECK(hipMemcpy(&nbytes, v->offsets + n, 8, hipMemcpyDeviceToHost));
     } else {
         nbytes = v->offsets[n];
     }
     const bool adopt = v->on_device == 2;
-    if (adopt && !v->data) return fail(PMX_ERR_INVALID, "null data");
+    if (adopt && !v->data) return pmx_fail(PMX_ERR_INVALID, "null data");
     pmx_library *lib = new pmx_library();
     lib->device = device;
     lib->offsets = nullptr;
@@ -521,12 +264,12 @@ extern "C" int pmx_library_upload(const pmx_library_view *v, int device, pmx_lib
         if (lib->owns && lib->offsets) (void)hipFree(lib->offsets);
         if (lib->owns && lib->data) (void)hipFree(lib->data);
         delete lib;
-        return fail(e == hipErrorOutOfMemory ? PMX_ERR_OOM : PMX_ERR_HIP, "library upload failed: %s", hipGetErrorString(e));
+        return pmx_fail(e == hipErrorOutOfMemory ? PMX_ERR_OOM : PMX_ERR_HIP, "library upload failed: %s", hipGetErrorString(e));
     }
     if (stats[5]) { // offsets are validated on the device, for host and device views alike
         if (lib->owns) (void)hipFree(lib->offsets), (void)hipFree(lib->data);
         delete lib;
-        return fail(PMX_ERR_INVALID, "%llu record offsets are not 16-byte aligned, run backwards or point past the data", stats[5]);
+        return pmx_fail(PMX_ERR_INVALID, "%llu record offsets are not 16-byte aligned, run backwards or point past the data", stats[5]);
     }
     lib->info.n_ligands = n;
     lib->info.n_bytes = nbytes;
@@ -540,13 +283,13 @@ extern "C" int pmx_library_upload(const pmx_library_view *v, int device, pmx_lib
 }
 
 extern "C" int pmx_library_info_get(const pmx_library *lib, pmx_library_info *info) {
-    if (!lib || !info) return fail(PMX_ERR_INVALID, "null argument");
+    if (!lib || !info) return pmx_fail(PMX_ERR_INVALID, "null argument");
     *info = lib->info;
     return PMX_OK;
 }
 
 extern "C" int pmx_library_buffers(const pmx_library *lib, const uint64_t **offsets_dev, const uint8_t **data_dev) {
-    if (!lib || !offsets_dev || !data_dev) return fail(PMX_ERR_INVALID, "null argument");
+    if (!lib || !offsets_dev || !data_dev) return pmx_fail(PMX_ERR_INVALID, "null argument");
     *offsets_dev = lib->offsets;
     *data_dev = lib->data;
     return PMX_OK;
@@ -675,10 +418,10 @@ struct BufferNeeds {
 };
 
 static int grow_buffers(ScreenWs &ws, const BufferNeeds &need, hipStream_t stream) {
-    HIPCHECK(ws.slices.grow(need.slices, stream));
-    HIPCHECK(ws.big.grow(need.big, stream));
-    HIPCHECK(ws.totbuf.grow(need.totbuf, stream));
-    HIPCHECK(ws.pabuf.grow(need.pabuf, stream));
+    PMX_HIPCHECK(ws.slices.grow(need.slices, stream));
+    PMX_HIPCHECK(ws.big.grow(need.big, stream));
+    PMX_HIPCHECK(ws.totbuf.grow(need.totbuf, stream));
+    PMX_HIPCHECK(ws.pabuf.grow(need.pabuf, stream));
     return PMX_OK;
 }
 
@@ -705,7 +448,7 @@ static int ensure_arena(ScreenWs &ws, hipStream_t stream) {
     }
     const size_t arena_min = std::min<size_t>((size_t)1 << 30, arena_want);
     if (ws.arena_shrunk_to) arena_want = std::min(arena_want, std::max(ws.arena_shrunk_to, arena_min));
-    HIPCHECK(ws.arena.grow(arena_want, stream, arena_min));
+    PMX_HIPCHECK(ws.arena.grow(arena_want, stream, arena_min));
     if (ws.arena.bytes < arena_want) ws.arena_shrunk_to = ws.arena.bytes;
     return PMX_OK;
 }
@@ -725,9 +468,9 @@ static int init_workspace(ScreenWs &ws, int device, hipStream_t stream) {
     if (ws.num_cu) return PMX_OK;
     auto init = [&]() -> int {
         hipDeviceProp_t prop;
-        HIPCHECK(hipGetDeviceProperties(&prop, device));
-        for (auto &e : ws.ev) HIPCHECK(hipEventCreate(&e));
-        HIPCHECK(ws.ctl.grow(sizeof(Ctl), stream));
+        PMX_HIPCHECK(hipGetDeviceProperties(&prop, device));
+        for (auto &e : ws.ev) PMX_HIPCHECK(hipEventCreate(&e));
+        PMX_HIPCHECK(ws.ctl.grow(sizeof(Ctl), stream));
         ws.num_cu = prop.multiProcessorCount;
         return PMX_OK;
     };
@@ -829,7 +572,7 @@ static int plan_pocket(const pmx_model *model, const pmx_library *lib, const Wei
 template <int G>
 static int score_screen(const pmx_model *const *models, int n_models, const pmx_library *lib, const Weights &W, uint64_t first, uint64_t count,
                         void *scores_dev, bool scores_f64, int32_t *status_dev, hipStream_t stream, ScreenWs &ws) {
-    if (count > 0xfffffff0ull) return fail(PMX_ERR_INVALID, "more than 2^32 ligands in one call");
+    if (count > 0xfffffff0ull) return pmx_fail(PMX_ERR_INVALID, "more than 2^32 ligands in one call");
     // ---- knobs
     const uint32_t flags = (uint32_t)env_long("PMX_TREE_FLAGS", 0);
     // [MI355X] round 6, passes a walk may take before it splits. On the bench library (92 passes per ligand, 7 % of the walks over 384) 384 / 384
@@ -874,15 +617,15 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
         int rc = grow_buffers(ws, need, stream);
         if (!rc) rc = ensure_arena<G>(ws, stream);
         if (rc) return rc;
-        HIPCHECK(ws.queue.grow((size_t)std::max<long>(1, env_long("PMX_TASKQ_MB", (G >= 32 ? 1024L : 2048L) * std::max(1, G / 8))) << 20, stream));
-        HIPCHECK(ws.lists.grow((size_t)super_max * 12, stream));
+        PMX_HIPCHECK(ws.queue.grow((size_t)std::max<long>(1, env_long("PMX_TASKQ_MB", (G >= 32 ? 1024L : 2048L) * std::max(1, G / 8))) << 20, stream));
+        PMX_HIPCHECK(ws.lists.grow((size_t)super_max * 12, stream));
     }
     Ctl *const ctl = ws.ctl.as<Ctl>();
     uint32_t *const lists = ws.lists.as<uint32_t>();
     uint8_t *const totbuf = ws.totbuf.as<uint8_t>(), *const pabuf = ws.pabuf.as<uint8_t>();
 
     // ---- pockets and their chunks
-    if (g_profiling) HIPCHECK(hipEventRecord(ws.ev[0], stream));
+    if (g_profiling) PMX_HIPCHECK(hipEventRecord(ws.ev[0], stream));
     ws.ctl_used = false;
     for (int m = 0; m < n_models; ++m) {
         const PocketPlan &pl = plan[(size_t)m];
@@ -930,7 +673,7 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
             const bool last_of_call = m + 1 == n_models && lo + super >= count;
             p.lo = (uint32_t)lo;
             p.hi = (uint32_t)std::min<uint64_t>(count, lo + super);
-            if (g_profiling && last_of_call) HIPCHECK(hipEventRecord(ws.ev[1], stream));
+            if (g_profiling && last_of_call) PMX_HIPCHECK(hipEventRecord(ws.ev[1], stream));
             ws.ligands_last = p.hi - p.lo;
             ctl_clear_kernel<<<dim3((sizeof(Ctl) / 4 + 255) / 256), dim3(256), 0, stream>>>(ctl, ws.ctl_used ? 0 : 1);
             ws.ctl_used = true;
@@ -948,8 +691,8 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
             p.retry_slot = 0;
             launch(2, std::min(pl.big_grid, lig_grid));
             if (g_profiling && last_of_call) {
-                HIPCHECK(hipEventRecord(ws.ev[2], stream));
-                HIPCHECK(hipEventRecord(ws.ev[4], stream));
+                PMX_HIPCHECK(hipEventRecord(ws.ev[2], stream));
+                PMX_HIPCHECK(hipEventRecord(ws.ev[4], stream));
             }
             rounds_and_finalize();
             // Ligands the arena pass had no room for, with the arena to themselves (only models and libraries whose largest tables
@@ -960,12 +703,12 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
                 rounds_and_finalize();
             }
             p.retry_in = nullptr;
-            if (g_profiling && last_of_call) HIPCHECK(hipEventRecord(ws.ev[5], stream));
+            if (g_profiling && last_of_call) PMX_HIPCHECK(hipEventRecord(ws.ev[5], stream));
         }
     }
-    HIPCHECK(hipGetLastError());
-    if (!debug_ok) return fail(PMX_ERR_INVALID, "the validation kernels (pmx_screen_debug.hip) do not match this build's parameter block");
-    if (g_profiling) HIPCHECK(hipEventRecord(ws.ev[3], stream));
+    PMX_HIPCHECK(hipGetLastError());
+    if (!debug_ok) return pmx_fail(PMX_ERR_INVALID, "the validation kernels (pmx_screen_debug.hip) do not match this build's parameter block");
+    if (g_profiling) PMX_HIPCHECK(hipEventRecord(ws.ev[3], stream));
     ws.ev_valid = g_profiling != 0;
     ws.last_stream = stream;
     return PMX_OK;
@@ -977,13 +720,13 @@ static int screen_stats(pmx_score_stats *out) {
     if (!w) return PMX_OK;
     std::lock_guard<std::mutex> lock(w->mu);
     if (w->released || !w->num_cu) return PMX_OK; // (the workspace was released after the call: its counters went with it)
-    HIPCHECK(hipSetDevice(g_last_device));
-    HIPCHECK(hipStreamSynchronize(w->last_stream));
+    PMX_HIPCHECK(hipSetDevice(g_last_device));
+    PMX_HIPCHECK(hipStreamSynchronize(w->last_stream));
     unsigned long long st[kStatWords] = {0};
     std::vector<unsigned char> host(sizeof(Ctl));
     *out = pmx_score_stats{};
     if (w->ctl_used) {
-        HIPCHECK(hipMemcpy(host.data(), w->ctl.ptr, sizeof(Ctl), hipMemcpyDeviceToHost));
+        PMX_HIPCHECK(hipMemcpy(host.data(), w->ctl.ptr, sizeof(Ctl), hipMemcpyDeviceToHost));
         const Ctl *c = reinterpret_cast<const Ctl *>(host.data());
         for (int sh = 0; sh < kScreenStatShards; ++sh)
             for (int i = 0; i < kStatWords; ++i) st[i] = (i == 5) ? std::max(st[i], c->stats[sh][i]) : st[i] + c->stats[sh][i];
@@ -1011,11 +754,11 @@ static int screen_stats(pmx_score_stats *out) {
     out->ligands_last = w->ligands_last;
     if (w->ev_valid) {
         float ms = 0.f;
-        HIPCHECK(hipEventElapsedTime(&ms, w->ev[0], w->ev[3]));
+        PMX_HIPCHECK(hipEventElapsedTime(&ms, w->ev[0], w->ev[3]));
         out->ms_total = ms;
-        HIPCHECK(hipEventElapsedTime(&ms, w->ev[1], w->ev[2]));
+        PMX_HIPCHECK(hipEventElapsedTime(&ms, w->ev[1], w->ev[2]));
         out->ms_ligand = ms;
-        HIPCHECK(hipEventElapsedTime(&ms, w->ev[4], w->ev[5]));
+        PMX_HIPCHECK(hipEventElapsedTime(&ms, w->ev[4], w->ev[5]));
         out->ms_tasks = ms;
     }
     return PMX_OK;
@@ -1049,22 +792,22 @@ static HeldWs hold_screen(int device, hipStream_t stream) {
 
 static int score_any(const pmx_model *const *models, int n_models, const pmx_library *lib, const float weights[PMX_NUM_TYPES], uint64_t first,
                      uint64_t count, void *scores_dev, bool scores_f64, int32_t *status_dev, void *stream_) {
-    if (!models || n_models < 0 || !lib || !weights || (!scores_dev && count && n_models)) return fail(PMX_ERR_INVALID, "null argument");
+    if (!models || n_models < 0 || !lib || !weights || (!scores_dev && count && n_models)) return pmx_fail(PMX_ERR_INVALID, "null argument");
     for (int i = 0; i < n_models; ++i) {
-        if (!models[i]) return fail(PMX_ERR_INVALID, "null model");
-        if (models[i]->device != lib->device) return fail(PMX_ERR_INVALID, "model and library live on different devices");
+        if (!models[i]) return pmx_fail(PMX_ERR_INVALID, "null model");
+        if (models[i]->device != lib->device) return pmx_fail(PMX_ERR_INVALID, "model and library live on different devices");
     }
-    if (first > lib->info.n_ligands || count > lib->info.n_ligands - first) return fail(PMX_ERR_INVALID, "ligand range out of bounds");
+    if (first > lib->info.n_ligands || count > lib->info.n_ligands - first) return pmx_fail(PMX_ERR_INVALID, "ligand range out of bounds");
     g_stats = pmx_score_stats{};
     g_last_screen.reset();
     if (count == 0 || n_models == 0) return PMX_OK;
-    HIPCHECK(hipSetDevice(lib->device));
+    PMX_HIPCHECK(hipSetDevice(lib->device));
     const Weights W = to_weights(weights);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const HeldWs held = hold_screen(lib->device, stream);
     int rc = PMX_OK;
     if (!with_lanes(lanes_of(lib), [&](auto g) { rc = score_screen<decltype(g)::value>(models, n_models, lib, W, first, count, scores_dev, scores_f64, status_dev, stream, *held.ws); }))
-        rc = fail(PMX_ERR_INVALID, "no kernels for %d conformer lanes", lanes_of(lib));
+        rc = pmx_fail(PMX_ERR_INVALID, "no kernels for %d conformer lanes", lanes_of(lib));
     g_last_screen = held.ws;
     g_last_device = lib->device;
     return rc;
@@ -1078,7 +821,7 @@ extern "C" int pmx_score_multi(const pmx_model *const *models, int n_models, con
 
 extern "C" int pmx_score(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], uint64_t first,
                          uint64_t count, float *scores_dev, int32_t *status_dev, void *stream) {
-    if (!model) return fail(PMX_ERR_INVALID, "null argument");
+    if (!model) return pmx_fail(PMX_ERR_INVALID, "null argument");
     return score_any(&model, 1, lib, weights, first, count, scores_dev, false, status_dev, stream);
 }
 
@@ -1091,7 +834,7 @@ extern "C" int pmx_score_multi_f64(const pmx_model *const *models, int n_models,
 
 extern "C" int pmx_score_f64(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], uint64_t first,
                              uint64_t count, double *scores_dev, int32_t *status_dev, void *stream) {
-    if (!model) return fail(PMX_ERR_INVALID, "null argument");
+    if (!model) return pmx_fail(PMX_ERR_INVALID, "null argument");
     return score_any(&model, 1, lib, weights, first, count, scores_dev, true, status_dev, stream);
 }
 
@@ -1099,12 +842,9 @@ extern "C" int pmx_score_f64(const pmx_model *model, const pmx_library *lib, con
 // Frees the cached scoring workspaces of `device` (table arenas, task queues, class lists, fused-engine buffers): they are
 // grown on demand and kept between calls, which is what a screening loop wants and what a long-lived host program that
 // is done screening does not.
-int pmx_topk_release(int device);
-int pmx_pack_release(int device);
-int pmx_select_release(int device);
 extern "C" int pmx_release_workspaces(int device) {
-    HIPCHECK(hipSetDevice(device));
-    HIPCHECK(hipDeviceSynchronize());
+    PMX_HIPCHECK(hipSetDevice(device));
+    PMX_HIPCHECK(hipDeviceSynchronize());
     std::vector<std::shared_ptr<ScreenWs>> taken;
     {
         std::lock_guard<std::mutex> lock(g_mu);
@@ -1119,7 +859,7 @@ extern "C" int pmx_release_workspaces(int device) {
     }
     for (auto &w : taken) {
         std::lock_guard<std::mutex> wl(w->mu); // a call that is enqueuing on this workspace finishes first
-        HIPCHECK(hipDeviceSynchronize());       // ... and what it enqueued
+        PMX_HIPCHECK(hipDeviceSynchronize());       // ... and what it enqueued
         w->free_buffers();
         w->released = true;
     }
@@ -1127,9 +867,6 @@ extern "C" int pmx_release_workspaces(int device) {
     if (!rc) rc = pmx_pack_release(device);
     return rc ? rc : pmx_select_release(device);
 }
-
-// error hook for pmx_topk.hip (keeps the thread-local message in one translation unit)
-int pmx_topk_fail(int code, const char *msg) { return fail(code, "%s", msg); }
 
 // ------------------------------------------------------------------------------------ explain (pmx_explain.hip)
 // The listed ligands' tables are built as pmx_score builds them - per-wave slices, then large slices, then the arena with its
@@ -1145,8 +882,8 @@ static int explain_screen(const pmx_model *model, const pmx_library *lib, const 
     if (!rc) rc = grow_buffers(ws, pl.need, stream);
     if (!rc && !ws.arena.ptr) rc = ensure_arena<G>(ws, stream); // (an arena made by pmx_score is taken as it is)
     if (rc) return rc;
-    HIPCHECK(ws.lists.grow((size_t)a.n * 12, stream));
-    HIPCHECK(ws.xctl.grow(sizeof(Ctl), stream));
+    PMX_HIPCHECK(ws.lists.grow((size_t)a.n * 12, stream));
+    PMX_HIPCHECK(ws.xctl.grow(sizeof(Ctl), stream));
     Ctl *const xctl = ws.xctl.as<Ctl>();
     uint32_t *const lists = ws.lists.as<uint32_t>();
     ScreenParams &p = pl.p;
@@ -1183,8 +920,8 @@ static int explain_screen(const pmx_model *model, const pmx_library *lib, const 
         launch(3, std::min(pl.big_grid, full));
     }
     pmx_xpl::launch_fixup(a, stream);
-    HIPCHECK(hipGetLastError());
-    if (!ok) return fail(PMX_ERR_INVALID, "the explain kernels (pmx_explain.hip) do not match this build's parameter block");
+    PMX_HIPCHECK(hipGetLastError());
+    if (!ok) return pmx_fail(PMX_ERR_INVALID, "the explain kernels (pmx_explain.hip) do not match this build's parameter block");
     return PMX_OK;
 }
 
@@ -1193,7 +930,7 @@ static int explain_screen(const pmx_model *model, const pmx_library *lib, const 
 static int explain_call(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const pmx_match_constraint *constraint,
                         int n_modes, const uint64_t *ligands_dev, uint32_t n, double *conf_max_dev, uint8_t *match_dev, uint8_t *levels_dev, int32_t *best_conformer_dev,
                         int32_t *status_dev, void *stream_) {
-    if (!model || !lib || !weights) return fail(PMX_ERR_INVALID, "null argument");
+    if (!model || !lib || !weights) return pmx_fail(PMX_ERR_INVALID, "null argument");
     pmx_match_constraint con;
     std::memset(&con, 0, sizeof con);
     if (constraint) {
@@ -1203,24 +940,24 @@ static int explain_call(const pmx_model *model, const pmx_library *lib, const fl
             return ((w[0] & ~m0) | (w[1] & ~m1)) != 0ull;
         };
         if (constraint->n_require < 0 || constraint->n_require > PMX_MAX_REQUIRE_GROUPS)
-            return fail(PMX_ERR_INVALID, "constraint: %d require groups (0 to %d)", (int)constraint->n_require, PMX_MAX_REQUIRE_GROUPS);
+            return pmx_fail(PMX_ERR_INVALID, "constraint: %d require groups (0 to %d)", (int)constraint->n_require, PMX_MAX_REQUIRE_GROUPS);
         con.n_require = constraint->n_require;
         for (int g = 0; g < con.n_require; ++g) {
-            if ((constraint->require[g][0] | constraint->require[g][1]) == 0ull) return fail(PMX_ERR_INVALID, "constraint: require group %d is empty", g);
-            if (beyond(constraint->require[g])) return fail(PMX_ERR_INVALID, "constraint: require group %d names a cluster outside the model's %d", g, K);
+            if ((constraint->require[g][0] | constraint->require[g][1]) == 0ull) return pmx_fail(PMX_ERR_INVALID, "constraint: require group %d is empty", g);
+            if (beyond(constraint->require[g])) return pmx_fail(PMX_ERR_INVALID, "constraint: require group %d names a cluster outside the model's %d", g, K);
             con.require[g][0] = constraint->require[g][0];
             con.require[g][1] = constraint->require[g][1];
         }
-        if (beyond(constraint->exclude)) return fail(PMX_ERR_INVALID, "constraint: the exclude set names a cluster outside the model's %d", K);
+        if (beyond(constraint->exclude)) return pmx_fail(PMX_ERR_INVALID, "constraint: the exclude set names a cluster outside the model's %d", K);
         con.exclude[0] = constraint->exclude[0];
         con.exclude[1] = constraint->exclude[1];
     }
-    if (n > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "more than %d ligands in one explain call", PMX_EXPLAIN_MAX);
-    if ((uint64_t)n * (uint64_t)n_modes > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "%u ligands x %d modes: more than %d in one call", n, n_modes, PMX_EXPLAIN_MAX);
+    if (n > PMX_EXPLAIN_MAX) return pmx_fail(PMX_ERR_INVALID, "more than %d ligands in one explain call", PMX_EXPLAIN_MAX);
+    if ((uint64_t)n * (uint64_t)n_modes > PMX_EXPLAIN_MAX) return pmx_fail(PMX_ERR_INVALID, "%u ligands x %d modes: more than %d in one call", n, n_modes, PMX_EXPLAIN_MAX);
     if (n == 0) return PMX_OK;
-    if (!ligands_dev || !conf_max_dev || !match_dev || !levels_dev || !best_conformer_dev || !status_dev) return fail(PMX_ERR_INVALID, "null argument");
-    if (model->device != lib->device) return fail(PMX_ERR_INVALID, "model and library live on different devices");
-    HIPCHECK(hipSetDevice(lib->device));
+    if (!ligands_dev || !conf_max_dev || !match_dev || !levels_dev || !best_conformer_dev || !status_dev) return pmx_fail(PMX_ERR_INVALID, "null argument");
+    if (model->device != lib->device) return pmx_fail(PMX_ERR_INVALID, "model and library live on different devices");
+    PMX_HIPCHECK(hipSetDevice(lib->device));
     const Weights W = to_weights(weights);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const pmx_xpl::Args a{ligands_dev, n, (uint32_t)n_modes, conf_max_dev, match_dev, levels_dev, best_conformer_dev, status_dev, con};
@@ -1228,7 +965,7 @@ static int explain_call(const pmx_model *model, const pmx_library *lib, const fl
     const HeldWs held = hold_screen(lib->device, stream);
     int rc = PMX_OK;
     if (!with_lanes(lanes_of(lib), [&](auto g) { rc = explain_screen<decltype(g)::value>(model, lib, W, a, constrained, stream, *held.ws); }))
-        rc = fail(PMX_ERR_INVALID, "no kernels for %d conformer lanes", lanes_of(lib));
+        rc = pmx_fail(PMX_ERR_INVALID, "no kernels for %d conformer lanes", lanes_of(lib));
     return rc;
 }
 
@@ -1246,7 +983,7 @@ extern "C" int pmx_explain_constrained(const pmx_model *model, const pmx_library
 extern "C" int pmx_explain_modes(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const pmx_match_constraint *constraint,
                                  int n_modes, const uint64_t *ligands_dev, uint32_t n, double *mode_max_dev, uint8_t *mode_match_dev, uint8_t *levels_dev,
                                  int32_t *best_conformer_dev, int32_t *status_dev, void *stream) {
-    if (n_modes < 1 || n_modes > PMX_MAX_MODES) return fail(PMX_ERR_INVALID, "%d modes (1 to %d)", n_modes, PMX_MAX_MODES);
+    if (n_modes < 1 || n_modes > PMX_MAX_MODES) return pmx_fail(PMX_ERR_INVALID, "%d modes (1 to %d)", n_modes, PMX_MAX_MODES);
     return explain_call(model, lib, weights, constraint, n_modes, ligands_dev, n, mode_max_dev, mode_match_dev, levels_dev, best_conformer_dev, status_dev, stream);
 }
 
@@ -1257,18 +994,18 @@ extern "C" int pmx_explain_modes(const pmx_model *model, const pmx_library *lib,
 template <class Launch>
 static int row_call(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], uint32_t n, const char *what, bool null_out,
                     pmx_rows::Kind kind, hipStream_t stream, Launch launch) {
-    if (!model || !lib || !weights) return fail(PMX_ERR_INVALID, "null argument");
-    if (n > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "more than %d rows in one %s call", PMX_EXPLAIN_MAX, what);
+    if (!model || !lib || !weights) return pmx_fail(PMX_ERR_INVALID, "null argument");
+    if (n > PMX_EXPLAIN_MAX) return pmx_fail(PMX_ERR_INVALID, "more than %d rows in one %s call", PMX_EXPLAIN_MAX, what);
     if (n == 0) return PMX_OK;
-    if (null_out) return fail(PMX_ERR_INVALID, "null argument");
-    if (model->device != lib->device) return fail(PMX_ERR_INVALID, "model and library live on different devices");
-    HIPCHECK(hipSetDevice(lib->device));
+    if (null_out) return pmx_fail(PMX_ERR_INVALID, "null argument");
+    if (model->device != lib->device) return pmx_fail(PMX_ERR_INVALID, "model and library live on different devices");
+    PMX_HIPCHECK(hipSetDevice(lib->device));
     const HeldWs held = hold_screen(lib->device, stream);
     ScreenWs &ws = *held.ws;
     const int rc = init_workspace(ws, lib->device, stream);
     if (rc) return rc;
-    HIPCHECK(ws.acur.grow(256, stream));
-    HIPCHECK(hipMemsetAsync(ws.acur.ptr, 0, 4, stream));
+    PMX_HIPCHECK(ws.acur.grow(256, stream));
+    PMX_HIPCHECK(hipMemsetAsync(ws.acur.ptr, 0, 4, stream));
     ScreenParams p{};
     p.M = model->dm;
     p.lib = lib->dl;
@@ -1278,8 +1015,8 @@ static int row_call(const pmx_model *model, const pmx_library *lib, const float 
     p.W = to_weights(weights);
     const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(kLdsPerCu / pmx_rows::lds_bytes(kind), 8));
     const unsigned blocks = std::min<unsigned>(n, (unsigned)ws.num_cu * per_cu);
-    if (!launch(blocks, p, ws.acur.as<uint32_t>())) return fail(PMX_ERR_INVALID, "the %s kernel (pmx_rows.hip) does not match this build's parameter block", what);
-    HIPCHECK(hipGetLastError());
+    if (!launch(blocks, p, ws.acur.as<uint32_t>())) return pmx_fail(PMX_ERR_INVALID, "the %s kernel (pmx_rows.hip) does not match this build's parameter block", what);
+    PMX_HIPCHECK(hipGetLastError());
     return PMX_OK;
 }
 

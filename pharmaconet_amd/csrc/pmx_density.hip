@@ -25,24 +25,7 @@
 #include <vector>
 
 #include "pmx.h"
-
-int pmx_topk_fail(int code, const char *msg); // sets the thread's error text; defined in pmx_api.hip
-#include <cstdarg>
-#include <cstdio>
-static int fail(int code, const char *fmt, ...) {
-    char buf[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return pmx_topk_fail(code, buf);
-}
-
-#define DM_HIPCHECK(call)                                                                                        \
-    do {                                                                                                         \
-        hipError_t e_ = (call);                                                                                  \
-        if (e_ != hipSuccess) return fail(PMX_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));          \
-    } while (0)
+#include "pmx_device.h"
 
 namespace {
 
@@ -231,10 +214,10 @@ struct pmx_density {
 // Uploads `n_maps` density maps (float32 [size][size][size] each, C order: mask[x][y][z]) and labels their components.
 // Stands in for the `np.where(mask > 0)` + search of density_map.py:91-110, for all hotspots of a pocket at once.
 extern "C" int pmx_density_create(const float *maps_host, int32_t n_maps, int32_t size, int device, pmx_density **out) {
-    if (!maps_host || !out || n_maps < 1 || size < 1 || size > 128) return fail(PMX_ERR_INVALID, "pmx_density_create: bad argument");
-    DM_HIPCHECK(hipSetDevice(device));
+    if (!maps_host || !out || n_maps < 1 || size < 1 || size > 128) return pmx_fail(PMX_ERR_INVALID, "pmx_density_create: bad argument");
+    PMX_HIPCHECK(hipSetDevice(device));
     const size_t V = (size_t)size * size * size, n = V * (size_t)n_maps;
-    if (n >= (1ull << 31)) return fail(PMX_ERR_INVALID, "pmx_density_create: %d maps of %d^3 voxels are too many for one call", n_maps, size);
+    if (n >= (1ull << 31)) return pmx_fail(PMX_ERR_INVALID, "pmx_density_create: %d maps of %d^3 voxels are too many for one call", n_maps, size);
     pmx_density *d = new pmx_density();
     d->device = device, d->n_maps = n_maps, d->size = size;
     if (hipMalloc((void **)&d->maps, n * 4) != hipSuccess || hipMalloc((void **)&d->labels, n * 4) != hipSuccess ||
@@ -243,7 +226,7 @@ extern "C" int pmx_density_create(const float *maps_host, int32_t n_maps, int32_
         if (d->labels) (void)hipFree(d->labels);
         if (d->work) (void)hipFree(d->work);
         delete d;
-        return fail(PMX_ERR_OOM, "pmx_density_create: out of device memory");
+        return pmx_fail(PMX_ERR_OOM, "pmx_density_create: out of device memory");
     }
     hipError_t e = hipMemcpy(d->maps, maps_host, n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
@@ -254,7 +237,7 @@ extern "C" int pmx_density_create(const float *maps_host, int32_t n_maps, int32_
     if (e != hipSuccess) {
         (void)hipFree(d->maps), (void)hipFree(d->labels), (void)hipFree(d->work);
         delete d;
-        return fail(PMX_ERR_HIP, "pmx_density_create: %s", hipGetErrorString(e));
+        return pmx_fail(PMX_ERR_HIP, "pmx_density_create: %s", hipGetErrorString(e));
     }
     *out = d;
     return PMX_OK;
@@ -262,10 +245,10 @@ extern "C" int pmx_density_create(const float *maps_host, int32_t n_maps, int32_
 
 // labels_out (host, [n_maps * size^3]): the smallest linear index ((x * size + y) * size + z) of each voxel's component, -1 outside.
 extern "C" int pmx_density_labels(pmx_density *d, int32_t *labels_out) {
-    if (!d || !labels_out) return fail(PMX_ERR_INVALID, "null argument");
-    DM_HIPCHECK(hipSetDevice(d->device));
+    if (!d || !labels_out) return pmx_fail(PMX_ERR_INVALID, "null argument");
+    PMX_HIPCHECK(hipSetDevice(d->device));
     const size_t n = (size_t)d->size * d->size * d->size * (size_t)d->n_maps;
-    DM_HIPCHECK(hipMemcpy(labels_out, d->labels, n * 4, hipMemcpyDeviceToHost));
+    PMX_HIPCHECK(hipMemcpy(labels_out, d->labels, n * 4, hipMemcpyDeviceToHost));
     return PMX_OK;
 }
 
@@ -275,19 +258,19 @@ extern "C" int pmx_density_labels(pmx_density *d, int32_t *labels_out) {
 extern "C" int pmx_density_order(pmx_density *d, int32_t n_components, const int32_t *comp_map, const int32_t *comp_seed,
                                  const int32_t *comp_offset, int32_t *members_out) {
     if (!d || n_components < 0 || (n_components > 0 && (!comp_map || !comp_seed || !comp_offset || !members_out)))
-        return fail(PMX_ERR_INVALID, "pmx_density_order: bad argument");
+        return pmx_fail(PMX_ERR_INVALID, "pmx_density_order: bad argument");
     if (n_components == 0) return PMX_OK;
-    DM_HIPCHECK(hipSetDevice(d->device));
+    PMX_HIPCHECK(hipSetDevice(d->device));
     const size_t V = (size_t)d->size * d->size * d->size;
     const int64_t total = comp_offset[n_components];
-    if (comp_offset[0] != 0 || total < 0 || (uint64_t)total > V * (uint64_t)d->n_maps) return fail(PMX_ERR_INVALID, "pmx_density_order: bad offsets");
+    if (comp_offset[0] != 0 || total < 0 || (uint64_t)total > V * (uint64_t)d->n_maps) return pmx_fail(PMX_ERR_INVALID, "pmx_density_order: bad offsets");
     for (int32_t c = 0; c < n_components; ++c) {
         if (comp_map[c] < 0 || comp_map[c] >= d->n_maps || comp_seed[c] < 0 || (size_t)comp_seed[c] >= V || comp_offset[c + 1] <= comp_offset[c])
-            return fail(PMX_ERR_INVALID, "pmx_density_order: component %d is malformed", c);
+            return pmx_fail(PMX_ERR_INVALID, "pmx_density_order: component %d is malformed", c);
     }
     int32_t *dev = nullptr; // [3 * n_components + 1] descriptors | [total] members | [total] counts
     const size_t desc = (size_t)3 * n_components + 1;
-    DM_HIPCHECK(hipMalloc((void **)&dev, (desc + 2 * (size_t)total) * 4));
+    PMX_HIPCHECK(hipMalloc((void **)&dev, (desc + 2 * (size_t)total) * 4));
     std::vector<int32_t> host(desc);
     std::memcpy(host.data(), comp_map, (size_t)n_components * 4);
     std::memcpy(host.data() + n_components, comp_seed, (size_t)n_components * 4);
@@ -302,7 +285,7 @@ extern "C" int pmx_density_order(pmx_density *d, int32_t n_components, const int
     }
     if (e == hipSuccess) e = hipMemcpy(members_out, dev + desc, (size_t)total * 4, hipMemcpyDeviceToHost);
     (void)hipFree(dev);
-    if (e != hipSuccess) return fail(PMX_ERR_HIP, "pmx_density_order: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_density_order: %s", hipGetErrorString(e));
     return PMX_OK;
 }
 

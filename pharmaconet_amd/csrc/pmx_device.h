@@ -1,5 +1,6 @@
-// pmx_device.h - device-side layouts shared by the kernels of libpmx (gfx950 only), and two host-only helpers: the dispatch on
-// their lane count (with_lanes) and the owner of a cached device buffer (DevBuf).
+// pmx_device.h - device-side layouts shared by the kernels of libpmx (gfx950 only), and what the host halves of the .hip units share: the
+// check of a HIP call (PMX_HIPCHECK), the functions one unit offers the others, the dispatch on the kernels' lane count (with_lanes) and
+// the owner of a cached device buffer (DevBuf).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,6 +8,22 @@
 #include <type_traits>
 
 #include "pmx.h"
+#include "pmx_error.h"
+
+// Host: returns from the calling function with the thread's message set when a HIP call fails.
+#define PMX_HIPCHECK(expr)                                                                                         \
+    do {                                                                                                           \
+        hipError_t e_ = (expr);                                                                                    \
+        if (e_ != hipSuccess)                                                                                      \
+            return pmx_fail(e_ == hipErrorOutOfMemory ? PMX_ERR_OOM : PMX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, \
+                            hipGetErrorString(e_), __FILE__, __LINE__);                                            \
+    } while (0)
+
+// Host: what the units of libpmx.so call in one another, outside include/pmx.h.
+int pmx_library_device(const pmx_library *lib); // pmx_api.hip (struct pmx_library stays in that unit)
+int pmx_topk_release(int device);               // pmx_topk.hip, pmx_pack_device.hip, pmx_select.hip: free the unit's cached buffers
+int pmx_pack_release(int device);               //   of `device` (pmx_release_workspaces)
+int pmx_select_release(int device);
 
 namespace pmx {
 

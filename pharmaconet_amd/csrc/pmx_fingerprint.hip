@@ -18,8 +18,7 @@
 #include <cstdio>
 
 #include "pmx.h"
-
-int pmx_topk_fail(int code, const char *msg); // error hook in pmx_api.hip
+#include "pmx_device.h"
 
 namespace {
 constexpr int kW = PMX_FINGERPRINT_WORDS;
@@ -119,29 +118,27 @@ __global__ __launch_bounds__(kBlock) void leaders_kernel(const uint64_t *fp, uin
     if (t == 0) *n_leaders = nl;
 }
 
-int fail(int code, const char *msg) { return pmx_topk_fail(code, msg); }
-int hip_fail(hipError_t e) { return pmx_topk_fail(e == hipErrorOutOfMemory ? PMX_ERR_OOM : PMX_ERR_HIP, hipGetErrorString(e)); }
 } // namespace
 
 extern "C" int pmx_fingerprint_tanimoto(const uint64_t *a_dev, uint32_t na, const uint64_t *b_dev, uint32_t nb, float *out_dev, int device, void *stream_) {
-    if (na > PMX_EXPLAIN_MAX || nb > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "pmx_fingerprint_tanimoto: more than 65536 fingerprints on a side");
+    if (na > PMX_EXPLAIN_MAX || nb > PMX_EXPLAIN_MAX) return pmx_fail(PMX_ERR_INVALID, "pmx_fingerprint_tanimoto: more than 65536 fingerprints on a side");
     if (na == 0 || nb == 0) return PMX_OK;
-    if (!a_dev || !b_dev || !out_dev) return fail(PMX_ERR_INVALID, "pmx_fingerprint_tanimoto: null argument");
-    if (hipSetDevice(device) != hipSuccess) return fail(PMX_ERR_HIP, "pmx_fingerprint_tanimoto: hipSetDevice failed");
+    if (!a_dev || !b_dev || !out_dev) return pmx_fail(PMX_ERR_INVALID, "pmx_fingerprint_tanimoto: null argument");
+    if (hipSetDevice(device) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_fingerprint_tanimoto: hipSetDevice failed");
     const dim3 grid((nb + 255u) / 256u, (na + (uint32_t)kRowsPerBlock - 1u) / (uint32_t)kRowsPerBlock);
     tanimoto_kernel<<<grid, dim3(256), 0, static_cast<hipStream_t>(stream_)>>>(a_dev, na, b_dev, nb, out_dev);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PMX_OK : hip_fail(e);
+    PMX_HIPCHECK(hipGetLastError());
+    return PMX_OK;
 }
 
 extern "C" int pmx_fingerprint_leaders(const uint64_t *fp_dev, uint32_t n, float threshold, uint32_t max_leaders, uint32_t *leader_of_dev, uint32_t *leaders_dev,
                                        uint32_t *n_leaders_dev, int device, void *stream_) {
-    if (!(threshold > 0.0f && threshold <= 1.0f)) return fail(PMX_ERR_INVALID, "pmx_fingerprint_leaders: the threshold is not in (0, 1]");
-    if (max_leaders == 0 || max_leaders > PMX_MAX_LEADERS) return fail(PMX_ERR_INVALID, "pmx_fingerprint_leaders: max_leaders is not in 1 .. 2048");
-    if (n > PMX_EXPLAIN_MAX) return fail(PMX_ERR_INVALID, "pmx_fingerprint_leaders: more than 65536 fingerprints");
-    if (!n_leaders_dev || (n && (!fp_dev || !leader_of_dev || !leaders_dev))) return fail(PMX_ERR_INVALID, "pmx_fingerprint_leaders: null argument");
-    if (hipSetDevice(device) != hipSuccess) return fail(PMX_ERR_HIP, "pmx_fingerprint_leaders: hipSetDevice failed");
+    if (!(threshold > 0.0f && threshold <= 1.0f)) return pmx_fail(PMX_ERR_INVALID, "pmx_fingerprint_leaders: the threshold is not in (0, 1]");
+    if (max_leaders == 0 || max_leaders > PMX_MAX_LEADERS) return pmx_fail(PMX_ERR_INVALID, "pmx_fingerprint_leaders: max_leaders is not in 1 .. 2048");
+    if (n > PMX_EXPLAIN_MAX) return pmx_fail(PMX_ERR_INVALID, "pmx_fingerprint_leaders: more than 65536 fingerprints");
+    if (!n_leaders_dev || (n && (!fp_dev || !leader_of_dev || !leaders_dev))) return pmx_fail(PMX_ERR_INVALID, "pmx_fingerprint_leaders: null argument");
+    if (hipSetDevice(device) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_fingerprint_leaders: hipSetDevice failed");
     leaders_kernel<<<dim3(1), dim3(kBlock), 0, static_cast<hipStream_t>(stream_)>>>(fp_dev, n, threshold, max_leaders, leader_of_dev, leaders_dev, n_leaders_dev);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PMX_OK : hip_fail(e);
+    PMX_HIPCHECK(hipGetLastError());
+    return PMX_OK;
 }

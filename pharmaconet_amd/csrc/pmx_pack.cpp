@@ -22,21 +22,7 @@
 #include <vector>
 
 #include "pmx.h"
-
-#ifdef PMX_PACK_STANDALONE
-// libpmx_pack.so: this file alone, for host processes that pack libraries and never touch a GPU (no HIP / RCCL runtime is
-// loaded with it). It brings its own error string.
-#include <cstdio>
-static thread_local char g_pack_err[256] = "";
-static int pmx_topk_fail(int code, const char *msg) {
-    std::snprintf(g_pack_err, sizeof(g_pack_err), "%s", msg);
-    return code;
-}
-extern "C" const char *pmx_last_error(void) { return g_pack_err; }
-extern "C" int pmx_version(void) { return 101; }
-#else
-int pmx_topk_fail(int code, const char *msg); // error hook in pmx_api.hip
-#endif
+#include "pmx_error.h"
 
 namespace {
 
@@ -413,18 +399,18 @@ extern "C" int pmx_pack_features(const pmx_feature_batch *b, int threads, uint64
     try { // no exception crosses the C boundary
         return pack_features_impl(b, threads, offsets_out, data_out, data_cap, data_bytes, status_out);
     } catch (const std::bad_alloc &) {
-        return pmx_topk_fail(PMX_ERR_OOM, "pmx_pack_features: out of host memory");
+        return pmx_fail(PMX_ERR_OOM, "pmx_pack_features: out of host memory");
     } catch (...) {
-        return pmx_topk_fail(PMX_ERR_INVALID, "pmx_pack_features: internal error");
+        return pmx_fail(PMX_ERR_INVALID, "pmx_pack_features: internal error");
     }
 }
 
 static int pack_features_impl(const pmx_feature_batch *b, int threads, uint64_t *offsets_out, uint8_t *data_out, uint64_t data_cap,
                               uint64_t *data_bytes, int32_t *status_out) {
-    if (!b || !offsets_out || (!data_out && data_cap) || !data_bytes) return pmx_topk_fail(PMX_ERR_INVALID, "null argument");
+    if (!b || !offsets_out || (!data_out && data_cap) || !data_bytes) return pmx_fail(PMX_ERR_INVALID, "null argument");
     for (uint64_t i = 0; i < b->n_mols; ++i) // offset arrays must not run backwards (everything else is checked per molecule)
         if (b->atom_off[i + 1] < b->atom_off[i] || b->feat_off[i + 1] < b->feat_off[i] || b->pos_off[i + 1] < b->pos_off[i])
-            return pmx_topk_fail(PMX_ERR_INVALID, "pmx_pack_features: offsets run backwards");
+            return pmx_fail(PMX_ERR_INVALID, "pmx_pack_features: offsets run backwards");
     const uint64_t n = b->n_mols;
     // every record gets the worst-case room of its molecule first (features x conformers), then the records are compacted
     std::vector<uint64_t> room(n + 1, 0);
@@ -443,7 +429,7 @@ static int pack_features_impl(const pmx_feature_batch *b, int threads, uint64_t 
     // from call to call, 2 MB aligned and advised as huge pages (512 times fewer faults where the kernel grants them).
     StagingArea staging;
     uint8_t *scratch = staging.acquire(room[n] + 16);
-    if (!scratch) return pmx_topk_fail(PMX_ERR_OOM, "pmx_pack_features: out of host memory");
+    if (!scratch) return pmx_fail(PMX_ERR_OOM, "pmx_pack_features: out of host memory");
     std::vector<int64_t> sizes(n, 0);
     std::atomic<uint64_t> next{0}, bad_input{0};
     auto work = [&]() {
@@ -496,7 +482,7 @@ static int pack_features_impl(const pmx_feature_batch *b, int threads, uint64_t 
     }
     offsets_out[n] = total;
     *data_bytes = total;
-    if (total > data_cap) return pmx_topk_fail(PMX_ERR_INVALID, "data_out too small (data_bytes holds the size needed)");
+    if (total > data_cap) return pmx_fail(PMX_ERR_INVALID, "data_out too small (data_bytes holds the size needed)");
     next = 0;
     auto compact = [&]() {
         for (;;) {

@@ -31,7 +31,6 @@
 #include "pmx_device.h"
 #include "pmx_scan.h"
 
-int pmx_topk_fail(int code, const char *msg); // error hook in pmx_api.hip
 
 namespace {
 
@@ -751,30 +750,30 @@ PackWork g_work[kMaxDevices];
 
 extern "C" int pmx_pack_features_device(const pmx_feature_batch *b, int device, void *stream_, uint64_t *offsets_out_dev, uint8_t *data_out_dev,
                                         uint64_t data_cap, uint64_t *data_bytes, int32_t *status_out_dev) {
-    if (!b || !offsets_out_dev || (!data_out_dev && data_cap) || !data_bytes) return pmx_topk_fail(PMX_ERR_INVALID, "null argument");
+    if (!b || !offsets_out_dev || (!data_out_dev && data_cap) || !data_bytes) return pmx_fail(PMX_ERR_INVALID, "null argument");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (hipSetDevice(device) != hipSuccess) return pmx_topk_fail(PMX_ERR_HIP, "pmx_pack_features_device: hipSetDevice failed");
+    if (hipSetDevice(device) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_pack_features_device: hipSetDevice failed");
     const uint64_t n = b->n_mols;
     *data_bytes = 0;
     if (n == 0) {
-        if (hipMemsetAsync(offsets_out_dev, 0, 8, stream) != hipSuccess) return pmx_topk_fail(PMX_ERR_HIP, "pmx_pack_features_device: memset failed");
+        if (hipMemsetAsync(offsets_out_dev, 0, 8, stream) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_pack_features_device: memset failed");
         return PMX_OK;
     }
-    if (n > 0x7fffffffull) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_pack_features_device: more than 2^31 - 1 molecules in one call");
-    if (device < 0 || device >= kMaxDevices) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_pack_features_device: device index out of range");
+    if (n > 0x7fffffffull) return pmx_fail(PMX_ERR_INVALID, "pmx_pack_features_device: more than 2^31 - 1 molecules in one call");
+    if (device < 0 || device >= kMaxDevices) return pmx_fail(PMX_ERR_INVALID, "pmx_pack_features_device: device index out of range");
     PackWork &w = g_work[device];
     std::lock_guard<std::mutex> lock(w.mu);
     // The buffers are shared by all calls on the device: one made on another stream than the last starts behind that call's record writer.
-    if (!w.done && hipEventCreateWithFlags(&w.done, hipEventDisableTiming) != hipSuccess) return pmx_topk_fail(PMX_ERR_HIP, "pmx_pack_features_device: hipEventCreate failed");
+    if (!w.done && hipEventCreateWithFlags(&w.done, hipEventDisableTiming) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_pack_features_device: hipEventCreate failed");
     if (w.pending && w.last != stream && hipStreamWaitEvent(stream, w.done, 0) != hipSuccess)
-        return pmx_topk_fail(PMX_ERR_HIP, "pmx_pack_features_device: hipStreamWaitEvent failed");
+        return pmx_fail(PMX_ERR_HIP, "pmx_pack_features_device: hipStreamWaitEvent failed");
     size_t scan_need = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_need, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)n, stream);
     hipError_t e = w.desc.grow(n * sizeof(PackDesc), stream);
     if (e == hipSuccess) e = w.sizes.grow(n * 8, stream);
     if (e == hipSuccess) e = w.scan.grow(scan_need ? scan_need : 8, stream);
     if (e == hipSuccess && !status_out_dev) e = w.status.grow(n * 4, stream);
-    if (e != hipSuccess) return pmx_topk_fail(e == hipErrorOutOfMemory ? PMX_ERR_OOM : PMX_ERR_HIP, hipGetErrorString(e));
+    PMX_HIPCHECK(e);
     DevBatch d{n, b->atom_off, b->atomic_num, b->nbr_off, b->nbr, b->feat_off, b->feat_type, b->feat_flags, b->feat_atom_off, b->feat_atoms,
                b->feat_center_off, b->feat_centers, b->n_conf, b->pos_off, b->positions};
     PackDesc *desc = w.desc.as<PackDesc>();
@@ -791,14 +790,14 @@ extern "C" int pmx_pack_features_device(const pmx_feature_batch *b, int device, 
     uint64_t total = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&total, offsets_out_dev + n, 8, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return pmx_topk_fail(PMX_ERR_HIP, hipGetErrorString(e));
+    PMX_HIPCHECK(e);
     *data_bytes = total;
     if (!data_out_dev) return PMX_OK; // sizing call: the exact size
-    if (total > data_cap) return pmx_topk_fail(PMX_ERR_INVALID, "data_out too small (data_bytes holds the size needed)");
+    if (total > data_cap) return pmx_fail(PMX_ERR_INVALID, "data_out too small (data_bytes holds the size needed)");
     record_kernel<<<dim3((unsigned)n), dim3(64), 0, stream>>>(d, desc, offsets_out_dev, data_out_dev);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(w.done, stream);
-    if (e != hipSuccess) return pmx_topk_fail(PMX_ERR_HIP, hipGetErrorString(e));
+    PMX_HIPCHECK(e);
     w.last = stream;
     w.pending = true;
     return PMX_OK;

@@ -14,12 +14,7 @@
 #include <vector>
 
 #include "pmx.h"
-
-#ifdef PMX_PACK_STANDALONE
-static int pmx_topk_fail(int code, const char *) { return code; } // (libpmx_pack.so keeps its message in pmx_pack.cpp)
-#else
-int pmx_topk_fail(int code, const char *msg); // error hook in pmx_api.hip
-#endif
+#include "pmx_error.h"
 
 namespace {
 
@@ -152,15 +147,15 @@ extern "C" int pmx_perceive_features(const pmx_atom_batch *b, int threads, uint6
                                      uint64_t *feat_atom_off, int32_t *feat_atoms, uint64_t *feat_center_off, int32_t *feat_centers,
                                      uint64_t cap_features, uint64_t cap_atoms, uint64_t cap_centers, uint64_t *n_features, uint64_t *n_feat_atoms,
                                      uint64_t *n_feat_centers, int32_t *status_out) {
-    if (!b || !feat_off || !n_features || !n_feat_atoms || !n_feat_centers) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_perceive_features: null argument");
+    if (!b || !feat_off || !n_features || !n_feat_atoms || !n_feat_centers) return pmx_fail(PMX_ERR_INVALID, "pmx_perceive_features: null argument");
     const uint64_t n = b->n_mols;
-    if (n && (!b->atom_off || !b->ring_off)) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_perceive_features: null offset array in the batch");
+    if (n && (!b->atom_off || !b->ring_off)) return pmx_fail(PMX_ERR_INVALID, "pmx_perceive_features: null offset array in the batch");
     if (n && b->atom_off[n] > b->atom_off[0] && (!b->atomic_num || !b->explicit_degree || !b->heavy_degree || !b->hyb || !b->h_count || !b->flags || !b->nbr_off))
-        return pmx_topk_fail(PMX_ERR_INVALID, "pmx_perceive_features: null per-atom array in the batch");
-    if (n && b->ring_off[n] > b->ring_off[0] && !b->ring_atom_off) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_perceive_features: rings without ring_atom_off");
+        return pmx_fail(PMX_ERR_INVALID, "pmx_perceive_features: null per-atom array in the batch");
+    if (n && b->ring_off[n] > b->ring_off[0] && !b->ring_atom_off) return pmx_fail(PMX_ERR_INVALID, "pmx_perceive_features: rings without ring_atom_off");
     for (uint64_t i = 0; i < n; ++i)
         if (b->atom_off[i + 1] < b->atom_off[i] || b->ring_off[i + 1] < b->ring_off[i])
-            return pmx_topk_fail(PMX_ERR_INVALID, "pmx_perceive_features: offsets run backwards");
+            return pmx_fail(PMX_ERR_INVALID, "pmx_perceive_features: offsets run backwards");
     try {
         // pass 1: perceive every molecule (kept per molecule), pass 2: lay the features out flat
         std::vector<std::vector<Feature>> all(n);
@@ -217,9 +212,9 @@ extern "C" int pmx_perceive_features(const pmx_atom_batch *b, int threads, uint6
         *n_features = nf, *n_feat_atoms = na, *n_feat_centers = nc;
         if (!feat_type) return PMX_OK; // counting call
         if (!feat_flags || !feat_atom_off || !feat_center_off || (na && !feat_atoms) || (nc && !feat_centers))
-            return pmx_topk_fail(PMX_ERR_INVALID, "pmx_perceive_features: null output");
+            return pmx_fail(PMX_ERR_INVALID, "pmx_perceive_features: null output");
         if (nf > cap_features || na > cap_atoms || nc > cap_centers)
-            return pmx_topk_fail(PMX_ERR_INVALID, "pmx_perceive_features: output capacity too small (the counts hold the sizes needed)");
+            return pmx_fail(PMX_ERR_INVALID, "pmx_perceive_features: output capacity too small (the counts hold the sizes needed)");
         uint64_t k = 0, ka = 0, kc = 0;
         for (uint64_t i = 0; i < n; ++i)
             for (const Feature &f : all[i]) {
@@ -232,8 +227,8 @@ extern "C" int pmx_perceive_features(const pmx_atom_batch *b, int threads, uint6
         feat_atom_off[k] = ka, feat_center_off[k] = kc;
         return PMX_OK;
     } catch (const std::bad_alloc &) {
-        return pmx_topk_fail(PMX_ERR_OOM, "pmx_perceive_features: out of host memory");
+        return pmx_fail(PMX_ERR_OOM, "pmx_perceive_features: out of host memory");
     } catch (...) {
-        return pmx_topk_fail(PMX_ERR_INVALID, "pmx_perceive_features: internal error");
+        return pmx_fail(PMX_ERR_INVALID, "pmx_perceive_features: internal error");
     }
 }

@@ -20,7 +20,7 @@
 //     h <= std_min / 5), so that an item costs one 32-byte gather and five FMAs instead of |A||B| (27 on average, up to
 //     169) Gaussian terms. The discrete part of match_utils.py - `num_pass < num_match * 0.5` (:61) - is NOT approximated:
 //     the set of distances where at least half of the model node pairs lie within 2 sigma is a union of float intervals
-//     computed exactly on the host when the model is created (pmx_api.hip, fn_windows) and stored with the cells; cells
+//     computed exactly on the host when the model is created (pmx_model_tables.cpp, cell_windows) and stored with the cells; cells
 //     where that set is not one interval are flagged and counted term by term on the device. Cells whose polynomial is not
 //     accurate relative to the function's own (tail) value are flagged too, and evaluated term by term in self entries
 //     (FnCell, exact_value). The node distances of the cluster pair in work are staged once in LDS (build_tables).

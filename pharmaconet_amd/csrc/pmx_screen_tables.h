@@ -441,7 +441,7 @@ __device__ __forceinline__ void item_finish(const ScreenParams &p, const ItemLoa
     v = __builtin_fmaf(t, v, L.a.y);
     v = __builtin_fmaf(t, v, L.a.x);
     acc = acc + v;
-    // lo <= d <= hi as "d is the median of (d, lo, hi)" (every window has lo <= hi; pmx_api.hip fn_windows): one compare, no mask arithmetic. A cell whose
+    // lo <= d <= hi as "d is the median of (d, lo, hi)" (every window has lo <= hi; pmx_model_tables.cpp cell_windows): one compare, no mask arithmetic. A cell whose
     // pass set is not one interval (lo = NaN; 0.8 items per ligand) is put right behind one wave-wide test instead of an exec-mask detour per item.
     const bool fail = __builtin_amdgcn_fmed3f(L.d, L.b.z, L.b.w) != L.d;
     fails += fail ? 1 : 0;

@@ -15,12 +15,7 @@
 #include <cstring>
 
 #include "pmx.h"
-
-#ifdef PMX_PACK_STANDALONE
-static int pmx_topk_fail(int code, const char *) { return code; } // (libpmx_pack.so keeps its message in pmx_pack.cpp)
-#else
-int pmx_topk_fail(int code, const char *msg); // error hook in pmx_api.hip
-#endif
+#include "pmx_error.h"
 
 namespace {
 
@@ -89,7 +84,7 @@ bool token(const char *&p, const char *e, const char *&t, size_t &tn) {
 // coordinate that is not a number), naming nothing else: *n_records then holds the index of the offending record.
 extern "C" int pmx_sdf_heavy_atoms(const char *text, uint64_t len, uint64_t max_records, uint64_t cap_records, uint64_t cap_atoms, uint64_t *n_records,
                                    uint64_t *n_atoms, int32_t *atoms_per_record, uint8_t *atomic_num, float *xyz) {
-    if (!text || !n_records || !n_atoms) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_sdf_heavy_atoms: null argument");
+    if (!text || !n_records || !n_atoms) return pmx_fail(PMX_ERR_INVALID, "pmx_sdf_heavy_atoms: null argument");
     const bool store = atomic_num != nullptr || xyz != nullptr;
     Cursor cur{text, text + len};
     uint64_t rec = 0, total = 0;
@@ -97,7 +92,7 @@ extern "C" int pmx_sdf_heavy_atoms(const char *text, uint64_t len, uint64_t max_
     auto fail_here = [&]() {
         *n_records = rec;
         *n_atoms = total;
-        return pmx_topk_fail(PMX_ERR_INVALID, "pmx_sdf_heavy_atoms: malformed record");
+        return pmx_fail(PMX_ERR_INVALID, "pmx_sdf_heavy_atoms: malformed record");
     };
     for (;;) {
         if (max_records && rec >= max_records) break;
@@ -150,7 +145,7 @@ extern "C" int pmx_sdf_heavy_atoms(const char *text, uint64_t len, uint64_t max_
                     el = atomic_number(t, tn);
                 }
                 if (el < 0) return fail_here();
-                if (!emit(el, x, y, z)) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_sdf_heavy_atoms: atom capacity too small");
+                if (!emit(el, x, y, z)) return pmx_fail(PMX_ERR_INVALID, "pmx_sdf_heavy_atoms: atom capacity too small");
             }
         } else {
             bool in_atoms = false, done = false;
@@ -185,11 +180,11 @@ extern "C" int pmx_sdf_heavy_atoms(const char *text, uint64_t len, uint64_t max_
                     if (!token(q, e2, t, tn) || !parse_double(t, tn, v[k])) return fail_here();
                 const int el = atomic_number(ty, tyn);
                 if (el < 0) return fail_here();
-                if (!emit(el, v[0], v[1], v[2])) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_sdf_heavy_atoms: atom capacity too small");
+                if (!emit(el, v[0], v[1], v[2])) return pmx_fail(PMX_ERR_INVALID, "pmx_sdf_heavy_atoms: atom capacity too small");
             }
         }
         if (store && atoms_per_record) {
-            if (rec >= cap_records) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_sdf_heavy_atoms: record capacity too small");
+            if (rec >= cap_records) return pmx_fail(PMX_ERR_INVALID, "pmx_sdf_heavy_atoms: record capacity too small");
             atoms_per_record[rec] = heavy;
         }
         ++rec;
@@ -213,7 +208,7 @@ extern "C" int pmx_sdf_heavy_atoms(const char *text, uint64_t len, uint64_t max_
 // understand - PMX_ERR_INVALID, and the caller goes the toolkit's way - rather than guess what the toolkit would make of it.
 extern "C" int pmx_mol2_heavy_atoms(const char *text, uint64_t len, uint64_t max_records, uint64_t cap_records, uint64_t cap_atoms, uint64_t *n_records,
                                     uint64_t *n_atoms, int32_t *atoms_per_record, uint8_t *atomic_num, float *xyz) {
-    if (!text || !n_records || !n_atoms) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_mol2_heavy_atoms: null argument");
+    if (!text || !n_records || !n_atoms) return pmx_fail(PMX_ERR_INVALID, "pmx_mol2_heavy_atoms: null argument");
     const bool store = atomic_num != nullptr || xyz != nullptr;
     Cursor cur{text, text + len};
     uint64_t rec = 0, total = 0;
@@ -223,12 +218,12 @@ extern "C" int pmx_mol2_heavy_atoms(const char *text, uint64_t len, uint64_t max
     auto fail_here = [&]() {
         *n_records = rec; // (the record in work)
         *n_atoms = total;
-        return pmx_topk_fail(PMX_ERR_INVALID, "pmx_mol2_heavy_atoms: malformed record");
+        return pmx_fail(PMX_ERR_INVALID, "pmx_mol2_heavy_atoms: malformed record");
     };
     auto close_record = [&]() -> int {
         if (!open) return PMX_OK;
         if (store && atoms_per_record) {
-            if (rec >= cap_records) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_mol2_heavy_atoms: record capacity too small");
+            if (rec >= cap_records) return pmx_fail(PMX_ERR_INVALID, "pmx_mol2_heavy_atoms: record capacity too small");
             atoms_per_record[rec] = heavy;
         }
         ++rec;
@@ -270,7 +265,7 @@ extern "C" int pmx_mol2_heavy_atoms(const char *text, uint64_t len, uint64_t max
         if (el <= 0) return fail_here(); // no element: not for this reader
         if (el == 1) continue;           // hydrogens are removed (Ligand.__init__: pbmol.removeh(), ligand.py:38)
         if (store) {
-            if (total >= cap_atoms) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_mol2_heavy_atoms: atom capacity too small");
+            if (total >= cap_atoms) return pmx_fail(PMX_ERR_INVALID, "pmx_mol2_heavy_atoms: atom capacity too small");
             if (atomic_num) atomic_num[total] = (uint8_t)el;
             if (xyz) xyz[3 * total] = (float)v[0], xyz[3 * total + 1] = (float)v[1], xyz[3 * total + 2] = (float)v[2];
         }

@@ -21,9 +21,6 @@
 #include "pmx_device.h"
 #include "pmx_scan.h"
 
-int pmx_topk_fail(int code, const char *msg);       // error hook in pmx_api.hip
-int pmx_library_device(const pmx_library *lib);     // pmx_api.hip
-
 namespace {
 
 // counters[0]: indices outside the library; counters[1]: the first position that holds one; counters[2]: total bytes (close_offsets_kernel)
@@ -73,30 +70,28 @@ bool overlap(const void *a, uint64_t na, const void *b, uint64_t nb) {
     return na && nb && pa < pb + nb && pb < pa + na;
 }
 
-int hip_fail(hipError_t e) { return pmx_topk_fail(e == hipErrorOutOfMemory ? PMX_ERR_OOM : PMX_ERR_HIP, hipGetErrorString(e)); }
-
 } // namespace
 
 extern "C" int pmx_library_select(const pmx_library *lib, const uint64_t *indices_dev, uint64_t n, uint64_t *offsets_out_dev, uint8_t *data_out_dev,
                                   uint64_t data_cap, uint64_t *data_bytes, void *stream_) {
-    if (!lib || !offsets_out_dev || !data_bytes || (n && !indices_dev) || (!data_out_dev && data_cap)) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_library_select: null argument");
+    if (!lib || !offsets_out_dev || !data_bytes || (n && !indices_dev) || (!data_out_dev && data_cap)) return pmx_fail(PMX_ERR_INVALID, "pmx_library_select: null argument");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int device = pmx_library_device(lib);
-    if (hipSetDevice(device) != hipSuccess) return pmx_topk_fail(PMX_ERR_HIP, "pmx_library_select: hipSetDevice failed");
+    if (hipSetDevice(device) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_library_select: hipSetDevice failed");
     *data_bytes = 0;
     if (n == 0) {
-        if (hipMemsetAsync(offsets_out_dev, 0, 8, stream) != hipSuccess) return pmx_topk_fail(PMX_ERR_HIP, "pmx_library_select: memset failed");
+        if (hipMemsetAsync(offsets_out_dev, 0, 8, stream) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_library_select: memset failed");
         return PMX_OK;
     }
-    if (n > 0x7fffffffull) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_library_select: more than 2^31 - 1 indices in one call");
-    if (device < 0 || device >= kMaxDevices) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_library_select: device index out of range");
+    if (n > 0x7fffffffull) return pmx_fail(PMX_ERR_INVALID, "pmx_library_select: more than 2^31 - 1 indices in one call");
+    if (device < 0 || device >= kMaxDevices) return pmx_fail(PMX_ERR_INVALID, "pmx_library_select: device index out of range");
     pmx_library_info info;
     const uint64_t *lib_offsets = nullptr;
     const uint8_t *lib_data = nullptr;
     if (pmx_library_info_get(lib, &info) != PMX_OK || pmx_library_buffers(lib, &lib_offsets, &lib_data) != PMX_OK) return PMX_ERR_INVALID;
     if (overlap(offsets_out_dev, (n + 1) * 8, lib_offsets, (info.n_ligands + 1) * 8) || overlap(offsets_out_dev, (n + 1) * 8, lib_data, info.n_bytes) ||
         overlap(data_out_dev, data_cap, lib_offsets, (info.n_ligands + 1) * 8) || overlap(data_out_dev, data_cap, lib_data, info.n_bytes))
-        return pmx_topk_fail(PMX_ERR_INVALID, "pmx_library_select: the output overlaps the source library's buffers");
+        return pmx_fail(PMX_ERR_INVALID, "pmx_library_select: the output overlaps the source library's buffers");
     SelectWork &w = g_work[device];
     std::lock_guard<std::mutex> lock(w.mu);
     size_t scan_need = 0;
@@ -104,12 +99,12 @@ extern "C" int pmx_library_select(const pmx_library *lib, const uint64_t *indice
     hipError_t e = w.sizes.grow(n * 8, stream);
     if (e == hipSuccess) e = w.scan.grow(scan_need ? scan_need : 8, stream);
     if (e == hipSuccess) e = w.counters.grow(3 * 8, stream);
-    if (e != hipSuccess) return hip_fail(e);
+    PMX_HIPCHECK(e);
     uint64_t *sizes = w.sizes.as<uint64_t>();
     unsigned long long *counters = w.counters.as<unsigned long long>();
     e = hipMemsetAsync(counters, 0, 8, stream);
     if (e == hipSuccess) e = hipMemsetAsync(counters + 1, 0xFF, 8, stream);
-    if (e != hipSuccess) return hip_fail(e);
+    PMX_HIPCHECK(e);
     sizes_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(lib_offsets, info.n_ligands, indices_dev, n, sizes, counters);
     size_t scan_bytes = w.scan.bytes;
     e = hipcub::DeviceScan::ExclusiveSum(w.scan.ptr, scan_bytes, sizes, offsets_out_dev, (int)n, stream);
@@ -120,20 +115,18 @@ extern "C" int pmx_library_select(const pmx_library *lib, const uint64_t *indice
     unsigned long long got[3] = {0, 0, 0};
     if (e == hipSuccess) e = hipMemcpyAsync(got, counters, sizeof(got), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hip_fail(e);
-    if (got[0]) {
-        char msg[160];
-        std::snprintf(msg, sizeof(msg), "pmx_library_select: %llu of %llu indices are outside the library's %llu ligands, the first at position %llu", got[0],
-                      (unsigned long long)n, (unsigned long long)info.n_ligands, got[1]);
-        return pmx_topk_fail(PMX_ERR_INVALID, msg);
-    }
+    PMX_HIPCHECK(e);
+    if (got[0])
+        return pmx_fail(PMX_ERR_INVALID, "pmx_library_select: %llu of %llu indices are outside the library's %llu ligands, the first at position %llu", got[0],
+                        (unsigned long long)n, (unsigned long long)info.n_ligands, got[1]);
     *data_bytes = got[2];
     if (!data_out_dev) return PMX_OK; // sizing call
-    if (got[2] > data_cap) return pmx_topk_fail(PMX_ERR_INVALID, "pmx_library_select: data_out too small (data_bytes holds the size needed)");
+    if (got[2] > data_cap) return pmx_fail(PMX_ERR_INVALID, "pmx_library_select: data_out too small (data_bytes holds the size needed)");
     copy_kernel<<<dim3((unsigned)((n + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(64 * kWavesPerBlock), 0, stream>>>(lib_offsets, lib_data, indices_dev, n, offsets_out_dev,
                                                                                                                   data_out_dev);
     e = hipGetLastError();
-    return e == hipSuccess ? PMX_OK : hip_fail(e);
+    PMX_HIPCHECK(e);
+    return PMX_OK;
 }
 
 // pmx_release_workspaces: the gather's buffers of `device` (the device is current and idle).

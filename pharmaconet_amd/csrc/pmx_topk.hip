@@ -22,8 +22,6 @@
 #include "pmx.h"
 #include "pmx_device.h"
 
-int pmx_topk_fail(int code, const char *msg); // defined in pmx_api.hip
-
 namespace {
 
 constexpr int kBins = 2048;
@@ -150,12 +148,6 @@ __global__ void sel_sort_emit(const float *scores, const uint64_t *index, uint64
 
 } // namespace
 
-#define TK_CHECK(expr)                                                        \
-    do {                                                                      \
-        hipError_t e_ = (expr);                                               \
-        if (e_ != hipSuccess) return pmx_topk_fail(PMX_ERR_HIP, hipGetErrorString(e_)); \
-    } while (0)
-
 // Workspace per (device, stream), of fixed size (it depends on the largest k only), allocated once under the lock; the
 // lock is held while a call enqueues, so two host threads ranking on one stream are serialised like the stream itself.
 namespace {
@@ -166,15 +158,15 @@ std::mutex g_topk_mu;
 
 extern "C" int pmx_topk(const float *scores_dev, const uint64_t *index_dev, uint64_t n, uint64_t base_index, int k,
                         float *out_scores_dev, uint64_t *out_index_dev, int device, void *stream_) {
-    if (k < 0 || (!scores_dev && n) || (k && (!out_scores_dev || !out_index_dev))) return pmx_topk_fail(PMX_ERR_INVALID, "bad top-k argument");
-    if (n > (uint64_t)INT32_MAX) return pmx_topk_fail(PMX_ERR_INVALID, "top-k over more than 2^31 - 1 scores: shard the library");
-    if (k > kMaxK) return pmx_topk_fail(PMX_ERR_INVALID, "top-k: k above 65536");
+    if (k < 0 || (!scores_dev && n) || (k && (!out_scores_dev || !out_index_dev))) return pmx_fail(PMX_ERR_INVALID, "bad top-k argument");
+    if (n > (uint64_t)INT32_MAX) return pmx_fail(PMX_ERR_INVALID, "top-k over more than 2^31 - 1 scores: shard the library");
+    if (k > kMaxK) return pmx_fail(PMX_ERR_INVALID, "top-k: k above 65536");
     if (k == 0) return PMX_OK;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    TK_CHECK(hipSetDevice(device));
+    PMX_HIPCHECK(hipSetDevice(device));
     std::lock_guard<std::mutex> lock(g_topk_mu);
     pmx::DevBuf &ws = g_topk_ws[std::make_pair(device, stream)];
-    TK_CHECK(ws.grow(kWsBytes, stream));
+    PMX_HIPCHECK(ws.grow(kWsBytes, stream));
     unsigned char *buf = ws.as<unsigned char>();
     SelState *st = reinterpret_cast<SelState *>(buf);
     uint32_t *hist = reinterpret_cast<uint32_t *>(buf + 256);
@@ -199,7 +191,7 @@ extern "C" int pmx_topk(const float *scores_dev, const uint64_t *index_dev, uint
     }
     if (n) sel_compact<<<dim3(blocks), dim3(256), 0, stream>>>(scores_dev, index_dev, n32, st, cand, m);
     sel_sort_emit<<<dim3(1), dim3(1024), 0, stream>>>(scores_dev, index_dev, base_index, st, cand, m, k, out_scores_dev, out_index_dev);
-    TK_CHECK(hipGetLastError());
+    PMX_HIPCHECK(hipGetLastError());
     return PMX_OK;
 }
 
@@ -228,17 +220,17 @@ struct pmx_comm {
 
 extern "C" int pmx_comm_unique_id(char id_out[PMX_COMM_ID_BYTES]) {
     static_assert(sizeof(ncclUniqueId) <= PMX_COMM_ID_BYTES, "PMX_COMM_ID_BYTES too small");
-    if (!id_out) return pmx_topk_fail(PMX_ERR_INVALID, "null id");
+    if (!id_out) return pmx_fail(PMX_ERR_INVALID, "null id");
     ncclUniqueId id;
-    if (ncclGetUniqueId(&id) != ncclSuccess) return pmx_topk_fail(PMX_ERR_HIP, "ncclGetUniqueId failed");
+    if (ncclGetUniqueId(&id) != ncclSuccess) return pmx_fail(PMX_ERR_HIP, "ncclGetUniqueId failed");
     std::memset(id_out, 0, PMX_COMM_ID_BYTES);
     std::memcpy(id_out, &id, sizeof(id));
     return PMX_OK;
 }
 
 extern "C" int pmx_comm_create(const char id[PMX_COMM_ID_BYTES], int rank, int nranks, int device, pmx_comm **out) {
-    if (!id || !out || nranks < 1 || rank < 0 || rank >= nranks) return pmx_topk_fail(PMX_ERR_INVALID, "bad communicator argument");
-    TK_CHECK(hipSetDevice(device));
+    if (!id || !out || nranks < 1 || rank < 0 || rank >= nranks) return pmx_fail(PMX_ERR_INVALID, "bad communicator argument");
+    PMX_HIPCHECK(hipSetDevice(device));
     ncclUniqueId uid;
     std::memcpy(&uid, id, sizeof(uid));
     pmx_comm *c = new pmx_comm();
@@ -248,7 +240,7 @@ extern "C" int pmx_comm_create(const char id[PMX_COMM_ID_BYTES], int rank, int n
     const ncclResult_t r = ncclCommInitRank(&c->comm, nranks, uid, rank);
     if (r != ncclSuccess) {
         delete c;
-        return pmx_topk_fail(PMX_ERR_HIP, ncclGetErrorString(r));
+        return pmx_fail(PMX_ERR_HIP, "%s", ncclGetErrorString(r));
     }
     *out = c;
     return PMX_OK;
@@ -256,12 +248,12 @@ extern "C" int pmx_comm_create(const char id[PMX_COMM_ID_BYTES], int rank, int n
 
 // What RCCL itself says about the communicator (not what the caller passed in): ranks, this rank, its device.
 extern "C" int pmx_comm_info(pmx_comm *c, int *rank_out, int *nranks_out, int *device_out) {
-    if (!c || !c->comm) return pmx_topk_fail(PMX_ERR_INVALID, "null communicator");
+    if (!c || !c->comm) return pmx_fail(PMX_ERR_INVALID, "null communicator");
     int n = 0, r = 0, d = 0;
     ncclResult_t e = ncclCommCount(c->comm, &n);
     if (e == ncclSuccess) e = ncclCommUserRank(c->comm, &r);
     if (e == ncclSuccess) e = ncclCommCuDevice(c->comm, &d);
-    if (e != ncclSuccess) return pmx_topk_fail(PMX_ERR_HIP, ncclGetErrorString(e));
+    if (e != ncclSuccess) return pmx_fail(PMX_ERR_HIP, "%s", ncclGetErrorString(e));
     if (rank_out) *rank_out = r;
     if (nranks_out) *nranks_out = n;
     if (device_out) *device_out = d;
@@ -280,17 +272,17 @@ extern "C" int pmx_comm_destroy(pmx_comm *c) {
 
 extern "C" int pmx_topk_allgather(pmx_comm *c, const float *scores_k_dev, const uint64_t *index_k_dev, int k, float *out_scores_dev,
                                   uint64_t *out_index_dev, void *stream_) {
-    if (!c || k < 0 || (k && (!scores_k_dev || !index_k_dev || !out_scores_dev || !out_index_dev))) return pmx_topk_fail(PMX_ERR_INVALID, "bad argument");
+    if (!c || k < 0 || (k && (!scores_k_dev || !index_k_dev || !out_scores_dev || !out_index_dev))) return pmx_fail(PMX_ERR_INVALID, "bad argument");
     if (k == 0) return PMX_OK;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    TK_CHECK(hipSetDevice(c->device));
-    TK_CHECK(c->gs.grow((size_t)c->nranks * k * sizeof(float), stream));
-    TK_CHECK(c->gi.grow((size_t)c->nranks * k * sizeof(uint64_t), stream));
+    PMX_HIPCHECK(hipSetDevice(c->device));
+    PMX_HIPCHECK(c->gs.grow((size_t)c->nranks * k * sizeof(float), stream));
+    PMX_HIPCHECK(c->gi.grow((size_t)c->nranks * k * sizeof(uint64_t), stream));
     ncclResult_t r = ncclGroupStart();
     if (r == ncclSuccess) r = ncclAllGather(scores_k_dev, c->gs.ptr, (size_t)k, ncclFloat32, c->comm, stream);
     if (r == ncclSuccess) r = ncclAllGather(index_k_dev, c->gi.ptr, (size_t)k, ncclUint64, c->comm, stream);
     if (r == ncclSuccess) r = ncclGroupEnd();
-    if (r != ncclSuccess) return pmx_topk_fail(PMX_ERR_HIP, ncclGetErrorString(r));
+    if (r != ncclSuccess) return pmx_fail(PMX_ERR_HIP, "%s", ncclGetErrorString(r));
     // ranks hold contiguous ascending shards, so position order in the gathered array is global index order: ties on the score
     // go by position = by global index; NaN entries (unsupported ligands, real indices) rank after every real score, and
     // padding entries (index UINT64_MAX, from ranks with fewer than k ligands) after those
