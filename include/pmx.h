@@ -552,6 +552,64 @@ int pmx_fingerprint_leaders(const uint64_t *fp_dev /* [n][PMX_FINGERPRINT_WORDS]
                             uint32_t *leader_of_dev /* [n] */, uint32_t *leaders_dev /* [max_leaders] */, uint32_t *n_leaders_dev /* [1] */,
                             int device, void *stream);
 
+/*
+ * Retrospective validation (pmx_enrich.hip): does a model, under given type weights, rank known binders above decoys? Per column of scores
+ * over one labelled list, and per bootstrap resample of the list, the integers and sums from which the host derives AUROC, enrichment
+ * factors and BEDROC. The specification is this comment (the reference has no counterpart); tests/enrichment_ref.py restates it in NumPy.
+ *
+ *   scores_dev   float32 [n_cols][col_stride], the first n of each row are used; 1 <= n < 2^31, 1 <= n_cols <= PMX_ENRICH_MAX_COLUMNS
+ *   status_dev   int32 [n] or NULL: PMX_LIGAND_*
+ *   labels_dev   uint8 [n]: 0 decoy, 1 active, 2 not counted. Any other value refuses the call - which is stream-ordered and reads nothing
+ *                back, so the refusal is written where the caller will read: every entry of totals is UINT64_MAX and the other outputs are
+ *                undefined
+ *   cut_ppm      uint32 [n_cut] in host memory (read before the call returns): cutoffs in parts per million of the list, each 1 .. 10^6;
+ *                n_cut <= PMX_ENRICH_MAX_CUTOFFS
+ *   alpha > 0    BEDROC's alpha;   n_boot <= PMX_ENRICH_MAX_BOOTSTRAP resamples;   seed of the bootstrap
+ *
+ * The ranked list of a column. Counted are the ligands labelled 0 or 1, N' of them. They are ranked by descending score, equal scores in
+ * ascending ligand index. A NaN score or a non-zero status counts as -inf (ranked last, tied with each other and with a score of -inf);
+ * -0.0 and +0.0 are one value. A tie group is a maximal run of equal scores. Every output but `order` is the expectation under random
+ * tie-breaking, so the order inside a group has no effect on it.
+ *
+ * Weights. Row 0 of every output is the sample: c_i = 1. Row b = 1 .. n_boot is a Poisson bootstrap resample: c_i = Poisson(1) from a
+ * counter-based hash of (seed, b, i), the same in every column (differences between columns are paired). Arithmetic mod 2^64:
+ *   mix(x):  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *   h = mix(mix(seed + 0x9E3779B97F4A7C15 * b) + i)
+ *   c_i = the number of entries of T[m] = floor(2^64 * P(Poisson(1) <= m)), m = 0 .. 20, that are <= h  (T[20] = 2^64 - 1: 21 entries)
+ * Per group g: a_g, d_g the weighted actives and decoys, c_g = a_g + d_g; A_before, C_before the sums of a_g, c_g over the groups ranked
+ * before it. A group with c_g = 0 contributes nothing. N*, n_a*, n_d*: the weighted totals of a row.
+ *
+ *   totals_dev   uint64 [1 + n_boot][3]            (N*, n_a*, n_d*)
+ *   u2_dev       uint64 [n_cols][1 + n_boot]       sum over g of d_g * (2 * A_before + a_g): twice the Mann-Whitney U with ties at one half.
+ *                                                  AUROC = u2 / (2 n_a* n_d*)
+ *   hits_dev     double [n_cols][1 + n_boot][n_cut]  k = (ppm * N* + 999999) / 1000000 in uint64 (the ceiling). For the group with
+ *                                                  C_before < k <= C_before + c_g:  (double)(A_before + a_g) when k = C_before + c_g, else
+ *                                                  (double)A_before + (double)a_g * (double)(k - C_before) / (double)c_g, evaluated left to
+ *                                                  right, each operation rounded to double (no fused multiply-add). 0 when N* = 0.
+ *   expsum_dev   double [n_cols][1 + n_boot]       sum over the groups with a_g > 0 of a_g * E_g, E_g the mean of exp(-alpha r / N*) over the
+ *                                                  group's ranks r = C_before + 1 .. C_before + c_g, formed as, with s = -alpha / (double)N*,
+ *                                                  (double)a_g * (exp(s * (C_before + 1)) * expm1(s * c_g) * (1 / expm1(s)) / c_g).
+ *                                                  Summed in a fixed order without floating-point atomics: a call gives the same bits
+ *                                                  every time; against another order of summation it agrees to rounding.
+ *   order_dev    int64 [n_cols][order_stride] or NULL: the ranked ligand indices of each column, the first min(N', order_stride) of a row
+ *
+ * The host derives EF = (hits / k) / (n_a* / N*), BEDROC (Truchon & Bayly 2007, from expsum, n_a*, N*, alpha) and percentile intervals over
+ * the rows; a row with no active, no decoy or N* = 0 is NaN there, not an error here. One stable radix sort per column (hipcub), one pass
+ * that leaves a byte per ranked position, and one work-group per (column, row) that walks the ranked list in tiles of PMX_ENRICH_TILE
+ * positions with a carry from tile to tile. Stream-ordered like pmx_score: enqueued, no synchronisation. The work buffers are kept per device
+ * (a call on another stream starts behind the call before it) and freed by pmx_release_workspaces.
+ */
+#define PMX_ENRICH_MAX_COLUMNS 64
+#define PMX_ENRICH_MAX_CUTOFFS 64
+#define PMX_ENRICH_MAX_BOOTSTRAP 4096
+#define PMX_ENRICH_TILE 2048
+int pmx_enrichment(const float *scores_dev, uint64_t col_stride, int n_cols, uint64_t n, const int32_t *status_dev, const uint8_t *labels_dev,
+                   const uint32_t *cut_ppm, int n_cut, double alpha, int n_boot, uint64_t seed, uint64_t *totals_dev, uint64_t *u2_dev, double *hits_dev,
+                   double *expsum_dev, int64_t *order_dev, uint64_t order_stride, int device, void *stream);
+/* HIP-event times of the last pmx_enrichment on `device` that was made with profiling on (pmx_set_profiling(1): events around the phases,
+ * nothing else changes): ms_out = {totals, keys + sort (all columns), ranked-byte pass (all columns), walk}. Waits for that call. */
+int pmx_enrichment_times(int device, double ms_out[4]);
+
 /* Frees the scoring workspaces libpmx keeps between calls on `device` (synchronises the device first). */
 int pmx_release_workspaces(int device);
 

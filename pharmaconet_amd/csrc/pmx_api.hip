@@ -34,6 +34,8 @@ static thread_local std::shared_ptr<ScreenWs> g_last_screen;
 static thread_local int g_last_device = 0;
 static int screen_stats(pmx_score_stats *out);
 
+int pmx_profiling() { return g_profiling; }
+
 extern "C" int pmx_set_profiling(int enabled) {
     g_profiling = enabled;
     return PMX_OK;
@@ -865,7 +867,8 @@ extern "C" int pmx_release_workspaces(int device) {
     }
     int rc = pmx_topk_release(device);
     if (!rc) rc = pmx_pack_release(device);
-    return rc ? rc : pmx_select_release(device);
+    if (!rc) rc = pmx_select_release(device);
+    return rc ? rc : pmx_enrich_release(device);
 }
 
 // ------------------------------------------------------------------------------------ explain (pmx_explain.hip)

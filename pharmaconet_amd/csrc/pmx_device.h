@@ -24,6 +24,8 @@ int pmx_library_device(const pmx_library *lib); // pmx_api.hip (struct pmx_libra
 int pmx_topk_release(int device);               // pmx_topk.hip, pmx_pack_device.hip, pmx_select.hip: free the unit's cached buffers
 int pmx_pack_release(int device);               //   of `device` (pmx_release_workspaces)
 int pmx_select_release(int device);
+int pmx_enrich_release(int device);             // pmx_enrich.hip
+int pmx_profiling();                            // pmx_api.hip: what pmx_set_profiling set
 
 namespace pmx {
 

@@ -15,9 +15,10 @@ import numpy as np
 from . import _ffi
 from .constants import weights_vector
 from .library import PackedLibrary, as_packed_library
+from .validation import ENRICH_TILE, FLOAT64_REFUSED, MAX_BOOTSTRAP, MAX_COLUMNS, POISSON1_CDF64, Enrichment, cutoffs_ppm  # noqa: F401  (the table and the tile of include/pmx.h)
 
-__all__ = ["Alignment", "Attribution", "DeviceLibrary", "Explanation", "PanelResult", "ScreeningResult", "align", "attribute", "explain", "score_one", "screen", "screen_multi", "topk",
-           "device_model", "last_score_stats"]
+__all__ = ["Alignment", "Attribution", "DeviceLibrary", "Enrichment", "Explanation", "PanelResult", "ScreeningResult", "align", "attribute", "enrichment", "explain", "score_one",
+           "screen", "screen_multi", "sweep", "topk", "device_model", "last_score_stats"]
 
 
 def _torch():
@@ -349,6 +350,11 @@ class ScreeningResult:
         model, library, weights = self._scored(None, library, None)
         return screen_multi([model, *models], library, weights=weights, indices=self._best(k).astype(np.int64), float64=str(self.scores.dtype).endswith("float64"))
 
+    def enrichment(self, labels, **kwargs) -> "Enrichment":
+        """`enrichment` of this screen's scores and status: does the model rank the actives of `labels` above its decoys? `labels` are in the
+        order of the scores (list order for a listed screen)."""
+        return enrichment(self.scores, labels, status=self.status, **kwargs)
+
     def modes(self, k: int, modes: int = 4, model=None, library=None, weights: dict[str, float] | None = None, require=None, exclude=None) -> "ModeSet":
         """`explain_modes` of this screen's k best ligands (the rows of `explain(k)`): the `modes` best binding modes per conformer."""
         model, library, weights = self._scored(model, library, weights)
@@ -427,7 +433,7 @@ def screen(
     torch = _torch()
     lib = _ffi.load()
     if float64 and topk is not None:
-        raise ValueError("float64 scores are ranked by the caller (the device top-k ranks float32 values)")
+        raise ValueError(FLOAT64_REFUSED)
     with _resident(library, device) as whole, _listed(whole, indices, first, count) as (dlib, listed, first, count):
         dev = dlib.device
         mh = device_model(model, dev)
@@ -496,6 +502,11 @@ class PanelResult:
         cols = [int(j) for j in np.lexsort((np.arange(len(sc)), -key))[:k] if st[j] == 0]
         return self.ligands()[cols], sc[cols]
 
+    def enrichment(self, labels, **kwargs) -> "Enrichment":
+        """`enrichment` with one column per pocket of the panel (`labels` in the order of `ligands()`): `delta(a, b, metric)` of the result
+        compares two pockets' models on the same resamples."""
+        return enrichment(self.scores, labels, status=self.status, **kwargs)
+
     def margin(self, target: int):
         """[count] on the device: the target pocket's score minus the best score of the other pockets - how selective each ligand is for it."""
         n = int(self.scores.shape[0])
@@ -523,6 +534,113 @@ def screen_multi(models, library, weights: dict[str, float] | None = None, first
                                                                                    scores.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream)))
     return PanelResult(scores=scores, status=status, first=first, indices=listed, models=models,
                        library=library if isinstance(library, (DeviceLibrary, PackedLibrary)) else None, weights=weights)
+
+
+def _labels_tensor(labels, n: int, tdev):
+    """Labels (bool / uint8: 0 decoy, 1 active, 2 not counted) as a uint8 tensor [n] on `tdev`; a host array is checked here, a device
+    tensor by the call itself (`pmx_enrichment` marks its totals)."""
+    torch = _torch()
+    if isinstance(labels, torch.Tensor):
+        if labels.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("labels as a tensor: bool or uint8")
+        t = labels.to(tdev).to(torch.uint8).reshape(-1).contiguous()
+    else:
+        host = np.asarray(labels)
+        if host.dtype != np.bool_ and host.dtype != np.uint8:
+            if not np.issubdtype(host.dtype, np.integer):
+                raise TypeError("labels: a bool or uint8 array")
+        if host.size and (host.astype(np.int64).min() < 0 or host.astype(np.int64).max() > 2):
+            raise ValueError("labels: 0 (decoy), 1 (active) or 2 (not counted)")
+        t = torch.from_numpy(np.ascontiguousarray(host.astype(np.uint8).reshape(-1))).to(tdev)
+    if int(t.numel()) != n:
+        raise ValueError(f"{int(t.numel())} labels for {n} scores")
+    return t
+
+
+def enrichment(scores, labels, status=None, cutoffs=(0.005, 0.01, 0.05), alpha: float = 20.0, bootstrap: int = 0, seed: int = 0, order: bool = False,
+               columns=None) -> Enrichment:
+    """Retrospective validation of one or more columns of scores over a labelled list (`pmx_enrichment`, include/pmx.h): AUROC, the
+    enrichment factor at each of `cutoffs` (fractions of the list) and BEDROC(`alpha`), each the expectation under random tie-breaking,
+    for the sample and for `bootstrap` Poisson resamples of it (seeded; a ligand has the same count in every column).
+
+    `scores`: float32 device tensor [n] or [n_cols, n] (`ScreeningResult.scores`, `PanelResult.scores`); `status`: int32 [n] or None;
+    `labels`: bool / uint8 array or device tensor [n] - 0 decoy, 1 active, 2 not counted. `order=True` also returns the ranked ligand
+    indices of every column. The call is enqueued on torch's current stream behind the producer of `scores`; the results are read back."""
+    torch = _torch()
+    lib = _ffi.load()
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
+        raise TypeError("scores: a float32 tensor on the device")
+    if scores.dtype == torch.float64:
+        raise ValueError(FLOAT64_REFUSED)
+    if scores.dtype != torch.float32 or scores.dim() not in (1, 2):
+        raise TypeError("scores: a float32 tensor [n] or [n_cols, n]")
+    sc = scores if scores.dim() == 2 else scores.reshape(1, -1)
+    if sc.stride(1) != 1 or (sc.shape[0] > 1 and sc.stride(0) < sc.shape[1]):
+        sc = sc.contiguous()
+    n_cols, n = int(sc.shape[0]), int(sc.shape[1])
+    if n < 1 or not 1 <= n_cols <= MAX_COLUMNS:
+        raise ValueError(f"enrichment: at least one ligand and 1 to {MAX_COLUMNS} columns")
+    if not 0 <= int(bootstrap) <= MAX_BOOTSTRAP:
+        raise ValueError(f"bootstrap: 0 to {MAX_BOOTSTRAP} resamples")
+    if not alpha > 0:
+        raise ValueError("alpha must be positive")
+    tdev = sc.device
+    ppm = cutoffs_ppm(cutoffs)
+    lab = _labels_tensor(labels, n, tdev)
+    st = None
+    if status is not None:
+        st = (status if isinstance(status, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(status, dtype=np.int32)))).to(tdev).to(torch.int32).reshape(-1).contiguous()
+        if int(st.numel()) != n:
+            raise ValueError(f"{int(st.numel())} status values for {n} scores")
+    rows, n_cut = 1 + int(bootstrap), len(ppm)
+    totals = torch.empty((rows, 3), dtype=torch.int64, device=tdev)
+    u2 = torch.empty((n_cols, rows), dtype=torch.int64, device=tdev)
+    hits = torch.empty((n_cols, rows, n_cut), dtype=torch.float64, device=tdev)
+    expsum = torch.empty((n_cols, rows), dtype=torch.float64, device=tdev)
+    ranked = None
+    if order:
+        n_counted = int((lab < 2).sum().item())
+        ranked = torch.empty((n_cols, n_counted), dtype=torch.int64, device=tdev)
+    stream = torch.cuda.current_stream(tdev).cuda_stream
+    _ffi.check(lib.pmx_enrichment(sc.data_ptr(), int(sc.stride(0)) if n_cols > 1 else n, n_cols, n, st.data_ptr() if st is not None else None, lab.data_ptr(),
+                                  (ctypes.c_uint32 * max(n_cut, 1))(*(int(p) for p in ppm)), n_cut, float(alpha), int(bootstrap), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                  totals.data_ptr(), u2.data_ptr(), hits.data_ptr() if n_cut else None, expsum.data_ptr(),
+                                  ranked.data_ptr() if ranked is not None and ranked.numel() else None, ranked.shape[1] if ranked is not None else 0,
+                                  tdev.index, ctypes.c_void_p(stream)))
+    tot = totals.cpu().numpy().view(np.uint64)
+    if int(tot[0, 0]) == 0xFFFFFFFFFFFFFFFF:
+        raise _ffi.PmxError("pmx_enrichment: labels other than 0 (decoy), 1 (active) and 2 (not counted)")
+    return Enrichment(totals=tot, u2=u2.cpu().numpy().view(np.uint64), hits=hits.cpu().numpy(), expsum=expsum.cpu().numpy(), cut_ppm=ppm, alpha=float(alpha),
+                      seed=int(seed), order=ranked.cpu().numpy() if ranked is not None else None, columns=list(columns) if columns is not None else [])
+
+
+def sweep(models, library, labels, weight_sets, cutoffs=(0.005, 0.01, 0.05), alpha: float = 20.0, bootstrap: int = 0, seed: int = 0, order: bool = False,
+          device=None, return_scores: bool = False):
+    """Calibration: every model of `models` under every weight set of `weight_sets` (dicts as `screen` takes them, None for the defaults)
+    over one labelled library - one `pmx_score` per (model, weight set) into one [n_cols, n] buffer, then one `enrichment` over all
+    columns. Column m * len(weight_sets) + w is named (m, w) and is bit for bit `screen(models[m], library, weights=weight_sets[w]).scores`;
+    the resamples are shared, so `delta((m, w), (m2, w2), metric)` is paired. It evaluates the sets it is given and changes no score.
+    (A ligand `pmx_score` reports with a non-zero status has a NaN score, which ranks as the status would.) With `return_scores` the
+    result is (Enrichment, scores tensor)."""
+    torch = _torch()
+    lib = _ffi.load()
+    models, weight_sets = list(models), list(weight_sets)
+    if not models or not weight_sets or len(models) * len(weight_sets) > MAX_COLUMNS:
+        raise ValueError(f"sweep: 1 to {MAX_COLUMNS} (model, weight set) columns")
+    with _resident(library, device) as dlib:
+        tdev = torch.device("cuda", dlib.device)
+        n = len(dlib)
+        scores = torch.empty((len(models) * len(weight_sets), n), dtype=torch.float32, device=tdev)
+        status = torch.empty(n, dtype=torch.int32, device=tdev)
+        stream = torch.cuda.current_stream(tdev).cuda_stream
+        columns = []
+        for m, model in enumerate(models):
+            mh = device_model(model, dlib.device)
+            for w, weights in enumerate(weight_sets):
+                _ffi.check(lib.pmx_score(mh.handle, dlib.handle, _weights_array(weights), 0, n, scores[len(columns)].data_ptr(), status.data_ptr(), ctypes.c_void_p(stream)))
+                columns.append((m, w))
+        en = enrichment(scores, labels, cutoffs=cutoffs, alpha=alpha, bootstrap=bootstrap, seed=seed, order=order, columns=columns)
+    return (en, scores) if return_scores else en
 
 
 def score_one(model, ligand, weights: dict[str, float] | None = None, device=None) -> float:

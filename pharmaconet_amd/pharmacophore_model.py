@@ -511,6 +511,12 @@ class PharmacophoreModel:
 
         return screen(self, library, weights=weights, topk=topk, **kwargs)
 
+    def sweep(self, library, labels, weight_sets, **kwargs):
+        """This model under each of `weight_sets` over a labelled library: the `Enrichment` of `engine.sweep([self], ...)`, one column per set."""
+        from .engine import sweep
+
+        return sweep([self], library, labels, weight_sets, **kwargs)
+
 
 class ModelNodeCluster:
     """`pharmacophore_model.py:207-246` (a view; `get_kwargs()` gives back the state entry)."""

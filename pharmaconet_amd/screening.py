@@ -6,6 +6,7 @@ processes; needs OpenBabel like the reference) or a packed library file (`.pmxli
 `pharmaconet_amd.library`) with an optional `<library>.names` text file giving one path per ligand.
 Output: `path,score` CSV, best first, ties in library order (`screening.py:70-75`). Scoring runs on the GPU.
 `--panel MODEL ... --panel_out PATH` scores the best hits against other pockets; `--save_top K PATH` keeps them as a packed library.
+`--actives FILE --enrichment_out PATH` validates the model retrospectively: the library's ligands named in FILE are the actives, the rest decoys.
 """
 
 from __future__ import annotations
@@ -49,6 +50,12 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--panel_k", type=int, default=100, metavar="K", help="hits in --panel_out")
         cfg.add_argument("--panel_out", type=str, default=None, metavar="PATH", help="CSV of the K best hits with their score against every --panel model and the margin over the best of them (needed with --panel)")
         cfg.add_argument("--save_top", nargs=2, default=None, metavar=("K", "PATH"), help="keep the K best hits as a packed library PATH (.pmxlib, with PATH.names) that -d takes")
+        cfg.add_argument("--actives", type=str, default=None, metavar="FILE", help="retrospective validation: a file with one ligand name per line (a name of the library, or its file stem) - the actives; every other ligand is a decoy")
+        cfg.add_argument("--enrichment_out", type=str, default=None, metavar="PATH", help="CSV `metric,value,ci_low,ci_high` with AUROC, BEDROC and the enrichment factors (needed with --actives)")
+        cfg.add_argument("--enrichment_cut", type=str, default="0.5,1,5", metavar="LIST", help="comma-separated cutoffs of the enrichment factors, in percent of the list")
+        cfg.add_argument("--bedroc_alpha", type=float, default=20.0, metavar="A", help="BEDROC's alpha")
+        cfg.add_argument("--bootstrap", type=int, default=0, metavar="B", help="bootstrap resamples behind the confidence intervals of --enrichment_out (0: none, at most 4096)")
+        cfg.add_argument("--bootstrap_seed", type=int, default=0, metavar="S", help="seed of the bootstrap")
         par = self.add_argument_group("parameter")
         par.add_argument("--hydrophobic", type=float, default=1.0, help="weight for hydrophobic carbon")
         par.add_argument("--aromatic", type=float, default=4.0, help="weight for aromatic ring")
@@ -169,6 +176,18 @@ def main(argv=None) -> None:
             save_k = 0
         if save_k <= 0:
             parser.error("--save_top takes a positive K and a path")
+    if bool(args.actives) != bool(args.enrichment_out):
+        parser.error("--actives FILE and --enrichment_out PATH go together")
+    try:
+        enrichment_cut = [float(v) / 100.0 for v in args.enrichment_cut.split(",")]
+    except ValueError:
+        parser.error("--enrichment_cut takes comma-separated percentages")
+    if args.actives and (not enrichment_cut or len(enrichment_cut) > 64 or any(not 1e-6 <= c <= 1.0 for c in enrichment_cut)):
+        parser.error("--enrichment_cut takes 1 to 64 percentages between 0.0001 and 100")
+    if not 0 <= args.bootstrap <= 4096:
+        parser.error("--bootstrap takes 0 to 4096")
+    if not args.bedroc_alpha > 0:
+        parser.error("--bedroc_alpha must be positive")
     try:
         require = [[int(v) for v in g.split(",")] for g in args.require]
         exclude = [int(v) for v in args.exclude.split(",")] if args.exclude else []
@@ -185,9 +204,18 @@ def main(argv=None) -> None:
         Hydrophobic=args.hydrophobic,
     )
     names, lib = load_library(Path(args.library_dir), args.cpus, on_device=True)
+    if args.actives:  # (before the screen: a name that matches nothing should not cost a pass)
+        from .validation import match_actives
+
+        try:
+            labels = match_actives(Path(args.actives).read_text().splitlines(), names)
+        except ValueError as e:
+            parser.error(f"--actives {args.actives}: {e}")
     result = model.screen(lib, weights=weight, float64=True)  # (the reference writes the float64 `GraphMatcher.run()` returns)
     scores, status = result.scores.cpu().numpy(), result.status.cpu().numpy()
     write_csv(Path(args.out), names, scores, status)
+    if args.actives:
+        write_enrichment(Path(args.enrichment_out), result, labels, enrichment_cut, args.bedroc_alpha, args.bootstrap, args.bootstrap_seed)
     if args.explain > 0:
         out = Path(args.explain_out) if args.explain_out else Path(str(args.out) + ".explain.csv")
         write_explain_csv(out, names, scores, status, model, lib, weight, args.explain)
@@ -212,6 +240,19 @@ def main(argv=None) -> None:
             write_panel_csv(Path(args.panel_out), names, scores, status, model, args.panel, dlib, weight, args.panel_k)
         if args.save_top:
             save_top(Path(args.save_top[1]), names, scores, status, dlib, save_k)
+
+
+def write_enrichment(out: Path, result, labels: np.ndarray, cutoffs: list[float], alpha: float, bootstrap: int, seed: int) -> None:
+    """`metric,value,ci_low,ci_high` of the screen against the labels (`engine.enrichment` on the float32 rounding of the screen's scores,
+    which is what `pmx_score` returns): the numbers of actives and decoys, AUROC, BEDROC and the enrichment factor at every cutoff, with
+    95 % percentile intervals over `bootstrap` resamples (empty without)."""
+    import torch
+
+    from .engine import enrichment
+    from .validation import write_enrichment_csv
+
+    en = enrichment(result.scores.to(torch.float32), labels, status=result.status, cutoffs=cutoffs, alpha=alpha, bootstrap=bootstrap, seed=seed)
+    write_enrichment_csv(out, en)
 
 
 def _best_hits(scores: np.ndarray, status: np.ndarray, k: int) -> list[int]:
