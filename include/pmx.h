@@ -553,6 +553,50 @@ int pmx_fingerprint_leaders(const uint64_t *fp_dev /* [n][PMX_FINGERPRINT_WORDS]
                             int device, void *stream);
 
 /*
+ * A ligand described by its own pharmacophore (pmx_ligand_fp.hip): per ligand of a resident library a two-point pharmacophore fingerprint -
+ * which unordered pairs of feature types it holds at which distance - in the 256-bit format pmx_fingerprint_tanimoto and
+ * pmx_fingerprint_leaders take, and a census of its types. The reference has no counterpart (it describes a ligand only against a pocket);
+ * the specification is this comment, and tests/ligand_fp_ref.py restates it in NumPy. Integer results: no tolerance anywhere.
+ * For ligand first + i, whose record has n nodes, C conformers and type masks tm[u] (pharmaconet_amd/library.py):
+ *   node pairs   every u < v in record order; clusters play no part
+ *   d2           for conformer c, in float32: dx, dy, dz the float32 differences of the record's coordinates, d2 = (dx*dx + dy*dy) + dz*dz,
+ *                every operation rounded to float32, no fused multiply-add, no square root
+ *   bin          the number of entries of E2 = {4, 9, 16, 25, 36, 56.25, 81, 144} - the squares of 2, 3, 4, 5, 6, 7.5, 9 and 12 Angstrom,
+ *                all exact in float32 - with d2 >= E2[k]: 0 .. 8; a NaN d2 gives bin 0
+ *   type pair    for every type a set in tm[u] and b set in tm[v]: lo = min(a, b), hi = max(a, b), p = lo * (15 - lo) / 2 + (hi - lo): 0 .. 27
+ *   bit          j = p * PMX_LFP_BINS + bin (0 .. 251) is set: bit j % 64 of word j / 64. Bits 252 .. 255 are always 0
+ *   conformers   conformer_dev == NULL or conformer_dev[i] == -1: a bit is set when any conformer c < C sets it - the union, what the
+ *                ligand can present; conformer_dev[i] = c >= 0: that conformer alone - a hit as posed (pmx_explain's best_conformer, say)
+ * Outputs, per ligand:
+ *   fingerprint_dev  uint64 [count][PMX_FINGERPRINT_WORDS]
+ *   type_count_dev   uint8 [count][8] or NULL: for t = 0 .. 6 the number of nodes with type t in their mask; entry [7] is n
+ *   status_dev       int32 [count] or NULL: PMX_LIGAND_OK; PMX_LIGAND_UNSUPPORTED for a record pmx_score reports so by its header (more than
+ *                    PMX_MAX_LIGAND_NODES nodes or PMX_MAX_LIGAND_CLUSTERS clusters, no conformer or more than PMX_MAX_CONFORMERS - header-only
+ *                    records included): fingerprint and counts are 0; PMX_LIGAND_KEY_INVALID where conformer_dev[i] < -1 or >= C: the
+ *                    fingerprint is 0, the counts are still written. A supported record with n < 2 is OK with an empty fingerprint.
+ * first + count > n_ligands is PMX_ERR_INVALID; count = 0 succeeds. Stream-ordered like pmx_score (enqueued, no synchronisation), no work
+ * buffer. One wavefront per ligand; OR is order-free, so the same bits come out however the work is laid out.
+ */
+#define PMX_LFP_BINS 9
+int pmx_library_fingerprints(const pmx_library *lib, uint64_t first, uint64_t count, const int32_t *conformer_dev /* [count] or NULL */,
+                             uint64_t *fingerprint_dev /* [count][PMX_FINGERPRINT_WORDS] */, uint8_t *type_count_dev /* [count][8] or NULL */,
+                             int32_t *status_dev /* [count] or NULL */, void *stream);
+
+/*
+ * Similarity search (pmx_ligand_fp.hip): nq query fingerprints against a list of n, of any length - pmx_fingerprint_tanimoto stops at
+ * 65536 rows a side, a library has 10^6 or more.
+ *   out_dev[q][i]   float32 [nq][out_stride]: sim(query[q], fp[i]) exactly as pmx_fingerprint_tanimoto defines it - one float32 division,
+ *                   1.0f when both sets are empty. The layout pmx_topk (a row) and pmx_enrichment (col_stride = out_stride) take as it is
+ *   fused_dev[i]    float32 [n] or NULL: the maximum over q - MAX fusion, the usual rule for several reference ligands
+ * n < 2^31, 1 <= nq <= PMX_SEARCH_MAX_QUERIES and out_stride >= n, otherwise PMX_ERR_INVALID; n = 0 succeeds and writes nothing. The
+ * pointers are memory of `device`. Each library fingerprint is read once for all queries (a thread per fingerprint). Stream-ordered, no
+ * synchronisation.
+ */
+#define PMX_SEARCH_MAX_QUERIES 64
+int pmx_fingerprint_search(const uint64_t *query_dev /* [nq][PMX_FINGERPRINT_WORDS] */, uint32_t nq, const uint64_t *fp_dev /* [n][PMX_FINGERPRINT_WORDS] */,
+                           uint64_t n, float *out_dev /* [nq][out_stride] */, uint64_t out_stride, float *fused_dev /* [n] or NULL */, int device, void *stream);
+
+/*
  * Retrospective validation (pmx_enrich.hip): does a model, under given type weights, rank known binders above decoys? Per column of scores
  * over one labelled list, and per bootstrap resample of the list, the integers and sums from which the host derives AUROC, enrichment
  * factors and BEDROC. The specification is this comment (the reference has no counterpart); tests/enrichment_ref.py restates it in NumPy.

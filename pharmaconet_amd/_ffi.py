@@ -222,6 +222,14 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
     ),
+    "pmx_library_fingerprints": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "pmx_fingerprint_search": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
+    ),
     "pmx_score_stats_get": (ctypes.c_int, [ctypes.POINTER(ScoreStats)]),
     "pmx_set_profiling": (ctypes.c_int, [ctypes.c_int]),
 }

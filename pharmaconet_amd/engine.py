@@ -17,8 +17,8 @@ from .constants import weights_vector
 from .library import PackedLibrary, as_packed_library
 from .validation import ENRICH_TILE, FLOAT64_REFUSED, MAX_BOOTSTRAP, MAX_COLUMNS, POISSON1_CDF64, Enrichment, cutoffs_ppm  # noqa: F401  (the table and the tile of include/pmx.h)
 
-__all__ = ["Alignment", "Attribution", "DeviceLibrary", "Enrichment", "Explanation", "PanelResult", "ScreeningResult", "align", "attribute", "enrichment", "explain", "score_one",
-           "screen", "screen_multi", "sweep", "topk", "device_model", "last_score_stats"]
+__all__ = ["Alignment", "Attribution", "DeviceLibrary", "Enrichment", "Explanation", "LigandFingerprints", "PanelResult", "ScreeningResult", "SimilarityResult", "align", "attribute",
+           "enrichment", "explain", "score_one", "screen", "screen_multi", "similar", "sweep", "topk", "device_model", "last_score_stats"]
 
 
 def _torch():
@@ -196,11 +196,75 @@ class DeviceLibrary:
         offsets, data = self.buffers()
         return PackedLibrary(offsets.cpu().numpy().view(np.uint64).copy(), data[: self.num_bytes].cpu().numpy().copy())
 
+    def fingerprints(self, first: int = 0, count: int | None = None, conformers=None) -> "LigandFingerprints":
+        """The ligand-side pharmacophore fingerprints and type census of ligands `[first, first + count)` (`pmx_library_fingerprints`,
+        csrc/pmx_ligand_fp.hip; the definition is in include/pmx.h). `conformers`: None for the union over a ligand's conformers - what it
+        can present - or per ligand a conformer index (a list, a NumPy array or an int32 device tensor; -1 is the union again) - a hit as
+        posed. Enqueued on torch's current stream, nothing is read back. The union fingerprints of the whole library are kept on the
+        object (32 bytes a ligand) until `close`."""
+        torch = _torch()
+        whole = first == 0 and count in (None, self.num_ligands) and conformers is None
+        if whole and getattr(self, "_fingerprints", None) is not None:
+            return self._fingerprints
+        count = self.num_ligands - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > self.num_ligands:
+            raise IndexError(f"ligands {first} .. {first + count} of a library of {self.num_ligands}")
+        tdev = torch.device("cuda", self.device)
+        conf = None
+        if conformers is not None:
+            conf = conformers if isinstance(conformers, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(conformers, dtype=np.int32).reshape(-1)))
+            conf = conf.to(tdev).to(torch.int32).reshape(-1).contiguous()
+            if int(conf.numel()) != count:
+                raise ValueError(f"{int(conf.numel())} conformers for {count} ligands")
+        with torch.cuda.device(tdev):
+            bits = torch.empty((count, _FP_WORDS), dtype=torch.int64, device=tdev)
+            counts = torch.empty((count, 8), dtype=torch.uint8, device=tdev)
+            status = torch.empty(count, dtype=torch.int32, device=tdev)
+            stream = ctypes.c_void_p(torch.cuda.current_stream(tdev).cuda_stream)
+            _ffi.check(_ffi.load().pmx_library_fingerprints(self.handle, first, count, conf.data_ptr() if conf is not None and count else None, bits.data_ptr() if count else None,
+                                                            counts.data_ptr() if count else None, status.data_ptr() if count else None, stream))
+        out = LigandFingerprints(bits=bits, type_counts=counts, status=status, first=first, device=self.device)
+        if whole:
+            self._fingerprints = out
+        return out
+
+    def where(self, min_counts=None, max_counts=None, max_nodes: int | None = None):
+        """The ligands whose type census passes, as an int64 device tensor of library indices, ascending - ready for `select` and
+        `screen(indices=...)`. `min_counts` / `max_counts`: per type the least / most nodes that carry it, as a dict keyed by type name
+        (`TYPE_NAMES`, as `weights` are given) or a sequence of seven; `max_nodes`: the most nodes. Ligands the fingerprint pass reports
+        with a non-zero status (they cannot be scored either) never pass. A few torch operations on `fingerprints().type_counts`."""
+        torch = _torch()
+        from .constants import TYPE_ID
+
+        fps = self.fingerprints()
+        census = fps.type_counts.to(torch.int32)
+        keep = fps.status == 0
+
+        def seven(bounds, what):
+            if isinstance(bounds, dict):
+                unknown = [k for k in bounds if k not in TYPE_ID]
+                if unknown:
+                    raise ValueError(f"{what}: unknown pharmacophore type {unknown[0]!r}")
+                return {TYPE_ID[k]: int(v) for k, v in bounds.items()}
+            vals = list(bounds)
+            if len(vals) != _ffi.NUM_TYPES:
+                raise ValueError(f"{what}: a dict keyed by type name, or seven numbers")
+            return {t: int(v) for t, v in enumerate(vals)}
+
+        for t, v in (seven(min_counts, "min_counts") if min_counts is not None else {}).items():
+            keep = keep & (census[:, t] >= v)
+        for t, v in (seven(max_counts, "max_counts") if max_counts is not None else {}).items():
+            keep = keep & (census[:, t] <= v)
+        if max_nodes is not None:
+            keep = keep & (census[:, 7] <= int(max_nodes))
+        return torch.nonzero(keep).reshape(-1)
+
     def close(self) -> None:
         if getattr(self, "handle", None):
             _ffi.load().pmx_library_destroy(self.handle)
             self.handle = None
         self._adopted = None
+        self._fingerprints = None
 
     def __del__(self):
         try:
@@ -378,6 +442,49 @@ class ScreeningResult:
         sizes = np.bincount(leader_of[leader_of >= 0], minlength=len(prof)).astype(np.int64)
         return DiverseHits(indices=prof.indices[leaders], scores=ex.scores[prof.rows[leaders]], cluster_size=sizes[leaders],
                            leaders=leaders, leader_of=leader_of, pool=prof.indices, profile=prof)
+
+    def diverse_ligands(self, k: int, pool: int | None = None, threshold: float = 0.7, library=None) -> "DiverseHits":
+        """The k first hits of this screen that are not the same ligand again: `diverse` with the ligand's own fingerprint in place of the
+        binding mode's. The best `pool` hits (`diverse`'s rule: default min(len, max(8 k, 1024), 65536), hits with a non-zero status
+        left out) are gathered (`DeviceLibrary.select`), fingerprinted over all their conformers (`DeviceLibrary.fingerprints`) and run
+        through `LigandFingerprints.leaders(threshold)` in rank order. Two analogues in two binding modes are one cluster here and two
+        for `diverse`; two scaffolds in one mode the other way round. `profile` of the result is None."""
+        if k <= 0:
+            raise ValueError("k must be positive")
+        _, library, _ = self._scored(self.model, library, None)
+        n = int(self.scores.numel())
+        pool = min(n, max(8 * k, 1024), 65536) if pool is None else int(pool)
+        if not 0 < pool <= 65536:
+            raise ValueError("pool: 1 to 65536 hits")
+        sc, st = self.scores.cpu().numpy().astype(np.float64), self.status.cpu().numpy()
+        key = np.where(st != 0, -np.inf, np.nan_to_num(sc, nan=-np.inf))
+        pos = np.lexsort((np.arange(n), -key))[:pool]  # (the order of `_best`)
+        pos = pos[st[pos] == 0]
+        idx = (self.indices.cpu().numpy()[pos] if self.indices is not None else pos + self.first).astype(np.int64)
+        with _resident(library) as dlib:
+            sub = dlib.select(idx)
+            try:
+                leaders, leader_of = sub.fingerprints().leaders(threshold=threshold, max_leaders=min(k, 2048))
+            finally:
+                sub.close()
+        sizes = np.bincount(leader_of[leader_of >= 0], minlength=len(idx)).astype(np.int64)
+        return DiverseHits(indices=idx[leaders].astype(np.uint64), scores=sc[pos][leaders], cluster_size=sizes[leaders], leaders=leaders, leader_of=leader_of,
+                           pool=idx.astype(np.uint64), profile=None)
+
+    def similar_to(self, rank: int, k: int = 100, library=None) -> "SimilarityResult":
+        """The library's neighbours of this screen's hit at `rank` (0 is the best hit): `similar` with that ligand as the one query,
+        fingerprinted at the conformer that explains its score (`Explanation.best_conformer`) - the hit as it is posed - against the union
+        fingerprints of the library."""
+        model, library, weights = self._scored(None, library, None)
+        best = self._best(int(rank) + 1)
+        if rank < 0 or len(best) <= rank:
+            raise IndexError(f"this screen has no hit at rank {rank}")
+        hit = int(best[rank])
+        with _resident(library) as dlib:
+            ex = explain(model, dlib, [hit], weights=weights)
+            if int(ex.status[0]) != 0:
+                raise ValueError(f"the hit at rank {rank} was not scored (status {int(ex.status[0])})")
+            return similar(dlib, query_indices=[hit], query_conformers=[int(ex.best_conformer[0])], k=k)
 
 
 def _weights_array(weights):
@@ -1236,6 +1343,7 @@ def align(model, library, indices, conformers, keys, weights: dict[str, float] |
 
 
 _MAX_MODEL_NODES, _FP_WORDS, _MAX_LEADERS = 256, 4, 2048  # PMX_MAX_MODEL_NODES, PMX_FINGERPRINT_WORDS, PMX_MAX_LEADERS
+_MAX_QUERIES = 64  # PMX_SEARCH_MAX_QUERIES
 
 
 def _fingerprint_tensor(fp, tdev):
@@ -1394,6 +1502,123 @@ def hotspots(model, library, indices, conformers, keys, weights: dict[str, float
     return HotspotProfile(indices=idx, conformers=conf, total=tt.copy() if n else np.zeros(0), share=[sh[i, :nm].copy() for i in range(n)],
                           terms=[tc[i, :nm].astype(np.int64) for i in range(n)], passes=[pc[i, :nm].astype(np.int64) for i in range(n)],
                           fingerprint=fp.cpu().numpy()[:n].view(np.uint64).copy().reshape(n, FW), levels=out_lv, status=st, device=where[0])
+
+
+@dataclass
+class LigandFingerprints:
+    """What `DeviceLibrary.fingerprints` returns: one row per ligand, on the device (definitions: `pmx_library_fingerprints` in include/pmx.h).
+
+    bits         torch.int64 [n, 4]: the 256-bit set - bit j % 64 of word j // 64 is (type pair j // 9, distance bin j % 9)
+    type_counts  torch.uint8 [n, 8]: per type the nodes that carry it; column 7 is the number of nodes
+    status       torch.int32 [n]: 0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer of the ligand)"""
+
+    bits: "object"
+    type_counts: "object"
+    status: "object"
+    first: int = 0
+    device: "int | None" = None
+
+    def __len__(self) -> int:
+        return int(self.status.numel())
+
+    def numpy(self):
+        """(fingerprints uint64 [n, 4], type counts uint8 [n, 8], status int32 [n]) on the host (waits for the stream)."""
+        n = len(self)
+        return self.bits.cpu().numpy().view(np.uint64).reshape(n, _FP_WORDS), self.type_counts.cpu().numpy().reshape(n, 8), self.status.cpu().numpy()
+
+    def similarity(self, other: "LigandFingerprints | None" = None) -> np.ndarray:
+        """Tanimoto similarity of the rows, on the GPU (`fingerprint_similarity`): float32 [n, m] against `other`'s rows (default: these);
+        at most 65536 rows a side - `similar` has no such limit."""
+        return fingerprint_similarity(self.numpy()[0], None if other is None else other.numpy()[0], device=self.device)
+
+    def leaders(self, threshold: float = 0.7, max_leaders: int = _MAX_LEADERS):
+        """Sphere exclusion over the rows in their order (`fingerprint_leaders`): (leaders, leader_of); at most 65536 rows."""
+        return fingerprint_leaders(self.numpy()[0], threshold=threshold, max_leaders=max_leaders, device=self.device)
+
+
+@dataclass
+class SimilarityResult:
+    """What `similar` returns, on the device.
+
+    scores        torch.float32 [nq, n]: row q is the Tanimoto similarity of every ligand of the library to query q
+    fused         torch.float32 [n]: the maximum over the queries (MAX fusion)
+    status        torch.int32 [n]: the library fingerprints' status; a ligand with a non-zero one has an empty fingerprint
+    topk_scores, topk_indices   the k best of `fused` (`pmx_topk`: ties in library order), None without k
+    query_indices int64 [nq] for queries named as ligands of the library itself, else None"""
+
+    scores: "object"
+    fused: "object"
+    status: "object"
+    topk_scores: "object | None" = None
+    topk_indices: "object | None" = None
+    query_indices: "np.ndarray | None" = None
+    columns: "object | None" = None  # [nq + 1, n]: `scores` and `fused` as one buffer (what `enrichment` ranks)
+
+    def ranking(self) -> list[tuple[int, float]]:
+        """[(ligand index, fused similarity)] of the top-k, best first."""
+        assert self.topk_scores is not None and self.topk_indices is not None
+        return [(int(i), float(s)) for i, s in zip(self.topk_indices.cpu().numpy(), self.topk_scores.cpu().numpy()) if i >= 0]
+
+    def enrichment(self, labels, **kwargs) -> "Enrichment":
+        """`enrichment` of the similarities: one column per query and a last one, named "fused", for their maximum - the baseline a
+        model's `ScreeningResult.enrichment` is compared with (`Enrichment.delta` is paired when both are columns of one call: `columns`
+        is a float32 [nq + 1, n] buffer to put next to a model's scores). Ligands that are queries themselves (`query_indices`) are
+        labelled 2, not counted: a query scores 1.0 against itself."""
+        torch = _torch()
+        nq, n = int(self.scores.shape[0]), int(self.scores.shape[1])
+        if nq + 1 > MAX_COLUMNS:
+            raise ValueError(f"enrichment of a similarity search: at most {MAX_COLUMNS - 1} queries (a column each and one for their maximum)")
+        lab = _labels_tensor(labels, n, self.scores.device).clone()
+        if self.query_indices is not None and len(self.query_indices):
+            lab[torch.from_numpy(np.asarray(self.query_indices, dtype=np.int64)).to(lab.device)] = 2
+        kwargs.setdefault("columns", list(range(nq)) + ["fused"])
+        return enrichment(self.columns, lab, status=self.status, **kwargs)
+
+
+def similar(library, queries=None, query_indices=None, query_conformers=None, k: int | None = 100, device=None) -> SimilarityResult:
+    """Ligand-based search: which ligands of `library` look like these known binders? Every ligand's own pharmacophore fingerprint (the
+    union over its conformers, `DeviceLibrary.fingerprints`, kept on a `DeviceLibrary` between calls) against 1 to 64 query fingerprints
+    (`pmx_fingerprint_search`: each library fingerprint is read once), and the k best by the maximum over the queries (`pmx_topk`).
+
+    The queries are `queries` - a `PackedLibrary`, a `DeviceLibrary` or whatever `as_packed_library` accepts, of reference ligands - or
+    `query_indices` - ligands of `library` itself. `query_conformers`: per query a conformer to fingerprint it at (-1 or None: the union).
+    Enqueued on torch's current stream; nothing is read back."""
+    torch = _torch()
+    lib = _ffi.load()
+    if (queries is None) == (query_indices is None):
+        raise ValueError("similar: either `queries` or `query_indices`")
+    with _resident(library, device) as dlib:
+        tdev = torch.device("cuda", dlib.device)
+        fps = dlib.fingerprints()
+        n = len(dlib)
+        qidx = None
+        if query_indices is not None:
+            qidx = np.ascontiguousarray(np.asarray(query_indices, dtype=np.int64).reshape(-1))
+            if qidx.size and (int(qidx.min()) < 0 or int(qidx.max()) >= n):
+                raise IndexError(f"query_indices outside the library's {n} ligands")
+            if query_conformers is None:
+                qbits = fps.bits[torch.from_numpy(qidx).to(tdev)].contiguous()
+            else:
+                sub = dlib.select(qidx)
+                try:
+                    qbits = sub.fingerprints(conformers=query_conformers).bits
+                finally:
+                    sub.close()
+        else:
+            with _resident(queries, dlib.device) as qlib:
+                qbits = qlib.fingerprints(conformers=query_conformers).bits
+        nq = int(qbits.shape[0])
+        if not 1 <= nq <= _MAX_QUERIES:
+            raise ValueError(f"similar: 1 to {_MAX_QUERIES} queries, not {nq}")
+        with torch.cuda.device(tdev):
+            columns = torch.empty((nq + 1, n), dtype=torch.float32, device=tdev)
+            stream = ctypes.c_void_p(torch.cuda.current_stream(tdev).cuda_stream)
+            _ffi.check(lib.pmx_fingerprint_search(qbits.data_ptr(), nq, fps.bits.data_ptr() if n else None, n, columns.data_ptr() if n else None, n,
+                                                  columns[nq].data_ptr() if n else None, dlib.device, stream))
+        result = SimilarityResult(scores=columns[:nq], fused=columns[nq], status=fps.status, query_indices=qidx, columns=columns)
+        if k is not None and n:
+            result.topk_scores, result.topk_indices = topk(columns[nq], int(k))
+    return result
 
 
 def last_score_stats() -> dict:

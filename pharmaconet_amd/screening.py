@@ -7,6 +7,7 @@ processes; needs OpenBabel like the reference) or a packed library file (`.pmxli
 Output: `path,score` CSV, best first, ties in library order (`screening.py:70-75`). Scoring runs on the GPU.
 `--panel MODEL ... --panel_out PATH` scores the best hits against other pockets; `--save_top K PATH` keeps them as a packed library.
 `--actives FILE --enrichment_out PATH` validates the model retrospectively: the library's ligands named in FILE are the actives, the rest decoys.
+`--similar_to NAME ... --similar_out PATH` lists the library's ligands most similar to the named ones by their own pharmacophore fingerprints.
 """
 
 from __future__ import annotations
@@ -56,6 +57,9 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--bedroc_alpha", type=float, default=20.0, metavar="A", help="BEDROC's alpha")
         cfg.add_argument("--bootstrap", type=int, default=0, metavar="B", help="bootstrap resamples behind the confidence intervals of --enrichment_out (0: none, at most 4096)")
         cfg.add_argument("--bootstrap_seed", type=int, default=0, metavar="S", help="seed of the bootstrap")
+        cfg.add_argument("--similar_to", action="append", default=[], metavar="NAME", help="ligand-based search: a ligand of the library (a name of the library, or its file stem) whose neighbours by ligand pharmacophore fingerprint are listed (repeatable: up to 64 queries, fused by maximum)")
+        cfg.add_argument("--similar_out", type=str, default=None, metavar="PATH", help="CSV `rank,path,similarity,<one column per query>` of the K most similar ligands (needed with --similar_to)")
+        cfg.add_argument("--similar_k", type=int, default=100, metavar="K", help="ligands in --similar_out")
         par = self.add_argument_group("parameter")
         par.add_argument("--hydrophobic", type=float, default=1.0, help="weight for hydrophobic carbon")
         par.add_argument("--aromatic", type=float, default=4.0, help="weight for aromatic ring")
@@ -184,6 +188,10 @@ def main(argv=None) -> None:
         parser.error("--enrichment_cut takes comma-separated percentages")
     if args.actives and (not enrichment_cut or len(enrichment_cut) > 64 or any(not 1e-6 <= c <= 1.0 for c in enrichment_cut)):
         parser.error("--enrichment_cut takes 1 to 64 percentages between 0.0001 and 100")
+    if bool(args.similar_to) != bool(args.similar_out):
+        parser.error("--similar_to NAME and --similar_out PATH go together")
+    if args.similar_to and not (len(args.similar_to) <= 64 and 0 < args.similar_k <= 65536):
+        parser.error("--similar_to takes up to 64 names, --similar_k 1 to 65536")
     if not 0 <= args.bootstrap <= 4096:
         parser.error("--bootstrap takes 0 to 4096")
     if not args.bedroc_alpha > 0:
@@ -211,11 +219,21 @@ def main(argv=None) -> None:
             labels = match_actives(Path(args.actives).read_text().splitlines(), names)
         except ValueError as e:
             parser.error(f"--actives {args.actives}: {e}")
+    if args.similar_to:
+        from .validation import match_actives
+
+        try:
+            match_actives(args.similar_to, names)  # (every name once, and each a ligand of the library)
+            queries = [int(np.flatnonzero(match_actives([q], names))[0]) for q in args.similar_to]
+        except ValueError as e:
+            parser.error(f"--similar_to: {str(e).replace('the actives file', '--similar_to')}")
     result = model.screen(lib, weights=weight, float64=True)  # (the reference writes the float64 `GraphMatcher.run()` returns)
     scores, status = result.scores.cpu().numpy(), result.status.cpu().numpy()
     write_csv(Path(args.out), names, scores, status)
     if args.actives:
         write_enrichment(Path(args.enrichment_out), result, labels, enrichment_cut, args.bedroc_alpha, args.bootstrap, args.bootstrap_seed)
+    if args.similar_to:
+        write_similar_csv(Path(args.similar_out), names, lib, queries, args.similar_to, args.similar_k)
     if args.explain > 0:
         out = Path(args.explain_out) if args.explain_out else Path(str(args.out) + ".explain.csv")
         write_explain_csv(out, names, scores, status, model, lib, weight, args.explain)
@@ -253,6 +271,20 @@ def write_enrichment(out: Path, result, labels: np.ndarray, cutoffs: list[float]
 
     en = enrichment(result.scores.to(torch.float32), labels, status=result.status, cutoffs=cutoffs, alpha=alpha, bootstrap=bootstrap, seed=seed)
     write_enrichment_csv(out, en)
+
+
+def write_similar_csv(out: Path, names: list[str], lib, queries: list[int], query_names: list[str], k: int) -> None:
+    """The k ligands of the library most similar to the query ligands by their own pharmacophore fingerprints (`engine.similar`: Tanimoto
+    similarity of the two-point fingerprints over all conformers), best first, ties in library order: the maximum over the queries and
+    one column per query, named by the query's file stem. The queries themselves are listed (each is 1.0 similar to itself)."""
+    from .engine import similar
+
+    res = similar(lib, query_indices=queries, k=min(k, len(names)))
+    order, fused, per_query = res.topk_indices.cpu().numpy(), res.topk_scores.cpu().numpy(), res.scores.cpu().numpy()
+    with open(out, "w") as w:
+        w.write("rank,path,similarity," + ",".join(Path(q).stem for q in query_names) + "\n")
+        for r, i in enumerate(order):
+            w.write(f"{r + 1},{names[int(i)]},{float(fused[r])}," + ",".join(str(float(v)) for v in per_query[:, int(i)]) + "\n")
 
 
 def _best_hits(scores: np.ndarray, status: np.ndarray, k: int) -> list[int]:
