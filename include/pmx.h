@@ -597,6 +597,61 @@ int pmx_fingerprint_search(const uint64_t *query_dev /* [nq][PMX_FINGERPRINT_WOR
                            uint64_t n, float *out_dev /* [nq][out_stride] */, uint64_t out_stride, float *fused_dev /* [n] or NULL */, int device, void *stream);
 
 /*
+ * Excluded volumes (pmx_pocket.hip): does a posed hit fit where pmx_align puts it? Every row of a call is a set of points under a rigid
+ * motion, checked against the atoms of the pocket: how deep the worst pair penetrates, how much overlaps in all, how many points clash and
+ * touch, and which residues are touched. The reference has no counterpart (it scores distances between pharmacophore points only); the
+ * specification is this comment, and tests/clash_ref.py restates it in NumPy.
+ *
+ * The pocket: pmx_pocket_create copies n <= PMX_POCKET_MAX_ATOMS atoms - float32 positions xyz[n][3] in the model's frame, radii radius[n]
+ * (the caller's: pharmaconet_amd/pocket.py uses Bondi's) and a group per atom (group[n], or NULL for "no group": 0xFFFF throughout) - to
+ * `device`. A group below 256 is a residue's bit of contact_fp; any other value is an atom outside the 256. n = 0 is allowed: a pocket
+ * without atoms. The copy is finished when the call returns. pmx_pocket_destroy frees it (NULL is allowed).
+ *
+ * The points of row i, one of two sources per call (both, or neither, is PMX_ERR_INVALID):
+ *   node mode    lib given, point_off_dev, points_dev and point_radius_dev NULL: the n_i nodes of library ligand ligands_dev[i] at conformer
+ *                conformer_dev[i], in record order, the record's float32 coordinates, each of radius point_radius
+ *   point mode   lib NULL: points_dev[point_off_dev[i] .. point_off_dev[i + 1]), float32 [.][3] - a whole molecule's atoms, say - with
+ *                radii point_radius_dev[.], or point_radius each where that pointer is NULL; ligands_dev and conformer_dev are not read
+ * Arithmetic, float64 with every operation rounded (no fused multiply-add), R = rot_dev[i] row-major, t = trans_dev[i], x widened:
+ *   posed point  p_k = ((R[k][0] x_0 + R[k][1] x_1) + R[k][2] x_2) + t_k
+ *   pair         point p of radius r_p, atom a at float32 y with radius r_a: dx, dy, dz = p - y; d = sqrt((dx dx + dy dy) + dz dz);
+ *                s = ((double)r_a + (double)r_p) - (double)tolerance; pen = s - d
+ *                the pair clashes iff pen > 0; it touches iff d < (double)contact
+ * Outputs, per row:
+ *   summary_dev     double [n][4]  [0] the largest pen over all pairs - negative when nothing clashes (the clearance), -inf with no point
+ *                                  or no atom; [1] the overlap: the sum of pen^2 over the clashing pairs; [2], [3] 0
+ *   count_dev       int32 [n][6]   [0] points; [1] points with a clashing pair; [2] clashing pairs; [3] points that touch some atom;
+ *                                  [4], [5] the point and the atom of summary[0] - the lowest point, then the lowest atom, among equals -
+ *                                  and -1 where there is no pair
+ *   point_pen_dev, point_atom_dev  per point its largest pen and the lowest-index atom that attains it (-inf and -1 for a pocket without
+ *                                  atoms). Node mode: double / int32 [n][PMX_MAX_LIGAND_NODES], NaN / -1 beyond the record's nodes; point
+ *                                  mode: [point_off_dev[n]], the layout of the points
+ *   contact_fp_dev  uint64 [n][PMX_FINGERPRINT_WORDS] or NULL: bit g % 64 of word g / 64 is set iff some atom of group g < 256 touches
+ *                                  some point of the row - the format pmx_fingerprint_tanimoto and pmx_fingerprint_leaders take
+ *   status_dev      int32 [n]      PMX_LIGAND_OK; node mode: PMX_LIGAND_UNSUPPORTED for an index outside the library and for a record that
+ *                                  pmx_score reports so by its header (header-only records included), PMX_LIGAND_KEY_INVALID when
+ *                                  conformer_dev[i] is not a conformer of the ligand (-1 is none); both modes: PMX_LIGAND_KEY_INVALID when
+ *                                  any of the row's 12 motion values is not finite - what pmx_align hands out for its own rows that are
+ *                                  not OK, so that such a row passes through with a status
+ * A row that is not OK has NaN in all of summary, counts of 0 with [4] = [5] = -1, NaN / -1 for every point it has room for, and an empty
+ * set. The overlap is summed per point in atom order, a lane's points in ascending order, the 64 lanes (point % 64) by a fixed butterfly:
+ * fixed-order sums, no floating-point atomic, the same bits on every run and for a row wherever it stands in a call.
+ * n <= PMX_EXPLAIN_MAX (otherwise PMX_ERR_INVALID); n = 0 succeeds and writes nothing. With n > 0 only contact_fp_dev may be NULL among the
+ * outputs; point_radius, tolerance and contact must be finite; in node mode the library is on the pocket's device. The pointers are memory of
+ * that device. Stream-ordered like pmx_align (enqueued, no synchronisation), no work buffer. One wavefront per row, a lane per point.
+ */
+#define PMX_POCKET_MAX_ATOMS 65536
+typedef struct pmx_pocket pmx_pocket;
+int pmx_pocket_create(const float *xyz /* [n][3] */, const float *radius /* [n] */, const uint16_t *group /* [n] or NULL */, uint32_t n, int device,
+                      pmx_pocket **out);
+int pmx_pocket_destroy(pmx_pocket *pocket);
+int pmx_pose_clash(const pmx_pocket *pocket, const pmx_library *lib /* NULL in point mode */, const uint64_t *ligands_dev, const int32_t *conformer_dev /* node mode: [n] each */,
+                   const uint64_t *point_off_dev /* [n + 1] */, const float *points_dev /* [.][3] */, const float *point_radius_dev /* [.] or NULL */,
+                   const double *rot_dev /* [n][9] */, const double *trans_dev /* [n][3] */, uint32_t n, float point_radius, float tolerance, float contact,
+                   double *summary_dev /* [n][4] */, int32_t *count_dev /* [n][6] */, double *point_pen_dev, int32_t *point_atom_dev,
+                   uint64_t *contact_fp_dev /* [n][PMX_FINGERPRINT_WORDS] or NULL */, int32_t *status_dev, void *stream);
+
+/*
  * Retrospective validation (pmx_enrich.hip): does a model, under given type weights, rank known binders above decoys? Per column of scores
  * over one labelled list, and per bootstrap resample of the list, the integers and sums from which the host derives AUROC, enrichment
  * factors and BEDROC. The specification is this comment (the reference has no counterpart); tests/enrichment_ref.py restates it in NumPy.

@@ -17,7 +17,7 @@ from .constants import weights_vector
 from .library import PackedLibrary, as_packed_library
 from .validation import ENRICH_TILE, FLOAT64_REFUSED, MAX_BOOTSTRAP, MAX_COLUMNS, POISSON1_CDF64, Enrichment, cutoffs_ppm  # noqa: F401  (the table and the tile of include/pmx.h)
 
-__all__ = ["Alignment", "Attribution", "DeviceLibrary", "Enrichment", "Explanation", "LigandFingerprints", "PanelResult", "ScreeningResult", "SimilarityResult", "align", "attribute",
+__all__ = ["Alignment", "Attribution", "ClashReport", "DeviceLibrary", "FittingHits", "Enrichment", "Explanation", "LigandFingerprints", "PanelResult", "ScreeningResult", "SimilarityResult", "align", "attribute", "clashes",
            "enrichment", "explain", "score_one", "screen", "screen_multi", "similar", "sweep", "topk", "device_model", "last_score_stats"]
 
 
@@ -470,6 +470,30 @@ class ScreeningResult:
         sizes = np.bincount(leader_of[leader_of >= 0], minlength=len(idx)).astype(np.int64)
         return DiverseHits(indices=idx[leaders].astype(np.uint64), scores=sc[pos][leaders], cluster_size=sizes[leaders], leaders=leaders, leader_of=leader_of,
                            pool=idx.astype(np.uint64), profile=None)
+
+    def fitting(self, k: int, pool: int | None = None, max_clashing: int = 0, pocket=None, atoms=None, model=None, library=None,
+                weights: dict[str, float] | None = None, **kw) -> "FittingHits":
+        """The k first hits of this screen whose pose fits the pocket: the best `pool` hits (default min(len, max(8 k, 1024), 65536)) are
+        explained, posed at their best conformer (`Explanation.poses`) and checked against the protein's atoms (`Alignment.clashes`); a hit
+        passes with status 0 and at most `max_clashing` clashing points. In rank order; a hit that was not scored, or whose pose is not OK,
+        never passes. `pocket`: a `pocket.PocketAtoms` (default: the protein the model carries). `atoms`: a function from a library index to
+        the `LigandFeatures` / `Ligand` of that ligand, for a check of the molecule's atoms; without it the pharmacophore nodes are checked.
+        Further arguments (`tolerance`, `contact`, `node_radius`) as `clashes` takes them."""
+        if k <= 0:
+            raise ValueError("k must be positive")
+        model, library, weights = self._scored(model, library, weights)
+        n = int(self.scores.numel())
+        pool = min(n, max(8 * k, 1024), 65536) if pool is None else int(pool)
+        if not 0 < pool <= 65536:
+            raise ValueError("pool: 1 to 65536 hits")
+        pocket = model.pocket_atoms() if pocket is None else pocket
+        with _resident(library) as dlib:
+            ex = explain(model, dlib, self._best(pool), weights=weights)
+            al = ex.poses(model, dlib, weights=weights)
+            rep = al.clashes(pocket, dlib, atoms=None if atoms is None else [atoms(int(i)) for i in al.indices], **kw)
+        passing = np.flatnonzero(rep.ok(max_clashing) & (al.status == 0))[:k]
+        return FittingHits(indices=al.indices[passing].astype(np.uint64), scores=ex.scores[al.rows[passing]], ranks=al.rows[passing].astype(np.int64), rows=passing,
+                           pool=ex.indices, poses=al, report=rep)
 
     def similar_to(self, rank: int, k: int = 100, library=None) -> "SimilarityResult":
         """The library's neighbours of this screen's hit at `rank` (0 is the best hit): `similar` with that ligand as the one query,
@@ -1314,6 +1338,31 @@ class Alignment:
         """Row i's motion applied to any [..., 3] array of points of the conformer's frame - a whole molecule's atoms, say: positions @ R.T + t."""
         return np.asarray(positions, dtype=np.float64) @ self.rotation[i].T + self.translation[i]
 
+    def clashes(self, pocket_or_model, library=None, atoms=None, **kw) -> "ClashReport":
+        """These poses checked against the pocket's atoms (`clashes`): row i of the report is row i of the alignment, and a row that is
+        not OK passes through with status 4. `pocket_or_model`: a `pocket.PocketAtoms`, or a model that carries its protein
+        (`PharmacophoreModel.pocket_atoms`). With `library` alone the rows' own pharmacophore nodes are checked (node mode: nothing but the
+        resident records is read). With `atoms` - per row the `LigandFeatures` / `Ligand` the record was packed from - the molecule's atoms
+        at the row's conformer are, hydrogens left out, with Bondi radii by atomic number (point mode). Further arguments as `clashes` takes them."""
+        from .pocket import PocketAtoms, atomic_number_radii
+
+        pocket = pocket_or_model if isinstance(pocket_or_model, PocketAtoms) else pocket_or_model.pocket_atoms()
+        if atoms is None:
+            if library is None:
+                raise ValueError("Alignment.clashes: the library the rows are ligands of, or `atoms`")
+            return clashes(pocket, library=library, indices=self.indices, conformers=self.conformers, rotation=self.rotation, translation=self.translation, **kw)
+        if len(atoms) != len(self):
+            raise ValueError(f"{len(atoms)} molecules for {len(self)} rows")
+        points, radii = [], []
+        for i, mol in enumerate(atoms):
+            pos = np.asarray(mol.atom_positions, dtype=np.float32)  # [n_atoms, C, 3]
+            c = int(self.conformers[i])
+            z = _atomic_numbers(mol)
+            heavy = z > 1  # (hydrogens are not checked: the pocket's are not read either)
+            points.append(pos[heavy, c] if 0 <= c < pos.shape[1] else np.zeros((0, 3), np.float32))  # (not a conformer: the row's status says so already)
+            radii.append(atomic_number_radii(z[heavy])[: len(points[-1])])
+        return clashes(pocket, rotation=self.rotation, translation=self.translation, points=points, point_radii=radii, **kw)
+
 
 def align(model, library, indices, conformers, keys, weights: dict[str, float] | None = None, device=None) -> Alignment:
     """The rigid fit (`pmx_align`, csrc/pmx_rows.hip) of library ligand `indices[i]`'s conformer `conformers[i]` under the match `keys[i]`, rows as
@@ -1340,6 +1389,198 @@ def align(model, library, indices, conformers, keys, weights: dict[str, float] |
     return Alignment(indices=idx, conformers=conf, rotation=rot.cpu().numpy()[:n].copy(), translation=trans.cpu().numpy()[:n].copy(),
                      rmsd=ft[:, 2].copy(), rmsd_nodes=ft[:, 3].copy(), weight=ft[:, 0].copy(), sse=ft[:, 1].copy(), scale=ft[:, 4].copy(), gap=ft[:, 5].copy(),
                      node=[nd[i, : nn[i]].copy() for i in range(n)], n_nodes=cn[:, 0].copy(), n_pairs=cn[:, 1].copy(), levels=out_lv, status=st)
+
+
+@dataclass
+class FittingHits:
+    """What `ScreeningResult.fitting` returns.
+
+    indices, scores  the first k hits of the pool whose pose passes, best first: indices in the library that was screened, and their scores
+    ranks            the hit's rank in the pool (0 is the screen's best hit)
+    rows             the hit's row of `poses` and `report`
+    pool             the library indices of the pool, best first
+    poses, report    the `Alignment` and the `ClashReport` of every posed hit of the pool (hits that were not scored have no row)"""
+
+    indices: np.ndarray
+    scores: np.ndarray
+    ranks: np.ndarray
+    rows: np.ndarray
+    pool: np.ndarray
+    poses: "Alignment"
+    report: "ClashReport"
+
+    def __len__(self) -> int:
+        return len(self.indices)
+
+
+def _atomic_numbers(mol) -> np.ndarray:
+    """Atomic numbers of a `LigandFeatures` (`atomic_nums`) or a `Ligand` (its toolkit answers)."""
+    z = getattr(mol, "atomic_nums", None)
+    if z is None:
+        z = mol.answers["atomic_num"]
+    return np.asarray(z, dtype=np.int64).reshape(-1)
+
+
+@dataclass
+class ClashReport:
+    """What `clashes` returns: one row per posed set of points (definitions: `pmx_pose_clash` in include/pmx.h).
+
+    clearance[i]    float64: the largest penetration over all (point, atom) pairs - negative when nothing clashes, -inf without a pair
+    overlap[i]      float64: the sum of penetration^2 over the clashing pairs
+    n_points[i], n_clashing[i], n_pairs[i], n_contacts[i]   points, points with a clashing pair, clashing pairs, points that touch an atom
+    worst[i]        (point, atom) of clearance[i]; (-1, -1) without a pair
+    point_penetration[i], point_atom[i]   per point its largest penetration and the atom that attains it
+    contact_fingerprint   uint64 [n, 4]: bit g says an atom of residue group g touches the row (`PocketAtoms.residue_labels[g]`)
+    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer of the ligand, or a motion that is not
+                    finite - a row of an `Alignment` that was not OK); such a row has NaN, zero counts and an empty fingerprint"""
+
+    clearance: np.ndarray
+    overlap: np.ndarray
+    n_points: np.ndarray
+    n_clashing: np.ndarray
+    n_pairs: np.ndarray
+    n_contacts: np.ndarray
+    worst: np.ndarray
+    point_penetration: list
+    point_atom: list
+    contact_fingerprint: np.ndarray
+    status: np.ndarray
+    device: "int | None" = None  # where `similarity` and `leaders` run
+
+    def __len__(self) -> int:
+        return len(self.status)
+
+    def ok(self, max_clashing: int = 0) -> np.ndarray:
+        """bool [n]: status 0 and at most `max_clashing` points with a clashing pair."""
+        return (self.status == 0) & (self.n_clashing <= int(max_clashing))
+
+    def residues(self, i: int, pocket) -> list[str]:
+        """The residues row i touches, by `pocket`'s labels."""
+        return pocket.residues(self.contact_fingerprint[i])
+
+    def atom_label(self, i: int, pocket) -> str:
+        """The pocket atom of row i's worst pair (`A:CYS12:SG`); '' without a pair."""
+        return pocket.atom_label(int(self.worst[i, 1]))
+
+    def similarity(self, other: "ClashReport | None" = None) -> np.ndarray:
+        """Tanimoto similarity of the contact fingerprints, on the GPU (`fingerprint_similarity`)."""
+        return fingerprint_similarity(self.contact_fingerprint, None if other is None else other.contact_fingerprint, device=self.device)
+
+    def leaders(self, threshold: float = 0.7, max_leaders: int = 2048):
+        """Sphere exclusion over the rows in their order by contact fingerprint (`fingerprint_leaders`): (leaders, leader_of)."""
+        return fingerprint_leaders(self.contact_fingerprint, threshold=threshold, max_leaders=max_leaders, device=self.device)
+
+
+class _PocketHandle:
+    def __init__(self, pocket, device: int):
+        handle = ctypes.c_void_p()
+        xyz, radius, group = (np.ascontiguousarray(pocket.xyz, dtype=np.float32), np.ascontiguousarray(pocket.radius, dtype=np.float32),
+                              np.ascontiguousarray(pocket.group, dtype=np.uint16))
+        n = len(radius)
+        _ffi.check(_ffi.load().pmx_pocket_create(xyz.ctypes.data if n else None, radius.ctypes.data if n else None, group.ctypes.data if n else None, n, device,
+                                                 ctypes.byref(handle)))
+        self.handle, self.device = handle, device
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                _ffi.load().pmx_pocket_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def device_pocket(pocket, device=None) -> _PocketHandle:
+    """The device copy of a `pocket.PocketAtoms`, made once per (pocket, device) and freed with the object."""
+    dev = _device_index(device)
+    if dev not in pocket._device:
+        pocket._device[dev] = _PocketHandle(pocket, dev)
+    return pocket._device[dev]
+
+
+def clashes(pocket, library=None, indices=None, conformers=None, rotation=None, translation=None, points=None, point_radii=None, node_radius: float = 1.0,
+            tolerance: float = 0.5, contact: float = 4.5, device=None) -> ClashReport:
+    """Posed rows against the pocket's atoms (`pmx_pose_clash`, csrc/pmx_pocket.hip): row i is a set of points moved by `rotation[i]`
+    [3, 3] and `translation[i]` [3] - what `Alignment` holds - and a pair (point, atom) clashes when the two spheres overlap by more than
+    `tolerance`, touches when the centres are closer than `contact`.
+      node mode   `library` (a `DeviceLibrary` or anything `as_packed_library` accepts), `indices`, `conformers`: the pharmacophore nodes of
+                  library ligand indices[i] at conformer conformers[i], each a sphere of `node_radius`
+      point mode  `points`: a list of [m_i, 3] arrays, any points of the conformer's frame - a whole molecule's atoms; `point_radii`: a
+                  matching list of radii (`pocket.atomic_number_radii` makes them from atomic numbers), or None for `node_radius` each
+    At most 65536 rows. Runs on torch's current stream of the device and waits for it."""
+    torch = _torch()
+    lib = _ffi.load()
+    rot = np.ascontiguousarray(np.asarray(rotation, dtype=np.float64).reshape(-1, 3, 3))
+    trans = np.ascontiguousarray(np.asarray(translation, dtype=np.float64).reshape(-1, 3))
+    n = len(rot)
+    if len(trans) != n:
+        raise ValueError("rotation and translation differ in length")
+    if n > 65536:
+        raise ValueError("at most 65536 rows per clashes call (PMX_EXPLAIN_MAX)")
+    node_mode = library is not None
+    if node_mode == (points is not None):
+        raise ValueError("clashes: a library with indices and conformers, or points - one of the two")
+    if node_mode:
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+        conf = np.ascontiguousarray(np.clip(np.asarray(conformers, dtype=np.int64).reshape(-1), -1, 2**31 - 1).astype(np.int32))
+        if len(idx) != n or len(conf) != n:
+            raise ValueError("indices, conformers and the motions differ in length")
+        if (idx < 0).any():
+            raise ValueError("negative ligand index")
+    else:
+        if len(points) != n:
+            raise ValueError(f"{len(points)} point sets for {n} motions")
+        pts = [np.asarray(p, dtype=np.float32).reshape(-1, 3) for p in points]
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(p) for p in pts])
+        flat = np.ascontiguousarray(np.concatenate(pts + [np.zeros((1, 3), np.float32)]))  # (never an empty buffer)
+        rad = None
+        if point_radii is not None:
+            if len(point_radii) != n:
+                raise ValueError(f"{len(point_radii)} radius lists for {n} point sets")
+            rs = [np.asarray(r, dtype=np.float32).reshape(-1) for r in point_radii]
+            if any(len(r) != len(p) for r, p in zip(rs, pts)):
+                raise ValueError("a list of radii differs in length from its points")
+            rad = np.ascontiguousarray(np.concatenate(rs + [np.zeros(1, np.float32)]))
+    m = max(n, 1)
+    with contextlib.ExitStack() as stack:
+        dlib = stack.enter_context(_resident(library, device)) if node_mode else None
+        dev = dlib.device if node_mode else _device_index(device)
+        ph = device_pocket(pocket, dev)
+        tdev = torch.device("cuda", dev)
+        with torch.cuda.device(tdev):
+            up = lambda a: torch.from_numpy(a).to(tdev)  # noqa: E731
+            t_rot, t_trans = up(rot.reshape(-1, 9) if n else np.zeros((1, 9))), up(trans if n else np.zeros((1, 3)))
+            if node_mode:
+                t_a, t_b, t_c = up(idx if n else np.zeros(1, np.int64)), up(conf if n else np.zeros(1, np.int32)), None
+                slots = m * _MAX_NODES
+            else:
+                t_a, t_b, t_c = up(off), up(flat), (up(rad) if rad is not None else None)
+                slots = max(int(off[-1]), 1)
+            summary = torch.empty((m, 4), dtype=torch.float64, device=tdev)
+            count = torch.empty((m, 6), dtype=torch.int32, device=tdev)
+            ppen = torch.empty(slots, dtype=torch.float64, device=tdev)
+            patom = torch.empty(slots, dtype=torch.int32, device=tdev)
+            fp = torch.empty((m, _FP_WORDS), dtype=torch.int64, device=tdev)
+            status = torch.empty(m, dtype=torch.int32, device=tdev)
+            stream = torch.cuda.current_stream(tdev)
+            _ffi.check(lib.pmx_pose_clash(ph.handle, dlib.handle if node_mode else None, t_a.data_ptr() if node_mode else None, t_b.data_ptr() if node_mode else None,
+                                          None if node_mode else t_a.data_ptr(), None if node_mode else t_b.data_ptr(), t_c.data_ptr() if t_c is not None else None,
+                                          t_rot.data_ptr(), t_trans.data_ptr(), n, float(node_radius), float(tolerance), float(contact), summary.data_ptr(), count.data_ptr(),
+                                          ppen.data_ptr(), patom.data_ptr(), fp.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+            stream.synchronize()
+        st = status.cpu().numpy()[:n].astype(np.int32)
+        if node_mode:
+            nn = _record_counts(dlib, idx, 0)
+            lo = np.arange(n, dtype=np.int64) * _MAX_NODES
+            hi = lo + np.where(st != 1, nn, 0)
+        else:
+            lo, hi = off[:-1], off[1:]
+    sm, cn = summary.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
+    pp, pa = ppen.cpu().numpy(), patom.cpu().numpy().astype(np.int64)
+    return ClashReport(clearance=sm[:, 0].copy(), overlap=sm[:, 1].copy(), n_points=cn[:, 0].copy(), n_clashing=cn[:, 1].copy(), n_pairs=cn[:, 2].copy(),
+                       n_contacts=cn[:, 3].copy(), worst=cn[:, 4:6].copy(), point_penetration=[pp[lo[i]: hi[i]].copy() for i in range(n)],
+                       point_atom=[pa[lo[i]: hi[i]].copy() for i in range(n)], contact_fingerprint=fp.cpu().numpy()[:n].view(np.uint64).copy(), status=st, device=dev)
 
 
 _MAX_MODEL_NODES, _FP_WORDS, _MAX_LEADERS = 256, 4, 2048  # PMX_MAX_MODEL_NODES, PMX_FINGERPRINT_WORDS, PMX_MAX_LEADERS

@@ -195,6 +195,7 @@ class PharmacophoreModel:
         self._flat = _flatten_state(state)
         self._engine_handle = None
         self._object_graph = None
+        self._pocket_atoms = {}
 
     @classmethod
     def create(cls, pdbblock, center, hotspot_infos, resolution: float = 0.5, size: int = 64, device="auto"):
@@ -247,6 +248,17 @@ class PharmacophoreModel:
         """float64 [Nm, 3]: `nodes[m].center`, the pharmacophore point of every model node (what `engine.align` fits ligand nodes onto)."""
         assert self._state is not None, "empty model"
         return np.array([[float(v) for v in node["center"]] for node in self._state["nodes"]], dtype=np.float64).reshape(-1, 3)
+
+    def pocket_atoms(self, **kw):
+        """The heavy atoms of the protein this model carries (`pdbblock`) as `pocket.PocketAtoms`, what `engine.clashes` checks posed hits
+        against; kept per set of arguments (`within`, `hetero`, `water`), with its device copy. ValueError when the block holds no atom."""
+        from .pocket import PocketAtoms
+
+        cache = self.__dict__.setdefault("_pocket_atoms", {})
+        key = tuple(sorted(kw.items()))
+        if key not in cache:
+            cache[key] = PocketAtoms.from_model(self, **kw)
+        return cache[key]
 
     # The reference's object graph (`pharmacophore_model.py:191-204,207-365`), built on first use from the state dict: code
     # written against `model.nodes / .edges / .node_dict / .node_cluster_dict / .node_clusters` keeps working. Read-only views -
@@ -464,6 +476,36 @@ class PharmacophoreModel:
                     rotation=al.rotation[0], translation=al.translation[0], rmsd=float(al.rmsd[0]), rmsd_nodes=float(al.rmsd_nodes[0]),
                     weight=float(al.weight[0]), sse=float(al.sse[0]), scale=float(al.scale[0]), gap=float(al.gap[0]), node=al.node[0],
                     n_nodes=int(al.n_nodes[0]), n_pairs=int(al.n_pairs[0]), levels=al.levels[0], status=int(al.status[0]))
+
+    def scoring_clash(self, ligand, conformer: int | None = None, key=None, weights: dict[str, float] | None = None, pocket=None, **kw) -> dict:
+        """One ligand fitted into the pocket (`scoring_pose`) and its pose checked against the protein's atoms (`engine.clashes`): the ligand's own
+        heavy atoms with Bondi radii when `ligand` has them (a `Ligand` / `LigandFeatures`; `level` is "atoms"), the record's pharmacophore
+        nodes otherwise ("nodes"). `pocket`: a `pocket.PocketAtoms` (default: `pocket_atoms()`, the protein this model carries). Returns
+        `scoring_pose`'s `conformer`, `key`, `rotation`, `translation`, `rmsd` with `level`, `clearance`, `overlap`, `n_points`, `n_clashing`,
+        `n_pairs`, `n_contacts`, `worst` (point, atom), `worst_atom` (its label), `point_penetration`, `point_atom`, `contact_fingerprint`,
+        `residues` (the touched residues), `ok` and `status`. Further arguments (`tolerance`, `contact`, `node_radius`) as `engine.clashes`."""
+        from .engine import clashes
+        from .library import as_packed_library
+        from .pocket import atomic_number_radii
+
+        pocket = self.pocket_atoms() if pocket is None else pocket
+        pose = self.scoring_pose(ligand, weights=weights, conformer=conformer, key=key)
+        c = pose["conformer"]
+        atoms = getattr(ligand, "atom_positions", None)
+        if atoms is not None:
+            from .engine import _atomic_numbers
+
+            z = _atomic_numbers(ligand)
+            pos = np.asarray(atoms, dtype=np.float32)
+            rep = clashes(pocket, rotation=[pose["rotation"]], translation=[pose["translation"]], points=[pos[z > 1, c] if 0 <= c < pos.shape[1] else np.zeros((0, 3))],
+                          point_radii=[atomic_number_radii(z[z > 1]) if 0 <= c < pos.shape[1] else np.zeros(0)], **kw)
+        else:
+            rep = clashes(pocket, library=as_packed_library(ligand), indices=[0], conformers=[c], rotation=[pose["rotation"]], translation=[pose["translation"]], **kw)
+        return dict(conformer=c, key=pose["key"], rotation=pose["rotation"], translation=pose["translation"], rmsd=pose["rmsd"],
+                    level="atoms" if atoms is not None else "nodes", clearance=float(rep.clearance[0]), overlap=float(rep.overlap[0]), n_points=int(rep.n_points[0]),
+                    n_clashing=int(rep.n_clashing[0]), n_pairs=int(rep.n_pairs[0]), n_contacts=int(rep.n_contacts[0]), worst=tuple(int(v) for v in rep.worst[0]),
+                    worst_atom=rep.atom_label(0, pocket), point_penetration=rep.point_penetration[0], point_atom=rep.point_atom[0],
+                    contact_fingerprint=rep.contact_fingerprint[0], residues=rep.residues(0, pocket), ok=bool(rep.ok()[0]), status=int(rep.status[0]))
 
     def explain(self, library, indices, weights: dict[str, float] | None = None, **kwargs):
         """Per-conformer maxima and explaining matches of library ligands `indices` (`engine.explain`)."""

@@ -5,6 +5,7 @@ type weights. `--library_dir` may be a directory of `.sdf` / `.mol2` files (perc
 processes; needs OpenBabel like the reference) or a packed library file (`.pmxlib`, see
 `pharmaconet_amd.library`) with an optional `<library>.names` text file giving one path per ligand.
 Output: `path,score` CSV, best first, ties in library order (`screening.py:70-75`). Scoring runs on the GPU.
+`--explain K --clashes PATH [--protein FILE.pdb]` checks the explained hits' poses against the protein's atoms (excluded volumes).
 `--panel MODEL ... --panel_out PATH` scores the best hits against other pockets; `--save_top K PATH` keeps them as a packed library.
 `--actives FILE --enrichment_out PATH` validates the model retrospectively: the library's ligands named in FILE are the actives, the rest decoys.
 `--similar_to NAME ... --similar_out PATH` lists the library's ligands most similar to the named ones by their own pharmacophore fingerprints.
@@ -36,6 +37,10 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--explain_out", type=str, default=None, help="CSV of the explained hits (default: <out>.explain.csv)")
         cfg.add_argument("--explain_nodes", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per pharmacophore node of each explained hit and the node's share of the hit's best conformer maximum")
         cfg.add_argument("--poses", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit and the rigid motion (rotation, translation) that puts its best conformer onto the matched pharmacophore points")
+        cfg.add_argument("--clashes", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit: its pose checked against the protein's heavy atoms (clashing points and pairs, deepest penetration, overlap, touched residues)")
+        cfg.add_argument("--protein", type=str, default=None, metavar="FILE.pdb", help="with --clashes: the protein, in the model's frame (default: the protein the model carries)")
+        cfg.add_argument("--clash_tolerance", type=float, default=0.5, metavar="T", help="with --clashes: overlap of two spheres, in Angstrom, that is not yet a clash")
+        cfg.add_argument("--clash_level", choices=("nodes", "atoms"), default="atoms", help="with --clashes: check the hit's pharmacophore nodes, or its heavy atoms (the hit files are read again; needs a library directory)")
         cfg.add_argument("--hotspots", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per (explained hit, model node it has terms with): the node's share of the hit's best conformer maximum and whether the hit engages it")
         cfg.add_argument("--diverse", type=int, default=None, metavar="K", help="list the K first hits that are not the same binding mode again (leaders by interaction fingerprint, in rank order)")
         cfg.add_argument("--diverse_pool", type=int, default=None, metavar="P", help="best hits that --diverse looks at (default: max(8 K, 1024), at most 65536)")
@@ -145,6 +150,14 @@ def main(argv=None) -> None:
         parser.error("--explain_nodes needs --explain K")
     if args.poses and args.explain <= 0:
         parser.error("--poses needs --explain K")
+    if args.clashes and args.explain <= 0:
+        parser.error("--clashes needs --explain K")
+    if not args.clashes and args.protein:
+        parser.error("--protein needs --clashes PATH")
+    if args.clashes and args.clash_level == "atoms" and Path(args.library_dir).is_file():
+        parser.error("--clash_level atoms reads the hit files again: a packed library has none (use --clash_level nodes)")
+    if args.clashes and not np.isfinite(args.clash_tolerance):
+        parser.error("--clash_tolerance takes a number")
     if args.hotspots and args.explain <= 0:
         parser.error("--hotspots needs --explain K")
     if args.diverse is not None and args.diverse <= 0:
@@ -211,6 +224,13 @@ def main(argv=None) -> None:
         Halogen=args.halogen,
         Hydrophobic=args.hydrophobic,
     )
+    if args.clashes:  # (before the screen: a model without a protein should not cost a pass)
+        from .pocket import PocketAtoms
+
+        try:
+            pocket = PocketAtoms.from_pdb(Path(args.protein), centers=model.node_centers) if args.protein else model.pocket_atoms()
+        except (OSError, ValueError) as e:
+            parser.error(f"--clashes: {e}" + ("" if args.protein else " (give it with --protein FILE.pdb)"))
     names, lib = load_library(Path(args.library_dir), args.cpus, on_device=True)
     if args.actives:  # (before the screen: a name that matches nothing should not cost a pass)
         from .validation import match_actives
@@ -241,6 +261,8 @@ def main(argv=None) -> None:
             write_explain_nodes_csv(Path(args.explain_nodes), names, scores, status, model, lib, weight, args.explain)
         if args.poses:
             write_poses_csv(Path(args.poses), names, scores, status, model, lib, weight, args.explain)
+        if args.clashes:
+            write_clashes_csv(Path(args.clashes), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_level, args.clash_tolerance)
         if args.hotspots:
             write_hotspots_csv(Path(args.hotspots), names, scores, status, model, lib, weight, args.explain)
         if args.modes is not None:
@@ -459,6 +481,30 @@ def write_poses_csv(out: Path, names: list[str], scores: np.ndarray, status: np.
             nums = [al.rmsd[r], al.rmsd_nodes[r]], [*al.rotation[r].reshape(-1), *al.translation[r]]
             w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{','.join(repr(float(v)) for v in nums[0])},{int(al.n_nodes[r])},"
                     f"{','.join(repr(float(v)) for v in nums[1])}\n")
+
+
+def write_clashes_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, pocket, level: str, tolerance: float) -> None:
+    """One row per hit of the k best, in the order of the poses CSV: the pose of the hit's best conformer (`engine.align`) checked against the
+    protein's heavy atoms (`engine.clashes`) - at level `nodes` the hit's pharmacophore nodes, at level `atoms` the heavy atoms of the hit's
+    file, read again. Points, clashing points, clashing pairs, the deepest penetration (negative: the clearance), the overlap, the points
+    within contact distance, the worst pair's point and protein atom, and the touched residues joined by `;`."""
+    from .engine import explain
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
+    atoms = None
+    if level == "atoms":
+        from .ligand import Ligand
+
+        atoms = [Ligand.load_from_file(names[order[int(row)]]) for row in al.rows]
+    rep = al.clashes(pocket, lib, atoms=atoms, tolerance=tolerance)
+    with open(out, "w") as w:
+        w.write("rank,path,conformer,level,points,clashing,pairs,clearance,overlap,contacts,worst_point,worst_atom,residues\n")
+        for r, row in enumerate(al.rows):
+            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{level},{int(rep.n_points[r])},{int(rep.n_clashing[r])},{int(rep.n_pairs[r])},"
+                    f"{float(rep.clearance[r])!r},{float(rep.overlap[r])!r},{int(rep.n_contacts[r])},{int(rep.worst[r, 0])},{rep.atom_label(r, pocket)},"
+                    f"{';'.join(rep.residues(r, pocket))}\n")
 
 
 if __name__ == "__main__":
