@@ -652,6 +652,69 @@ int pmx_pose_clash(const pmx_pocket *pocket, const pmx_library *lib /* NULL in p
                    uint64_t *contact_fp_dev /* [n][PMX_FINGERPRINT_WORDS] or NULL */, int32_t *status_dev, void *stream);
 
 /*
+ * Restrained rigid-body clash relief (pmx_refine.hip): a pose whose least-squares fit grazes a side chain is moved out of it, one that runs
+ * through the backbone stays rejected. Per row a bounded, deterministic Levenberg-Marquardt minimisation over the six rigid degrees of
+ * freedom of E = Ec + restraint Er: the overlap pmx_pose_clash defines, plus a harmonic restraint that holds anchors near where the start
+ * motion put them. The reference has no counterpart; the specification is this comment, and tests/refine_ref.py restates it in NumPy.
+ *
+ * Points: a row's points, their radii, node mode and point mode, and the status rules are pmx_pose_clash's (a start motion that is not
+ * finite: PMX_LIGAND_KEY_INVALID; a record that is not supported: PMX_LIGAND_UNSUPPORTED).
+ * Anchors, what the restraint holds: with anchor_off_dev NULL the row's own points, each of weight 1 (anchors_dev, anchor_target_dev and
+ * anchor_weight_dev are then NULL too). Otherwise anchors_dev[anchor_off_dev[i] .. anchor_off_dev[i + 1]), float32 [.][3] in the
+ * conformer's frame, with weights anchor_weight_dev[.] (float64; 1 each where that pointer is NULL; a weight that is negative or not finite
+ * gives the row PMX_LIGAND_KEY_INVALID) and targets anchor_target_dev[.][3] (float64, the pocket's frame; where that pointer is NULL an
+ * anchor's target is its own position under the row's start motion, by the posed-point formula: "stay where the fit put you").
+ *
+ * Energy at a motion (R, t). Posed points p (and posed anchors q) and the pairs' d and pen by the operations of the pmx_pose_clash comment:
+ * float64, every operation rounded, no fused multiply-add.
+ *   Ec = the sum of pen^2 over the pairs with pen > 0, in pmx_pose_clash's order (per point in atom order, a lane's points ascending, the
+ *        fixed butterfly over the 64 lanes)
+ *   Er = the sum over the anchors of w ((e_0 e_0 + e_1 e_1) + e_2 e_2), e = q - b (a lane's anchors, anchor % 64, ascending; the butterfly)
+ *   E  = Ec + restraint * Er
+ * Normal equations at (R, t). c = the sum of the posed points (summed like Er) / the number of points, 0 for a row without points. A small
+ * motion is delta p = omega x (p - c) + tau. A clashing pair with d > 0 and nhat = (dx, dy, dz) / d has the residual pen and the Jacobian row
+ * -v, v = [(p - c) x nhat, nhat]; a pair with d == 0 counts in Ec only. An anchor at q has the three residuals sqrt(restraint w) (q - b) with
+ * rows sqrt(restraint w) [-[q - c]_x, I]: in closed form, with r = q - c and k = restraint * w, the blocks k (|r|^2 I - r r^T), k [r]_x, k I
+ * of H and k [r x e, e] of g. H = sum J^T J (6 x 6, 21 values), g = sum J^T r; per lane the pairs' terms in (point, atom) order, then the
+ * anchors', and the butterfly.
+ * Iteration:
+ *   1. evaluate at the start motion
+ *   2. no pair clashes: stop, reason 0 - the outputs are the input motion bit for bit
+ *   3. otherwise lambda = 1e-3, and while iterations < max_iter:
+ *        solve (H + lambda diag(H_ii + 1e-9)) delta = -g by Cholesky; omega = delta[0 .. 3), tau = delta[3 .. 6)
+ *        Rd = I + (sin th / th) K + (2 sin^2(th / 2) / th^2) K^2, K = [omega]_x, th = |omega| (the identity at th = 0)
+ *        trial: R' = Rd R, t' = Rd (t - c) + c + tau; evaluate there; ++iterations
+ *        E' < E: accept, lambda = max(lambda / 4, 1e-9); if E - E' <= ftol * E: stop, reason 1
+ *        otherwise: lambda *= 8; if lambda > 1e8: stop, reason 3
+ *      (a pivot of the Cholesky that is not positive, or a delta that is not finite, is a rejected trial: it counts as an iteration
+ *      without an evaluation)
+ *   4. running out of max_iter: reason 2. 0 <= max_iter <= PMX_REFINE_MAX_ITER; max_iter = 0 evaluates and returns the start.
+ * The loop is bounded by max_iter evaluations whatever the data; no other loop depends on convergence.
+ * Outputs, per row:
+ *   rot_out_dev, trans_out_dev   double [n][9], [n][3]: the last accepted motion
+ *   energy_dev   double [n][8]   Ec at the start, Er at the start, Ec final, Er final, the anchor rmsd sqrt(Er / sum w) (0 without weight),
+ *                                the net rotation angle from the start in rad (0 when no step was accepted), |c_final - c_start|, the
+ *                                final lambda
+ *   count_dev    int32 [n][4]    iterations, accepted steps, stop reason, clashing pairs at the final motion
+ *   status_dev   int32 [n]       PMX_LIGAND_*
+ * A row that is not OK has NaN motions and energies, counts of 0 and a stop reason of -1.
+ * Cross-checks. Every evaluation poses the points from the stored (R, t) by the formula above, so bit for bit: Ec at the start is
+ * pmx_pose_clash's overlap at the input motion; Ec final and count[3] are pmx_pose_clash's overlap and pair count at rot_out / trans_out.
+ * n <= PMX_EXPLAIN_MAX (otherwise PMX_ERR_INVALID); n = 0 succeeds and writes nothing. restraint >= 0 and ftol >= 0, both finite;
+ * point_radius and tolerance finite; one source of points per call; in node mode the library is on the pocket's device; no output may be
+ * NULL: otherwise PMX_ERR_INVALID. The pointers are memory of that device. Stream-ordered (enqueued, no synchronisation), no work buffer,
+ * no floating-point atomic: the same bits on every run, and for a row wherever it stands in a call. One wavefront per row.
+ */
+#define PMX_REFINE_MAX_ITER 64
+int pmx_pose_refine(const pmx_pocket *pocket, const pmx_library *lib /* NULL in point mode */, const uint64_t *ligands_dev, const int32_t *conformer_dev,
+                    const uint64_t *point_off_dev, const float *points_dev, const float *point_radius_dev,
+                    const uint64_t *anchor_off_dev /* [n + 1] or NULL */, const float *anchors_dev /* [.][3] */,
+                    const double *anchor_target_dev /* [.][3] or NULL */, const double *anchor_weight_dev /* [.] or NULL */,
+                    const double *rot_dev, const double *trans_dev, uint32_t n, float point_radius, float tolerance, double restraint, double ftol,
+                    int max_iter, double *rot_out_dev /* [n][9] */, double *trans_out_dev /* [n][3] */, double *energy_dev /* [n][8] */,
+                    int32_t *count_dev /* [n][4] */, int32_t *status_dev, void *stream);
+
+/*
  * Retrospective validation (pmx_enrich.hip): does a model, under given type weights, rank known binders above decoys? Per column of scores
  * over one labelled list, and per bootstrap resample of the list, the integers and sums from which the host derives AUROC, enrichment
  * factors and BEDROC. The specification is this comment (the reference has no counterpart); tests/enrichment_ref.py restates it in NumPy.

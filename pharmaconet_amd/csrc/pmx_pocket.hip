@@ -23,19 +23,15 @@
 
 #include "pmx.h"
 #include "pmx_device.h"
-
-struct pmx_pocket {
-    int device = 0;
-    uint32_t n = 0;
-    float max_radius = 0.0f;   // the largest of the radii (0 without atoms): what bounds a pair's contact sum
-    float4 *atoms = nullptr;   // [n] x, y, z, radius
-    uint16_t *group = nullptr; // [n]
-};
+#include "pmx_pose.h" // struct pmx_pocket, the row front end, the posed point and the butterfly: shared with pmx_refine.hip
 
 namespace {
-using pmx::parse_record;
-using pmx::Record;
-using pmx::record_supported;
+using pmx::pose_load;
+using pmx::pose_point;
+using pmx::pose_row;
+using pmx::PoseRow;
+using pmx::PoseSource;
+using pmx::wave_sum;
 
 constexpr int kW = PMX_FINGERPRINT_WORDS;
 constexpr int kN = PMX_MAX_LIGAND_NODES;
@@ -47,14 +43,7 @@ struct ClashArgs {
     const uint16_t *group;
     uint32_t n_atoms;
     float max_radius;
-    const uint64_t *lib_offsets; // node mode (null in point mode)
-    const uint8_t *lib_data;
-    uint64_t lib_n;
-    const uint64_t *ligands;
-    const int32_t *conformer;
-    const uint64_t *point_off; // point mode
-    const float *points;
-    const float *point_radius;
+    PoseSource src;
     const double *rot, *trans;
     uint32_t n;
     float radius, tolerance, contact;
@@ -66,24 +55,11 @@ struct ClashArgs {
     int32_t *status;
 };
 
-__device__ __forceinline__ int wave_sum(int x) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m);
-    return x;
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m); // (a + b in both partners: the same bits in every lane, the same on every run)
-    return x;
-}
-
 __global__ __launch_bounds__(64 * kWaves) void clash_kernel(const ClashArgs a) {
     // (everything a wavefront decides by is a scalar: its row, the record's header, the motion)
     const uint32_t row = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
     if (row >= a.n) return;
     const int lane = (int)(threadIdx.x % 64);
-    const bool node_mode = a.points == nullptr;
     const double nan = __builtin_nan(""), ninf = -__builtin_inf();
 
     double R[9], t[3];
@@ -100,44 +76,11 @@ __global__ __launch_bounds__(64 * kWaves) void clash_kernel(const ClashArgs a) {
     }
 
     // ---- the row's points
-    int status = finite ? PMX_LIGAND_OK : PMX_LIGAND_KEY_INVALID;
-    uint64_t out_at;  // where the row's per-point outputs begin
-    uint32_t out_len; // ... and how many there are (written in full, whatever the status)
-    uint32_t npts = 0;
-    const float *xyz = nullptr; // node mode: float k of node u at xyz[(3 u + k) * stride]; point mode: xyz[3 u + k]
-    uint32_t stride = 1;
-    const float *radii = nullptr;
-    if (node_mode) {
-        out_at = (uint64_t)row * kN;
-        out_len = kN;
-        const uint64_t lig = a.ligands[row];
-        const int c = a.conformer[row];
-        bool supported = lig < a.lib_n; // (not a ligand of the library: nothing is read)
-        if (supported) {
-            const Record rec = parse_record(a.lib_data + a.lib_offsets[lig]);
-            supported = __builtin_amdgcn_readfirstlane((int)record_supported(rec)) != 0;
-            const int C = __builtin_amdgcn_readfirstlane(rec.C);
-            if (supported) {
-                if (c < 0 || c >= C) {
-                    status = PMX_LIGAND_KEY_INVALID;
-                } else {
-                    npts = (uint32_t)__builtin_amdgcn_readfirstlane(rec.n);
-                    xyz = rec.xyz + c;
-                    stride = (uint32_t)C;
-                }
-            }
-        }
-        if (!supported) status = PMX_LIGAND_UNSUPPORTED;
-    } else {
-        const uint64_t o0 = a.point_off[row], o1 = a.point_off[row + 1];
-        const uint64_t len = o1 > o0 ? o1 - o0 : 0ull;
-        out_at = o0;
-        out_len = (uint32_t)(len < 0x7fffffffull ? len : 0x7fffffffull);
-        npts = out_len;
-        xyz = a.points + o0 * 3;
-        radii = a.point_radius ? a.point_radius + o0 : nullptr;
-    }
-    if (status != PMX_LIGAND_OK) npts = 0;
+    const PoseRow pr = pose_row(a.src, row, finite);
+    const int status = pr.status;
+    const uint64_t out_at = pr.out_at;
+    const uint32_t out_len = pr.out_len, npts = pr.npts;
+    const float *radii = pr.radii;
 
     // ---- pairs
     const double tol = (double)a.tolerance, contact = (double)a.contact;
@@ -149,12 +92,9 @@ __global__ __launch_bounds__(64 * kWaves) void clash_kernel(const ClashArgs a) {
         const bool on = u < npts;
         double p0 = 0.0, p1 = 0.0, p2 = 0.0, rp = (double)a.radius;
         if (on) {
-            const size_t at = node_mode ? (size_t)u * 3 * stride : (size_t)u * 3;
-            const size_t step = node_mode ? stride : 1;
-            const double x0 = (double)xyz[at], x1 = (double)xyz[at + step], x2 = (double)xyz[at + 2 * step];
-            p0 = ((R[0] * x0 + R[1] * x1) + R[2] * x2) + t[0];
-            p1 = ((R[3] * x0 + R[4] * x1) + R[5] * x2) + t[1];
-            p2 = ((R[6] * x0 + R[7] * x1) + R[8] * x2) + t[2];
+            double x0, x1, x2;
+            pose_load(pr, u, x0, x1, x2);
+            pose_point(R, t, x0, x1, x2, p0, p1, p2);
             if (radii) rp = (double)radii[u];
         }
         double pbest = ninf, pov = 0.0;
@@ -291,32 +231,17 @@ extern "C" int pmx_pose_clash(const pmx_pocket *pocket, const pmx_library *lib, 
                               const float *points_dev, const float *point_radius_dev, const double *rot_dev, const double *trans_dev, uint32_t n, float point_radius,
                               float tolerance, float contact, double *summary_dev, int32_t *count_dev, double *point_pen_dev, int32_t *point_atom_dev, uint64_t *contact_fp_dev,
                               int32_t *status_dev, void *stream_) {
-    if (!pocket) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_clash: null pocket");
-    const bool nodes = lib != nullptr, points = points_dev != nullptr || point_off_dev != nullptr || point_radius_dev != nullptr;
-    if (nodes == points) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_clash: %s", nodes ? "a library and points: one source of points per call" : "neither a library nor points");
-    if (n > PMX_EXPLAIN_MAX) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_clash: %u rows, at most %d", n, PMX_EXPLAIN_MAX);
-    if (!std::isfinite(point_radius) || !std::isfinite(tolerance) || !std::isfinite(contact)) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_clash: radius, tolerance and contact must be finite");
     ClashArgs a{};
-    if (nodes) {
-        pmx_library_info info;
-        if (pmx_library_info_get(lib, &info) != PMX_OK || pmx_library_buffers(lib, &a.lib_offsets, &a.lib_data) != PMX_OK) return PMX_ERR_INVALID;
-        if (pmx_library_device(lib) != pocket->device) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_clash: the pocket is on device %d, the library on %d", pocket->device, pmx_library_device(lib));
-        a.lib_n = info.n_ligands;
-    }
+    const int rc = pmx::pose_source("pmx_pose_clash", pocket, lib, ligands_dev, conformer_dev, point_off_dev, points_dev, point_radius_dev, rot_dev, trans_dev, n, &a.src);
+    if (rc != PMX_OK) return rc;
+    if (!std::isfinite(point_radius) || !std::isfinite(tolerance) || !std::isfinite(contact)) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_clash: radius, tolerance and contact must be finite");
     if (n == 0) return PMX_OK;
-    if (nodes ? (!ligands_dev || !conformer_dev) : (!point_off_dev || !points_dev)) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_clash: null %s", nodes ? "ligands_dev or conformer_dev" : "point_off_dev or points_dev");
-    if (!rot_dev || !trans_dev) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_clash: null rot_dev or trans_dev");
     if (!summary_dev || !count_dev || !point_pen_dev || !point_atom_dev || !status_dev) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_clash: null output (only contact_fp_dev may be)");
     if (hipSetDevice(pocket->device) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_pose_clash: hipSetDevice failed");
     a.atoms = pocket->atoms;
     a.group = pocket->group;
     a.n_atoms = pocket->n;
     a.max_radius = pocket->max_radius;
-    a.ligands = ligands_dev;
-    a.conformer = conformer_dev;
-    a.point_off = point_off_dev;
-    a.points = points_dev;
-    a.point_radius = point_radius_dev;
     a.rot = rot_dev;
     a.trans = trans_dev;
     a.n = n;

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import dataclasses
 from dataclasses import dataclass
 
 import numpy as np
@@ -472,15 +473,24 @@ class ScreeningResult:
                            pool=idx.astype(np.uint64), profile=None)
 
     def fitting(self, k: int, pool: int | None = None, max_clashing: int = 0, pocket=None, atoms=None, model=None, library=None,
-                weights: dict[str, float] | None = None, **kw) -> "FittingHits":
+                weights: dict[str, float] | None = None, refine: bool = False, **kw) -> "FittingHits":
         """The k first hits of this screen whose pose fits the pocket: the best `pool` hits (default min(len, max(8 k, 1024), 65536)) are
         explained, posed at their best conformer (`Explanation.poses`) and checked against the protein's atoms (`Alignment.clashes`); a hit
         passes with status 0 and at most `max_clashing` clashing points. In rank order; a hit that was not scored, or whose pose is not OK,
         never passes. `pocket`: a `pocket.PocketAtoms` (default: the protein the model carries). `atoms`: a function from a library index to
         the `LigandFeatures` / `Ligand` of that ligand, for a check of the molecule's atoms; without it the pharmacophore nodes are checked.
-        Further arguments (`tolerance`, `contact`, `node_radius`) as `clashes` takes them."""
+        Further arguments (`tolerance`, `contact`, `node_radius`) as `clashes` takes them.
+        With `refine`, a pose that fails the check is moved out of the protein's atoms (`Alignment.refine`) and checked again; `poses` and
+        `report` then describe the poses as used - the refined one where the fitted one failed - and `refined` has the refinement of every
+        posed hit: one call refines all rows of the pool (a row keeps its place, and the call costs milliseconds), but only
+        the motions of the rows that failed are used. The fit fields of `poses` (`rmsd`, `sse`, `node`, ...) still describe the
+        least-squares fit, not the refined motion; `refined.anchor_rmsd` says how far that moved. `restraint`, `max_iter` and `ftol` go to `refine`, and `refine_tolerance` is the tolerance it runs at (default: the
+        check's; a penalty balanced against a restraint leaves a little overlap, so a smaller one is what makes grazing poses pass)."""
         if k <= 0:
             raise ValueError("k must be positive")
+        refine_kw = {name: kw.pop(name) for name in ("restraint", "max_iter", "ftol", "refine_tolerance") if name in kw}
+        if refine_kw and not refine:
+            raise ValueError(f"{sorted(refine_kw)}: arguments of the refinement, which is off (refine=True)")
         model, library, weights = self._scored(model, library, weights)
         n = int(self.scores.numel())
         pool = min(n, max(8 * k, 1024), 65536) if pool is None else int(pool)
@@ -490,10 +500,22 @@ class ScreeningResult:
         with _resident(library) as dlib:
             ex = explain(model, dlib, self._best(pool), weights=weights)
             al = ex.poses(model, dlib, weights=weights)
-            rep = al.clashes(pocket, dlib, atoms=None if atoms is None else [atoms(int(i)) for i in al.indices], **kw)
+            mols = None if atoms is None else [atoms(int(i)) for i in al.indices]
+            rep = al.clashes(pocket, dlib, atoms=mols, **kw)
+            refined = None
+            failing = ~rep.ok(max_clashing) & (al.status == 0)
+            if refine and failing.any():
+                shared = {name: kw[name] for name in ("tolerance", "node_radius", "device") if name in kw}
+                if "refine_tolerance" in refine_kw:
+                    shared["tolerance"] = refine_kw.pop("refine_tolerance")
+                refined = al.refine(pocket, dlib, atoms=mols, **shared, **refine_kw)
+                use = failing & (refined.status == 0)
+                al = dataclasses.replace(al, rotation=np.where(use[:, None, None], refined.rotation, al.rotation),
+                                         translation=np.where(use[:, None], refined.translation, al.translation))
+                rep = al.clashes(pocket, dlib, atoms=mols, **kw)  # (a row that was not refined has the bits it had)
         passing = np.flatnonzero(rep.ok(max_clashing) & (al.status == 0))[:k]
         return FittingHits(indices=al.indices[passing].astype(np.uint64), scores=ex.scores[al.rows[passing]], ranks=al.rows[passing].astype(np.int64), rows=passing,
-                           pool=ex.indices, poses=al, report=rep)
+                           pool=ex.indices, poses=al, report=rep, refined=refined)
 
     def similar_to(self, rank: int, k: int = 100, library=None) -> "SimilarityResult":
         """The library's neighbours of this screen's hit at `rank` (0 is the best hit): `similar` with that ligand as the one query,
@@ -1344,24 +1366,18 @@ class Alignment:
         (`PharmacophoreModel.pocket_atoms`). With `library` alone the rows' own pharmacophore nodes are checked (node mode: nothing but the
         resident records is read). With `atoms` - per row the `LigandFeatures` / `Ligand` the record was packed from - the molecule's atoms
         at the row's conformer are, hydrogens left out, with Bondi radii by atomic number (point mode). Further arguments as `clashes` takes them."""
-        from .pocket import PocketAtoms, atomic_number_radii
+        return _check_poses(self, "Alignment.clashes", pocket_or_model, library, atoms, kw)
 
-        pocket = pocket_or_model if isinstance(pocket_or_model, PocketAtoms) else pocket_or_model.pocket_atoms()
-        if atoms is None:
-            if library is None:
-                raise ValueError("Alignment.clashes: the library the rows are ligands of, or `atoms`")
-            return clashes(pocket, library=library, indices=self.indices, conformers=self.conformers, rotation=self.rotation, translation=self.translation, **kw)
-        if len(atoms) != len(self):
-            raise ValueError(f"{len(atoms)} molecules for {len(self)} rows")
-        points, radii = [], []
-        for i, mol in enumerate(atoms):
-            pos = np.asarray(mol.atom_positions, dtype=np.float32)  # [n_atoms, C, 3]
-            c = int(self.conformers[i])
-            z = _atomic_numbers(mol)
-            heavy = z > 1  # (hydrogens are not checked: the pocket's are not read either)
-            points.append(pos[heavy, c] if 0 <= c < pos.shape[1] else np.zeros((0, 3), np.float32))  # (not a conformer: the row's status says so already)
-            radii.append(atomic_number_radii(z[heavy])[: len(points[-1])])
-        return clashes(pocket, rotation=self.rotation, translation=self.translation, points=points, point_radii=radii, **kw)
+    def refine(self, pocket_or_model, library=None, atoms=None, **kw) -> "RefinedPoses":
+        """These poses moved out of the pocket's atoms and held near the fit (`refine`): row i of the result is row i of the alignment, and
+        a row that is not OK passes through with status 4. With `library` alone the points and the anchors are the rows' pharmacophore
+        nodes (node mode); with `atoms` - per row the molecule the record was packed from - they are its heavy atoms with Bondi radii
+        (point mode). Further arguments (`restraint`, `max_iter`, `ftol`, `tolerance`, `node_radius`) as `refine` takes them."""
+        pocket, source = _pose_source(self, "Alignment.refine", pocket_or_model, library, atoms)
+        out = refine(pocket, rotation=self.rotation, translation=self.translation, **source, **kw)
+        if out.indices is None:
+            out.indices, out.conformers = self.indices.copy(), np.asarray(self.conformers, dtype=np.int64).copy()
+        return out
 
 
 def align(model, library, indices, conformers, keys, weights: dict[str, float] | None = None, device=None) -> Alignment:
@@ -1408,6 +1424,7 @@ class FittingHits:
     pool: np.ndarray
     poses: "Alignment"
     report: "ClashReport"
+    refined: "RefinedPoses | None" = None  # `fitting(refine=True)`: the refinement of every posed hit; its motion is used where the fit failed
 
     def __len__(self) -> int:
         return len(self.indices)
@@ -1498,6 +1515,64 @@ def device_pocket(pocket, device=None) -> _PocketHandle:
     return pocket._device[dev]
 
 
+class _PoseRows:
+    """The rows `clashes` and `refine` share: motions and one source of points, checked and laid out as `pmx_pose_clash` and
+    `pmx_pose_refine` take them. `what` names the caller in a message."""
+
+    def __init__(self, what, library, indices, conformers, rotation, translation, points, point_radii):
+        self.rot = np.ascontiguousarray(np.asarray(rotation, dtype=np.float64).reshape(-1, 3, 3))
+        self.trans = np.ascontiguousarray(np.asarray(translation, dtype=np.float64).reshape(-1, 3))
+        n = self.n = len(self.rot)
+        if len(self.trans) != n:
+            raise ValueError("rotation and translation differ in length")
+        if n > 65536:
+            raise ValueError(f"at most 65536 rows per {what} call (PMX_EXPLAIN_MAX)")
+        self.node_mode = library is not None
+        if self.node_mode == (points is not None):
+            raise ValueError(f"{what}: a library with indices and conformers, or points - one of the two")
+        self.idx = self.conf = self.off = self.flat = self.rad = None
+        if self.node_mode:
+            self.idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+            self.conf = np.ascontiguousarray(np.clip(np.asarray(conformers, dtype=np.int64).reshape(-1), -1, 2**31 - 1).astype(np.int32))
+            if len(self.idx) != n or len(self.conf) != n:
+                raise ValueError("indices, conformers and the motions differ in length")
+            if (self.idx < 0).any():
+                raise ValueError("negative ligand index")
+        else:
+            if len(points) != n:
+                raise ValueError(f"{len(points)} point sets for {n} motions")
+            self.off, self.flat, pts = _ragged(points, np.float32, 3)
+            if point_radii is not None:
+                if len(point_radii) != n:
+                    raise ValueError(f"{len(point_radii)} radius lists for {n} point sets")
+                _, self.rad, rs = _ragged(point_radii, np.float32, None)
+                if any(len(r) != len(p) for r, p in zip(rs, pts)):
+                    raise ValueError("a list of radii differs in length from its points")
+
+    def upload(self, tdev):
+        """The device tensors (kept alive by the caller) and the seven source and motion arguments that follow the pocket and the library."""
+        torch = _torch()
+        n = self.n
+        up = lambda a: torch.from_numpy(a).to(tdev)  # noqa: E731
+        t_rot, t_trans = up(self.rot.reshape(-1, 9) if n else np.zeros((1, 9))), up(self.trans if n else np.zeros((1, 3)))
+        if self.node_mode:
+            t_a, t_b = up(self.idx if n else np.zeros(1, np.int64)), up(self.conf if n else np.zeros(1, np.int32))
+            keep, src = (t_rot, t_trans, t_a, t_b), (t_a.data_ptr(), t_b.data_ptr(), None, None, None)
+        else:
+            t_a, t_b, t_c = up(self.off), up(self.flat), (up(self.rad) if self.rad is not None else None)
+            keep, src = (t_rot, t_trans, t_a, t_b, t_c), (None, None, t_a.data_ptr(), t_b.data_ptr(), t_c.data_ptr() if t_c is not None else None)
+        return keep, src, (t_rot.data_ptr(), t_trans.data_ptr())
+
+
+def _ragged(lists, dtype, width):
+    """(offsets int64 [n + 1], the rows back to back and never empty, the rows) of a list of arrays of [m_i, width] (or [m_i] for width None)."""
+    rows = [np.asarray(p, dtype=dtype).reshape((-1, width) if width else (-1,)) for p in lists]
+    off = np.zeros(len(rows) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(p) for p in rows])
+    flat = np.ascontiguousarray(np.concatenate(rows + [np.zeros((1, width) if width else 1, dtype)]))  # (never an empty buffer)
+    return off, flat, rows
+
+
 def clashes(pocket, library=None, indices=None, conformers=None, rotation=None, translation=None, points=None, point_radii=None, node_radius: float = 1.0,
             tolerance: float = 0.5, contact: float = 4.5, device=None) -> ClashReport:
     """Posed rows against the pocket's atoms (`pmx_pose_clash`, csrc/pmx_pocket.hip): row i is a set of points moved by `rotation[i]`
@@ -1510,38 +1585,8 @@ def clashes(pocket, library=None, indices=None, conformers=None, rotation=None, 
     At most 65536 rows. Runs on torch's current stream of the device and waits for it."""
     torch = _torch()
     lib = _ffi.load()
-    rot = np.ascontiguousarray(np.asarray(rotation, dtype=np.float64).reshape(-1, 3, 3))
-    trans = np.ascontiguousarray(np.asarray(translation, dtype=np.float64).reshape(-1, 3))
-    n = len(rot)
-    if len(trans) != n:
-        raise ValueError("rotation and translation differ in length")
-    if n > 65536:
-        raise ValueError("at most 65536 rows per clashes call (PMX_EXPLAIN_MAX)")
-    node_mode = library is not None
-    if node_mode == (points is not None):
-        raise ValueError("clashes: a library with indices and conformers, or points - one of the two")
-    if node_mode:
-        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
-        conf = np.ascontiguousarray(np.clip(np.asarray(conformers, dtype=np.int64).reshape(-1), -1, 2**31 - 1).astype(np.int32))
-        if len(idx) != n or len(conf) != n:
-            raise ValueError("indices, conformers and the motions differ in length")
-        if (idx < 0).any():
-            raise ValueError("negative ligand index")
-    else:
-        if len(points) != n:
-            raise ValueError(f"{len(points)} point sets for {n} motions")
-        pts = [np.asarray(p, dtype=np.float32).reshape(-1, 3) for p in points]
-        off = np.zeros(n + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(p) for p in pts])
-        flat = np.ascontiguousarray(np.concatenate(pts + [np.zeros((1, 3), np.float32)]))  # (never an empty buffer)
-        rad = None
-        if point_radii is not None:
-            if len(point_radii) != n:
-                raise ValueError(f"{len(point_radii)} radius lists for {n} point sets")
-            rs = [np.asarray(r, dtype=np.float32).reshape(-1) for r in point_radii]
-            if any(len(r) != len(p) for r, p in zip(rs, pts)):
-                raise ValueError("a list of radii differs in length from its points")
-            rad = np.ascontiguousarray(np.concatenate(rs + [np.zeros(1, np.float32)]))
+    rows = _PoseRows("clashes", library, indices, conformers, rotation, translation, points, point_radii)
+    n, node_mode = rows.n, rows.node_mode
     m = max(n, 1)
     with contextlib.ExitStack() as stack:
         dlib = stack.enter_context(_resident(library, device)) if node_mode else None
@@ -1549,14 +1594,8 @@ def clashes(pocket, library=None, indices=None, conformers=None, rotation=None, 
         ph = device_pocket(pocket, dev)
         tdev = torch.device("cuda", dev)
         with torch.cuda.device(tdev):
-            up = lambda a: torch.from_numpy(a).to(tdev)  # noqa: E731
-            t_rot, t_trans = up(rot.reshape(-1, 9) if n else np.zeros((1, 9))), up(trans if n else np.zeros((1, 3)))
-            if node_mode:
-                t_a, t_b, t_c = up(idx if n else np.zeros(1, np.int64)), up(conf if n else np.zeros(1, np.int32)), None
-                slots = m * _MAX_NODES
-            else:
-                t_a, t_b, t_c = up(off), up(flat), (up(rad) if rad is not None else None)
-                slots = max(int(off[-1]), 1)
+            keep, src, motion = rows.upload(tdev)
+            slots = m * _MAX_NODES if node_mode else max(int(rows.off[-1]), 1)
             summary = torch.empty((m, 4), dtype=torch.float64, device=tdev)
             count = torch.empty((m, 6), dtype=torch.int32, device=tdev)
             ppen = torch.empty(slots, dtype=torch.float64, device=tdev)
@@ -1564,23 +1603,179 @@ def clashes(pocket, library=None, indices=None, conformers=None, rotation=None, 
             fp = torch.empty((m, _FP_WORDS), dtype=torch.int64, device=tdev)
             status = torch.empty(m, dtype=torch.int32, device=tdev)
             stream = torch.cuda.current_stream(tdev)
-            _ffi.check(lib.pmx_pose_clash(ph.handle, dlib.handle if node_mode else None, t_a.data_ptr() if node_mode else None, t_b.data_ptr() if node_mode else None,
-                                          None if node_mode else t_a.data_ptr(), None if node_mode else t_b.data_ptr(), t_c.data_ptr() if t_c is not None else None,
-                                          t_rot.data_ptr(), t_trans.data_ptr(), n, float(node_radius), float(tolerance), float(contact), summary.data_ptr(), count.data_ptr(),
-                                          ppen.data_ptr(), patom.data_ptr(), fp.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+            _ffi.check(lib.pmx_pose_clash(ph.handle, dlib.handle if node_mode else None, *src, *motion, n, float(node_radius), float(tolerance), float(contact),
+                                          summary.data_ptr(), count.data_ptr(), ppen.data_ptr(), patom.data_ptr(), fp.data_ptr(), status.data_ptr(),
+                                          ctypes.c_void_p(stream.cuda_stream)))
             stream.synchronize()
+            del keep
         st = status.cpu().numpy()[:n].astype(np.int32)
         if node_mode:
-            nn = _record_counts(dlib, idx, 0)
+            nn = _record_counts(dlib, rows.idx, 0)
             lo = np.arange(n, dtype=np.int64) * _MAX_NODES
             hi = lo + np.where(st != 1, nn, 0)
         else:
-            lo, hi = off[:-1], off[1:]
+            lo, hi = rows.off[:-1], rows.off[1:]
     sm, cn = summary.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
     pp, pa = ppen.cpu().numpy(), patom.cpu().numpy().astype(np.int64)
     return ClashReport(clearance=sm[:, 0].copy(), overlap=sm[:, 1].copy(), n_points=cn[:, 0].copy(), n_clashing=cn[:, 1].copy(), n_pairs=cn[:, 2].copy(),
                        n_contacts=cn[:, 3].copy(), worst=cn[:, 4:6].copy(), point_penetration=[pp[lo[i]: hi[i]].copy() for i in range(n)],
                        point_atom=[pa[lo[i]: hi[i]].copy() for i in range(n)], contact_fingerprint=fp.cpu().numpy()[:n].view(np.uint64).copy(), status=st, device=dev)
+
+
+@dataclass
+class RefinedPoses:
+    """What `refine` returns: one row per posed set of points (definitions: `pmx_pose_refine` in include/pmx.h). Floats are float64.
+
+    rotation[i], translation[i]   the refined motion: a point x of the conformer sits at R x + t. The input's own bits where nothing clashed
+    overlap_start[i], overlap[i]  the overlap (`ClashReport.overlap`) at the input motion and at the refined one
+    restraint_start[i], restraint_energy[i]   sum over the anchors of w |R a + t - b|^2, before and after (unscaled by `restraint`)
+    anchor_rmsd[i]  sqrt(restraint_energy / sum w): how far the anchors moved off their targets
+    angle[i], shift[i]   the net rotation from the input motion in rad, and how far the centroid of the posed points moved
+    iterations[i], accepted[i]    evaluations after the first, and the steps among them that lowered the energy
+    stop[i]         0 nothing clashed, 1 converged (decrease <= ftol E), 2 out of iterations, 3 no step found (lambda > 1e8); -1 not OK
+    n_pairs[i]      clashing pairs at the refined motion
+    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer, a motion that is not finite, a weight
+                    that is negative or not finite); such a row has NaN floats, zero counts and stop -1
+    indices, conformers   node mode: the rows' ligands and conformers (None in point mode)"""
+
+    rotation: np.ndarray
+    translation: np.ndarray
+    overlap_start: np.ndarray
+    overlap: np.ndarray
+    restraint_start: np.ndarray
+    restraint_energy: np.ndarray
+    anchor_rmsd: np.ndarray
+    angle: np.ndarray
+    shift: np.ndarray
+    iterations: np.ndarray
+    accepted: np.ndarray
+    stop: np.ndarray
+    n_pairs: np.ndarray
+    status: np.ndarray
+    indices: "np.ndarray | None" = None
+    conformers: "np.ndarray | None" = None
+
+    def __len__(self) -> int:
+        return len(self.status)
+
+    def transform(self, i: int, positions) -> np.ndarray:
+        """Row i's refined motion applied to any [..., 3] array of points of the conformer's frame: positions @ R.T + t."""
+        return np.asarray(positions, dtype=np.float64) @ self.rotation[i].T + self.translation[i]
+
+    def clashes(self, pocket_or_model, library=None, atoms=None, **kw) -> "ClashReport":
+        """The refined poses checked against the pocket's atoms, as `Alignment.clashes` checks the fitted ones: the rows' nodes with
+        `library`, the molecules' heavy atoms with `atoms`. A row that is not OK passes through with status 4."""
+        return _check_poses(self, "RefinedPoses.clashes", pocket_or_model, library, atoms, kw)
+
+
+def _heavy_atoms(atoms, conformers):
+    """Per row the heavy atoms of `atoms[i]` (a `LigandFeatures` / `Ligand`) at conformer `conformers[i]`, float32 [m_i, 3], and their
+    Bondi radii by atomic number. Hydrogens are left out (the pocket's are not read either); a row whose conformer the molecule does not have
+    gets no point (its status says so already)."""
+    from .pocket import atomic_number_radii
+
+    points, radii = [], []
+    for mol, c in zip(atoms, conformers):
+        pos = np.asarray(mol.atom_positions, dtype=np.float32)  # [n_atoms, C, 3]
+        c = int(c)
+        z = _atomic_numbers(mol)
+        heavy = z > 1
+        points.append(pos[heavy, c] if 0 <= c < pos.shape[1] else np.zeros((0, 3), np.float32))
+        radii.append(atomic_number_radii(z[heavy])[: len(points[-1])])
+    return points, radii
+
+
+def _pose_source(poses, what, pocket_or_model, library, atoms):
+    """(pocket, the keyword arguments that name the points of `poses`' rows for `clashes` / `refine`): node mode with `library` alone,
+    point mode - the molecules' heavy atoms - with `atoms`."""
+    from .pocket import PocketAtoms
+
+    pocket = pocket_or_model if isinstance(pocket_or_model, PocketAtoms) else pocket_or_model.pocket_atoms()
+    if atoms is None:
+        if library is None:
+            raise ValueError(f"{what}: the library the rows are ligands of, or `atoms`")
+        return pocket, dict(library=library, indices=poses.indices, conformers=poses.conformers)
+    if poses.conformers is None:
+        raise ValueError(f"{what}: these rows have no conformers to take the atoms at")
+    if len(atoms) != len(poses):
+        raise ValueError(f"{len(atoms)} molecules for {len(poses)} rows")
+    points, radii = _heavy_atoms(atoms, poses.conformers)
+    return pocket, dict(points=points, point_radii=radii)
+
+
+def _check_poses(poses, what, pocket_or_model, library, atoms, kw) -> "ClashReport":
+    pocket, source = _pose_source(poses, what, pocket_or_model, library, atoms)
+    return clashes(pocket, rotation=poses.rotation, translation=poses.translation, **source, **kw)
+
+
+def refine(pocket, library=None, indices=None, conformers=None, rotation=None, translation=None, points=None, point_radii=None, anchors=None, anchor_targets=None,
+           anchor_weights=None, node_radius: float = 1.0, tolerance: float = 0.5, restraint: float = 0.1, max_iter: int = 32, ftol: float = 1e-9,
+           device=None) -> RefinedPoses:
+    """Posed rows moved out of the pocket's atoms (`pmx_pose_refine`, csrc/pmx_refine.hip): per row a bounded Levenberg-Marquardt
+    minimisation over the rigid motion of the overlap `clashes` reports plus `restraint` times a harmonic term that holds the row's anchors
+    where the input motion put them. Rows, points and radii as `clashes` takes them (node mode or point mode).
+      anchors         None: the row's own points, each of weight 1. Otherwise a list of [k_i, 3] arrays in the conformer's frame
+      anchor_targets  a matching list of [k_i, 3] float64 positions in the pocket's frame (default: the anchors under the input motion)
+      anchor_weights  a matching list of [k_i] weights >= 0 (default 1 each)
+      restraint       the weight of the restraint against the overlap, both in A^2. The default 0.1 is uncalibrated: nobody has measured
+                      which value separates a grazed side chain from a pierced backbone best; DESIGN.md has what is known
+      max_iter, ftol  at most `max_iter` (<= 64) trial motions per row; a step that lowers the energy by no more than ftol * E ends the row
+    A penalty on the overlap balanced against a restraint never reaches an overlap of exactly zero: to make a pose pass a check at
+    `tolerance`, refine at a smaller one. At most 65536 rows. Runs on torch's current stream of the device and waits for it."""
+    torch = _torch()
+    lib = _ffi.load()
+    rows = _PoseRows("refine", library, indices, conformers, rotation, translation, points, point_radii)
+    n, node_mode = rows.n, rows.node_mode
+    if not 0 <= int(max_iter) <= 64:
+        raise ValueError("max_iter: 0 to 64 (PMX_REFINE_MAX_ITER)")
+    if not (np.isfinite(restraint) and restraint >= 0 and np.isfinite(ftol) and ftol >= 0):
+        raise ValueError("restraint and ftol must be finite and not negative")
+    a_off = a_flat = a_tgt = a_wts = None
+    if anchors is None:
+        if anchor_targets is not None or anchor_weights is not None:
+            raise ValueError("refine: anchor_targets and anchor_weights go with anchors")
+    else:
+        if len(anchors) != n:
+            raise ValueError(f"{len(anchors)} anchor sets for {n} motions")
+        a_off, a_flat, arows = _ragged(anchors, np.float32, 3)
+        for name, given, width in (("anchor_targets", anchor_targets, 3), ("anchor_weights", anchor_weights, None)):
+            if given is None:
+                continue
+            if len(given) != n:
+                raise ValueError(f"{len(given)} lists of {name} for {n} anchor sets")
+            _, flat, rs = _ragged(given, np.float64, width)
+            if any(len(r) != len(p) for r, p in zip(rs, arows)):
+                raise ValueError(f"a list of {name} differs in length from its anchors")
+            if width:
+                a_tgt = flat
+            else:
+                a_wts = flat
+    m = max(n, 1)
+    with contextlib.ExitStack() as stack:
+        dlib = stack.enter_context(_resident(library, device)) if node_mode else None
+        dev = dlib.device if node_mode else _device_index(device)
+        ph = device_pocket(pocket, dev)
+        tdev = torch.device("cuda", dev)
+        with torch.cuda.device(tdev):
+            keep, src, motion = rows.upload(tdev)
+            t_anchor = [None if a is None else torch.from_numpy(a).to(tdev) for a in (a_off, a_flat, a_tgt, a_wts)]
+            rot = torch.empty((m, 3, 3), dtype=torch.float64, device=tdev)
+            trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
+            energy = torch.empty((m, 8), dtype=torch.float64, device=tdev)
+            count = torch.empty((m, 4), dtype=torch.int32, device=tdev)
+            status = torch.empty(m, dtype=torch.int32, device=tdev)
+            stream = torch.cuda.current_stream(tdev)
+            _ffi.check(lib.pmx_pose_refine(ph.handle, dlib.handle if node_mode else None, *src, *(None if a is None else a.data_ptr() for a in t_anchor), *motion, n,
+                                           float(node_radius), float(tolerance), float(restraint), float(ftol), int(max_iter), rot.data_ptr(), trans.data_ptr(),
+                                           energy.data_ptr(), count.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+            stream.synchronize()
+            del keep, t_anchor
+    en, cn = energy.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
+    return RefinedPoses(rotation=rot.cpu().numpy()[:n].copy(), translation=trans.cpu().numpy()[:n].copy(), overlap_start=en[:, 0].copy(), overlap=en[:, 2].copy(),
+                        restraint_start=en[:, 1].copy(), restraint_energy=en[:, 3].copy(), anchor_rmsd=en[:, 4].copy(), angle=en[:, 5].copy(), shift=en[:, 6].copy(),
+                        iterations=cn[:, 0].copy(), accepted=cn[:, 1].copy(), stop=cn[:, 2].copy(), n_pairs=cn[:, 3].copy(),
+                        status=status.cpu().numpy()[:n].astype(np.int32), indices=rows.idx.copy() if node_mode else None,
+                        conformers=rows.conf.astype(np.int64) if node_mode else None)
 
 
 _MAX_MODEL_NODES, _FP_WORDS, _MAX_LEADERS = 256, 4, 2048  # PMX_MAX_MODEL_NODES, PMX_FINGERPRINT_WORDS, PMX_MAX_LEADERS

@@ -507,6 +507,35 @@ class PharmacophoreModel:
                     worst_atom=rep.atom_label(0, pocket), point_penetration=rep.point_penetration[0], point_atom=rep.point_atom[0],
                     contact_fingerprint=rep.contact_fingerprint[0], residues=rep.residues(0, pocket), ok=bool(rep.ok()[0]), status=int(rep.status[0]))
 
+    def scoring_refine(self, ligand, conformer: int | None = None, key=None, weights: dict[str, float] | None = None, pocket=None, **kw) -> dict:
+        """One ligand fitted into the pocket (`scoring_pose`) and its pose moved out of the protein's atoms (`engine.refine`), the one-ligand
+        form beside `scoring_clash`: the ligand's own heavy atoms with Bondi radii are the points and the anchors when `ligand` has them
+        (`level` "atoms"), the record's pharmacophore nodes otherwise ("nodes"). Returns `conformer`, `key`, `level`, the fitted `rotation`
+        and `translation`, the refined `refined_rotation` and `refined_translation`, `overlap_start`, `overlap`, `restraint_energy`,
+        `anchor_rmsd`, `angle`, `shift`, `iterations`, `accepted`, `stop`, `n_pairs`, `status`, and `ok`: whether the refined pose passes
+        `engine.clashes` at the same tolerance. Further arguments (`restraint`, `max_iter`, `ftol`, `tolerance`, `node_radius`) as
+        `engine.refine`."""
+        from .engine import _heavy_atoms, clashes, refine
+        from .library import as_packed_library
+
+        pocket = self.pocket_atoms() if pocket is None else pocket
+        pose = self.scoring_pose(ligand, weights=weights, conformer=conformer, key=key)
+        c = pose["conformer"]
+        atoms = getattr(ligand, "atom_positions", None)
+        if atoms is not None:
+            points, radii = _heavy_atoms([ligand], [c])
+            source = dict(points=points, point_radii=radii)
+        else:
+            source = dict(library=as_packed_library(ligand), indices=[0], conformers=[c])
+        ref = refine(pocket, rotation=[pose["rotation"]], translation=[pose["translation"]], **source, **kw)
+        check = {name: kw[name] for name in ("tolerance", "node_radius", "device") if name in kw}
+        rep = clashes(pocket, rotation=ref.rotation, translation=ref.translation, **source, **check)
+        return dict(conformer=c, key=pose["key"], level="atoms" if atoms is not None else "nodes", rotation=pose["rotation"], translation=pose["translation"],
+                    refined_rotation=ref.rotation[0], refined_translation=ref.translation[0], overlap_start=float(ref.overlap_start[0]), overlap=float(ref.overlap[0]),
+                    restraint_energy=float(ref.restraint_energy[0]), anchor_rmsd=float(ref.anchor_rmsd[0]), angle=float(ref.angle[0]), shift=float(ref.shift[0]),
+                    iterations=int(ref.iterations[0]), accepted=int(ref.accepted[0]), stop=int(ref.stop[0]), n_pairs=int(ref.n_pairs[0]), status=int(ref.status[0]),
+                    ok=bool(rep.ok()[0]))
+
     def explain(self, library, indices, weights: dict[str, float] | None = None, **kwargs):
         """Per-conformer maxima and explaining matches of library ligands `indices` (`engine.explain`)."""
         from .engine import explain

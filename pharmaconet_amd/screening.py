@@ -6,6 +6,7 @@ processes; needs OpenBabel like the reference) or a packed library file (`.pmxli
 `pharmaconet_amd.library`) with an optional `<library>.names` text file giving one path per ligand.
 Output: `path,score` CSV, best first, ties in library order (`screening.py:70-75`). Scoring runs on the GPU.
 `--explain K --clashes PATH [--protein FILE.pdb]` checks the explained hits' poses against the protein's atoms (excluded volumes).
+`--explain K --refine_out PATH [--refine_restraint X] [--refine_iter N]` moves those poses out of the protein's atoms (restrained rigid-body refinement).
 `--panel MODEL ... --panel_out PATH` scores the best hits against other pockets; `--save_top K PATH` keeps them as a packed library.
 `--actives FILE --enrichment_out PATH` validates the model retrospectively: the library's ligands named in FILE are the actives, the rest decoys.
 `--similar_to NAME ... --similar_out PATH` lists the library's ligands most similar to the named ones by their own pharmacophore fingerprints.
@@ -41,6 +42,9 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--protein", type=str, default=None, metavar="FILE.pdb", help="with --clashes: the protein, in the model's frame (default: the protein the model carries)")
         cfg.add_argument("--clash_tolerance", type=float, default=0.5, metavar="T", help="with --clashes: overlap of two spheres, in Angstrom, that is not yet a clash")
         cfg.add_argument("--clash_level", choices=("nodes", "atoms"), default="atoms", help="with --clashes: check the hit's pharmacophore nodes, or its heavy atoms (the hit files are read again; needs a library directory)")
+        cfg.add_argument("--refine_out", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit: its pose moved out of the protein's atoms by a restrained rigid-body refinement, checked before and after (uses --protein, --clash_tolerance and --clash_level)")
+        cfg.add_argument("--refine_restraint", type=float, default=0.1, metavar="X", help="with --refine_out: the weight of the restraint that holds the pose near its fit (uncalibrated default)")
+        cfg.add_argument("--refine_iter", type=int, default=32, metavar="N", help="with --refine_out: at most N trial motions per pose (0 to 64)")
         cfg.add_argument("--hotspots", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per (explained hit, model node it has terms with): the node's share of the hit's best conformer maximum and whether the hit engages it")
         cfg.add_argument("--diverse", type=int, default=None, metavar="K", help="list the K first hits that are not the same binding mode again (leaders by interaction fingerprint, in rank order)")
         cfg.add_argument("--diverse_pool", type=int, default=None, metavar="P", help="best hits that --diverse looks at (default: max(8 K, 1024), at most 65536)")
@@ -152,12 +156,18 @@ def main(argv=None) -> None:
         parser.error("--poses needs --explain K")
     if args.clashes and args.explain <= 0:
         parser.error("--clashes needs --explain K")
-    if not args.clashes and args.protein:
-        parser.error("--protein needs --clashes PATH")
-    if args.clashes and args.clash_level == "atoms" and Path(args.library_dir).is_file():
+    if args.refine_out and args.explain <= 0:
+        parser.error("--refine_out needs --explain K")
+    if not (args.clashes or args.refine_out) and args.protein:
+        parser.error("--protein needs --clashes PATH or --refine_out PATH")
+    if (args.clashes or args.refine_out) and args.clash_level == "atoms" and Path(args.library_dir).is_file():
         parser.error("--clash_level atoms reads the hit files again: a packed library has none (use --clash_level nodes)")
-    if args.clashes and not np.isfinite(args.clash_tolerance):
+    if (args.clashes or args.refine_out) and not np.isfinite(args.clash_tolerance):
         parser.error("--clash_tolerance takes a number")
+    if args.refine_out and not (np.isfinite(args.refine_restraint) and args.refine_restraint >= 0):
+        parser.error("--refine_restraint takes a number that is not negative")
+    if args.refine_out and not 0 <= args.refine_iter <= 64:
+        parser.error("--refine_iter takes 0 to 64")
     if args.hotspots and args.explain <= 0:
         parser.error("--hotspots needs --explain K")
     if args.diverse is not None and args.diverse <= 0:
@@ -224,13 +234,13 @@ def main(argv=None) -> None:
         Halogen=args.halogen,
         Hydrophobic=args.hydrophobic,
     )
-    if args.clashes:  # (before the screen: a model without a protein should not cost a pass)
+    if args.clashes or args.refine_out:  # (before the screen: a model without a protein should not cost a pass)
         from .pocket import PocketAtoms
 
         try:
             pocket = PocketAtoms.from_pdb(Path(args.protein), centers=model.node_centers) if args.protein else model.pocket_atoms()
         except (OSError, ValueError) as e:
-            parser.error(f"--clashes: {e}" + ("" if args.protein else " (give it with --protein FILE.pdb)"))
+            parser.error(f"{'--clashes' if args.clashes else '--refine_out'}: {e}" + ("" if args.protein else " (give it with --protein FILE.pdb)"))
     names, lib = load_library(Path(args.library_dir), args.cpus, on_device=True)
     if args.actives:  # (before the screen: a name that matches nothing should not cost a pass)
         from .validation import match_actives
@@ -263,6 +273,9 @@ def main(argv=None) -> None:
             write_poses_csv(Path(args.poses), names, scores, status, model, lib, weight, args.explain)
         if args.clashes:
             write_clashes_csv(Path(args.clashes), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_level, args.clash_tolerance)
+        if args.refine_out:
+            write_refine_csv(Path(args.refine_out), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_level, args.clash_tolerance,
+                             args.refine_restraint, args.refine_iter)
         if args.hotspots:
             write_hotspots_csv(Path(args.hotspots), names, scores, status, model, lib, weight, args.explain)
         if args.modes is not None:
@@ -505,6 +518,39 @@ def write_clashes_csv(out: Path, names: list[str], scores: np.ndarray, status: n
             w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{level},{int(rep.n_points[r])},{int(rep.n_clashing[r])},{int(rep.n_pairs[r])},"
                     f"{float(rep.clearance[r])!r},{float(rep.overlap[r])!r},{int(rep.n_contacts[r])},{int(rep.worst[r, 0])},{rep.atom_label(r, pocket)},"
                     f"{';'.join(rep.residues(r, pocket))}\n")
+
+
+REFINE_HEADER = ("rank,path,conformer,level,pairs_before,overlap_before,pairs_after,overlap_after,clearance_after,clashing_after,anchor_rmsd,angle_deg,shift,iterations,stop,"
+                 "r00,r01,r02,r10,r11,r12,r20,r21,r22,tx,ty,tz")
+
+
+def write_refine_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, pocket, level: str, tolerance: float,
+                     restraint: float, max_iter: int) -> None:
+    """One row per hit of the k best, in the order of the poses CSV: the pose of the hit's best conformer (`engine.align`) moved out of the
+    protein's heavy atoms (`engine.refine`) - the hit's pharmacophore nodes at level `nodes`, the heavy atoms of its file at level `atoms` -
+    with the check (`engine.clashes`) before and after: clashing pairs and overlap before; pairs, overlap, the deepest penetration and the
+    clashing points after; how far the anchors moved (rmsd), the net rotation in degrees, the centroid's shift, the trial motions taken and
+    why they ended (`RefinedPoses.stop`); the refined rotation, row-major, and translation. A pose that is not OK has nan and stop -1."""
+    from .engine import explain
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
+    atoms = None
+    if level == "atoms":
+        from .ligand import Ligand
+
+        atoms = [Ligand.load_from_file(names[order[int(row)]]) for row in al.rows]
+    before = al.clashes(pocket, lib, atoms=atoms, tolerance=tolerance)
+    ref = al.refine(pocket, lib, atoms=atoms, tolerance=tolerance, restraint=restraint, max_iter=max_iter)
+    after = ref.clashes(pocket, lib, atoms=atoms, tolerance=tolerance)
+    with open(out, "w") as w:
+        w.write(REFINE_HEADER + "\n")
+        for r, row in enumerate(al.rows):
+            motion = ",".join(repr(float(v)) for v in (*ref.rotation[r].reshape(-1), *ref.translation[r]))
+            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{level},{int(before.n_pairs[r])},{float(before.overlap[r])!r},{int(after.n_pairs[r])},"
+                    f"{float(after.overlap[r])!r},{float(after.clearance[r])!r},{int(after.n_clashing[r])},{float(ref.anchor_rmsd[r])!r},"
+                    f"{float(np.degrees(ref.angle[r]))!r},{float(ref.shift[r])!r},{int(ref.iterations[r])},{int(ref.stop[r])},{motion}\n")
 
 
 if __name__ == "__main__":
