@@ -153,7 +153,8 @@ int pmx_score_multi(const pmx_model *const *models, int n_models, const pmx_libr
 
 /*
  * The ranking step of screening.py:70 (`result.sort(key=score, reverse=True)`, stable): the k best
- * of scores_dev[n] in descending score order, ties in ascending index order. index_dev may be
+ * of scores_dev[n] in descending score order, ties in ascending index order. -0.0 and +0.0 are one value (they tie; each is
+ * reported as given). index_dev may be
  * NULL (element i has index base_index + i) or give each element's global index.
  * out_scores_dev[k], out_index_dev[k]; if n < k the tail is filled with -inf / UINT64_MAX. A NaN score (an unsupported ligand)
  * ranks after every real score and is reported as NaN with its index; input elements whose index is UINT64_MAX are padding

@@ -59,6 +59,17 @@ struct Weights {
 
 __host__ __device__ inline uint64_t round16(uint64_t x) { return (x + 15) & ~uint64_t(15); }
 
+// Rank key of a real score (not a NaN), the one definition for every unit that ranks (pmx_topk.hip, pmx_enrich.hip): an ascending key
+// is a descending score, equal scores have equal keys. -0.0 and +0.0 are one value, so the zero is made +0.0 before its bits are read
+// (the units are built with -fno-fast-math: the comparison stays). +inf -> 0x007fffff, +-0.0 -> 0x7fffffff, -inf -> 0xff800000, the
+// largest key of a real score; the keys above it are the callers' (NaN, padding, uncounted).
+__host__ __device__ inline uint32_t score_rank_key(float s) {
+    if (s == 0.0f) s = 0.0f;
+    uint32_t u = __builtin_bit_cast(uint32_t, s);
+    u = (u >> 31) ? ~u : (u | 0x80000000u); // ascending with the float
+    return ~u;
+}
+
 // A ligand record of the packed library (pharmaconet_amd/library.py).
 struct Record {
     int n, C, ncl;

@@ -116,10 +116,7 @@ __global__ __launch_bounds__(kThreads) void keys_kernel(const float *scores, con
     if (i >= n) return;
     float s = scores[i];
     if (s != s || (status && status[i] != 0)) s = -INFINITY;
-    if (s == 0.0f) s = 0.0f; // -0.0 and +0.0 are one value
-    uint32_t u = __float_as_uint(s);
-    u = (u >> 31) ? ~u : (u | 0x80000000u); // ascending with the float
-    keys[i] = labels[i] < 2u ? ~u : kKeyUncounted;
+    keys[i] = labels[i] < 2u ? pmx::score_rank_key(s) : kKeyUncounted; // (-0.0 and +0.0 are one value)
     idx[i] = i;
 }
 

@@ -35,13 +35,12 @@ struct SelState {
     uint32_t pad[2];
 };
 
-// Rank key of a score: ascending key = descending score. Real scores (incl. -inf) < NaN (0xfffffffe) < padding (0xffffffff).
+// Rank key of a score: ascending key = descending score. Real scores (incl. -inf; -0.0 and +0.0 share one key:
+// pmx::score_rank_key) < NaN (0xfffffffe) < padding (0xffffffff).
 __device__ inline uint32_t rank_key(float s, bool padding) {
     if (padding) return 0xffffffffu;
     if (s != s) return 0xfffffffeu;
-    uint32_t u = __float_as_uint(s);
-    u = (u >> 31) ? ~u : (u | 0x80000000u); // ascending with the float
-    return ~u;
+    return pmx::score_rank_key(s);
 }
 
 __global__ void sel_init(SelState *st, uint32_t *hist, uint32_t k, int take_all) {

@@ -538,7 +538,26 @@ def _weights_array(weights):
 
 
 def topk(scores, k: int, base_index: int = 0, indices=None):
-    """k best of a device float32 tensor: (scores [k], int64 global indices [k]); ties by ascending index."""
+    """k best of a device float32 tensor: (scores [k], int64 global indices [k]); ties by ascending index.
+
+    The library is handed addresses and a count, so what it would read as other bytes is refused here (ValueError): `scores` must be a
+    contiguous float32 tensor on a GPU, `indices` (if given) a contiguous int64 tensor of the same length on the same device, k >= 0."""
+    import torch
+
+    k = int(k)
+    if scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise ValueError(f"topk: scores must be a contiguous float32 tensor, not {scores.dtype}{'' if scores.is_contiguous() else ' (not contiguous)'}")
+    if k < 0:
+        raise ValueError(f"topk: k must not be negative, not {k}")
+    if indices is not None:
+        if indices.dtype != torch.int64 or not indices.is_contiguous():
+            raise ValueError(f"topk: indices must be a contiguous int64 tensor, not {indices.dtype}{'' if indices.is_contiguous() else ' (not contiguous)'}")
+        if indices.numel() != scores.numel():
+            raise ValueError(f"topk: {indices.numel()} indices for {scores.numel()} scores")
+        if indices.device != scores.device:
+            raise ValueError(f"topk: indices on {indices.device}, scores on {scores.device}")
+    if not scores.is_cuda:
+        raise ValueError(f"topk: scores must be on a GPU, not on {scores.device}")
     torch = _torch()
     lib = _ffi.load()
     dev = scores.device.index
