@@ -716,6 +716,61 @@ int pmx_pose_refine(const pmx_pocket *pocket, const pmx_library *lib /* NULL in 
                     int32_t *count_dev /* [n][4] */, int32_t *status_dev, void *stream);
 
 /*
+ * Pose search (pmx_pose_search.hip): which of a hit's conformers, under which of its binding modes, to pose. pmx_explain's single pose -
+ * the best conformer under its own key - often grazes a side chain where the second conformer, or the same conformer under its second
+ * mode, sits in the cavity. The call takes the output of a pmx_explain_modes call over exactly ligands_dev[n] (with or without a
+ * constraint) - mode_max_dev [n][n_modes][PMX_MAX_CONFORMERS], mode_match_dev [n][n_modes][PMX_MAX_CONFORMERS][PMX_MAX_LEVELS] and its
+ * status_dev [n] (explain_status_dev) - fits the slots with pmx_align, checks the fits with pmx_pose_clash in node mode, and chooses one
+ * slot per hit. The reference has no counterpart; the specification is this comment, and tests/pose_search_ref.py restates it in NumPy.
+ *
+ * Slot (i, m, c), m < n_modes, c < conf_stride (the conformers searched per hit; a ligand with fewer has zeros there), v = mode_max[i][m][c].
+ *   vbest      of hit i: the largest v > 0 over its slots (0 when there is none, or when the hit's explain status is not 0)
+ *   row        of a slot: (ligands_dev[i], c, mode_match[i][m][c]) as pmx_align and pmx_pose_clash take rows; model, lib, weights and
+ *              node_center_dev are pmx_align's, point_radius, tolerance and contact pmx_pose_clash's
+ *   candidate  a slot for which all of these hold: the explain status of hit i is 0; v > 0; pmx_align of the row has status OK and
+ *              count[0] >= min_fitted fitted nodes; pmx_pose_clash of the row under that motion has status OK; v >= min_fraction * vbest,
+ *              the product formed in float64
+ *   dropped    a slot of a hit with explain status 0 and v > 0 for which v >= min_fraction * vbest does not hold, whatever its fit
+ *   passes     a candidate whose count of points with a clashing pair (pmx_pose_clash's count[1]) is <= max_clashing
+ *   the choice among the passing candidates: the largest v, then the lowest c, then the lowest m. When no candidate passes, among the
+ *              candidates: the smallest overlap (pmx_pose_clash's summary[1]), then the largest v, then the lowest c, then the lowest m.
+ *              Without a candidate there is no choice.
+ * Every comparison is on the float64 bits the two calls produce, or on integers: nothing new is rounded but fraction below.
+ * Consequence: where the default pose - the hit's best conformer under mode 0, what pmx_explain poses - passes and has min_fitted fitted
+ * nodes, it is the choice: it has the largest v of all slots, the lowest c among those that reach it, and m = 0.
+ * Outputs, per hit:
+ *   choice_dev  int32 [n][6]   conformer, mode (-1, -1 without a choice), passes 0 / 1, candidates, passing candidates, dropped slots
+ *   value_dev   double [n][2]  v of the choice and v / vbest; NaN without a choice
+ *   key_dev     uint8 [n][PMX_MAX_LEVELS]  the choice's key; 0xFF throughout without a choice
+ *   rot_dev, trans_dev, fit_dev, node_dev, count_dev, levels_dev   what pmx_align writes for the row (ligand, conformer, key) of the
+ *               choice, bit for bit; without a choice the row has conformer -1: NaN and counts of 0, as for any pmx_align row that is not OK
+ *   summary_dev, clash_count_dev, point_pen_dev, point_atom_dev, contact_fp_dev   what pmx_pose_clash writes for that row under that
+ *               motion, bit for bit (without a choice: a row that is not OK)
+ *   status_dev  int32 [n]      the hit's explain status. "Nothing to pose" is no error: status 0 with 0 candidates
+ *   row_status_dev  int32 [2][n]  the statuses pmx_align ([0][i]) and pmx_pose_clash ([1][i]) give that row: OK with a choice, and
+ *               otherwise what says why a hit could not be posed at all (PMX_LIGAND_UNSUPPORTED or PMX_LIGAND_KEY_INVALID)
+ * 1 <= n_modes <= PMX_MAX_MODES, 1 <= conf_stride <= PMX_MAX_CONFORMERS, max_clashing >= 0, min_fitted >= 1, min_fraction in [0, 1],
+ * point_radius, tolerance and contact finite, n * n_modes * conf_stride <= PMX_EXPLAIN_MAX: otherwise PMX_ERR_INVALID. n = 0 succeeds and
+ * writes nothing. With n > 0 no pointer may be NULL; the library is on the pocket's device and the pointers are memory of it.
+ * work_dev: at least pmx_pose_search_work_bytes(n, n_modes, conf_stride) bytes of that device, 16-byte aligned, the caller's; its
+ * contents mean nothing before or after. The query answers 0 for a shape the call would refuse and grows with each argument.
+ * The call allocates nothing and synchronises nothing: stream-ordered like pmx_align, whose workspace of (device, stream) it uses. A
+ * kernel writes the slots' rows into the work buffer (a slot that cannot be a candidate by its v alone gets conformer -1 and passes
+ * through both calls as PMX_LIGAND_KEY_INVALID), pmx_align and pmx_pose_clash run on them, a second kernel - one wavefront per hit, its
+ * lanes over the hit's slots in trips of 64, a lexicographic reduction of fixed shape - chooses, and the two calls run once more on the n
+ * chosen rows. No atomic: the same bits on every run, and for a hit wherever it stands in a call.
+ */
+uint64_t pmx_pose_search_work_bytes(uint32_t n, int n_modes, int conf_stride);
+int pmx_pose_search(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], const double *node_center_dev,
+                    const pmx_pocket *pocket, const uint64_t *ligands_dev, uint32_t n, const double *mode_max_dev, const uint8_t *mode_match_dev,
+                    const int32_t *explain_status_dev, int n_modes, int conf_stride, float point_radius, float tolerance, float contact,
+                    int max_clashing, int min_fitted, double min_fraction, int32_t *choice_dev /* [n][6] */, double *value_dev /* [n][2] */,
+                    uint8_t *key_dev /* [n][PMX_MAX_LEVELS] */, double *rot_dev, double *trans_dev, double *fit_dev, double *node_dev,
+                    int32_t *count_dev /* [n][2] */, uint8_t *levels_dev, double *summary_dev, int32_t *clash_count_dev /* [n][6] */,
+                    double *point_pen_dev, int32_t *point_atom_dev, uint64_t *contact_fp_dev, int32_t *status_dev,
+                    int32_t *row_status_dev /* [2][n] */, void *work_dev, uint64_t work_bytes, void *stream);
+
+/*
  * Retrospective validation (pmx_enrich.hip): does a model, under given type weights, rank known binders above decoys? Per column of scores
  * over one labelled list, and per bootstrap resample of the list, the integers and sums from which the host derives AUROC, enrichment
  * factors and BEDROC. The specification is this comment (the reference has no counterpart); tests/enrichment_ref.py restates it in NumPy.

@@ -91,6 +91,8 @@ class ScoreStats(ctypes.Structure):
 
 MAX_REQUIRE_GROUPS = 8
 MAX_MODES = 8  # include/pmx.h PMX_MAX_MODES
+MAX_CONFORMERS = 64  # PMX_MAX_CONFORMERS
+EXPLAIN_MAX = 65536  # PMX_EXPLAIN_MAX: rows of one explain / row / pose call; pmx_pose_search: hits x modes x conformers
 
 
 class MatchConstraint(ctypes.Structure):
@@ -242,6 +244,13 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_float, ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_int,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    ),
+    "pmx_pose_search_work_bytes": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_int, ctypes.c_int]),
+    "pmx_pose_search": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+         *([ctypes.c_void_p] * 16), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
     ),
     "pmx_score_stats_get": (ctypes.c_int, [ctypes.POINTER(ScoreStats)]),
     "pmx_set_profiling": (ctypes.c_int, [ctypes.c_int]),

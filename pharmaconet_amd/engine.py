@@ -473,7 +473,7 @@ class ScreeningResult:
                            pool=idx.astype(np.uint64), profile=None)
 
     def fitting(self, k: int, pool: int | None = None, max_clashing: int = 0, pocket=None, atoms=None, model=None, library=None,
-                weights: dict[str, float] | None = None, refine: bool = False, **kw) -> "FittingHits":
+                weights: dict[str, float] | None = None, refine: bool = False, search: int = 0, **kw) -> "FittingHits":
         """The k first hits of this screen whose pose fits the pocket: the best `pool` hits (default min(len, max(8 k, 1024), 65536)) are
         explained, posed at their best conformer (`Explanation.poses`) and checked against the protein's atoms (`Alignment.clashes`); a hit
         passes with status 0 and at most `max_clashing` clashing points. In rank order; a hit that was not scored, or whose pose is not OK,
@@ -485,9 +485,20 @@ class ScreeningResult:
         posed hit: one call refines all rows of the pool (a row keeps its place, and the call costs milliseconds), but only
         the motions of the rows that failed are used. The fit fields of `poses` (`rmsd`, `sse`, `node`, ...) still describe the
         least-squares fit, not the refined motion; `refined.anchor_rmsd` says how far that moved. `restraint`, `max_iter` and `ftol` go to `refine`, and `refine_tolerance` is the tolerance it runs at (default: the
-        check's; a penalty balanced against a restraint leaves a little overlap, so a smaller one is what makes grazing poses pass)."""
+        check's; a penalty balanced against a restraint leaves a little overlap, so a smaller one is what makes grazing poses pass).
+        With `search` = M > 0, a hit is posed not at its best conformer alone but where `pose_search` over all its conformers and their M
+        best binding modes puts it: the best-scoring pose whose nodes pass, else the one of smallest overlap - which is then what `refine`
+        starts from. `min_fraction` and `min_fitted` go to the search (a pose worth less than `min_fraction` of the hit's best is not
+        considered). `poses` has a row for every hit that was scored; one without any pose has conformer -1 and never passes. `atoms`
+        verifies the chosen poses exactly as without the search."""
         if k <= 0:
             raise ValueError("k must be positive")
+        search = int(search)
+        if not 0 <= search <= _ffi.MAX_MODES:
+            raise ValueError(f"search: 0 (off) or 1 to {_ffi.MAX_MODES} binding modes")
+        search_kw = {name: kw.pop(name) for name in ("min_fraction", "min_fitted") if name in kw}
+        if search_kw and not search:
+            raise ValueError(f"{sorted(search_kw)}: arguments of the pose search, which is off (search=M)")
         refine_kw = {name: kw.pop(name) for name in ("restraint", "max_iter", "ftol", "refine_tolerance") if name in kw}
         if refine_kw and not refine:
             raise ValueError(f"{sorted(refine_kw)}: arguments of the refinement, which is off (refine=True)")
@@ -498,8 +509,18 @@ class ScreeningResult:
             raise ValueError("pool: 1 to 65536 hits")
         pocket = model.pocket_atoms() if pocket is None else pocket
         with _resident(library) as dlib:
-            ex = explain(model, dlib, self._best(pool), weights=weights)
-            al = ex.poses(model, dlib, weights=weights)
+            if search:
+                shared = {name: kw[name] for name in ("tolerance", "contact", "node_radius") if name in kw}
+                ms = explain_modes(model, dlib, self._best(pool), modes=search, weights=weights)
+                ps = ms.pose_search(model, dlib, pocket, weights=weights, max_clashing=max_clashing, **shared, **search_kw)
+                ex = ms.explanation(0)  # (the hits' scores, as without the search)
+                scored = np.flatnonzero(ps.status == 0)
+                al = ps.alignment()
+                al = dataclasses.replace(al, **{f.name: ([getattr(al, f.name)[r] for r in scored] if isinstance(getattr(al, f.name), list) else getattr(al, f.name)[scored])
+                                                for f in dataclasses.fields(al)})  # (`rows`, the hit behind each row, becomes `scored`)
+            else:
+                ex = explain(model, dlib, self._best(pool), weights=weights)
+                al = ex.poses(model, dlib, weights=weights)
             mols = None if atoms is None else [atoms(int(i)) for i in al.indices]
             rep = al.clashes(pocket, dlib, atoms=mols, **kw)
             refined = None
@@ -1022,10 +1043,9 @@ def _constraint(require, exclude):
     return groups, excluded
 
 
-def _explain_rows(model, library: "DeviceLibrary", indices, modes: int, weights, constraint, entry: str) -> "ModeSet":
-    """One call of `entry` (its limits are the call's to enforce) and its rows cut to each ligand's conformers and levels, as a `ModeSet`:
-    `pmx_explain` (no constraint) and `pmx_explain_constrained` (`constraint` None - a NULL constraint - or normalised (groups, excluded))
-    answer with one mode, `pmx_explain_modes` with `modes`."""
+def _explain_call(model, library: "DeviceLibrary", indices, modes: int, weights, constraint, entry: str):
+    """One call of `entry` enqueued on torch's current stream of the library's device, not waited for: (idx, ligands, values, match, levels,
+    best, status, stream) - the indices, and the call's device tensors as the C ABI lays them out (at least one row each)."""
     torch = _torch()
     lib = _ffi.load()
     idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
@@ -1049,7 +1069,17 @@ def _explain_rows(model, library: "DeviceLibrary", indices, modes: int, weights,
         which = {"pmx_explain": (), "pmx_explain_constrained": (con,), "pmx_explain_modes": (con, modes)}[entry]
         _ffi.check(getattr(lib, entry)(mh.handle, library.handle, _weights_array(weights), *which, lig.data_ptr(), n, values.data_ptr(), match.data_ptr(),
                                        levels.data_ptr(), best.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
-        stream.synchronize()
+    return idx, lig, values, match, levels, best, status, stream
+
+
+def _explain_rows(model, library: "DeviceLibrary", indices, modes: int, weights, constraint, entry: str) -> "ModeSet":
+    """One call of `entry` (its limits are the call's to enforce) and its rows cut to each ligand's conformers and levels, as a `ModeSet`:
+    `pmx_explain` (no constraint) and `pmx_explain_constrained` (`constraint` None - a NULL constraint - or normalised (groups, excluded))
+    answer with one mode, `pmx_explain_modes` with `modes`."""
+    idx, _, values, match, levels, best, status, stream = _explain_call(model, library, indices, modes, weights, constraint, entry)
+    stream.synchronize()
+    n = len(idx)
+    L, CM = 20, 64  # PMX_MAX_LEVELS, PMX_MAX_CONFORMERS
     vl, mt, lv = values.cpu().numpy().reshape(-1, modes, CM)[:n], match.cpu().numpy().reshape(-1, modes, CM, L)[:n], levels.cpu().numpy()[:n]
     st, bc = status.cpu().numpy()[:n].astype(np.int32), best.cpu().numpy()[:n].astype(np.int64)
     conf = _record_counts(library, idx, 1)
@@ -1130,6 +1160,35 @@ class ModeSet:
                            match=[k[m] for k in self.match], status=self.status, require=self.require, exclude=self.exclude)
 
 
+    def pose_search(self, model, library, pocket=None, weights: dict[str, float] | None = None, max_clashing: int = 0, min_fitted: int = 1, min_fraction: float = 0.0,
+                    tolerance: float = 0.5, contact: float = 4.5, node_radius: float = 1.0, conformers: int | None = None, device=None) -> "PoseSearch":
+        """`pose_search` of these rows over the modes already held: the values and keys are uploaded instead of explained again. `weights`
+        must be the ones the modes were made with (they weigh the fit)."""
+        L, CM = _MAX_LEVELS, _ffi.MAX_CONFORMERS
+        n, modes = len(self), self.modes
+        values = np.zeros((max(n, 1), modes, CM), np.float64)
+        match = np.full((max(n, 1), modes, CM, L), NO_MATCH, np.uint8)
+        for i in range(n):
+            if self.status[i] != 0:
+                values[i] = np.nan
+                continue
+            C, nl = self.values[i].shape[1], len(self.levels[i])
+            values[i, :, :C] = self.values[i]
+            match[i, :, :C, :nl] = np.where(self.match[i] < 0, NO_MATCH, self.match[i]).astype(np.uint8)
+        status = np.ascontiguousarray(self.status, dtype=np.int32) if n else np.zeros(1, np.int32)
+        idx = np.ascontiguousarray(self.indices, dtype=np.int64)
+        torch = _torch()
+        with _resident(library, device) as dlib:
+            tdev = torch.device("cuda", dlib.device)
+
+            def explained(lo, hi):
+                hi = max(hi, lo + 1)
+                return tuple(torch.from_numpy(np.ascontiguousarray(a[lo:hi])).to(tdev) for a in (values, match, status))
+
+            return _pose_search(model, dlib, _search_pocket(model, pocket), idx, modes, weights, explained, max_clashing, min_fitted, min_fraction, tolerance, contact,
+                                node_radius, conformers)
+
+
 def explain_modes(model, library, indices, modes: int = 4, weights: dict[str, float] | None = None, device=None, require=None, exclude=None) -> ModeSet:
     """The `modes` (1 to 8) best binding modes per conformer of the library ligands `indices` (`pmx_explain_modes`, csrc/pmx_explain.hip):
     mode 0 is `explain`'s answer bit for bit, the others are the runners-up in the order a `ModeSet` describes. Any number of ligands
@@ -1146,6 +1205,166 @@ def explain_modes(model, library, indices, modes: int = 4, weights: dict[str, fl
                    match=[m for p in parts for m in p.match], levels=[v for p in parts for v in p.levels],
                    best_conformer=np.concatenate([p.best_conformer for p in parts]), status=np.concatenate([p.status for p in parts]),
                    require=parts[0].require, exclude=parts[0].exclude)
+
+
+@dataclass
+class PoseSearch:
+    """What `pose_search` returns: per listed hit the conformer and the binding mode to pose it in (definitions: `pmx_pose_search` in
+    include/pmx.h). Among the slots (mode m < `modes`, conformer c) whose fit is OK, has `min_fitted` fitted nodes and is worth
+    `min_fraction` of the hit's best leaf total: the best-scoring one that passes the clash check, else the one of smallest overlap.
+
+    conformer[i], mode[i]   the choice, -1 and -1 where the hit has no candidate (it was not scored, scores 0, or no fit is OK)
+    passes[i]               the chosen pose has at most `max_clashing` clashing points
+    n_candidates[i], n_passing[i], n_dropped[i]   candidates, passing candidates, and slots left out by `min_fraction`
+    value[i], fraction[i]   the chosen leaf's total, and that over the hit's best total: 1.0 where nothing was given up; NaN without a choice
+    key[i]                  int [nl]: the chosen key (`Explanation.match`), all -1 without a choice
+    status[i]               the hit's status as `explain` reports it
+    `alignment()` and `report()` are what `align` and `clashes` answer for the chosen rows, bit for bit."""
+
+    indices: np.ndarray
+    modes: int
+    conformer: np.ndarray
+    mode: np.ndarray
+    passes: np.ndarray
+    n_candidates: np.ndarray
+    n_passing: np.ndarray
+    n_dropped: np.ndarray
+    value: np.ndarray
+    fraction: np.ndarray
+    key: list
+    status: np.ndarray
+    poses: "Alignment"
+    clash: "ClashReport"
+
+    def __len__(self) -> int:
+        return len(self.indices)
+
+    def alignment(self) -> "Alignment":
+        """The chosen rows as an ordinary `Alignment` (`clashes(atoms=...)`, `refine`, `transform`): row i is hit i; a hit without a
+        choice is a row with conformer -1 and status 4 (or 1)."""
+        return self.poses
+
+    def report(self) -> "ClashReport":
+        """The `ClashReport` of the chosen rows' pharmacophore nodes, at the search's own radius, tolerance and contact distance."""
+        return self.clash
+
+
+def _search_chunks(conf: np.ndarray, modes: int):
+    """(lo, hi, conf_stride) of consecutive runs of hits with (hi - lo) * modes * conf_stride <= 65536, conf_stride the most conformers
+    (1 to 64) of a hit of the run."""
+    conf = np.clip(conf, 1, _ffi.MAX_CONFORMERS)
+    lo, n = 0, len(conf)
+    while lo < n:
+        hi, stride = lo, 1
+        while hi < n and (hi + 1 - lo) * modes * max(stride, int(conf[hi])) <= _ffi.EXPLAIN_MAX:
+            stride = max(stride, int(conf[hi]))
+            hi += 1
+        yield lo, hi, stride
+        lo = hi
+
+
+def _pose_search(model, dlib: "DeviceLibrary", pocket, idx: np.ndarray, modes: int, weights, explained, max_clashing, min_fitted, min_fraction, tolerance, contact,
+                 node_radius, conformers) -> PoseSearch:
+    """`pose_search` on a resident library. `explained(lo, hi)` enqueues - or uploads - rows lo .. hi of the hits' `pmx_explain_modes` output
+    and returns the device tensors (values, match, status). Every chunk is enqueued before the one wait."""
+    torch = _torch()
+    lib = _ffi.load()
+    if (idx < 0).any():
+        raise ValueError("negative ligand index")
+    if int(max_clashing) < 0 or int(min_fitted) < 1 or not 0.0 <= float(min_fraction) <= 1.0:
+        raise ValueError("pose_search: max_clashing >= 0, min_fitted >= 1 and min_fraction in [0, 1]")
+    if conformers is not None and not 1 <= int(conformers) <= _ffi.MAX_CONFORMERS:
+        raise ValueError(f"pose_search: conformers 1 to {_ffi.MAX_CONFORMERS}")
+    n = len(idx)
+    m = max(n, 1)
+    L, NN = _MAX_LEVELS, _MAX_NODES
+    mh = device_model(model, dlib.device)
+    ph = device_pocket(pocket, dlib.device)
+    tdev = torch.device("cuda", dlib.device)
+    conf = _record_counts(dlib, idx, 1)
+    chunks = list(_search_chunks(conf if conformers is None else np.minimum(conf, int(conformers)), modes))
+    with torch.cuda.device(tdev):
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=tdev)  # noqa: E731
+        f64, i32, u8 = torch.float64, torch.int32, torch.uint8
+        out = dict(choice=new((m, 6), i32), value=new((m, 2), f64), key=new((m, L), u8), rot=new((m, 9), f64), trans=new((m, 3), f64), fit=new((m, 8), f64),
+                   node=new((m, NN), f64), count=new((m, 2), i32), levels=new((m, L), u8), summary=new((m, 4), f64), ccount=new((m, 6), i32), ppen=new((m, NN), f64),
+                   patom=new((m, NN), i32), fp=new((m, _FP_WORDS), torch.int64), status=new((m,), i32))
+        row_status = [new((2, max(hi - lo, 1)), i32) for lo, hi, _ in chunks]
+        need = max([int(lib.pmx_pose_search_work_bytes(hi - lo, modes, stride)) for lo, hi, stride in chunks] + [256])
+        work = new((need,), u8)
+        centers = mh.node_centers(model)
+        stream = torch.cuda.current_stream(tdev)
+        keep = []
+        for (lo, hi, stride), rs in zip(chunks, row_status):
+            lig = torch.from_numpy(np.ascontiguousarray(idx[lo:hi])).to(tdev)
+            values, match, est = explained(lo, hi)
+            keep.append((lig, values, match, est))
+            at = lambda name: out[name][lo:].data_ptr()  # noqa: E731, B023
+            _ffi.check(lib.pmx_pose_search(mh.handle, dlib.handle, _weights_array(weights), centers.data_ptr(), ph.handle, lig.data_ptr(), hi - lo, values.data_ptr(),
+                                           match.data_ptr(), est.data_ptr(), modes, stride, float(node_radius), float(tolerance), float(contact), int(max_clashing),
+                                           int(min_fitted), float(min_fraction), at("choice"), at("value"), at("key"), at("rot"), at("trans"), at("fit"), at("node"),
+                                           at("count"), at("levels"), at("summary"), at("ccount"), at("ppen"), at("patom"), at("fp"), at("status"), rs.data_ptr(),
+                                           work.data_ptr(), need, ctypes.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+        del keep
+    nn = _record_counts(dlib, idx, 0)
+    h = {k: v.cpu().numpy()[:n] for k, v in out.items()}
+    ast = np.concatenate([r.cpu().numpy()[0, : hi - lo] for (lo, hi, _), r in zip(chunks, row_status)] + [np.zeros(0, np.int32)]).astype(np.int32)
+    cst = np.concatenate([r.cpu().numpy()[1, : hi - lo] for (lo, hi, _), r in zip(chunks, row_status)] + [np.zeros(0, np.int32)]).astype(np.int32)
+    ch, lv = h["choice"].astype(np.int64), h["levels"]
+    nl = [int(np.count_nonzero(lv[i] != NO_LEVEL)) for i in range(n)]
+    keys = []
+    for i in range(n):
+        k = h["key"][i, : nl[i]].astype(np.int64)
+        k[k == NO_MATCH] = -1
+        keys.append(k)
+    an = [int(nn[i]) if ast[i] != 1 else 0 for i in range(n)]
+    cn = [int(nn[i]) if cst[i] != 1 else 0 for i in range(n)]
+    ft, cc = h["fit"], h["ccount"].astype(np.int64)
+    idx = idx.astype(np.int64)
+    poses = Alignment(indices=idx, conformers=ch[:, 0].copy(), rotation=h["rot"].reshape(-1, 3, 3).copy(), translation=h["trans"].copy(), rmsd=ft[:, 2].copy(),
+                      rmsd_nodes=ft[:, 3].copy(), weight=ft[:, 0].copy(), sse=ft[:, 1].copy(), scale=ft[:, 4].copy(), gap=ft[:, 5].copy(),
+                      node=[h["node"][i, : an[i]].copy() for i in range(n)], n_nodes=h["count"][:, 0].astype(np.int64), n_pairs=h["count"][:, 1].astype(np.int64),
+                      levels=[lv[i, : nl[i]].astype(np.int64) for i in range(n)], status=ast, rows=np.arange(n, dtype=np.int64))
+    clash = ClashReport(clearance=h["summary"][:, 0].copy(), overlap=h["summary"][:, 1].copy(), n_points=cc[:, 0].copy(), n_clashing=cc[:, 1].copy(), n_pairs=cc[:, 2].copy(),
+                        n_contacts=cc[:, 3].copy(), worst=cc[:, 4:6].copy(), point_penetration=[h["ppen"][i, : cn[i]].copy() for i in range(n)],
+                        point_atom=[h["patom"][i, : cn[i]].astype(np.int64) for i in range(n)], contact_fingerprint=h["fp"].view(np.uint64).copy(), status=cst,
+                        device=dlib.device)
+    return PoseSearch(indices=idx, modes=modes, conformer=ch[:, 0].copy(), mode=ch[:, 1].copy(), passes=ch[:, 2] != 0, n_candidates=ch[:, 3].copy(), n_passing=ch[:, 4].copy(),
+                      n_dropped=ch[:, 5].copy(), value=h["value"][:, 0].copy(), fraction=h["value"][:, 1].copy(), key=keys, status=h["status"].astype(np.int32), poses=poses,
+                      clash=clash)
+
+
+def _search_pocket(model, pocket):
+    from .pocket import PocketAtoms
+
+    if pocket is None:
+        return model.pocket_atoms()
+    return pocket if isinstance(pocket, PocketAtoms) else pocket.pocket_atoms()
+
+
+def pose_search(model, library, pocket, indices, modes: int = 4, weights: dict[str, float] | None = None, require=None, exclude=None, max_clashing: int = 0,
+                min_fitted: int = 1, min_fraction: float = 0.0, tolerance: float = 0.5, contact: float = 4.5, node_radius: float = 1.0,
+                conformers: int | None = None, device=None) -> PoseSearch:
+    """Per hit of `indices` the conformer and binding mode that fits the pocket (`pmx_explain_modes`, then `pmx_pose_search`,
+    csrc/pmx_pose_search.hip): every conformer (the first `conformers` of each, if given) under each of its `modes` (1 to 8) best modes is
+    fitted (`align`) and checked against the atoms of `pocket` (a `pocket.PocketAtoms`, a model that carries its protein, or None for
+    `model`'s own) as `clashes` checks pharmacophore nodes of `node_radius` at `tolerance` and `contact`. See `PoseSearch` for the choice.
+    `require` / `exclude` as `explain_modes` takes them. Any number of hits: calls of at most 65536 (hit, mode, conformer) slots each, all
+    enqueued on torch's current stream of the library's device and waited for once."""
+    modes = int(modes)
+    if not 1 <= modes <= _ffi.MAX_MODES:
+        raise _ffi.PmxError(f"{modes} modes (1 to {_ffi.MAX_MODES}, PMX_MAX_MODES)")
+    constraint = _constraint(require, exclude)
+    idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+    with _resident(library, device) as dlib:
+
+        def explained(lo, hi):
+            _, _, values, match, _, _, status, _ = _explain_call(model, dlib, idx[lo:hi], modes, weights, constraint, "pmx_explain_modes")
+            return values, match, status
+
+        return _pose_search(model, dlib, _search_pocket(model, pocket), idx, modes, weights, explained, max_clashing, min_fitted, min_fraction, tolerance, contact,
+                            node_radius, conformers)
 
 
 @dataclass

@@ -7,6 +7,7 @@ processes; needs OpenBabel like the reference) or a packed library file (`.pmxli
 Output: `path,score` CSV, best first, ties in library order (`screening.py:70-75`). Scoring runs on the GPU.
 `--explain K --clashes PATH [--protein FILE.pdb]` checks the explained hits' poses against the protein's atoms (excluded volumes).
 `--explain K --refine_out PATH [--refine_restraint X] [--refine_iter N]` moves those poses out of the protein's atoms (restrained rigid-body refinement).
+`--explain K --pose_search PATH [--pose_search_modes M] [--pose_min_fraction F]` poses every explained hit in the conformer and binding mode that fits the pocket.
 `--panel MODEL ... --panel_out PATH` scores the best hits against other pockets; `--save_top K PATH` keeps them as a packed library.
 `--actives FILE --enrichment_out PATH` validates the model retrospectively: the library's ligands named in FILE are the actives, the rest decoys.
 `--similar_to NAME ... --similar_out PATH` lists the library's ligands most similar to the named ones by their own pharmacophore fingerprints.
@@ -43,6 +44,9 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--clash_tolerance", type=float, default=0.5, metavar="T", help="with --clashes: overlap of two spheres, in Angstrom, that is not yet a clash")
         cfg.add_argument("--clash_level", choices=("nodes", "atoms"), default="atoms", help="with --clashes: check the hit's pharmacophore nodes, or its heavy atoms (the hit files are read again; needs a library directory)")
         cfg.add_argument("--refine_out", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit: its pose moved out of the protein's atoms by a restrained rigid-body refinement, checked before and after (uses --protein, --clash_tolerance and --clash_level)")
+        cfg.add_argument("--pose_search", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit: the conformer and binding mode, of all its conformers and their M best modes, whose fitted pharmacophore nodes do not clash with the protein (else the one of smallest overlap), with its motion (uses --protein and --clash_tolerance)")
+        cfg.add_argument("--pose_search_modes", type=int, default=4, metavar="M", help="with --pose_search: binding modes searched per conformer (1 to 8)")
+        cfg.add_argument("--pose_min_fraction", type=float, default=0.0, metavar="F", help="with --pose_search: leave out poses whose match scores less than F (0 to 1) of the hit's best")
         cfg.add_argument("--refine_restraint", type=float, default=0.1, metavar="X", help="with --refine_out: the weight of the restraint that holds the pose near its fit (uncalibrated default)")
         cfg.add_argument("--refine_iter", type=int, default=32, metavar="N", help="with --refine_out: at most N trial motions per pose (0 to 64)")
         cfg.add_argument("--hotspots", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per (explained hit, model node it has terms with): the node's share of the hit's best conformer maximum and whether the hit engages it")
@@ -158,8 +162,16 @@ def main(argv=None) -> None:
         parser.error("--clashes needs --explain K")
     if args.refine_out and args.explain <= 0:
         parser.error("--refine_out needs --explain K")
-    if not (args.clashes or args.refine_out) and args.protein:
-        parser.error("--protein needs --clashes PATH or --refine_out PATH")
+    if args.pose_search and args.explain <= 0:
+        parser.error("--pose_search needs --explain K")
+    if not (args.clashes or args.refine_out or args.pose_search) and args.protein:
+        parser.error("--protein needs --clashes PATH, --refine_out PATH or --pose_search PATH")
+    if args.pose_search and not 1 <= args.pose_search_modes <= 8:
+        parser.error("--pose_search_modes takes 1 to 8")
+    if args.pose_search and not 0.0 <= args.pose_min_fraction <= 1.0:
+        parser.error("--pose_min_fraction takes a number from 0 to 1")
+    if args.pose_search and not np.isfinite(args.clash_tolerance):
+        parser.error("--clash_tolerance takes a number")
     if (args.clashes or args.refine_out) and args.clash_level == "atoms" and Path(args.library_dir).is_file():
         parser.error("--clash_level atoms reads the hit files again: a packed library has none (use --clash_level nodes)")
     if (args.clashes or args.refine_out) and not np.isfinite(args.clash_tolerance):
@@ -234,13 +246,13 @@ def main(argv=None) -> None:
         Halogen=args.halogen,
         Hydrophobic=args.hydrophobic,
     )
-    if args.clashes or args.refine_out:  # (before the screen: a model without a protein should not cost a pass)
+    if args.clashes or args.refine_out or args.pose_search:  # (before the screen: a model without a protein should not cost a pass)
         from .pocket import PocketAtoms
 
         try:
             pocket = PocketAtoms.from_pdb(Path(args.protein), centers=model.node_centers) if args.protein else model.pocket_atoms()
         except (OSError, ValueError) as e:
-            parser.error(f"{'--clashes' if args.clashes else '--refine_out'}: {e}" + ("" if args.protein else " (give it with --protein FILE.pdb)"))
+            parser.error(f"{'--clashes' if args.clashes else '--refine_out' if args.refine_out else '--pose_search'}: {e}" + ("" if args.protein else " (give it with --protein FILE.pdb)"))
     names, lib = load_library(Path(args.library_dir), args.cpus, on_device=True)
     if args.actives:  # (before the screen: a name that matches nothing should not cost a pass)
         from .validation import match_actives
@@ -276,6 +288,9 @@ def main(argv=None) -> None:
         if args.refine_out:
             write_refine_csv(Path(args.refine_out), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_level, args.clash_tolerance,
                              args.refine_restraint, args.refine_iter)
+        if args.pose_search:
+            write_pose_search_csv(Path(args.pose_search), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_tolerance, args.pose_search_modes,
+                                  args.pose_min_fraction)
         if args.hotspots:
             write_hotspots_csv(Path(args.hotspots), names, scores, status, model, lib, weight, args.explain)
         if args.modes is not None:
@@ -494,6 +509,32 @@ def write_poses_csv(out: Path, names: list[str], scores: np.ndarray, status: np.
             nums = [al.rmsd[r], al.rmsd_nodes[r]], [*al.rotation[r].reshape(-1), *al.translation[r]]
             w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{','.join(repr(float(v)) for v in nums[0])},{int(al.n_nodes[r])},"
                     f"{','.join(repr(float(v)) for v in nums[1])}\n")
+
+
+POSE_SEARCH_HEADER = ("rank,path,conformer,mode,passes,candidates,passing,mode_score,fraction_of_best,clashing,overlap,clearance,rmsd,rmsd_nodes,fitted_nodes,"
+                      + ",".join(f"r{i}{j}" for i in range(3) for j in range(3)) + ",tx,ty,tz")
+
+
+def write_pose_search_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, pocket, tolerance: float, modes: int,
+                          min_fraction: float) -> None:
+    """One row per hit of the k best, in the order of the poses CSV: the hit posed where `engine.pose_search` puts it - of all its conformers
+    under their `modes` best binding modes the best-scoring one whose fitted pharmacophore nodes do not clash with the protein, else the
+    one of smallest overlap. The conformer and mode (-1 and -1 for a hit without any pose), whether it passes, how many candidates there
+    were and how many passed, the mode's leaf total and its share of the hit's best, the clash check and the fit of the chosen pose, and
+    the motion as the poses CSV has it. Every number is the `repr` of the float64 the GPU returned."""
+    from .engine import pose_search
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    ps = pose_search(model, lib, pocket, order, modes=modes, weights=weights, min_fraction=min_fraction, tolerance=tolerance)
+    al, rep = ps.alignment(), ps.report()
+    with open(out, "w") as w:
+        w.write(POSE_SEARCH_HEADER + "\n")
+        for r in range(len(ps)):
+            nums = [ps.value[r], ps.fraction[r]], [rep.overlap[r], rep.clearance[r], al.rmsd[r], al.rmsd_nodes[r]], [*al.rotation[r].reshape(-1), *al.translation[r]]
+            w.write(f"{r + 1},{names[order[r]]},{int(ps.conformer[r])},{int(ps.mode[r])},{int(ps.passes[r])},{int(ps.n_candidates[r])},{int(ps.n_passing[r])},"
+                    f"{','.join(repr(float(v)) for v in nums[0])},{int(rep.n_clashing[r])},{','.join(repr(float(v)) for v in nums[1])},{int(al.n_nodes[r])},"
+                    f"{','.join(repr(float(v)) for v in nums[2])}\n")
 
 
 def write_clashes_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, pocket, level: str, tolerance: float) -> None:
