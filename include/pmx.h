@@ -771,6 +771,71 @@ int pmx_pose_search(const pmx_model *model, const pmx_library *lib, const float 
                     int32_t *row_status_dev /* [2][n] */, void *work_dev, uint64_t work_bytes, void *stream);
 
 /*
+ * Pose fit (pmx_pose_fit.hip): do the ligand's pharmacophore nodes sit on the pocket's hotspots once a pose exists? pmx_align reports a
+ * residual over the pairs it was told to fit, pmx_pose_refine moves the ligand and rescores nothing, and the reference's score reads
+ * internal distances only - one number for every rigid placement. This call scores the placement: the Gaussian overlap of the posed ligand
+ * nodes with the model nodes in the pocket's frame, with the model node's radius as its positional sigma (the reference's own reading of
+ * it: an edge's distance_std is sqrt(r1^2 + r2^2), utils/density_map.py:277) and the reference's conventions for a term - weight *
+ * exp(-z^2 / 2), passing iff |z| < 2, the majority rule per node (match_utils.py:51-69). The reference has no counterpart; the
+ * specification is this comment, and tests/pose_fit_ref.py restates it in NumPy.
+ *
+ * Row i: library ligand ligands_dev[i] at conformer conformer_dev[i] under R = rot_dev[i] (row-major), t = trans_dev[i]. The points are
+ * the record's n_i nodes in record order, exactly as pmx_pose_clash takes them in node mode.
+ * Pairs (u, m) of a ligand node u and a model node m, one of two modes per call:
+ *   key mode    key_dev given: the pairs of pmx_align for (ligand, conformer, key_dev[i]) - for every matched level, every node u of its
+ *               cluster and every model node m of the matched cluster whose type is in u's type mask - from the same row front end
+ *   free mode   key_dev NULL: every node u of the record with every model node m whose type is in u's type mask: what the pose touches,
+ *               whatever match produced it - and poses that came from elsewhere
+ *   In both modes a pair is left out when w = (double)weights[node_type[m]] <= 0, and when s_m = node_sigma_dev[m] is not a finite number > 0.
+ * Arithmetic, float64 with every operation rounded (no fused multiply-add), x widened from the record's float32:
+ *   posed point  p_u by pmx_pose_clash's formula
+ *   pair         e = p_u - y_m, y_m = node_center_dev[m]; d2 = (e_0 e_0 + e_1 e_1) + e_2 e_2; v = s_m s_m; z2 = d2 / v;
+ *                the pair passes iff d2 < 4.0 v; g = w exp(-0.5 z2)
+ * Per node u with n_u > 0 pairs, its model nodes in ascending m:
+ *   node_fit[u]     (the sum of g, in ascending m) / (double)n_u - the reference's mean over a node's matches
+ *   W_u             (the sum of w, in ascending m) / (double)n_u - what node_fit[u] is with every pair at z = 0
+ *   node_target[u]  the m of the smallest z2, the lowest m among equals; node_z2[u] that z2; node_best[u] the g of that pair
+ *   in place        iff 2 pass_u >= n_u, pass_u the node's passing pairs
+ *   A node without a pair, and the lanes beyond the record, have -1 in all four.
+ * Per model node m:
+ *   hotspot_z2[m]    the smallest z2 over the pairs (u, m): +inf for a node in no pair and for m >= n_nodes
+ *   hotspot_node[m]  the lowest u that attains it; -1 without a pair
+ *   occupied_fp      bit m % 64 of word m / 64 is set iff some pair (u, m) passes - the format pmx_fingerprint_tanimoto and
+ *                    pmx_fingerprint_leaders take
+ * Per row:
+ *   summary[0]  fit = sum_u node_fit[u]          summary[1]  ideal = sum_u W_u (fit / ideal is 1 with every node on all its hotspots)
+ *   summary[2]  best_fit = sum_u node_best[u]    summary[3]  best_ideal = sum_u w of u's best pair
+ *               each sum has lane u's value at lane u and 0 for a node without a pair, and is added up by the fixed butterfly of 64 lanes
+ *               (at step k = 1, 2, 4, .. 32 lanes i and i ^ k both form v_i + v_(i ^ k))
+ *   count       {nodes with a pair, pairs, nodes in place, passing pairs}
+ * Outputs, per row:
+ *   summary_dev  double [n][4]     count_dev  int32 [n][4]
+ *   node_fit_dev, node_best_dev, node_z2_dev  double [n][PMX_MAX_LIGAND_NODES]     node_target_dev  int32 [n][PMX_MAX_LIGAND_NODES]
+ *   hotspot_z2_dev  double [n][PMX_MAX_MODEL_NODES]     hotspot_node_dev  int32 [n][PMX_MAX_MODEL_NODES]
+ *   occupied_fp_dev  uint64 [n][PMX_FINGERPRINT_WORDS]
+ *   status_dev   int32 [n]  PMX_LIGAND_OK; PMX_LIGAND_UNSUPPORTED and PMX_LIGAND_KEY_INVALID as pmx_pose_clash gives them in node mode (an
+ *                index outside the library, a record pmx_score reports unsupported; a conformer that is none of the ligand's, a motion value
+ *                that is not finite); in key mode also as pmx_align gives them (a level of too many candidates; a match that is no
+ *                candidate of its level)
+ * A row that is not OK has NaN in summary and in the three per-node doubles, -1 in node_target and hotspot_node, NaN in hotspot_z2, counts
+ * of 0 and an empty set. A valid row without pairs has zeros in summary and count. The number is no docking score: it knows no direction,
+ * no clash and no atom, and it is not the reference's score.
+ * n <= PMX_EXPLAIN_MAX (otherwise PMX_ERR_INVALID); n = 0 succeeds and writes nothing. With n > 0 only key_dev may be NULL. Model and
+ * library are on one device, and the pointers are memory of it. Stream-ordered (enqueued, no synchronisation), no allocation, no work
+ * buffer, no atomic: the same bits on every run, and for a row wherever it stands in a call. One wavefront per row: a lane per ligand
+ * node, the model nodes walked in ascending order by all lanes together, so a lane's sums run in the specified order; the minimum per
+ * model node is a cross-lane minimum of (z2, u) under a total order.
+ */
+int pmx_pose_fit(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES],
+                 const double *node_center_dev /* [n_nodes][3] */, const double *node_sigma_dev /* [n_nodes] */,
+                 const uint64_t *ligands_dev, const int32_t *conformer_dev, const uint8_t *key_dev /* [n][PMX_MAX_LEVELS] or NULL */,
+                 const double *rot_dev /* [n][9] */, const double *trans_dev /* [n][3] */, uint32_t n,
+                 double *summary_dev /* [n][4] */, int32_t *count_dev /* [n][4] */,
+                 double *node_fit_dev /* [n][64] */, double *node_best_dev /* [n][64] */, double *node_z2_dev /* [n][64] */, int32_t *node_target_dev /* [n][64] */,
+                 double *hotspot_z2_dev /* [n][256] */, int32_t *hotspot_node_dev /* [n][256] */,
+                 uint64_t *occupied_fp_dev /* [n][PMX_FINGERPRINT_WORDS] */, int32_t *status_dev, void *stream);
+
+/*
  * Retrospective validation (pmx_enrich.hip): does a model, under given type weights, rank known binders above decoys? Per column of scores
  * over one labelled list, and per bootstrap resample of the list, the integers and sums from which the host derives AUROC, enrichment
  * factors and BEDROC. The specification is this comment (the reference has no counterpart); tests/enrichment_ref.py restates it in NumPy.

@@ -994,6 +994,29 @@ extern "C" int pmx_explain_modes(const pmx_model *model, const pmx_library *lib,
 // pmx_attribute, pmx_align and pmx_hotspots: one kernel over the call's rows; no tables, no slices, no arena. Of the workspace of (device, stream) it
 // takes the CU count and four bytes for its row cursor, cleared in stream order in front of the launch. `what`: the call's name in a
 // message; null_out: one of the caller's own device pointers is null; launch(blocks, p, cursor) starts the caller's kernel.
+// What a row kernel reads of a model, a library and the weights: the parameter block with those filled in and nothing else.
+static ScreenParams row_params(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES]) {
+    ScreenParams p{};
+    p.M = model->dm;
+    p.lib = lib->dl;
+    p.sidtab = model->sidtab;
+    p.sub_off = model->sub_off;
+    p.sub_nodes = model->sub_nodes;
+    p.W = to_weights(weights);
+    return p;
+}
+
+// pmx_device.h: the same block for a unit that launches a row kernel of its own (pmx_pose_fit.hip); struct pmx_model stays in this unit.
+int pmx_row_params(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], void *params_out, size_t bytes, int *device_out) {
+    if (!model || !lib || !weights) return pmx_fail(PMX_ERR_INVALID, "null argument");
+    if (bytes != sizeof(ScreenParams)) return pmx_fail(PMX_ERR_INVALID, "a row kernel's parameter block does not match this build's");
+    if (model->device != lib->device) return pmx_fail(PMX_ERR_INVALID, "model and library live on different devices");
+    const ScreenParams p = row_params(model, lib, weights);
+    std::memcpy(params_out, &p, sizeof p);
+    *device_out = lib->device;
+    return PMX_OK;
+}
+
 template <class Launch>
 static int row_call(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], uint32_t n, const char *what, bool null_out,
                     pmx_rows::Kind kind, hipStream_t stream, Launch launch) {
@@ -1009,13 +1032,7 @@ static int row_call(const pmx_model *model, const pmx_library *lib, const float 
     if (rc) return rc;
     PMX_HIPCHECK(ws.acur.grow(256, stream));
     PMX_HIPCHECK(hipMemsetAsync(ws.acur.ptr, 0, 4, stream));
-    ScreenParams p{};
-    p.M = model->dm;
-    p.lib = lib->dl;
-    p.sidtab = model->sidtab;
-    p.sub_off = model->sub_off;
-    p.sub_nodes = model->sub_nodes;
-    p.W = to_weights(weights);
+    const ScreenParams p = row_params(model, lib, weights);
     const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(kLdsPerCu / pmx_rows::lds_bytes(kind), 8));
     const unsigned blocks = std::min<unsigned>(n, (unsigned)ws.num_cu * per_cu);
     if (!launch(blocks, p, ws.acur.as<uint32_t>())) return pmx_fail(PMX_ERR_INVALID, "the %s kernel (pmx_rows.hip) does not match this build's parameter block", what);

@@ -1,5 +1,5 @@
 // pmx_pose.h - what the kernels that pose points against the pocket share (pmx_pocket.hip: pmx_pose_clash; pmx_refine.hip:
-// pmx_pose_refine), so that the two cannot drift: the pocket itself, where a row's points come from and which status it has (the row front
+// pmx_pose_refine; pmx_pose_fit.hip takes the row front end, the posed point and the butterfly), so that they cannot drift: the pocket itself, where a row's points come from and which status it has (the row front
 // end), the posed point as include/pmx.h gives it, the fixed butterfly, and the host's checks of the arguments the two calls have in common.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -18,8 +18,8 @@ from .constants import weights_vector
 from .library import PackedLibrary, as_packed_library
 from .validation import ENRICH_TILE, FLOAT64_REFUSED, MAX_BOOTSTRAP, MAX_COLUMNS, POISSON1_CDF64, Enrichment, cutoffs_ppm  # noqa: F401  (the table and the tile of include/pmx.h)
 
-__all__ = ["Alignment", "Attribution", "ClashReport", "DeviceLibrary", "FittingHits", "Enrichment", "Explanation", "LigandFingerprints", "PanelResult", "ScreeningResult", "SimilarityResult", "align", "attribute", "clashes",
-           "enrichment", "explain", "score_one", "screen", "screen_multi", "similar", "sweep", "topk", "device_model", "last_score_stats"]
+__all__ = ["Alignment", "Attribution", "ClashReport", "DeviceLibrary", "FittingHits", "Enrichment", "Explanation", "LigandFingerprints", "PanelResult", "PoseFit", "ScreeningResult", "SimilarityResult", "align", "attribute", "clashes",
+           "enrichment", "explain", "score_one", "screen", "screen_multi", "similar", "sweep", "topk", "device_model", "last_score_stats", "pose_fit"]
 
 
 def _torch():
@@ -61,6 +61,16 @@ class _ModelHandle:
         _ffi.check(lib.pmx_model_create(ctypes.byref(desc), device, ctypes.byref(handle)))
         self.handle = handle
         self._node_centers = None
+        self._node_sigmas = None
+
+    def node_sigmas(self, model):
+        """The model nodes' `radius` as a float64 [Nm] tensor on the handle's device (`pmx_pose_fit`'s sigmas): uploaded on first use, kept."""
+        if self._node_sigmas is None:
+            torch = _torch()
+            host = np.zeros(max(model.num_nodes, 1), dtype=np.float64)  # (never an empty buffer)
+            host[: model.num_nodes] = model.node_radii
+            self._node_sigmas = torch.from_numpy(host).to(torch.device("cuda", self.device))
+        return self._node_sigmas
 
     def node_centers(self, model):
         """The model nodes' `center` as a float64 [Nm, 3] tensor on the handle's device (`pmx_align`'s targets): uploaded on first use, kept."""
@@ -473,7 +483,7 @@ class ScreeningResult:
                            pool=idx.astype(np.uint64), profile=None)
 
     def fitting(self, k: int, pool: int | None = None, max_clashing: int = 0, pocket=None, atoms=None, model=None, library=None,
-                weights: dict[str, float] | None = None, refine: bool = False, search: int = 0, **kw) -> "FittingHits":
+                weights: dict[str, float] | None = None, refine: bool = False, search: int = 0, fit: bool = False, **kw) -> "FittingHits":
         """The k first hits of this screen whose pose fits the pocket: the best `pool` hits (default min(len, max(8 k, 1024), 65536)) are
         explained, posed at their best conformer (`Explanation.poses`) and checked against the protein's atoms (`Alignment.clashes`); a hit
         passes with status 0 and at most `max_clashing` clashing points. In rank order; a hit that was not scored, or whose pose is not OK,
@@ -490,7 +500,9 @@ class ScreeningResult:
         best binding modes puts it: the best-scoring pose whose nodes pass, else the one of smallest overlap - which is then what `refine`
         starts from. `min_fraction` and `min_fitted` go to the search (a pose worth less than `min_fraction` of the hit's best is not
         considered). `poses` has a row for every hit that was scored; one without any pose has conformer -1 and never passes. `atoms`
-        verifies the chosen poses exactly as without the search."""
+        verifies the chosen poses exactly as without the search.
+        With `fit`, `FittingHits.fit` is the `PoseFit` of every posed hit (`Alignment.pose_fit`, free mode) at the motion finally used -
+        the refined one where the refinement was used; nothing else changes."""
         if k <= 0:
             raise ValueError("k must be positive")
         search = int(search)
@@ -534,9 +546,10 @@ class ScreeningResult:
                 al = dataclasses.replace(al, rotation=np.where(use[:, None, None], refined.rotation, al.rotation),
                                          translation=np.where(use[:, None], refined.translation, al.translation))
                 rep = al.clashes(pocket, dlib, atoms=mols, **kw)  # (a row that was not refined has the bits it had)
+            pf = al.pose_fit(model, dlib, weights=weights) if fit else None
         passing = np.flatnonzero(rep.ok(max_clashing) & (al.status == 0))[:k]
         return FittingHits(indices=al.indices[passing].astype(np.uint64), scores=ex.scores[al.rows[passing]], ranks=al.rows[passing].astype(np.int64), rows=passing,
-                           pool=ex.indices, poses=al, report=rep, refined=refined)
+                           pool=ex.indices, poses=al, report=rep, refined=refined, fit=pf)
 
     def similar_to(self, rank: int, k: int = 100, library=None) -> "SimilarityResult":
         """The library's neighbours of this screen's hit at `rank` (0 is the best hit): `similar` with that ligand as the one query,
@@ -944,6 +957,13 @@ class Explanation:
         out.rows = np.asarray(rows, dtype=np.int64)
         return out
 
+    def pose_fit(self, model, library, conformer: int | None = None, weights: dict[str, float] | None = None, **kw) -> "PoseFit":
+        """`pose_fit` of every row with status 0, posed as `poses` poses it and scored in key mode under the same key: how well the
+        explained match, once fitted, sits on the hotspots it was fitted to. Rows as `poses` has them."""
+        rows, conf, keys = self._own_rows(conformer)
+        al = align(model, library, self.indices[rows], conf, keys, weights=weights)
+        return al.pose_fit(model, library, keys=keys, weights=weights, **kw)
+
     def hotspots(self, model, library, conformer: int | None = None, weights: dict[str, float] | None = None) -> "HotspotProfile":
         """`hotspots` of every row with status 0, at its best conformer (or `conformer`) under that conformer's own key: which model nodes
         carry the explained maximum, and the row's interaction fingerprint. `rows` of the result says which row of this explanation each
@@ -1247,6 +1267,10 @@ class PoseSearch:
     def report(self) -> "ClashReport":
         """The `ClashReport` of the chosen rows' pharmacophore nodes, at the search's own radius, tolerance and contact distance."""
         return self.clash
+
+    def pose_fit(self, model, library, **kw) -> "PoseFit":
+        """`pose_fit` of the chosen rows in key mode under the chosen keys: row i is hit i, a hit without a choice a row with status 4 (or 1)."""
+        return self.poses.pose_fit(model, library, keys=self.key, **kw)
 
 
 def _search_chunks(conf: np.ndarray, modes: int):
@@ -1617,6 +1641,12 @@ class Alignment:
             out.indices, out.conformers = self.indices.copy(), np.asarray(self.conformers, dtype=np.int64).copy()
         return out
 
+    def pose_fit(self, model, library, keys=None, **kw) -> "PoseFit":
+        """How well these poses sit on the model's hotspots (`pose_fit`): row i of the result is row i of the alignment, and a row that
+        is not OK passes through with status 4. `keys`: the rows' keys, for the pairs the fit was made on (key mode); None for every pair
+        of matching type (free mode). Further arguments (`weights`, `centers`, `sigmas`) as `pose_fit` takes them."""
+        return pose_fit(model, library, self.indices, self.conformers, self.rotation, self.translation, keys=keys, **kw)
+
 
 def align(model, library, indices, conformers, keys, weights: dict[str, float] | None = None, device=None) -> Alignment:
     """The rigid fit (`pmx_align`, csrc/pmx_rows.hip) of library ligand `indices[i]`'s conformer `conformers[i]` under the match `keys[i]`, rows as
@@ -1663,6 +1693,7 @@ class FittingHits:
     poses: "Alignment"
     report: "ClashReport"
     refined: "RefinedPoses | None" = None  # `fitting(refine=True)`: the refinement of every posed hit; its motion is used where the fit failed
+    fit: "PoseFit | None" = None  # `fitting(fit=True)`: the `PoseFit` (free mode) of every posed hit at the motion finally used
 
     def __len__(self) -> int:
         return len(self.indices)
@@ -1905,6 +1936,13 @@ class RefinedPoses:
         `library`, the molecules' heavy atoms with `atoms`. A row that is not OK passes through with status 4."""
         return _check_poses(self, "RefinedPoses.clashes", pocket_or_model, library, atoms, kw)
 
+    def pose_fit(self, model, library, keys=None, **kw) -> "PoseFit":
+        """How well the refined poses sit on the model's hotspots, as `Alignment.pose_fit` says it of the fitted ones (node mode rows
+        only: the rows' ligands and conformers). A row the refinement left untouched has the bits it had before."""
+        if self.indices is None:
+            raise ValueError("RefinedPoses.pose_fit: these rows are points of the caller's, not ligands of a library")
+        return pose_fit(model, library, self.indices, self.conformers, self.rotation, self.translation, keys=keys, **kw)
+
 
 def _heavy_atoms(atoms, conformers):
     """Per row the heavy atoms of `atoms[i]` (a `LigandFeatures` / `Ligand`) at conformer `conformers[i]`, float32 [m_i, 3], and their
@@ -2014,6 +2052,138 @@ def refine(pocket, library=None, indices=None, conformers=None, rotation=None, t
                         iterations=cn[:, 0].copy(), accepted=cn[:, 1].copy(), stop=cn[:, 2].copy(), n_pairs=cn[:, 3].copy(),
                         status=status.cpu().numpy()[:n].astype(np.int32), indices=rows.idx.copy() if node_mode else None,
                         conformers=rows.conf.astype(np.int64) if node_mode else None)
+
+
+@dataclass
+class PoseFit:
+    """What `pose_fit` returns: one row per posed ligand - the Gaussian overlap of its posed pharmacophore nodes with the model's hotspots,
+    each hotspot's radius its positional sigma (definitions: `pmx_pose_fit` in include/pmx.h). Floats are float64. Not a docking score: no
+    direction, no atoms, and not the reference's score.
+
+    fit[i], ideal[i]        the sum over the nodes of the mean of w exp(-z^2 / 2) over a node's pairs, and the same with every z = 0
+    fraction[i]             fit / ideal: 1.0 with every node on all its hotspots; 0 where ideal is 0
+    best_fit[i], best_ideal[i], best_fraction[i]   the same over each node's nearest hotspot (smallest z) alone
+    n_nodes[i], n_pairs[i]  nodes with a pair, and pairs    n_in_place[i]  nodes most of whose pairs pass (|z| < 2)    n_passing[i]  passing pairs
+    node_fit[i], node_best[i], node_z2[i], node_target[i]   [n] per node of the record: its mean, its nearest hotspot's term, that z^2 and that
+                            model node; -1 for a node without a pair
+    hotspot_z2[i], hotspot_node[i]   [Nm] per model node: the smallest z^2 of a pair with it (+inf without one) and the ligand node (-1)
+    occupied_fingerprint    uint64 [n, 4]: bit m says some pair with model node m passes
+    status[i]               0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer, a motion that is not finite - a
+                            row of an `Alignment` that was not OK -, a match that is no candidate); such a row has NaN floats, zero counts,
+                            -1 targets and an empty fingerprint"""
+
+    indices: np.ndarray
+    conformers: np.ndarray
+    fit: np.ndarray
+    ideal: np.ndarray
+    fraction: np.ndarray
+    best_fit: np.ndarray
+    best_ideal: np.ndarray
+    best_fraction: np.ndarray
+    n_nodes: np.ndarray
+    n_pairs: np.ndarray
+    n_in_place: np.ndarray
+    n_passing: np.ndarray
+    node_fit: list
+    node_best: list
+    node_z2: list
+    node_target: list
+    hotspot_z2: list
+    hotspot_node: list
+    occupied_fingerprint: np.ndarray
+    status: np.ndarray
+    device: "int | None" = None  # where `similarity` and `leaders` run
+
+    def __len__(self) -> int:
+        return len(self.status)
+
+    def occupied(self, i: int) -> np.ndarray:
+        """The model nodes row i occupies (the set bits of its fingerprint), ascending."""
+        bits = np.unpackbits(np.ascontiguousarray(self.occupied_fingerprint[i]).view(np.uint8), bitorder="little")
+        return np.flatnonzero(bits).astype(np.int64)
+
+    def coverage(self, i: int, model, weights: dict[str, float] | None = None) -> float:
+        """The occupied model nodes over the model nodes of positive weight (0.0 where no node has weight)."""
+        w = np.asarray(weights_vector(weights), dtype=np.float32)[np.asarray(model.flat.node_type, dtype=np.int64)[: model.num_nodes]]
+        total = int(np.count_nonzero(w > 0))
+        return len(self.occupied(i)) / total if total else 0.0
+
+    def similarity(self, other: "PoseFit | None" = None) -> np.ndarray:
+        """Tanimoto similarity of the occupied-hotspot fingerprints, on the GPU (`fingerprint_similarity`)."""
+        return fingerprint_similarity(self.occupied_fingerprint, None if other is None else other.occupied_fingerprint, device=self.device)
+
+    def leaders(self, threshold: float = 0.7, max_leaders: int = 2048):
+        """Sphere exclusion over the rows in their order by occupied hotspots (`fingerprint_leaders`): (leaders, leader_of)."""
+        return fingerprint_leaders(self.occupied_fingerprint, threshold=threshold, max_leaders=max_leaders, device=self.device)
+
+
+def _ratio(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """a / b in float64, 0 where b is 0 (NaN stays NaN)."""
+    out = np.zeros_like(a)
+    np.divide(a, b, out=out, where=b != 0)
+    return out
+
+
+def pose_fit(model, library, indices, conformers, rotation, translation, keys=None, weights: dict[str, float] | None = None, centers=None, sigmas=None,
+             device=None) -> PoseFit:
+    """Posed library ligands against the model's hotspots (`pmx_pose_fit`, csrc/pmx_pose_fit.hip): row i is the pharmacophore nodes of
+    library ligand indices[i] at conformer conformers[i], moved by `rotation[i]` [3, 3] and `translation[i]` [3] - what `Alignment` and
+    `RefinedPoses` hold.
+      keys      None (free mode): a node pairs with every model node of a type it has. Otherwise the rows' keys as `align` takes them (key
+                mode): the pairs are `align`'s for that key
+      centers, sigmas   float64 [Nm, 3] / [Nm] in place of the model nodes' `center` and `radius`: "what if this hotspot were tighter". A
+                sigma that is not a finite number > 0 takes its model node out
+    At most 65536 rows. Runs on torch's current stream of the device and waits for it."""
+    torch = _torch()
+    lib = _ffi.load()
+    rows = _PoseRows("pose_fit", library, indices, conformers, rotation, translation, None, None)
+    n = rows.n
+    nm = int(model.num_nodes)
+    kb = None
+    if keys is not None:
+        _, _, kb = _listed_rows(rows.idx, rows.conf, keys, "pose_fit")
+    over = []
+    for name, given, shape in (("centers", centers, (nm, 3)), ("sigmas", sigmas, (nm,))):
+        if given is None:
+            over.append(None)
+            continue
+        arr = np.ascontiguousarray(np.asarray(given, dtype=np.float64))
+        if arr.shape != shape:
+            raise ValueError(f"pose_fit: {name} of shape {arr.shape}, the model has {nm} nodes ({shape})")
+        over.append(np.concatenate([arr.reshape(-1), np.zeros(3)]))  # (never an empty buffer)
+    m = max(n, 1)
+    with _resident(library, device) as dlib:
+        mh = device_model(model, dlib.device)
+        dev = dlib.device
+        tdev = torch.device("cuda", dev)
+        with torch.cuda.device(tdev):
+            keep, src, motion = rows.upload(tdev)
+            t_cen = mh.node_centers(model) if over[0] is None else torch.from_numpy(over[0]).to(tdev)
+            t_sig = mh.node_sigmas(model) if over[1] is None else torch.from_numpy(over[1]).to(tdev)
+            t_key = None if kb is None else torch.from_numpy(kb).to(tdev)
+            f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=tdev)  # noqa: E731
+            i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=tdev)  # noqa: E731
+            summary, count = f64(m, 4), i32(m, 4)
+            nfit, nbest, nz2, ntgt = f64(m, _MAX_NODES), f64(m, _MAX_NODES), f64(m, _MAX_NODES), i32(m, _MAX_NODES)
+            hz2, hnode = f64(m, _MAX_MODEL_NODES), i32(m, _MAX_MODEL_NODES)
+            fp = torch.empty((m, _FP_WORDS), dtype=torch.int64, device=tdev)
+            status = i32(m)
+            stream = torch.cuda.current_stream(tdev)
+            _ffi.check(lib.pmx_pose_fit(mh.handle, dlib.handle, _weights_array(weights), t_cen.data_ptr(), t_sig.data_ptr(), src[0], src[1],
+                                        None if t_key is None else t_key.data_ptr(), *motion, n, summary.data_ptr(), count.data_ptr(), nfit.data_ptr(), nbest.data_ptr(),
+                                        nz2.data_ptr(), ntgt.data_ptr(), hz2.data_ptr(), hnode.data_ptr(), fp.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+            stream.synchronize()
+            del keep, t_key
+        st = status.cpu().numpy()[:n].astype(np.int32)
+        nn = np.where(st != 1, _record_counts(dlib, rows.idx, 0), 0) if n else np.zeros(0, np.int64)
+    sm, cn = summary.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
+    cut = lambda t, w, dt=None: [(a[: w[i]].copy() if dt is None else a[: w[i]].astype(dt)) for i, a in enumerate(t.cpu().numpy()[:n])]  # noqa: E731
+    wm = np.full(n, nm, dtype=np.int64)
+    return PoseFit(indices=rows.idx.astype(np.int64), conformers=rows.conf.astype(np.int64), fit=sm[:, 0].copy(), ideal=sm[:, 1].copy(), fraction=_ratio(sm[:, 0], sm[:, 1]),
+                   best_fit=sm[:, 2].copy(), best_ideal=sm[:, 3].copy(), best_fraction=_ratio(sm[:, 2], sm[:, 3]), n_nodes=cn[:, 0].copy(), n_pairs=cn[:, 1].copy(),
+                   n_in_place=cn[:, 2].copy(), n_passing=cn[:, 3].copy(), node_fit=cut(nfit, nn), node_best=cut(nbest, nn), node_z2=cut(nz2, nn),
+                   node_target=cut(ntgt, nn, np.int64), hotspot_z2=cut(hz2, wm), hotspot_node=cut(hnode, wm, np.int64),
+                   occupied_fingerprint=fp.cpu().numpy()[:n].view(np.uint64).copy(), status=st, device=dev)
 
 
 _MAX_MODEL_NODES, _FP_WORDS, _MAX_LEADERS = 256, 4, 2048  # PMX_MAX_MODEL_NODES, PMX_FINGERPRINT_WORDS, PMX_MAX_LEADERS

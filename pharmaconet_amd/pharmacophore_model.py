@@ -249,6 +249,13 @@ class PharmacophoreModel:
         assert self._state is not None, "empty model"
         return np.array([[float(v) for v in node["center"]] for node in self._state["nodes"]], dtype=np.float64).reshape(-1, 3)
 
+    @property
+    def node_radii(self) -> np.ndarray:
+        """float64 [Nm]: `nodes[m].radius`, which the reference reads as the positional sigma of the node (an edge's `distance_std` is
+        sqrt(r1^2 + r2^2)) - what `engine.pose_fit` measures a posed ligand node's distance from `center` in."""
+        assert self._state is not None, "empty model"
+        return np.array([float(node["radius"]) for node in self._state["nodes"]], dtype=np.float64).reshape(-1)
+
     def pocket_atoms(self, **kw):
         """The heavy atoms of the protein this model carries (`pdbblock`) as `pocket.PocketAtoms`, what `engine.clashes` checks posed hits
         against; kept per set of arguments (`within`, `hetero`, `water`), with its device copy. ValueError when the block holds no atom."""
@@ -564,6 +571,39 @@ class PharmacophoreModel:
                     restraint_energy=float(ref.restraint_energy[0]), anchor_rmsd=float(ref.anchor_rmsd[0]), angle=float(ref.angle[0]), shift=float(ref.shift[0]),
                     iterations=int(ref.iterations[0]), accepted=int(ref.accepted[0]), stop=int(ref.stop[0]), n_pairs=int(ref.n_pairs[0]), status=int(ref.status[0]),
                     ok=bool(rep.ok()[0]))
+
+    def scoring_pose_fit(self, ligand, conformer: int | None = None, key=None, refine: bool = False, free: bool = False, weights: dict[str, float] | None = None,
+                         pocket=None, centers=None, sigmas=None, **kw) -> dict:
+        """One ligand fitted into the pocket (`scoring_pose`) and its pose scored in place (`engine.pose_fit`): how well its pharmacophore
+        nodes sit on the hotspots, in key mode under the pose's own key (with `free`, against every hotspot of matching type). Returns
+        `conformer`, `key`, `rotation`, `translation`, `rmsd` of the pose and `fit`, `ideal`, `fraction`, `best_fit`, `best_fraction`,
+        `n_nodes`, `n_pairs`, `n_in_place`, `n_passing`, `node_fit`, `node_z2`, `node_target`, `hotspot_z2`, `hotspot_node`, `occupied`
+        (the model nodes some pair passes at), `coverage` and `status`. With `refine`, the pose is also moved out of the protein's atoms
+        (`engine.refine` on the record's nodes; `pocket` defaults to `pocket_atoms()`, further arguments as `engine.refine`) and `refined`
+        holds the same fields for the refined motion, with `refined_rotation`, `refined_translation` and `stop`: what the refinement cost
+        is `fraction` against `refined["fraction"]`."""
+        from .engine import pose_fit, refine as refine_poses
+        from .library import as_packed_library
+
+        packed = as_packed_library(ligand)
+        pose = self.scoring_pose(ligand, weights=weights, conformer=conformer, key=key)
+        c, keys = pose["conformer"], (None if free else [pose["key"]])
+
+        def one(rotation, translation):
+            pf = pose_fit(self, packed, [0], [c], [rotation], [translation], keys=keys, weights=weights, centers=centers, sigmas=sigmas)
+            return dict(fit=float(pf.fit[0]), ideal=float(pf.ideal[0]), fraction=float(pf.fraction[0]), best_fit=float(pf.best_fit[0]),
+                        best_fraction=float(pf.best_fraction[0]), n_nodes=int(pf.n_nodes[0]), n_pairs=int(pf.n_pairs[0]), n_in_place=int(pf.n_in_place[0]),
+                        n_passing=int(pf.n_passing[0]), node_fit=pf.node_fit[0], node_z2=pf.node_z2[0], node_target=pf.node_target[0], hotspot_z2=pf.hotspot_z2[0],
+                        hotspot_node=pf.hotspot_node[0], occupied=pf.occupied(0), coverage=pf.coverage(0, self, weights), status=int(pf.status[0]))
+
+        out = dict(conformer=c, key=pose["key"], rotation=pose["rotation"], translation=pose["translation"], rmsd=pose["rmsd"], **one(pose["rotation"], pose["translation"]))
+        if refine:
+            ref = refine_poses(self.pocket_atoms() if pocket is None else pocket, library=packed, indices=[0], conformers=[c], rotation=[pose["rotation"]],
+                               translation=[pose["translation"]], **kw)
+            out["refined"] = dict(refined_rotation=ref.rotation[0], refined_translation=ref.translation[0], stop=int(ref.stop[0]), **one(ref.rotation[0], ref.translation[0]))
+        elif kw:
+            raise ValueError(f"{sorted(kw)}: arguments of the refinement, which is off (refine=True)")
+        return out
 
     def explain(self, library, indices, weights: dict[str, float] | None = None, **kwargs):
         """Per-conformer maxima and explaining matches of library ligands `indices` (`engine.explain`)."""

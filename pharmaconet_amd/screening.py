@@ -7,6 +7,7 @@ processes; needs OpenBabel like the reference) or a packed library file (`.pmxli
 Output: `path,score` CSV, best first, ties in library order (`screening.py:70-75`). Scoring runs on the GPU.
 `--explain K --clashes PATH [--protein FILE.pdb]` checks the explained hits' poses against the protein's atoms (excluded volumes).
 `--explain K --refine_out PATH [--refine_restraint X] [--refine_iter N]` moves those poses out of the protein's atoms (restrained rigid-body refinement).
+`--explain K --pose_fit PATH [--pose_fit_mode key|free]` scores those poses in place: the overlap of the posed pharmacophore nodes with the model's hotspots (with --refine_out also at the refined motion).
 `--explain K --pose_search PATH [--pose_search_modes M] [--pose_min_fraction F]` poses every explained hit in the conformer and binding mode that fits the pocket.
 `--panel MODEL ... --panel_out PATH` scores the best hits against other pockets; `--save_top K PATH` keeps them as a packed library.
 `--actives FILE --enrichment_out PATH` validates the model retrospectively: the library's ligands named in FILE are the actives, the rest decoys.
@@ -47,6 +48,8 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--pose_search", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit: the conformer and binding mode, of all its conformers and their M best modes, whose fitted pharmacophore nodes do not clash with the protein (else the one of smallest overlap), with its motion (uses --protein and --clash_tolerance)")
         cfg.add_argument("--pose_search_modes", type=int, default=4, metavar="M", help="with --pose_search: binding modes searched per conformer (1 to 8)")
         cfg.add_argument("--pose_min_fraction", type=float, default=0.0, metavar="F", help="with --pose_search: leave out poses whose match scores less than F (0 to 1) of the hit's best")
+        cfg.add_argument("--pose_fit", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit: how well the posed pharmacophore nodes sit on the model's hotspots (Gaussian overlap, the hotspot's radius as sigma); with --refine_out a second row per hit for the refined pose")
+        cfg.add_argument("--pose_fit_mode", choices=("key", "free"), default="key", help="with --pose_fit: score the pairs of the hit's explaining match (key), or every hotspot of a type the node has (free)")
         cfg.add_argument("--refine_restraint", type=float, default=0.1, metavar="X", help="with --refine_out: the weight of the restraint that holds the pose near its fit (uncalibrated default)")
         cfg.add_argument("--refine_iter", type=int, default=32, metavar="N", help="with --refine_out: at most N trial motions per pose (0 to 64)")
         cfg.add_argument("--hotspots", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per (explained hit, model node it has terms with): the node's share of the hit's best conformer maximum and whether the hit engages it")
@@ -164,6 +167,8 @@ def main(argv=None) -> None:
         parser.error("--refine_out needs --explain K")
     if args.pose_search and args.explain <= 0:
         parser.error("--pose_search needs --explain K")
+    if args.pose_fit and args.explain <= 0:
+        parser.error("--pose_fit needs --explain K")
     if not (args.clashes or args.refine_out or args.pose_search) and args.protein:
         parser.error("--protein needs --clashes PATH, --refine_out PATH or --pose_search PATH")
     if args.pose_search and not 1 <= args.pose_search_modes <= 8:
@@ -288,6 +293,9 @@ def main(argv=None) -> None:
         if args.refine_out:
             write_refine_csv(Path(args.refine_out), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_level, args.clash_tolerance,
                              args.refine_restraint, args.refine_iter)
+        if args.pose_fit:
+            refine = dict(pocket=pocket, level=args.clash_level, tolerance=args.clash_tolerance, restraint=args.refine_restraint, max_iter=args.refine_iter) if args.refine_out else None
+            write_pose_fit_csv(Path(args.pose_fit), names, scores, status, model, lib, weight, args.explain, args.pose_fit_mode, refine)
         if args.pose_search:
             write_pose_search_csv(Path(args.pose_search), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_tolerance, args.pose_search_modes,
                                   args.pose_min_fraction)
@@ -592,6 +600,41 @@ def write_refine_csv(out: Path, names: list[str], scores: np.ndarray, status: np
             w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{level},{int(before.n_pairs[r])},{float(before.overlap[r])!r},{int(after.n_pairs[r])},"
                     f"{float(after.overlap[r])!r},{float(after.clearance[r])!r},{int(after.n_clashing[r])},{float(ref.anchor_rmsd[r])!r},"
                     f"{float(np.degrees(ref.angle[r]))!r},{float(ref.shift[r])!r},{int(ref.iterations[r])},{int(ref.stop[r])},{motion}\n")
+
+
+POSE_FIT_HEADER = "rank,path,conformer,stage,fitted_nodes,pairs,in_place,passing,fit,ideal,fraction,best_fit,best_fraction,occupied_nodes"
+
+
+def write_pose_fit_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, mode: str, refine: dict | None) -> None:
+    """One row per hit of the k best, in the order of the poses CSV, with stage `fit`: the pose of the hit's best conformer (`engine.align`)
+    scored in place (`engine.pose_fit`) - in mode `key` over the pairs of the explaining match, in mode `free` over every hotspot of a type
+    the node has. Nodes with a pair, pairs, nodes in place, passing pairs, the fit, its ideal and their ratio, the same over each node's
+    nearest hotspot, and the occupied model nodes joined by `;`. With `refine` (the arguments of the refine CSV) a second row per hit, stage
+    `refined`, for the motion `engine.refine` ends at. Every float is the `repr` of the float64 the GPU returned."""
+    from .engine import explain
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    ex = explain(model, lib, order, weights=weights)
+    _, _, keys = ex._own_rows(None)
+    al = ex.poses(model, lib, weights=weights)
+    keys = keys if mode == "key" else None
+    stages = [("fit", al.pose_fit(model, lib, keys=keys, weights=weights))]
+    if refine is not None:
+        atoms = None
+        if refine["level"] == "atoms":
+            from .ligand import Ligand
+
+            atoms = [Ligand.load_from_file(names[order[int(row)]]) for row in al.rows]
+        ref = al.refine(refine["pocket"], lib, atoms=atoms, tolerance=refine["tolerance"], restraint=refine["restraint"], max_iter=refine["max_iter"])
+        stages.append(("refined", ref.pose_fit(model, lib, keys=keys, weights=weights)))
+    with open(out, "w") as w:
+        w.write(POSE_FIT_HEADER + "\n")
+        for r, row in enumerate(al.rows):
+            for stage, pf in stages:
+                nums = ",".join(repr(float(v)) for v in (pf.fit[r], pf.ideal[r], pf.fraction[r], pf.best_fit[r], pf.best_fraction[r]))
+                w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{stage},{int(pf.n_nodes[r])},{int(pf.n_pairs[r])},{int(pf.n_in_place[r])},"
+                        f"{int(pf.n_passing[r])},{nums},{';'.join(str(int(m)) for m in pf.occupied(r))}\n")
 
 
 if __name__ == "__main__":
