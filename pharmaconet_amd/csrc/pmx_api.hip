@@ -19,6 +19,7 @@
 
 #include "pmx.h"
 #include "pmx_screen.hip"
+#include "pmx_handles.h"
 #include "pmx_debug.h"
 #include "pmx_explain.h"
 #include "pmx_rows.h"
@@ -48,31 +49,6 @@ extern "C" int pmx_score_stats_get(pmx_score_stats *out) {
 }
 
 // -------------------------------------------------------------------------------------- model
-struct FnEntry { // tabulated pair functions for one set of type weights
-    Weights W;
-    FnCell *cells = nullptr;
-    hipEvent_t ready = nullptr; // recorded after fn_build_kernel on the stream that built it
-    uint64_t stamp = 0;
-};
-
-// The tables of pmx_model_tables.cpp in one device allocation; every pointer below and in `dm` points into `blob`.
-struct pmx_model {
-    int device;
-    DevModel dm;
-    void *blob;
-    uint8_t node_type[PMX_MAX_MODEL_NODES]; // host copy
-    // node subsets and tabulated pair functions (pmx_screen_layout.h FnTable, pmx_screen_tables.h fn_build_kernel)
-    uint32_t NS = 0, NF = 0, ncell = 0;
-    float h = 0.f;
-    const uint16_t *sidtab = nullptr;  // [K * 128]
-    const uint32_t *sub_off = nullptr;  // [NS + 1]: the nodes of subset s are sub_nodes[sub_off[s] .. sub_off[s + 1]), ascending
-    const uint8_t *sub_nodes = nullptr;
-    const float2 *win = nullptr;        // [NF * ncell] exact pass windows
-    std::mutex fn_mu;
-    std::vector<FnEntry> fn;
-    uint64_t fn_stamp = 0;
-};
-
 static_assert(sizeof(F2) == sizeof(float2) && offsetof(F2, y) == offsetof(float2, y), "F2 is float2");
 static_assert(sizeof(F4) == sizeof(float4) && offsetof(F4, y) == offsetof(float4, y) && offsetof(F4, z) == offsetof(float4, z) && offsetof(F4, w) == offsetof(float4, w),
               "F4 is float4");
@@ -204,15 +180,6 @@ extern "C" int pmx_model_destroy(pmx_model *m) {
 }
 
 // ------------------------------------------------------------------------------------ library
-struct pmx_library {
-    int device;
-    DevLibrary dl;
-    uint64_t *offsets;
-    uint8_t *data;
-    bool owns; // false: the caller's device buffers, adopted as they are (pmx_library_view.on_device == 2)
-    pmx_library_info info;
-};
-
 extern "C" int pmx_library_upload(const pmx_library_view *v, int device, pmx_library **out) {
     if (!v || !out) return pmx_fail(PMX_ERR_INVALID, "null argument");
     if (!v->offsets) return pmx_fail(PMX_ERR_INVALID, "null offsets");
@@ -296,8 +263,6 @@ extern "C" int pmx_library_buffers(const pmx_library *lib, const uint64_t **offs
     *data_dev = lib->data;
     return PMX_OK;
 }
-
-int pmx_library_device(const pmx_library *lib) { return lib->device; } // for pmx_select.hip (the struct stays in this translation unit)
 
 extern "C" int pmx_library_destroy(pmx_library *lib) {
     if (!lib) return PMX_OK;
@@ -571,6 +536,33 @@ static int plan_pocket(const pmx_model *model, const pmx_library *lib, const Wei
     return PMX_OK;
 }
 
+// The table passes of one chunk, in the one order pmx_score and pmx_explain both run them: every ligand whose tables fit a slice; the
+// others with large slices (fewer wavefronts); what exceeds those from the arena - ligands that find it full (of the tables of over-budget
+// trees, or of each other) are listed in the storage of the overflow list, which is done with; then those, with the arena to themselves
+// (only models and libraries whose largest tables exceed a large slice have such passes), the last pass reporting what still does not
+// fit. launch(mode, blocks) starts the caller's kernel on `p`; grid0 is the slice pass's grid, `grid` every later pass's. after_pass()
+// runs behind every arena pass and says whether to go on (PMX_OK).
+template <class Launch, class AfterPass>
+static int chunk_passes(ScreenParams &p, const PocketPlan &pl, const ScreenWs &ws, uint32_t grid0, uint32_t grid, hipStream_t stream, Launch launch, AfterPass after_pass) {
+    p.slices = ws.slices.as<uint8_t>();
+    p.slice_bytes = pl.slice_bytes;
+    launch(0, grid0);
+    p.slices = ws.big.as<uint8_t>();
+    p.slice_bytes = pl.big_bytes;
+    launch(1, grid);
+    p.retry_out = p.ovf_list;
+    p.retry_slot = 0;
+    launch(2, grid);
+    int rc = after_pass();
+    for (int t = 0; t < pl.arena_retries && !rc; ++t) {
+        prepare_retry(p, p.ctl, p.ovf_list, p.list_cap, t, pl.arena_retries, stream);
+        launch(3, grid);
+        rc = after_pass();
+    }
+    p.retry_in = nullptr;
+    return rc;
+}
+
 template <int G>
 static int score_screen(const pmx_model *const *models, int n_models, const pmx_library *lib, const Weights &W, uint64_t first, uint64_t count,
                         void *scores_dev, bool scores_f64, int32_t *status_dev, hipStream_t stream, ScreenWs &ws) {
@@ -588,7 +580,6 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
     const bool exact = (flags & 8) != 0;
     // any validation switch: the kernels of pmx_screen_debug.hip (libpmx's own read those bits as zero, pmx_screen_layout.h PMX_WFLAGS)
     const bool debug_kernels = (flags & ~PMX_PRODUCT_FLAGS) != 0;
-    bool debug_ok = true;
     const bool tails = pair_tails(models, n_models, W); // (term-by-term tails for widely spread type weights, see pair_tails)
 
     // ---- plan: per pocket, parameters and launch shapes
@@ -647,7 +638,7 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
         p.pabuf = pabuf;
         auto launch = [&](int mode, uint32_t blocks) {
             p.mode = mode;
-            if (debug_kernels) debug_ok &= pmx_debug::launch_ligand(G, exact, tails, blocks, pl.lds, stream, &p, sizeof p);
+            if (debug_kernels) pmx_debug::launch_ligand(G, exact, tails, blocks, pl.lds, stream, p);
             else if (tails) ligand_kernel<G, false, true><<<dim3(blocks), dim3(64), pl.lds, stream>>>(p);
             else ligand_kernel<G, false, false><<<dim3(blocks), dim3(64), pl.lds, stream>>>(p);
         };
@@ -662,7 +653,7 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
                 p.budget = r < task_decay_from ? task_budget : std::max<uint32_t>(task_budget_min, task_budget >> std::min(r - task_decay_from + 1, 16));
                 p.last_round = r + 1 == rounds ? 1u : 0u;
                 round_kernel<<<dim3(1), dim3(64), 0, stream>>>(ctl, p.qcap);
-                if (debug_kernels) debug_ok &= pmx_debug::launch_task(G, task_grid, pl.lds, stream, &p, sizeof p);
+                if (debug_kernels) pmx_debug::launch_task(G, task_grid, pl.lds, stream, p);
                 else task_kernel<G><<<dim3(task_grid), dim3(64), pl.lds, stream>>>(p);
             }
             finalize_kernel<G><<<dim3((super + 255) / 256), dim3(256), 0, stream>>>(p);
@@ -679,37 +670,21 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
             ws.ligands_last = p.hi - p.lo;
             ctl_clear_kernel<<<dim3((sizeof(Ctl) / 4 + 255) / 256), dim3(256), 0, stream>>>(ctl, ws.ctl_used ? 0 : 1);
             ws.ctl_used = true;
-            // every ligand whose tables fit a slice
-            p.slices = ws.slices.as<uint8_t>();
-            p.slice_bytes = pl.slice_bytes;
-            launch(0, lig_grid);
-            // the others with large slices (fewer wavefronts)
-            p.slices = ws.big.as<uint8_t>();
-            p.slice_bytes = pl.big_bytes;
-            launch(1, std::min(pl.big_grid, lig_grid));
-            // and what exceeds those from the arena; ligands that find it full (of the tables of over-budget trees, or of each
-            // other) are listed in the storage of the overflow list, which is done with
-            p.retry_out = lists;
-            p.retry_slot = 0;
-            launch(2, std::min(pl.big_grid, lig_grid));
-            if (g_profiling && last_of_call) {
-                PMX_HIPCHECK(hipEventRecord(ws.ev[2], stream));
-                PMX_HIPCHECK(hipEventRecord(ws.ev[4], stream));
-            }
-            rounds_and_finalize();
-            // Ligands the arena pass had no room for, with the arena to themselves (only models and libraries whose largest tables
-            // exceed a large slice have such passes), the last pass reporting what still does not fit.
-            for (int t = 0; t < pl.arena_retries; ++t) {
-                prepare_retry(p, ctl, lists, super, t, pl.arena_retries, stream);
-                launch(3, std::min(pl.big_grid, lig_grid));
+            bool mark = g_profiling && last_of_call; // the first arena pass of the call's last chunk ends the ligand kernels and starts the rounds
+            const int rc = chunk_passes(p, pl, ws, lig_grid, std::min(pl.big_grid, lig_grid), stream, launch, [&]() -> int {
+                if (mark) {
+                    PMX_HIPCHECK(hipEventRecord(ws.ev[2], stream));
+                    PMX_HIPCHECK(hipEventRecord(ws.ev[4], stream));
+                    mark = false;
+                }
                 rounds_and_finalize();
-            }
-            p.retry_in = nullptr;
+                return PMX_OK;
+            });
+            if (rc) return rc;
             if (g_profiling && last_of_call) PMX_HIPCHECK(hipEventRecord(ws.ev[5], stream));
         }
     }
     PMX_HIPCHECK(hipGetLastError());
-    if (!debug_ok) return pmx_fail(PMX_ERR_INVALID, "the validation kernels (pmx_screen_debug.hip) do not match this build's parameter block");
     if (g_profiling) PMX_HIPCHECK(hipEventRecord(ws.ev[3], stream));
     ws.ev_valid = g_profiling != 0;
     ws.last_stream = stream;
@@ -771,12 +746,6 @@ static int lanes_of(const pmx_library *lib) {
     int g = 1;
     while (g < std::min(lib->info.max_conformers, PMX_MAX_CONFORMERS)) g <<= 1;
     return g;
-}
-
-static Weights to_weights(const float weights[PMX_NUM_TYPES]) {
-    Weights W;
-    for (int t = 0; t < PMX_NUM_TYPES; ++t) W.w[t] = weights[t];
-    return W;
 }
 
 // The workspace of (device, stream), held: one call at a time enqueues on it. (lock is released before ws goes)
@@ -907,24 +876,13 @@ static int explain_screen(const pmx_model *model, const pmx_library *lib, const 
     ctl_clear_kernel<<<dim3((sizeof(Ctl) / 4 + 255) / 256), dim3(256), 0, stream>>>(xctl, 1);
     const size_t lds = pmx_xpl::lds_bytes(G, model->dm.K, (int)p.max_nodes, constrained, (int)a.n_modes);
     const uint32_t full = (uint32_t)ws.num_cu * pl.waves_per_cu;
-    bool ok = true;
-    auto launch = [&](int mode, uint32_t blocks) { ok &= pmx_xpl::launch(G, tails, constrained, mode, std::max(1u, blocks), (unsigned)lds, stream, &p, sizeof p, a); };
-    p.slices = ws.slices.as<uint8_t>();
-    p.slice_bytes = pl.slice_bytes;
-    launch(0, std::min(full, a.n));
-    p.slices = ws.big.as<uint8_t>();
-    p.slice_bytes = pl.big_bytes;
-    launch(1, std::min(pl.big_grid, full));
-    p.retry_out = lists;
-    p.retry_slot = 0;
-    launch(2, std::min(pl.big_grid, full));
-    for (int t = 0; t < pl.arena_retries; ++t) {
-        prepare_retry(p, xctl, lists, a.n, t, pl.arena_retries, stream);
-        launch(3, std::min(pl.big_grid, full));
-    }
+    auto launch = [&](int mode, uint32_t blocks) {
+        p.mode = mode;
+        pmx_xpl::launch(G, tails, constrained, std::max(1u, blocks), (unsigned)lds, stream, p, a);
+    };
+    (void)chunk_passes(p, pl, ws, std::min(full, a.n), std::min(pl.big_grid, full), stream, launch, [] { return PMX_OK; }); // (no rounds: every walk ends in its pass)
     pmx_xpl::launch_fixup(a, stream);
     PMX_HIPCHECK(hipGetLastError());
-    if (!ok) return pmx_fail(PMX_ERR_INVALID, "the explain kernels (pmx_explain.hip) do not match this build's parameter block");
     return PMX_OK;
 }
 
@@ -994,29 +952,6 @@ extern "C" int pmx_explain_modes(const pmx_model *model, const pmx_library *lib,
 // pmx_attribute, pmx_align and pmx_hotspots: one kernel over the call's rows; no tables, no slices, no arena. Of the workspace of (device, stream) it
 // takes the CU count and four bytes for its row cursor, cleared in stream order in front of the launch. `what`: the call's name in a
 // message; null_out: one of the caller's own device pointers is null; launch(blocks, p, cursor) starts the caller's kernel.
-// What a row kernel reads of a model, a library and the weights: the parameter block with those filled in and nothing else.
-static ScreenParams row_params(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES]) {
-    ScreenParams p{};
-    p.M = model->dm;
-    p.lib = lib->dl;
-    p.sidtab = model->sidtab;
-    p.sub_off = model->sub_off;
-    p.sub_nodes = model->sub_nodes;
-    p.W = to_weights(weights);
-    return p;
-}
-
-// pmx_device.h: the same block for a unit that launches a row kernel of its own (pmx_pose_fit.hip); struct pmx_model stays in this unit.
-int pmx_row_params(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], void *params_out, size_t bytes, int *device_out) {
-    if (!model || !lib || !weights) return pmx_fail(PMX_ERR_INVALID, "null argument");
-    if (bytes != sizeof(ScreenParams)) return pmx_fail(PMX_ERR_INVALID, "a row kernel's parameter block does not match this build's");
-    if (model->device != lib->device) return pmx_fail(PMX_ERR_INVALID, "model and library live on different devices");
-    const ScreenParams p = row_params(model, lib, weights);
-    std::memcpy(params_out, &p, sizeof p);
-    *device_out = lib->device;
-    return PMX_OK;
-}
-
 template <class Launch>
 static int row_call(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], uint32_t n, const char *what, bool null_out,
                     pmx_rows::Kind kind, hipStream_t stream, Launch launch) {
@@ -1035,7 +970,7 @@ static int row_call(const pmx_model *model, const pmx_library *lib, const float 
     const ScreenParams p = row_params(model, lib, weights);
     const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(kLdsPerCu / pmx_rows::lds_bytes(kind), 8));
     const unsigned blocks = std::min<unsigned>(n, (unsigned)ws.num_cu * per_cu);
-    if (!launch(blocks, p, ws.acur.as<uint32_t>())) return pmx_fail(PMX_ERR_INVALID, "the %s kernel (pmx_rows.hip) does not match this build's parameter block", what);
+    launch(blocks, p, ws.acur.as<uint32_t>());
     PMX_HIPCHECK(hipGetLastError());
     return PMX_OK;
 }
@@ -1047,7 +982,7 @@ extern "C" int pmx_attribute(const pmx_model *model, const pmx_library *lib, con
     const bool null_out = !ligands_dev || !conformer_dev || !key_dev || !total_dev || !node_dev || !entry_dev || !fails_dev || !levels_dev || !status_dev;
     return row_call(model, lib, weights, n, "attribute", null_out, pmx_rows::kAttribute, stream, [&](unsigned blocks, const ScreenParams &p, uint32_t *cursor) {
         const pmx_rows::AttributeArgs a{{ligands_dev, conformer_dev, key_dev, n, levels_dev, status_dev, cursor}, total_dev, node_dev, entry_dev, fails_dev};
-        return pmx_rows::launch(pmx_rows::kAttribute, blocks, stream, &p, sizeof p, &a);
+        pmx_rows::launch(blocks, stream, p, a);
     });
 }
 
@@ -1058,7 +993,7 @@ extern "C" int pmx_hotspots(const pmx_model *model, const pmx_library *lib, cons
     const bool null_out = !ligands_dev || !conformer_dev || !key_dev || !total_dev || !hotspot_dev || !terms_dev || !pass_dev || !fingerprint_dev || !levels_dev || !status_dev;
     return row_call(model, lib, weights, n, "hotspots", null_out, pmx_rows::kHotspots, stream, [&](unsigned blocks, const ScreenParams &p, uint32_t *cursor) {
         const pmx_rows::HotspotArgs a{{ligands_dev, conformer_dev, key_dev, n, levels_dev, status_dev, cursor}, total_dev, hotspot_dev, terms_dev, pass_dev, fingerprint_dev};
-        return pmx_rows::launch(pmx_rows::kHotspots, blocks, stream, &p, sizeof p, &a);
+        pmx_rows::launch(blocks, stream, p, a);
     });
 }
 
@@ -1069,6 +1004,6 @@ extern "C" int pmx_align(const pmx_model *model, const pmx_library *lib, const f
     const bool null_out = !node_center_dev || !ligands_dev || !conformer_dev || !key_dev || !rot_dev || !trans_dev || !fit_dev || !node_dev || !count_dev || !levels_dev || !status_dev;
     return row_call(model, lib, weights, n, "align", null_out, pmx_rows::kAlign, stream, [&](unsigned blocks, const ScreenParams &p, uint32_t *cursor) {
         const pmx_rows::AlignArgs a{{ligands_dev, conformer_dev, key_dev, n, levels_dev, status_dev, cursor}, node_center_dev, rot_dev, trans_dev, fit_dev, node_dev, count_dev};
-        return pmx_rows::launch(pmx_rows::kAlign, blocks, stream, &p, sizeof p, &a);
+        pmx_rows::launch(blocks, stream, p, a);
     });
 }

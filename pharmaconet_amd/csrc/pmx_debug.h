@@ -2,11 +2,11 @@
 // pmx_api.hip calls them when a bit outside PMX_PRODUCT_FLAGS is set; libpmx's own kernels read those bits as zero.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <cstddef>
+
+#include "pmx_screen_layout.h"
 
 namespace pmx_debug {
-// `params`: the caller's pmx::ScreenParams (same source, same layout; `bytes` is checked against this side's sizeof).
-// G = lanes per slot (1 .. 64, a power of two). Returns false when G or the size is not one this side knows.
-bool launch_ligand(int G, bool exact, bool tails, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes);
-bool launch_task(int G, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes);
+// G = lanes per slot (1 .. 64, a power of two). Returns false when G is not a lane count the kernels are built for.
+bool launch_ligand(int G, bool exact, bool tails, unsigned blocks, unsigned lds, hipStream_t stream, const pmx::ScreenParams &p);
+bool launch_task(int G, unsigned blocks, unsigned lds, hipStream_t stream, const pmx::ScreenParams &p);
 } // namespace pmx_debug

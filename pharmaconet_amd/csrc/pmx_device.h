@@ -19,10 +19,7 @@
                             hipGetErrorString(e_), __FILE__, __LINE__);                                            \
     } while (0)
 
-// Host: what the units of libpmx.so call in one another, outside include/pmx.h.
-int pmx_library_device(const pmx_library *lib); // pmx_api.hip (struct pmx_library stays in that unit)
-int pmx_row_params(const pmx_model *model, const pmx_library *lib, const float weights[PMX_NUM_TYPES], void *params_out, size_t bytes,
-                   int *device_out);            // pmx_api.hip: the ScreenParams (`bytes` = its sizeof) of a row kernel, and the device of both
+// Host: what the units of libpmx.so call in one another, outside include/pmx.h. (What stands behind a model or library handle: pmx_handles.h.)
 int pmx_topk_release(int device);               // pmx_topk.hip, pmx_pack_device.hip, pmx_select.hip: free the unit's cached buffers
 int pmx_pack_release(int device);               //   of `device` (pmx_release_workspaces)
 int pmx_select_release(int device);

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "pmx.h"
+#include "pmx_screen_layout.h"
 
 namespace pmx_xpl {
 // Where one call's answers go (device pointers, see pmx_explain in include/pmx.h); row i belongs to ligands[i].
@@ -24,11 +25,10 @@ struct Args {
 // totals per conformer lane (4 KB at 64 lanes and 8 modes; the keys, 10 KB there, live in the row's output block instead: a leaf
 // enters a list rarely after the first few).
 size_t lds_bytes(int G, int K, int max_nodes, bool constrained, int n_modes);
-// `params`: the caller's pmx::ScreenParams (same source and layout; `bytes` is checked against this side's sizeof). mode as
-// ScreenParams::mode: 0 the listed ligands with tables in per-wave slices, 1 the large-slice pass, 2 / 3 the arena passes.
-// `constrained`: the kernels that test every leaf against a.con; without it a.con is not read. Returns false when G or the size is
-// not one this side knows.
-bool launch(int G, bool tails, bool constrained, int mode, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes, const Args &a);
+// `p` with p.mode as the pass: 0 the listed ligands with tables in per-wave slices, 1 the large-slice pass, 2 / 3 the arena passes.
+// `constrained`: the kernels that test every leaf against a.con; without it a.con is not read. Returns false when G is not a lane
+// count the kernels are built for.
+bool launch(int G, bool tails, bool constrained, unsigned blocks, unsigned lds, hipStream_t stream, const pmx::ScreenParams &p, const Args &a);
 void launch_init(const Args &a, hipStream_t stream);  // rows as for a ligand without levels: maxima 0, no match, no levels (every mode's)
 void launch_fixup(const Args &a, hipStream_t stream); // rows of ligands with a non-zero status: maxima NaN (every mode's), best conformer -1
 } // namespace pmx_xpl

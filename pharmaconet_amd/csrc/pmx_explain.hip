@@ -38,7 +38,6 @@
 // lists are those of the full tree. The feasibility drops of the constrained walker do not look at values and are unchanged.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <cstring>
 
 #define PMX_NS pmx_x
 #include "pmx_screen_tables.h"
@@ -403,16 +402,12 @@ size_t lds_bytes(int G, int K, int max_nodes, bool constrained, int n_modes) {
 }
 
 template <int G, bool CONSTRAINED>
-static void launch_shape(bool tails, unsigned blocks, unsigned lds, hipStream_t stream, const pmx_x::ScreenParams &p, const Args &a) {
+static void launch_shape(bool tails, unsigned blocks, unsigned lds, hipStream_t stream, const pmx::ScreenParams &p, const Args &a) {
     if (tails) pmx_x::explain_kernel<G, true, CONSTRAINED><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
     else pmx_x::explain_kernel<G, false, CONSTRAINED><<<dim3(blocks), dim3(64), lds, stream>>>(p, a);
 }
 
-bool launch(int G, bool tails, bool constrained, int mode, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes, const Args &a) {
-    if (bytes != sizeof(pmx_x::ScreenParams)) return false;
-    pmx_x::ScreenParams p;
-    std::memcpy(&p, params, sizeof p);
-    p.mode = mode;
+bool launch(int G, bool tails, bool constrained, unsigned blocks, unsigned lds, hipStream_t stream, const pmx::ScreenParams &p, const Args &a) {
     return pmx::with_lanes(G, [&](auto g) {
         constexpr int L = decltype(g)::value;
         constrained ? launch_shape<L, true>(tails, blocks, lds, stream, p, a) : launch_shape<L, false>(tails, blocks, lds, stream, p, a);

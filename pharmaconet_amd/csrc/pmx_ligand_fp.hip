@@ -33,6 +33,7 @@
 
 #include "pmx.h"
 #include "pmx_device.h"
+#include "pmx_handles.h"
 
 namespace {
 using pmx::parse_record;
@@ -183,22 +184,19 @@ __global__ __launch_bounds__(256) void search_kernel(const uint64_t *__restrict_
 extern "C" int pmx_library_fingerprints(const pmx_library *lib, uint64_t first, uint64_t count, const int32_t *conformer_dev, uint64_t *fingerprint_dev, uint8_t *type_count_dev,
                                         int32_t *status_dev, void *stream_) {
     if (!lib) return pmx_fail(PMX_ERR_INVALID, "pmx_library_fingerprints: null library");
-    pmx_library_info info;
-    const uint64_t *lib_offsets = nullptr;
-    const uint8_t *lib_data = nullptr;
-    if (pmx_library_info_get(lib, &info) != PMX_OK || pmx_library_buffers(lib, &lib_offsets, &lib_data) != PMX_OK) return PMX_ERR_INVALID;
+    const pmx_library_info &info = lib->info;
     if (first > info.n_ligands || count > info.n_ligands - first)
         return pmx_fail(PMX_ERR_INVALID, "pmx_library_fingerprints: ligands %llu .. %llu of a library of %llu", (unsigned long long)first, (unsigned long long)(first + count),
                         (unsigned long long)info.n_ligands);
     if (count == 0) return PMX_OK;
     if (!fingerprint_dev) return pmx_fail(PMX_ERR_INVALID, "pmx_library_fingerprints: null fingerprint_dev");
-    if (hipSetDevice(pmx_library_device(lib)) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_library_fingerprints: hipSetDevice failed");
+    if (hipSetDevice(lib->device) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_library_fingerprints: hipSetDevice failed");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     constexpr uint64_t kChunk = 1ull << 30; // ligands per launch (a grid has fewer than 2^31 blocks)
     for (uint64_t at = 0; at < count; at += kChunk) {
         const uint64_t todo = count - at < kChunk ? count - at : kChunk;
         ligand_fp_kernel<<<dim3((unsigned)((todo + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, stream>>>(
-            lib_offsets, lib_data, first + at, todo, conformer_dev ? conformer_dev + at : nullptr, fingerprint_dev + at * kW, type_count_dev ? type_count_dev + at * 8 : nullptr,
+            lib->offsets, lib->data, first + at, todo, conformer_dev ? conformer_dev + at : nullptr, fingerprint_dev + at * kW, type_count_dev ? type_count_dev + at * 8 : nullptr,
             status_dev ? status_dev + at : nullptr);
         PMX_HIPCHECK(hipGetLastError());
     }

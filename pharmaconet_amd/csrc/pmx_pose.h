@@ -9,6 +9,7 @@
 
 #include "pmx.h"
 #include "pmx_device.h"
+#include "pmx_handles.h"
 
 struct pmx_pocket {
     int device = 0;
@@ -126,10 +127,10 @@ inline int pose_source(const char *fn, const pmx_pocket *pocket, const pmx_libra
     if (n > PMX_EXPLAIN_MAX) return pmx_fail(PMX_ERR_INVALID, "%s: %u rows, at most %d", fn, n, PMX_EXPLAIN_MAX);
     *out = PoseSource{};
     if (nodes) {
-        pmx_library_info info;
-        if (pmx_library_info_get(lib, &info) != PMX_OK || pmx_library_buffers(lib, &out->lib_offsets, &out->lib_data) != PMX_OK) return PMX_ERR_INVALID;
-        if (pmx_library_device(lib) != pocket->device) return pmx_fail(PMX_ERR_INVALID, "%s: the pocket is on device %d, the library on %d", fn, pocket->device, pmx_library_device(lib));
-        out->lib_n = info.n_ligands;
+        if (lib->device != pocket->device) return pmx_fail(PMX_ERR_INVALID, "%s: the pocket is on device %d, the library on %d", fn, pocket->device, lib->device);
+        out->lib_offsets = lib->offsets;
+        out->lib_data = lib->data;
+        out->lib_n = lib->info.n_ligands;
     }
     if (n == 0) return PMX_OK;
     if (nodes ? (!ligands_dev || !conformer_dev) : (!point_off_dev || !points_dev)) return pmx_fail(PMX_ERR_INVALID, "%s: null %s", fn, nodes ? "ligands_dev or conformer_dev" : "point_off_dev or points_dev");

@@ -213,16 +213,15 @@ extern "C" int pmx_pose_fit(const pmx_model *model, const pmx_library *lib, cons
                             double *summary_dev, int32_t *count_dev, double *node_fit_dev, double *node_best_dev, double *node_z2_dev, int32_t *node_target_dev,
                             double *hotspot_z2_dev, int32_t *hotspot_node_dev, uint64_t *occupied_fp_dev, int32_t *status_dev, void *stream_) {
     using namespace pmx_f;
-    ScreenParams p;
-    int device = 0;
-    const int rc = pmx_row_params(model, lib, weights, &p, sizeof p, &device);
-    if (rc != PMX_OK) return rc;
+    if (!model || !lib || !weights) return pmx_fail(PMX_ERR_INVALID, "null argument");
+    if (model->device != lib->device) return pmx_fail(PMX_ERR_INVALID, "model and library live on different devices");
     if (n > PMX_EXPLAIN_MAX) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_fit: %u rows, at most %d", n, PMX_EXPLAIN_MAX);
     if (n == 0) return PMX_OK;
     if (!node_center_dev || !node_sigma_dev || !ligands_dev || !conformer_dev || !rot_dev || !trans_dev) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_fit: null input (only key_dev may be)");
     if (!summary_dev || !count_dev || !node_fit_dev || !node_best_dev || !node_z2_dev || !node_target_dev || !hotspot_z2_dev || !hotspot_node_dev || !occupied_fp_dev || !status_dev)
         return pmx_fail(PMX_ERR_INVALID, "pmx_pose_fit: null output");
-    PMX_HIPCHECK(hipSetDevice(device));
+    PMX_HIPCHECK(hipSetDevice(lib->device));
+    const ScreenParams p = row_params(model, lib, weights);
     const FitArgs a{node_center_dev, node_sigma_dev, ligands_dev, conformer_dev, key_dev, rot_dev, trans_dev, n, summary_dev, count_dev, node_fit_dev, node_best_dev, node_z2_dev,
                     node_target_dev, hotspot_z2_dev, hotspot_node_dev, occupied_fp_dev, status_dev};
     const dim3 grid((n + kWaves - 1) / kWaves), block(64 * kWaves);

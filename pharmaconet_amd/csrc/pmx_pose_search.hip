@@ -252,7 +252,7 @@ extern "C" int pmx_pose_search(const pmx_model *model, const pmx_library *lib, c
     const Work w = work_layout(work_dev, n, R);
     if (work_bytes < w.bytes) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_search: a work buffer of %llu bytes, %llu needed", (unsigned long long)work_bytes, (unsigned long long)w.bytes);
     if (reinterpret_cast<uintptr_t>(work_dev) % 16 != 0) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_search: the work buffer is not 16-byte aligned");
-    const int device = pmx_library_device(lib);
+    const int device = lib->device;
     if (device != pocket->device) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_search: the pocket is on device %d, the library on %d", pocket->device, device);
     PMX_HIPCHECK(hipSetDevice(device));
     hipStream_t stream = static_cast<hipStream_t>(stream_);

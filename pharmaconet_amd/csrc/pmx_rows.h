@@ -1,9 +1,11 @@
-// pmx_rows.h - launcher of the row kernels (pmx_rows.hip): attribution, rigid fit and hotspot shares of listed (ligand, conformer, key) rows, called by
+// pmx_rows.h - launchers of the row kernels (pmx_rows.hip): attribution, rigid fit and hotspot shares of listed (ligand, conformer, key) rows, called by
 // pmx_attribute(), pmx_align() and pmx_hotspots() in pmx_api.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <stdint.h>
+
+#include "pmx_screen_layout.h"
 
 namespace pmx_rows {
 // One call's rows and what every row kernel says about a row (device pointers); row i is ligands[i] at conformer[i] under key[i].
@@ -46,8 +48,8 @@ struct HotspotArgs {
 enum Kind { kAttribute, kAlign, kHotspots };
 // Static LDS of one wavefront of the kernel: how many fit a compute unit.
 size_t lds_bytes(Kind kind);
-// `params`: the caller's pmx::ScreenParams with the model, the library, the node subsets and the weights filled in (same source and
-// layout; `bytes` is checked against this side's sizeof). `args`: the AttributeArgs, AlignArgs or HotspotArgs of `kind`. Returns false when the size
-// is not the one this side knows.
-bool launch(Kind kind, unsigned blocks, hipStream_t stream, const void *params, size_t bytes, const void *args);
+// `p`: the model, the library, the node subsets and the weights filled in (row_params, pmx_handles.h); the arguments pick the kernel.
+void launch(unsigned blocks, hipStream_t stream, const pmx::ScreenParams &p, const AttributeArgs &a);
+void launch(unsigned blocks, hipStream_t stream, const pmx::ScreenParams &p, const AlignArgs &a);
+void launch(unsigned blocks, hipStream_t stream, const pmx::ScreenParams &p, const HotspotArgs &a);
 } // namespace pmx_rows

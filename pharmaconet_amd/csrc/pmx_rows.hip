@@ -41,7 +41,6 @@
 //
 // In no kernel does a lane add to another lane's sum, and there is no floating-point atomic: the same call gives the same bits.
 #include <hip/hip_runtime.h>
-#include <cstring>
 
 #define PMX_NS pmx_r
 #include "pmx_screen_tables.h"
@@ -690,14 +689,8 @@ namespace pmx_rows {
 
 size_t lds_bytes(Kind kind) { return kind == kAttribute ? (size_t)pmx_r::kAttributeLds : (kind == kHotspots ? (size_t)pmx_r::kHotspotsLds : sizeof(pmx_r::RowLds)); }
 
-bool launch(Kind kind, unsigned blocks, hipStream_t stream, const void *params, size_t bytes, const void *args) {
-    if (bytes != sizeof(pmx_r::ScreenParams)) return false;
-    pmx_r::ScreenParams p;
-    std::memcpy(&p, params, sizeof p);
-    if (kind == kAttribute) pmx_r::attribute_kernel<<<dim3(blocks), dim3(64), 0, stream>>>(p, *static_cast<const AttributeArgs *>(args));
-    else if (kind == kHotspots) pmx_r::hotspots_kernel<<<dim3(blocks), dim3(64), 0, stream>>>(p, *static_cast<const HotspotArgs *>(args));
-    else pmx_r::align_kernel<<<dim3(blocks), dim3(64), 0, stream>>>(p, *static_cast<const AlignArgs *>(args));
-    return true;
-}
+void launch(unsigned blocks, hipStream_t stream, const pmx::ScreenParams &p, const AttributeArgs &a) { pmx_r::attribute_kernel<<<dim3(blocks), dim3(64), 0, stream>>>(p, a); }
+void launch(unsigned blocks, hipStream_t stream, const pmx::ScreenParams &p, const AlignArgs &a) { pmx_r::align_kernel<<<dim3(blocks), dim3(64), 0, stream>>>(p, a); }
+void launch(unsigned blocks, hipStream_t stream, const pmx::ScreenParams &p, const HotspotArgs &a) { pmx_r::hotspots_kernel<<<dim3(blocks), dim3(64), 0, stream>>>(p, a); }
 
 } // namespace pmx_rows

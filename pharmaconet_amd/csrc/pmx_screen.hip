@@ -1,9 +1,11 @@
 // pmx_screen.hip - the screening hot path on gfx950 (CDNA4, wave64): one wavefront scores one ligand from its packed
-// record to its score. This file holds the kernels; what they are made of sits in three headers, each on top of the one before:
-//   pmx_screen_layout.h   records, queue, control block, parameter block, a wave's LDS (host and device; what the host sizes buffers from)
+// record to its score. This file holds the kernels; what they are made of sits in four headers, each on top of the one before:
+//   pmx_screen_layout.h   records, queue, control block, kernel parameters (host and device, namespace pmx: one type for every unit)
+//   pmx_screen_lds.h      PMX_NS and a wave's LDS, the one layout a compile-time switch changes (host and device; sizes launches)
 //   pmx_screen_tables.h   wave helpers, the pair-function builder, the table phase and the bounds, prepare_ligand
 //   pmx_screen_walk.h     the walker, its bound tests, prepare_walk, run_job
-// pmx_api.hip (namespace pmx) and pmx_screen_debug.hip (pmx_dbg) include this file; pmx_explain.hip (pmx_x) stops at the tables.
+// pmx_api.hip (namespace pmx) and pmx_screen_debug.hip (pmx_dbg) include this file; pmx_explain.hip (pmx_x), pmx_rows.hip (pmx_r) and
+// pmx_pose_fit.hip (pmx_f) stop at the tables.
 //
 // Reference path: PharmacophoreModel._scoring -> GraphMatcher.run() (src/pmnet/scoring/graph_match.py:63-279,
 // scoring/match_utils.py:9-122, scoring/tree.py:15-104); citations below are relative to /root/reference/src/pmnet.

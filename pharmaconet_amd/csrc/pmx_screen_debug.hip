@@ -1,8 +1,7 @@
 // pmx_screen_debug.hip - pmx_screen.hip once more, as namespace pmx_dbg, with every PMX_TREE_FLAGS switch compiled in: the kernels
 // behind the validation settings of the tests (no bounds, no fused levels, no cache, term-by-term items, ...) and the phase studies
-// of tools/. libpmx's own kernels (namespace pmx) carry none of these switches; see the note on PMX_NS in pmx_screen_layout.h.
+// of tools/. libpmx's own kernels (namespace pmx) carry none of these switches; see the note on PMX_NS in pmx_screen_lds.h.
 #include <hip/hip_runtime.h>
-#include <cstring>
 
 #define PMX_DEBUG_KERNELS 1
 #define PMX_NS pmx_dbg
@@ -11,10 +10,7 @@
 
 namespace pmx_debug {
 
-bool launch_ligand(int G, bool exact, bool tails, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes) {
-    if (bytes != sizeof(pmx_dbg::ScreenParams)) return false;
-    pmx_dbg::ScreenParams p;
-    std::memcpy(&p, params, sizeof p);
+bool launch_ligand(int G, bool exact, bool tails, unsigned blocks, unsigned lds, hipStream_t stream, const pmx::ScreenParams &p) {
     return pmx::with_lanes(G, [&](auto g) {
         constexpr int L = decltype(g)::value;
         if (exact) pmx_dbg::ligand_kernel<L, true, false><<<dim3(blocks), dim3(64), lds, stream>>>(p);
@@ -23,10 +19,7 @@ bool launch_ligand(int G, bool exact, bool tails, unsigned blocks, unsigned lds,
     });
 }
 
-bool launch_task(int G, unsigned blocks, unsigned lds, hipStream_t stream, const void *params, size_t bytes) {
-    if (bytes != sizeof(pmx_dbg::ScreenParams)) return false;
-    pmx_dbg::ScreenParams p;
-    std::memcpy(&p, params, sizeof p);
+bool launch_task(int G, unsigned blocks, unsigned lds, hipStream_t stream, const pmx::ScreenParams &p) {
     return pmx::with_lanes(G, [&](auto g) { pmx_dbg::task_kernel<decltype(g)::value><<<dim3(blocks), dim3(64), lds, stream>>>(p); });
 }
 

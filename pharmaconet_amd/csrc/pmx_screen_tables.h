@@ -2,11 +2,11 @@
 // bounds in a wave's slice or in the arena. The wave helpers, the pair-function builder (fn_build_kernel), the table items, scan_ligand,
 // build_tables, chain_lengths, build_bounds and prepare_ligand, which strings them together. The product walker (pmx_screen_walk.h)
 // and the explain walker (pmx_explain.hip) both start from what prepare_ligand leaves; the row kernels (pmx_rows.hip) take parse_record and the
-// level rule (cluster_candidates, level_slot) only. Layouts: pmx_screen_layout.h.
+// level rule (cluster_candidates, level_slot) only. Layouts: pmx_screen_layout.h (shared, namespace pmx) and pmx_screen_lds.h (per PMX_NS).
 #pragma once
 #include <type_traits>
 
-#include "pmx_screen_layout.h"
+#include "pmx_screen_lds.h"
 
 // ---- tuning constants of this file (-D through PMX_CXXFLAGS or tools/build_variant.py; none changes a layout)
 #ifndef PMX_ITEM_BATCH
@@ -54,7 +54,7 @@
 #endif
 
 namespace PMX_NS {
-using namespace pmx; // (pmx_device.h)
+using namespace pmx; // (pmx_device.h, pmx_screen_layout.h)
 
 struct WaveStats { // lives in LDS (WaveShape::off_stat), updated by lane 0
     unsigned long long frames, passes, over, items, exact, longest, tasks, overflow;

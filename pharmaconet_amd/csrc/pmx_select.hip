@@ -19,6 +19,7 @@
 
 #include "pmx.h"
 #include "pmx_device.h"
+#include "pmx_handles.h"
 #include "pmx_scan.h"
 
 namespace {
@@ -76,7 +77,7 @@ extern "C" int pmx_library_select(const pmx_library *lib, const uint64_t *indice
                                   uint64_t data_cap, uint64_t *data_bytes, void *stream_) {
     if (!lib || !offsets_out_dev || !data_bytes || (n && !indices_dev) || (!data_out_dev && data_cap)) return pmx_fail(PMX_ERR_INVALID, "pmx_library_select: null argument");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int device = pmx_library_device(lib);
+    const int device = lib->device;
     if (hipSetDevice(device) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_library_select: hipSetDevice failed");
     *data_bytes = 0;
     if (n == 0) {
@@ -85,10 +86,9 @@ extern "C" int pmx_library_select(const pmx_library *lib, const uint64_t *indice
     }
     if (n > 0x7fffffffull) return pmx_fail(PMX_ERR_INVALID, "pmx_library_select: more than 2^31 - 1 indices in one call");
     if (device < 0 || device >= kMaxDevices) return pmx_fail(PMX_ERR_INVALID, "pmx_library_select: device index out of range");
-    pmx_library_info info;
-    const uint64_t *lib_offsets = nullptr;
-    const uint8_t *lib_data = nullptr;
-    if (pmx_library_info_get(lib, &info) != PMX_OK || pmx_library_buffers(lib, &lib_offsets, &lib_data) != PMX_OK) return PMX_ERR_INVALID;
+    const pmx_library_info &info = lib->info;
+    const uint64_t *const lib_offsets = lib->offsets;
+    const uint8_t *const lib_data = lib->data;
     if (overlap(offsets_out_dev, (n + 1) * 8, lib_offsets, (info.n_ligands + 1) * 8) || overlap(offsets_out_dev, (n + 1) * 8, lib_data, info.n_bytes) ||
         overlap(data_out_dev, data_cap, lib_offsets, (info.n_ligands + 1) * 8) || overlap(data_out_dev, data_cap, lib_data, info.n_bytes))
         return pmx_fail(PMX_ERR_INVALID, "pmx_library_select: the output overlaps the source library's buffers");

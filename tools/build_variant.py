@@ -22,9 +22,10 @@ def main():
     procs = []
     for src in SOURCES:
         obj = out / f"{name}_{src.rsplit('.', 1)[0]}.o"
-        # (the three translation units that include the screening headers - the product kernels, the validation kernels and the explain
-        # kernel, which builds its tables with the same code - are always compiled with the variant's flags: a kernel built with the base
-        # macros under a host side built with the variant's would have another LDS layout and other launch bounds)
+        # (five translation units include the screening headers. The three that hold or size the screening kernels - the product kernels, the
+        # validation kernels and the explain kernel, which builds its tables with the same code - are always compiled with the variant's
+        # flags: a kernel built with the base macros under a host side built with the variant's would have another LDS layout and other
+        # launch bounds; ADVICE r5. pmx_rows.hip and pmx_pose_fit.hip take the record and wavefront helpers alone)
         screening = src in ("pmx_api.hip", "pmx_screen_debug.hip", "pmx_explain.hip")
         base_obj = out / f"base_{src.rsplit('.', 1)[0]}.o"
         fresh = base_obj.exists() and base_obj.stat().st_mtime > max((CSRC / src).stat().st_mtime, (REPO / "include" / "pmx.h").stat().st_mtime)
