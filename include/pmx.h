@@ -716,6 +716,64 @@ int pmx_pose_refine(const pmx_pocket *pocket, const pmx_library *lib /* NULL in 
                     int32_t *count_dev /* [n][4] */, int32_t *status_dev, void *stream);
 
 /*
+ * The atom store (pmx_atoms.hip): each ligand's heavy atoms resident next to its record, so that the point-mode rows of pmx_pose_clash and
+ * pmx_pose_refine - a whole molecule's atoms - can be made on the device, for any (ligand, conformer), without a host array. A store is the
+ * companion of a library: one record per ligand, in the library's order, the coordinates in the record's own frame (what pmx_align's
+ * motion applies to). The reference has no counterpart; the specification is this comment, and tests/atoms_ref.py restates it in NumPy.
+ *
+ * A record (little endian, 16-byte aligned like a ligand record):
+ *   u16 n_atoms | u16 n_conf | u32 0
+ *   u8  element[n_atoms]          atomic numbers of the heavy atoms (Z > 1), in the molecule's order, each <= 127
+ *   pad to 4 bytes
+ *   f32 xyz[n_atoms][n_conf][3]   the molecule's atom positions, heavy atoms only, as the perception hands them over
+ *   pad to 16 bytes
+ * n_atoms <= PMX_MAX_LIGAND_ATOMS, 1 <= n_conf <= PMX_MAX_CONFORMERS. A header-only record - 16 bytes, n_atoms = 0 - means "no atoms
+ * kept": a molecule with more heavy atoms than that, with none, or whose ligand record is the unsupported marker.
+ * A store is offsets u64[n_ligands + 1] (offsets[0] = 0, bytes) and data; pharmaconet_amd/atoms.py (PackedAtoms) builds and stores it.
+ *
+ * pmx_atoms_upload copies a host store to `device` and with it radius_of_element[128], the radius of a point by atomic number (the
+ * caller's: pharmaconet_amd/pocket.py's Bondi table, so that a gathered radius is the host path's bit for bit). It checks on the host, before
+ * anything is copied: offsets rising in multiples of 16, every header within the limits and consistent with its record's size, every
+ * element <= 127 - otherwise PMX_ERR_INVALID, so that no kernel has to doubt a record. The copy is finished when the call returns.
+ * pmx_atoms_info_get: n_ligands, n_bytes, max_atoms (the largest n_atoms) and n_empty (header-only records). pmx_atoms_destroy frees the
+ * copy (NULL is allowed).
+ *
+ * pmx_atoms_gather: row i < n is the heavy atoms of ligand ligands_dev[i] at conformer conformer_dev[i], in record order:
+ *   point_off_dev     uint64 [n + 1]  point_off[0] = 0; row i's points are [point_off[i], point_off[i + 1])
+ *   points_dev        float32 [cap_points][3]  the record's float32 coordinates of that conformer, copied
+ *   point_radius_dev  float32 [cap_points]     radius_of_element[element]
+ *   status_dev        int32 [n]  PMX_LIGAND_OK; PMX_LIGAND_UNSUPPORTED for an index outside the store and for a header-only record (whatever
+ *                     the conformer); otherwise PMX_LIGAND_KEY_INVALID for a conformer < 0 or >= the record's n_conf
+ * A row that is not OK has no points: point_off[i + 1] == point_off[i]. These are the three point-mode arguments of pmx_pose_clash and
+ * pmx_pose_refine; a caller that wants a row without atoms reported as not OK - in point mode an empty row is a valid row with clearance
+ * -inf - merges status_dev into theirs (pmx_pose_search_atoms does).
+ * n <= PMX_EXPLAIN_MAX and cap_points >= n * max_atoms of the store: otherwise PMX_ERR_INVALID - checked on the host, so that no row can
+ * write past the buffers and nothing has to be read back. n = 0 succeeds and writes point_off[0] = 0 only. With n > 0 no pointer may be
+ * NULL; the pointers are memory of the store's device. Stream-ordered (enqueued, no synchronisation), no allocation, no work buffer, no
+ * atomic: the same bits on every run, and for a row wherever it stands in a call. Three kernels: a size per row, one block's scan of the
+ * sizes into point_off_dev, one wavefront per row for the copy.
+ */
+#define PMX_MAX_LIGAND_ATOMS 256
+typedef struct pmx_atoms pmx_atoms;
+typedef struct {
+    uint64_t n_ligands;
+    const uint64_t *offsets; /* [n_ligands + 1], host */
+    const uint8_t *data;     /* host */
+} pmx_atoms_view;
+typedef struct {
+    uint64_t n_ligands;
+    uint64_t n_bytes;
+    int32_t max_atoms;
+    int32_t n_empty;
+} pmx_atoms_info;
+int pmx_atoms_upload(const pmx_atoms_view *view, const float radius_of_element[128], int device, pmx_atoms **out);
+int pmx_atoms_info_get(const pmx_atoms *atoms, pmx_atoms_info *info);
+int pmx_atoms_destroy(pmx_atoms *atoms);
+int pmx_atoms_gather(const pmx_atoms *atoms, const uint64_t *ligands_dev, const int32_t *conformer_dev, uint32_t n, uint64_t cap_points,
+                     uint64_t *point_off_dev /* [n + 1] */, float *points_dev /* [cap_points][3] */, float *point_radius_dev /* [cap_points] */,
+                     int32_t *status_dev /* [n] */, void *stream);
+
+/*
  * Pose search (pmx_pose_search.hip): which of a hit's conformers, under which of its binding modes, to pose. pmx_explain's single pose -
  * the best conformer under its own key - often grazes a side chain where the second conformer, or the same conformer under its second
  * mode, sits in the cavity. The call takes the output of a pmx_explain_modes call over exactly ligands_dev[n] (with or without a
@@ -769,6 +827,44 @@ int pmx_pose_search(const pmx_model *model, const pmx_library *lib, const float 
                     int32_t *count_dev /* [n][2] */, uint8_t *levels_dev, double *summary_dev, int32_t *clash_count_dev /* [n][6] */,
                     double *point_pen_dev, int32_t *point_atom_dev, uint64_t *contact_fp_dev, int32_t *status_dev,
                     int32_t *row_status_dev /* [2][n] */, void *work_dev, uint64_t work_bytes, void *stream);
+
+/*
+ * Pose search at atom level (pmx_pose_search.hip): pmx_pose_search with the clash check made on the ligand's heavy atoms, taken from an
+ * atom store (pmx_atoms, above) that is the companion of `lib`. Where the node-level search picks a pose whose pharmacophore nodes are
+ * clear, the atoms between them may still run through a side chain; this call chooses on what the next step would check. Nodes are
+ * still what pmx_align fits. The rule is pmx_pose_search's word for word, with two changes:
+ *   row        of a slot: pmx_align's row as there; the clash check is pmx_pose_clash in point mode on the row pmx_atoms_gather makes of
+ *              (ligands_dev[i], c) - the store's coordinates, the store's radii by element - under the fitted motion. point_radius is not
+ *              read (every point has its own radius) but must be finite
+ *   candidate  additionally: pmx_atoms_gather of the row has status OK. A slot whose gather status is not OK gets that status as its
+ *              clash status - in point mode a row without points would pass with clearance -inf
+ *   passes, the choice, dropped, vbest: as there, on the atoms' count[1] and summary[1]
+ * Consequence: where the default pose - the hit's best conformer under mode 0 - has atoms in the store, passes at atom level and has
+ * min_fitted fitted nodes, it is the choice.
+ * Outputs, per hit: choice_dev, value_dev, key_dev, status_dev and the pmx_align outputs as pmx_pose_search's. The clash outputs are those
+ * of the chosen row in point-mode layout: summary_dev, clash_count_dev, contact_fp_dev as there; point_off_dev uint64 [n + 1] what
+ * pmx_atoms_gather writes for the n chosen rows (a hit without a choice has no points); point_pen_dev double and point_atom_dev int32 in
+ * that layout, each with room for n * max_atoms of the store.
+ *   row_status_dev  int32 [3][n]  the statuses pmx_align ([0][i]), pmx_atoms_gather ([1][i]) and pmx_pose_clash ([2][i]) give the chosen
+ *               row; [2][i] is [1][i] where that is not OK. A hit whose atom record is header-only has no choice and [1][i] =
+ *               PMX_LIGAND_UNSUPPORTED
+ * Limits and errors as pmx_pose_search's; the store is on the library's device. work_dev: at least
+ * pmx_pose_search_atoms_work_bytes(n, n_modes, conf_stride, max_atoms) bytes, max_atoms the store's (pmx_atoms_info); the query answers 0
+ * for a shape the call would refuse (max_atoms outside 0 .. PMX_MAX_LIGAND_ATOMS included) and grows with each argument. The call allocates
+ * nothing and synchronises nothing. Its kernels are pmx_pose_search's two, unchanged, and a status merge; between them pmx_align,
+ * pmx_atoms_gather and pmx_pose_clash run on the slots, and once more on the n chosen rows. No atomic: the same bits on every run, and for
+ * a hit wherever it stands in a call.
+ */
+uint64_t pmx_pose_search_atoms_work_bytes(uint32_t n, int n_modes, int conf_stride, int max_atoms);
+int pmx_pose_search_atoms(const pmx_model *model, const pmx_library *lib, const pmx_atoms *atoms, const float weights[PMX_NUM_TYPES],
+                          const double *node_center_dev, const pmx_pocket *pocket, const uint64_t *ligands_dev, uint32_t n,
+                          const double *mode_max_dev, const uint8_t *mode_match_dev, const int32_t *explain_status_dev, int n_modes,
+                          int conf_stride, float point_radius, float tolerance, float contact, int max_clashing, int min_fitted,
+                          double min_fraction, int32_t *choice_dev /* [n][6] */, double *value_dev /* [n][2] */,
+                          uint8_t *key_dev /* [n][PMX_MAX_LEVELS] */, double *rot_dev, double *trans_dev, double *fit_dev, double *node_dev,
+                          int32_t *count_dev /* [n][2] */, uint8_t *levels_dev, double *summary_dev, int32_t *clash_count_dev /* [n][6] */,
+                          uint64_t *point_off_dev /* [n + 1] */, double *point_pen_dev, int32_t *point_atom_dev, uint64_t *contact_fp_dev,
+                          int32_t *status_dev, int32_t *row_status_dev /* [3][n] */, void *work_dev, uint64_t work_bytes, void *stream);
 
 /*
  * Pose fit (pmx_pose_fit.hip): do the ligand's pharmacophore nodes sit on the pocket's hotspots once a pose exists? pmx_align reports a

@@ -6,9 +6,10 @@ Public surface mirrors `pmnet` for this path only: `PharmacophoreModel` with
 `pharmaconet_amd/csrc` (HIP, gfx950) behind the C ABI of `include/pmx.h`.
 """
 
+from .atoms import PackedAtoms
 from .constants import DEFAULT_WEIGHTS, TYPE_NAMES
 from .library import LigandFeatures, PackedLibrary, pack_ligand
 from .pharmacophore_model import PharmacophoreModel
 
 __version__ = "0.1.0"
-__all__ = ["PharmacophoreModel", "PackedLibrary", "LigandFeatures", "pack_ligand", "DEFAULT_WEIGHTS", "TYPE_NAMES"]
+__all__ = ["PharmacophoreModel", "PackedLibrary", "PackedAtoms", "LigandFeatures", "pack_ligand", "DEFAULT_WEIGHTS", "TYPE_NAMES"]

@@ -52,6 +52,17 @@ class LibraryInfo(ctypes.Structure):
     ]
 
 
+class AtomsView(ctypes.Structure):
+    _fields_ = [("n_ligands", ctypes.c_uint64), ("offsets", ctypes.c_void_p), ("data", ctypes.c_void_p)]
+
+
+class AtomsInfo(ctypes.Structure):
+    _fields_ = [("n_ligands", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("max_atoms", ctypes.c_int32), ("n_empty", ctypes.c_int32)]
+
+
+MAX_LIGAND_ATOMS = 256  # include/pmx.h PMX_MAX_LIGAND_ATOMS
+
+
 class FeatureBatch(ctypes.Structure):
     _fields_ = [
         ("n_mols", ctypes.c_uint64),
@@ -251,6 +262,20 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_double,
          *([ctypes.c_void_p] * 16), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
+    ),
+    "pmx_pose_search_atoms_work_bytes": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "pmx_pose_search_atoms": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+         *([ctypes.c_void_p] * 17), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p],
+    ),
+    "pmx_atoms_upload": (ctypes.c_int, [ctypes.POINTER(AtomsView), ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "pmx_atoms_info_get": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AtomsInfo)]),
+    "pmx_atoms_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "pmx_atoms_gather": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     ),
     "pmx_pose_fit": (
         ctypes.c_int,

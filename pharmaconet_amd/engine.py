@@ -14,11 +14,12 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _ffi
+from .atoms import PackedAtoms
 from .constants import weights_vector
 from .library import PackedLibrary, as_packed_library
 from .validation import ENRICH_TILE, FLOAT64_REFUSED, MAX_BOOTSTRAP, MAX_COLUMNS, POISSON1_CDF64, Enrichment, cutoffs_ppm  # noqa: F401  (the table and the tile of include/pmx.h)
 
-__all__ = ["Alignment", "Attribution", "ClashReport", "DeviceLibrary", "FittingHits", "Enrichment", "Explanation", "LigandFingerprints", "PanelResult", "PoseFit", "ScreeningResult", "SimilarityResult", "align", "attribute", "clashes",
+__all__ = ["Alignment", "Attribution", "ClashReport", "DeviceAtoms", "DeviceLibrary", "FittingHits", "Enrichment", "Explanation", "LigandFingerprints", "PanelResult", "PoseFit", "ScreeningResult", "SimilarityResult", "align", "attribute", "clashes",
            "enrichment", "explain", "score_one", "screen", "screen_multi", "similar", "sweep", "topk", "device_model", "last_score_stats", "pose_fit"]
 
 
@@ -284,6 +285,103 @@ class DeviceLibrary:
             pass
 
 
+class DeviceAtoms:
+    """An atom store resident in HBM (`pmx_atoms_upload`, csrc/pmx_atoms.hip): the heavy atoms of every ligand of a library, from which
+    `clashes`, `refine` and `pose_search` take a row's points on the device (`atoms=`). The radii are `pocket.atomic_number_radii`'s, copied
+    once with the store, so a gathered radius is the bits the list-of-molecules path computes."""
+
+    def __init__(self, atoms: PackedAtoms, device=None):
+        from .pocket import atomic_number_radii
+
+        self.device = _device_index(device)
+        offsets = np.ascontiguousarray(atoms.offsets, dtype=np.uint64)
+        data = np.ascontiguousarray(atoms.data, dtype=np.uint8)
+        table = np.ascontiguousarray(atomic_number_radii(np.arange(128)), dtype=np.float32)
+        view = _ffi.AtomsView(len(atoms), offsets.ctypes.data, data.ctypes.data if data.size else None)
+        lib = _ffi.load()
+        handle = ctypes.c_void_p()
+        _ffi.check(lib.pmx_atoms_upload(ctypes.byref(view), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), self.device, ctypes.byref(handle)))
+        self.handle = handle
+        info = _ffi.AtomsInfo()
+        _ffi.check(lib.pmx_atoms_info_get(self.handle, ctypes.byref(info)))
+        self.num_ligands = int(info.n_ligands)
+        self.num_bytes = int(info.n_bytes)
+        self.max_atoms = int(info.max_atoms)
+        self.num_empty = int(info.n_empty)
+
+    def __len__(self) -> int:
+        return self.num_ligands
+
+    def gather_device(self, lig, conf, n: int):
+        """`pmx_atoms_gather` of rows (lig[i], conf[i]), device tensors (int64, int32) of this store's device, enqueued on torch's current
+        stream: (point_off int64 [n + 1], points float32 [cap, 3], radii float32 [cap], status int32 [n]) with cap = max(n * max_atoms, 1)."""
+        torch = _torch()
+        if self.handle is None:
+            raise _ffi.PmxError("this atom store was closed")
+        tdev = torch.device("cuda", self.device)
+        cap = n * self.max_atoms
+        with torch.cuda.device(tdev):
+            off = torch.empty(n + 1, dtype=torch.int64, device=tdev)
+            points = torch.empty((max(cap, 1), 3), dtype=torch.float32, device=tdev)
+            radii = torch.empty(max(cap, 1), dtype=torch.float32, device=tdev)
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=tdev)
+            stream = torch.cuda.current_stream(tdev)
+            _ffi.check(_ffi.load().pmx_atoms_gather(self.handle, lig.data_ptr(), conf.data_ptr(), n, cap, off.data_ptr(), points.data_ptr(), radii.data_ptr(), status.data_ptr(),
+                                                    ctypes.c_void_p(stream.cuda_stream)))
+        return off, points, radii, status
+
+    def gather(self, indices, conformers):
+        """The rows as host arrays, for inspection: (point_off int64 [n + 1], points float32 [total, 3], radii float32 [total], status int32 [n])."""
+        torch = _torch()
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
+        conf = np.ascontiguousarray(np.clip(np.asarray(conformers, dtype=np.int64).reshape(-1), -1, 2**31 - 1).astype(np.int32))
+        if len(idx) != len(conf):
+            raise ValueError("indices and conformers differ in length")
+        if (idx < 0).any():
+            raise ValueError("negative ligand index")
+        n = len(idx)
+        if n > _ffi.EXPLAIN_MAX:
+            raise ValueError("at most 65536 rows per gather (PMX_EXPLAIN_MAX)")
+        tdev = torch.device("cuda", self.device)
+        lig = torch.from_numpy(idx if n else np.zeros(1, np.int64)).to(tdev)
+        cf = torch.from_numpy(conf if n else np.zeros(1, np.int32)).to(tdev)
+        off, points, radii, status = self.gather_device(lig, cf, n)
+        torch.cuda.current_stream(tdev).synchronize()
+        off = off.cpu().numpy()
+        total = int(off[-1])
+        return off, points.cpu().numpy()[:total].copy(), radii.cpu().numpy()[:total].copy(), status.cpu().numpy()[:n].copy()
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            _ffi.load().pmx_atoms_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+@contextlib.contextmanager
+def _resident_atoms(atoms, device: int):
+    """A `DeviceAtoms` on `device` for a `DeviceAtoms` (as it is) or a `PackedAtoms` (uploaded for the call and freed after it)."""
+    if isinstance(atoms, DeviceAtoms):
+        if atoms.device != device:
+            raise _ffi.PmxError(f"the atom store is on device {atoms.device}, the call on {device}")
+        yield atoms
+        return
+    dat = DeviceAtoms(atoms, device)
+    try:
+        yield dat
+    finally:
+        dat.close()
+
+
+def _is_store(atoms) -> bool:
+    return isinstance(atoms, (DeviceAtoms, PackedAtoms))
+
+
 def _listed_indices(indices, tdev):
     """A list of ligand indices as a flat int64 tensor on `tdev`: a list or a NumPy array is uploaded, a device tensor stays where it is."""
     torch = _torch()
@@ -500,7 +598,10 @@ class ScreeningResult:
         best binding modes puts it: the best-scoring pose whose nodes pass, else the one of smallest overlap - which is then what `refine`
         starts from. `min_fraction` and `min_fitted` go to the search (a pose worth less than `min_fraction` of the hit's best is not
         considered). `poses` has a row for every hit that was scored; one without any pose has conformer -1 and never passes. `atoms`
-        verifies the chosen poses exactly as without the search.
+        as a function verifies the chosen poses exactly as without the search.
+        `atoms` may also be the library's atom store (a `DeviceAtoms` / `PackedAtoms`): the molecules' atoms are then taken from it on the
+        device, and with `search` the search itself chooses on the atoms (`pose_search(atoms=...)`), so that what it picks is what the
+        check accepts.
         With `fit`, `FittingHits.fit` is the `PoseFit` of every posed hit (`Alignment.pose_fit`, free mode) at the motion finally used -
         the refined one where the refinement was used; nothing else changes."""
         if k <= 0:
@@ -520,11 +621,13 @@ class ScreeningResult:
         if not 0 < pool <= 65536:
             raise ValueError("pool: 1 to 65536 hits")
         pocket = model.pocket_atoms() if pocket is None else pocket
-        with _resident(library) as dlib:
+        with contextlib.ExitStack() as stack:
+            dlib = stack.enter_context(_resident(library))
+            store = stack.enter_context(_resident_atoms(atoms, dlib.device)) if _is_store(atoms) else None  # (uploaded once for all the calls below)
             if search:
                 shared = {name: kw[name] for name in ("tolerance", "contact", "node_radius") if name in kw}
                 ms = explain_modes(model, dlib, self._best(pool), modes=search, weights=weights)
-                ps = ms.pose_search(model, dlib, pocket, weights=weights, max_clashing=max_clashing, **shared, **search_kw)
+                ps = ms.pose_search(model, dlib, pocket, weights=weights, max_clashing=max_clashing, atoms=store, **shared, **search_kw)
                 ex = ms.explanation(0)  # (the hits' scores, as without the search)
                 scored = np.flatnonzero(ps.status == 0)
                 al = ps.alignment()
@@ -533,7 +636,7 @@ class ScreeningResult:
             else:
                 ex = explain(model, dlib, self._best(pool), weights=weights)
                 al = ex.poses(model, dlib, weights=weights)
-            mols = None if atoms is None else [atoms(int(i)) for i in al.indices]
+            mols = None if atoms is None else store if store is not None else [atoms(int(i)) for i in al.indices]
             rep = al.clashes(pocket, dlib, atoms=mols, **kw)
             refined = None
             failing = ~rep.ok(max_clashing) & (al.status == 0)
@@ -1181,9 +1284,9 @@ class ModeSet:
 
 
     def pose_search(self, model, library, pocket=None, weights: dict[str, float] | None = None, max_clashing: int = 0, min_fitted: int = 1, min_fraction: float = 0.0,
-                    tolerance: float = 0.5, contact: float = 4.5, node_radius: float = 1.0, conformers: int | None = None, device=None) -> "PoseSearch":
+                    tolerance: float = 0.5, contact: float = 4.5, node_radius: float = 1.0, conformers: int | None = None, device=None, atoms=None) -> "PoseSearch":
         """`pose_search` of these rows over the modes already held: the values and keys are uploaded instead of explained again. `weights`
-        must be the ones the modes were made with (they weigh the fit)."""
+        must be the ones the modes were made with (they weigh the fit). `atoms`: the library's atom store, for the search at atom level."""
         L, CM = _MAX_LEVELS, _ffi.MAX_CONFORMERS
         n, modes = len(self), self.modes
         values = np.zeros((max(n, 1), modes, CM), np.float64)
@@ -1206,7 +1309,7 @@ class ModeSet:
                 return tuple(torch.from_numpy(np.ascontiguousarray(a[lo:hi])).to(tdev) for a in (values, match, status))
 
             return _pose_search(model, dlib, _search_pocket(model, pocket), idx, modes, weights, explained, max_clashing, min_fitted, min_fraction, tolerance, contact,
-                                node_radius, conformers)
+                                node_radius, conformers, atoms)
 
 
 def explain_modes(model, library, indices, modes: int = 4, weights: dict[str, float] | None = None, device=None, require=None, exclude=None) -> ModeSet:
@@ -1255,6 +1358,9 @@ class PoseSearch:
     status: np.ndarray
     poses: "Alignment"
     clash: "ClashReport"
+    # (no fields - what is compared field by field stays what it was: set by `pose_search(atoms=...)` on its result)
+    level = "nodes"  # "atoms": the search checked the ligands' heavy atoms, from an atom store (`pmx_pose_search_atoms`)
+    gather_status = None  # atom level: int32 [n], what the store says of the chosen row (1: it has no atoms for the hit)
 
     def __len__(self) -> int:
         return len(self.indices)
@@ -1265,7 +1371,8 @@ class PoseSearch:
         return self.poses
 
     def report(self) -> "ClashReport":
-        """The `ClashReport` of the chosen rows' pharmacophore nodes, at the search's own radius, tolerance and contact distance."""
+        """The `ClashReport` of the chosen rows' pharmacophore nodes - at level "atoms": of their heavy atoms -, at the search's own radius,
+        tolerance and contact distance."""
         return self.clash
 
     def pose_fit(self, model, library, **kw) -> "PoseFit":
@@ -1288,9 +1395,22 @@ def _search_chunks(conf: np.ndarray, modes: int):
 
 
 def _pose_search(model, dlib: "DeviceLibrary", pocket, idx: np.ndarray, modes: int, weights, explained, max_clashing, min_fitted, min_fraction, tolerance, contact,
-                 node_radius, conformers) -> PoseSearch:
+                 node_radius, conformers, atoms=None) -> PoseSearch:
     """`pose_search` on a resident library. `explained(lo, hi)` enqueues - or uploads - rows lo .. hi of the hits' `pmx_explain_modes` output
-    and returns the device tensors (values, match, status). Every chunk is enqueued before the one wait."""
+    and returns the device tensors (values, match, status). Every chunk is enqueued before the one wait. `atoms`: the library's atom store
+    (`DeviceAtoms` / `PackedAtoms`) for the search at atom level (`pmx_pose_search_atoms`)."""
+    if atoms is not None:
+        if not _is_store(atoms):
+            raise TypeError("pose_search: atoms is the library's atom store, a DeviceAtoms or a PackedAtoms")
+        with _resident_atoms(atoms, dlib.device) as dat:
+            if len(dat) != len(dlib):
+                raise ValueError(f"pose_search: an atom store of {len(dat)} ligands for a library of {len(dlib)}")
+            return _pose_search_on(model, dlib, pocket, idx, modes, weights, explained, max_clashing, min_fitted, min_fraction, tolerance, contact, node_radius, conformers, dat)
+    return _pose_search_on(model, dlib, pocket, idx, modes, weights, explained, max_clashing, min_fitted, min_fraction, tolerance, contact, node_radius, conformers, None)
+
+
+def _pose_search_on(model, dlib: "DeviceLibrary", pocket, idx: np.ndarray, modes: int, weights, explained, max_clashing, min_fitted, min_fraction, tolerance, contact,
+                    node_radius, conformers, dat: "DeviceAtoms | None") -> PoseSearch:
     torch = _torch()
     lib = _ffi.load()
     if (idx < 0).any():
@@ -1313,17 +1433,31 @@ def _pose_search(model, dlib: "DeviceLibrary", pocket, idx: np.ndarray, modes: i
         out = dict(choice=new((m, 6), i32), value=new((m, 2), f64), key=new((m, L), u8), rot=new((m, 9), f64), trans=new((m, 3), f64), fit=new((m, 8), f64),
                    node=new((m, NN), f64), count=new((m, 2), i32), levels=new((m, L), u8), summary=new((m, 4), f64), ccount=new((m, 6), i32), ppen=new((m, NN), f64),
                    patom=new((m, NN), i32), fp=new((m, _FP_WORDS), torch.int64), status=new((m,), i32))
-        row_status = [new((2, max(hi - lo, 1)), i32) for lo, hi, _ in chunks]
-        need = max([int(lib.pmx_pose_search_work_bytes(hi - lo, modes, stride)) for lo, hi, stride in chunks] + [256])
+        row_status = [new((3 if dat is not None else 2, max(hi - lo, 1)), i32) for lo, hi, _ in chunks]
+        if dat is not None:  # the clash outputs in point-mode layout, per chunk: its own offsets, and room for max_atoms points per hit
+            A = dat.max_atoms
+            del out["ppen"], out["patom"]
+            pts = [(new((hi - lo + 1,), torch.int64), new((max((hi - lo) * A, 1),), f64), new((max((hi - lo) * A, 1),), i32)) for lo, hi, _ in chunks]
+            need = max([int(lib.pmx_pose_search_atoms_work_bytes(hi - lo, modes, stride, A)) for lo, hi, stride in chunks] + [256])
+        else:
+            need = max([int(lib.pmx_pose_search_work_bytes(hi - lo, modes, stride)) for lo, hi, stride in chunks] + [256])
         work = new((need,), u8)
         centers = mh.node_centers(model)
         stream = torch.cuda.current_stream(tdev)
         keep = []
-        for (lo, hi, stride), rs in zip(chunks, row_status):
+        for k, ((lo, hi, stride), rs) in enumerate(zip(chunks, row_status)):
             lig = torch.from_numpy(np.ascontiguousarray(idx[lo:hi])).to(tdev)
             values, match, est = explained(lo, hi)
             keep.append((lig, values, match, est))
             at = lambda name: out[name][lo:].data_ptr()  # noqa: E731, B023
+            if dat is not None:
+                poff, ppen, patom = pts[k]
+                _ffi.check(lib.pmx_pose_search_atoms(mh.handle, dlib.handle, dat.handle, _weights_array(weights), centers.data_ptr(), ph.handle, lig.data_ptr(), hi - lo,
+                                                     values.data_ptr(), match.data_ptr(), est.data_ptr(), modes, stride, float(node_radius), float(tolerance), float(contact),
+                                                     int(max_clashing), int(min_fitted), float(min_fraction), at("choice"), at("value"), at("key"), at("rot"), at("trans"),
+                                                     at("fit"), at("node"), at("count"), at("levels"), at("summary"), at("ccount"), poff.data_ptr(), ppen.data_ptr(),
+                                                     patom.data_ptr(), at("fp"), at("status"), rs.data_ptr(), work.data_ptr(), need, ctypes.c_void_p(stream.cuda_stream)))
+                continue
             _ffi.check(lib.pmx_pose_search(mh.handle, dlib.handle, _weights_array(weights), centers.data_ptr(), ph.handle, lig.data_ptr(), hi - lo, values.data_ptr(),
                                            match.data_ptr(), est.data_ptr(), modes, stride, float(node_radius), float(tolerance), float(contact), int(max_clashing),
                                            int(min_fitted), float(min_fraction), at("choice"), at("value"), at("key"), at("rot"), at("trans"), at("fit"), at("node"),
@@ -1334,7 +1468,8 @@ def _pose_search(model, dlib: "DeviceLibrary", pocket, idx: np.ndarray, modes: i
     nn = _record_counts(dlib, idx, 0)
     h = {k: v.cpu().numpy()[:n] for k, v in out.items()}
     ast = np.concatenate([r.cpu().numpy()[0, : hi - lo] for (lo, hi, _), r in zip(chunks, row_status)] + [np.zeros(0, np.int32)]).astype(np.int32)
-    cst = np.concatenate([r.cpu().numpy()[1, : hi - lo] for (lo, hi, _), r in zip(chunks, row_status)] + [np.zeros(0, np.int32)]).astype(np.int32)
+    cst = np.concatenate([r.cpu().numpy()[-1, : hi - lo] for (lo, hi, _), r in zip(chunks, row_status)] + [np.zeros(0, np.int32)]).astype(np.int32)
+    gst = None if dat is None else np.concatenate([r.cpu().numpy()[1, : hi - lo] for (lo, hi, _), r in zip(chunks, row_status)] + [np.zeros(0, np.int32)]).astype(np.int32)
     ch, lv = h["choice"].astype(np.int64), h["levels"]
     nl = [int(np.count_nonzero(lv[i] != NO_LEVEL)) for i in range(n)]
     keys = []
@@ -1350,13 +1485,23 @@ def _pose_search(model, dlib: "DeviceLibrary", pocket, idx: np.ndarray, modes: i
                       rmsd_nodes=ft[:, 3].copy(), weight=ft[:, 0].copy(), sse=ft[:, 1].copy(), scale=ft[:, 4].copy(), gap=ft[:, 5].copy(),
                       node=[h["node"][i, : an[i]].copy() for i in range(n)], n_nodes=h["count"][:, 0].astype(np.int64), n_pairs=h["count"][:, 1].astype(np.int64),
                       levels=[lv[i, : nl[i]].astype(np.int64) for i in range(n)], status=ast, rows=np.arange(n, dtype=np.int64))
+    if dat is not None:
+        point_pen, point_atom = [], []
+        for (lo, hi, _), (poff, ppen, patom) in zip(chunks, pts):
+            o, pp, pa = poff.cpu().numpy(), ppen.cpu().numpy(), patom.cpu().numpy().astype(np.int64)
+            point_pen += [pp[o[i]: o[i + 1]].copy() for i in range(hi - lo)]
+            point_atom += [pa[o[i]: o[i + 1]].copy() for i in range(hi - lo)]
+    else:
+        point_pen, point_atom = [h["ppen"][i, : cn[i]].copy() for i in range(n)], [h["patom"][i, : cn[i]].astype(np.int64) for i in range(n)]
     clash = ClashReport(clearance=h["summary"][:, 0].copy(), overlap=h["summary"][:, 1].copy(), n_points=cc[:, 0].copy(), n_clashing=cc[:, 1].copy(), n_pairs=cc[:, 2].copy(),
-                        n_contacts=cc[:, 3].copy(), worst=cc[:, 4:6].copy(), point_penetration=[h["ppen"][i, : cn[i]].copy() for i in range(n)],
-                        point_atom=[h["patom"][i, : cn[i]].astype(np.int64) for i in range(n)], contact_fingerprint=h["fp"].view(np.uint64).copy(), status=cst,
-                        device=dlib.device)
-    return PoseSearch(indices=idx, modes=modes, conformer=ch[:, 0].copy(), mode=ch[:, 1].copy(), passes=ch[:, 2] != 0, n_candidates=ch[:, 3].copy(), n_passing=ch[:, 4].copy(),
+                        n_contacts=cc[:, 3].copy(), worst=cc[:, 4:6].copy(), point_penetration=point_pen, point_atom=point_atom,
+                        contact_fingerprint=h["fp"].view(np.uint64).copy(), status=cst, device=dlib.device)
+    found = PoseSearch(indices=idx, modes=modes, conformer=ch[:, 0].copy(), mode=ch[:, 1].copy(), passes=ch[:, 2] != 0, n_candidates=ch[:, 3].copy(), n_passing=ch[:, 4].copy(),
                       n_dropped=ch[:, 5].copy(), value=h["value"][:, 0].copy(), fraction=h["value"][:, 1].copy(), key=keys, status=h["status"].astype(np.int32), poses=poses,
                       clash=clash)
+    if dat is not None:
+        found.level, found.gather_status = "atoms", gst
+    return found
 
 
 def _search_pocket(model, pocket):
@@ -1369,13 +1514,16 @@ def _search_pocket(model, pocket):
 
 def pose_search(model, library, pocket, indices, modes: int = 4, weights: dict[str, float] | None = None, require=None, exclude=None, max_clashing: int = 0,
                 min_fitted: int = 1, min_fraction: float = 0.0, tolerance: float = 0.5, contact: float = 4.5, node_radius: float = 1.0,
-                conformers: int | None = None, device=None) -> PoseSearch:
+                conformers: int | None = None, device=None, atoms=None) -> PoseSearch:
     """Per hit of `indices` the conformer and binding mode that fits the pocket (`pmx_explain_modes`, then `pmx_pose_search`,
     csrc/pmx_pose_search.hip): every conformer (the first `conformers` of each, if given) under each of its `modes` (1 to 8) best modes is
     fitted (`align`) and checked against the atoms of `pocket` (a `pocket.PocketAtoms`, a model that carries its protein, or None for
     `model`'s own) as `clashes` checks pharmacophore nodes of `node_radius` at `tolerance` and `contact`. See `PoseSearch` for the choice.
     `require` / `exclude` as `explain_modes` takes them. Any number of hits: calls of at most 65536 (hit, mode, conformer) slots each, all
-    enqueued on torch's current stream of the library's device and waited for once."""
+    enqueued on torch's current stream of the library's device and waited for once.
+    With `atoms` - the library's atom store, a `DeviceAtoms` or a `PackedAtoms` - every fit is checked on the ligand's heavy atoms with
+    Bondi radii instead of its nodes (`pmx_pose_search_atoms`): `PoseSearch.level` is "atoms", `report()` the atoms' `ClashReport`, and a
+    hit the store has no atoms for gets no pose."""
     modes = int(modes)
     if not 1 <= modes <= _ffi.MAX_MODES:
         raise _ffi.PmxError(f"{modes} modes (1 to {_ffi.MAX_MODES}, PMX_MAX_MODES)")
@@ -1388,7 +1536,7 @@ def pose_search(model, library, pocket, indices, modes: int = 4, weights: dict[s
             return values, match, status
 
         return _pose_search(model, dlib, _search_pocket(model, pocket), idx, modes, weights, explained, max_clashing, min_fitted, min_fraction, tolerance, contact,
-                            node_radius, conformers)
+                            node_radius, conformers, atoms)
 
 
 @dataclass
@@ -1788,7 +1936,7 @@ class _PoseRows:
     """The rows `clashes` and `refine` share: motions and one source of points, checked and laid out as `pmx_pose_clash` and
     `pmx_pose_refine` take them. `what` names the caller in a message."""
 
-    def __init__(self, what, library, indices, conformers, rotation, translation, points, point_radii):
+    def __init__(self, what, library, indices, conformers, rotation, translation, points, point_radii, atoms=None):
         self.rot = np.ascontiguousarray(np.asarray(rotation, dtype=np.float64).reshape(-1, 3, 3))
         self.trans = np.ascontiguousarray(np.asarray(translation, dtype=np.float64).reshape(-1, 3))
         n = self.n = len(self.rot)
@@ -1797,10 +1945,16 @@ class _PoseRows:
         if n > 65536:
             raise ValueError(f"at most 65536 rows per {what} call (PMX_EXPLAIN_MAX)")
         self.node_mode = library is not None
-        if self.node_mode == (points is not None):
+        self.store = atoms  # a `DeviceAtoms` / `PackedAtoms`: point mode, the points gathered on the device
+        if atoms is not None:
+            if not _is_store(atoms):
+                raise TypeError(f"{what}: atoms is a DeviceAtoms or a PackedAtoms")
+            if self.node_mode or points is not None or point_radii is not None:
+                raise ValueError(f"{what}: a library, points or an atom store - exactly one source of points")
+        elif self.node_mode == (points is not None):
             raise ValueError(f"{what}: a library with indices and conformers, or points - one of the two")
-        self.idx = self.conf = self.off = self.flat = self.rad = None
-        if self.node_mode:
+        self.idx = self.conf = self.off = self.flat = self.rad = self.gstatus = None
+        if self.node_mode or atoms is not None:
             self.idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
             self.conf = np.ascontiguousarray(np.clip(np.asarray(conformers, dtype=np.int64).reshape(-1), -1, 2**31 - 1).astype(np.int32))
             if len(self.idx) != n or len(self.conf) != n:
@@ -1818,12 +1972,23 @@ class _PoseRows:
                 if any(len(r) != len(p) for r, p in zip(rs, pts)):
                     raise ValueError("a list of radii differs in length from its points")
 
-    def upload(self, tdev):
-        """The device tensors (kept alive by the caller) and the seven source and motion arguments that follow the pocket and the library."""
+    def upload(self, tdev, dat: "DeviceAtoms | None" = None):
+        """The device tensors (kept alive by the caller) and the seven source and motion arguments that follow the pocket and the library.
+        With an atom store (`dat`, resident on `tdev`) the points are gathered there; a row whose gather status is not OK has no points and
+        gets a motion of NaN, so that the call reports it as it reports any row that is not OK (`finish` puts the gather's status in)."""
         torch = _torch()
         n = self.n
         up = lambda a: torch.from_numpy(a).to(tdev)  # noqa: E731
         t_rot, t_trans = up(self.rot.reshape(-1, 9) if n else np.zeros((1, 9))), up(self.trans if n else np.zeros((1, 3)))
+        if dat is not None:
+            t_a, t_b = up(self.idx if n else np.zeros(1, np.int64)), up(self.conf if n else np.zeros(1, np.int32))
+            off, pts, rad, self.gstatus = dat.gather_device(t_a, t_b, n)
+            if n:
+                bad = (self.gstatus != 0)[:, None]
+                t_rot, t_trans = t_rot.masked_fill(bad, float("nan")), t_trans.masked_fill(bad, float("nan"))
+            self.slots, self._off_dev = max(n * dat.max_atoms, 1), off
+            keep, src = (t_rot, t_trans, t_a, t_b, off, pts, rad), (None, None, off.data_ptr(), pts.data_ptr(), rad.data_ptr())
+            return keep, src, (t_rot.data_ptr(), t_trans.data_ptr())
         if self.node_mode:
             t_a, t_b = up(self.idx if n else np.zeros(1, np.int64)), up(self.conf if n else np.zeros(1, np.int32))
             keep, src = (t_rot, t_trans, t_a, t_b), (t_a.data_ptr(), t_b.data_ptr(), None, None, None)
@@ -1831,6 +1996,15 @@ class _PoseRows:
             t_a, t_b, t_c = up(self.off), up(self.flat), (up(self.rad) if self.rad is not None else None)
             keep, src = (t_rot, t_trans, t_a, t_b, t_c), (None, None, t_a.data_ptr(), t_b.data_ptr(), t_c.data_ptr() if t_c is not None else None)
         return keep, src, (t_rot.data_ptr(), t_trans.data_ptr())
+
+
+    def finish(self, status: np.ndarray) -> np.ndarray:
+        """After the wait: the rows' statuses with the gather's where that is not OK, and - store mode - the offsets of the rows' points."""
+        if self.gstatus is None:
+            return status
+        self.off = self._off_dev.cpu().numpy().astype(np.int64)
+        g = self.gstatus.cpu().numpy()[: self.n].astype(np.int32)
+        return np.where(g != 0, g, status).astype(np.int32)
 
 
 def _ragged(lists, dtype, width):
@@ -1843,7 +2017,7 @@ def _ragged(lists, dtype, width):
 
 
 def clashes(pocket, library=None, indices=None, conformers=None, rotation=None, translation=None, points=None, point_radii=None, node_radius: float = 1.0,
-            tolerance: float = 0.5, contact: float = 4.5, device=None) -> ClashReport:
+            tolerance: float = 0.5, contact: float = 4.5, device=None, atoms=None) -> ClashReport:
     """Posed rows against the pocket's atoms (`pmx_pose_clash`, csrc/pmx_pocket.hip): row i is a set of points moved by `rotation[i]`
     [3, 3] and `translation[i]` [3] - what `Alignment` holds - and a pair (point, atom) clashes when the two spheres overlap by more than
     `tolerance`, touches when the centres are closer than `contact`.
@@ -1851,20 +2025,24 @@ def clashes(pocket, library=None, indices=None, conformers=None, rotation=None, 
                   library ligand indices[i] at conformer conformers[i], each a sphere of `node_radius`
       point mode  `points`: a list of [m_i, 3] arrays, any points of the conformer's frame - a whole molecule's atoms; `point_radii`: a
                   matching list of radii (`pocket.atomic_number_radii` makes them from atomic numbers), or None for `node_radius` each
-    At most 65536 rows. Runs on torch's current stream of the device and waits for it."""
+      atom store  `atoms` (a `DeviceAtoms`, or a `PackedAtoms` uploaded for the call), `indices`, `conformers`: the heavy atoms of ligand
+                  indices[i] at conformer conformers[i] with Bondi radii, gathered on the device (`pmx_atoms_gather`) - point mode without
+                  host arrays. A row the store has no atoms for (status 1), or whose conformer the record lacks (status 4), is not OK
+    Exactly one of the three. At most 65536 rows. Runs on torch's current stream of the device and waits for it."""
     torch = _torch()
     lib = _ffi.load()
-    rows = _PoseRows("clashes", library, indices, conformers, rotation, translation, points, point_radii)
+    rows = _PoseRows("clashes", library, indices, conformers, rotation, translation, points, point_radii, atoms)
     n, node_mode = rows.n, rows.node_mode
     m = max(n, 1)
     with contextlib.ExitStack() as stack:
         dlib = stack.enter_context(_resident(library, device)) if node_mode else None
-        dev = dlib.device if node_mode else _device_index(device)
+        dev = dlib.device if node_mode else atoms.device if isinstance(atoms, DeviceAtoms) else _device_index(device)
+        dat = stack.enter_context(_resident_atoms(atoms, dev)) if atoms is not None else None
         ph = device_pocket(pocket, dev)
         tdev = torch.device("cuda", dev)
         with torch.cuda.device(tdev):
-            keep, src, motion = rows.upload(tdev)
-            slots = m * _MAX_NODES if node_mode else max(int(rows.off[-1]), 1)
+            keep, src, motion = rows.upload(tdev, dat)
+            slots = m * _MAX_NODES if node_mode else rows.slots if dat is not None else max(int(rows.off[-1]), 1)
             summary = torch.empty((m, 4), dtype=torch.float64, device=tdev)
             count = torch.empty((m, 6), dtype=torch.int32, device=tdev)
             ppen = torch.empty(slots, dtype=torch.float64, device=tdev)
@@ -1877,7 +2055,7 @@ def clashes(pocket, library=None, indices=None, conformers=None, rotation=None, 
                                           ctypes.c_void_p(stream.cuda_stream)))
             stream.synchronize()
             del keep
-        st = status.cpu().numpy()[:n].astype(np.int32)
+        st = rows.finish(status.cpu().numpy()[:n].astype(np.int32))
         if node_mode:
             nn = _record_counts(dlib, rows.idx, 0)
             lo = np.arange(n, dtype=np.int64) * _MAX_NODES
@@ -1963,7 +2141,8 @@ def _heavy_atoms(atoms, conformers):
 
 def _pose_source(poses, what, pocket_or_model, library, atoms):
     """(pocket, the keyword arguments that name the points of `poses`' rows for `clashes` / `refine`): node mode with `library` alone,
-    point mode - the molecules' heavy atoms - with `atoms`."""
+    point mode - the molecules' heavy atoms - with `atoms`: a list of molecules, one per row, or the library's atom store
+    (`DeviceAtoms` / `PackedAtoms`)."""
     from .pocket import PocketAtoms
 
     pocket = pocket_or_model if isinstance(pocket_or_model, PocketAtoms) else pocket_or_model.pocket_atoms()
@@ -1973,6 +2152,8 @@ def _pose_source(poses, what, pocket_or_model, library, atoms):
         return pocket, dict(library=library, indices=poses.indices, conformers=poses.conformers)
     if poses.conformers is None:
         raise ValueError(f"{what}: these rows have no conformers to take the atoms at")
+    if _is_store(atoms):  # the rows' atoms are gathered on the device, from the store that goes with the rows' library
+        return pocket, dict(atoms=atoms, indices=poses.indices, conformers=poses.conformers)
     if len(atoms) != len(poses):
         raise ValueError(f"{len(atoms)} molecules for {len(poses)} rows")
     points, radii = _heavy_atoms(atoms, poses.conformers)
@@ -1986,10 +2167,10 @@ def _check_poses(poses, what, pocket_or_model, library, atoms, kw) -> "ClashRepo
 
 def refine(pocket, library=None, indices=None, conformers=None, rotation=None, translation=None, points=None, point_radii=None, anchors=None, anchor_targets=None,
            anchor_weights=None, node_radius: float = 1.0, tolerance: float = 0.5, restraint: float = 0.1, max_iter: int = 32, ftol: float = 1e-9,
-           device=None) -> RefinedPoses:
+           device=None, atoms=None) -> RefinedPoses:
     """Posed rows moved out of the pocket's atoms (`pmx_pose_refine`, csrc/pmx_refine.hip): per row a bounded Levenberg-Marquardt
     minimisation over the rigid motion of the overlap `clashes` reports plus `restraint` times a harmonic term that holds the row's anchors
-    where the input motion put them. Rows, points and radii as `clashes` takes them (node mode or point mode).
+    where the input motion put them. Rows, points and radii as `clashes` takes them (node mode, point mode, or an atom store `atoms`).
       anchors         None: the row's own points, each of weight 1. Otherwise a list of [k_i, 3] arrays in the conformer's frame
       anchor_targets  a matching list of [k_i, 3] float64 positions in the pocket's frame (default: the anchors under the input motion)
       anchor_weights  a matching list of [k_i] weights >= 0 (default 1 each)
@@ -2000,7 +2181,7 @@ def refine(pocket, library=None, indices=None, conformers=None, rotation=None, t
     `tolerance`, refine at a smaller one. At most 65536 rows. Runs on torch's current stream of the device and waits for it."""
     torch = _torch()
     lib = _ffi.load()
-    rows = _PoseRows("refine", library, indices, conformers, rotation, translation, points, point_radii)
+    rows = _PoseRows("refine", library, indices, conformers, rotation, translation, points, point_radii, atoms)
     n, node_mode = rows.n, rows.node_mode
     if not 0 <= int(max_iter) <= 64:
         raise ValueError("max_iter: 0 to 64 (PMX_REFINE_MAX_ITER)")
@@ -2029,11 +2210,12 @@ def refine(pocket, library=None, indices=None, conformers=None, rotation=None, t
     m = max(n, 1)
     with contextlib.ExitStack() as stack:
         dlib = stack.enter_context(_resident(library, device)) if node_mode else None
-        dev = dlib.device if node_mode else _device_index(device)
+        dev = dlib.device if node_mode else atoms.device if isinstance(atoms, DeviceAtoms) else _device_index(device)
+        dat = stack.enter_context(_resident_atoms(atoms, dev)) if atoms is not None else None
         ph = device_pocket(pocket, dev)
         tdev = torch.device("cuda", dev)
         with torch.cuda.device(tdev):
-            keep, src, motion = rows.upload(tdev)
+            keep, src, motion = rows.upload(tdev, dat)
             t_anchor = [None if a is None else torch.from_numpy(a).to(tdev) for a in (a_off, a_flat, a_tgt, a_wts)]
             rot = torch.empty((m, 3, 3), dtype=torch.float64, device=tdev)
             trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
@@ -2050,7 +2232,7 @@ def refine(pocket, library=None, indices=None, conformers=None, rotation=None, t
     return RefinedPoses(rotation=rot.cpu().numpy()[:n].copy(), translation=trans.cpu().numpy()[:n].copy(), overlap_start=en[:, 0].copy(), overlap=en[:, 2].copy(),
                         restraint_start=en[:, 1].copy(), restraint_energy=en[:, 3].copy(), anchor_rmsd=en[:, 4].copy(), angle=en[:, 5].copy(), shift=en[:, 6].copy(),
                         iterations=cn[:, 0].copy(), accepted=cn[:, 1].copy(), stop=cn[:, 2].copy(), n_pairs=cn[:, 3].copy(),
-                        status=status.cpu().numpy()[:n].astype(np.int32), indices=rows.idx.copy() if node_mode else None,
+                        status=rows.finish(status.cpu().numpy()[:n].astype(np.int32)), indices=rows.idx.copy() if node_mode else None,
                         conformers=rows.conf.astype(np.int64) if node_mode else None)
 
 

@@ -484,7 +484,7 @@ class PharmacophoreModel:
                     weight=float(al.weight[0]), sse=float(al.sse[0]), scale=float(al.scale[0]), gap=float(al.gap[0]), node=al.node[0],
                     n_nodes=int(al.n_nodes[0]), n_pairs=int(al.n_pairs[0]), levels=al.levels[0], status=int(al.status[0]))
 
-    def scoring_pose_search(self, ligand, modes: int = 4, weights: dict[str, float] | None = None, pocket=None, **kw) -> dict:
+    def scoring_pose_search(self, ligand, modes: int = 4, weights: dict[str, float] | None = None, pocket=None, level: str = "nodes", **kw) -> dict:
         """One ligand put into the pocket in the conformer and binding mode that fits it (`engine.pose_search`), the one-ligand form beside
         `scoring_pose`: every conformer under each of its `modes` best modes is fitted and checked against the protein's atoms (`pocket`, default
         `pocket_atoms()`), and the best-scoring pose that passes is returned - or, where none passes, the one of smallest overlap, the start
@@ -492,13 +492,23 @@ class PharmacophoreModel:
         `n_candidates`, `n_passing`, `value`, `fraction` (of the ligand's best leaf total), `rotation`, `translation`, `rmsd`, `rmsd_nodes`,
         `n_nodes`, `n_clashing`, `overlap`, `clearance` and `status`; conformer -1 and positions None when the ligand has no pose at all.
         Further arguments (`require`, `exclude`, `max_clashing`, `min_fitted`, `min_fraction`, `tolerance`, `contact`, `node_radius`) as
-        `engine.pose_search`. Takes what `_scoring` takes."""
+        `engine.pose_search`. Takes what `_scoring` takes. With `level="atoms"` the search checks the ligand's heavy atoms instead of its nodes
+        (`engine.pose_search(atoms=...)`; `ligand` must then carry its atoms: a `Ligand` / `LigandFeatures`); the result says which `level` it is."""
         from .engine import pose_search
         from .library import as_packed_library
 
         packed = as_packed_library(ligand)
         if len(packed) != 1:
             raise ValueError("scoring_pose_search takes exactly one ligand")
+        if level not in ("nodes", "atoms"):
+            raise ValueError("level: 'nodes' or 'atoms'")
+        if level == "atoms":
+            from .atoms import PackedAtoms
+
+            mol = getattr(ligand, "features", ligand) if not hasattr(ligand, "atom_positions") else ligand
+            if not hasattr(mol, "atom_positions"):
+                raise ValueError("scoring_pose_search(level='atoms'): the ligand has no atoms (a packed record); give the molecule")
+            kw = dict(kw, atoms=PackedAtoms.for_library([mol], packed))
         ps = pose_search(self, packed, self.pocket_atoms() if pocket is None else pocket, [0], modes=modes, weights=weights, **kw)
         if int(ps.status[0]) != 0:
             n, c, _ = packed.header(0)
@@ -511,7 +521,7 @@ class PharmacophoreModel:
         return dict(conformer=c, mode=int(ps.mode[0]), key=ps.key[0], passes=bool(ps.passes[0]), n_candidates=int(ps.n_candidates[0]), n_passing=int(ps.n_passing[0]),
                     value=float(ps.value[0]), fraction=float(ps.fraction[0]), positions=positions, node_positions=node_positions, rotation=al.rotation[0],
                     translation=al.translation[0], rmsd=float(al.rmsd[0]), rmsd_nodes=float(al.rmsd_nodes[0]), n_nodes=int(al.n_nodes[0]),
-                    n_clashing=int(rep.n_clashing[0]), overlap=float(rep.overlap[0]), clearance=float(rep.clearance[0]), status=int(al.status[0]))
+                    n_clashing=int(rep.n_clashing[0]), overlap=float(rep.overlap[0]), clearance=float(rep.clearance[0]), status=int(al.status[0]), level=ps.level)
 
     def scoring_clash(self, ligand, conformer: int | None = None, key=None, weights: dict[str, float] | None = None, pocket=None, **kw) -> dict:
         """One ligand fitted into the pocket (`scoring_pose`) and its pose checked against the protein's atoms (`engine.clashes`): the ligand's own

@@ -8,7 +8,7 @@ Output: `path,score` CSV, best first, ties in library order (`screening.py:70-75
 `--explain K --clashes PATH [--protein FILE.pdb]` checks the explained hits' poses against the protein's atoms (excluded volumes).
 `--explain K --refine_out PATH [--refine_restraint X] [--refine_iter N]` moves those poses out of the protein's atoms (restrained rigid-body refinement).
 `--explain K --pose_fit PATH [--pose_fit_mode key|free]` scores those poses in place: the overlap of the posed pharmacophore nodes with the model's hotspots (with --refine_out also at the refined motion).
-`--explain K --pose_search PATH [--pose_search_modes M] [--pose_min_fraction F]` poses every explained hit in the conformer and binding mode that fits the pocket.
+`--explain K --pose_search PATH [--pose_search_modes M] [--pose_min_fraction F] [--pose_search_level nodes|atoms]` poses every explained hit in the conformer and binding mode that fits the pocket.
 `--panel MODEL ... --panel_out PATH` scores the best hits against other pockets; `--save_top K PATH` keeps them as a packed library.
 `--actives FILE --enrichment_out PATH` validates the model retrospectively: the library's ligands named in FILE are the actives, the rest decoys.
 `--similar_to NAME ... --similar_out PATH` lists the library's ligands most similar to the named ones by their own pharmacophore fingerprints.
@@ -23,6 +23,7 @@ from pathlib import Path
 
 import numpy as np
 
+from .atoms import PackedAtoms, atoms_path
 from .library import PackedLibrary
 from .pharmacophore_model import PharmacophoreModel
 
@@ -43,10 +44,11 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--clashes", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit: its pose checked against the protein's heavy atoms (clashing points and pairs, deepest penetration, overlap, touched residues)")
         cfg.add_argument("--protein", type=str, default=None, metavar="FILE.pdb", help="with --clashes: the protein, in the model's frame (default: the protein the model carries)")
         cfg.add_argument("--clash_tolerance", type=float, default=0.5, metavar="T", help="with --clashes: overlap of two spheres, in Angstrom, that is not yet a clash")
-        cfg.add_argument("--clash_level", choices=("nodes", "atoms"), default="atoms", help="with --clashes: check the hit's pharmacophore nodes, or its heavy atoms (the hit files are read again; needs a library directory)")
+        cfg.add_argument("--clash_level", choices=("nodes", "atoms"), default="atoms", help="with --clashes: check the hit's pharmacophore nodes, or its heavy atoms (of a library directory the hit files are read again; a packed library needs its .atoms file, which --save_top writes)")
         cfg.add_argument("--refine_out", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit: its pose moved out of the protein's atoms by a restrained rigid-body refinement, checked before and after (uses --protein, --clash_tolerance and --clash_level)")
         cfg.add_argument("--pose_search", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit: the conformer and binding mode, of all its conformers and their M best modes, whose fitted pharmacophore nodes do not clash with the protein (else the one of smallest overlap), with its motion (uses --protein and --clash_tolerance)")
         cfg.add_argument("--pose_search_modes", type=int, default=4, metavar="M", help="with --pose_search: binding modes searched per conformer (1 to 8)")
+        cfg.add_argument("--pose_search_level", choices=("nodes", "atoms"), default="nodes", help="with --pose_search: choose on the fitted pharmacophore nodes, or on the hit's heavy atoms (the library's atom store: a library directory, or a .pmxlib with its .atoms file); clashing, overlap and clearance are then the atoms'")
         cfg.add_argument("--pose_min_fraction", type=float, default=0.0, metavar="F", help="with --pose_search: leave out poses whose match scores less than F (0 to 1) of the hit's best")
         cfg.add_argument("--pose_fit", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit: how well the posed pharmacophore nodes sit on the model's hotspots (Gaussian overlap, the hotspot's radius as sigma); with --refine_out a second row per hit for the refined pose")
         cfg.add_argument("--pose_fit_mode", choices=("key", "free"), default="key", help="with --pose_fit: score the pairs of the hit's explaining match (key), or every hotspot of a type the node has (free)")
@@ -95,10 +97,12 @@ def _read_file(path: str):
     return lig.answers, lig.atom_positions
 
 
-def load_library(library: Path, cpus: int, on_device: bool = False):
+def load_library(library: Path, cpus: int, on_device: bool = False, with_atoms: bool = False):
     """(names, library) of a packed library file or of a directory of molecule files (screening.py:63-68). With `on_device` the records of a
     directory are made on the GPU (`pmx_pack_features_device`) and the library returned is device-resident; the host packer takes the batch if a
-    molecule is beyond the device builder's fixed scratch, and always without `on_device` (library preparation on a host without a GPU)."""
+    molecule is beyond the device builder's fixed scratch, and always without `on_device` (library preparation on a host without a GPU).
+    With `with_atoms` a third value: the library's atom store (`atoms.PackedAtoms`) - of a directory the molecules' heavy atoms, of a packed
+    library what its `.atoms` file holds, None where there is no such file."""
     if library.is_file():
         lib = PackedLibrary.load(library)
         names_file = Path(str(library) + ".names")
@@ -108,6 +112,11 @@ def load_library(library: Path, cpus: int, on_device: bool = False):
                 raise ValueError(f"{names_file}: {len(names)} names for {len(lib)} ligands")
         else:
             names = [f"{library}#{i}" for i in range(len(lib))]
+        if with_atoms:
+            store = PackedAtoms.load(atoms_path(library)) if atoms_path(library).is_file() else None
+            if store is not None and len(store) != len(lib):
+                raise ValueError(f"{atoms_path(library)}: atoms of {len(store)} ligands for a library of {len(lib)}")
+            return names, lib, store
         return names, lib
     from .library import pack_features_native
     from .ligand import perceive_batch
@@ -134,6 +143,8 @@ def load_library(library: Path, cpus: int, on_device: bool = False):
         if st != 0:  # scored by the reference, not by this engine: reported, never silently dropped
             why = "outside the engine's structural limits (include/pmx.h)" if st == 1 else "feature graph the packer does not accept"
             print(f"warning: {f}: {why}; written with score nan", file=sys.stderr)
+    if with_atoms:
+        return [str(f) for f in file_list], lib, PackedAtoms.from_flat(flat, np.asarray(status) == 0)
     return [str(f) for f in file_list], lib
 
 
@@ -177,8 +188,12 @@ def main(argv=None) -> None:
         parser.error("--pose_min_fraction takes a number from 0 to 1")
     if args.pose_search and not np.isfinite(args.clash_tolerance):
         parser.error("--clash_tolerance takes a number")
-    if (args.clashes or args.refine_out) and args.clash_level == "atoms" and Path(args.library_dir).is_file():
-        parser.error("--clash_level atoms reads the hit files again: a packed library has none (use --clash_level nodes)")
+    packed_without_atoms = (Path(args.library_dir).is_file() or args.library_dir.endswith(".pmxlib")) and not atoms_path(args.library_dir).is_file()
+    if (args.clashes or args.refine_out) and args.clash_level == "atoms" and packed_without_atoms:
+        parser.error(f"--clash_level atoms takes the hits' atoms from {atoms_path(args.library_dir)}, which does not exist (--save_top writes it from a library directory; "
+                     "or use --clash_level nodes)")
+    if args.pose_search and args.pose_search_level == "atoms" and packed_without_atoms:
+        parser.error(f"--pose_search_level atoms takes the hits' atoms from {atoms_path(args.library_dir)}, which does not exist (--save_top writes it from a library directory)")
     if (args.clashes or args.refine_out) and not np.isfinite(args.clash_tolerance):
         parser.error("--clash_tolerance takes a number")
     if args.refine_out and not (np.isfinite(args.refine_restraint) and args.refine_restraint >= 0):
@@ -258,7 +273,14 @@ def main(argv=None) -> None:
             pocket = PocketAtoms.from_pdb(Path(args.protein), centers=model.node_centers) if args.protein else model.pocket_atoms()
         except (OSError, ValueError) as e:
             parser.error(f"{'--clashes' if args.clashes else '--refine_out' if args.refine_out else '--pose_search'}: {e}" + ("" if args.protein else " (give it with --protein FILE.pdb)"))
-    names, lib = load_library(Path(args.library_dir), args.cpus, on_device=True)
+    # the library's atom store: the check of a packed library's atoms, the atom-level search, and what --save_top keeps next to the records
+    packed = Path(args.library_dir).is_file()
+    atom_search = bool(args.pose_search) and args.pose_search_level == "atoms"
+    if atom_search or args.save_top or (packed and (args.clashes or args.refine_out) and args.clash_level == "atoms"):
+        names, lib, store = load_library(Path(args.library_dir), args.cpus, on_device=True, with_atoms=True)
+    else:
+        (names, lib), store = load_library(Path(args.library_dir), args.cpus, on_device=True), None
+    hit_atoms = store if packed else None  # (a directory's hits are read again, as before; a packed library's atoms come from its store)
     if args.actives:  # (before the screen: a name that matches nothing should not cost a pass)
         from .validation import match_actives
 
@@ -289,16 +311,17 @@ def main(argv=None) -> None:
         if args.poses:
             write_poses_csv(Path(args.poses), names, scores, status, model, lib, weight, args.explain)
         if args.clashes:
-            write_clashes_csv(Path(args.clashes), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_level, args.clash_tolerance)
+            write_clashes_csv(Path(args.clashes), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_level, args.clash_tolerance, hit_atoms)
         if args.refine_out:
             write_refine_csv(Path(args.refine_out), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_level, args.clash_tolerance,
-                             args.refine_restraint, args.refine_iter)
+                             args.refine_restraint, args.refine_iter, hit_atoms)
         if args.pose_fit:
-            refine = dict(pocket=pocket, level=args.clash_level, tolerance=args.clash_tolerance, restraint=args.refine_restraint, max_iter=args.refine_iter) if args.refine_out else None
+            refine = (dict(pocket=pocket, level=args.clash_level, tolerance=args.clash_tolerance, restraint=args.refine_restraint, max_iter=args.refine_iter, store=hit_atoms)
+                      if args.refine_out else None)
             write_pose_fit_csv(Path(args.pose_fit), names, scores, status, model, lib, weight, args.explain, args.pose_fit_mode, refine)
         if args.pose_search:
             write_pose_search_csv(Path(args.pose_search), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_tolerance, args.pose_search_modes,
-                                  args.pose_min_fraction)
+                                  args.pose_min_fraction, store if atom_search else None)
         if args.hotspots:
             write_hotspots_csv(Path(args.hotspots), names, scores, status, model, lib, weight, args.explain)
         if args.modes is not None:
@@ -315,7 +338,7 @@ def main(argv=None) -> None:
         if args.panel_out:
             write_panel_csv(Path(args.panel_out), names, scores, status, model, args.panel, dlib, weight, args.panel_k)
         if args.save_top:
-            save_top(Path(args.save_top[1]), names, scores, status, dlib, save_k)
+            save_top(Path(args.save_top[1]), names, scores, status, dlib, save_k, store)  # (a packed library's store, where it has one, goes along too)
 
 
 def write_enrichment(out: Path, result, labels: np.ndarray, cutoffs: list[float], alpha: float, bootstrap: int, seed: int) -> None:
@@ -366,14 +389,17 @@ def write_panel_csv(out: Path, names: list[str], scores: np.ndarray, status: np.
             w.write(f"{r + 1},{names[i]},{float(sc[0, r])}," + ",".join(str(float(v)) for v in sc[1:, r]) + f",{float(margin[r])}\n")
 
 
-def save_top(path: Path, names: list[str], scores: np.ndarray, status: np.ndarray, lib, k: int) -> None:
+def save_top(path: Path, names: list[str], scores: np.ndarray, status: np.ndarray, lib, k: int, store: PackedAtoms | None = None) -> None:
     """The k best hits of a screen, in the order of the main CSV, as a packed library file of their own (`DeviceLibrary.select`, read back with
-    `download`) and its `.names` file: what `--library_dir` takes for the next campaign."""
+    `download`) and its `.names` file: what `--library_dir` takes for the next campaign. With `store`, the library's atom store, the hits'
+    heavy atoms go with them as `PATH.atoms` (`PackedAtoms.select`), so that the saved library can still be checked at atom level."""
     order = _best_hits(scores, status, k)
     sub = lib.select(order)
     sub.download().save(path)
     sub.close()
     Path(str(path) + ".names").write_text("".join(f"{names[i]}\n" for i in order))
+    if store is not None:
+        store.select(order).save(atoms_path(path))
 
 
 def write_constrained_csv(out: Path, names: list[str], model, lib, weights, k: int, require, exclude) -> None:
@@ -524,17 +550,18 @@ POSE_SEARCH_HEADER = ("rank,path,conformer,mode,passes,candidates,passing,mode_s
 
 
 def write_pose_search_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, pocket, tolerance: float, modes: int,
-                          min_fraction: float) -> None:
+                          min_fraction: float, store: PackedAtoms | None = None) -> None:
     """One row per hit of the k best, in the order of the poses CSV: the hit posed where `engine.pose_search` puts it - of all its conformers
     under their `modes` best binding modes the best-scoring one whose fitted pharmacophore nodes do not clash with the protein, else the
     one of smallest overlap. The conformer and mode (-1 and -1 for a hit without any pose), whether it passes, how many candidates there
     were and how many passed, the mode's leaf total and its share of the hit's best, the clash check and the fit of the chosen pose, and
-    the motion as the poses CSV has it. Every number is the `repr` of the float64 the GPU returned."""
+    the motion as the poses CSV has it. Every number is the `repr` of the float64 the GPU returned. With `store`, the library's atom store, the
+    search chooses on the hits' heavy atoms (`--pose_search_level atoms`): the same columns, the clash values then being the atoms'."""
     from .engine import pose_search
 
     key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
     order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    ps = pose_search(model, lib, pocket, order, modes=modes, weights=weights, min_fraction=min_fraction, tolerance=tolerance)
+    ps = pose_search(model, lib, pocket, order, modes=modes, weights=weights, min_fraction=min_fraction, tolerance=tolerance, atoms=store)
     al, rep = ps.alignment(), ps.report()
     with open(out, "w") as w:
         w.write(POSE_SEARCH_HEADER + "\n")
@@ -545,7 +572,18 @@ def write_pose_search_csv(out: Path, names: list[str], scores: np.ndarray, statu
                     f"{','.join(repr(float(v)) for v in nums[2])}\n")
 
 
-def write_clashes_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, pocket, level: str, tolerance: float) -> None:
+def _hit_atoms(store, names: list[str], order: list[int], rows):
+    """What `Alignment.clashes(atoms=...)` takes for the posed hits at level `atoms`: the library's atom store where there is one (a packed
+    library: the rows' atoms are gathered on the GPU), else the hits' files, read again."""
+    if store is not None:
+        return store
+    from .ligand import Ligand
+
+    return [Ligand.load_from_file(names[order[int(row)]]) for row in rows]
+
+
+def write_clashes_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, pocket, level: str, tolerance: float,
+                      store: PackedAtoms | None = None) -> None:
     """One row per hit of the k best, in the order of the poses CSV: the pose of the hit's best conformer (`engine.align`) checked against the
     protein's heavy atoms (`engine.clashes`) - at level `nodes` the hit's pharmacophore nodes, at level `atoms` the heavy atoms of the hit's
     file, read again. Points, clashing points, clashing pairs, the deepest penetration (negative: the clearance), the overlap, the points
@@ -555,11 +593,7 @@ def write_clashes_csv(out: Path, names: list[str], scores: np.ndarray, status: n
     key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
     order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
     al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
-    atoms = None
-    if level == "atoms":
-        from .ligand import Ligand
-
-        atoms = [Ligand.load_from_file(names[order[int(row)]]) for row in al.rows]
+    atoms = _hit_atoms(store, names, order, al.rows) if level == "atoms" else None
     rep = al.clashes(pocket, lib, atoms=atoms, tolerance=tolerance)
     with open(out, "w") as w:
         w.write("rank,path,conformer,level,points,clashing,pairs,clearance,overlap,contacts,worst_point,worst_atom,residues\n")
@@ -574,7 +608,7 @@ REFINE_HEADER = ("rank,path,conformer,level,pairs_before,overlap_before,pairs_af
 
 
 def write_refine_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, pocket, level: str, tolerance: float,
-                     restraint: float, max_iter: int) -> None:
+                     restraint: float, max_iter: int, store: PackedAtoms | None = None) -> None:
     """One row per hit of the k best, in the order of the poses CSV: the pose of the hit's best conformer (`engine.align`) moved out of the
     protein's heavy atoms (`engine.refine`) - the hit's pharmacophore nodes at level `nodes`, the heavy atoms of its file at level `atoms` -
     with the check (`engine.clashes`) before and after: clashing pairs and overlap before; pairs, overlap, the deepest penetration and the
@@ -585,11 +619,7 @@ def write_refine_csv(out: Path, names: list[str], scores: np.ndarray, status: np
     key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
     order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
     al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
-    atoms = None
-    if level == "atoms":
-        from .ligand import Ligand
-
-        atoms = [Ligand.load_from_file(names[order[int(row)]]) for row in al.rows]
+    atoms = _hit_atoms(store, names, order, al.rows) if level == "atoms" else None
     before = al.clashes(pocket, lib, atoms=atoms, tolerance=tolerance)
     ref = al.refine(pocket, lib, atoms=atoms, tolerance=tolerance, restraint=restraint, max_iter=max_iter)
     after = ref.clashes(pocket, lib, atoms=atoms, tolerance=tolerance)
@@ -621,11 +651,7 @@ def write_pose_fit_csv(out: Path, names: list[str], scores: np.ndarray, status: 
     keys = keys if mode == "key" else None
     stages = [("fit", al.pose_fit(model, lib, keys=keys, weights=weights))]
     if refine is not None:
-        atoms = None
-        if refine["level"] == "atoms":
-            from .ligand import Ligand
-
-            atoms = [Ligand.load_from_file(names[order[int(row)]]) for row in al.rows]
+        atoms = _hit_atoms(refine.get("store"), names, order, al.rows) if refine["level"] == "atoms" else None
         ref = al.refine(refine["pocket"], lib, atoms=atoms, tolerance=refine["tolerance"], restraint=refine["restraint"], max_iter=refine["max_iter"])
         stages.append(("refined", ref.pose_fit(model, lib, keys=keys, weights=weights)))
     with open(out, "w") as w:
