@@ -932,6 +932,82 @@ int pmx_pose_fit(const pmx_model *model, const pmx_library *lib, const float wei
                  uint64_t *occupied_fp_dev /* [n][PMX_FINGERPRINT_WORDS] */, int32_t *status_dev, void *stream);
 
 /*
+ * Shape overlap with a known ligand (pmx_pose_shape.hip): does a posed hit fill the volume a known binder fills? Every other pose call
+ * judges a pose against the protein or the model's hotspots; this one judges it against a reference ligand in the pocket's frame: the
+ * first-order Gaussian volume overlap of Grant and Pickup (atom-centred Gaussians of amplitude p = 2 sqrt 2), the shape Tanimoto and the
+ * two Tversky fractions, nearest-atom distances both ways, and the atom-for-atom RMSD where the two atom lists are one molecule's. The
+ * pose is judged where it is: nothing is moved. The reference has no counterpart; the specification is this comment, and
+ * tests/shape_ref.py restates it in NumPy.
+ *
+ * The reference ligand: pmx_shape_ref_create copies 1 <= m <= PMX_MAX_LIGAND_ATOMS atoms - float32 positions xyz[m][3] in the pocket's
+ * frame, radii radius[m] - to `device`. Every coordinate must be finite and every radius finite and > 0: anything else is PMX_ERR_INVALID,
+ * checked on the host before anything is copied. The handle keeps the atoms widened to float64, each atom's alpha (below) and O_BB, the
+ * self-overlap of the reference: the O_AA (below) of the reference's own atoms and radii taken as a point-mode row under the identity
+ * motion, computed once at create by the kernel of pmx_pose_shape - the same term order, lane assignment and butterfly as any row, so the
+ * two are equal bit for bit. The copy and O_BB are finished when the call returns. pmx_shape_ref_self hands O_BB out;
+ * pmx_shape_ref_destroy frees the handle (NULL is allowed).
+ *
+ * Rows: the two sources of points (node mode, point mode - the three point-mode arguments are what pmx_atoms_gather writes), the posed
+ * point p_k = ((R[k][0] x_0 + R[k][1] x_1) + R[k][2] x_2) + t_k and the status rules are exactly pmx_pose_clash's, with two more rules: a
+ * row with a point whose radius is not finite or is <= 0 gets PMX_LIGAND_KEY_INVALID (node mode: point_radius; point mode:
+ * point_radius_dev[.], or point_radius where that pointer is NULL; a row without points has no such point), and a point-mode row of more
+ * than PMX_MAX_LIGAND_ATOMS points gets PMX_LIGAND_UNSUPPORTED (no row of pmx_atoms_gather is one).
+ * Arithmetic, float64 with every operation rounded (no fused multiply-add), float32 inputs widened. Constants, as literals:
+ * KAPPA = 2.4179879310247046 (pi (3 p / 4 pi)^(2/3)), PI = 3.141592653589793; p^2 is exactly 8.0.
+ *   alpha of a radius r   alpha = KAPPA / ((double)r * (double)r)
+ *   pair term             a posed point p with alpha_a, an atom (or posed point) at y with alpha_b: e = p - y;
+ *                         d2 = (e_0 e_0 + e_1 e_1) + e_2 e_2; s = alpha_a + alpha_b; q = PI / s; k = (alpha_a * alpha_b) / s;
+ *                         V = (8.0 * (q * sqrt(q))) * exp(-(k * d2))
+ *                         Everything but exp is a correctly rounded operation: a restatement differs from the device through exp alone.
+ * Per posed point a of the row:
+ *   cross_a    the sum of V over the reference atoms in ascending b
+ *   self_a     the sum of V over all points a' of the row in ascending a', a itself included (d2 = 0: the term's prefactor)
+ *   near2_a    the smallest d2 to a reference atom; point_ref[a] the lowest b that attains it; point_near[a] = sqrt(near2_a)
+ * Per reference atom b < m:
+ *   ref_near2_b  the smallest d2 over the row's points, d2 formed from e = p - y exactly as above, so that both sides see the same bits;
+ *                ref_point[b] the lowest a that attains it; ref_near[b] = sqrt(ref_near2_b). For a row without points, and for b >= m,
+ *                these are +inf and -1.
+ * Row sums: each has a lane's points (point % 64) in ascending order, the 64 lanes by the fixed butterfly (at step k = 1, 2, 4, .. 32 lanes
+ * i and i ^ k both form v_i + v_(i ^ k)):
+ *   O_AB = the sum of cross_a     O_AA = the sum of self_a     S_A = the sum of near2_a     S_B = the sum of ref_near2_b (lane b % 64)
+ *   S_O  = when the row has exactly m points, the sum of |p_a - y_a|^2, point a against reference atom a
+ * Outputs, per row:
+ *   summary_dev  double [n][10]  [0] O_AB  [1] O_AA  [2] O_BB
+ *                                [3] O_AB / ((O_AA + O_BB) - O_AB), the shape Tanimoto
+ *                                [4] O_AB / O_BB: how much of the known ligand the row fills
+ *                                [5] O_AB / O_AA: how much of the row lies inside it; 0 where O_AA is 0
+ *                                [6] sqrt(S_A / points), NaN without a point   [7] sqrt(S_B / m), +inf without a point
+ *                                [8] sqrt(S_O / m) when points == m, otherwise NaN   [9] 0
+ *   count_dev    int32 [n][4]    [0] points; [1] points with near2_a < c2; [2] reference atoms with ref_near2_b < c2; [3] m;
+ *                                c2 = (double)cover * (double)cover
+ *   point_near_dev, point_ref_dev  double / int32 in the layout of pmx_pose_clash's point_pen_dev / point_atom_dev: node mode
+ *                                [n][PMX_MAX_LIGAND_NODES] with NaN / -1 beyond the record's nodes; point mode the layout of the points
+ *   ref_near_dev  double [n][PMX_MAX_LIGAND_ATOMS]     ref_point_dev  int32 [n][PMX_MAX_LIGAND_ATOMS]
+ *   status_dev   int32 [n]
+ * A row that is not OK has NaN in all of summary, counts of 0 (all four), NaN / -1 for every point it has room for and NaN / -1 in all of
+ * its ref_near / ref_point.
+ * Three consequences are exact. (i) A row whose points are the reference's own atoms, in order, with the same radii, under the identity
+ * motion (where the posed point equals the input exactly) has O_AB == O_AA == O_BB bit for bit and therefore Tanimoto exactly 1.0, every
+ * near 0 and summary[8] == 0. (ii) One point on one reference atom gives exactly 8.0 * (q * sqrt(q)). (iii) A row far from the reference
+ * has O_AB == 0 through underflow, and Tanimoto exactly 0.
+ * The first-order overlap counts every pair once and subtracts nothing for triples, so O_AA over-counts a molecule's volume; the excess
+ * largely cancels in the three ratios and not in the absolute volumes.
+ * n <= PMX_EXPLAIN_MAX (otherwise PMX_ERR_INVALID); n = 0 succeeds and writes nothing. With n > 0 no output may be NULL. point_radius
+ * and cover must be finite, cover >= 0. In node mode the library is on the reference's device; the pointers are memory of that device.
+ * Stream-ordered (enqueued, no synchronisation), no allocation, no work buffer, no atomic: the same bits on every run, and for a row
+ * wherever it stands in a call. One wavefront per row, every pair evaluated (no cut-off by distance): points * (m + points) exp a row.
+ */
+typedef struct pmx_shape_ref pmx_shape_ref;
+int pmx_shape_ref_create(const float *xyz /* [m][3] */, const float *radius /* [m] */, uint32_t m, int device, pmx_shape_ref **out);
+int pmx_shape_ref_self(const pmx_shape_ref *ref, double *self_out);
+int pmx_shape_ref_destroy(pmx_shape_ref *ref);
+int pmx_pose_shape(const pmx_shape_ref *ref, const pmx_library *lib /* NULL in point mode */, const uint64_t *ligands_dev, const int32_t *conformer_dev /* node mode: [n] each */,
+                   const uint64_t *point_off_dev /* [n + 1] */, const float *points_dev /* [.][3] */, const float *point_radius_dev /* [.] or NULL */,
+                   const double *rot_dev /* [n][9] */, const double *trans_dev /* [n][3] */, uint32_t n, float point_radius, float cover,
+                   double *summary_dev /* [n][10] */, int32_t *count_dev /* [n][4] */, double *point_near_dev, int32_t *point_ref_dev,
+                   double *ref_near_dev /* [n][PMX_MAX_LIGAND_ATOMS] */, int32_t *ref_point_dev /* [n][PMX_MAX_LIGAND_ATOMS] */, int32_t *status_dev, void *stream);
+
+/*
  * Retrospective validation (pmx_enrich.hip): does a model, under given type weights, rank known binders above decoys? Per column of scores
  * over one labelled list, and per bootstrap resample of the list, the integers and sums from which the host derives AUROC, enrichment
  * factors and BEDROC. The specification is this comment (the reference has no counterpart); tests/enrichment_ref.py restates it in NumPy.

@@ -1,5 +1,6 @@
 // pmx_pose.h - what the kernels that pose points against the pocket share (pmx_pocket.hip: pmx_pose_clash; pmx_refine.hip:
-// pmx_pose_refine; pmx_pose_fit.hip takes the row front end, the posed point and the butterfly), so that they cannot drift: the pocket itself, where a row's points come from and which status it has (the row front
+// pmx_pose_refine; pmx_pose_fit.hip takes the row front end, the posed point and the butterfly; pmx_pose_shape.hip those and the host's
+// checks, against a reference ligand instead of the pocket), so that they cannot drift: the pocket itself, where a row's points come from and which status it has (the row front
 // end), the posed point as include/pmx.h gives it, the fixed butterfly, and the host's checks of the arguments the two calls have in common.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -116,18 +117,17 @@ __device__ __forceinline__ double wave_sum(double x) {
     return x;
 }
 
-// Host: the checks pmx_pose_clash and pmx_pose_refine share - the pocket, one source of points, the row count, the library's device - and
-// the source itself. `fn` names the caller in the message.
-inline int pose_source(const char *fn, const pmx_pocket *pocket, const pmx_library *lib, const uint64_t *ligands_dev, const int32_t *conformer_dev,
+// Host: the checks the pose calls share - one source of points, the row count, the library's device - and the source itself. `fn` names
+// the caller in the message, `owner` what the rows are judged against (the pocket, the reference) and `device` where that lives.
+inline int pose_source(const char *fn, const char *owner, int device, const pmx_library *lib, const uint64_t *ligands_dev, const int32_t *conformer_dev,
                        const uint64_t *point_off_dev, const float *points_dev, const float *point_radius_dev, const double *rot_dev, const double *trans_dev, uint32_t n,
                        PoseSource *out) {
-    if (!pocket) return pmx_fail(PMX_ERR_INVALID, "%s: null pocket", fn);
     const bool nodes = lib != nullptr, points = points_dev != nullptr || point_off_dev != nullptr || point_radius_dev != nullptr;
     if (nodes == points) return pmx_fail(PMX_ERR_INVALID, "%s: %s", fn, nodes ? "a library and points: one source of points per call" : "neither a library nor points");
     if (n > PMX_EXPLAIN_MAX) return pmx_fail(PMX_ERR_INVALID, "%s: %u rows, at most %d", fn, n, PMX_EXPLAIN_MAX);
     *out = PoseSource{};
     if (nodes) {
-        if (lib->device != pocket->device) return pmx_fail(PMX_ERR_INVALID, "%s: the pocket is on device %d, the library on %d", fn, pocket->device, lib->device);
+        if (lib->device != device) return pmx_fail(PMX_ERR_INVALID, "%s: the %s is on device %d, the library on %d", fn, owner, device, lib->device);
         out->lib_offsets = lib->offsets;
         out->lib_data = lib->data;
         out->lib_n = lib->info.n_ligands;
@@ -141,6 +141,14 @@ inline int pose_source(const char *fn, const pmx_pocket *pocket, const pmx_libra
     out->points = points_dev;
     out->point_radius = point_radius_dev;
     return PMX_OK;
+}
+
+// ... against a pocket: what pmx_pose_clash and pmx_pose_refine call.
+inline int pose_source(const char *fn, const pmx_pocket *pocket, const pmx_library *lib, const uint64_t *ligands_dev, const int32_t *conformer_dev,
+                       const uint64_t *point_off_dev, const float *points_dev, const float *point_radius_dev, const double *rot_dev, const double *trans_dev, uint32_t n,
+                       PoseSource *out) {
+    if (!pocket) return pmx_fail(PMX_ERR_INVALID, "%s: null pocket", fn);
+    return pose_source(fn, "pocket", pocket->device, lib, ligands_dev, conformer_dev, point_off_dev, points_dev, point_radius_dev, rot_dev, trans_dev, n, out);
 }
 
 } // namespace pmx

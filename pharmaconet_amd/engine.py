@@ -20,7 +20,8 @@ from .library import PackedLibrary, as_packed_library
 from .validation import ENRICH_TILE, FLOAT64_REFUSED, MAX_BOOTSTRAP, MAX_COLUMNS, POISSON1_CDF64, Enrichment, cutoffs_ppm  # noqa: F401  (the table and the tile of include/pmx.h)
 
 __all__ = ["Alignment", "Attribution", "ClashReport", "DeviceAtoms", "DeviceLibrary", "FittingHits", "Enrichment", "Explanation", "LigandFingerprints", "PanelResult", "PoseFit", "ScreeningResult", "SimilarityResult", "align", "attribute", "clashes",
-           "enrichment", "explain", "score_one", "screen", "screen_multi", "similar", "sweep", "topk", "device_model", "last_score_stats", "pose_fit"]
+           "enrichment", "explain", "score_one", "screen", "screen_multi", "similar", "sweep", "topk", "device_model", "last_score_stats", "pose_fit", "ShapeReport", "shape",
+           "device_shape_ref"]
 
 
 def _torch():
@@ -581,7 +582,7 @@ class ScreeningResult:
                            pool=idx.astype(np.uint64), profile=None)
 
     def fitting(self, k: int, pool: int | None = None, max_clashing: int = 0, pocket=None, atoms=None, model=None, library=None,
-                weights: dict[str, float] | None = None, refine: bool = False, search: int = 0, fit: bool = False, **kw) -> "FittingHits":
+                weights: dict[str, float] | None = None, refine: bool = False, search: int = 0, fit: bool = False, shape=None, **kw) -> "FittingHits":
         """The k first hits of this screen whose pose fits the pocket: the best `pool` hits (default min(len, max(8 k, 1024), 65536)) are
         explained, posed at their best conformer (`Explanation.poses`) and checked against the protein's atoms (`Alignment.clashes`); a hit
         passes with status 0 and at most `max_clashing` clashing points. In rank order; a hit that was not scored, or whose pose is not OK,
@@ -603,7 +604,13 @@ class ScreeningResult:
         device, and with `search` the search itself chooses on the atoms (`pose_search(atoms=...)`), so that what it picks is what the
         check accepts.
         With `fit`, `FittingHits.fit` is the `PoseFit` of every posed hit (`Alignment.pose_fit`, free mode) at the motion finally used -
-        the refined one where the refinement was used; nothing else changes."""
+        the refined one where the refinement was used; nothing else changes.
+        With `shape` - a `shape.ReferenceLigand`, the known binder - `FittingHits.shape` is the `ShapeReport` of every posed hit
+        (`Alignment.shape`) at the motion finally used, on the points the clash check read (the molecules' atoms with `atoms`, the nodes
+        otherwise; `shape_cover` is its `cover`); nothing else changes."""
+        shape_kw = {"cover": kw.pop("shape_cover")} if "shape_cover" in kw else {}
+        if shape_kw and shape is None:
+            raise ValueError("shape_cover: an argument of the shape report, which is off (shape=reference)")
         if k <= 0:
             raise ValueError("k must be positive")
         search = int(search)
@@ -650,9 +657,16 @@ class ScreeningResult:
                                          translation=np.where(use[:, None], refined.translation, al.translation))
                 rep = al.clashes(pocket, dlib, atoms=mols, **kw)  # (a row that was not refined has the bits it had)
             pf = al.pose_fit(model, dlib, weights=weights) if fit else None
+            sh = None
+            if shape is not None:
+                if "node_radius" in kw:
+                    shape_kw["node_radius"] = kw["node_radius"]
+                if "device" in kw:
+                    shape_kw["device"] = kw["device"]
+                sh = al.shape(shape, dlib, atoms=mols, **shape_kw)
         passing = np.flatnonzero(rep.ok(max_clashing) & (al.status == 0))[:k]
         return FittingHits(indices=al.indices[passing].astype(np.uint64), scores=ex.scores[al.rows[passing]], ranks=al.rows[passing].astype(np.int64), rows=passing,
-                           pool=ex.indices, poses=al, report=rep, refined=refined, fit=pf)
+                           pool=ex.indices, poses=al, report=rep, refined=refined, fit=pf, shape=sh)
 
     def similar_to(self, rank: int, k: int = 100, library=None) -> "SimilarityResult":
         """The library's neighbours of this screen's hit at `rank` (0 is the best hit): `similar` with that ligand as the one query,
@@ -1379,6 +1393,11 @@ class PoseSearch:
         """`pose_fit` of the chosen rows in key mode under the chosen keys: row i is hit i, a hit without a choice a row with status 4 (or 1)."""
         return self.poses.pose_fit(model, library, keys=self.key, **kw)
 
+    def shape(self, reference, library=None, atoms=None, **kw) -> "ShapeReport":
+        """`shape` of the chosen rows against a reference ligand (`Alignment.shape` of `alignment()`): row i is hit i, a hit without a
+        choice a row with status 4 (or 1)."""
+        return self.poses.shape(reference, library, atoms=atoms, **kw)
+
 
 def _search_chunks(conf: np.ndarray, modes: int):
     """(lo, hi, conf_stride) of consecutive runs of hits with (hi - lo) * modes * conf_stride <= 65536, conf_stride the most conformers
@@ -1795,6 +1814,13 @@ class Alignment:
         of matching type (free mode). Further arguments (`weights`, `centers`, `sigmas`) as `pose_fit` takes them."""
         return pose_fit(model, library, self.indices, self.conformers, self.rotation, self.translation, keys=keys, **kw)
 
+    def shape(self, reference, library=None, atoms=None, **kw) -> "ShapeReport":
+        """These poses compared with a known ligand (`shape`; `reference` a `shape.ReferenceLigand`): row i of the report is row i of the
+        alignment, and a row that is not OK passes through with status 4. The points are the rows' pharmacophore nodes with `library`
+        alone, the molecules' heavy atoms with `atoms` (per row the molecule, or the library's atom store), as `Alignment.clashes` takes
+        them. Further arguments (`node_radius`, `cover`) as `shape` takes them."""
+        return _shape_poses(self, "Alignment.shape", reference, library, atoms, kw)
+
 
 def align(model, library, indices, conformers, keys, weights: dict[str, float] | None = None, device=None) -> Alignment:
     """The rigid fit (`pmx_align`, csrc/pmx_rows.hip) of library ligand `indices[i]`'s conformer `conformers[i]` under the match `keys[i]`, rows as
@@ -1842,6 +1868,7 @@ class FittingHits:
     report: "ClashReport"
     refined: "RefinedPoses | None" = None  # `fitting(refine=True)`: the refinement of every posed hit; its motion is used where the fit failed
     fit: "PoseFit | None" = None  # `fitting(fit=True)`: the `PoseFit` (free mode) of every posed hit at the motion finally used
+    shape: "ShapeReport | None" = None  # `fitting(shape=reference)`: the `ShapeReport` of every posed hit at the motion finally used
 
     def __len__(self) -> int:
         return len(self.indices)
@@ -2070,6 +2097,137 @@ def clashes(pocket, library=None, indices=None, conformers=None, rotation=None, 
 
 
 @dataclass
+class ShapeReport:
+    """What `shape` returns: one row per posed set of points against a reference ligand (definitions: `pmx_pose_shape` in include/pmx.h).
+    Floats are float64.
+
+    overlap[i], self_overlap[i], reference_overlap[i]   O_AB, O_AA, O_BB: the first-order Gaussian overlap volumes (row with reference, row
+                    with itself, reference with itself), A^3. They over-count a molecule's volume; the ratios below largely cancel that
+    tanimoto[i]     O_AB / (O_AA + O_BB - O_AB): the shape Tanimoto, exactly 1 for the reference's own atoms in place
+    reference_fraction[i]   O_AB / O_BB: how much of the known ligand the row fills
+    fit_fraction[i]         O_AB / O_AA: how much of the row lies inside the known ligand
+    rms_to_reference[i]     the root mean square, over the row's points, of the distance to the nearest reference atom (NaN without a point)
+    rms_from_reference[i]   the same over the reference atoms, to the nearest point of the row (+inf without a point)
+    rmsd_in_order[i]        atom-for-atom RMSD, point a against reference atom a, where the row has exactly as many points as the
+                    reference has atoms - the same molecule in the same atom order - and NaN otherwise
+    n_points[i], n_covered[i], n_reference_covered[i]   points, points within `cover` of a reference atom, reference atoms within `cover`
+                    of a point
+    point_distance[i], point_reference_atom[i]   per point the distance to its nearest reference atom, and that atom
+    reference_distance[i], reference_point[i]    per reference atom the distance to the row's nearest point, and that point
+    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer of the ligand, a motion that is not
+                    finite, a radius that is not a finite number > 0); such a row has NaN, zero counts and -1"""
+
+    overlap: np.ndarray
+    self_overlap: np.ndarray
+    reference_overlap: np.ndarray
+    tanimoto: np.ndarray
+    reference_fraction: np.ndarray
+    fit_fraction: np.ndarray
+    rms_to_reference: np.ndarray
+    rms_from_reference: np.ndarray
+    rmsd_in_order: np.ndarray
+    n_points: np.ndarray
+    n_covered: np.ndarray
+    n_reference_covered: np.ndarray
+    point_distance: list
+    point_reference_atom: list
+    reference_distance: list
+    reference_point: list
+    status: np.ndarray
+
+    def __len__(self) -> int:
+        return len(self.status)
+
+
+class _ShapeRefHandle:
+    def __init__(self, reference, device: int):
+        handle = ctypes.c_void_p()
+        xyz, radius = np.ascontiguousarray(reference.xyz, dtype=np.float32), np.ascontiguousarray(reference.radius, dtype=np.float32)
+        _ffi.check(_ffi.load().pmx_shape_ref_create(xyz.ctypes.data, radius.ctypes.data, len(radius), device, ctypes.byref(handle)))
+        self.handle, self.device, self.m = handle, device, len(radius)
+
+    @property
+    def self_overlap(self) -> float:
+        out = ctypes.c_double()
+        _ffi.check(_ffi.load().pmx_shape_ref_self(self.handle, ctypes.byref(out)))
+        return out.value
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                _ffi.load().pmx_shape_ref_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def device_shape_ref(reference, device=None) -> _ShapeRefHandle:
+    """The device copy of a `shape.ReferenceLigand`, made once per (reference, device) and freed with the object."""
+    dev = _device_index(device)
+    if dev not in reference._device:
+        reference._device[dev] = _ShapeRefHandle(reference, dev)
+    return reference._device[dev]
+
+
+def shape(reference, library=None, indices=None, conformers=None, rotation=None, translation=None, points=None, point_radii=None, atoms=None,
+          node_radius: float = 1.0, cover: float = 2.0, device=None) -> ShapeReport:
+    """Posed rows against a known ligand (`pmx_pose_shape`, csrc/pmx_pose_shape.hip): row i is a set of points moved by `rotation[i]` and
+    `translation[i]` - what `Alignment` holds - and `reference` a `shape.ReferenceLigand` in the pocket's frame. The Gaussian shape overlap
+    of the two, its Tanimoto and Tversky ratios, and nearest-atom distances both ways; a point (a reference atom) is covered when its
+    nearest counterpart is closer than `cover`. The pose is judged where it is: nothing is moved. The three sources of points - node mode
+    (`library`, `indices`, `conformers`, each node a sphere of `node_radius`), point mode (`points`, `point_radii`) and the atom store
+    (`atoms`, `indices`, `conformers`) - are those of `clashes`; a row holds at most 256 points. Exactly one of the three. At most 65536
+    rows. Runs on torch's current stream of the device and waits for it."""
+    torch = _torch()
+    lib = _ffi.load()
+    rows = _PoseRows("shape", library, indices, conformers, rotation, translation, points, point_radii, atoms)
+    n, node_mode = rows.n, rows.node_mode
+    m = max(n, 1)
+    with contextlib.ExitStack() as stack:
+        dlib = stack.enter_context(_resident(library, device)) if node_mode else None
+        dev = dlib.device if node_mode else atoms.device if isinstance(atoms, DeviceAtoms) else _device_index(device)
+        dat = stack.enter_context(_resident_atoms(atoms, dev)) if atoms is not None else None
+        rh = device_shape_ref(reference, dev)
+        tdev = torch.device("cuda", dev)
+        with torch.cuda.device(tdev):
+            keep, src, motion = rows.upload(tdev, dat)
+            slots = m * _MAX_NODES if node_mode else rows.slots if dat is not None else max(int(rows.off[-1]), 1)
+            summary = torch.empty((m, 10), dtype=torch.float64, device=tdev)
+            count = torch.empty((m, 4), dtype=torch.int32, device=tdev)
+            pnear = torch.empty(slots, dtype=torch.float64, device=tdev)
+            pref = torch.empty(slots, dtype=torch.int32, device=tdev)
+            rnear = torch.empty((m, _ffi.MAX_LIGAND_ATOMS), dtype=torch.float64, device=tdev)
+            rpoint = torch.empty((m, _ffi.MAX_LIGAND_ATOMS), dtype=torch.int32, device=tdev)
+            status = torch.empty(m, dtype=torch.int32, device=tdev)
+            stream = torch.cuda.current_stream(tdev)
+            _ffi.check(lib.pmx_pose_shape(rh.handle, dlib.handle if node_mode else None, *src, *motion, n, float(node_radius), float(cover), summary.data_ptr(),
+                                          count.data_ptr(), pnear.data_ptr(), pref.data_ptr(), rnear.data_ptr(), rpoint.data_ptr(), status.data_ptr(),
+                                          ctypes.c_void_p(stream.cuda_stream)))
+            stream.synchronize()
+            del keep
+        st = rows.finish(status.cpu().numpy()[:n].astype(np.int32))
+        if node_mode:
+            nn = _record_counts(dlib, rows.idx, 0)
+            lo = np.arange(n, dtype=np.int64) * _MAX_NODES
+            hi = lo + np.where(st != 1, nn, 0)
+        else:
+            lo, hi = rows.off[:-1], rows.off[1:]
+    sm, cn = summary.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
+    pn, pr = pnear.cpu().numpy(), pref.cpu().numpy().astype(np.int64)
+    rn, rp = rnear.cpu().numpy()[:n, : rh.m], rpoint.cpu().numpy()[:n, : rh.m].astype(np.int64)
+    return ShapeReport(overlap=sm[:, 0].copy(), self_overlap=sm[:, 1].copy(), reference_overlap=sm[:, 2].copy(), tanimoto=sm[:, 3].copy(),
+                       reference_fraction=sm[:, 4].copy(), fit_fraction=sm[:, 5].copy(), rms_to_reference=sm[:, 6].copy(), rms_from_reference=sm[:, 7].copy(),
+                       rmsd_in_order=sm[:, 8].copy(), n_points=cn[:, 0].copy(), n_covered=cn[:, 1].copy(), n_reference_covered=cn[:, 2].copy(),
+                       point_distance=[pn[lo[i]: hi[i]].copy() for i in range(n)], point_reference_atom=[pr[lo[i]: hi[i]].copy() for i in range(n)],
+                       reference_distance=[rn[i].copy() for i in range(n)], reference_point=[rp[i].copy() for i in range(n)], status=st)
+
+
+def _shape_poses(poses, what, reference, library, atoms, kw) -> "ShapeReport":
+    _, source = _pose_source(poses, what, None, library, atoms)
+    return shape(reference, rotation=poses.rotation, translation=poses.translation, **source, **kw)
+
+
+@dataclass
 class RefinedPoses:
     """What `refine` returns: one row per posed set of points (definitions: `pmx_pose_refine` in include/pmx.h). Floats are float64.
 
@@ -2121,6 +2279,11 @@ class RefinedPoses:
             raise ValueError("RefinedPoses.pose_fit: these rows are points of the caller's, not ligands of a library")
         return pose_fit(model, library, self.indices, self.conformers, self.rotation, self.translation, keys=keys, **kw)
 
+    def shape(self, reference, library=None, atoms=None, **kw) -> "ShapeReport":
+        """The refined poses compared with a known ligand, as `Alignment.shape` compares the fitted ones: the rows' nodes with `library`,
+        the molecules' heavy atoms with `atoms`. A row that is not OK passes through with status 4."""
+        return _shape_poses(self, "RefinedPoses.shape", reference, library, atoms, kw)
+
 
 def _heavy_atoms(atoms, conformers):
     """Per row the heavy atoms of `atoms[i]` (a `LigandFeatures` / `Ligand`) at conformer `conformers[i]`, float32 [m_i, 3], and their
@@ -2145,7 +2308,8 @@ def _pose_source(poses, what, pocket_or_model, library, atoms):
     (`DeviceAtoms` / `PackedAtoms`)."""
     from .pocket import PocketAtoms
 
-    pocket = pocket_or_model if isinstance(pocket_or_model, PocketAtoms) else pocket_or_model.pocket_atoms()
+    # (`shape` judges the rows against a reference ligand: no pocket)
+    pocket = pocket_or_model if pocket_or_model is None or isinstance(pocket_or_model, PocketAtoms) else pocket_or_model.pocket_atoms()
     if atoms is None:
         if library is None:
             raise ValueError(f"{what}: the library the rows are ligands of, or `atoms`")

@@ -582,6 +582,48 @@ class PharmacophoreModel:
                     iterations=int(ref.iterations[0]), accepted=int(ref.accepted[0]), stop=int(ref.stop[0]), n_pairs=int(ref.n_pairs[0]), status=int(ref.status[0]),
                     ok=bool(rep.ok()[0]))
 
+    def scoring_shape(self, ligand, reference, conformer: int | None = None, key=None, refine: bool = False, weights: dict[str, float] | None = None, pocket=None,
+                      node_radius: float = 1.0, cover: float = 2.0, **kw) -> dict:
+        """One ligand fitted into the pocket (`scoring_pose`) and its pose compared with a known ligand (`engine.shape`; `reference` a
+        `shape.ReferenceLigand` in the pocket's frame), the one-ligand form beside `scoring_clash`: the ligand's own heavy atoms with Bondi
+        radii are the points when `ligand` has them (`level` "atoms"), the record's pharmacophore nodes, each of `node_radius`, otherwise
+        ("nodes"). Returns `conformer`, `key`, `rotation`, `translation`, `rmsd` of the pose, `level`, and `overlap`, `self_overlap`,
+        `reference_overlap`, `tanimoto`, `reference_fraction`, `fit_fraction`, `rms_to_reference`, `rms_from_reference`, `rmsd_in_order`,
+        `n_points`, `n_covered`, `n_reference_covered`, `point_distance`, `point_reference_atom`, `reference_distance`, `reference_point`
+        and `status`. With `refine`, the pose is also moved out of the protein's atoms (`engine.refine` on the same points; `pocket`
+        defaults to `pocket_atoms()`, further arguments as `engine.refine`) and `refined` holds the same fields for the refined motion,
+        with `refined_rotation`, `refined_translation` and `stop`."""
+        from .engine import _heavy_atoms, refine as refine_poses, shape
+        from .library import as_packed_library
+
+        pose = self.scoring_pose(ligand, weights=weights, conformer=conformer, key=key)
+        c = pose["conformer"]
+        atoms = getattr(ligand, "atom_positions", None)
+        if atoms is not None:
+            points, radii = _heavy_atoms([ligand], [c])
+            source = dict(points=points, point_radii=radii)
+        else:
+            source = dict(library=as_packed_library(ligand), indices=[0], conformers=[c])
+
+        def one(rotation, translation):
+            sh = shape(reference, rotation=[rotation], translation=[translation], node_radius=node_radius, cover=cover, **source)
+            return dict(overlap=float(sh.overlap[0]), self_overlap=float(sh.self_overlap[0]), reference_overlap=float(sh.reference_overlap[0]), tanimoto=float(sh.tanimoto[0]),
+                        reference_fraction=float(sh.reference_fraction[0]), fit_fraction=float(sh.fit_fraction[0]), rms_to_reference=float(sh.rms_to_reference[0]),
+                        rms_from_reference=float(sh.rms_from_reference[0]), rmsd_in_order=float(sh.rmsd_in_order[0]), n_points=int(sh.n_points[0]),
+                        n_covered=int(sh.n_covered[0]), n_reference_covered=int(sh.n_reference_covered[0]), point_distance=sh.point_distance[0],
+                        point_reference_atom=sh.point_reference_atom[0], reference_distance=sh.reference_distance[0], reference_point=sh.reference_point[0],
+                        status=int(sh.status[0]))
+
+        out = dict(conformer=c, key=pose["key"], rotation=pose["rotation"], translation=pose["translation"], rmsd=pose["rmsd"],
+                   level="atoms" if atoms is not None else "nodes", **one(pose["rotation"], pose["translation"]))
+        if refine:
+            ref = refine_poses(self.pocket_atoms() if pocket is None else pocket, rotation=[pose["rotation"]], translation=[pose["translation"]], node_radius=node_radius,
+                               **source, **kw)
+            out["refined"] = dict(refined_rotation=ref.rotation[0], refined_translation=ref.translation[0], stop=int(ref.stop[0]), **one(ref.rotation[0], ref.translation[0]))
+        elif kw:
+            raise ValueError(f"{sorted(kw)}: arguments of the refinement, which is off (refine=True)")
+        return out
+
     def scoring_pose_fit(self, ligand, conformer: int | None = None, key=None, refine: bool = False, free: bool = False, weights: dict[str, float] | None = None,
                          pocket=None, centers=None, sigmas=None, **kw) -> dict:
         """One ligand fitted into the pocket (`scoring_pose`) and its pose scored in place (`engine.pose_fit`): how well its pharmacophore

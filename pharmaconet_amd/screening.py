@@ -6,6 +6,7 @@ processes; needs OpenBabel like the reference) or a packed library file (`.pmxli
 `pharmaconet_amd.library`) with an optional `<library>.names` text file giving one path per ligand.
 Output: `path,score` CSV, best first, ties in library order (`screening.py:70-75`). Scoring runs on the GPU.
 `--explain K --clashes PATH [--protein FILE.pdb]` checks the explained hits' poses against the protein's atoms (excluded volumes).
+`--explain K --pose_shape PATH --shape_ref FILE.pdb` compares the explained hits' poses with a known ligand (Gaussian shape overlap).
 `--explain K --refine_out PATH [--refine_restraint X] [--refine_iter N]` moves those poses out of the protein's atoms (restrained rigid-body refinement).
 `--explain K --pose_fit PATH [--pose_fit_mode key|free]` scores those poses in place: the overlap of the posed pharmacophore nodes with the model's hotspots (with --refine_out also at the refined motion).
 `--explain K --pose_search PATH [--pose_search_modes M] [--pose_min_fraction F] [--pose_search_level nodes|atoms]` poses every explained hit in the conformer and binding mode that fits the pocket.
@@ -52,6 +53,10 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--pose_min_fraction", type=float, default=0.0, metavar="F", help="with --pose_search: leave out poses whose match scores less than F (0 to 1) of the hit's best")
         cfg.add_argument("--pose_fit", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per explained hit: how well the posed pharmacophore nodes sit on the model's hotspots (Gaussian overlap, the hotspot's radius as sigma); with --refine_out a second row per hit for the refined pose")
         cfg.add_argument("--pose_fit_mode", choices=("key", "free"), default="key", help="with --pose_fit: score the pairs of the hit's explaining match (key), or every hotspot of a type the node has (free)")
+        cfg.add_argument("--pose_shape", type=str, default=None, metavar="PATH", help="with --explain K and --shape_ref: CSV with one row per explained hit: the Gaussian shape overlap of its pose with a known ligand (overlap volume, shape Tanimoto, the fractions of the reference and of the hit that are filled, nearest-atom distances both ways); with --refine_out a second row per hit for the refined pose")
+        cfg.add_argument("--shape_ref", type=str, default=None, metavar="FILE.pdb", help="with --pose_shape: the known ligand, in the model's frame (its heavy atoms, Bondi radii)")
+        cfg.add_argument("--shape_cover", type=float, default=2.0, metavar="D", help="with --pose_shape: an atom counts as covered when its nearest counterpart is closer than D Angstrom")
+        cfg.add_argument("--shape_level", choices=("nodes", "atoms"), default="atoms", help="with --pose_shape: compare the hit's pharmacophore nodes, or its heavy atoms (where they come from: as --clash_level)")
         cfg.add_argument("--refine_restraint", type=float, default=0.1, metavar="X", help="with --refine_out: the weight of the restraint that holds the pose near its fit (uncalibrated default)")
         cfg.add_argument("--refine_iter", type=int, default=32, metavar="N", help="with --refine_out: at most N trial motions per pose (0 to 64)")
         cfg.add_argument("--hotspots", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per (explained hit, model node it has terms with): the node's share of the hit's best conformer maximum and whether the hit engages it")
@@ -180,6 +185,14 @@ def main(argv=None) -> None:
         parser.error("--pose_search needs --explain K")
     if args.pose_fit and args.explain <= 0:
         parser.error("--pose_fit needs --explain K")
+    if args.pose_shape and args.explain <= 0:
+        parser.error("--pose_shape needs --explain K")
+    if args.pose_shape and not args.shape_ref:
+        parser.error("--pose_shape needs --shape_ref FILE.pdb, the known ligand")
+    if args.shape_ref and not args.pose_shape:
+        parser.error("--shape_ref needs --pose_shape PATH")
+    if args.pose_shape and not (np.isfinite(args.shape_cover) and args.shape_cover >= 0):
+        parser.error("--shape_cover takes a distance that is not negative")
     if not (args.clashes or args.refine_out or args.pose_search) and args.protein:
         parser.error("--protein needs --clashes PATH, --refine_out PATH or --pose_search PATH")
     if args.pose_search and not 1 <= args.pose_search_modes <= 8:
@@ -192,6 +205,9 @@ def main(argv=None) -> None:
     if (args.clashes or args.refine_out) and args.clash_level == "atoms" and packed_without_atoms:
         parser.error(f"--clash_level atoms takes the hits' atoms from {atoms_path(args.library_dir)}, which does not exist (--save_top writes it from a library directory; "
                      "or use --clash_level nodes)")
+    if args.pose_shape and args.shape_level == "atoms" and packed_without_atoms:
+        parser.error(f"--shape_level atoms takes the hits' atoms from {atoms_path(args.library_dir)}, which does not exist (--save_top writes it from a library directory; "
+                     "or use --shape_level nodes)")
     if args.pose_search and args.pose_search_level == "atoms" and packed_without_atoms:
         parser.error(f"--pose_search_level atoms takes the hits' atoms from {atoms_path(args.library_dir)}, which does not exist (--save_top writes it from a library directory)")
     if (args.clashes or args.refine_out) and not np.isfinite(args.clash_tolerance):
@@ -273,10 +289,18 @@ def main(argv=None) -> None:
             pocket = PocketAtoms.from_pdb(Path(args.protein), centers=model.node_centers) if args.protein else model.pocket_atoms()
         except (OSError, ValueError) as e:
             parser.error(f"{'--clashes' if args.clashes else '--refine_out' if args.refine_out else '--pose_search'}: {e}" + ("" if args.protein else " (give it with --protein FILE.pdb)"))
+    if args.pose_shape:  # (before the screen: a reference that cannot be read should not cost a pass)
+        from .shape import ReferenceLigand
+
+        try:
+            shape_ref = ReferenceLigand.from_pdb(Path(args.shape_ref))
+        except (OSError, ValueError) as e:
+            parser.error(f"--shape_ref {args.shape_ref}: {e}")
     # the library's atom store: the check of a packed library's atoms, the atom-level search, and what --save_top keeps next to the records
     packed = Path(args.library_dir).is_file()
     atom_search = bool(args.pose_search) and args.pose_search_level == "atoms"
-    if atom_search or args.save_top or (packed and (args.clashes or args.refine_out) and args.clash_level == "atoms"):
+    if (atom_search or args.save_top or (packed and (args.clashes or args.refine_out) and args.clash_level == "atoms")
+            or (packed and args.pose_shape and args.shape_level == "atoms")):
         names, lib, store = load_library(Path(args.library_dir), args.cpus, on_device=True, with_atoms=True)
     else:
         (names, lib), store = load_library(Path(args.library_dir), args.cpus, on_device=True), None
@@ -319,6 +343,10 @@ def main(argv=None) -> None:
             refine = (dict(pocket=pocket, level=args.clash_level, tolerance=args.clash_tolerance, restraint=args.refine_restraint, max_iter=args.refine_iter, store=hit_atoms)
                       if args.refine_out else None)
             write_pose_fit_csv(Path(args.pose_fit), names, scores, status, model, lib, weight, args.explain, args.pose_fit_mode, refine)
+        if args.pose_shape:
+            refine = (dict(pocket=pocket, level=args.clash_level, tolerance=args.clash_tolerance, restraint=args.refine_restraint, max_iter=args.refine_iter, store=hit_atoms)
+                      if args.refine_out else None)
+            write_pose_shape_csv(Path(args.pose_shape), names, scores, status, model, lib, weight, args.explain, shape_ref, args.shape_level, args.shape_cover, hit_atoms, refine)
         if args.pose_search:
             write_pose_search_csv(Path(args.pose_search), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_tolerance, args.pose_search_modes,
                                   args.pose_min_fraction, store if atom_search else None)
@@ -661,6 +689,38 @@ def write_pose_fit_csv(out: Path, names: list[str], scores: np.ndarray, status: 
                 nums = ",".join(repr(float(v)) for v in (pf.fit[r], pf.ideal[r], pf.fraction[r], pf.best_fit[r], pf.best_fraction[r]))
                 w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{stage},{int(pf.n_nodes[r])},{int(pf.n_pairs[r])},{int(pf.n_in_place[r])},"
                         f"{int(pf.n_passing[r])},{nums},{';'.join(str(int(m)) for m in pf.occupied(r))}\n")
+
+
+POSE_SHAPE_HEADER = ("rank,path,conformer,stage,level,points,covered,reference_atoms,reference_covered,overlap,tanimoto,reference_fraction,fit_fraction,rms_to_reference,"
+                     "rms_from_reference")
+
+
+def write_pose_shape_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, reference, level: str, cover: float,
+                         store: PackedAtoms | None = None, refine: dict | None = None) -> None:
+    """One row per hit of the k best, in the order of the poses CSV, with stage `fit`: the pose of the hit's best conformer (`engine.align`)
+    compared with the known ligand `reference` (`engine.shape`) - at level `nodes` the hit's pharmacophore nodes, at level `atoms` its heavy
+    atoms, from where the clashes CSV takes them. Points and the points within `cover` of a reference atom, the reference's atoms and
+    those within `cover` of a point, the overlap volume, the shape Tanimoto, the fraction of the reference that is filled and of the hit that
+    lies inside it, and the root mean square nearest-atom distance both ways. With `refine` (the arguments of the refine CSV) a second row
+    per hit, stage `refined`, for the motion `engine.refine` ends at. Every float is the `repr` of the float64 the GPU returned."""
+    from .engine import explain
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
+    atoms = _hit_atoms(store, names, order, al.rows) if level == "atoms" else None
+    stages = [("fit", al.shape(reference, lib, atoms=atoms, cover=cover))]
+    if refine is not None:
+        moved = _hit_atoms(refine.get("store"), names, order, al.rows) if refine["level"] == "atoms" else None
+        ref = al.refine(refine["pocket"], lib, atoms=moved, tolerance=refine["tolerance"], restraint=refine["restraint"], max_iter=refine["max_iter"])
+        stages.append(("refined", ref.shape(reference, lib, atoms=atoms, cover=cover)))
+    with open(out, "w") as w:
+        w.write(POSE_SHAPE_HEADER + "\n")
+        for r, row in enumerate(al.rows):
+            for stage, sh in stages:
+                nums = ",".join(repr(float(v)) for v in (sh.overlap[r], sh.tanimoto[r], sh.reference_fraction[r], sh.fit_fraction[r], sh.rms_to_reference[r], sh.rms_from_reference[r]))
+                w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{stage},{level},{int(sh.n_points[r])},{int(sh.n_covered[r])},{len(reference)},"
+                        f"{int(sh.n_reference_covered[r])},{nums}\n")
 
 
 if __name__ == "__main__":
