@@ -1008,6 +1008,81 @@ int pmx_pose_shape(const pmx_shape_ref *ref, const pmx_library *lib /* NULL in p
                    double *ref_near_dev /* [n][PMX_MAX_LIGAND_ATOMS] */, int32_t *ref_point_dev /* [n][PMX_MAX_LIGAND_ATOMS] */, int32_t *status_dev, void *stream);
 
 /*
+ * Shape overlay (pmx_shape_overlay.hip): pmx_pose_shape judges a pose where it stands; these two calls move it. pmx_shape_overlay maximises
+ * a row's O_AB over its rigid motion from the motion it is given - a rigid motion changes neither O_AA nor O_BB, so that also maximises the
+ * shape Tanimoto - and pmx_shape_starts gives a row the four motions that lay its inertial frame on the reference's, so that an overlay
+ * need not start from a pose at all. Rigid only, shape only (no atom types, no hydrogens), unweighted frames, and a local maximum: the one
+ * the start leads to. The reference has no counterpart; the specification is this comment, and tests/overlay_ref.py restates it in NumPy.
+ *
+ * Rows: the sources of points (node mode, point mode, what pmx_atoms_gather writes), the pmx_shape_ref handle, the radius rules and the
+ * status rules are exactly pmx_pose_shape's. Arithmetic is float64 with every operation rounded, float32 inputs widened.
+ *
+ * pmx_shape_overlay. Evaluation at a motion (R, t): the posed points by pmx_pose_clash's formula from the stored (R, t); c = their sum (a
+ * lane's points, point % 64, ascending; the fixed butterfly; each coordinate) / the number of points, as pmx_pose_refine's. For a posed
+ * point a and a reference atom b, e, d2, k and V are exactly the pair term of the pmx_pose_shape comment, and kappa = (2.0 * k) * V. Per
+ * point, each a running sum in ascending b:
+ *   cross_a = the sum of V     f_a = the sum of kappa * e (each component)     w_a = the sum of kappa
+ * O_AB = the sum of cross_a as pmx_pose_shape sums it (a lane's points ascending, the butterfly); E = -O_AB. f_a is the exact gradient of E
+ * in p_a. With r = p_a - c and a small motion delta p = omega x r + tau, the exact gradient is g = the sum over a of [r x f_a, f_a] and the
+ * surrogate Hessian H = the sum over a of the closed-form anchor blocks of pmx_pose_refine with k = w_a: w_a (|r|^2 I - r r^T), w_a [r]_x,
+ * w_a I, formed once per point, operation for operation as there (rr = (r_0 r_0 + r_1 r_1) + r_2 r_2; w (rr - r_0 r_0); w * -(r_0 r_1);
+ * w * -r_2; .. ; g_0 = r_1 f_2 - r_2 f_1, ..), a lane's points ascending, the butterfly per value. H is positive semidefinite: it is the
+ * curvature of the quadratic that bounds -V from above at the current d2 (-exp(-k d2) is concave in d2).
+ * Iteration: pmx_pose_refine's with the same constants, on E = -O_AB:
+ *   1. evaluate at the start motion; O_AA once, from the points posed there, in pmx_pose_shape's order
+ *   2. the row has no point, or O_AB is not > 0 (a row far away: every term underflows): stop, reason 0 - the outputs are the input motion
+ *      bit for bit
+ *   3. otherwise lambda = 1e-3, and while iterations < max_iter:
+ *        solve (H + lambda diag(H_ii + 1e-9)) delta = -g by Cholesky; omega = delta[0 .. 3), tau = delta[3 .. 6)
+ *        Rd = Rodrigues of omega as in pmx_pose_refine; trial: R' = Rd R, t' = Rd (t - c) + c + tau; evaluate there; ++iterations
+ *        O_AB' > O_AB: accept, lambda = max(lambda / 4, 1e-9); if O_AB' - O_AB <= ftol * O_AB (the value before the step): stop, reason 1
+ *        otherwise: lambda *= 8; if lambda > 1e8: stop, reason 3
+ *      (a pivot that is not positive, or a delta that is not finite, is a rejected trial: an iteration without an evaluation)
+ *   4. running out of max_iter: reason 2. 0 <= max_iter <= PMX_REFINE_MAX_ITER; max_iter = 0 evaluates once and returns the start.
+ * A row that starts exactly at a maximum has g = 0 up to rounding, no trial raises O_AB, and it ends with reason 3 after about 13 rejected
+ * trials (1e-3 * 8^13 > 1e8), not with reason 1. No loop depends on convergence.
+ * Outputs, per row:
+ *   rot_out_dev, trans_out_dev   double [n][9], [n][3]: the last accepted motion
+ *   energy_dev   double [n][8]   O_AB at the start, O_AB final, O_AA, O_BB (the handle's), the Tanimoto O_AB / ((O_AA + O_BB) - O_AB) at
+ *                                the start and final, the net rotation angle from the start in rad (0 when no step was accepted),
+ *                                |c_final - c_start|
+ *   count_dev    int32 [n][4]    iterations, accepted steps, stop reason, points
+ *   status_dev   int32 [n]       PMX_LIGAND_*
+ * A row that is not OK has NaN motions and energies, counts of 0 and a stop reason of -1.
+ * Cross-checks, bit for bit: energy[0] and energy[2] are pmx_pose_shape's summary[0] and summary[1] at the input motion; energy[1] is its
+ * summary[0] at rot_out / trans_out; O_AB final is never below O_AB at the start.
+ * n <= PMX_EXPLAIN_MAX (otherwise PMX_ERR_INVALID); n = 0 succeeds and writes nothing. ftol >= 0 and finite, point_radius finite; one
+ * source of points per call; no output may be NULL. Stream-ordered (enqueued, no synchronisation), no allocation, no work buffer, no
+ * atomic: the same bits on every run, and for a row wherever it stands in a call. One wavefront per row; an evaluation is points * m exp.
+ *
+ * pmx_shape_starts. The frame of a point set - the row's unposed points, or the reference's atoms; unweighted:
+ *   centre   the sum of the points (a lane's points, index % 64, ascending; the butterfly; each coordinate) / their number
+ *   S        the six sums xx, xy, xz, yy, yz, zz of d_i d_j, d = x - centre, summed the same way
+ *   Jacobi   A = the symmetric 3 x 3 of S, V = I; PMX_SHAPE_JACOBI_SWEEPS sweeps over the pairs (p, q) = (0,1), (0,2), (1,2), r the third
+ *            index; a pair whose A_pq is exactly 0 is skipped; otherwise theta = (A_qq - A_pp) / (2.0 * A_pq);
+ *            at = |theta| + sqrt(theta * theta + 1.0); tn = 1.0 / at for theta >= 0, otherwise -1.0 / at; cc = 1.0 / sqrt(tn * tn + 1.0);
+ *            ss = tn * cc; A_pp -= tn * A_pq; A_qq += tn * A_pq (the old A_pq in both); A_pq = 0;
+ *            (A_rp, A_rq) = (cc * A_rp - ss * A_rq, ss * A_rp + cc * A_rq); every row k of V: (V_kp, V_kq) = (cc * V_kp - ss * V_kq,
+ *            ss * V_kp + cc * V_kq). Only + - * / and sqrt: a restatement has the same bits.
+ *   axes     the columns of V by descending A_ii, equal values keeping the lower index; the third axis is replaced by the cross product
+ *            of the first two, so the frame is right-handed. A set of no points has the identity frame at the origin.
+ * Start s = start_dev[i] of row i, with a_k the row's axes and centre c_A, b_k and c_B the reference's: D_0 = I, D_s the half turn about
+ * axis s - 1 (signs d = (1,1,1), (1,-1,-1), (-1,1,-1), (-1,-1,1));
+ *   R_ij = (d_0 (b_0i a_0j) + d_1 (b_1i a_1j)) + d_2 (b_2i a_2j)      t_i = c_Bi - ((R_i0 c_A0 + R_i1 c_A1) + R_i2 c_A2)
+ * frame_dev double [n][16]: the row's centre [0..3), axis k at [3 + 3 k ..), the three sorted A_ii (sums, not divided by the number) at
+ * [12..15), [15] 0. A start outside 0 .. 3 gives the row PMX_LIGAND_KEY_INVALID; a point-mode row of more than PMX_MAX_LIGAND_ATOMS points
+ * PMX_LIGAND_UNSUPPORTED; a row that is not OK has NaN in rot_out, trans_out and frame. The same limits and ordering rules as above.
+ */
+#define PMX_SHAPE_JACOBI_SWEEPS 8
+int pmx_shape_overlay(const pmx_shape_ref *ref, const pmx_library *lib /* NULL in point mode */, const uint64_t *ligands_dev, const int32_t *conformer_dev,
+                      const uint64_t *point_off_dev, const float *points_dev, const float *point_radius_dev, const double *rot_dev, const double *trans_dev,
+                      uint32_t n, float point_radius, double ftol, int max_iter, double *rot_out_dev /* [n][9] */, double *trans_out_dev /* [n][3] */,
+                      double *energy_dev /* [n][8] */, int32_t *count_dev /* [n][4] */, int32_t *status_dev, void *stream);
+int pmx_shape_starts(const pmx_shape_ref *ref, const pmx_library *lib /* NULL in point mode */, const uint64_t *ligands_dev, const int32_t *conformer_dev,
+                     const uint64_t *point_off_dev, const float *points_dev, const int32_t *start_dev /* [n] */, uint32_t n, double *rot_out_dev /* [n][9] */,
+                     double *trans_out_dev /* [n][3] */, double *frame_dev /* [n][16] */, int32_t *status_dev, void *stream);
+
+/*
  * Retrospective validation (pmx_enrich.hip): does a model, under given type weights, rank known binders above decoys? Per column of scores
  * over one labelled list, and per bootstrap resample of the list, the integers and sums from which the host derives AUROC, enrichment
  * factors and BEDROC. The specification is this comment (the reference has no counterpart); tests/enrichment_ref.py restates it in NumPy.

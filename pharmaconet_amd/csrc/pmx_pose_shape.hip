@@ -22,27 +22,23 @@
 
 #include "pmx.h"
 #include "pmx_device.h"
-#include "pmx_pose.h" // the row front end, the posed point, the butterfly and the host's checks: shared with pmx_pose_clash
-
-struct pmx_shape_ref {
-    int device = 0;
-    uint32_t m = 0;
-    double o_bb = 0.0;       // the reference's self-overlap: summary[1] of its own atoms as a row under the identity motion
-    double4 *atoms = nullptr; // [m] y widened, alpha
-};
+#include "pmx_pose.h"  // the row front end, the posed point, the butterfly and the host's checks: shared with pmx_pose_clash
+#include "pmx_shape.h" // the reference's handle, the radius rules and the pair term: shared with pmx_shape_overlay.hip
 
 namespace {
+using pmx::alpha_of;
+using pmx::dist2;
+using pmx::pair_term;
 using pmx::pose_load;
 using pmx::pose_point;
 using pmx::pose_row;
 using pmx::PoseRow;
 using pmx::PoseSource;
+using pmx::radius_ok;
 using pmx::wave_sum;
 
 constexpr int kA = PMX_MAX_LIGAND_ATOMS;
 constexpr int kWaves = 4;
-constexpr double kKappa = 2.4179879310247046;
-constexpr double kPi = 3.141592653589793;
 static_assert(kA % 64 == 0 && PMX_MAX_LIGAND_NODES <= kA, "a row's points and the reference take whole trips of the lanes; a record's nodes fit");
 
 struct ShapeArgs {
@@ -61,22 +57,6 @@ struct ShapeArgs {
     int32_t *ref_point;
     int32_t *status;
 };
-
-__host__ __device__ __forceinline__ bool radius_ok(float r) { return std::isfinite(r) && r > 0.0f; }
-__host__ __device__ __forceinline__ double alpha_of(float r) { return kKappa / ((double)r * (double)r); }
-
-__device__ __forceinline__ double dist2(const double4 &p, const double4 &y) {
-    const double e0 = p.x - y.x, e1 = p.y - y.y, e2 = p.z - y.z;
-    return (e0 * e0 + e1 * e1) + e2 * e2;
-}
-
-// The pair term of include/pmx.h.
-__device__ __forceinline__ double pair_term(double d2, double aa, double ab) {
-    const double s = aa + ab;
-    const double q = kPi / s;
-    const double k = (aa * ab) / s;
-    return (8.0 * (q * __builtin_sqrt(q))) * exp(-(k * d2));
-}
 
 __global__ __launch_bounds__(64 * kWaves) void shape_kernel(const ShapeArgs a) {
     __shared__ double4 Lref[kA];

@@ -1,0 +1,663 @@
+// pmx_shape_overlay.hip - shape overlay on gfx950: pmx_shape_overlay moves each posed row - a library ligand's nodes, or any points of the
+// caller's - by a bounded Levenberg-Marquardt maximisation of its Gaussian overlap O_AB with a known ligand over the six rigid degrees of
+// freedom; pmx_shape_starts gives a row the four motions that lay its inertial frame on the reference's, so that an overlay need not start
+// from a pose. The definitions are the comment of include/pmx.h; tests/overlay_ref.py restates them.
+//
+// overlay_kernel - one wavefront per row, kWaves per block.
+//   LDS       the reference (32 bytes an atom, at most 8 KB) staged once by the block; per wavefront its row's unposed points, widened, with
+//             their alphas (X, at most 8 KB) and the points posed at the input motion (P, at most 8 KB; read once, for O_AA): 72 KB a
+//             block. One barrier, after the staging; every wavefront of the block reaches it. After it the LDS is only read.
+//   evaluate  at a motion (R, t), two passes of the wave over X:
+//     centroid  a lane per point in trips of 64, posed as pmx_pose_clash poses it; the lanes' sums by the fixed butterfly
+//     pairs     a lane per point walks the reference in ascending b - a broadcast read - for cross, f (3 values) and w: one exp and a
+//               handful of multiply-adds a pair. The point's block of H (15 values that are not 0 by structure) and g (6) is formed once
+//               per point, the closed form in r = p - c
+//   reduce    O_AB, H, g: one butterfly each - the same bits in every lane afterwards
+//   solve     the 6x6 Cholesky, Rodrigues and the decision are computed by all lanes alike; every branch is taken through readfirstlane
+// The solve and Rodrigues are copies of pmx_refine.hip's: that unit's kernel is held to bit-level identities and a register table, and a
+// shared header would have rebuilt it. H, g and the motions are named by constant indices only: registers, no scratch.
+//
+// starts_kernel - one wavefront per row, no LDS: the lanes' sums of the row's unposed points and of the reference's atoms, the butterfly,
+// then the 3x3 Jacobi in every lane alike.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "pmx.h"
+#include "pmx_device.h"
+#include "pmx_pose.h"
+#include "pmx_shape.h"
+
+namespace {
+using pmx::alpha_of;
+using pmx::dist2;
+using pmx::pair_term;
+using pmx::pose_load;
+using pmx::pose_point;
+using pmx::pose_row;
+using pmx::PoseRow;
+using pmx::PoseSource;
+using pmx::radius_ok;
+using pmx::wave_sum;
+
+constexpr int kA = PMX_MAX_LIGAND_ATOMS;
+constexpr int kWaves = 4;
+static_assert(kA % 64 == 0 && PMX_MAX_LIGAND_NODES <= kA, "a row's points take whole trips of the lanes; a record's nodes fit");
+
+struct OverlayArgs {
+    const double4 *ref;
+    uint32_t m;
+    double o_bb;
+    PoseSource src;
+    const double *rot, *trans;
+    uint32_t n;
+    float radius;
+    double ftol;
+    int max_iter;
+    double *rot_out, *trans_out, *energy;
+    int32_t *count, *status;
+};
+
+struct StartsArgs {
+    const double4 *ref;
+    uint32_t m;
+    PoseSource src;
+    const int32_t *start;
+    uint32_t n;
+    double *rot_out, *trans_out, *frame;
+    int32_t *status;
+};
+
+__device__ __forceinline__ bool uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
+
+// index of H(i, j), i <= j, in the 21 values of the upper triangle
+__host__ __device__ constexpr int hidx(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
+
+struct Eval {
+    double oab;
+    double c[3];
+    double H[21], g[6];
+};
+
+// O_AB, c, H and g at (R, t). X: the row's unposed points with their alphas; Lref: the reference.
+__device__ __forceinline__ void evaluate(const double4 *X, uint32_t npts, const double4 *Lref, uint32_t m, const double (&R)[9], const double (&t)[3], int lane, Eval &e) {
+    // ---- the centroid of the posed points
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (uint32_t base = 0; base < npts; base += 64) {
+        const uint32_t u = base + (uint32_t)lane;
+        if (u < npts) {
+            const double4 x = X[u];
+            double p0, p1, p2;
+            pose_point(R, t, x.x, x.y, x.z, p0, p1, p2);
+            s0 += p0;
+            s1 += p1;
+            s2 += p2;
+        }
+    }
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    const double c0 = npts ? s0 / (double)npts : 0.0, c1 = npts ? s1 / (double)npts : 0.0, c2 = npts ? s2 / (double)npts : 0.0;
+    e.c[0] = c0;
+    e.c[1] = c1;
+    e.c[2] = c2;
+
+    // ---- pairs, and each point's block. (H(0,3), H(1,4), H(2,5), H(3,4), H(3,5) and H(4,5) are 0 by structure)
+    double sAB = 0.0;
+    double h00 = 0.0, h01 = 0.0, h02 = 0.0, h11 = 0.0, h12 = 0.0, h22 = 0.0, h04 = 0.0, h05 = 0.0, h13 = 0.0, h15 = 0.0, h23 = 0.0, h24 = 0.0, hw = 0.0;
+    double g0 = 0.0, g1 = 0.0, g2 = 0.0, g3 = 0.0, g4 = 0.0, g5 = 0.0;
+    for (uint32_t base = 0; base < npts; base += 64) {
+        const uint32_t u = base + (uint32_t)lane;
+        if (u < npts) {
+            const double4 x = X[u];
+            double4 p;
+            pose_point(R, t, x.x, x.y, x.z, p.x, p.y, p.z);
+            p.w = x.w;
+            double cross = 0.0, f0 = 0.0, f1 = 0.0, f2 = 0.0, w = 0.0;
+            for (uint32_t b = 0; b < m; ++b) {
+                const double4 y = Lref[b];
+                const double e0 = p.x - y.x, e1 = p.y - y.y, e2 = p.z - y.z;
+                const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+                double k;
+                const double V = pair_term(d2, p.w, y.w, k);
+                const double kappa = (2.0 * k) * V;
+                cross = cross + V;
+                f0 = f0 + kappa * e0;
+                f1 = f1 + kappa * e1;
+                f2 = f2 + kappa * e2;
+                w = w + kappa;
+            }
+            sAB = sAB + cross;
+            const double r0 = p.x - c0, r1 = p.y - c1, r2 = p.z - c2;
+            const double rr = (r0 * r0 + r1 * r1) + r2 * r2;
+            h00 += w * (rr - r0 * r0);
+            h01 += w * -(r0 * r1);
+            h02 += w * -(r0 * r2);
+            h11 += w * (rr - r1 * r1);
+            h12 += w * -(r1 * r2);
+            h22 += w * (rr - r2 * r2);
+            h04 += w * -r2;
+            h05 += w * r1;
+            h13 += w * r2;
+            h15 += w * -r0;
+            h23 += w * -r1;
+            h24 += w * r0;
+            hw += w;
+            g0 += r1 * f2 - r2 * f1;
+            g1 += r2 * f0 - r0 * f2;
+            g2 += r0 * f1 - r1 * f0;
+            g3 += f0;
+            g4 += f1;
+            g5 += f2;
+        }
+    }
+
+    // ---- the row
+    e.oab = wave_sum(sAB);
+#pragma unroll
+    for (int k = 0; k < 21; ++k) e.H[k] = 0.0;
+    e.H[hidx(0, 0)] = wave_sum(h00);
+    e.H[hidx(0, 1)] = wave_sum(h01);
+    e.H[hidx(0, 2)] = wave_sum(h02);
+    e.H[hidx(1, 1)] = wave_sum(h11);
+    e.H[hidx(1, 2)] = wave_sum(h12);
+    e.H[hidx(2, 2)] = wave_sum(h22);
+    e.H[hidx(0, 4)] = wave_sum(h04);
+    e.H[hidx(0, 5)] = wave_sum(h05);
+    e.H[hidx(1, 3)] = wave_sum(h13);
+    e.H[hidx(1, 5)] = wave_sum(h15);
+    e.H[hidx(2, 3)] = wave_sum(h23);
+    e.H[hidx(2, 4)] = wave_sum(h24);
+    e.H[hidx(3, 3)] = e.H[hidx(4, 4)] = e.H[hidx(5, 5)] = wave_sum(hw);
+    e.g[0] = wave_sum(g0);
+    e.g[1] = wave_sum(g1);
+    e.g[2] = wave_sum(g2);
+    e.g[3] = wave_sum(g3);
+    e.g[4] = wave_sum(g4);
+    e.g[5] = wave_sum(g5);
+}
+
+// (H + lambda diag(H_ii + 1e-9)) delta = -g by Cholesky; false when a pivot is not positive. (pmx_refine.hip's, operation for operation)
+__device__ __forceinline__ bool solve(const double (&H)[21], const double (&g)[6], double lambda, double (&x)[6]) {
+    double L[21]; // L(i, j), j <= i, at hidx(j, i)
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double s = H[hidx(j, j)] + lambda * (H[hidx(j, j)] + 1e-9);
+#pragma unroll
+        for (int k = 0; k < j; ++k) s -= L[hidx(k, j)] * L[hidx(k, j)];
+        ok = ok && s > 0.0;
+        const double ljj = __builtin_sqrt(s);
+        L[hidx(j, j)] = ljj;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double v = H[hidx(j, i)];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v -= L[hidx(k, i)] * L[hidx(k, j)];
+            L[hidx(j, i)] = v / ljj;
+        }
+    }
+    double y[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double v = -g[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) v -= L[hidx(k, i)] * y[k];
+        y[i] = v / L[hidx(i, i)];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double v = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) v -= L[hidx(i, k)] * x[k];
+        x[i] = v / L[hidx(i, i)];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) ok = ok && std::isfinite(x[i]);
+    return ok;
+}
+
+// Rodrigues of omega: I + (sin th / th) K + (2 sin^2(th / 2) / th^2) K^2, K = [omega]_x, K^2 = omega omega^T - th^2 I.
+__device__ __forceinline__ void rodrigues(double w0, double w1, double w2, double (&Rd)[9]) {
+    const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
+    const double th = __builtin_sqrt(th2);
+    double sa = 1.0, sb = 0.5;
+    if (th > 0.0) {
+        const double sh = sin(0.5 * th);
+        sa = sin(th) / th;
+        sb = ((2.0 * sh) * sh) / (th * th);
+    }
+    const double w[3] = {w0, w1, w2};
+    const double K[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Rd[3 * i + j] = (i == j ? 1.0 : 0.0) + (sa * K[3 * i + j] + sb * (w[i] * w[j] - (i == j ? th2 : 0.0)));
+}
+
+__device__ __forceinline__ double tanimoto(double oab, double oaa, double obb) { return oab / ((oaa + obb) - oab); }
+
+__global__ __launch_bounds__(64 * kWaves) void overlay_kernel(const OverlayArgs a) {
+    __shared__ double4 Lref[kA];
+    __shared__ double4 Lx[kWaves][kA];
+    __shared__ double4 Lp[kWaves][kA];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
+    const uint32_t row = blockIdx.x * kWaves + (uint32_t)wave;
+    const bool live = row < a.n;
+    const int lane = (int)(threadIdx.x % 64);
+    const double nan = __builtin_nan("");
+
+    for (uint32_t b = threadIdx.x; b < a.m; b += 64 * kWaves) Lref[b] = a.ref[b];
+
+    // ---- the row's points: unposed with their alphas, and posed at the input motion
+    double R0[9], t0[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R0[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t0[k] = 0.0;
+    int status = PMX_LIGAND_OK;
+    uint32_t npts = 0;
+    double4 *X = Lx[wave], *P = Lp[wave];
+    if (live) {
+        bool finite = true;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            R0[k] = a.rot[(size_t)row * 9 + k];
+            finite = finite && std::isfinite(R0[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            t0[k] = a.trans[(size_t)row * 3 + k];
+            finite = finite && std::isfinite(t0[k]);
+        }
+        const PoseRow pr = pose_row(a.src, row, finite);
+        status = pr.status;
+        npts = pr.npts;
+        if (npts > (uint32_t)kA) { // (more points than a molecule of the atom store can have: nothing of the row is staged)
+            status = PMX_LIGAND_UNSUPPORTED;
+            npts = 0;
+        }
+        bool bad = false;
+        for (uint32_t base = 0; base < npts; base += 64) {
+            const uint32_t u = base + (uint32_t)lane;
+            if (u < npts) {
+                double x0, x1, x2, p0, p1, p2;
+                pose_load(pr, u, x0, x1, x2);
+                pose_point(R0, t0, x0, x1, x2, p0, p1, p2);
+                const float r = pr.radii ? pr.radii[u] : a.radius;
+                bad = bad || !radius_ok(r);
+                const double al = alpha_of(r);
+                X[u] = make_double4(x0, x1, x2, al);
+                P[u] = make_double4(p0, p1, p2, al);
+            }
+        }
+        if (__ballot(bad) != 0ull) {
+            status = PMX_LIGAND_KEY_INVALID;
+            npts = 0;
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+
+    if (status != PMX_LIGAND_OK) {
+        if (lane < 9) a.rot_out[(size_t)row * 9 + lane] = nan;
+        if (lane < 3) a.trans_out[(size_t)row * 3 + lane] = nan;
+        if (lane < 8) a.energy[(size_t)row * 8 + lane] = nan;
+        if (lane < 4) a.count[(size_t)row * 4 + lane] = lane == 2 ? -1 : 0;
+        if (lane == 0) a.status[row] = status;
+        return;
+    }
+    const uint32_t m = a.m;
+
+    // ---- O_AA, once, of the points posed at the input motion: pmx_pose_shape's terms in its order
+    double sAA = 0.0;
+    for (uint32_t base = 0; base < npts; base += 64) {
+        const uint32_t u = base + (uint32_t)lane;
+        if (u < npts) {
+            const double4 p = P[u];
+            double self = 0.0;
+            for (uint32_t v = 0; v < npts; ++v) {
+                const double4 q = P[v];
+                self = self + pair_term(dist2(p, q), p.w, q.w);
+            }
+            sAA = sAA + self;
+        }
+    }
+    const double oaa = wave_sum(sAA);
+
+    // ---- the iteration. `cur` is the last accepted evaluation, at (R, t); a trial is evaluated at (Rt, tt)
+    double R[9], t[3], Rt[9], tt[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = Rt[k] = R0[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = tt[k] = t0[k];
+    Eval cur, tr;
+    evaluate(X, npts, Lref, m, R, t, lane, cur);
+    const double o_start = cur.oab;
+    const double cs0 = cur.c[0], cs1 = cur.c[1], cs2 = cur.c[2];
+    double O = cur.oab;
+    double lambda = 1e-3;
+    int iterations = 0, accepted = 0, reason = 2;
+    if (uniform(npts == 0 || !(O > 0.0))) { // (no point, or a row so far away that every term underflows: nothing to follow)
+        reason = 0;
+    } else {
+        while (uniform(iterations < a.max_iter)) {
+            double delta[6];
+            if (!uniform(solve(cur.H, cur.g, lambda, delta))) { // (a pivot that is not positive: a rejected trial without an evaluation)
+                ++iterations;
+                lambda *= 8.0;
+                if (uniform(lambda > 1e8)) {
+                    reason = 3;
+                    break;
+                }
+                continue;
+            }
+            double Rd[9];
+            rodrigues(delta[0], delta[1], delta[2], Rd);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) Rt[3 * i + j] = (Rd[3 * i] * R[j] + Rd[3 * i + 1] * R[3 + j]) + Rd[3 * i + 2] * R[6 + j];
+            }
+            {
+                const double w0 = t[0] - cur.c[0], w1 = t[1] - cur.c[1], w2 = t[2] - cur.c[2];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) tt[i] = (((Rd[3 * i] * w0 + Rd[3 * i + 1] * w1) + Rd[3 * i + 2] * w2) + cur.c[i]) + delta[3 + i];
+            }
+            evaluate(X, npts, Lref, m, Rt, tt, lane, tr);
+            ++iterations;
+            const double Ot = tr.oab;
+            if (uniform(Ot > O)) { // (E' < E, E = -O_AB)
+                const double before = O;
+                ++accepted;
+                cur = tr;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) R[k] = Rt[k];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) t[k] = tt[k];
+                O = Ot;
+                lambda = fmax(lambda / 4.0, 1e-9);
+                if (uniform(Ot - before <= a.ftol * before)) {
+                    reason = 1;
+                    break;
+                }
+            } else {
+                lambda *= 8.0;
+                if (uniform(lambda > 1e8)) {
+                    reason = 3;
+                    break;
+                }
+            }
+        }
+    }
+
+    // ---- the row's outputs: the last accepted motion (the input's own bits when nothing was accepted)
+    // net rotation from the start: Q = R R0^T, angle = atan2(|vee(Q - Q^T)| / 2, (tr Q - 1) / 2)
+    double Q[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Q[3 * i + j] = (R[3 * i] * R0[3 * j] + R[3 * i + 1] * R0[3 * j + 1]) + R[3 * i + 2] * R0[3 * j + 2];
+    }
+    const double a0 = Q[7] - Q[5], a1 = Q[2] - Q[6], a2 = Q[3] - Q[1];
+    const double sn = 0.5 * __builtin_sqrt((a0 * a0 + a1 * a1) + a2 * a2), cs = 0.5 * (((Q[0] + Q[4]) + Q[8]) - 1.0);
+    const double angle = accepted ? atan2(sn, cs) : 0.0;
+    const double h0 = cur.c[0] - cs0, h1 = cur.c[1] - cs1, h2 = cur.c[2] - cs2;
+    const double shift = __builtin_sqrt((h0 * h0 + h1 * h1) + h2 * h2);
+    double out = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out = lane == k ? R[k] : out;
+    if (lane < 9) a.rot_out[(size_t)row * 9 + lane] = out;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out = lane == k ? t[k] : out;
+    if (lane < 3) a.trans_out[(size_t)row * 3 + lane] = out;
+    const double obb = a.o_bb;
+    const double en[8] = {o_start, O, oaa, obb, tanimoto(o_start, oaa, obb), tanimoto(O, oaa, obb), angle, shift};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) out = lane == k ? en[k] : out;
+    if (lane < 8) a.energy[(size_t)row * 8 + lane] = out;
+    if (lane < 4) a.count[(size_t)row * 4 + lane] = lane == 0 ? iterations : lane == 1 ? accepted : lane == 2 ? reason : (int)npts;
+    if (lane == 0) a.status[row] = status;
+}
+
+// ---- inertial frames
+
+struct Frame {
+    double c[3];
+    double ax[9]; // axis k at ax[3 k ..]
+    double ev[3];
+};
+
+// The frame from a set's centre and its six sums of centred products (xx, xy, xz, yy, yz, zz): the cyclic Jacobi of include/pmx.h.
+__device__ __forceinline__ void jacobi_frame(uint32_t count, double c0, double c1, double c2, const double (&S)[6], Frame &f) {
+    double A[3][3] = {{S[0], S[1], S[2]}, {S[1], S[3], S[4]}, {S[2], S[4], S[5]}};
+    double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    if (count < 1) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) A[i][j] = 0.0;
+        c0 = c1 = c2 = 0.0;
+    }
+#pragma unroll 1
+    for (int sweep = 0; sweep < PMX_SHAPE_JACOBI_SWEEPS; ++sweep) {
+#pragma unroll
+        for (int pair = 0; pair < 3; ++pair) {
+            const int p = pair == 2 ? 1 : 0, q = pair == 0 ? 1 : 2, r = 3 - p - q;
+            const double apq = A[p][q];
+            if (apq != 0.0) {
+                const double app = A[p][p], aqq = A[q][q];
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double at = __builtin_fabs(theta) + __builtin_sqrt(theta * theta + 1.0);
+                const double tn = theta >= 0.0 ? 1.0 / at : -1.0 / at;
+                const double cc = 1.0 / __builtin_sqrt(tn * tn + 1.0);
+                const double ss = tn * cc;
+                A[p][p] = app - tn * apq;
+                A[q][q] = aqq + tn * apq;
+                A[p][q] = A[q][p] = 0.0;
+                const double arp = A[r][p], arq = A[r][q];
+                A[r][p] = A[p][r] = cc * arp - ss * arq;
+                A[r][q] = A[q][r] = ss * arp + cc * arq;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const double vkp = V[k][p], vkq = V[k][q];
+                    V[k][p] = cc * vkp - ss * vkq;
+                    V[k][q] = ss * vkp + cc * vkq;
+                }
+            }
+        }
+    }
+    // descending eigenvalue, equal values keeping the lower index: the place of column i
+    const double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2];
+    const int k0 = (int)(e1 > e0) + (int)(e2 > e0);
+    const int k1 = (int)(e0 >= e1) + (int)(e2 > e1);
+    // (column 2 takes the place that is left)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        // (selects, no indexing by a variable: registers)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) f.ax[3 * k + j] = k0 == k ? V[j][0] : k1 == k ? V[j][1] : V[j][2];
+        f.ev[k] = k0 == k ? e0 : k1 == k ? e1 : e2;
+    }
+    f.ax[6] = f.ax[1] * f.ax[5] - f.ax[2] * f.ax[4];
+    f.ax[7] = f.ax[2] * f.ax[3] - f.ax[0] * f.ax[5];
+    f.ax[8] = f.ax[0] * f.ax[4] - f.ax[1] * f.ax[3];
+    f.c[0] = c0;
+    f.c[1] = c1;
+    f.c[2] = c2;
+}
+
+__global__ __launch_bounds__(64 * kWaves) void starts_kernel(const StartsArgs a) {
+    const uint32_t row = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
+    if (row >= a.n) return;
+    const int lane = (int)(threadIdx.x % 64);
+    const double nan = __builtin_nan("");
+
+    const PoseRow pr = pose_row(a.src, row, true);
+    int status = pr.status;
+    uint32_t npts = pr.npts;
+    if (npts > (uint32_t)kA) {
+        status = PMX_LIGAND_UNSUPPORTED;
+        npts = 0;
+    }
+    const int start = a.start[row];
+    if (status == PMX_LIGAND_OK && (start < 0 || start > 3)) status = PMX_LIGAND_KEY_INVALID;
+    if (status != PMX_LIGAND_OK) {
+        if (lane < 9) a.rot_out[(size_t)row * 9 + lane] = nan;
+        if (lane < 3) a.trans_out[(size_t)row * 3 + lane] = nan;
+        if (lane < 16) a.frame[(size_t)row * 16 + lane] = nan;
+        if (lane == 0) a.status[row] = status;
+        return;
+    }
+
+    // ---- the row's frame
+    Frame fa, fb;
+    {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        for (uint32_t u = (uint32_t)lane; u < npts; u += 64) {
+            double x0, x1, x2;
+            pose_load(pr, u, x0, x1, x2);
+            s0 += x0;
+            s1 += x1;
+            s2 += x2;
+        }
+        s0 = wave_sum(s0);
+        s1 = wave_sum(s1);
+        s2 = wave_sum(s2);
+        const double c0 = npts ? s0 / (double)npts : 0.0, c1 = npts ? s1 / (double)npts : 0.0, c2 = npts ? s2 / (double)npts : 0.0;
+        double S[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (uint32_t u = (uint32_t)lane; u < npts; u += 64) {
+            double x0, x1, x2;
+            pose_load(pr, u, x0, x1, x2);
+            const double d0 = x0 - c0, d1 = x1 - c1, d2 = x2 - c2;
+            S[0] += d0 * d0;
+            S[1] += d0 * d1;
+            S[2] += d0 * d2;
+            S[3] += d1 * d1;
+            S[4] += d1 * d2;
+            S[5] += d2 * d2;
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) S[k] = wave_sum(S[k]);
+        jacobi_frame(npts, c0, c1, c2, S, fa);
+    }
+    // ---- the reference's
+    {
+        const uint32_t m = a.m;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        for (uint32_t b = (uint32_t)lane; b < m; b += 64) {
+            const double4 y = a.ref[b];
+            s0 += y.x;
+            s1 += y.y;
+            s2 += y.z;
+        }
+        s0 = wave_sum(s0);
+        s1 = wave_sum(s1);
+        s2 = wave_sum(s2);
+        const double c0 = s0 / (double)m, c1 = s1 / (double)m, c2 = s2 / (double)m; // (a reference has at least one atom)
+        double S[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (uint32_t b = (uint32_t)lane; b < m; b += 64) {
+            const double4 y = a.ref[b];
+            const double d0 = y.x - c0, d1 = y.y - c1, d2 = y.z - c2;
+            S[0] += d0 * d0;
+            S[1] += d0 * d1;
+            S[2] += d0 * d2;
+            S[3] += d1 * d1;
+            S[4] += d1 * d2;
+            S[5] += d2 * d2;
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) S[k] = wave_sum(S[k]);
+        jacobi_frame(m, c0, c1, c2, S, fb);
+    }
+
+    // ---- R = E_B D_s E_A^T, t = c_B - R c_A; D_0 = I, D_s the half turn about axis s - 1
+    const double d0 = (start == 0 || start == 1) ? 1.0 : -1.0, d1 = (start == 0 || start == 2) ? 1.0 : -1.0, d2 = (start == 0 || start == 3) ? 1.0 : -1.0;
+    double R[9], t[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) R[3 * i + j] = (d0 * (fb.ax[i] * fa.ax[j]) + d1 * (fb.ax[3 + i] * fa.ax[3 + j])) + d2 * (fb.ax[6 + i] * fa.ax[6 + j]);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = fb.c[i] - ((R[3 * i] * fa.c[0] + R[3 * i + 1] * fa.c[1]) + R[3 * i + 2] * fa.c[2]);
+    double out = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out = lane == k ? R[k] : out;
+    if (lane < 9) a.rot_out[(size_t)row * 9 + lane] = out;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out = lane == k ? t[k] : out;
+    if (lane < 3) a.trans_out[(size_t)row * 3 + lane] = out;
+    out = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out = lane == k ? fa.c[k] : out;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out = lane == 3 + k ? fa.ax[k] : out;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out = lane == 12 + k ? fa.ev[k] : out;
+    if (lane < 16) a.frame[(size_t)row * 16 + lane] = out;
+    if (lane == 0) a.status[row] = status;
+}
+
+} // namespace
+
+extern "C" int pmx_shape_overlay(const pmx_shape_ref *ref, const pmx_library *lib, const uint64_t *ligands_dev, const int32_t *conformer_dev, const uint64_t *point_off_dev,
+                                 const float *points_dev, const float *point_radius_dev, const double *rot_dev, const double *trans_dev, uint32_t n, float point_radius,
+                                 double ftol, int max_iter, double *rot_out_dev, double *trans_out_dev, double *energy_dev, int32_t *count_dev, int32_t *status_dev,
+                                 void *stream_) {
+    if (!ref) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_overlay: null reference");
+    OverlayArgs a{};
+    const int rc = pmx::pose_source("pmx_shape_overlay", "reference", ref->device, lib, ligands_dev, conformer_dev, point_off_dev, points_dev, point_radius_dev, rot_dev, trans_dev,
+                                    n, &a.src);
+    if (rc != PMX_OK) return rc;
+    if (!std::isfinite(point_radius)) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_overlay: point_radius must be finite");
+    if (!std::isfinite(ftol) || ftol < 0.0) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_overlay: ftol must be finite and not negative");
+    if (max_iter < 0 || max_iter > PMX_REFINE_MAX_ITER) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_overlay: max_iter %d, 0 .. %d", max_iter, PMX_REFINE_MAX_ITER);
+    if (n == 0) return PMX_OK;
+    if (!rot_out_dev || !trans_out_dev || !energy_dev || !count_dev || !status_dev) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_overlay: null output");
+    if (hipSetDevice(ref->device) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_shape_overlay: hipSetDevice failed");
+    a.ref = ref->atoms;
+    a.m = ref->m;
+    a.o_bb = ref->o_bb;
+    a.rot = rot_dev;
+    a.trans = trans_dev;
+    a.n = n;
+    a.radius = point_radius;
+    a.ftol = ftol;
+    a.max_iter = max_iter;
+    a.rot_out = rot_out_dev;
+    a.trans_out = trans_out_dev;
+    a.energy = energy_dev;
+    a.count = count_dev;
+    a.status = status_dev;
+    overlay_kernel<<<dim3((n + kWaves - 1) / kWaves), dim3(64 * kWaves), 0, static_cast<hipStream_t>(stream_)>>>(a);
+    PMX_HIPCHECK(hipGetLastError());
+    return PMX_OK;
+}
+
+extern "C" int pmx_shape_starts(const pmx_shape_ref *ref, const pmx_library *lib, const uint64_t *ligands_dev, const int32_t *conformer_dev, const uint64_t *point_off_dev,
+                                const float *points_dev, const int32_t *start_dev, uint32_t n, double *rot_out_dev, double *trans_out_dev, double *frame_dev,
+                                int32_t *status_dev, void *stream_) {
+    if (!ref) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_starts: null reference");
+    if (n > 0 && n <= PMX_EXPLAIN_MAX && (!rot_out_dev || !trans_out_dev || !frame_dev || !status_dev)) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_starts: null output");
+    StartsArgs a{};
+    // (the call reads no motion: the two outputs stand in where the shared check asks for one)
+    const int rc = pmx::pose_source("pmx_shape_starts", "reference", ref->device, lib, ligands_dev, conformer_dev, point_off_dev, points_dev, nullptr, rot_out_dev, trans_out_dev, n,
+                                    &a.src);
+    if (rc != PMX_OK) return rc;
+    if (n == 0) return PMX_OK;
+    if (!start_dev) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_starts: null start_dev");
+    if (hipSetDevice(ref->device) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_shape_starts: hipSetDevice failed");
+    a.ref = ref->atoms;
+    a.m = ref->m;
+    a.start = start_dev;
+    a.n = n;
+    a.rot_out = rot_out_dev;
+    a.trans_out = trans_out_dev;
+    a.frame = frame_dev;
+    a.status = status_dev;
+    starts_kernel<<<dim3((n + kWaves - 1) / kWaves), dim3(64 * kWaves), 0, static_cast<hipStream_t>(stream_)>>>(a);
+    PMX_HIPCHECK(hipGetLastError());
+    return PMX_OK;
+}

@@ -534,6 +534,43 @@ class ScreeningResult:
         model, library, weights = self._scored(model, library, weights)
         return explain_modes(model, library, self._best(k), modes=modes, weights=weights, require=require, exclude=exclude)
 
+    def overlay(self, k: int, reference, atoms=None, starts: int = 4, conformers: str = "best", model=None, library=None, weights: dict[str, float] | None = None,
+                **kw) -> "ShapeOverlay":
+        """`overlay` of this screen's k best ligands (best first) on a known ligand: ligand-based shape screening of a screen's top hits.
+        The points are the hits' pharmacophore nodes, or their heavy atoms with `atoms` (the library's atom store).
+          conformers="best"   each hit at the conformer of its best match (`explain(k).poses`); with `starts=0` from that fitted pose,
+                              with `starts=4` from the four inertial starts
+          conformers="all"    every conformer of each hit from the inertial starts (`starts=4`), keeping per hit the conformer of highest
+                              final Tanimoto, the lower among equals
+        k * conformers * starts may not exceed 65536 rows. Further arguments (`node_radius`, `ftol`, `max_iter`) as `overlay` takes them."""
+        model, library, weights = self._scored(model, library, weights)
+        if conformers not in ("best", "all"):
+            raise ValueError("ScreeningResult.overlay: conformers is 'best' or 'all'")
+        if starts not in (0, 4):
+            raise ValueError("ScreeningResult.overlay: starts is 0 or 4")
+        source = (lambda idx, conf: dict(atoms=atoms, indices=idx, conformers=conf)) if atoms is not None else (lambda idx, conf: dict(library=library, indices=idx, conformers=conf))
+        if conformers == "best":
+            if k * max(starts, 1) > _ffi.EXPLAIN_MAX:
+                raise ValueError(f"ScreeningResult.overlay: {k} hits x {max(starts, 1)} starts exceed {_ffi.EXPLAIN_MAX} rows")
+            al = explain(model, library, self._best(k), weights=weights).poses(model, library, weights=weights)
+            if starts == 0:
+                return al.overlay(reference, library if atoms is None else None, atoms=atoms, **kw)
+            return overlay(reference, starts=starts, **source(al.indices, al.conformers), **kw)
+        if starts == 0:
+            raise ValueError("ScreeningResult.overlay: conformers='all' has a fitted pose for one conformer only; use starts=4")
+        hits = self._best(k).astype(np.int64)
+        with _resident(library) as dlib:
+            n_conf = np.maximum(_record_counts(dlib, hits, 1), 1)
+        rows = int(n_conf.sum()) * starts
+        if rows > _ffi.EXPLAIN_MAX:
+            raise ValueError(f"ScreeningResult.overlay: {len(hits)} hits x their conformers x {starts} starts are {rows} rows, more than {_ffi.EXPLAIN_MAX}; lower k or use conformers='best'")
+        idx, conf = np.repeat(hits, n_conf), np.concatenate([np.arange(c) for c in n_conf]) if len(hits) else np.zeros(0, np.int64)
+        every = overlay(reference, starts=starts, **source(idx, conf), **kw)
+        first = np.concatenate([[0], np.cumsum(n_conf)[:-1]]).astype(np.int64) if len(hits) else np.zeros(0, np.int64)
+        value = np.where(np.isnan(every.tanimoto), -np.inf, every.tanimoto)
+        pick = np.array([lo + int(np.argmax(value[lo: lo + c])) for lo, c in zip(first, n_conf)], dtype=np.int64)  # (the first among equals)
+        return ShapeOverlay(**{f.name: (None if getattr(every, f.name) is None else getattr(every, f.name)[pick]) for f in dataclasses.fields(every)})
+
 
     def diverse(self, k: int, pool: int | None = None, threshold: float = 0.7, model=None, library=None, weights: dict[str, float] | None = None) -> "DiverseHits":
         """The k first hits of this screen that are not the same binding mode again: the best `pool` hits (default
@@ -1398,6 +1435,11 @@ class PoseSearch:
         choice a row with status 4 (or 1)."""
         return self.poses.shape(reference, library, atoms=atoms, **kw)
 
+    def overlay(self, reference, library=None, atoms=None, **kw) -> "ShapeOverlay":
+        """`overlay` of the chosen rows from their own motions (`Alignment.overlay` of `alignment()`): row i is hit i, a hit without a
+        choice a row with status 4 (or 1)."""
+        return self.poses.overlay(reference, library, atoms=atoms, **kw)
+
 
 def _search_chunks(conf: np.ndarray, modes: int):
     """(lo, hi, conf_stride) of consecutive runs of hits with (hi - lo) * modes * conf_stride <= 65536, conf_stride the most conformers
@@ -1820,6 +1862,12 @@ class Alignment:
         alone, the molecules' heavy atoms with `atoms` (per row the molecule, or the library's atom store), as `Alignment.clashes` takes
         them. Further arguments (`node_radius`, `cover`) as `shape` takes them."""
         return _shape_poses(self, "Alignment.shape", reference, library, atoms, kw)
+
+    def overlay(self, reference, library=None, atoms=None, **kw) -> "ShapeOverlay":
+        """These poses moved to their nearest shape match with a known ligand (`overlay` from each row's own motion): how far is the fit
+        from it, and how much overlap does it lack? Row i of the result is row i of the alignment; the points as `Alignment.shape` takes
+        them. Further arguments (`node_radius`, `ftol`, `max_iter`) as `overlay` takes them."""
+        return _overlay_poses(self, "Alignment.overlay", reference, library, atoms, kw)
 
 
 def align(model, library, indices, conformers, keys, weights: dict[str, float] | None = None, device=None) -> Alignment:
@@ -2283,6 +2331,232 @@ class RefinedPoses:
         """The refined poses compared with a known ligand, as `Alignment.shape` compares the fitted ones: the rows' nodes with `library`,
         the molecules' heavy atoms with `atoms`. A row that is not OK passes through with status 4."""
         return _shape_poses(self, "RefinedPoses.shape", reference, library, atoms, kw)
+
+    def overlay(self, reference, library=None, atoms=None, **kw) -> "ShapeOverlay":
+        """The refined poses moved to their nearest shape match with a known ligand, as `Alignment.overlay` moves the fitted ones."""
+        return _overlay_poses(self, "RefinedPoses.overlay", reference, library, atoms, kw)
+
+
+@dataclass
+class ShapeOverlay:
+    """What `overlay` returns: one row per hit - the rigid motion that maximises its Gaussian shape overlap with a reference ligand from
+    where it started (definitions: `pmx_shape_overlay` and `pmx_shape_starts` in include/pmx.h). Floats are float64. Rigid only, shape
+    only (no atom types, no hydrogens), and a local maximum: the one the start leads to.
+
+    rotation[i], translation[i]   the overlaid motion: a point x of the conformer sits at R x + t. The start's own bits where no step was taken
+    overlap_start[i], overlap[i]  O_AB at the start motion and at the overlaid one (never lower)
+    self_overlap[i], reference_overlap[i]   O_AA and O_BB, which no rigid motion changes
+    tanimoto_start[i], tanimoto[i]   O_AB / (O_AA + O_BB - O_AB) before and after
+    angle[i], shift[i]   the net rotation from the start in rad, and how far the centroid of the posed points moved
+    iterations[i], accepted[i]    trial motions, and the ones among them that raised O_AB
+    stop[i]         0 nothing to follow (no point, or O_AB = 0: too far away), 1 converged (increase <= ftol O_AB), 2 out of iterations,
+                    3 no step found (lambda > 1e8: a row that starts at a maximum ends so); -1 not OK
+    n_points[i]     the row's points
+    start[i]        with `starts=4`: which inertial start (0: the frames laid on each other, 1 .. 3: and a half turn about the row's
+                    first, second or third axis) was kept - the one of highest final Tanimoto, the lower among equals; -1 with `starts=0`
+    start_tanimoto  [n, starts]: every start's final Tanimoto
+    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID); such a row has NaN floats, zero counts and stop -1
+    indices, conformers   the rows' ligands and conformers (None for points of the caller's)"""
+
+    rotation: np.ndarray
+    translation: np.ndarray
+    overlap_start: np.ndarray
+    overlap: np.ndarray
+    self_overlap: np.ndarray
+    reference_overlap: np.ndarray
+    tanimoto_start: np.ndarray
+    tanimoto: np.ndarray
+    angle: np.ndarray
+    shift: np.ndarray
+    iterations: np.ndarray
+    accepted: np.ndarray
+    stop: np.ndarray
+    n_points: np.ndarray
+    start: np.ndarray
+    start_tanimoto: np.ndarray
+    status: np.ndarray
+    indices: "np.ndarray | None" = None
+    conformers: "np.ndarray | None" = None
+
+    def __len__(self) -> int:
+        return len(self.status)
+
+    def transform(self, i: int, positions) -> np.ndarray:
+        """Row i's overlaid motion applied to any [..., 3] array of points of the conformer's frame: positions @ R.T + t."""
+        return np.asarray(positions, dtype=np.float64) @ self.rotation[i].T + self.translation[i]
+
+    def shape(self, reference, library=None, atoms=None, **kw) -> "ShapeReport":
+        """The overlaid poses compared with a known ligand, as `Alignment.shape` compares the fitted ones."""
+        return _shape_poses(self, "ShapeOverlay.shape", reference, library, atoms, kw)
+
+    def clashes(self, pocket_or_model, library=None, atoms=None, **kw) -> "ClashReport":
+        """The overlaid poses checked against the pocket's atoms, as `Alignment.clashes` checks the fitted ones: a shape overlay knows
+        nothing of the protein."""
+        return _check_poses(self, "ShapeOverlay.clashes", pocket_or_model, library, atoms, kw)
+
+    def refine(self, pocket_or_model, library=None, atoms=None, **kw) -> "RefinedPoses":
+        """The overlaid poses moved out of the pocket's atoms and held near the overlay, as `Alignment.refine` does it of the fitted ones."""
+        if self.indices is None:
+            raise ValueError("ShapeOverlay.refine: these rows are points of the caller's, not ligands of a library")
+        return Alignment.refine(self, pocket_or_model, library, atoms, **kw)
+
+    def pose_fit(self, model, library, keys=None, **kw) -> "PoseFit":
+        """How well the overlaid poses sit on the model's hotspots (free mode unless `keys` are given), as `Alignment.pose_fit`."""
+        if self.indices is None:
+            raise ValueError("ShapeOverlay.pose_fit: these rows are points of the caller's, not ligands of a library")
+        return pose_fit(model, library, self.indices, self.conformers, self.rotation, self.translation, keys=keys, **kw)
+
+
+def overlay(reference, library=None, indices=None, conformers=None, rotation=None, translation=None, points=None, point_radii=None, atoms=None, starts: int = 0,
+            node_radius: float = 1.0, ftol: float = 1e-6, max_iter: int = 32, device=None) -> ShapeOverlay:
+    """Rows overlaid on a known ligand (`pmx_shape_overlay`, csrc/pmx_shape_overlay.hip): per row a bounded Levenberg-Marquardt
+    maximisation over the rigid motion of the Gaussian shape overlap `shape` reports. Rows, points and radii as `shape` takes them (node
+    mode, point mode, or an atom store `atoms`).
+      starts=0   each row is optimised from its given motion: how far is this pose from its best shape match nearby?
+      starts=4   `rotation` / `translation` are ignored and may be None: each hit is run from the four motions that lay its inertial frame
+                 on the reference's (`pmx_shape_starts`), and the start of highest final Tanimoto is kept (the lower among equals). At
+                 most 16384 hits
+      max_iter, ftol  at most `max_iter` (<= 64) trial motions per row; a step that raises O_AB by no more than ftol * O_AB ends the row
+    Rigid only, shape only (no atom types, no hydrogens), unweighted inertial frames, and a local maximum. At most 65536 rows. Runs on
+    torch's current stream of the device and waits for it."""
+    torch = _torch()
+    lib = _ffi.load()
+    if starts not in (0, 4):
+        raise ValueError("overlay: starts is 0 (from the given motions) or 4 (the inertial starts)")
+    if not 0 <= int(max_iter) <= 64:
+        raise ValueError("max_iter: 0 to 64 (PMX_REFINE_MAX_ITER)")
+    if not (np.isfinite(ftol) and ftol >= 0):
+        raise ValueError("ftol must be finite and not negative")
+    if not np.isfinite(node_radius):
+        raise ValueError("node_radius must be finite")
+    k = max(starts, 1)
+    if starts:
+        hits = len(points) if points is not None else len(np.asarray(indices).reshape(-1))
+        if hits > 16384:
+            raise ValueError(f"overlay: {hits} hits, at most 16384 with starts=4 (65536 rows)")
+        rep = lambda v: None if v is None else [x for x in v for _ in range(k)]  # noqa: E731
+        points, point_radii = rep(points), rep(point_radii)
+        if indices is not None:
+            indices, conformers = np.repeat(np.asarray(indices).reshape(-1), k), np.repeat(np.asarray(conformers).reshape(-1), k)
+        rotation, translation = np.zeros((hits * k, 3, 3)), np.zeros((hits * k, 3))
+    elif rotation is None or translation is None:
+        raise ValueError("overlay: starts=0 optimises the given motions - rotation and translation")
+    rows = _PoseRows("overlay", library, indices, conformers, rotation, translation, points, point_radii, atoms)
+    n, node_mode = rows.n, rows.node_mode
+    m = max(n, 1)
+    with contextlib.ExitStack() as stack:
+        dlib = stack.enter_context(_resident(library, device)) if node_mode else None
+        dev = dlib.device if node_mode else atoms.device if isinstance(atoms, DeviceAtoms) else _device_index(device)
+        dat = stack.enter_context(_resident_atoms(atoms, dev)) if atoms is not None else None
+        rh = device_shape_ref(reference, dev)
+        tdev = torch.device("cuda", dev)
+        with torch.cuda.device(tdev):
+            keep, src, motion = rows.upload(tdev, dat)
+            rot = torch.empty((m, 3, 3), dtype=torch.float64, device=tdev)
+            trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
+            energy = torch.empty((m, 8), dtype=torch.float64, device=tdev)
+            count = torch.empty((m, 4), dtype=torch.int32, device=tdev)
+            status = torch.empty(m, dtype=torch.int32, device=tdev)
+            stream = torch.cuda.current_stream(tdev)
+            sptr = ctypes.c_void_p(stream.cuda_stream)
+            lh = dlib.handle if node_mode else None
+            if starts:
+                which = torch.arange(m, dtype=torch.int32, device=tdev) % k
+                s_rot = torch.empty((m, 9), dtype=torch.float64, device=tdev)
+                s_trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
+                frame = torch.empty((m, 16), dtype=torch.float64, device=tdev)
+                s_status = torch.empty(m, dtype=torch.int32, device=tdev)
+                _ffi.check(lib.pmx_shape_starts(rh.handle, lh, *src[:4], which.data_ptr(), n, s_rot.data_ptr(), s_trans.data_ptr(), frame.data_ptr(), s_status.data_ptr(), sptr))
+                if rows.gstatus is not None and n:  # (a row the store has no atoms for stays not OK)
+                    bad = (rows.gstatus != 0)[:, None]
+                    s_rot, s_trans = s_rot.masked_fill(bad, float("nan")), s_trans.masked_fill(bad, float("nan"))
+                keep = (keep, which, s_rot, s_trans, frame, s_status)
+                motion = (s_rot.data_ptr(), s_trans.data_ptr())
+            _ffi.check(lib.pmx_shape_overlay(rh.handle, lh, *src, *motion, n, float(node_radius), float(ftol), int(max_iter), rot.data_ptr(), trans.data_ptr(),
+                                             energy.data_ptr(), count.data_ptr(), status.data_ptr(), sptr))
+            stream.synchronize()
+            del keep
+    st = rows.finish(status.cpu().numpy()[:n].astype(np.int32))
+    en, cn = energy.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
+    R, t = rot.cpu().numpy()[:n], trans.cpu().numpy()[:n]
+    hits = n // k
+    if starts:
+        each = en[:, 5].reshape(hits, k)
+        best = np.argmax(np.where(np.isnan(each), -np.inf, each), axis=1) if hits else np.zeros(0, np.int64)  # (the first among equals)
+        pick = np.arange(hits) * k + best
+        start, start_tanimoto = best.astype(np.int64), each.copy()
+    else:
+        pick, start, start_tanimoto = np.arange(n), np.full(n, -1, np.int64), np.zeros((n, 0))
+    has_rows = node_mode or atoms is not None
+    return ShapeOverlay(rotation=R[pick].copy(), translation=t[pick].copy(), overlap_start=en[pick, 0], overlap=en[pick, 1], self_overlap=en[pick, 2],
+                        reference_overlap=en[pick, 3], tanimoto_start=en[pick, 4], tanimoto=en[pick, 5], angle=en[pick, 6], shift=en[pick, 7], iterations=cn[pick, 0],
+                        accepted=cn[pick, 1], stop=cn[pick, 2], n_points=cn[pick, 3], start=start, start_tanimoto=start_tanimoto, status=st[pick],
+                        indices=rows.idx[pick].copy() if has_rows else None, conformers=rows.conf[pick].astype(np.int64) if has_rows else None)
+
+
+@dataclass
+class ShapeStarts:
+    """What `overlay_starts` returns (definitions: `pmx_shape_starts` in include/pmx.h): per row the start motion `rotation[i]`,
+    `translation[i]`, and the row's own inertial frame - `centre[i]` [3], `axes[i]` [3, 3] (axis k is row k; right-handed, by descending
+    `values[i]` [3], the sums of squares along them) - for a caller who wants another set of starts. A row that is not OK (`status[i]`
+    1 or 4; 4 also for a start outside 0 .. 3) has NaN."""
+
+    rotation: np.ndarray
+    translation: np.ndarray
+    centre: np.ndarray
+    axes: np.ndarray
+    values: np.ndarray
+    status: np.ndarray
+
+    def __len__(self) -> int:
+        return len(self.status)
+
+
+def overlay_starts(reference, start, library=None, indices=None, conformers=None, points=None, atoms=None, device=None) -> ShapeStarts:
+    """The inertial start motions of rows (`pmx_shape_starts`): row i's points - as `overlay` takes them - laid with their unweighted
+    inertial frame on the reference's, start[i] = 0, or 1 .. 3 for a further half turn about the row's first, second or third axis. What
+    `overlay(..., starts=4)` runs from. At most 65536 rows."""
+    torch = _torch()
+    lib = _ffi.load()
+    start = np.ascontiguousarray(np.clip(np.asarray(start, dtype=np.int64).reshape(-1), -1, 2**31 - 1).astype(np.int32))
+    n = len(start)
+    rows = _PoseRows("overlay_starts", library, indices, conformers, np.zeros((n, 3, 3)), np.zeros((n, 3)), points, None, atoms)
+    node_mode = rows.node_mode
+    m = max(n, 1)
+    with contextlib.ExitStack() as stack:
+        dlib = stack.enter_context(_resident(library, device)) if node_mode else None
+        dev = dlib.device if node_mode else atoms.device if isinstance(atoms, DeviceAtoms) else _device_index(device)
+        dat = stack.enter_context(_resident_atoms(atoms, dev)) if atoms is not None else None
+        rh = device_shape_ref(reference, dev)
+        tdev = torch.device("cuda", dev)
+        with torch.cuda.device(tdev):
+            keep, src, _ = rows.upload(tdev, dat)
+            which = torch.from_numpy(start if n else np.zeros(1, np.int32)).to(tdev)
+            rot = torch.empty((m, 3, 3), dtype=torch.float64, device=tdev)
+            trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
+            frame = torch.empty((m, 16), dtype=torch.float64, device=tdev)
+            status = torch.empty(m, dtype=torch.int32, device=tdev)
+            stream = torch.cuda.current_stream(tdev)
+            _ffi.check(lib.pmx_shape_starts(rh.handle, dlib.handle if node_mode else None, *src[:4], which.data_ptr(), n, rot.data_ptr(), trans.data_ptr(), frame.data_ptr(),
+                                            status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+            stream.synchronize()
+            del keep
+    st = rows.finish(status.cpu().numpy()[:n].astype(np.int32))
+    R, t, fr = rot.cpu().numpy()[:n].copy(), trans.cpu().numpy()[:n].copy(), frame.cpu().numpy()[:n].copy()
+    if rows.gstatus is not None:  # (a row the store has no atoms for is not OK, whatever its empty point list gave)
+        for a in (R, t, fr):
+            a[st != 0] = np.nan
+    return ShapeStarts(rotation=R, translation=t, centre=fr[:, 0:3].copy(), axes=fr[:, 3:12].reshape(-1, 3, 3).copy(), values=fr[:, 12:15].copy(), status=st)
+
+
+def _overlay_poses(poses, what, reference, library, atoms, kw) -> "ShapeOverlay":
+    if kw.get("starts", 0):
+        raise ValueError(f"{what}: the local overlay of these poses; `overlay(..., starts=4)` is the one that needs no pose")
+    _, source = _pose_source(poses, what, None, library, atoms)
+    out = overlay(reference, rotation=poses.rotation, translation=poses.translation, **source, **kw)
+    if out.indices is None and poses.indices is not None:
+        out.indices, out.conformers = np.asarray(poses.indices).copy(), np.asarray(poses.conformers, dtype=np.int64).copy()
+    return out
 
 
 def _heavy_atoms(atoms, conformers):

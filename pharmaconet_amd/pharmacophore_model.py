@@ -624,6 +624,52 @@ class PharmacophoreModel:
             raise ValueError(f"{sorted(kw)}: arguments of the refinement, which is off (refine=True)")
         return out
 
+    def scoring_overlay(self, ligand, reference, starts: int = 4, level: str = "atoms", weights: dict[str, float] | None = None, **kw) -> dict:
+        """One ligand overlaid on a known ligand (`engine.overlay`; `reference` a `shape.ReferenceLigand` in the pocket's frame), the
+        one-ligand form beside `scoring_shape`. With `starts=4` every conformer is run from the four inertial starts - no pharmacophore fit
+        is involved - and the conformer and start of highest final Tanimoto are kept (the lower among equals); with `starts=0` the fitted
+        pose of `scoring_pose` is moved to its nearest shape match. `level` "atoms": the ligand's heavy atoms with Bondi radii (a `Ligand` /
+        `LigandFeatures`); "nodes": the record's pharmacophore nodes. Returns `conformer`, `start`, `level`, `rotation`, `translation`,
+        `positions` (all the molecule's atoms, posed; None for a packed record), `node_positions`, `overlap_start`, `overlap`,
+        `self_overlap`, `reference_overlap`, `tanimoto_start`, `tanimoto`, `angle`, `shift`, `iterations`, `accepted`, `stop`, `n_points`
+        and `status`. Further arguments (`node_radius`, `ftol`, `max_iter`) as `engine.overlay`."""
+        from .engine import _heavy_atoms, overlay
+        from .library import as_packed_library
+
+        if level not in ("nodes", "atoms"):
+            raise ValueError("level: 'nodes' or 'atoms'")
+        if starts not in (0, 4):
+            raise ValueError("starts: 0 or 4")
+        packed = as_packed_library(ligand)
+        if len(packed) != 1:
+            raise ValueError("scoring_overlay takes exactly one ligand")
+        atoms = getattr(ligand, "atom_positions", None)
+        if level == "atoms" and atoms is None:
+            raise ValueError("scoring_overlay(level='atoms'): the ligand has no atoms (a packed record); give the molecule, or level='nodes'")
+        if starts:
+            conf = list(range(int(packed.header(0)[1])))
+            motion = {}
+        else:
+            pose = self.scoring_pose(ligand, weights=weights)
+            conf = [pose["conformer"]]
+            motion = dict(rotation=[pose["rotation"]], translation=[pose["translation"]])
+        if level == "atoms":
+            points, radii = _heavy_atoms([ligand] * len(conf), conf)
+            source = dict(points=points, point_radii=radii)
+        else:
+            source = dict(library=packed, indices=[0] * len(conf), conformers=conf)
+        ov = overlay(reference, starts=starts, **source, **motion, **kw)
+        value = np.where(np.isnan(ov.tanimoto), -np.inf, ov.tanimoto)
+        r = int(np.argmax(value))  # (the first among equals)
+        c = int(conf[r])
+        ok = int(ov.status[r]) == 0
+        positions = ov.transform(r, np.asarray(atoms, dtype=np.float64)[:, c]) if ok and atoms is not None else None
+        node_positions = ov.transform(r, packed.unpack(0)["xyz"][:, :, c].astype(np.float64)) if ok else None
+        return dict(conformer=c, start=int(ov.start[r]), level=level, rotation=ov.rotation[r], translation=ov.translation[r], positions=positions, node_positions=node_positions,
+                    overlap_start=float(ov.overlap_start[r]), overlap=float(ov.overlap[r]), self_overlap=float(ov.self_overlap[r]), reference_overlap=float(ov.reference_overlap[r]),
+                    tanimoto_start=float(ov.tanimoto_start[r]), tanimoto=float(ov.tanimoto[r]), angle=float(ov.angle[r]), shift=float(ov.shift[r]),
+                    iterations=int(ov.iterations[r]), accepted=int(ov.accepted[r]), stop=int(ov.stop[r]), n_points=int(ov.n_points[r]), status=int(ov.status[r]))
+
     def scoring_pose_fit(self, ligand, conformer: int | None = None, key=None, refine: bool = False, free: bool = False, weights: dict[str, float] | None = None,
                          pocket=None, centers=None, sigmas=None, **kw) -> dict:
         """One ligand fitted into the pocket (`scoring_pose`) and its pose scored in place (`engine.pose_fit`): how well its pharmacophore

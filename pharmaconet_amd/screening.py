@@ -7,6 +7,7 @@ processes; needs OpenBabel like the reference) or a packed library file (`.pmxli
 Output: `path,score` CSV, best first, ties in library order (`screening.py:70-75`). Scoring runs on the GPU.
 `--explain K --clashes PATH [--protein FILE.pdb]` checks the explained hits' poses against the protein's atoms (excluded volumes).
 `--explain K --pose_shape PATH --shape_ref FILE.pdb` compares the explained hits' poses with a known ligand (Gaussian shape overlap).
+`--explain K --overlay_out PATH --shape_ref FILE.pdb` overlays the explained hits on that ligand (a rigid maximisation of the overlap).
 `--explain K --refine_out PATH [--refine_restraint X] [--refine_iter N]` moves those poses out of the protein's atoms (restrained rigid-body refinement).
 `--explain K --pose_fit PATH [--pose_fit_mode key|free]` scores those poses in place: the overlap of the posed pharmacophore nodes with the model's hotspots (with --refine_out also at the refined motion).
 `--explain K --pose_search PATH [--pose_search_modes M] [--pose_min_fraction F] [--pose_search_level nodes|atoms]` poses every explained hit in the conformer and binding mode that fits the pocket.
@@ -56,7 +57,10 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--pose_shape", type=str, default=None, metavar="PATH", help="with --explain K and --shape_ref: CSV with one row per explained hit: the Gaussian shape overlap of its pose with a known ligand (overlap volume, shape Tanimoto, the fractions of the reference and of the hit that are filled, nearest-atom distances both ways); with --refine_out a second row per hit for the refined pose")
         cfg.add_argument("--shape_ref", type=str, default=None, metavar="FILE.pdb", help="with --pose_shape: the known ligand, in the model's frame (its heavy atoms, Bondi radii)")
         cfg.add_argument("--shape_cover", type=float, default=2.0, metavar="D", help="with --pose_shape: an atom counts as covered when its nearest counterpart is closer than D Angstrom")
-        cfg.add_argument("--shape_level", choices=("nodes", "atoms"), default="atoms", help="with --pose_shape: compare the hit's pharmacophore nodes, or its heavy atoms (where they come from: as --clash_level)")
+        cfg.add_argument("--overlay_out", type=str, default=None, metavar="PATH", help="with --explain K and --shape_ref: CSV with one row per explained hit: its best conformer overlaid on the known ligand (a rigid, local maximisation of the Gaussian shape overlap; no atom types): the shape Tanimoto before and after, how far the hit moved, and the motion")
+        cfg.add_argument("--overlay_starts", type=int, choices=(0, 4), default=4, help="with --overlay_out: 4 runs each hit from the four motions that lay its inertial frame on the known ligand's and keeps the best; 0 starts from the hit's fitted pose")
+        cfg.add_argument("--overlay_iter", type=int, default=32, metavar="N", help="with --overlay_out: at most N trial motions per start (0 to 64)")
+        cfg.add_argument("--shape_level", choices=("nodes", "atoms"), default="atoms", help="with --pose_shape / --overlay_out: compare the hit's pharmacophore nodes, or its heavy atoms (where they come from: as --clash_level)")
         cfg.add_argument("--refine_restraint", type=float, default=0.1, metavar="X", help="with --refine_out: the weight of the restraint that holds the pose near its fit (uncalibrated default)")
         cfg.add_argument("--refine_iter", type=int, default=32, metavar="N", help="with --refine_out: at most N trial motions per pose (0 to 64)")
         cfg.add_argument("--hotspots", type=str, default=None, metavar="PATH", help="with --explain K: CSV with one row per (explained hit, model node it has terms with): the node's share of the hit's best conformer maximum and whether the hit engages it")
@@ -189,8 +193,14 @@ def main(argv=None) -> None:
         parser.error("--pose_shape needs --explain K")
     if args.pose_shape and not args.shape_ref:
         parser.error("--pose_shape needs --shape_ref FILE.pdb, the known ligand")
-    if args.shape_ref and not args.pose_shape:
-        parser.error("--shape_ref needs --pose_shape PATH")
+    if args.overlay_out and args.explain <= 0:
+        parser.error("--overlay_out needs --explain K")
+    if args.overlay_out and not args.shape_ref:
+        parser.error("--overlay_out needs --shape_ref FILE.pdb, the known ligand")
+    if args.overlay_out and not 0 <= args.overlay_iter <= 64:
+        parser.error("--overlay_iter takes 0 to 64")
+    if args.shape_ref and not (args.pose_shape or args.overlay_out):
+        parser.error("--shape_ref needs --pose_shape PATH or --overlay_out PATH")
     if args.pose_shape and not (np.isfinite(args.shape_cover) and args.shape_cover >= 0):
         parser.error("--shape_cover takes a distance that is not negative")
     if not (args.clashes or args.refine_out or args.pose_search) and args.protein:
@@ -205,7 +215,7 @@ def main(argv=None) -> None:
     if (args.clashes or args.refine_out) and args.clash_level == "atoms" and packed_without_atoms:
         parser.error(f"--clash_level atoms takes the hits' atoms from {atoms_path(args.library_dir)}, which does not exist (--save_top writes it from a library directory; "
                      "or use --clash_level nodes)")
-    if args.pose_shape and args.shape_level == "atoms" and packed_without_atoms:
+    if (args.pose_shape or args.overlay_out) and args.shape_level == "atoms" and packed_without_atoms:
         parser.error(f"--shape_level atoms takes the hits' atoms from {atoms_path(args.library_dir)}, which does not exist (--save_top writes it from a library directory; "
                      "or use --shape_level nodes)")
     if args.pose_search and args.pose_search_level == "atoms" and packed_without_atoms:
@@ -289,7 +299,7 @@ def main(argv=None) -> None:
             pocket = PocketAtoms.from_pdb(Path(args.protein), centers=model.node_centers) if args.protein else model.pocket_atoms()
         except (OSError, ValueError) as e:
             parser.error(f"{'--clashes' if args.clashes else '--refine_out' if args.refine_out else '--pose_search'}: {e}" + ("" if args.protein else " (give it with --protein FILE.pdb)"))
-    if args.pose_shape:  # (before the screen: a reference that cannot be read should not cost a pass)
+    if args.pose_shape or args.overlay_out:  # (before the screen: a reference that cannot be read should not cost a pass)
         from .shape import ReferenceLigand
 
         try:
@@ -300,7 +310,7 @@ def main(argv=None) -> None:
     packed = Path(args.library_dir).is_file()
     atom_search = bool(args.pose_search) and args.pose_search_level == "atoms"
     if (atom_search or args.save_top or (packed and (args.clashes or args.refine_out) and args.clash_level == "atoms")
-            or (packed and args.pose_shape and args.shape_level == "atoms")):
+            or (packed and (args.pose_shape or args.overlay_out) and args.shape_level == "atoms")):
         names, lib, store = load_library(Path(args.library_dir), args.cpus, on_device=True, with_atoms=True)
     else:
         (names, lib), store = load_library(Path(args.library_dir), args.cpus, on_device=True), None
@@ -347,6 +357,9 @@ def main(argv=None) -> None:
             refine = (dict(pocket=pocket, level=args.clash_level, tolerance=args.clash_tolerance, restraint=args.refine_restraint, max_iter=args.refine_iter, store=hit_atoms)
                       if args.refine_out else None)
             write_pose_shape_csv(Path(args.pose_shape), names, scores, status, model, lib, weight, args.explain, shape_ref, args.shape_level, args.shape_cover, hit_atoms, refine)
+        if args.overlay_out:
+            write_overlay_csv(Path(args.overlay_out), names, scores, status, model, lib, weight, args.explain, shape_ref, args.shape_level, args.overlay_starts, args.overlay_iter,
+                              hit_atoms)
         if args.pose_search:
             write_pose_search_csv(Path(args.pose_search), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_tolerance, args.pose_search_modes,
                                   args.pose_min_fraction, store if atom_search else None)
@@ -721,6 +734,40 @@ def write_pose_shape_csv(out: Path, names: list[str], scores: np.ndarray, status
                 nums = ",".join(repr(float(v)) for v in (sh.overlap[r], sh.tanimoto[r], sh.reference_fraction[r], sh.fit_fraction[r], sh.rms_to_reference[r], sh.rms_from_reference[r]))
                 w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{stage},{level},{int(sh.n_points[r])},{int(sh.n_covered[r])},{len(reference)},"
                         f"{int(sh.n_reference_covered[r])},{nums}\n")
+
+
+OVERLAY_HEADER = ("rank,path,conformer,level,start,points,iterations,stop,tanimoto_start,tanimoto,overlap,reference_fraction,fit_fraction,angle_deg,shift,"
+                  "r00,r01,r02,r10,r11,r12,r20,r21,r22,tx,ty,tz")
+
+
+def write_overlay_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, reference, level: str, starts: int, max_iter: int,
+                      store: PackedAtoms | None = None) -> None:
+    """One row per hit of the k best, in the order of the poses CSV: the hit's best conformer overlaid on the known ligand `reference`
+    (`engine.overlay`) - at level `nodes` its pharmacophore nodes, at level `atoms` its heavy atoms, from where the pose-shape CSV takes
+    them. With `starts` 4 the hit is run from the four inertial starts and `start` says which was kept; with 0 it is run from its fitted
+    pose (`engine.align`) and `start` is -1. The shape Tanimoto at the start and at the end, the overlap volume there, the fraction of the
+    reference that is filled and of the hit that lies inside it, the net rotation in degrees and the centroid's shift from the start, and
+    the motion. Every float is the `repr` of the float64 the GPU returned (the two fractions and the degrees are formed from them)."""
+    from .engine import _pose_source, explain, overlay
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
+    atoms = _hit_atoms(store, names, order, al.rows) if level == "atoms" else None
+    if starts:
+        _, source = _pose_source(al, "--overlay_out", None, lib, atoms)
+        ov = overlay(reference, starts=starts, max_iter=max_iter, **source)
+    else:
+        ov = al.overlay(reference, lib, atoms=atoms, max_iter=max_iter)
+    with np.errstate(all="ignore"):
+        ref_fraction = ov.overlap / ov.reference_overlap
+        fit_fraction = np.where(ov.self_overlap == 0.0, 0.0, ov.overlap / np.where(ov.self_overlap == 0.0, 1.0, ov.self_overlap))
+    with open(out, "w") as w:
+        w.write(OVERLAY_HEADER + "\n")
+        for r, row in enumerate(al.rows):
+            nums = ",".join(repr(float(v)) for v in (ov.tanimoto_start[r], ov.tanimoto[r], ov.overlap[r], ref_fraction[r], fit_fraction[r], np.degrees(ov.angle[r]), ov.shift[r],
+                                                      *ov.rotation[r].reshape(-1), *ov.translation[r]))
+            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{level},{int(ov.start[r])},{int(ov.n_points[r])},{int(ov.iterations[r])},{int(ov.stop[r])},{nums}\n")
 
 
 if __name__ == "__main__":
