@@ -27,6 +27,7 @@
 
 namespace {
 using pmx::pose_load;
+using pmx::pose_motion;
 using pmx::pose_point;
 using pmx::pose_row;
 using pmx::PoseRow;
@@ -63,17 +64,7 @@ __global__ __launch_bounds__(64 * kWaves) void clash_kernel(const ClashArgs a) {
     const double nan = __builtin_nan(""), ninf = -__builtin_inf();
 
     double R[9], t[3];
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        R[k] = a.rot[(size_t)row * 9 + k];
-        finite = finite && std::isfinite(R[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        t[k] = a.trans[(size_t)row * 3 + k];
-        finite = finite && std::isfinite(t[k]);
-    }
+    const bool finite = pose_motion(a.rot, a.trans, row, R, t);
 
     // ---- the row's points
     const PoseRow pr = pose_row(a.src, row, finite);

@@ -46,6 +46,22 @@ struct PoseRow {
     const float *radii; // per point, or null for the call's radius
 };
 
+// The row's motion: R and t loaded, and whether all 12 values are finite (what `pose_row` takes as `finite`).
+__device__ __forceinline__ bool pose_motion(const double *rot, const double *trans, uint32_t row, double (&R)[9], double (&t)[3]) {
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        R[k] = rot[(size_t)row * 9 + k];
+        finite = finite && std::isfinite(R[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        t[k] = trans[(size_t)row * 3 + k];
+        finite = finite && std::isfinite(t[k]);
+    }
+    return finite;
+}
+
 // The row front end: `finite` says that the row's 12 motion values are.
 __device__ __forceinline__ PoseRow pose_row(const PoseSource &a, uint32_t row, bool finite) {
     PoseRow r;

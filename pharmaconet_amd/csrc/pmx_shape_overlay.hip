@@ -34,6 +34,7 @@ using pmx::alpha_of;
 using pmx::dist2;
 using pmx::pair_term;
 using pmx::pose_load;
+using pmx::pose_motion;
 using pmx::pose_point;
 using pmx::pose_row;
 using pmx::PoseRow;
@@ -260,17 +261,7 @@ __global__ __launch_bounds__(64 * kWaves) void overlay_kernel(const OverlayArgs 
     uint32_t npts = 0;
     double4 *X = Lx[wave], *P = Lp[wave];
     if (live) {
-        bool finite = true;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            R0[k] = a.rot[(size_t)row * 9 + k];
-            finite = finite && std::isfinite(R0[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            t0[k] = a.trans[(size_t)row * 3 + k];
-            finite = finite && std::isfinite(t0[k]);
-        }
+        const bool finite = pose_motion(a.rot, a.trans, row, R0, t0);
         const PoseRow pr = pose_row(a.src, row, finite);
         status = pr.status;
         npts = pr.npts;

@@ -14,402 +14,21 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _ffi
-from .atoms import PackedAtoms
-from .constants import weights_vector
-from .library import PackedLibrary, as_packed_library
+from ._device import (_FP_WORDS, _MAX_LEADERS, _MAX_LEVELS, _MAX_MODEL_NODES, _MAX_NODES, _MAX_QUERIES, NO_LEVEL, NO_MATCH, DeviceAtoms, DeviceLibrary,  # noqa: F401
+                      _device_index, _is_store, _listed_indices, _ModelHandle, _record_counts, _resident, _resident_atoms, _torch,
+                      _weights_array, device_model)
+from .atoms import PackedAtoms  # noqa: F401
+from .constants import weights_vector  # noqa: F401
+from .library import PackedLibrary, as_packed_library  # noqa: F401
+# the posed-hit layer (poses.py); every name of it stays importable from here
+from .poses import (Alignment, ClashReport, PoseFit, RefinedPoses, ShapeOverlay, ShapeReport, ShapeStarts, _atomic_numbers, _fingerprint_tensor,  # noqa: F401
+                    _heavy_atoms, _PocketHandle, _pose_source, _PoseRows, _ragged, _ratio, _ShapeRefHandle, clashes, device_pocket,
+                    device_shape_ref, fingerprint_leaders, fingerprint_similarity, overlay, overlay_starts, pose_fit, refine, shape)
 from .validation import ENRICH_TILE, FLOAT64_REFUSED, MAX_BOOTSTRAP, MAX_COLUMNS, POISSON1_CDF64, Enrichment, cutoffs_ppm  # noqa: F401  (the table and the tile of include/pmx.h)
 
 __all__ = ["Alignment", "Attribution", "ClashReport", "DeviceAtoms", "DeviceLibrary", "FittingHits", "Enrichment", "Explanation", "LigandFingerprints", "PanelResult", "PoseFit", "ScreeningResult", "SimilarityResult", "align", "attribute", "clashes",
            "enrichment", "explain", "score_one", "screen", "screen_multi", "similar", "sweep", "topk", "device_model", "last_score_stats", "pose_fit", "ShapeReport", "shape",
            "device_shape_ref"]
-
-
-def _torch():
-    import torch
-
-    if not torch.cuda.is_available():
-        raise _ffi.PmxError("no GPU visible: pharmaconet_amd scores on an MI355X only (there is no CPU path)")
-    return torch
-
-
-def _device_index(device) -> int:
-    torch = _torch()
-    if device is None:
-        return torch.cuda.current_device()
-    dev = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
-    return dev.index if dev.index is not None else torch.cuda.current_device()
-
-
-class _ModelHandle:
-    def __init__(self, flat, device: int):
-        lib = _ffi.load()
-        self.device = device
-        self._keep = dict(
-            node_type=np.ascontiguousarray(flat.node_type, dtype=np.uint8),
-            edge_mean=np.ascontiguousarray(flat.edge_mean, dtype=np.float32),
-            edge_std=np.ascontiguousarray(flat.edge_std, dtype=np.float32),
-            cluster_nodes=np.ascontiguousarray(flat.cluster_nodes, dtype=np.uint64),
-            cluster_typemask=np.ascontiguousarray(flat.cluster_typemask, dtype=np.uint8),
-            cluster_center=np.ascontiguousarray(flat.cluster_center, dtype=np.float64),
-            cluster_size=np.ascontiguousarray(flat.cluster_size, dtype=np.float64),
-        )
-        desc = _ffi.ModelDesc(
-            flat.num_nodes,
-            flat.num_clusters,
-            *(self._keep[k].ctypes.data for k in (
-                "node_type", "edge_mean", "edge_std", "cluster_nodes", "cluster_typemask", "cluster_center", "cluster_size")),
-        )
-        handle = ctypes.c_void_p()
-        _ffi.check(lib.pmx_model_create(ctypes.byref(desc), device, ctypes.byref(handle)))
-        self.handle = handle
-        self._node_centers = None
-        self._node_sigmas = None
-
-    def node_sigmas(self, model):
-        """The model nodes' `radius` as a float64 [Nm] tensor on the handle's device (`pmx_pose_fit`'s sigmas): uploaded on first use, kept."""
-        if self._node_sigmas is None:
-            torch = _torch()
-            host = np.zeros(max(model.num_nodes, 1), dtype=np.float64)  # (never an empty buffer)
-            host[: model.num_nodes] = model.node_radii
-            self._node_sigmas = torch.from_numpy(host).to(torch.device("cuda", self.device))
-        return self._node_sigmas
-
-    def node_centers(self, model):
-        """The model nodes' `center` as a float64 [Nm, 3] tensor on the handle's device (`pmx_align`'s targets): uploaded on first use, kept."""
-        if self._node_centers is None:
-            torch = _torch()
-            host = np.zeros((max(model.num_nodes, 1), 3), dtype=np.float64)  # (never an empty buffer: a model without nodes has no pairs either)
-            host[: model.num_nodes] = model.node_centers
-            self._node_centers = torch.from_numpy(host).to(torch.device("cuda", self.device))
-        return self._node_centers
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _ffi.load().pmx_model_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
-
-def device_model(model, device=None) -> _ModelHandle:
-    """Device tables of a `PharmacophoreModel`, created once per (model, device)."""
-    dev = _device_index(device)
-    cache = model._engine_handle
-    if not isinstance(cache, dict):
-        cache = {}
-        model._engine_handle = cache
-    if dev not in cache:
-        cache[dev] = _ModelHandle(model.flat, dev)
-    return cache[dev]
-
-
-class DeviceLibrary:
-    """A packed ligand library resident in HBM (upload once, score against many models / weights)."""
-
-    def __init__(self, library: PackedLibrary, device=None):
-        self.device = _device_index(device)
-        offsets = np.ascontiguousarray(library.offsets, dtype=np.uint64)
-        data = np.ascontiguousarray(library.data, dtype=np.uint8)
-        self._n_conf = library.headers()[:, 1].copy() if len(library) else np.zeros(0, np.uint16)  # (what `explain` cuts its rows to)
-        self._n_nodes = library.headers()[:, 0].copy() if len(library) else np.zeros(0, np.uint16)  # (... and `attribute`)
-        view = _ffi.LibraryView(len(library), offsets.ctypes.data, data.ctypes.data if data.size else None, 0)
-        self._upload(view)
-
-    def _upload(self, view) -> None:
-        """pmx_library_upload of `view` on self.device: the handle and what the library says about itself."""
-        lib = _ffi.load()
-        handle = ctypes.c_void_p()
-        _ffi.check(lib.pmx_library_upload(ctypes.byref(view), self.device, ctypes.byref(handle)))
-        self.handle = handle
-        info = _ffi.LibraryInfo()
-        _ffi.check(lib.pmx_library_info_get(self.handle, ctypes.byref(info)))
-        self.num_ligands = int(info.n_ligands)
-        self.num_bytes = int(info.n_bytes)
-        self.total_conformers = int(info.total_conformers)
-        self.max_nodes = int(info.max_nodes)
-        self.max_conformers = int(info.max_conformers)
-        self.max_clusters = int(info.max_clusters)
-        self.num_unsupported = int(info.n_unsupported)
-
-    @classmethod
-    def from_device_buffers(cls, offsets, data, device=None, adopt: bool = False) -> "DeviceLibrary":
-        """A library already in device memory: `offsets` int64/uint64 [N + 1] and `data` uint8 torch tensors - copied, or with `adopt` used in
-        place (the tensors are kept alive by the object and must not be written to while it lives)."""
-        torch = _torch()
-        self = cls.__new__(cls)
-        self.device = _device_index(device if device is not None else offsets.device)
-        torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()  # (pmx_library_upload reads a complete view, on the default stream)
-        adopt = adopt and data.numel() > 0  # (an empty library has nothing to adopt: torch hands out a null pointer for it)
-        if adopt:
-            if not (offsets.is_contiguous() and data.is_contiguous()):
-                raise ValueError("adopted buffers must be contiguous")
-            self._adopted = (offsets, data)
-        view = _ffi.LibraryView(int(offsets.numel()) - 1, offsets.data_ptr(), data.data_ptr(), 2 if adopt else 1)
-        self._upload(view)
-        return self
-
-    @classmethod
-    def from_features(cls, flat, device=None, check: bool = True) -> "DeviceLibrary":
-        """Typed features -> resident library without the host packer: `pack_features_device` + adoption of its buffers.
-        `flat`: `library.flatten_features(...)` arrays (NumPy: uploaded; or torch tensors already on the device). With `check`
-        a molecule outside the device builder's fixed scratch (status 3) raises - pack such a batch with `pack_features_native`."""
-        offsets, data, status = pack_features_device(flat, device)
-        if check and bool((status == 3).any()):
-            raise _ffi.PmxError("a molecule exceeds the device packer's fixed scratch (include/pmx.h): use library.pack_features_native for this batch")
-        self = cls.from_device_buffers(offsets, data, device if device is not None else offsets.device, adopt=True)
-        self.pack_status = status
-        return self
-
-    def __len__(self) -> int:
-        return self.num_ligands
-
-    def select(self, indices) -> "DeviceLibrary":
-        """The records of ligands `indices` (any order, repeats allowed) as a resident library of their own, gathered on the device
-        (`pmx_library_select`, csrc/pmx_select.hip): record i is a byte copy of record `indices[i]`, as `PackedLibrary.select` makes it on
-        the host. `indices`: a list, a NumPy array, or an int64 torch tensor on the device (which stays there). Runs on torch's current
-        stream; the new library's buffers are torch's, adopted, so `explain`, `attribute`, `align` and `download` work on it. An index outside
-        the library is a `PmxError` that says how many there are and where the first is (IndexError for a negative one in a host list)."""
-        torch = _torch()
-        lib = _ffi.load()
-        tdev = torch.device("cuda", self.device)
-        idx = _listed_indices(indices, tdev)
-        n = int(idx.numel())
-        with torch.cuda.device(tdev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(tdev).cuda_stream)
-            offsets = torch.empty(n + 1, dtype=torch.int64, device=tdev)
-            nbytes = ctypes.c_uint64(0)
-            _ffi.check(lib.pmx_library_select(self.handle, idx.data_ptr() if n else None, n, offsets.data_ptr(), None, 0, ctypes.byref(nbytes), stream))
-            data = torch.empty(int(nbytes.value), dtype=torch.uint8, device=tdev)
-            if data.numel():
-                _ffi.check(lib.pmx_library_select(self.handle, idx.data_ptr(), n, offsets.data_ptr(), data.data_ptr(), data.numel(), ctypes.byref(nbytes), stream))
-            return DeviceLibrary.from_device_buffers(offsets, data, tdev, adopt=True)  # (waits for the stream: `idx` may go)
-
-    def buffers(self):
-        """(offsets int64 [N + 1], data uint8 [bytes]): the device buffers this library reads, as torch tensors - the adopted ones, or views of
-        the library's own (`pmx_library_buffers`), valid until `close`. Not to be written to."""
-        src = getattr(self, "_adopted", None)
-        if src is not None:
-            return src
-        torch = _torch()
-        po, pd = ctypes.c_void_p(), ctypes.c_void_p()
-        _ffi.check(_ffi.load().pmx_library_buffers(self.handle, ctypes.byref(po), ctypes.byref(pd)))
-        tdev = torch.device("cuda", self.device)
-
-        class _View:  # (torch reads foreign device memory through the CUDA array interface)
-            def __init__(self, ptr, count, typestr):
-                self.__cuda_array_interface__ = dict(shape=(count,), typestr=typestr, data=(int(ptr), False), version=2, strides=None)
-
-        offsets = torch.as_tensor(_View(po.value, self.num_ligands + 1, "<i8"), device=tdev)
-        data = torch.as_tensor(_View(pd.value, self.num_bytes, "|u1"), device=tdev) if self.num_bytes else torch.empty(0, dtype=torch.uint8, device=tdev)
-        return offsets, data
-
-    def download(self) -> PackedLibrary:
-        """The library as a host `PackedLibrary`, whatever it was made from (waits for torch's current stream)."""
-        offsets, data = self.buffers()
-        return PackedLibrary(offsets.cpu().numpy().view(np.uint64).copy(), data[: self.num_bytes].cpu().numpy().copy())
-
-    def fingerprints(self, first: int = 0, count: int | None = None, conformers=None) -> "LigandFingerprints":
-        """The ligand-side pharmacophore fingerprints and type census of ligands `[first, first + count)` (`pmx_library_fingerprints`,
-        csrc/pmx_ligand_fp.hip; the definition is in include/pmx.h). `conformers`: None for the union over a ligand's conformers - what it
-        can present - or per ligand a conformer index (a list, a NumPy array or an int32 device tensor; -1 is the union again) - a hit as
-        posed. Enqueued on torch's current stream, nothing is read back. The union fingerprints of the whole library are kept on the
-        object (32 bytes a ligand) until `close`."""
-        torch = _torch()
-        whole = first == 0 and count in (None, self.num_ligands) and conformers is None
-        if whole and getattr(self, "_fingerprints", None) is not None:
-            return self._fingerprints
-        count = self.num_ligands - first if count is None else int(count)
-        if first < 0 or count < 0 or first + count > self.num_ligands:
-            raise IndexError(f"ligands {first} .. {first + count} of a library of {self.num_ligands}")
-        tdev = torch.device("cuda", self.device)
-        conf = None
-        if conformers is not None:
-            conf = conformers if isinstance(conformers, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(conformers, dtype=np.int32).reshape(-1)))
-            conf = conf.to(tdev).to(torch.int32).reshape(-1).contiguous()
-            if int(conf.numel()) != count:
-                raise ValueError(f"{int(conf.numel())} conformers for {count} ligands")
-        with torch.cuda.device(tdev):
-            bits = torch.empty((count, _FP_WORDS), dtype=torch.int64, device=tdev)
-            counts = torch.empty((count, 8), dtype=torch.uint8, device=tdev)
-            status = torch.empty(count, dtype=torch.int32, device=tdev)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(tdev).cuda_stream)
-            _ffi.check(_ffi.load().pmx_library_fingerprints(self.handle, first, count, conf.data_ptr() if conf is not None and count else None, bits.data_ptr() if count else None,
-                                                            counts.data_ptr() if count else None, status.data_ptr() if count else None, stream))
-        out = LigandFingerprints(bits=bits, type_counts=counts, status=status, first=first, device=self.device)
-        if whole:
-            self._fingerprints = out
-        return out
-
-    def where(self, min_counts=None, max_counts=None, max_nodes: int | None = None):
-        """The ligands whose type census passes, as an int64 device tensor of library indices, ascending - ready for `select` and
-        `screen(indices=...)`. `min_counts` / `max_counts`: per type the least / most nodes that carry it, as a dict keyed by type name
-        (`TYPE_NAMES`, as `weights` are given) or a sequence of seven; `max_nodes`: the most nodes. Ligands the fingerprint pass reports
-        with a non-zero status (they cannot be scored either) never pass. A few torch operations on `fingerprints().type_counts`."""
-        torch = _torch()
-        from .constants import TYPE_ID
-
-        fps = self.fingerprints()
-        census = fps.type_counts.to(torch.int32)
-        keep = fps.status == 0
-
-        def seven(bounds, what):
-            if isinstance(bounds, dict):
-                unknown = [k for k in bounds if k not in TYPE_ID]
-                if unknown:
-                    raise ValueError(f"{what}: unknown pharmacophore type {unknown[0]!r}")
-                return {TYPE_ID[k]: int(v) for k, v in bounds.items()}
-            vals = list(bounds)
-            if len(vals) != _ffi.NUM_TYPES:
-                raise ValueError(f"{what}: a dict keyed by type name, or seven numbers")
-            return {t: int(v) for t, v in enumerate(vals)}
-
-        for t, v in (seven(min_counts, "min_counts") if min_counts is not None else {}).items():
-            keep = keep & (census[:, t] >= v)
-        for t, v in (seven(max_counts, "max_counts") if max_counts is not None else {}).items():
-            keep = keep & (census[:, t] <= v)
-        if max_nodes is not None:
-            keep = keep & (census[:, 7] <= int(max_nodes))
-        return torch.nonzero(keep).reshape(-1)
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            _ffi.load().pmx_library_destroy(self.handle)
-            self.handle = None
-        self._adopted = None
-        self._fingerprints = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceAtoms:
-    """An atom store resident in HBM (`pmx_atoms_upload`, csrc/pmx_atoms.hip): the heavy atoms of every ligand of a library, from which
-    `clashes`, `refine` and `pose_search` take a row's points on the device (`atoms=`). The radii are `pocket.atomic_number_radii`'s, copied
-    once with the store, so a gathered radius is the bits the list-of-molecules path computes."""
-
-    def __init__(self, atoms: PackedAtoms, device=None):
-        from .pocket import atomic_number_radii
-
-        self.device = _device_index(device)
-        offsets = np.ascontiguousarray(atoms.offsets, dtype=np.uint64)
-        data = np.ascontiguousarray(atoms.data, dtype=np.uint8)
-        table = np.ascontiguousarray(atomic_number_radii(np.arange(128)), dtype=np.float32)
-        view = _ffi.AtomsView(len(atoms), offsets.ctypes.data, data.ctypes.data if data.size else None)
-        lib = _ffi.load()
-        handle = ctypes.c_void_p()
-        _ffi.check(lib.pmx_atoms_upload(ctypes.byref(view), table.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), self.device, ctypes.byref(handle)))
-        self.handle = handle
-        info = _ffi.AtomsInfo()
-        _ffi.check(lib.pmx_atoms_info_get(self.handle, ctypes.byref(info)))
-        self.num_ligands = int(info.n_ligands)
-        self.num_bytes = int(info.n_bytes)
-        self.max_atoms = int(info.max_atoms)
-        self.num_empty = int(info.n_empty)
-
-    def __len__(self) -> int:
-        return self.num_ligands
-
-    def gather_device(self, lig, conf, n: int):
-        """`pmx_atoms_gather` of rows (lig[i], conf[i]), device tensors (int64, int32) of this store's device, enqueued on torch's current
-        stream: (point_off int64 [n + 1], points float32 [cap, 3], radii float32 [cap], status int32 [n]) with cap = max(n * max_atoms, 1)."""
-        torch = _torch()
-        if self.handle is None:
-            raise _ffi.PmxError("this atom store was closed")
-        tdev = torch.device("cuda", self.device)
-        cap = n * self.max_atoms
-        with torch.cuda.device(tdev):
-            off = torch.empty(n + 1, dtype=torch.int64, device=tdev)
-            points = torch.empty((max(cap, 1), 3), dtype=torch.float32, device=tdev)
-            radii = torch.empty(max(cap, 1), dtype=torch.float32, device=tdev)
-            status = torch.empty(max(n, 1), dtype=torch.int32, device=tdev)
-            stream = torch.cuda.current_stream(tdev)
-            _ffi.check(_ffi.load().pmx_atoms_gather(self.handle, lig.data_ptr(), conf.data_ptr(), n, cap, off.data_ptr(), points.data_ptr(), radii.data_ptr(), status.data_ptr(),
-                                                    ctypes.c_void_p(stream.cuda_stream)))
-        return off, points, radii, status
-
-    def gather(self, indices, conformers):
-        """The rows as host arrays, for inspection: (point_off int64 [n + 1], points float32 [total, 3], radii float32 [total], status int32 [n])."""
-        torch = _torch()
-        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
-        conf = np.ascontiguousarray(np.clip(np.asarray(conformers, dtype=np.int64).reshape(-1), -1, 2**31 - 1).astype(np.int32))
-        if len(idx) != len(conf):
-            raise ValueError("indices and conformers differ in length")
-        if (idx < 0).any():
-            raise ValueError("negative ligand index")
-        n = len(idx)
-        if n > _ffi.EXPLAIN_MAX:
-            raise ValueError("at most 65536 rows per gather (PMX_EXPLAIN_MAX)")
-        tdev = torch.device("cuda", self.device)
-        lig = torch.from_numpy(idx if n else np.zeros(1, np.int64)).to(tdev)
-        cf = torch.from_numpy(conf if n else np.zeros(1, np.int32)).to(tdev)
-        off, points, radii, status = self.gather_device(lig, cf, n)
-        torch.cuda.current_stream(tdev).synchronize()
-        off = off.cpu().numpy()
-        total = int(off[-1])
-        return off, points.cpu().numpy()[:total].copy(), radii.cpu().numpy()[:total].copy(), status.cpu().numpy()[:n].copy()
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            _ffi.load().pmx_atoms_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-@contextlib.contextmanager
-def _resident_atoms(atoms, device: int):
-    """A `DeviceAtoms` on `device` for a `DeviceAtoms` (as it is) or a `PackedAtoms` (uploaded for the call and freed after it)."""
-    if isinstance(atoms, DeviceAtoms):
-        if atoms.device != device:
-            raise _ffi.PmxError(f"the atom store is on device {atoms.device}, the call on {device}")
-        yield atoms
-        return
-    dat = DeviceAtoms(atoms, device)
-    try:
-        yield dat
-    finally:
-        dat.close()
-
-
-def _is_store(atoms) -> bool:
-    return isinstance(atoms, (DeviceAtoms, PackedAtoms))
-
-
-def _listed_indices(indices, tdev):
-    """A list of ligand indices as a flat int64 tensor on `tdev`: a list or a NumPy array is uploaded, a device tensor stays where it is."""
-    torch = _torch()
-    if isinstance(indices, torch.Tensor):
-        if indices.dtype != torch.int64:
-            raise TypeError("ligand indices as a tensor: int64")
-        return indices.to(tdev).reshape(-1).contiguous()
-    host = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
-    if (host < 0).any():
-        raise IndexError("negative ligand index")
-    return torch.from_numpy(host).to(tdev)
-
-
-@contextlib.contextmanager
-def _resident(library, device=None):
-    """`library` in HBM for the length of the block: a `DeviceLibrary` as it is, anything else `as_packed_library` accepts uploaded for the
-    block and closed behind it, once the device is done with it."""
-    if isinstance(library, DeviceLibrary):
-        yield library
-        return
-    owned = DeviceLibrary(as_packed_library(library), device)
-    try:
-        yield owned
-    finally:
-        torch = _torch()
-        torch.cuda.synchronize(torch.device("cuda", owned.device))
-        owned.close()
 
 
 FEATURE_FIELDS = ("atom_off", "atomic_num", "nbr_off", "nbr", "feat_off", "feat_type", "feat_flags", "feat_atom_off", "feat_atoms",
@@ -721,10 +340,6 @@ class ScreeningResult:
             return similar(dlib, query_indices=[hit], query_conformers=[int(ex.best_conformer[0])], k=k)
 
 
-def _weights_array(weights):
-    return (ctypes.c_float * _ffi.NUM_TYPES)(*weights_vector(weights))
-
-
 def topk(scores, k: int, base_index: int = 0, indices=None):
     """k best of a device float32 tensor: (scores [k], int64 global indices [k]); ties by ascending index.
 
@@ -1019,8 +634,6 @@ def score_one(model, ligand, weights: dict[str, float] | None = None, device=Non
     return float(result.scores.cpu()[0])
 
 
-NO_MATCH = 0xFF  # include/pmx.h pmx_explain: a level matched to None
-NO_LEVEL = 0xFE
 
 
 @dataclass
@@ -1136,21 +749,6 @@ class Explanation:
             m = self.match[i]
             keys.append(m[c] if 0 <= c < m.shape[0] else np.full(len(self.levels[i]), -1, np.int64))  # (not a conformer of the ligand: reported by the row's status)
         return rows, conf, keys
-
-
-def _record_counts(library: "DeviceLibrary", idx: np.ndarray, field: int) -> np.ndarray:
-    """Header field `field` (0: nodes, 1: conformers) of library ligands `idx` (0 outside the library): kept per ligand when the library was
-    uploaded from the host, read from the library's device records (`DeviceLibrary.buffers`) otherwise."""
-    ok = idx < len(library)
-    j = np.where(ok, idx, 0)
-    kept = getattr(library, "_n_conf" if field == 1 else "_n_nodes", None)
-    if kept is not None:
-        return np.where(ok, kept[j].astype(np.int64) if len(kept) else 0, 0)
-    torch = _torch()
-    offsets, data = library.buffers()
-    starts = offsets.view(torch.int64)[torch.from_numpy(j).to(offsets.device)] + 2 * field
-    v = data[starts].to(torch.int64) | (data[starts + 1].to(torch.int64) << 8)
-    return np.where(ok, v.cpu().numpy(), 0)
 
 
 def normalize_constraint(require=None, exclude=None, num_clusters: int | None = None):
@@ -1669,7 +1267,6 @@ def screen_constrained(model, library, topk: int, require=None, exclude=None, we
 KEY_INVALID = 4  # include/pmx.h PMX_LIGAND_KEY_INVALID
 
 
-_MAX_LEVELS, _MAX_NODES = 20, 64  # PMX_MAX_LEVELS, PMX_MAX_LIGAND_NODES
 
 
 def _listed_rows(indices, conformers, keys, what: str):
@@ -1792,84 +1389,6 @@ def attribute(model, library, indices, conformers, keys, weights: dict[str, floa
                        levels=out_lv, status=st)
 
 
-@dataclass
-class Alignment:
-    """What `align` returns: one row per (ligand, conformer, key) - the rigid motion that puts the matched nodes of the conformer onto the
-    pharmacophore points of the model nodes they are matched to, and how well (definitions: `pmx_align` in include/pmx.h). All float64.
-
-    rotation[i]     [3, 3] proper rotation R        translation[i]  [3] t: a point x of the conformer sits at R x + t in the pocket
-    weight[i]       W, the sum of the pair weights  sse[i]          sum over pairs of w |R x_u + t - y_m|^2
-    rmsd[i]         sqrt(sse / W)                   rmsd_nodes[i]   the same with every node's targets replaced by their weighted centroid
-    scale[i]        E0 = sum w (|x_u - xbar|^2 + |y_m - ybar|^2)
-    gap[i]          lambda_1 - lambda_2 of Horn's matrix: where gap / scale is tiny (one fitted node, nodes on a line) the rotation is not unique
-    node[i]         [n]: per node of the packed record its distance from its targets' centroid after the fit, -1 for a node without a pair
-    n_nodes[i], n_pairs[i]  fitted nodes and pairs  levels[i]       int [nl]: the ligand cluster behind each tree level
-    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer of the ligand, or a match that is no candidate
-                    of its level); every float of such a row is NaN. A valid row without pairs has R = I, t = 0 and zeros."""
-
-    indices: np.ndarray
-    conformers: np.ndarray
-    rotation: np.ndarray
-    translation: np.ndarray
-    rmsd: np.ndarray
-    rmsd_nodes: np.ndarray
-    weight: np.ndarray
-    sse: np.ndarray
-    scale: np.ndarray
-    gap: np.ndarray
-    node: list
-    n_nodes: np.ndarray
-    n_pairs: np.ndarray
-    levels: list
-    status: np.ndarray
-    rows: "np.ndarray | None" = None  # `Explanation.poses`: the explanation's row behind each row
-
-    def __len__(self) -> int:
-        return len(self.indices)
-
-    def transform(self, i: int, positions) -> np.ndarray:
-        """Row i's motion applied to any [..., 3] array of points of the conformer's frame - a whole molecule's atoms, say: positions @ R.T + t."""
-        return np.asarray(positions, dtype=np.float64) @ self.rotation[i].T + self.translation[i]
-
-    def clashes(self, pocket_or_model, library=None, atoms=None, **kw) -> "ClashReport":
-        """These poses checked against the pocket's atoms (`clashes`): row i of the report is row i of the alignment, and a row that is
-        not OK passes through with status 4. `pocket_or_model`: a `pocket.PocketAtoms`, or a model that carries its protein
-        (`PharmacophoreModel.pocket_atoms`). With `library` alone the rows' own pharmacophore nodes are checked (node mode: nothing but the
-        resident records is read). With `atoms` - per row the `LigandFeatures` / `Ligand` the record was packed from - the molecule's atoms
-        at the row's conformer are, hydrogens left out, with Bondi radii by atomic number (point mode). Further arguments as `clashes` takes them."""
-        return _check_poses(self, "Alignment.clashes", pocket_or_model, library, atoms, kw)
-
-    def refine(self, pocket_or_model, library=None, atoms=None, **kw) -> "RefinedPoses":
-        """These poses moved out of the pocket's atoms and held near the fit (`refine`): row i of the result is row i of the alignment, and
-        a row that is not OK passes through with status 4. With `library` alone the points and the anchors are the rows' pharmacophore
-        nodes (node mode); with `atoms` - per row the molecule the record was packed from - they are its heavy atoms with Bondi radii
-        (point mode). Further arguments (`restraint`, `max_iter`, `ftol`, `tolerance`, `node_radius`) as `refine` takes them."""
-        pocket, source = _pose_source(self, "Alignment.refine", pocket_or_model, library, atoms)
-        out = refine(pocket, rotation=self.rotation, translation=self.translation, **source, **kw)
-        if out.indices is None:
-            out.indices, out.conformers = self.indices.copy(), np.asarray(self.conformers, dtype=np.int64).copy()
-        return out
-
-    def pose_fit(self, model, library, keys=None, **kw) -> "PoseFit":
-        """How well these poses sit on the model's hotspots (`pose_fit`): row i of the result is row i of the alignment, and a row that
-        is not OK passes through with status 4. `keys`: the rows' keys, for the pairs the fit was made on (key mode); None for every pair
-        of matching type (free mode). Further arguments (`weights`, `centers`, `sigmas`) as `pose_fit` takes them."""
-        return pose_fit(model, library, self.indices, self.conformers, self.rotation, self.translation, keys=keys, **kw)
-
-    def shape(self, reference, library=None, atoms=None, **kw) -> "ShapeReport":
-        """These poses compared with a known ligand (`shape`; `reference` a `shape.ReferenceLigand`): row i of the report is row i of the
-        alignment, and a row that is not OK passes through with status 4. The points are the rows' pharmacophore nodes with `library`
-        alone, the molecules' heavy atoms with `atoms` (per row the molecule, or the library's atom store), as `Alignment.clashes` takes
-        them. Further arguments (`node_radius`, `cover`) as `shape` takes them."""
-        return _shape_poses(self, "Alignment.shape", reference, library, atoms, kw)
-
-    def overlay(self, reference, library=None, atoms=None, **kw) -> "ShapeOverlay":
-        """These poses moved to their nearest shape match with a known ligand (`overlay` from each row's own motion): how far is the fit
-        from it, and how much overlap does it lack? Row i of the result is row i of the alignment; the points as `Alignment.shape` takes
-        them. Further arguments (`node_radius`, `ftol`, `max_iter`) as `overlay` takes them."""
-        return _overlay_poses(self, "Alignment.overlay", reference, library, atoms, kw)
-
-
 def align(model, library, indices, conformers, keys, weights: dict[str, float] | None = None, device=None) -> Alignment:
     """The rigid fit (`pmx_align`, csrc/pmx_rows.hip) of library ligand `indices[i]`'s conformer `conformers[i]` under the match `keys[i]`, rows as
     `attribute` takes them. The key need not be a leaf of the ligand's tree. At most 65536 rows; any order, repeats allowed. `library` is a
@@ -1920,942 +1439,6 @@ class FittingHits:
 
     def __len__(self) -> int:
         return len(self.indices)
-
-
-def _atomic_numbers(mol) -> np.ndarray:
-    """Atomic numbers of a `LigandFeatures` (`atomic_nums`) or a `Ligand` (its toolkit answers)."""
-    z = getattr(mol, "atomic_nums", None)
-    if z is None:
-        z = mol.answers["atomic_num"]
-    return np.asarray(z, dtype=np.int64).reshape(-1)
-
-
-@dataclass
-class ClashReport:
-    """What `clashes` returns: one row per posed set of points (definitions: `pmx_pose_clash` in include/pmx.h).
-
-    clearance[i]    float64: the largest penetration over all (point, atom) pairs - negative when nothing clashes, -inf without a pair
-    overlap[i]      float64: the sum of penetration^2 over the clashing pairs
-    n_points[i], n_clashing[i], n_pairs[i], n_contacts[i]   points, points with a clashing pair, clashing pairs, points that touch an atom
-    worst[i]        (point, atom) of clearance[i]; (-1, -1) without a pair
-    point_penetration[i], point_atom[i]   per point its largest penetration and the atom that attains it
-    contact_fingerprint   uint64 [n, 4]: bit g says an atom of residue group g touches the row (`PocketAtoms.residue_labels[g]`)
-    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer of the ligand, or a motion that is not
-                    finite - a row of an `Alignment` that was not OK); such a row has NaN, zero counts and an empty fingerprint"""
-
-    clearance: np.ndarray
-    overlap: np.ndarray
-    n_points: np.ndarray
-    n_clashing: np.ndarray
-    n_pairs: np.ndarray
-    n_contacts: np.ndarray
-    worst: np.ndarray
-    point_penetration: list
-    point_atom: list
-    contact_fingerprint: np.ndarray
-    status: np.ndarray
-    device: "int | None" = None  # where `similarity` and `leaders` run
-
-    def __len__(self) -> int:
-        return len(self.status)
-
-    def ok(self, max_clashing: int = 0) -> np.ndarray:
-        """bool [n]: status 0 and at most `max_clashing` points with a clashing pair."""
-        return (self.status == 0) & (self.n_clashing <= int(max_clashing))
-
-    def residues(self, i: int, pocket) -> list[str]:
-        """The residues row i touches, by `pocket`'s labels."""
-        return pocket.residues(self.contact_fingerprint[i])
-
-    def atom_label(self, i: int, pocket) -> str:
-        """The pocket atom of row i's worst pair (`A:CYS12:SG`); '' without a pair."""
-        return pocket.atom_label(int(self.worst[i, 1]))
-
-    def similarity(self, other: "ClashReport | None" = None) -> np.ndarray:
-        """Tanimoto similarity of the contact fingerprints, on the GPU (`fingerprint_similarity`)."""
-        return fingerprint_similarity(self.contact_fingerprint, None if other is None else other.contact_fingerprint, device=self.device)
-
-    def leaders(self, threshold: float = 0.7, max_leaders: int = 2048):
-        """Sphere exclusion over the rows in their order by contact fingerprint (`fingerprint_leaders`): (leaders, leader_of)."""
-        return fingerprint_leaders(self.contact_fingerprint, threshold=threshold, max_leaders=max_leaders, device=self.device)
-
-
-class _PocketHandle:
-    def __init__(self, pocket, device: int):
-        handle = ctypes.c_void_p()
-        xyz, radius, group = (np.ascontiguousarray(pocket.xyz, dtype=np.float32), np.ascontiguousarray(pocket.radius, dtype=np.float32),
-                              np.ascontiguousarray(pocket.group, dtype=np.uint16))
-        n = len(radius)
-        _ffi.check(_ffi.load().pmx_pocket_create(xyz.ctypes.data if n else None, radius.ctypes.data if n else None, group.ctypes.data if n else None, n, device,
-                                                 ctypes.byref(handle)))
-        self.handle, self.device = handle, device
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _ffi.load().pmx_pocket_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
-
-def device_pocket(pocket, device=None) -> _PocketHandle:
-    """The device copy of a `pocket.PocketAtoms`, made once per (pocket, device) and freed with the object."""
-    dev = _device_index(device)
-    if dev not in pocket._device:
-        pocket._device[dev] = _PocketHandle(pocket, dev)
-    return pocket._device[dev]
-
-
-class _PoseRows:
-    """The rows `clashes` and `refine` share: motions and one source of points, checked and laid out as `pmx_pose_clash` and
-    `pmx_pose_refine` take them. `what` names the caller in a message."""
-
-    def __init__(self, what, library, indices, conformers, rotation, translation, points, point_radii, atoms=None):
-        self.rot = np.ascontiguousarray(np.asarray(rotation, dtype=np.float64).reshape(-1, 3, 3))
-        self.trans = np.ascontiguousarray(np.asarray(translation, dtype=np.float64).reshape(-1, 3))
-        n = self.n = len(self.rot)
-        if len(self.trans) != n:
-            raise ValueError("rotation and translation differ in length")
-        if n > 65536:
-            raise ValueError(f"at most 65536 rows per {what} call (PMX_EXPLAIN_MAX)")
-        self.node_mode = library is not None
-        self.store = atoms  # a `DeviceAtoms` / `PackedAtoms`: point mode, the points gathered on the device
-        if atoms is not None:
-            if not _is_store(atoms):
-                raise TypeError(f"{what}: atoms is a DeviceAtoms or a PackedAtoms")
-            if self.node_mode or points is not None or point_radii is not None:
-                raise ValueError(f"{what}: a library, points or an atom store - exactly one source of points")
-        elif self.node_mode == (points is not None):
-            raise ValueError(f"{what}: a library with indices and conformers, or points - one of the two")
-        self.idx = self.conf = self.off = self.flat = self.rad = self.gstatus = None
-        if self.node_mode or atoms is not None:
-            self.idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64).reshape(-1))
-            self.conf = np.ascontiguousarray(np.clip(np.asarray(conformers, dtype=np.int64).reshape(-1), -1, 2**31 - 1).astype(np.int32))
-            if len(self.idx) != n or len(self.conf) != n:
-                raise ValueError("indices, conformers and the motions differ in length")
-            if (self.idx < 0).any():
-                raise ValueError("negative ligand index")
-        else:
-            if len(points) != n:
-                raise ValueError(f"{len(points)} point sets for {n} motions")
-            self.off, self.flat, pts = _ragged(points, np.float32, 3)
-            if point_radii is not None:
-                if len(point_radii) != n:
-                    raise ValueError(f"{len(point_radii)} radius lists for {n} point sets")
-                _, self.rad, rs = _ragged(point_radii, np.float32, None)
-                if any(len(r) != len(p) for r, p in zip(rs, pts)):
-                    raise ValueError("a list of radii differs in length from its points")
-
-    def upload(self, tdev, dat: "DeviceAtoms | None" = None):
-        """The device tensors (kept alive by the caller) and the seven source and motion arguments that follow the pocket and the library.
-        With an atom store (`dat`, resident on `tdev`) the points are gathered there; a row whose gather status is not OK has no points and
-        gets a motion of NaN, so that the call reports it as it reports any row that is not OK (`finish` puts the gather's status in)."""
-        torch = _torch()
-        n = self.n
-        up = lambda a: torch.from_numpy(a).to(tdev)  # noqa: E731
-        t_rot, t_trans = up(self.rot.reshape(-1, 9) if n else np.zeros((1, 9))), up(self.trans if n else np.zeros((1, 3)))
-        if dat is not None:
-            t_a, t_b = up(self.idx if n else np.zeros(1, np.int64)), up(self.conf if n else np.zeros(1, np.int32))
-            off, pts, rad, self.gstatus = dat.gather_device(t_a, t_b, n)
-            if n:
-                bad = (self.gstatus != 0)[:, None]
-                t_rot, t_trans = t_rot.masked_fill(bad, float("nan")), t_trans.masked_fill(bad, float("nan"))
-            self.slots, self._off_dev = max(n * dat.max_atoms, 1), off
-            keep, src = (t_rot, t_trans, t_a, t_b, off, pts, rad), (None, None, off.data_ptr(), pts.data_ptr(), rad.data_ptr())
-            return keep, src, (t_rot.data_ptr(), t_trans.data_ptr())
-        if self.node_mode:
-            t_a, t_b = up(self.idx if n else np.zeros(1, np.int64)), up(self.conf if n else np.zeros(1, np.int32))
-            keep, src = (t_rot, t_trans, t_a, t_b), (t_a.data_ptr(), t_b.data_ptr(), None, None, None)
-        else:
-            t_a, t_b, t_c = up(self.off), up(self.flat), (up(self.rad) if self.rad is not None else None)
-            keep, src = (t_rot, t_trans, t_a, t_b, t_c), (None, None, t_a.data_ptr(), t_b.data_ptr(), t_c.data_ptr() if t_c is not None else None)
-        return keep, src, (t_rot.data_ptr(), t_trans.data_ptr())
-
-
-    def finish(self, status: np.ndarray) -> np.ndarray:
-        """After the wait: the rows' statuses with the gather's where that is not OK, and - store mode - the offsets of the rows' points."""
-        if self.gstatus is None:
-            return status
-        self.off = self._off_dev.cpu().numpy().astype(np.int64)
-        g = self.gstatus.cpu().numpy()[: self.n].astype(np.int32)
-        return np.where(g != 0, g, status).astype(np.int32)
-
-
-def _ragged(lists, dtype, width):
-    """(offsets int64 [n + 1], the rows back to back and never empty, the rows) of a list of arrays of [m_i, width] (or [m_i] for width None)."""
-    rows = [np.asarray(p, dtype=dtype).reshape((-1, width) if width else (-1,)) for p in lists]
-    off = np.zeros(len(rows) + 1, dtype=np.int64)
-    off[1:] = np.cumsum([len(p) for p in rows])
-    flat = np.ascontiguousarray(np.concatenate(rows + [np.zeros((1, width) if width else 1, dtype)]))  # (never an empty buffer)
-    return off, flat, rows
-
-
-def clashes(pocket, library=None, indices=None, conformers=None, rotation=None, translation=None, points=None, point_radii=None, node_radius: float = 1.0,
-            tolerance: float = 0.5, contact: float = 4.5, device=None, atoms=None) -> ClashReport:
-    """Posed rows against the pocket's atoms (`pmx_pose_clash`, csrc/pmx_pocket.hip): row i is a set of points moved by `rotation[i]`
-    [3, 3] and `translation[i]` [3] - what `Alignment` holds - and a pair (point, atom) clashes when the two spheres overlap by more than
-    `tolerance`, touches when the centres are closer than `contact`.
-      node mode   `library` (a `DeviceLibrary` or anything `as_packed_library` accepts), `indices`, `conformers`: the pharmacophore nodes of
-                  library ligand indices[i] at conformer conformers[i], each a sphere of `node_radius`
-      point mode  `points`: a list of [m_i, 3] arrays, any points of the conformer's frame - a whole molecule's atoms; `point_radii`: a
-                  matching list of radii (`pocket.atomic_number_radii` makes them from atomic numbers), or None for `node_radius` each
-      atom store  `atoms` (a `DeviceAtoms`, or a `PackedAtoms` uploaded for the call), `indices`, `conformers`: the heavy atoms of ligand
-                  indices[i] at conformer conformers[i] with Bondi radii, gathered on the device (`pmx_atoms_gather`) - point mode without
-                  host arrays. A row the store has no atoms for (status 1), or whose conformer the record lacks (status 4), is not OK
-    Exactly one of the three. At most 65536 rows. Runs on torch's current stream of the device and waits for it."""
-    torch = _torch()
-    lib = _ffi.load()
-    rows = _PoseRows("clashes", library, indices, conformers, rotation, translation, points, point_radii, atoms)
-    n, node_mode = rows.n, rows.node_mode
-    m = max(n, 1)
-    with contextlib.ExitStack() as stack:
-        dlib = stack.enter_context(_resident(library, device)) if node_mode else None
-        dev = dlib.device if node_mode else atoms.device if isinstance(atoms, DeviceAtoms) else _device_index(device)
-        dat = stack.enter_context(_resident_atoms(atoms, dev)) if atoms is not None else None
-        ph = device_pocket(pocket, dev)
-        tdev = torch.device("cuda", dev)
-        with torch.cuda.device(tdev):
-            keep, src, motion = rows.upload(tdev, dat)
-            slots = m * _MAX_NODES if node_mode else rows.slots if dat is not None else max(int(rows.off[-1]), 1)
-            summary = torch.empty((m, 4), dtype=torch.float64, device=tdev)
-            count = torch.empty((m, 6), dtype=torch.int32, device=tdev)
-            ppen = torch.empty(slots, dtype=torch.float64, device=tdev)
-            patom = torch.empty(slots, dtype=torch.int32, device=tdev)
-            fp = torch.empty((m, _FP_WORDS), dtype=torch.int64, device=tdev)
-            status = torch.empty(m, dtype=torch.int32, device=tdev)
-            stream = torch.cuda.current_stream(tdev)
-            _ffi.check(lib.pmx_pose_clash(ph.handle, dlib.handle if node_mode else None, *src, *motion, n, float(node_radius), float(tolerance), float(contact),
-                                          summary.data_ptr(), count.data_ptr(), ppen.data_ptr(), patom.data_ptr(), fp.data_ptr(), status.data_ptr(),
-                                          ctypes.c_void_p(stream.cuda_stream)))
-            stream.synchronize()
-            del keep
-        st = rows.finish(status.cpu().numpy()[:n].astype(np.int32))
-        if node_mode:
-            nn = _record_counts(dlib, rows.idx, 0)
-            lo = np.arange(n, dtype=np.int64) * _MAX_NODES
-            hi = lo + np.where(st != 1, nn, 0)
-        else:
-            lo, hi = rows.off[:-1], rows.off[1:]
-    sm, cn = summary.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
-    pp, pa = ppen.cpu().numpy(), patom.cpu().numpy().astype(np.int64)
-    return ClashReport(clearance=sm[:, 0].copy(), overlap=sm[:, 1].copy(), n_points=cn[:, 0].copy(), n_clashing=cn[:, 1].copy(), n_pairs=cn[:, 2].copy(),
-                       n_contacts=cn[:, 3].copy(), worst=cn[:, 4:6].copy(), point_penetration=[pp[lo[i]: hi[i]].copy() for i in range(n)],
-                       point_atom=[pa[lo[i]: hi[i]].copy() for i in range(n)], contact_fingerprint=fp.cpu().numpy()[:n].view(np.uint64).copy(), status=st, device=dev)
-
-
-@dataclass
-class ShapeReport:
-    """What `shape` returns: one row per posed set of points against a reference ligand (definitions: `pmx_pose_shape` in include/pmx.h).
-    Floats are float64.
-
-    overlap[i], self_overlap[i], reference_overlap[i]   O_AB, O_AA, O_BB: the first-order Gaussian overlap volumes (row with reference, row
-                    with itself, reference with itself), A^3. They over-count a molecule's volume; the ratios below largely cancel that
-    tanimoto[i]     O_AB / (O_AA + O_BB - O_AB): the shape Tanimoto, exactly 1 for the reference's own atoms in place
-    reference_fraction[i]   O_AB / O_BB: how much of the known ligand the row fills
-    fit_fraction[i]         O_AB / O_AA: how much of the row lies inside the known ligand
-    rms_to_reference[i]     the root mean square, over the row's points, of the distance to the nearest reference atom (NaN without a point)
-    rms_from_reference[i]   the same over the reference atoms, to the nearest point of the row (+inf without a point)
-    rmsd_in_order[i]        atom-for-atom RMSD, point a against reference atom a, where the row has exactly as many points as the
-                    reference has atoms - the same molecule in the same atom order - and NaN otherwise
-    n_points[i], n_covered[i], n_reference_covered[i]   points, points within `cover` of a reference atom, reference atoms within `cover`
-                    of a point
-    point_distance[i], point_reference_atom[i]   per point the distance to its nearest reference atom, and that atom
-    reference_distance[i], reference_point[i]    per reference atom the distance to the row's nearest point, and that point
-    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer of the ligand, a motion that is not
-                    finite, a radius that is not a finite number > 0); such a row has NaN, zero counts and -1"""
-
-    overlap: np.ndarray
-    self_overlap: np.ndarray
-    reference_overlap: np.ndarray
-    tanimoto: np.ndarray
-    reference_fraction: np.ndarray
-    fit_fraction: np.ndarray
-    rms_to_reference: np.ndarray
-    rms_from_reference: np.ndarray
-    rmsd_in_order: np.ndarray
-    n_points: np.ndarray
-    n_covered: np.ndarray
-    n_reference_covered: np.ndarray
-    point_distance: list
-    point_reference_atom: list
-    reference_distance: list
-    reference_point: list
-    status: np.ndarray
-
-    def __len__(self) -> int:
-        return len(self.status)
-
-
-class _ShapeRefHandle:
-    def __init__(self, reference, device: int):
-        handle = ctypes.c_void_p()
-        xyz, radius = np.ascontiguousarray(reference.xyz, dtype=np.float32), np.ascontiguousarray(reference.radius, dtype=np.float32)
-        _ffi.check(_ffi.load().pmx_shape_ref_create(xyz.ctypes.data, radius.ctypes.data, len(radius), device, ctypes.byref(handle)))
-        self.handle, self.device, self.m = handle, device, len(radius)
-
-    @property
-    def self_overlap(self) -> float:
-        out = ctypes.c_double()
-        _ffi.check(_ffi.load().pmx_shape_ref_self(self.handle, ctypes.byref(out)))
-        return out.value
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _ffi.load().pmx_shape_ref_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
-
-def device_shape_ref(reference, device=None) -> _ShapeRefHandle:
-    """The device copy of a `shape.ReferenceLigand`, made once per (reference, device) and freed with the object."""
-    dev = _device_index(device)
-    if dev not in reference._device:
-        reference._device[dev] = _ShapeRefHandle(reference, dev)
-    return reference._device[dev]
-
-
-def shape(reference, library=None, indices=None, conformers=None, rotation=None, translation=None, points=None, point_radii=None, atoms=None,
-          node_radius: float = 1.0, cover: float = 2.0, device=None) -> ShapeReport:
-    """Posed rows against a known ligand (`pmx_pose_shape`, csrc/pmx_pose_shape.hip): row i is a set of points moved by `rotation[i]` and
-    `translation[i]` - what `Alignment` holds - and `reference` a `shape.ReferenceLigand` in the pocket's frame. The Gaussian shape overlap
-    of the two, its Tanimoto and Tversky ratios, and nearest-atom distances both ways; a point (a reference atom) is covered when its
-    nearest counterpart is closer than `cover`. The pose is judged where it is: nothing is moved. The three sources of points - node mode
-    (`library`, `indices`, `conformers`, each node a sphere of `node_radius`), point mode (`points`, `point_radii`) and the atom store
-    (`atoms`, `indices`, `conformers`) - are those of `clashes`; a row holds at most 256 points. Exactly one of the three. At most 65536
-    rows. Runs on torch's current stream of the device and waits for it."""
-    torch = _torch()
-    lib = _ffi.load()
-    rows = _PoseRows("shape", library, indices, conformers, rotation, translation, points, point_radii, atoms)
-    n, node_mode = rows.n, rows.node_mode
-    m = max(n, 1)
-    with contextlib.ExitStack() as stack:
-        dlib = stack.enter_context(_resident(library, device)) if node_mode else None
-        dev = dlib.device if node_mode else atoms.device if isinstance(atoms, DeviceAtoms) else _device_index(device)
-        dat = stack.enter_context(_resident_atoms(atoms, dev)) if atoms is not None else None
-        rh = device_shape_ref(reference, dev)
-        tdev = torch.device("cuda", dev)
-        with torch.cuda.device(tdev):
-            keep, src, motion = rows.upload(tdev, dat)
-            slots = m * _MAX_NODES if node_mode else rows.slots if dat is not None else max(int(rows.off[-1]), 1)
-            summary = torch.empty((m, 10), dtype=torch.float64, device=tdev)
-            count = torch.empty((m, 4), dtype=torch.int32, device=tdev)
-            pnear = torch.empty(slots, dtype=torch.float64, device=tdev)
-            pref = torch.empty(slots, dtype=torch.int32, device=tdev)
-            rnear = torch.empty((m, _ffi.MAX_LIGAND_ATOMS), dtype=torch.float64, device=tdev)
-            rpoint = torch.empty((m, _ffi.MAX_LIGAND_ATOMS), dtype=torch.int32, device=tdev)
-            status = torch.empty(m, dtype=torch.int32, device=tdev)
-            stream = torch.cuda.current_stream(tdev)
-            _ffi.check(lib.pmx_pose_shape(rh.handle, dlib.handle if node_mode else None, *src, *motion, n, float(node_radius), float(cover), summary.data_ptr(),
-                                          count.data_ptr(), pnear.data_ptr(), pref.data_ptr(), rnear.data_ptr(), rpoint.data_ptr(), status.data_ptr(),
-                                          ctypes.c_void_p(stream.cuda_stream)))
-            stream.synchronize()
-            del keep
-        st = rows.finish(status.cpu().numpy()[:n].astype(np.int32))
-        if node_mode:
-            nn = _record_counts(dlib, rows.idx, 0)
-            lo = np.arange(n, dtype=np.int64) * _MAX_NODES
-            hi = lo + np.where(st != 1, nn, 0)
-        else:
-            lo, hi = rows.off[:-1], rows.off[1:]
-    sm, cn = summary.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
-    pn, pr = pnear.cpu().numpy(), pref.cpu().numpy().astype(np.int64)
-    rn, rp = rnear.cpu().numpy()[:n, : rh.m], rpoint.cpu().numpy()[:n, : rh.m].astype(np.int64)
-    return ShapeReport(overlap=sm[:, 0].copy(), self_overlap=sm[:, 1].copy(), reference_overlap=sm[:, 2].copy(), tanimoto=sm[:, 3].copy(),
-                       reference_fraction=sm[:, 4].copy(), fit_fraction=sm[:, 5].copy(), rms_to_reference=sm[:, 6].copy(), rms_from_reference=sm[:, 7].copy(),
-                       rmsd_in_order=sm[:, 8].copy(), n_points=cn[:, 0].copy(), n_covered=cn[:, 1].copy(), n_reference_covered=cn[:, 2].copy(),
-                       point_distance=[pn[lo[i]: hi[i]].copy() for i in range(n)], point_reference_atom=[pr[lo[i]: hi[i]].copy() for i in range(n)],
-                       reference_distance=[rn[i].copy() for i in range(n)], reference_point=[rp[i].copy() for i in range(n)], status=st)
-
-
-def _shape_poses(poses, what, reference, library, atoms, kw) -> "ShapeReport":
-    _, source = _pose_source(poses, what, None, library, atoms)
-    return shape(reference, rotation=poses.rotation, translation=poses.translation, **source, **kw)
-
-
-@dataclass
-class RefinedPoses:
-    """What `refine` returns: one row per posed set of points (definitions: `pmx_pose_refine` in include/pmx.h). Floats are float64.
-
-    rotation[i], translation[i]   the refined motion: a point x of the conformer sits at R x + t. The input's own bits where nothing clashed
-    overlap_start[i], overlap[i]  the overlap (`ClashReport.overlap`) at the input motion and at the refined one
-    restraint_start[i], restraint_energy[i]   sum over the anchors of w |R a + t - b|^2, before and after (unscaled by `restraint`)
-    anchor_rmsd[i]  sqrt(restraint_energy / sum w): how far the anchors moved off their targets
-    angle[i], shift[i]   the net rotation from the input motion in rad, and how far the centroid of the posed points moved
-    iterations[i], accepted[i]    evaluations after the first, and the steps among them that lowered the energy
-    stop[i]         0 nothing clashed, 1 converged (decrease <= ftol E), 2 out of iterations, 3 no step found (lambda > 1e8); -1 not OK
-    n_pairs[i]      clashing pairs at the refined motion
-    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer, a motion that is not finite, a weight
-                    that is negative or not finite); such a row has NaN floats, zero counts and stop -1
-    indices, conformers   node mode: the rows' ligands and conformers (None in point mode)"""
-
-    rotation: np.ndarray
-    translation: np.ndarray
-    overlap_start: np.ndarray
-    overlap: np.ndarray
-    restraint_start: np.ndarray
-    restraint_energy: np.ndarray
-    anchor_rmsd: np.ndarray
-    angle: np.ndarray
-    shift: np.ndarray
-    iterations: np.ndarray
-    accepted: np.ndarray
-    stop: np.ndarray
-    n_pairs: np.ndarray
-    status: np.ndarray
-    indices: "np.ndarray | None" = None
-    conformers: "np.ndarray | None" = None
-
-    def __len__(self) -> int:
-        return len(self.status)
-
-    def transform(self, i: int, positions) -> np.ndarray:
-        """Row i's refined motion applied to any [..., 3] array of points of the conformer's frame: positions @ R.T + t."""
-        return np.asarray(positions, dtype=np.float64) @ self.rotation[i].T + self.translation[i]
-
-    def clashes(self, pocket_or_model, library=None, atoms=None, **kw) -> "ClashReport":
-        """The refined poses checked against the pocket's atoms, as `Alignment.clashes` checks the fitted ones: the rows' nodes with
-        `library`, the molecules' heavy atoms with `atoms`. A row that is not OK passes through with status 4."""
-        return _check_poses(self, "RefinedPoses.clashes", pocket_or_model, library, atoms, kw)
-
-    def pose_fit(self, model, library, keys=None, **kw) -> "PoseFit":
-        """How well the refined poses sit on the model's hotspots, as `Alignment.pose_fit` says it of the fitted ones (node mode rows
-        only: the rows' ligands and conformers). A row the refinement left untouched has the bits it had before."""
-        if self.indices is None:
-            raise ValueError("RefinedPoses.pose_fit: these rows are points of the caller's, not ligands of a library")
-        return pose_fit(model, library, self.indices, self.conformers, self.rotation, self.translation, keys=keys, **kw)
-
-    def shape(self, reference, library=None, atoms=None, **kw) -> "ShapeReport":
-        """The refined poses compared with a known ligand, as `Alignment.shape` compares the fitted ones: the rows' nodes with `library`,
-        the molecules' heavy atoms with `atoms`. A row that is not OK passes through with status 4."""
-        return _shape_poses(self, "RefinedPoses.shape", reference, library, atoms, kw)
-
-    def overlay(self, reference, library=None, atoms=None, **kw) -> "ShapeOverlay":
-        """The refined poses moved to their nearest shape match with a known ligand, as `Alignment.overlay` moves the fitted ones."""
-        return _overlay_poses(self, "RefinedPoses.overlay", reference, library, atoms, kw)
-
-
-@dataclass
-class ShapeOverlay:
-    """What `overlay` returns: one row per hit - the rigid motion that maximises its Gaussian shape overlap with a reference ligand from
-    where it started (definitions: `pmx_shape_overlay` and `pmx_shape_starts` in include/pmx.h). Floats are float64. Rigid only, shape
-    only (no atom types, no hydrogens), and a local maximum: the one the start leads to.
-
-    rotation[i], translation[i]   the overlaid motion: a point x of the conformer sits at R x + t. The start's own bits where no step was taken
-    overlap_start[i], overlap[i]  O_AB at the start motion and at the overlaid one (never lower)
-    self_overlap[i], reference_overlap[i]   O_AA and O_BB, which no rigid motion changes
-    tanimoto_start[i], tanimoto[i]   O_AB / (O_AA + O_BB - O_AB) before and after
-    angle[i], shift[i]   the net rotation from the start in rad, and how far the centroid of the posed points moved
-    iterations[i], accepted[i]    trial motions, and the ones among them that raised O_AB
-    stop[i]         0 nothing to follow (no point, or O_AB = 0: too far away), 1 converged (increase <= ftol O_AB), 2 out of iterations,
-                    3 no step found (lambda > 1e8: a row that starts at a maximum ends so); -1 not OK
-    n_points[i]     the row's points
-    start[i]        with `starts=4`: which inertial start (0: the frames laid on each other, 1 .. 3: and a half turn about the row's
-                    first, second or third axis) was kept - the one of highest final Tanimoto, the lower among equals; -1 with `starts=0`
-    start_tanimoto  [n, starts]: every start's final Tanimoto
-    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID); such a row has NaN floats, zero counts and stop -1
-    indices, conformers   the rows' ligands and conformers (None for points of the caller's)"""
-
-    rotation: np.ndarray
-    translation: np.ndarray
-    overlap_start: np.ndarray
-    overlap: np.ndarray
-    self_overlap: np.ndarray
-    reference_overlap: np.ndarray
-    tanimoto_start: np.ndarray
-    tanimoto: np.ndarray
-    angle: np.ndarray
-    shift: np.ndarray
-    iterations: np.ndarray
-    accepted: np.ndarray
-    stop: np.ndarray
-    n_points: np.ndarray
-    start: np.ndarray
-    start_tanimoto: np.ndarray
-    status: np.ndarray
-    indices: "np.ndarray | None" = None
-    conformers: "np.ndarray | None" = None
-
-    def __len__(self) -> int:
-        return len(self.status)
-
-    def transform(self, i: int, positions) -> np.ndarray:
-        """Row i's overlaid motion applied to any [..., 3] array of points of the conformer's frame: positions @ R.T + t."""
-        return np.asarray(positions, dtype=np.float64) @ self.rotation[i].T + self.translation[i]
-
-    def shape(self, reference, library=None, atoms=None, **kw) -> "ShapeReport":
-        """The overlaid poses compared with a known ligand, as `Alignment.shape` compares the fitted ones."""
-        return _shape_poses(self, "ShapeOverlay.shape", reference, library, atoms, kw)
-
-    def clashes(self, pocket_or_model, library=None, atoms=None, **kw) -> "ClashReport":
-        """The overlaid poses checked against the pocket's atoms, as `Alignment.clashes` checks the fitted ones: a shape overlay knows
-        nothing of the protein."""
-        return _check_poses(self, "ShapeOverlay.clashes", pocket_or_model, library, atoms, kw)
-
-    def refine(self, pocket_or_model, library=None, atoms=None, **kw) -> "RefinedPoses":
-        """The overlaid poses moved out of the pocket's atoms and held near the overlay, as `Alignment.refine` does it of the fitted ones."""
-        if self.indices is None:
-            raise ValueError("ShapeOverlay.refine: these rows are points of the caller's, not ligands of a library")
-        return Alignment.refine(self, pocket_or_model, library, atoms, **kw)
-
-    def pose_fit(self, model, library, keys=None, **kw) -> "PoseFit":
-        """How well the overlaid poses sit on the model's hotspots (free mode unless `keys` are given), as `Alignment.pose_fit`."""
-        if self.indices is None:
-            raise ValueError("ShapeOverlay.pose_fit: these rows are points of the caller's, not ligands of a library")
-        return pose_fit(model, library, self.indices, self.conformers, self.rotation, self.translation, keys=keys, **kw)
-
-
-def overlay(reference, library=None, indices=None, conformers=None, rotation=None, translation=None, points=None, point_radii=None, atoms=None, starts: int = 0,
-            node_radius: float = 1.0, ftol: float = 1e-6, max_iter: int = 32, device=None) -> ShapeOverlay:
-    """Rows overlaid on a known ligand (`pmx_shape_overlay`, csrc/pmx_shape_overlay.hip): per row a bounded Levenberg-Marquardt
-    maximisation over the rigid motion of the Gaussian shape overlap `shape` reports. Rows, points and radii as `shape` takes them (node
-    mode, point mode, or an atom store `atoms`).
-      starts=0   each row is optimised from its given motion: how far is this pose from its best shape match nearby?
-      starts=4   `rotation` / `translation` are ignored and may be None: each hit is run from the four motions that lay its inertial frame
-                 on the reference's (`pmx_shape_starts`), and the start of highest final Tanimoto is kept (the lower among equals). At
-                 most 16384 hits
-      max_iter, ftol  at most `max_iter` (<= 64) trial motions per row; a step that raises O_AB by no more than ftol * O_AB ends the row
-    Rigid only, shape only (no atom types, no hydrogens), unweighted inertial frames, and a local maximum. At most 65536 rows. Runs on
-    torch's current stream of the device and waits for it."""
-    torch = _torch()
-    lib = _ffi.load()
-    if starts not in (0, 4):
-        raise ValueError("overlay: starts is 0 (from the given motions) or 4 (the inertial starts)")
-    if not 0 <= int(max_iter) <= 64:
-        raise ValueError("max_iter: 0 to 64 (PMX_REFINE_MAX_ITER)")
-    if not (np.isfinite(ftol) and ftol >= 0):
-        raise ValueError("ftol must be finite and not negative")
-    if not np.isfinite(node_radius):
-        raise ValueError("node_radius must be finite")
-    k = max(starts, 1)
-    if starts:
-        hits = len(points) if points is not None else len(np.asarray(indices).reshape(-1))
-        if hits > 16384:
-            raise ValueError(f"overlay: {hits} hits, at most 16384 with starts=4 (65536 rows)")
-        rep = lambda v: None if v is None else [x for x in v for _ in range(k)]  # noqa: E731
-        points, point_radii = rep(points), rep(point_radii)
-        if indices is not None:
-            indices, conformers = np.repeat(np.asarray(indices).reshape(-1), k), np.repeat(np.asarray(conformers).reshape(-1), k)
-        rotation, translation = np.zeros((hits * k, 3, 3)), np.zeros((hits * k, 3))
-    elif rotation is None or translation is None:
-        raise ValueError("overlay: starts=0 optimises the given motions - rotation and translation")
-    rows = _PoseRows("overlay", library, indices, conformers, rotation, translation, points, point_radii, atoms)
-    n, node_mode = rows.n, rows.node_mode
-    m = max(n, 1)
-    with contextlib.ExitStack() as stack:
-        dlib = stack.enter_context(_resident(library, device)) if node_mode else None
-        dev = dlib.device if node_mode else atoms.device if isinstance(atoms, DeviceAtoms) else _device_index(device)
-        dat = stack.enter_context(_resident_atoms(atoms, dev)) if atoms is not None else None
-        rh = device_shape_ref(reference, dev)
-        tdev = torch.device("cuda", dev)
-        with torch.cuda.device(tdev):
-            keep, src, motion = rows.upload(tdev, dat)
-            rot = torch.empty((m, 3, 3), dtype=torch.float64, device=tdev)
-            trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
-            energy = torch.empty((m, 8), dtype=torch.float64, device=tdev)
-            count = torch.empty((m, 4), dtype=torch.int32, device=tdev)
-            status = torch.empty(m, dtype=torch.int32, device=tdev)
-            stream = torch.cuda.current_stream(tdev)
-            sptr = ctypes.c_void_p(stream.cuda_stream)
-            lh = dlib.handle if node_mode else None
-            if starts:
-                which = torch.arange(m, dtype=torch.int32, device=tdev) % k
-                s_rot = torch.empty((m, 9), dtype=torch.float64, device=tdev)
-                s_trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
-                frame = torch.empty((m, 16), dtype=torch.float64, device=tdev)
-                s_status = torch.empty(m, dtype=torch.int32, device=tdev)
-                _ffi.check(lib.pmx_shape_starts(rh.handle, lh, *src[:4], which.data_ptr(), n, s_rot.data_ptr(), s_trans.data_ptr(), frame.data_ptr(), s_status.data_ptr(), sptr))
-                if rows.gstatus is not None and n:  # (a row the store has no atoms for stays not OK)
-                    bad = (rows.gstatus != 0)[:, None]
-                    s_rot, s_trans = s_rot.masked_fill(bad, float("nan")), s_trans.masked_fill(bad, float("nan"))
-                keep = (keep, which, s_rot, s_trans, frame, s_status)
-                motion = (s_rot.data_ptr(), s_trans.data_ptr())
-            _ffi.check(lib.pmx_shape_overlay(rh.handle, lh, *src, *motion, n, float(node_radius), float(ftol), int(max_iter), rot.data_ptr(), trans.data_ptr(),
-                                             energy.data_ptr(), count.data_ptr(), status.data_ptr(), sptr))
-            stream.synchronize()
-            del keep
-    st = rows.finish(status.cpu().numpy()[:n].astype(np.int32))
-    en, cn = energy.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
-    R, t = rot.cpu().numpy()[:n], trans.cpu().numpy()[:n]
-    hits = n // k
-    if starts:
-        each = en[:, 5].reshape(hits, k)
-        best = np.argmax(np.where(np.isnan(each), -np.inf, each), axis=1) if hits else np.zeros(0, np.int64)  # (the first among equals)
-        pick = np.arange(hits) * k + best
-        start, start_tanimoto = best.astype(np.int64), each.copy()
-    else:
-        pick, start, start_tanimoto = np.arange(n), np.full(n, -1, np.int64), np.zeros((n, 0))
-    has_rows = node_mode or atoms is not None
-    return ShapeOverlay(rotation=R[pick].copy(), translation=t[pick].copy(), overlap_start=en[pick, 0], overlap=en[pick, 1], self_overlap=en[pick, 2],
-                        reference_overlap=en[pick, 3], tanimoto_start=en[pick, 4], tanimoto=en[pick, 5], angle=en[pick, 6], shift=en[pick, 7], iterations=cn[pick, 0],
-                        accepted=cn[pick, 1], stop=cn[pick, 2], n_points=cn[pick, 3], start=start, start_tanimoto=start_tanimoto, status=st[pick],
-                        indices=rows.idx[pick].copy() if has_rows else None, conformers=rows.conf[pick].astype(np.int64) if has_rows else None)
-
-
-@dataclass
-class ShapeStarts:
-    """What `overlay_starts` returns (definitions: `pmx_shape_starts` in include/pmx.h): per row the start motion `rotation[i]`,
-    `translation[i]`, and the row's own inertial frame - `centre[i]` [3], `axes[i]` [3, 3] (axis k is row k; right-handed, by descending
-    `values[i]` [3], the sums of squares along them) - for a caller who wants another set of starts. A row that is not OK (`status[i]`
-    1 or 4; 4 also for a start outside 0 .. 3) has NaN."""
-
-    rotation: np.ndarray
-    translation: np.ndarray
-    centre: np.ndarray
-    axes: np.ndarray
-    values: np.ndarray
-    status: np.ndarray
-
-    def __len__(self) -> int:
-        return len(self.status)
-
-
-def overlay_starts(reference, start, library=None, indices=None, conformers=None, points=None, atoms=None, device=None) -> ShapeStarts:
-    """The inertial start motions of rows (`pmx_shape_starts`): row i's points - as `overlay` takes them - laid with their unweighted
-    inertial frame on the reference's, start[i] = 0, or 1 .. 3 for a further half turn about the row's first, second or third axis. What
-    `overlay(..., starts=4)` runs from. At most 65536 rows."""
-    torch = _torch()
-    lib = _ffi.load()
-    start = np.ascontiguousarray(np.clip(np.asarray(start, dtype=np.int64).reshape(-1), -1, 2**31 - 1).astype(np.int32))
-    n = len(start)
-    rows = _PoseRows("overlay_starts", library, indices, conformers, np.zeros((n, 3, 3)), np.zeros((n, 3)), points, None, atoms)
-    node_mode = rows.node_mode
-    m = max(n, 1)
-    with contextlib.ExitStack() as stack:
-        dlib = stack.enter_context(_resident(library, device)) if node_mode else None
-        dev = dlib.device if node_mode else atoms.device if isinstance(atoms, DeviceAtoms) else _device_index(device)
-        dat = stack.enter_context(_resident_atoms(atoms, dev)) if atoms is not None else None
-        rh = device_shape_ref(reference, dev)
-        tdev = torch.device("cuda", dev)
-        with torch.cuda.device(tdev):
-            keep, src, _ = rows.upload(tdev, dat)
-            which = torch.from_numpy(start if n else np.zeros(1, np.int32)).to(tdev)
-            rot = torch.empty((m, 3, 3), dtype=torch.float64, device=tdev)
-            trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
-            frame = torch.empty((m, 16), dtype=torch.float64, device=tdev)
-            status = torch.empty(m, dtype=torch.int32, device=tdev)
-            stream = torch.cuda.current_stream(tdev)
-            _ffi.check(lib.pmx_shape_starts(rh.handle, dlib.handle if node_mode else None, *src[:4], which.data_ptr(), n, rot.data_ptr(), trans.data_ptr(), frame.data_ptr(),
-                                            status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
-            stream.synchronize()
-            del keep
-    st = rows.finish(status.cpu().numpy()[:n].astype(np.int32))
-    R, t, fr = rot.cpu().numpy()[:n].copy(), trans.cpu().numpy()[:n].copy(), frame.cpu().numpy()[:n].copy()
-    if rows.gstatus is not None:  # (a row the store has no atoms for is not OK, whatever its empty point list gave)
-        for a in (R, t, fr):
-            a[st != 0] = np.nan
-    return ShapeStarts(rotation=R, translation=t, centre=fr[:, 0:3].copy(), axes=fr[:, 3:12].reshape(-1, 3, 3).copy(), values=fr[:, 12:15].copy(), status=st)
-
-
-def _overlay_poses(poses, what, reference, library, atoms, kw) -> "ShapeOverlay":
-    if kw.get("starts", 0):
-        raise ValueError(f"{what}: the local overlay of these poses; `overlay(..., starts=4)` is the one that needs no pose")
-    _, source = _pose_source(poses, what, None, library, atoms)
-    out = overlay(reference, rotation=poses.rotation, translation=poses.translation, **source, **kw)
-    if out.indices is None and poses.indices is not None:
-        out.indices, out.conformers = np.asarray(poses.indices).copy(), np.asarray(poses.conformers, dtype=np.int64).copy()
-    return out
-
-
-def _heavy_atoms(atoms, conformers):
-    """Per row the heavy atoms of `atoms[i]` (a `LigandFeatures` / `Ligand`) at conformer `conformers[i]`, float32 [m_i, 3], and their
-    Bondi radii by atomic number. Hydrogens are left out (the pocket's are not read either); a row whose conformer the molecule does not have
-    gets no point (its status says so already)."""
-    from .pocket import atomic_number_radii
-
-    points, radii = [], []
-    for mol, c in zip(atoms, conformers):
-        pos = np.asarray(mol.atom_positions, dtype=np.float32)  # [n_atoms, C, 3]
-        c = int(c)
-        z = _atomic_numbers(mol)
-        heavy = z > 1
-        points.append(pos[heavy, c] if 0 <= c < pos.shape[1] else np.zeros((0, 3), np.float32))
-        radii.append(atomic_number_radii(z[heavy])[: len(points[-1])])
-    return points, radii
-
-
-def _pose_source(poses, what, pocket_or_model, library, atoms):
-    """(pocket, the keyword arguments that name the points of `poses`' rows for `clashes` / `refine`): node mode with `library` alone,
-    point mode - the molecules' heavy atoms - with `atoms`: a list of molecules, one per row, or the library's atom store
-    (`DeviceAtoms` / `PackedAtoms`)."""
-    from .pocket import PocketAtoms
-
-    # (`shape` judges the rows against a reference ligand: no pocket)
-    pocket = pocket_or_model if pocket_or_model is None or isinstance(pocket_or_model, PocketAtoms) else pocket_or_model.pocket_atoms()
-    if atoms is None:
-        if library is None:
-            raise ValueError(f"{what}: the library the rows are ligands of, or `atoms`")
-        return pocket, dict(library=library, indices=poses.indices, conformers=poses.conformers)
-    if poses.conformers is None:
-        raise ValueError(f"{what}: these rows have no conformers to take the atoms at")
-    if _is_store(atoms):  # the rows' atoms are gathered on the device, from the store that goes with the rows' library
-        return pocket, dict(atoms=atoms, indices=poses.indices, conformers=poses.conformers)
-    if len(atoms) != len(poses):
-        raise ValueError(f"{len(atoms)} molecules for {len(poses)} rows")
-    points, radii = _heavy_atoms(atoms, poses.conformers)
-    return pocket, dict(points=points, point_radii=radii)
-
-
-def _check_poses(poses, what, pocket_or_model, library, atoms, kw) -> "ClashReport":
-    pocket, source = _pose_source(poses, what, pocket_or_model, library, atoms)
-    return clashes(pocket, rotation=poses.rotation, translation=poses.translation, **source, **kw)
-
-
-def refine(pocket, library=None, indices=None, conformers=None, rotation=None, translation=None, points=None, point_radii=None, anchors=None, anchor_targets=None,
-           anchor_weights=None, node_radius: float = 1.0, tolerance: float = 0.5, restraint: float = 0.1, max_iter: int = 32, ftol: float = 1e-9,
-           device=None, atoms=None) -> RefinedPoses:
-    """Posed rows moved out of the pocket's atoms (`pmx_pose_refine`, csrc/pmx_refine.hip): per row a bounded Levenberg-Marquardt
-    minimisation over the rigid motion of the overlap `clashes` reports plus `restraint` times a harmonic term that holds the row's anchors
-    where the input motion put them. Rows, points and radii as `clashes` takes them (node mode, point mode, or an atom store `atoms`).
-      anchors         None: the row's own points, each of weight 1. Otherwise a list of [k_i, 3] arrays in the conformer's frame
-      anchor_targets  a matching list of [k_i, 3] float64 positions in the pocket's frame (default: the anchors under the input motion)
-      anchor_weights  a matching list of [k_i] weights >= 0 (default 1 each)
-      restraint       the weight of the restraint against the overlap, both in A^2. The default 0.1 is uncalibrated: nobody has measured
-                      which value separates a grazed side chain from a pierced backbone best; DESIGN.md has what is known
-      max_iter, ftol  at most `max_iter` (<= 64) trial motions per row; a step that lowers the energy by no more than ftol * E ends the row
-    A penalty on the overlap balanced against a restraint never reaches an overlap of exactly zero: to make a pose pass a check at
-    `tolerance`, refine at a smaller one. At most 65536 rows. Runs on torch's current stream of the device and waits for it."""
-    torch = _torch()
-    lib = _ffi.load()
-    rows = _PoseRows("refine", library, indices, conformers, rotation, translation, points, point_radii, atoms)
-    n, node_mode = rows.n, rows.node_mode
-    if not 0 <= int(max_iter) <= 64:
-        raise ValueError("max_iter: 0 to 64 (PMX_REFINE_MAX_ITER)")
-    if not (np.isfinite(restraint) and restraint >= 0 and np.isfinite(ftol) and ftol >= 0):
-        raise ValueError("restraint and ftol must be finite and not negative")
-    a_off = a_flat = a_tgt = a_wts = None
-    if anchors is None:
-        if anchor_targets is not None or anchor_weights is not None:
-            raise ValueError("refine: anchor_targets and anchor_weights go with anchors")
-    else:
-        if len(anchors) != n:
-            raise ValueError(f"{len(anchors)} anchor sets for {n} motions")
-        a_off, a_flat, arows = _ragged(anchors, np.float32, 3)
-        for name, given, width in (("anchor_targets", anchor_targets, 3), ("anchor_weights", anchor_weights, None)):
-            if given is None:
-                continue
-            if len(given) != n:
-                raise ValueError(f"{len(given)} lists of {name} for {n} anchor sets")
-            _, flat, rs = _ragged(given, np.float64, width)
-            if any(len(r) != len(p) for r, p in zip(rs, arows)):
-                raise ValueError(f"a list of {name} differs in length from its anchors")
-            if width:
-                a_tgt = flat
-            else:
-                a_wts = flat
-    m = max(n, 1)
-    with contextlib.ExitStack() as stack:
-        dlib = stack.enter_context(_resident(library, device)) if node_mode else None
-        dev = dlib.device if node_mode else atoms.device if isinstance(atoms, DeviceAtoms) else _device_index(device)
-        dat = stack.enter_context(_resident_atoms(atoms, dev)) if atoms is not None else None
-        ph = device_pocket(pocket, dev)
-        tdev = torch.device("cuda", dev)
-        with torch.cuda.device(tdev):
-            keep, src, motion = rows.upload(tdev, dat)
-            t_anchor = [None if a is None else torch.from_numpy(a).to(tdev) for a in (a_off, a_flat, a_tgt, a_wts)]
-            rot = torch.empty((m, 3, 3), dtype=torch.float64, device=tdev)
-            trans = torch.empty((m, 3), dtype=torch.float64, device=tdev)
-            energy = torch.empty((m, 8), dtype=torch.float64, device=tdev)
-            count = torch.empty((m, 4), dtype=torch.int32, device=tdev)
-            status = torch.empty(m, dtype=torch.int32, device=tdev)
-            stream = torch.cuda.current_stream(tdev)
-            _ffi.check(lib.pmx_pose_refine(ph.handle, dlib.handle if node_mode else None, *src, *(None if a is None else a.data_ptr() for a in t_anchor), *motion, n,
-                                           float(node_radius), float(tolerance), float(restraint), float(ftol), int(max_iter), rot.data_ptr(), trans.data_ptr(),
-                                           energy.data_ptr(), count.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
-            stream.synchronize()
-            del keep, t_anchor
-    en, cn = energy.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
-    return RefinedPoses(rotation=rot.cpu().numpy()[:n].copy(), translation=trans.cpu().numpy()[:n].copy(), overlap_start=en[:, 0].copy(), overlap=en[:, 2].copy(),
-                        restraint_start=en[:, 1].copy(), restraint_energy=en[:, 3].copy(), anchor_rmsd=en[:, 4].copy(), angle=en[:, 5].copy(), shift=en[:, 6].copy(),
-                        iterations=cn[:, 0].copy(), accepted=cn[:, 1].copy(), stop=cn[:, 2].copy(), n_pairs=cn[:, 3].copy(),
-                        status=rows.finish(status.cpu().numpy()[:n].astype(np.int32)), indices=rows.idx.copy() if node_mode else None,
-                        conformers=rows.conf.astype(np.int64) if node_mode else None)
-
-
-@dataclass
-class PoseFit:
-    """What `pose_fit` returns: one row per posed ligand - the Gaussian overlap of its posed pharmacophore nodes with the model's hotspots,
-    each hotspot's radius its positional sigma (definitions: `pmx_pose_fit` in include/pmx.h). Floats are float64. Not a docking score: no
-    direction, no atoms, and not the reference's score.
-
-    fit[i], ideal[i]        the sum over the nodes of the mean of w exp(-z^2 / 2) over a node's pairs, and the same with every z = 0
-    fraction[i]             fit / ideal: 1.0 with every node on all its hotspots; 0 where ideal is 0
-    best_fit[i], best_ideal[i], best_fraction[i]   the same over each node's nearest hotspot (smallest z) alone
-    n_nodes[i], n_pairs[i]  nodes with a pair, and pairs    n_in_place[i]  nodes most of whose pairs pass (|z| < 2)    n_passing[i]  passing pairs
-    node_fit[i], node_best[i], node_z2[i], node_target[i]   [n] per node of the record: its mean, its nearest hotspot's term, that z^2 and that
-                            model node; -1 for a node without a pair
-    hotspot_z2[i], hotspot_node[i]   [Nm] per model node: the smallest z^2 of a pair with it (+inf without one) and the ligand node (-1)
-    occupied_fingerprint    uint64 [n, 4]: bit m says some pair with model node m passes
-    status[i]               0, 1 (PMX_LIGAND_UNSUPPORTED) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer, a motion that is not finite - a
-                            row of an `Alignment` that was not OK -, a match that is no candidate); such a row has NaN floats, zero counts,
-                            -1 targets and an empty fingerprint"""
-
-    indices: np.ndarray
-    conformers: np.ndarray
-    fit: np.ndarray
-    ideal: np.ndarray
-    fraction: np.ndarray
-    best_fit: np.ndarray
-    best_ideal: np.ndarray
-    best_fraction: np.ndarray
-    n_nodes: np.ndarray
-    n_pairs: np.ndarray
-    n_in_place: np.ndarray
-    n_passing: np.ndarray
-    node_fit: list
-    node_best: list
-    node_z2: list
-    node_target: list
-    hotspot_z2: list
-    hotspot_node: list
-    occupied_fingerprint: np.ndarray
-    status: np.ndarray
-    device: "int | None" = None  # where `similarity` and `leaders` run
-
-    def __len__(self) -> int:
-        return len(self.status)
-
-    def occupied(self, i: int) -> np.ndarray:
-        """The model nodes row i occupies (the set bits of its fingerprint), ascending."""
-        bits = np.unpackbits(np.ascontiguousarray(self.occupied_fingerprint[i]).view(np.uint8), bitorder="little")
-        return np.flatnonzero(bits).astype(np.int64)
-
-    def coverage(self, i: int, model, weights: dict[str, float] | None = None) -> float:
-        """The occupied model nodes over the model nodes of positive weight (0.0 where no node has weight)."""
-        w = np.asarray(weights_vector(weights), dtype=np.float32)[np.asarray(model.flat.node_type, dtype=np.int64)[: model.num_nodes]]
-        total = int(np.count_nonzero(w > 0))
-        return len(self.occupied(i)) / total if total else 0.0
-
-    def similarity(self, other: "PoseFit | None" = None) -> np.ndarray:
-        """Tanimoto similarity of the occupied-hotspot fingerprints, on the GPU (`fingerprint_similarity`)."""
-        return fingerprint_similarity(self.occupied_fingerprint, None if other is None else other.occupied_fingerprint, device=self.device)
-
-    def leaders(self, threshold: float = 0.7, max_leaders: int = 2048):
-        """Sphere exclusion over the rows in their order by occupied hotspots (`fingerprint_leaders`): (leaders, leader_of)."""
-        return fingerprint_leaders(self.occupied_fingerprint, threshold=threshold, max_leaders=max_leaders, device=self.device)
-
-
-def _ratio(a: np.ndarray, b: np.ndarray) -> np.ndarray:
-    """a / b in float64, 0 where b is 0 (NaN stays NaN)."""
-    out = np.zeros_like(a)
-    np.divide(a, b, out=out, where=b != 0)
-    return out
-
-
-def pose_fit(model, library, indices, conformers, rotation, translation, keys=None, weights: dict[str, float] | None = None, centers=None, sigmas=None,
-             device=None) -> PoseFit:
-    """Posed library ligands against the model's hotspots (`pmx_pose_fit`, csrc/pmx_pose_fit.hip): row i is the pharmacophore nodes of
-    library ligand indices[i] at conformer conformers[i], moved by `rotation[i]` [3, 3] and `translation[i]` [3] - what `Alignment` and
-    `RefinedPoses` hold.
-      keys      None (free mode): a node pairs with every model node of a type it has. Otherwise the rows' keys as `align` takes them (key
-                mode): the pairs are `align`'s for that key
-      centers, sigmas   float64 [Nm, 3] / [Nm] in place of the model nodes' `center` and `radius`: "what if this hotspot were tighter". A
-                sigma that is not a finite number > 0 takes its model node out
-    At most 65536 rows. Runs on torch's current stream of the device and waits for it."""
-    torch = _torch()
-    lib = _ffi.load()
-    rows = _PoseRows("pose_fit", library, indices, conformers, rotation, translation, None, None)
-    n = rows.n
-    nm = int(model.num_nodes)
-    kb = None
-    if keys is not None:
-        _, _, kb = _listed_rows(rows.idx, rows.conf, keys, "pose_fit")
-    over = []
-    for name, given, shape in (("centers", centers, (nm, 3)), ("sigmas", sigmas, (nm,))):
-        if given is None:
-            over.append(None)
-            continue
-        arr = np.ascontiguousarray(np.asarray(given, dtype=np.float64))
-        if arr.shape != shape:
-            raise ValueError(f"pose_fit: {name} of shape {arr.shape}, the model has {nm} nodes ({shape})")
-        over.append(np.concatenate([arr.reshape(-1), np.zeros(3)]))  # (never an empty buffer)
-    m = max(n, 1)
-    with _resident(library, device) as dlib:
-        mh = device_model(model, dlib.device)
-        dev = dlib.device
-        tdev = torch.device("cuda", dev)
-        with torch.cuda.device(tdev):
-            keep, src, motion = rows.upload(tdev)
-            t_cen = mh.node_centers(model) if over[0] is None else torch.from_numpy(over[0]).to(tdev)
-            t_sig = mh.node_sigmas(model) if over[1] is None else torch.from_numpy(over[1]).to(tdev)
-            t_key = None if kb is None else torch.from_numpy(kb).to(tdev)
-            f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=tdev)  # noqa: E731
-            i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=tdev)  # noqa: E731
-            summary, count = f64(m, 4), i32(m, 4)
-            nfit, nbest, nz2, ntgt = f64(m, _MAX_NODES), f64(m, _MAX_NODES), f64(m, _MAX_NODES), i32(m, _MAX_NODES)
-            hz2, hnode = f64(m, _MAX_MODEL_NODES), i32(m, _MAX_MODEL_NODES)
-            fp = torch.empty((m, _FP_WORDS), dtype=torch.int64, device=tdev)
-            status = i32(m)
-            stream = torch.cuda.current_stream(tdev)
-            _ffi.check(lib.pmx_pose_fit(mh.handle, dlib.handle, _weights_array(weights), t_cen.data_ptr(), t_sig.data_ptr(), src[0], src[1],
-                                        None if t_key is None else t_key.data_ptr(), *motion, n, summary.data_ptr(), count.data_ptr(), nfit.data_ptr(), nbest.data_ptr(),
-                                        nz2.data_ptr(), ntgt.data_ptr(), hz2.data_ptr(), hnode.data_ptr(), fp.data_ptr(), status.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
-            stream.synchronize()
-            del keep, t_key
-        st = status.cpu().numpy()[:n].astype(np.int32)
-        nn = np.where(st != 1, _record_counts(dlib, rows.idx, 0), 0) if n else np.zeros(0, np.int64)
-    sm, cn = summary.cpu().numpy()[:n], count.cpu().numpy()[:n].astype(np.int64)
-    cut = lambda t, w, dt=None: [(a[: w[i]].copy() if dt is None else a[: w[i]].astype(dt)) for i, a in enumerate(t.cpu().numpy()[:n])]  # noqa: E731
-    wm = np.full(n, nm, dtype=np.int64)
-    return PoseFit(indices=rows.idx.astype(np.int64), conformers=rows.conf.astype(np.int64), fit=sm[:, 0].copy(), ideal=sm[:, 1].copy(), fraction=_ratio(sm[:, 0], sm[:, 1]),
-                   best_fit=sm[:, 2].copy(), best_ideal=sm[:, 3].copy(), best_fraction=_ratio(sm[:, 2], sm[:, 3]), n_nodes=cn[:, 0].copy(), n_pairs=cn[:, 1].copy(),
-                   n_in_place=cn[:, 2].copy(), n_passing=cn[:, 3].copy(), node_fit=cut(nfit, nn), node_best=cut(nbest, nn), node_z2=cut(nz2, nn),
-                   node_target=cut(ntgt, nn, np.int64), hotspot_z2=cut(hz2, wm), hotspot_node=cut(hnode, wm, np.int64),
-                   occupied_fingerprint=fp.cpu().numpy()[:n].view(np.uint64).copy(), status=st, device=dev)
-
-
-_MAX_MODEL_NODES, _FP_WORDS, _MAX_LEADERS = 256, 4, 2048  # PMX_MAX_MODEL_NODES, PMX_FINGERPRINT_WORDS, PMX_MAX_LEADERS
-_MAX_QUERIES = 64  # PMX_SEARCH_MAX_QUERIES
-
-
-def _fingerprint_tensor(fp, tdev):
-    torch = _torch()
-    fp = np.ascontiguousarray(np.asarray(fp, dtype=np.uint64).reshape(-1, _FP_WORDS))
-    if len(fp) > 65536:
-        raise ValueError("at most 65536 fingerprints per call (PMX_EXPLAIN_MAX)")
-    return torch.from_numpy(np.ascontiguousarray(fp.view(np.int64).reshape(max(len(fp), 0), _FP_WORDS))).to(tdev), len(fp)
-
-
-def fingerprint_similarity(a, b=None, device=None) -> np.ndarray:
-    """Tanimoto similarity (`pmx_fingerprint_tanimoto`, csrc/pmx_fingerprint.hip) of the uint64 [n, 4] fingerprints `a` against `b` (default:
-    `a` itself): float32 [n, m], popcount(x & y) / popcount(x | y) and 1 where both are empty. Waits for the stream."""
-    torch = _torch()
-    lib = _ffi.load()
-    dev = _device_index(device)
-    tdev = torch.device("cuda", dev)
-    with torch.cuda.device(tdev):
-        ta, na = _fingerprint_tensor(a, tdev)
-        tb, nb = (ta, na) if b is None else _fingerprint_tensor(b, tdev)
-        out = torch.empty((na, nb), dtype=torch.float32, device=tdev)
-        stream = torch.cuda.current_stream(tdev)
-        _ffi.check(lib.pmx_fingerprint_tanimoto(ta.data_ptr(), na, tb.data_ptr(), nb, out.data_ptr(), dev, ctypes.c_void_p(stream.cuda_stream)))
-        stream.synchronize()
-    return out.cpu().numpy()
-
-
-def fingerprint_leaders(fp, threshold: float = 0.7, max_leaders: int = _MAX_LEADERS, device=None):
-    """Sphere exclusion in row order (`pmx_fingerprint_leaders`): (leaders, leader_of) - the rows that became leaders, ascending, and per row
-    the leader it joined (itself for a leader; -1 for a row that joined none after `max_leaders` leaders existed). A row joins the first
-    earlier leader it is at least `threshold` similar to. Waits for the stream."""
-    torch = _torch()
-    lib = _ffi.load()
-    dev = _device_index(device)
-    tdev = torch.device("cuda", dev)
-    with torch.cuda.device(tdev):
-        t, n = _fingerprint_tensor(fp, tdev)
-        leader_of = torch.empty(max(n, 1), dtype=torch.int32, device=tdev)
-        leaders = torch.empty(max(int(max_leaders), 1), dtype=torch.int32, device=tdev)
-        count = torch.zeros(1, dtype=torch.int32, device=tdev)
-        stream = torch.cuda.current_stream(tdev)
-        _ffi.check(lib.pmx_fingerprint_leaders(t.data_ptr(), n, float(threshold), int(max_leaders), leader_of.data_ptr(), leaders.data_ptr(), count.data_ptr(), dev,
-                                               ctypes.c_void_p(stream.cuda_stream)))
-        stream.synchronize()
-    nl = int(count.cpu()[0])
-    lo = leader_of.cpu().numpy()[:n].view(np.uint32).astype(np.int64)
-    lo[lo == 0xFFFFFFFF] = -1
-    return leaders.cpu().numpy()[:nl].view(np.uint32).astype(np.int64), lo
 
 
 @dataclass

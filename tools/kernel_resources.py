@@ -3,16 +3,18 @@
 
     python tools/kernel_resources.py [--out profiles/r4_kernel_resources.json]
 
-Compiles csrc/pmx_api.hip, csrc/pmx_pack_device.hip, csrc/pmx_explain.hip, csrc/pmx_rows.hip, csrc/pmx_enrich.hip, csrc/pmx_pocket.hip, csrc/pmx_refine.hip, csrc/pmx_pose_search.hip, csrc/pmx_pose_fit.hip, csrc/pmx_pose_shape.hip, csrc/pmx_shape_overlay.hip and csrc/pmx_atoms.hip device-only with the build's flags, unbundles the gfx950 code object and reads the
+Compiles every .hip unit of `pharmaconet_amd.build.SOURCES` device-only with the build's flags, unbundles the gfx950 code object and reads the
 AMDGPU metadata notes (llvm-readelf --notes)."""
 import json, re, subprocess, sys, tempfile
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO))
-from pharmaconet_amd.build import FLAGS, CSRC, hipcc  # noqa: E402
+from pharmaconet_amd.build import FLAGS, CSRC, SOURCES, hipcc  # noqa: E402
 
 LLVM = Path("/opt/rocm/lib/llvm/bin")
+UNITS = tuple(s for s in SOURCES if s.endswith(".hip"))  # (a unit without a kernel of its own contributes no rows)
+__doc__ += "\n\nThe units: " + ", ".join(UNITS) + "."
 
 
 def main():
@@ -25,7 +27,7 @@ def main():
         flags = [f for f in FLAGS if f != "-fPIC"]
         import os
         extra = os.environ.get("PMX_CXXFLAGS", "").split()
-        for src in ("pmx_api.hip", "pmx_pack_device.hip", "pmx_explain.hip", "pmx_rows.hip", "pmx_enrich.hip", "pmx_pocket.hip", "pmx_refine.hip", "pmx_pose_search.hip", "pmx_pose_fit.hip", "pmx_pose_shape.hip", "pmx_shape_overlay.hip", "pmx_atoms.hip"):  # the screening / top-k kernels, the device packer's, the explain kernels, the row kernels (attribution and fit), the enrichment kernels, the pose kernels (clash check, refinement, the pose search, the pose fit, the shape overlap and the shape overlay), the atom store's gather
+        for src in UNITS:
             subprocess.run([hipcc(), *flags, *extra, f"-I{REPO / 'include'}", f"-I{CSRC}", "--cuda-device-only", "-c", str(CSRC / src), "-o", str(td / "dev.o")], check=True)
             subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={td / 'dev.o'}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={td / 'dev.co'}"], check=True)
             notes += subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(td / "dev.co")], check=True, capture_output=True, text=True).stdout
@@ -56,7 +58,7 @@ def main():
         from pharmaconet_amd.build import hipcc_version, read_stamp
 
         out.write_text(json.dumps({
-            "source": "llvm-readelf --notes of the gfx950 code objects of csrc/pmx_api.hip, pmx_pack_device.hip, pmx_explain.hip, pmx_rows.hip, pmx_enrich.hip, pmx_pocket.hip, pmx_refine.hip, pmx_pose_search.hip and pmx_pose_fit.hip (tools/kernel_resources.py)",
+            "source": "llvm-readelf --notes of the gfx950 code objects of csrc/" + ", ".join(UNITS) + " (tools/kernel_resources.py)",
             "kernels": rows,
             "hipcc": hipcc_version(),
             "build_stamp": read_stamp(),
