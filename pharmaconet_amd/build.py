@@ -21,7 +21,7 @@ SOURCES = ("pmx_api.hip", "pmx_screen_debug.hip", "pmx_explain.hip", "pmx_rows.h
 HOST_SOURCES = tuple(s for s in SOURCES if s.endswith(".cpp"))
 # every file under csrc/ that a unit of SOURCES #includes, directly or not (tests/test_cabi.py checks the closure): with SOURCES, what the
 # digest of the stamp covers
-DEPS = ("pmx_screen.hip", "pmx_screen_walk.h", "pmx_screen_tables.h", "pmx_screen_layout.h", "pmx_screen_lds.h", "pmx_handles.h", "pmx_device.h", "pmx_debug.h", "pmx_explain.h", "pmx_rows.h", "pmx_rows_front.h", "pmx_pose.h", "pmx_shape.h", "pmx_atoms.h", "pmx_scan.h", "pmx_error.h", "pmx_model_tables.h")
+DEPS = ("pmx_screen.hip", "pmx_screen_walk.h", "pmx_screen_tables.h", "pmx_screen_layout.h", "pmx_screen_lds.h", "pmx_handles.h", "pmx_device.h", "pmx_debug.h", "pmx_explain.h", "pmx_rows.h", "pmx_rows_front.h", "pmx_pose.h", "pmx_lm.h", "pmx_shape.h", "pmx_atoms.h", "pmx_scan.h", "pmx_error.h", "pmx_model_tables.h")
 FLAGS = (
     "--offload-arch=gfx950",
     "-O3",

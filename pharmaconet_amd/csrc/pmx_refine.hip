@@ -11,7 +11,7 @@
 //                over before its square root (the ballot). A clashing pair is rare: its 21 + 6 products are added under the lane mask
 //     anchors    a lane per anchor, strided; the closed form of its block of H and g in r = q - c
 //   reduce     Ec, Er, the pair count, H (21 values), g (6): one butterfly each - the same bits in every lane afterwards
-//   solve      the 6x6 Cholesky, Rodrigues and the decision are computed by all lanes alike; every branch is taken through readfirstlane
+//   iterate    pmx::lm_run of pmx_lm.h, the loop this call shares with pmx_shape_overlay, following E = Ec + restraint Er down
 // H, g and the motions are named by constant indices only (every loop over them is unrolled): registers, no scratch.
 #include <hip/hip_runtime.h>
 
@@ -20,15 +20,22 @@
 
 #include "pmx.h"
 #include "pmx_device.h"
+#include "pmx_lm.h"
 #include "pmx_pose.h"
 
 namespace {
+using pmx::hidx;
+using pmx::lm_net_motion;
+using pmx::lm_run;
+using pmx::LmRun;
 using pmx::pose_load;
 using pmx::pose_motion;
 using pmx::pose_point;
 using pmx::pose_row;
 using pmx::PoseRow;
 using pmx::PoseSource;
+using pmx::store_motion;
+using pmx::store_not_ok;
 using pmx::wave_sum;
 
 constexpr int kWaves = 4;
@@ -50,11 +57,6 @@ struct RefineArgs {
     double *rot_out, *trans_out, *energy;
     int32_t *count, *status;
 };
-
-__device__ __forceinline__ bool uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
-
-// index of H(i, j), i <= j, in the 21 values of the upper triangle
-__host__ __device__ constexpr int hidx(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
 
 struct Eval {
     double Ec, Er;
@@ -213,69 +215,24 @@ __device__ __forceinline__ void evaluate(const RefineArgs &a, const PoseRow &pr,
     for (int k = 0; k < 6; ++k) e.g[k] = wave_sum(g[k]);
 }
 
-// (H + lambda diag(H_ii + 1e-9)) delta = -g by Cholesky; false when a pivot is not positive.
-__device__ __forceinline__ bool solve(const double (&H)[21], const double (&g)[6], double lambda, double (&x)[6]) {
-    double L[21]; // L(i, j), j <= i, at hidx(j, i)
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double s = H[hidx(j, j)] + lambda * (H[hidx(j, j)] + 1e-9);
-#pragma unroll
-        for (int k = 0; k < j; ++k) s -= L[hidx(k, j)] * L[hidx(k, j)];
-        ok = ok && s > 0.0;
-        const double ljj = __builtin_sqrt(s);
-        L[hidx(j, j)] = ljj;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = H[hidx(j, i)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= L[hidx(k, i)] * L[hidx(k, j)];
-            L[hidx(j, i)] = v / ljj;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = -g[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= L[hidx(k, i)] * y[k];
-        y[i] = v / L[hidx(i, i)];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) v -= L[hidx(i, k)] * x[k];
-        x[i] = v / L[hidx(i, i)];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) ok = ok && std::isfinite(x[i]);
-    return ok;
-}
-
-// Rodrigues of omega: I + (sin th / th) K + (2 sin^2(th / 2) / th^2) K^2, K = [omega]_x, K^2 = omega omega^T - th^2 I.
-__device__ __forceinline__ void rodrigues(double w0, double w1, double w2, double (&Rd)[9]) {
-    const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
-    const double th = __builtin_sqrt(th2);
-    double sa = 1.0, sb = 0.5;
-    if (th > 0.0) {
-        const double sh = sin(0.5 * th);
-        sa = sin(th) / th;
-        sb = ((2.0 * sh) * sh) / (th * th);
-    }
-    const double w[3] = {w0, w1, w2};
-    const double K[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Rd[3 * i + j] = (i == j ? 1.0 : 0.0) + (sa * K[3 * i + j] + sb * (w[i] * w[j] - (i == j ? th2 : 0.0)));
-}
+// What pmx::lm_run follows: E = Ec + restraint Er, down.
+struct Relief {
+    using Eval = ::Eval;
+    const RefineArgs &a;
+    const PoseRow &pr;
+    const Anchors &an;
+    const double (&R0)[9], (&t0)[3];
+    int lane;
+    __device__ __forceinline__ void eval(const double (&R)[9], const double (&t)[3], Eval &e) const { evaluate(a, pr, an, R0, t0, R, t, lane, e); }
+    __device__ __forceinline__ double value(const Eval &e) const { return e.Ec + a.restraint * e.Er; }
+    __device__ __forceinline__ bool better(double trial, double cur) const { return trial < cur; }
+    __device__ __forceinline__ double gain(double before, double after) const { return before - after; }
+};
 
 __global__ __launch_bounds__(64 * kWaves) void refine_kernel(const RefineArgs a) {
     const uint32_t row = blockIdx.x * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
     if (row >= a.n) return;
     const int lane = (int)(threadIdx.x % 64);
-    const double nan = __builtin_nan("");
 
     double R0[9], t0[3];
     const bool finite = pose_motion(a.rot, a.trans, row, R0, t0);
@@ -309,106 +266,34 @@ __global__ __launch_bounds__(64 * kWaves) void refine_kernel(const RefineArgs a)
     }
 
     if (status != PMX_LIGAND_OK) {
-        if (lane < 9) a.rot_out[(size_t)row * 9 + lane] = nan;
-        if (lane < 3) a.trans_out[(size_t)row * 3 + lane] = nan;
-        if (lane < 8) a.energy[(size_t)row * 8 + lane] = nan;
-        if (lane < 4) a.count[(size_t)row * 4 + lane] = lane == 2 ? -1 : 0;
-        if (lane == 0) a.status[row] = status;
+        store_not_ok(a.rot_out, a.trans_out, a.energy, a.count, a.status, row, lane, status);
         return;
     }
 
-    // ---- the iteration. `cur` is the last accepted evaluation, at (R, t); a trial is evaluated at (Rt, tt)
-    double R[9], t[3], Rt[9], tt[3];
+    // ---- the iteration, from the evaluation at the start; a row without a clashing pair has nothing to follow
+    double R[9], t[3];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = Rt[k] = R0[k];
+    for (int k = 0; k < 9; ++k) R[k] = R0[k];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = tt[k] = t0[k];
-    Eval cur, tr;
-    evaluate(a, pr, an, R0, t0, R, t, lane, cur);
+    for (int k = 0; k < 3; ++k) t[k] = t0[k];
+    const Relief obj{a, pr, an, R0, t0, lane};
+    Eval cur;
+    obj.eval(R, t, cur);
     const double ec_start = cur.Ec, er_start = cur.Er;
-    const double cs0 = cur.c[0], cs1 = cur.c[1], cs2 = cur.c[2];
-    double E = cur.Ec + a.restraint * cur.Er;
-    double lambda = 1e-3;
-    int iterations = 0, accepted = 0, reason = 2;
-    if (uniform(cur.pairs == 0)) {
-        reason = 0;
-    } else {
-        while (uniform(iterations < a.max_iter)) {
-            double delta[6];
-            if (!uniform(solve(cur.H, cur.g, lambda, delta))) { // (a pivot that is not positive: a rejected trial without an evaluation)
-                ++iterations;
-                lambda *= 8.0;
-                if (uniform(lambda > 1e8)) {
-                    reason = 3;
-                    break;
-                }
-                continue;
-            }
-            double Rd[9];
-            rodrigues(delta[0], delta[1], delta[2], Rd);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) Rt[3 * i + j] = (Rd[3 * i] * R[j] + Rd[3 * i + 1] * R[3 + j]) + Rd[3 * i + 2] * R[6 + j];
-            }
-            {
-                const double w0 = t[0] - cur.c[0], w1 = t[1] - cur.c[1], w2 = t[2] - cur.c[2];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) tt[i] = (((Rd[3 * i] * w0 + Rd[3 * i + 1] * w1) + Rd[3 * i + 2] * w2) + cur.c[i]) + delta[3 + i];
-            }
-            evaluate(a, pr, an, R0, t0, Rt, tt, lane, tr);
-            ++iterations;
-            const double Et = tr.Ec + a.restraint * tr.Er;
-            if (uniform(Et < E)) {
-                const double before = E;
-                ++accepted;
-                cur = tr;
-#pragma unroll
-                for (int k = 0; k < 9; ++k) R[k] = Rt[k];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) t[k] = tt[k];
-                E = Et;
-                lambda = fmax(lambda / 4.0, 1e-9);
-                if (uniform(before - Et <= a.ftol * before)) {
-                    reason = 1;
-                    break;
-                }
-            } else {
-                lambda *= 8.0;
-                if (uniform(lambda > 1e8)) {
-                    reason = 3;
-                    break;
-                }
-            }
-        }
-    }
+    const double c_start[3] = {cur.c[0], cur.c[1], cur.c[2]};
+    const LmRun run = lm_run(obj, cur, R, t, cur.pairs != 0, a.ftol, a.max_iter);
 
     // ---- the row's outputs: the last accepted motion (the input's own bits when nothing was accepted)
-    // net rotation from the start: Q = R R0^T, angle = atan2(|vee(Q - Q^T)| / 2, (tr Q - 1) / 2)
-    double Q[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Q[3 * i + j] = (R[3 * i] * R0[3 * j] + R[3 * i + 1] * R0[3 * j + 1]) + R[3 * i + 2] * R0[3 * j + 2];
-    }
-    const double a0 = Q[7] - Q[5], a1 = Q[2] - Q[6], a2 = Q[3] - Q[1];
-    const double sn = 0.5 * __builtin_sqrt((a0 * a0 + a1 * a1) + a2 * a2), cs = 0.5 * (((Q[0] + Q[4]) + Q[8]) - 1.0);
-    const double angle = accepted ? atan2(sn, cs) : 0.0;
-    const double h0 = cur.c[0] - cs0, h1 = cur.c[1] - cs1, h2 = cur.c[2] - cs2;
-    const double shift = __builtin_sqrt((h0 * h0 + h1 * h1) + h2 * h2);
+    double angle, shift;
+    lm_net_motion(R, R0, run.accepted, cur.c, c_start, angle, shift);
     const double rmsd = wsum > 0.0 ? __builtin_sqrt(cur.Er / wsum) : 0.0;
+    store_motion(a.rot_out, a.trans_out, row, lane, R, t);
+    const double en[8] = {ec_start, er_start, cur.Ec, cur.Er, rmsd, angle, shift, run.lambda};
     double out = 0.0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) out = lane == k ? R[k] : out;
-    if (lane < 9) a.rot_out[(size_t)row * 9 + lane] = out;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out = lane == k ? t[k] : out;
-    if (lane < 3) a.trans_out[(size_t)row * 3 + lane] = out;
-    const double en[8] = {ec_start, er_start, cur.Ec, cur.Er, rmsd, angle, shift, lambda};
 #pragma unroll
     for (int k = 0; k < 8; ++k) out = lane == k ? en[k] : out;
     if (lane < 8) a.energy[(size_t)row * 8 + lane] = out;
-    if (lane < 4) a.count[(size_t)row * 4 + lane] = lane == 0 ? iterations : lane == 1 ? accepted : lane == 2 ? reason : cur.pairs;
+    if (lane < 4) a.count[(size_t)row * 4 + lane] = lane == 0 ? run.iterations : lane == 1 ? run.accepted : lane == 2 ? run.reason : cur.pairs;
     if (lane == 0) a.status[row] = status;
 }
 
@@ -423,8 +308,7 @@ extern "C" int pmx_pose_refine(const pmx_pocket *pocket, const pmx_library *lib,
     const int rc = pmx::pose_source("pmx_pose_refine", pocket, lib, ligands_dev, conformer_dev, point_off_dev, points_dev, point_radius_dev, rot_dev, trans_dev, n, &a.src);
     if (rc != PMX_OK) return rc;
     if (!std::isfinite(point_radius) || !std::isfinite(tolerance)) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_refine: radius and tolerance must be finite");
-    if (!std::isfinite(restraint) || restraint < 0.0 || !std::isfinite(ftol) || ftol < 0.0) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_refine: restraint and ftol must be finite and not negative");
-    if (max_iter < 0 || max_iter > PMX_REFINE_MAX_ITER) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_refine: max_iter %d, 0 .. %d", max_iter, PMX_REFINE_MAX_ITER);
+    if (const int bad = pmx::lm_check("pmx_pose_refine", "restraint and ftol", ftol, max_iter, restraint)) return bad;
     if ((anchor_off_dev == nullptr) != (anchors_dev == nullptr)) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_refine: anchor_off_dev and anchors_dev go together");
     if (!anchor_off_dev && (anchor_target_dev || anchor_weight_dev)) return pmx_fail(PMX_ERR_INVALID, "pmx_pose_refine: anchor targets or weights without anchors");
     if (n == 0) return PMX_OK;

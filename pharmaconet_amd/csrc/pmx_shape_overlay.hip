@@ -13,9 +13,8 @@
 //               handful of multiply-adds a pair. The point's block of H (15 values that are not 0 by structure) and g (6) is formed once
 //               per point, the closed form in r = p - c
 //   reduce    O_AB, H, g: one butterfly each - the same bits in every lane afterwards
-//   solve     the 6x6 Cholesky, Rodrigues and the decision are computed by all lanes alike; every branch is taken through readfirstlane
-// The solve and Rodrigues are copies of pmx_refine.hip's: that unit's kernel is held to bit-level identities and a register table, and a
-// shared header would have rebuilt it. H, g and the motions are named by constant indices only: registers, no scratch.
+//   iterate   pmx::lm_run of pmx_lm.h, the loop this call shares with pmx_pose_refine, following O_AB up
+// H, g and the motions are named by constant indices only: registers, no scratch.
 //
 // starts_kernel - one wavefront per row, no LDS: the lanes' sums of the row's unposed points and of the reference's atoms, the butterfly,
 // then the 3x3 Jacobi in every lane alike.
@@ -26,12 +25,17 @@
 
 #include "pmx.h"
 #include "pmx_device.h"
+#include "pmx_lm.h"
 #include "pmx_pose.h"
 #include "pmx_shape.h"
 
 namespace {
 using pmx::alpha_of;
 using pmx::dist2;
+using pmx::hidx;
+using pmx::lm_net_motion;
+using pmx::lm_run;
+using pmx::LmRun;
 using pmx::pair_term;
 using pmx::pose_load;
 using pmx::pose_motion;
@@ -40,6 +44,8 @@ using pmx::pose_row;
 using pmx::PoseRow;
 using pmx::PoseSource;
 using pmx::radius_ok;
+using pmx::store_motion;
+using pmx::store_not_ok;
 using pmx::wave_sum;
 
 constexpr int kA = PMX_MAX_LIGAND_ATOMS;
@@ -69,11 +75,6 @@ struct StartsArgs {
     double *rot_out, *trans_out, *frame;
     int32_t *status;
 };
-
-__device__ __forceinline__ bool uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
-
-// index of H(i, j), i <= j, in the 21 values of the upper triangle
-__host__ __device__ constexpr int hidx(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
 
 struct Eval {
     double oab;
@@ -179,63 +180,19 @@ __device__ __forceinline__ void evaluate(const double4 *X, uint32_t npts, const 
     e.g[5] = wave_sum(g5);
 }
 
-// (H + lambda diag(H_ii + 1e-9)) delta = -g by Cholesky; false when a pivot is not positive. (pmx_refine.hip's, operation for operation)
-__device__ __forceinline__ bool solve(const double (&H)[21], const double (&g)[6], double lambda, double (&x)[6]) {
-    double L[21]; // L(i, j), j <= i, at hidx(j, i)
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double s = H[hidx(j, j)] + lambda * (H[hidx(j, j)] + 1e-9);
-#pragma unroll
-        for (int k = 0; k < j; ++k) s -= L[hidx(k, j)] * L[hidx(k, j)];
-        ok = ok && s > 0.0;
-        const double ljj = __builtin_sqrt(s);
-        L[hidx(j, j)] = ljj;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = H[hidx(j, i)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= L[hidx(k, i)] * L[hidx(k, j)];
-            L[hidx(j, i)] = v / ljj;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = -g[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= L[hidx(k, i)] * y[k];
-        y[i] = v / L[hidx(i, i)];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) v -= L[hidx(i, k)] * x[k];
-        x[i] = v / L[hidx(i, i)];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) ok = ok && std::isfinite(x[i]);
-    return ok;
-}
-
-// Rodrigues of omega: I + (sin th / th) K + (2 sin^2(th / 2) / th^2) K^2, K = [omega]_x, K^2 = omega omega^T - th^2 I.
-__device__ __forceinline__ void rodrigues(double w0, double w1, double w2, double (&Rd)[9]) {
-    const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
-    const double th = __builtin_sqrt(th2);
-    double sa = 1.0, sb = 0.5;
-    if (th > 0.0) {
-        const double sh = sin(0.5 * th);
-        sa = sin(th) / th;
-        sb = ((2.0 * sh) * sh) / (th * th);
-    }
-    const double w[3] = {w0, w1, w2};
-    const double K[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Rd[3 * i + j] = (i == j ? 1.0 : 0.0) + (sa * K[3 * i + j] + sb * (w[i] * w[j] - (i == j ? th2 : 0.0)));
-}
+// What pmx::lm_run follows: O_AB, up. (E' < E, E = -O_AB)
+struct Overlap {
+    using Eval = ::Eval;
+    const double4 *X;
+    uint32_t npts;
+    const double4 *Lref;
+    uint32_t m;
+    int lane;
+    __device__ __forceinline__ void eval(const double (&R)[9], const double (&t)[3], Eval &e) const { evaluate(X, npts, Lref, m, R, t, lane, e); }
+    __device__ __forceinline__ double value(const Eval &e) const { return e.oab; }
+    __device__ __forceinline__ bool better(double trial, double cur) const { return trial > cur; }
+    __device__ __forceinline__ double gain(double before, double after) const { return after - before; }
+};
 
 __device__ __forceinline__ double tanimoto(double oab, double oaa, double obb) { return oab / ((oaa + obb) - oab); }
 
@@ -247,7 +204,6 @@ __global__ __launch_bounds__(64 * kWaves) void overlay_kernel(const OverlayArgs 
     const uint32_t row = blockIdx.x * kWaves + (uint32_t)wave;
     const bool live = row < a.n;
     const int lane = (int)(threadIdx.x % 64);
-    const double nan = __builtin_nan("");
 
     for (uint32_t b = threadIdx.x; b < a.m; b += 64 * kWaves) Lref[b] = a.ref[b];
 
@@ -292,11 +248,7 @@ __global__ __launch_bounds__(64 * kWaves) void overlay_kernel(const OverlayArgs 
     if (!live) return;
 
     if (status != PMX_LIGAND_OK) {
-        if (lane < 9) a.rot_out[(size_t)row * 9 + lane] = nan;
-        if (lane < 3) a.trans_out[(size_t)row * 3 + lane] = nan;
-        if (lane < 8) a.energy[(size_t)row * 8 + lane] = nan;
-        if (lane < 4) a.count[(size_t)row * 4 + lane] = lane == 2 ? -1 : 0;
-        if (lane == 0) a.status[row] = status;
+        store_not_ok(a.rot_out, a.trans_out, a.energy, a.count, a.status, row, lane, status);
         return;
     }
     const uint32_t m = a.m;
@@ -317,98 +269,31 @@ __global__ __launch_bounds__(64 * kWaves) void overlay_kernel(const OverlayArgs 
     }
     const double oaa = wave_sum(sAA);
 
-    // ---- the iteration. `cur` is the last accepted evaluation, at (R, t); a trial is evaluated at (Rt, tt)
-    double R[9], t[3], Rt[9], tt[3];
+    // ---- the iteration, from the evaluation at the start. No point, or a row so far away that every term underflows: nothing to follow
+    double R[9], t[3];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = Rt[k] = R0[k];
+    for (int k = 0; k < 9; ++k) R[k] = R0[k];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = tt[k] = t0[k];
-    Eval cur, tr;
-    evaluate(X, npts, Lref, m, R, t, lane, cur);
+    for (int k = 0; k < 3; ++k) t[k] = t0[k];
+    const Overlap obj{X, npts, Lref, m, lane};
+    Eval cur;
+    obj.eval(R, t, cur);
     const double o_start = cur.oab;
-    const double cs0 = cur.c[0], cs1 = cur.c[1], cs2 = cur.c[2];
-    double O = cur.oab;
-    double lambda = 1e-3;
-    int iterations = 0, accepted = 0, reason = 2;
-    if (uniform(npts == 0 || !(O > 0.0))) { // (no point, or a row so far away that every term underflows: nothing to follow)
-        reason = 0;
-    } else {
-        while (uniform(iterations < a.max_iter)) {
-            double delta[6];
-            if (!uniform(solve(cur.H, cur.g, lambda, delta))) { // (a pivot that is not positive: a rejected trial without an evaluation)
-                ++iterations;
-                lambda *= 8.0;
-                if (uniform(lambda > 1e8)) {
-                    reason = 3;
-                    break;
-                }
-                continue;
-            }
-            double Rd[9];
-            rodrigues(delta[0], delta[1], delta[2], Rd);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) Rt[3 * i + j] = (Rd[3 * i] * R[j] + Rd[3 * i + 1] * R[3 + j]) + Rd[3 * i + 2] * R[6 + j];
-            }
-            {
-                const double w0 = t[0] - cur.c[0], w1 = t[1] - cur.c[1], w2 = t[2] - cur.c[2];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) tt[i] = (((Rd[3 * i] * w0 + Rd[3 * i + 1] * w1) + Rd[3 * i + 2] * w2) + cur.c[i]) + delta[3 + i];
-            }
-            evaluate(X, npts, Lref, m, Rt, tt, lane, tr);
-            ++iterations;
-            const double Ot = tr.oab;
-            if (uniform(Ot > O)) { // (E' < E, E = -O_AB)
-                const double before = O;
-                ++accepted;
-                cur = tr;
-#pragma unroll
-                for (int k = 0; k < 9; ++k) R[k] = Rt[k];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) t[k] = tt[k];
-                O = Ot;
-                lambda = fmax(lambda / 4.0, 1e-9);
-                if (uniform(Ot - before <= a.ftol * before)) {
-                    reason = 1;
-                    break;
-                }
-            } else {
-                lambda *= 8.0;
-                if (uniform(lambda > 1e8)) {
-                    reason = 3;
-                    break;
-                }
-            }
-        }
-    }
+    const double c_start[3] = {cur.c[0], cur.c[1], cur.c[2]};
+    const LmRun run = lm_run(obj, cur, R, t, npts != 0 && o_start > 0.0, a.ftol, a.max_iter);
+    const double O = run.value;
 
     // ---- the row's outputs: the last accepted motion (the input's own bits when nothing was accepted)
-    // net rotation from the start: Q = R R0^T, angle = atan2(|vee(Q - Q^T)| / 2, (tr Q - 1) / 2)
-    double Q[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Q[3 * i + j] = (R[3 * i] * R0[3 * j] + R[3 * i + 1] * R0[3 * j + 1]) + R[3 * i + 2] * R0[3 * j + 2];
-    }
-    const double a0 = Q[7] - Q[5], a1 = Q[2] - Q[6], a2 = Q[3] - Q[1];
-    const double sn = 0.5 * __builtin_sqrt((a0 * a0 + a1 * a1) + a2 * a2), cs = 0.5 * (((Q[0] + Q[4]) + Q[8]) - 1.0);
-    const double angle = accepted ? atan2(sn, cs) : 0.0;
-    const double h0 = cur.c[0] - cs0, h1 = cur.c[1] - cs1, h2 = cur.c[2] - cs2;
-    const double shift = __builtin_sqrt((h0 * h0 + h1 * h1) + h2 * h2);
-    double out = 0.0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) out = lane == k ? R[k] : out;
-    if (lane < 9) a.rot_out[(size_t)row * 9 + lane] = out;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out = lane == k ? t[k] : out;
-    if (lane < 3) a.trans_out[(size_t)row * 3 + lane] = out;
+    double angle, shift;
+    lm_net_motion(R, R0, run.accepted, cur.c, c_start, angle, shift);
+    store_motion(a.rot_out, a.trans_out, row, lane, R, t);
     const double obb = a.o_bb;
     const double en[8] = {o_start, O, oaa, obb, tanimoto(o_start, oaa, obb), tanimoto(O, oaa, obb), angle, shift};
+    double out = 0.0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) out = lane == k ? en[k] : out;
     if (lane < 8) a.energy[(size_t)row * 8 + lane] = out;
-    if (lane < 4) a.count[(size_t)row * 4 + lane] = lane == 0 ? iterations : lane == 1 ? accepted : lane == 2 ? reason : (int)npts;
+    if (lane < 4) a.count[(size_t)row * 4 + lane] = lane == 0 ? run.iterations : lane == 1 ? run.accepted : lane == 2 ? run.reason : (int)npts;
     if (lane == 0) a.status[row] = status;
 }
 
@@ -603,8 +488,7 @@ extern "C" int pmx_shape_overlay(const pmx_shape_ref *ref, const pmx_library *li
                                     n, &a.src);
     if (rc != PMX_OK) return rc;
     if (!std::isfinite(point_radius)) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_overlay: point_radius must be finite");
-    if (!std::isfinite(ftol) || ftol < 0.0) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_overlay: ftol must be finite and not negative");
-    if (max_iter < 0 || max_iter > PMX_REFINE_MAX_ITER) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_overlay: max_iter %d, 0 .. %d", max_iter, PMX_REFINE_MAX_ITER);
+    if (const int bad = pmx::lm_check("pmx_shape_overlay", "ftol", ftol, max_iter)) return bad;
     if (n == 0) return PMX_OK;
     if (!rot_out_dev || !trans_out_dev || !energy_dev || !count_dev || !status_dev) return pmx_fail(PMX_ERR_INVALID, "pmx_shape_overlay: null output");
     if (hipSetDevice(ref->device) != hipSuccess) return pmx_fail(PMX_ERR_HIP, "pmx_shape_overlay: hipSetDevice failed");

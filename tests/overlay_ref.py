@@ -7,9 +7,8 @@ taken and how the step is applied:
   "jitter"    forward, with each component of every delta multiplied by 1 +- 2^-52 from a seeded generator
 
 The three differ by rounding alone; how far their results lie apart is the sensitivity figure S of tests/test_overlay_cpu.py, from which the
-bars of the GPU tests follow. `overlay_row` also returns `decision_margin`: the smallest relative distance of any decision the row took from
-its threshold - |O' - O| / O of every accept or reject, |(O' - O) - ftol O| / O of every accepted step, |lambda - 1e8| / 1e8 of every
-rejected one - which says how far the row's integers are from changing.
+bars of the GPU tests follow. The iteration itself is tests/lm_ref.py's, which the refinement's restatement runs too; `overlay_row` also
+returns its `decision_margin` - how far the row's integers are from changing.
 
 The frame and the starts use only + - * / and sqrt, one Python float at a time: the device has the same bits."""
 
@@ -18,20 +17,12 @@ import math
 import numpy as np
 
 import shape_ref
-from refine_ref import _IU, _mat3, hidx, rodrigues, solve
+from lm_ref import _IU, LANES, _butterfly, hidx, lm_loop, net_motion
 
 OK, UNSUPPORTED, KEY_INVALID = 0, 1, 4
 MAX_ITER = 64
 MAX_ATOMS = 256
-LANES = 64
 JACOBI_SWEEPS = 8
-_XOR = [np.arange(LANES) ^ m for m in (1, 2, 4, 8, 16, 32)]
-
-
-def _butterfly(x):
-    for idx in _XOR:
-        x = x + x[idx]
-    return x[0]
 
 
 def _lane_sum(terms, reverse=False):
@@ -162,64 +153,16 @@ def overlay_row(ref_xyz, ref_radius, points, radii, R, t, ftol=1e-6, max_iter=32
     if o_bb is None:
         o_bb = shape_ref.self_overlap(ref_xyz, ref_radius)
     row = Row(ref_xyz, ref_radius, x, rad)
-    R0 = R
     rng = np.random.default_rng(seed)
     oaa = self_overlap_of(row, R, t)
-    cur = evaluate(row, R, t, variant)
-    start = cur
-    O = cur["oab"]
-    if trace is not None:
-        trace.append(O)
-    lam, iterations, accepted, reason, margin = 1e-3, 0, 0, 2, np.inf
-    if row.n == 0 or not O > 0.0:
-        reason = 0
-    else:
-        while iterations < max_iter:
-            delta = solve(cur["H"], cur["g"], lam)
-            if delta is None:
-                iterations += 1
-                lam *= 8.0
-                margin = min(margin, abs(lam - 1e8) / 1e8)
-                if lam > 1e8:
-                    reason = 3
-                    break
-                continue
-            if variant == "jitter":
-                delta = delta * (1.0 + rng.choice([-1.0, 1.0], size=6) * 2.0**-52)
-            Rd = rodrigues(delta[:3])
-            Rt = _mat3(Rd, R)
-            w = t - cur["c"]
-            tt = np.array([(((Rd[i, 0] * w[0] + Rd[i, 1] * w[1]) + Rd[i, 2] * w[2]) + cur["c"][i]) + delta[3 + i] for i in range(3)])
-            tr = evaluate(row, Rt, tt, variant)
-            iterations += 1
-            Ot = tr["oab"]
-            margin = min(margin, abs(Ot - O) / O)
-            if Ot > O:
-                before = O
-                accepted += 1
-                cur, R, t, O = tr, Rt, tt, Ot
-                if trace is not None:
-                    trace.append(O)
-                lam = max(lam / 4.0, 1e-9)
-                margin = min(margin, abs((Ot - before) - ftol * before) / before)
-                if Ot - before <= ftol * before:
-                    reason = 1
-                    break
-            else:
-                lam *= 8.0
-                margin = min(margin, abs(lam - 1e8) / 1e8)
-                if lam > 1e8:
-                    reason = 3
-                    break
-    Q = np.array([[(R[i, 0] * R0[j, 0] + R[i, 1] * R0[j, 1]) + R[i, 2] * R0[j, 2] for j in range(3)] for i in range(3)])
-    a0, a1, a2 = Q[2, 1] - Q[1, 2], Q[0, 2] - Q[2, 0], Q[1, 0] - Q[0, 1]
-    sn, cs = 0.5 * np.sqrt((a0 * a0 + a1 * a1) + a2 * a2), 0.5 * (((Q[0, 0] + Q[1, 1]) + Q[2, 2]) - 1.0)
-    angle = float(np.arctan2(sn, cs)) if accepted else 0.0
-    h = cur["c"] - start["c"]
-    shift = float(np.sqrt((h[0] * h[0] + h[1] * h[1]) + h[2] * h[2]))
-    return dict(status=OK, rotation=R, translation=t,
+    start = evaluate(row, R, t, variant)
+    run = lm_loop(lambda Rt, tt: evaluate(row, Rt, tt, variant), lambda ev: ev["oab"], lambda trial, cur: trial > cur, lambda before, after: after - before,
+                  row.n != 0 and start["oab"] > 0.0, start, R, t, ftol, max_iter, rng if variant == "jitter" else None, trace)
+    O = run["value"]
+    angle, shift = net_motion(run["R"], R, run["accepted"], run["cur"]["c"], start["c"])
+    return dict(status=OK, rotation=run["R"], translation=run["t"],
                 energy=np.array([start["oab"], O, oaa, o_bb, tanimoto(start["oab"], oaa, o_bb), tanimoto(O, oaa, o_bb), angle, shift]),
-                count=np.array([iterations, accepted, reason, row.n]), decision_margin=margin)
+                count=np.array([run["iterations"], run["accepted"], run["reason"], row.n]), decision_margin=run["decision_margin"])
 
 
 # ---------------------------------------------------------------------------------------------------------------- frames and starts

@@ -6,30 +6,16 @@
   "jitter"    forward, with each component of every delta multiplied by 1 +- 2^-52 from a seeded generator
 
 The three differ by rounding alone; how far their results lie apart is the sensitivity figure S of tests/test_refine_cpu.py, from which the
-bars of the GPU tests follow. `refine_row` also returns `decision_margin`: the smallest |E' - E| / E and |decrease - ftol E| / E over the
-decisions the row took - how far the row's integers are from changing."""
+bars of the GPU tests follow. The iteration itself is tests/lm_ref.py's, which the overlay's restatement runs too; `refine_row` also returns
+its `decision_margin` - how far the row's integers are from changing."""
 
 import numpy as np
 
 import clash_ref
+from lm_ref import _IU, LANES, _butterfly, _mat3, hidx, lm_loop, net_motion, rodrigues, solve  # noqa: F401 (other test modules take them from here)
 
 OK, UNSUPPORTED, KEY_INVALID = 0, 1, 4
 MAX_ITER = 64
-LANES = 64
-_XOR = [np.arange(LANES) ^ m for m in (1, 2, 4, 8, 16, 32)]
-
-
-def hidx(i, j):
-    return i * 6 - i * (i - 1) // 2 + (j - i)
-
-
-_IU = [(i, j) for i in range(6) for j in range(i, 6)]
-
-
-def _butterfly(x):
-    for idx in _XOR:
-        x = x + x[idx]
-    return x[0]
 
 
 def _lane_sum(terms, slots, variant):
@@ -156,55 +142,6 @@ def normal_equations(row, R, t, variant="forward"):
     return H, ev["g"], ev["c"]
 
 
-def solve(H21, g, lam):
-    """(H + lam diag(H_ii + 1e-9)) delta = -g by Cholesky, the operations in the header's order; None for a pivot that is not positive."""
-    H21 = [float(v) for v in H21]
-    L = [[0.0] * 6 for _ in range(6)]
-    for j in range(6):
-        s = H21[hidx(j, j)] + lam * (H21[hidx(j, j)] + 1e-9)
-        for k in range(j):
-            s -= L[j][k] * L[j][k]
-        if not s > 0.0:
-            return None
-        L[j][j] = float(np.sqrt(s))
-        for i in range(j + 1, 6):
-            v = H21[hidx(j, i)]
-            for k in range(j):
-                v -= L[i][k] * L[j][k]
-            L[i][j] = v / L[j][j]
-    y = [0.0] * 6
-    for i in range(6):
-        v = -float(g[i])
-        for k in range(i):
-            v -= L[i][k] * y[k]
-        y[i] = v / L[i][i]
-    x = [0.0] * 6
-    for i in range(5, -1, -1):
-        v = y[i]
-        for k in range(i + 1, 6):
-            v -= L[k][i] * x[k]
-        x[i] = v / L[i][i]
-    x = np.array(x)
-    return x if np.isfinite(x).all() else None
-
-
-def rodrigues(w):
-    th2 = float((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2])
-    th = float(np.sqrt(th2))
-    sa, sb = 1.0, 0.5
-    if th > 0.0:
-        sh = float(np.sin(0.5 * th))
-        sa = float(np.sin(th)) / th
-        sb = ((2.0 * sh) * sh) / (th * th)
-    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
-    K2 = np.outer(w, w) - th2 * np.eye(3)
-    return np.eye(3) + (sa * K + sb * K2)
-
-
-def _mat3(A, B):
-    return np.array([[(A[i, 0] * B[0, j] + A[i, 1] * B[1, j]) + A[i, 2] * B[2, j] for j in range(3)] for i in range(3)])
-
-
 def refine_row(atom_xyz, atom_radius, points, radii, R, t, anchors=None, targets=None, weights=None, tolerance=0.5, restraint=0.1, ftol=1e-9, max_iter=32,
                variant="forward", seed=0, trace=None):
     """One row. Returns the kernel's fields - rotation, translation, energy (8), count (4), status - and `decision_margin`. `trace`, a
@@ -219,58 +156,12 @@ def refine_row(atom_xyz, atom_radius, points, radii, R, t, anchors=None, targets
         return bad
     row = Row(atom_xyz, atom_radius, points, radii, anchors, targets, weights, R, t, tolerance, restraint)
     rng = np.random.default_rng(seed)
-    cur = evaluate(row, R, t, variant)
-    start = cur
-    E = cur["Ec"] + row.restraint * cur["Er"]
-    if trace is not None:
-        trace.append(E)
-    lam, iterations, accepted, reason, margin = 1e-3, 0, 0, 2, np.inf
-    if cur["pairs"] == 0:
-        reason = 0
-    else:
-        while iterations < max_iter:
-            delta = solve(cur["H"], cur["g"], lam)
-            if delta is None:
-                iterations += 1
-                lam *= 8.0
-                if lam > 1e8:
-                    reason = 3
-                    break
-                continue
-            if variant == "jitter":
-                delta = delta * (1.0 + rng.choice([-1.0, 1.0], size=6) * 2.0**-52)
-            Rd = rodrigues(delta[:3])
-            Rt = _mat3(Rd, R)
-            w = t - cur["c"]
-            tt = np.array([(((Rd[i, 0] * w[0] + Rd[i, 1] * w[1]) + Rd[i, 2] * w[2]) + cur["c"][i]) + delta[3 + i] for i in range(3)])
-            tr = evaluate(row, Rt, tt, variant)
-            iterations += 1
-            Et = tr["Ec"] + row.restraint * tr["Er"]
-            if not (Et == 0.0 and E == 0.0):  # (no pair and no restraint energy on either side: 0 < 0 is no matter of rounding)
-                margin = min(margin, abs(Et - E) / E)
-            if Et < E:
-                before = E
-                accepted += 1
-                cur, R, t, E = tr, Rt, tt, Et
-                if trace is not None:
-                    trace.append(E)
-                lam = max(lam / 4.0, 1e-9)
-                margin = min(margin, abs((before - Et) - ftol * before) / before)
-                if before - Et <= ftol * before:
-                    reason = 1
-                    break
-            else:
-                lam *= 8.0
-                if lam > 1e8:
-                    reason = 3
-                    break
-    Q = np.array([[(R[i, 0] * row.R0[j, 0] + R[i, 1] * row.R0[j, 1]) + R[i, 2] * row.R0[j, 2] for j in range(3)] for i in range(3)])
-    a0, a1, a2 = Q[2, 1] - Q[1, 2], Q[0, 2] - Q[2, 0], Q[1, 0] - Q[0, 1]
-    sn, cs = 0.5 * np.sqrt((a0 * a0 + a1 * a1) + a2 * a2), 0.5 * (((Q[0, 0] + Q[1, 1]) + Q[2, 2]) - 1.0)
-    angle = float(np.arctan2(sn, cs)) if accepted else 0.0
-    h = cur["c"] - start["c"]
-    shift = float(np.sqrt((h[0] * h[0] + h[1] * h[1]) + h[2] * h[2]))
+    start = evaluate(row, R, t, variant)
+    run = lm_loop(lambda Rt, tt: evaluate(row, Rt, tt, variant), lambda ev: ev["Ec"] + row.restraint * ev["Er"], lambda trial, cur: trial < cur,
+                  lambda before, after: before - after, start["pairs"] != 0, start, R, t, ftol, max_iter, rng if variant == "jitter" else None, trace)
+    cur = run["cur"]
+    angle, shift = net_motion(run["R"], row.R0, run["accepted"], cur["c"], start["c"])
     wsum = float(_lane_sum(row.w, np.arange(len(row.w)), "forward")) if anchors is not None else float(row.m)
     rmsd = float(np.sqrt(cur["Er"] / wsum)) if wsum > 0 else 0.0
-    return dict(status=OK, rotation=R, translation=t, energy=np.array([start["Ec"], start["Er"], cur["Ec"], cur["Er"], rmsd, angle, shift, lam]),
-                count=np.array([iterations, accepted, reason, cur["pairs"]]), decision_margin=margin)
+    return dict(status=OK, rotation=run["R"], translation=run["t"], energy=np.array([start["Ec"], start["Er"], cur["Ec"], cur["Er"], rmsd, angle, shift, run["lam"]]),
+                count=np.array([run["iterations"], run["accepted"], run["reason"], cur["pairs"]]), decision_margin=run["decision_margin"])
