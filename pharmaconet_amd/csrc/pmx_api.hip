@@ -448,12 +448,12 @@ static int init_workspace(ScreenWs &ws, int device, hipStream_t stream) {
 
 // Type weights further apart than PMX_TAILS_RATIO (default 8 = the ratio of the reference's own defaults, graph_match.py:32-40: any override that spreads the weights further takes the exact tails): pair items
 // evaluate rough cells term by term like self items do (item_finish<TAILS>, pmx_screen_tables.h) - slower, and only then.
-// PMX_PAIR_TAILS = 0 / 1 forces it off / on. Decided over all models of a call (pmx_score_multi: the pockets' types together).
-static bool pair_tails(const pmx_model *const *models, int n_models, const Weights &W) {
+// PMX_PAIR_TAILS = 0 / 1 forces it off / on. Decided per pocket, by the types it holds: pmx_score_multi scores each pocket as pmx_score scores
+// it alone and as pmx_explain explains it, whatever else is in the panel (tests/test_gpu_library_select.py).
+static bool pair_tails(const pmx_model *model, const Weights &W) {
     float wmin = INFINITY, wmax = 0.f;
     bool present[PMX_NUM_TYPES] = {};
-    for (int m = 0; m < n_models; ++m)
-        for (int i = 0; i < models[m]->dm.Nm; ++i) present[models[m]->node_type[i]] = true; // (only the types the pockets hold can meet in an entry)
+    for (int i = 0; i < model->dm.Nm; ++i) present[model->node_type[i]] = true; // (only the types the pocket holds can meet in an entry)
     for (int t = 0; t < PMX_NUM_TYPES; ++t) {
         const float a = std::fabs(W.w[t]);
         if (present[t] && a > 0.f && std::isfinite(a)) wmin = std::min(wmin, a), wmax = std::max(wmax, a);
@@ -580,7 +580,6 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
     const bool exact = (flags & 8) != 0;
     // any validation switch: the kernels of pmx_screen_debug.hip (libpmx's own read those bits as zero, pmx_screen_layout.h PMX_WFLAGS)
     const bool debug_kernels = (flags & ~PMX_PRODUCT_FLAGS) != 0;
-    const bool tails = pair_tails(models, n_models, W); // (term-by-term tails for widely spread type weights, see pair_tails)
 
     // ---- plan: per pocket, parameters and launch shapes
     {
@@ -623,6 +622,7 @@ static int score_screen(const pmx_model *const *models, int n_models, const pmx_
     for (int m = 0; m < n_models; ++m) {
         const PocketPlan &pl = plan[(size_t)m];
         ScreenParams p = pl.p;
+        const bool tails = pair_tails(models[m], W); // (term-by-term tails for widely spread type weights, see pair_tails)
         const uint32_t super = pl.super;
         const uint32_t lig_grid = (uint32_t)ws.num_cu * pl.waves_per_cu, task_grid = (uint32_t)ws.num_cu * pl.task_waves_per_cu;
         p.ctl = ctl;
@@ -848,7 +848,7 @@ static int explain_screen(const pmx_model *model, const pmx_library *lib, const 
                           ScreenWs &ws) {
     int rc = init_workspace(ws, lib->device, stream);
     if (rc) return rc;
-    const bool tails = pair_tails(&model, 1, W); // (as pmx_score / pmx_score_f64 decide it for this model)
+    const bool tails = pair_tails(model, W); // (as pmx_score, pmx_score_multi and their _f64 forms decide it for this model)
     PocketPlan pl;
     rc = plan_pocket<G>(model, lib, W, ws.num_cu, stream, pl);
     if (!rc) rc = grow_buffers(ws, pl.need, stream);

@@ -15,6 +15,7 @@ import pytest
 from conftest import load_golden
 from constrained_ref import qualifies, random_constraint
 from explain_ref import NONE, Tables, candidates, ligand_levels, path_score
+from tail_cases import PAIR_SHAPE_SETS, SHAPES, WEIGHT_SETS, _Shim, pair_shape_cases, pair_shape_explained
 
 pytestmark = pytest.mark.gpu
 
@@ -23,6 +24,10 @@ TIE = 1e-5  # a key is pinned where the next total lies more than this (relative
 CONFORMERS = [2, 3, 4, 12, 16, 20, 32, 33, 48]
 LIBRARIES = (("set_6oim_c8", 160), ("set_s64_c8", 48))
 MAX_MODES = 8
+# type weights further apart than PMX_TAILS_RATIO: the first ligands of the same libraries, at G = 1 ... 64
+SPREAD_CONFORMERS = (1, 2, 3, 8, 12, 20, 33)
+SPREAD_WEIGHTS = ("charged_heavy", "charged_light")
+SPREAD_LIBRARIES = (("set_6oim_c8", 64), ("set_s64_c8", 24))
 THREADS = min(os.cpu_count() or 8, 16)
 
 
@@ -63,12 +68,12 @@ def key_exact(gap):
 class Case:
     """One library of the sweep with the oracle's answers: `free` without a constraint, `bound` under `cons[i]` for ligand i (both at 8 modes)."""
 
-    def __init__(self, name, model, lib, seed, constrained=True):
+    def __init__(self, name, model, lib, seed, constrained=True, weights=None):
         from oracle import oracle
         from pharmaconet_amd.constants import weights_vector
 
-        self.name, self.model, self.lib = name, model, lib
-        self.w7 = weights_vector(None)
+        self.name, self.model, self.lib, self.weights = name, model, lib, weights
+        self.w7 = weights_vector(weights)
         self.C = np.array([lib.header(i)[1] for i in range(len(lib))])
         self.free = oracle.oracle_explain(model.flat, lib, self.w7, n_modes=MAX_MODES, num_threads=THREADS)
         self.free["gap"] = mode_gaps(self.free)
@@ -97,16 +102,21 @@ class Case:
         return abs(path_score(self.model, rec, self.w7, self.levels(i), key, c, T) - value) <= RTOL * value
 
 
+def sweep_cases(conformers, weights=None, libraries=LIBRARIES):
+    """The two libraries of test_every_lane_shape_matches_the_oracle at this conformer count (or their first ligands: the generator draws
+    every ligand from a stream of its own) under the type weights `weights`: computed once, shared, never written to."""
+    return _sweep_cases(conformers, None if weights is None else tuple(sorted(weights.items())), tuple(libraries))
+
+
 @functools.lru_cache(maxsize=None)
-def sweep_cases(conformers):
-    """The two libraries of test_every_lane_shape_matches_the_oracle at this conformer count: computed once, shared, never written to."""
+def _sweep_cases(conformers, weight_items, libraries):
     from tools.synthetic import synthetic_library
 
     out = []
-    for name, n in LIBRARIES:
+    for name, n in libraries:
         model, _, _, _ = load_golden(name)
         lib = synthetic_library(n, num_conformers=conformers, model_nodes=_model_nodes(model), active_fraction=0.5, seed=5000 + conformers)
-        out.append(Case(name, model, lib, 5000 + conformers))
+        out.append(Case(name, model, lib, 5000 + conformers, weights=None if weight_items is None else dict(weight_items)))
     return tuple(out)
 
 
@@ -192,24 +202,24 @@ def run_all_three(case, modes=(1, 4, 8), constrained_modes=4):
     dlib = DeviceLibrary(case.lib)
     w_max, w_con, w_modes = [0.0], [0.0], [0.0]
     keys = np.zeros(2, np.int64)
-    ex = explain(case.model, dlib, idx)
-    sc = screen(case.model, dlib, float64=True).scores.cpu().numpy()
+    ex = explain(case.model, dlib, idx, weights=case.weights)
+    sc = screen(case.model, dlib, weights=case.weights, float64=True).scores.cpu().numpy()
     for i in idx:
         keys += check_explanation_row(case, ex, i, i, case.free, None, "explain", w_max)
         assert ulp_close(ex.conf_max[i].mean(), sc[i]), (case.name, i, ex.conf_max[i].mean(), sc[i])
     for M in modes:
-        ms = explain_modes(case.model, dlib, idx, modes=M)
+        ms = explain_modes(case.model, dlib, idx, modes=M, weights=case.weights)
         for i in idx:
             keys += check_modes_row(case, ms, i, i, M, case.free, None, f"modes={M}", w_modes)
             assert same_as_explain(ms, i, ex, i), (case.name, i, M)
     changed = 0
     for i in idx:
         require, exclude = case.cons[i]
-        cx = explain(case.model, dlib, [i], require=require, exclude=exclude)
+        cx = explain(case.model, dlib, [i], weights=case.weights, require=require, exclude=exclude)
         keys += check_explanation_row(case, cx, 0, i, case.bound, case.cons[i], "constrained", w_con)
         assert (cx.conf_max[0] <= ex.conf_max[i]).all(), (case.name, i, require, exclude)
         changed += not np.array_equal(cx.conf_max[0], ex.conf_max[i])
-        ms = explain_modes(case.model, dlib, [i], modes=constrained_modes, require=require, exclude=exclude)
+        ms = explain_modes(case.model, dlib, [i], modes=constrained_modes, weights=case.weights, require=require, exclude=exclude)
         keys += check_modes_row(case, ms, 0, i, constrained_modes, case.bound, case.cons[i], f"constrained modes={constrained_modes}", w_modes)
         assert same_as_explain(ms, 0, cx, 0), (case.name, i, "constrained")
     assert changed > 0, case.name  # the constraints bite
@@ -230,6 +240,70 @@ def test_explain_family_matches_the_oracle_at_every_lane_shape(conformers):
         print(f"C={conformers} {case.name}: worst relative error maxima {w_max:.2e}, constrained maxima {w_con:.2e}, mode values {w_modes:.2e}; "
               f"{keys[0]} keys compared exactly, {keys[1]} by total; key-exact share of the oracle's entries: maxima {top:.3f}, modes {exact:.3f}")
         assert keys[0] > 0
+
+
+@pytest.mark.parametrize("wname", SPREAD_WEIGHTS)
+@pytest.mark.parametrize("conformers", SPREAD_CONFORMERS)
+def test_explain_family_under_spread_weights(conformers, wname):
+    """explain_kernel<G, true, *>: type weights a factor 1000 apart, so pair items take the term-by-term tails (`pair_tails`, csrc/pmx_api.hip).
+    Everything the test above checks, on the first 64 and 24 ligands of its libraries, at one mode count - and the mean against
+    pmx_score_f64 now holds across the two deciders of the arm (explain_screen and score_screen)."""
+    cases = sweep_cases(conformers, WEIGHT_SETS[wname], SPREAD_LIBRARIES)
+    top, exact = honest(cases)
+    for case in cases:
+        w_max, w_con, w_modes, keys = run_all_three(case, modes=(8,), constrained_modes=4)
+        print(f"C={conformers} [{wname}] {case.name}: worst relative error maxima {w_max:.2e}, constrained maxima {w_con:.2e}, mode values {w_modes:.2e}; "
+              f"{keys[0]} keys compared exactly, {keys[1]} by total; key-exact share of the oracle's entries: maxima {top:.3f}, modes {exact:.3f}")
+        assert keys[0] > 0
+
+
+@pytest.mark.parametrize("conformers", SHAPES)
+def test_explain_takes_the_tail_arm(conformers, monkeypatch):
+    """The test that fails if the explain kernels ignore `tails`: the libraries of test_gpu_tail_shapes.py (one heavy item swept through its
+    tails, on the grid where the tabulated tail alone is off by 1e-5) through explain and explain_modes(modes=2), on the two-cluster model
+    as `engine.screen` takes it there (an object with `.flat`). Maxima and mode values at 2e-6 with the oracle's zeros, mode 0 bit for bit
+    explain; with PMX_PAIR_TAILS=0 other bits in a maximum of a record that is mostly that one tail item; and in both settings the mean
+    within 4 ulp of pmx_score_f64, which decides the arm on its own."""
+    from pharmaconet_amd.engine import DeviceLibrary, explain, explain_modes, screen
+
+    wname, sigma_min_to = PAIR_SHAPE_SETS[0]
+    wdict = WEIGHT_SETS[wname]
+    cases, refs = pair_shape_cases(wname, sigma_min_to, conformers), pair_shape_explained(wname, sigma_min_to, conformers)
+    assert len(cases) == 6 and sum(int(c.mostly_tail.sum()) for c in cases) > 0
+    worst, worst_off, n_differ = 0.0, 0.0, 0
+    for c, ref in zip(cases, refs):
+        shim = _Shim(c.flat)
+        dlib = DeviceLibrary(c.lib)
+        idx = np.arange(len(c.lib))
+        want = ref["values"][:, :, :conformers]  # [n, 2, C]
+        assert (want[:, 0] > 0).all(), (c.a, c.b)
+
+        def family():
+            ex = explain(shim, dlib, idx, weights=wdict)
+            ms = explain_modes(shim, dlib, idx, modes=2, weights=wdict)
+            sc = screen(shim, dlib, weights=wdict, float64=True).scores.cpu().numpy()
+            assert (ex.status == 0).all() and (ms.status == 0).all(), (c.a, c.b)
+            for i in idx:
+                assert same_as_explain(ms, i, ex, i), (c.a, c.b, i)
+            conf_max, values = np.stack(ex.conf_max), np.stack(ms.values)
+            assert ulp_close(conf_max.mean(axis=1), sc).all(), (c.a, c.b)
+            return conf_max, values
+
+        conf_max, values = family()
+        assert conf_max.shape == want[:, 0].shape and values.shape == want.shape
+        assert np.array_equal(values == 0, want == 0), (c.a, c.b)
+        nz = want > 0
+        worst = max(worst, float((np.abs(values[nz] - want[nz]) / want[nz]).max()))
+        assert np.allclose(conf_max, want[:, 0], rtol=RTOL, atol=0) and np.allclose(values, want, rtol=RTOL, atol=0), (c.a, c.b, worst)
+        monkeypatch.setenv("PMX_PAIR_TAILS", "0")
+        off, _ = family()
+        monkeypatch.delenv("PMX_PAIR_TAILS")
+        worst_off = max(worst_off, float((np.abs(off - want[:, 0]) / want[:, 0]).max()))
+        n_differ += int((conf_max != off).any(axis=1)[c.mostly_tail].sum())
+        dlib.close()
+    print(f"C={conformers} [{wname}, sigma_min {sigma_min_to}]: worst relative error of the mode values {worst:.2e} (maxima with the tabulated tails "
+          f"alone, PMX_PAIR_TAILS=0: {worst_off:.2e}); {n_differ} mostly-tail records change with the arm")
+    assert n_differ > 0, "no mostly-tail maximum depends on the arm"
 
 
 def raw_call(model, dlib, idx, modes=0, constraint=None):
@@ -314,18 +388,22 @@ def test_mixed_conformer_counts_in_one_library():
             assert np.allclose(values, want, rtol=RTOL, atol=0) and np.array_equal(values == 0, want == 0), what
 
 
-@pytest.mark.parametrize("conformers", [3, 16, 33])
-def test_attribution_of_explained_ligands_at_other_shapes(conformers):
+@pytest.mark.parametrize("conformers,wname", [(3, "default"), (16, "default"), (33, "default"), (3, "charged_heavy"), (16, "charged_heavy"), (33, "charged_heavy")],
+                         ids=["3", "16", "33", "3-charged_heavy", "16-charged_heavy", "33-charged_heavy"])
+def test_attribution_of_explained_ligands_at_other_shapes(conformers, wname):
     """`Explanation.attribution` of every explained ligand at G = 4, 16 and 64: pmx_attribute's total of the reported key at the best
-    conformer is that conformer's maximum (2e-6, test_gpu_attribution.py::test_attribution_of_explained_ligands), its shares add up to it."""
+    conformer is that conformer's maximum (2e-6, test_gpu_attribution.py::test_attribution_of_explained_ligands), its shares add up to it.
+    Under `charged_heavy` this is the cross-check of the TAILS design on realistic ligands: pmx_attribute evaluates every item term by
+    term, explain reads the tables and takes the term-by-term tails."""
     from pharmaconet_amd.engine import DeviceLibrary, explain
 
     attributed = 0
-    for case in sweep_cases(conformers):
+    weights = WEIGHT_SETS[wname]
+    for case in sweep_cases(conformers) if weights is None else sweep_cases(conformers, weights, SPREAD_LIBRARIES):
         dlib = DeviceLibrary(case.lib)
-        ex = explain(case.model, dlib, np.arange(len(case.lib)))
+        ex = explain(case.model, dlib, np.arange(len(case.lib)), weights=weights)
         assert (ex.status == 0).all()
-        at = ex.attribution(case.model, dlib)
+        at = ex.attribution(case.model, dlib, weights=weights)
         assert len(at) == len(ex) and (at.status == 0).all(), case.name
         worst = 0.0
         for r, i in enumerate(at.rows):

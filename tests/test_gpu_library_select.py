@@ -325,6 +325,47 @@ def test_screen_multi_and_panel():
         screen_multi([m0], dlib).margin(0)
 
 
+def test_screen_multi_and_panel_one_pocket_one_answer():
+    """The bit-equalities of the test above under {"Halogen": 100}: model_clustered21 holds no Halogen, Aromatic or Anion node, so alone its
+    weights are 8 : 1 apart and its pair items read the tables; model_6oim_like's are 100 : 1 apart and take the term-by-term tails. In a
+    panel each pocket is still scored as `screen` scores it alone, and as `explain` explains it (means of the maxima, 4 ulp)."""
+    from pharmaconet_amd import PharmacophoreModel
+    from pharmaconet_amd.constants import TYPE_ID
+    from pharmaconet_amd.engine import explain, screen, screen_multi
+
+    weights = {"Halogen": 100.0}
+    m0, lib, _, dlib, _, status = whole_screen("set_6oim_c8", False)
+    m1 = PharmacophoreModel.load(GOLDEN / "model_clustered21.pm")
+    held = [{int(t) for t in m.flat.node_type} for m in (m0, m1)]
+    assert TYPE_ID["Halogen"] in held[0] and not held[1] & {TYPE_ID[t] for t in ("Halogen", "Aromatic", "Anion")}
+    for float64 in (False, True):
+        want = [screen(m, dlib, weights=weights, float64=float64).scores.cpu().numpy() for m in (m0, m1)]
+        for models, rows in (([m0, m1], (0, 1)), ([m1, m0], (1, 0))):
+            panel = screen_multi(models, dlib, weights=weights, float64=float64)
+            got = panel.scores.cpu().numpy()
+            assert got.shape == (2, len(lib)) and got.dtype == want[0].dtype
+            for r, m in enumerate(rows):
+                differ = np.flatnonzero(~((got[r] == want[m]) | (np.isnan(got[r]) & np.isnan(want[m]))))
+                assert differ.size == 0, (float64, rows, m, differ[:8].tolist(), got[r][differ[:8]].tolist(), want[m][differ[:8]].tolist())
+            assert np.array_equal(panel.status.cpu().numpy(), status)
+    assert np.count_nonzero(want[1]) > len(lib) // 2  # (float64 columns from here on)
+    # (explain walks a tree to its end with one wavefront: of model_6oim_like's, those the reference counts at most 10^5 nodes in; the others' all)
+    light = np.flatnonzero(load_golden("set_6oim_c8")[3]["n_tree"] <= 100000)
+    for m, column, idx in ((m0, got[1], light), (m1, got[0], np.arange(len(lib)))):  # the last panel was [m1, m0]
+        ex = explain(m, dlib, idx, weights=weights)
+        ok = status[idx] == 0
+        assert np.array_equal(ex.status, status[idx]) and ok.sum() > len(lib) // 2
+        means = np.array([v.mean() for v in ex.conf_max])[ok]
+        assert (np.abs(means - column[idx][ok]) <= 4 * np.spacing(np.maximum(np.abs(means), np.abs(column[idx][ok])))).all()
+    # ScreeningResult.panel: the screen's k best against the other pocket
+    k = 12
+    other_scores = screen(m1, dlib, weights=weights).scores.cpu().numpy()
+    res = screen(m0, dlib, weights=weights, topk=k)
+    top = res.topk_indices.cpu().numpy()
+    ps = res.panel(k, [m1]).scores.cpu().numpy()
+    assert np.array_equal(ps[0], res.topk_scores.cpu().numpy()) and np.array_equal(ps[1], other_scores[top])
+
+
 def test_cli_panel_and_save_top(tmp_path):
     from pharmaconet_amd import PackedLibrary
     from pharmaconet_amd.screening import main

@@ -10,88 +10,19 @@ clusters, two-cluster ligands whose pair entry has L1 x L2 = 2 or 4 node pairs -
 under the default weights and under overrides with weight ratios up to 1000 (w x w ratio 10^6), GPU against the oracle.
 """
 
-import dataclasses
 import itertools
 import os
-import struct
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, rel_err
+from tail_cases import WEIGHT_SETS, _Shim, _pin, _record, _rescaled, _subsets, _two_cluster_model, heavy_tail_library
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 2e-6  # where the oracle's score is above FLOOR
 FLOOR = 1e-30
-
-WEIGHT_SETS = {
-    "default": None,
-    "charged_heavy": {"Cation": 100.0, "Anion": 100.0, "Hydrophobic": 0.1},  # VERDICT r4's example (--cation 100 --hydrophobic 0.1)
-    "charged_light": {"Cation": 0.1, "Anion": 0.1, "Hydrophobic": 100.0},   # ... and its inverse
-    # types that share clusters in the fixture models (Cation + HBond, Aromatic + Hydrophobic) a factor 1000 apart
-    "core_heavy": {"Cation": 100.0, "Anion": 100.0, "Aromatic": 100.0, "HBond_donor": 0.1, "HBond_acceptor": 0.1, "Hydrophobic": 0.1, "Halogen": 0.1},
-    "core_light": {"Cation": 0.1, "Anion": 0.1, "Aromatic": 0.1, "HBond_donor": 100.0, "HBond_acceptor": 100.0, "Hydrophobic": 100.0, "Halogen": 100.0},
-}
-
-
-class _Shim:
-    """What engine.screen needs of a model: `.flat` and a slot for the device handle."""
-
-    def __init__(self, flat):
-        self.flat = flat
-        self._engine_handle = None
-
-
-def _record(masks_a, masks_b, xyz: np.ndarray) -> bytes:
-    """Two ligand clusters (nodes of `masks_a`, then of `masks_b`); xyz float32 [n][3][C]."""
-    n, C = xyz.shape[0], xyz.shape[2]
-    head = struct.pack("<HHHH", n, C, 2, 0) + bytes(list(masks_a) + list(masks_b)) + bytes([len(masks_a), n])
-    head += b"\0" * (-len(head) % 4)
-    rec = head + np.ascontiguousarray(xyz, dtype=np.float32).tobytes()
-    return rec + b"\0" * (-len(rec) % 16)
-
-
-def _subsets(flat, a: int):
-    """Distinct non-empty node subsets of model cluster `a` by ligand type mask (graph_match.py:148-150): {node tuple: mask}."""
-    nodes = int(np.asarray(flat.cluster_nodes).reshape(flat.num_clusters, -1)[a, 0])
-    subs = {}
-    for mask in range(1, 128):
-        sub = tuple(m for m in range(flat.num_nodes) if (nodes >> m) & 1 and (mask >> int(flat.node_type[m])) & 1)
-        if sub and sub not in subs:
-            subs[sub] = mask
-    return subs
-
-
-def _two_cluster_model(flat, a: int, b: int):
-    """The model reduced to clusters a and b (all nodes and edges kept, so node indices stand)."""
-    idx = [a, b]
-    return dataclasses.replace(
-        flat,
-        cluster_nodes=np.asarray(flat.cluster_nodes)[idx].copy(),
-        cluster_typemask=flat.cluster_typemask[idx].copy(),
-        cluster_center=flat.cluster_center[idx].copy(),
-        cluster_size=flat.cluster_size[idx].copy(),
-        cluster_type=tuple(flat.cluster_type[i] for i in idx),
-    )
-
-
-def _pin(flat, A, B):
-    """A distance at which the item of node subsets (A, B) passes the majority test of match_utils.py:55-61 (the edge mean that
-    most terms lie within 2 sigma of), or None."""
-    mean = flat.edge_mean.astype(np.float32)
-    std = flat.edge_std.astype(np.float32)
-    best, best_d = -1, None
-    for m, n in itertools.product(A, B):
-        d = np.float32(mean[m, n])
-        if not np.isfinite(d):
-            continue
-        cnt = sum(1 for mm, nn in itertools.product(A, B) if abs(np.float32(d - mean[mm, nn]) / std[mm, nn]) < 2.0)
-        if cnt > best:
-            best, best_d = cnt, float(d)
-    if best_d is None or 2 * best < len(A) * len(B):
-        return None
-    return best_d
 
 
 def _coords_12(t, p03):
@@ -224,34 +155,6 @@ def test_pair_entries_with_one_item_in_the_tails_match_the_oracle(name, max_pair
         assert st["worst"] <= RTOL, f"[{wname}] max rel err {st['worst']:.3e} at (a, b, oracle score) = {st['at']}"
 
 
-def _heavy_light(flat, a, w7):
-    """The node subsets of cluster `a` made of its heaviest-weighted type only and of its lightest only: ((nodes, mask), (nodes, mask)) or None."""
-    subs = _subsets(flat, a)
-    ws = sorted({w7[int(flat.node_type[m])] for sub in subs for m in sub})
-    if len(ws) < 2:
-        return None
-    pick = {}
-    for sub, mask in subs.items():
-        kinds = {w7[int(flat.node_type[m])] for m in sub}
-        for name, w in (("H", ws[-1]), ("L", ws[0])):
-            if kinds == {w} and (name not in pick or len(sub) > len(pick[name][0])):
-                pick[name] = (sub, mask)
-    return (pick["H"], pick["L"]) if len(pick) == 2 else None
-
-
-def _rescaled(flat, sigma_min_to: float):
-    """The same model with every length multiplied so that its smallest edge sigma is `sigma_min_to` - just above a power of two, the
-    tabulated functions' grid (h = the largest power of two <= sigma_min / 4) is as coarse against the sigmas as it can get."""
-    f = np.float64(sigma_min_to) / np.float64(np.nanmin(flat.edge_std))
-    return dataclasses.replace(
-        flat,
-        edge_mean=(flat.edge_mean.astype(np.float64) * f).astype(np.float32),
-        edge_std=(flat.edge_std.astype(np.float64) * f).astype(np.float32),
-        cluster_center=flat.cluster_center * f,
-        cluster_size=flat.cluster_size * f,
-    )
-
-
 @pytest.mark.parametrize("wname,sigma_min_to", [("core_heavy", None), ("core_light", None), ("charged_heavy", None), ("core_heavy", 1.0000005), ("core_light", 2.000001)])
 def test_one_heavy_item_in_the_tails_beside_light_items_that_pass(wname, sigma_min_to, oracle, monkeypatch):
     """The entry the 2- and 4-pair sweeps above cannot build (their mixed items cap the contrast at w_max / w_min): two ligand
@@ -262,7 +165,7 @@ def test_one_heavy_item_in_the_tails_beside_light_items_that_pass(wname, sigma_m
     rough cells term by term when the call's weights are this far apart (item_finish<TAILS>); PMX_PAIR_TAILS=0 shows what the
     tabulated value alone would have given (the fixture model's sigmas are 5.6 grid steps and more; rescaled so that the smallest is
     exactly 4, the tabulated tail alone is off by 10^-5)."""
-    from pharmaconet_amd import PackedLibrary, PharmacophoreModel, engine
+    from pharmaconet_amd import PharmacophoreModel, engine
     from pharmaconet_amd.constants import weights_vector
 
     flat = PharmacophoreModel.load(GOLDEN / "model_6oim_like.pm").flat
@@ -271,35 +174,15 @@ def test_one_heavy_item_in_the_tails_beside_light_items_that_pass(wname, sigma_m
     wdict = WEIGHT_SETS[wname]
     w7 = weights_vector(wdict)
     rng = np.random.default_rng(7)
-    far = 12.0 * float(np.nanmax(flat.edge_std))  # where the heavy nodes sit, off the axis of the light ones
-    step = 0.0125 * float(np.nanmin(flat.edge_std)) / 1.4
     worst, worst_off, n_scores, n_tail, n_pairs, n_exactv = 0.0, 0.0, 0, 0, 0, 0
     for a in range(flat.num_clusters):
         for b in range(flat.num_clusters):
             if a == b:
                 continue
-            ha, hb = _heavy_light(flat, a, w7), _heavy_light(flat, b, w7)
-            if ha is None or hb is None:
-                continue
-            (Ha, mHa), (La, mLa) = ha
-            (Hb, mHb), (Lb, mLb) = hb
-            p_ll, p_hh = _pin(flat, La, Lb), _pin(flat, Ha, Hb)
-            if p_ll is None or p_hh is None:
+            lib = heavy_tail_library(flat, w7, a, b, 8, rng=rng)  # (one jitter draw per cluster pair that has a library)
+            if lib is None:
                 continue
             n_pairs += 1
-            jit = rng.normal(size=(2, 3, 3)) * 0.14 * float(np.nanmin(flat.edge_std))
-            recs = []
-            for j in range(200):
-                t = np.maximum(p_hh - 240 * step + (j * 8 + np.arange(8)) * step, 0.05)  # the heavy pair, from 2 sigma inside its mean to 10 sigma beyond
-                xyz = np.zeros((8, 3, 8))
-                for k in range(3):
-                    xyz[k] = jit[0, k][:, None]
-                    xyz[4 + k] = jit[1, k][:, None]
-                    xyz[4 + k, 0, :] += p_ll
-                xyz[3, 0, :], xyz[3, 1, :] = p_ll / 2 - t / 2, far
-                xyz[7, 0, :], xyz[7, 1, :] = p_ll / 2 + t / 2, far
-                recs.append(_record([mLa] * 3 + [mHa], [mLb] * 3 + [mHb], xyz.astype(np.float32)))
-            lib = PackedLibrary.from_records(recs)
             sub = _two_cluster_model(flat, a, b)
             ref, stats = oracle.oracle_score(sub, lib, w7, num_threads=os.cpu_count() or 8, with_stats=True)
             assert np.all(stats["p_entries"] - stats["p_invalid"] > 0)

@@ -7,7 +7,6 @@ engine tabulates the sums over model node pairs as functions of the one distance
 cluster of the fixture models and every pair of its node subsets, two-node single-cluster ligands whose node distance runs
 from 0 to 5 A beyond the table's range, against the oracle."""
 
-import dataclasses
 import os
 import struct
 
@@ -15,73 +14,12 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, rel_err
+from tail_cases import _Shim, _single_cluster_model, _subset_pairs, _sweep_library, _table_range
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 2e-6  # where the oracle's score is above 1e-30
 FLOOR = 1e-30
-
-
-class _Shim:
-    """What engine.screen needs of a model: `.flat` and a slot for the device handle."""
-
-    def __init__(self, flat):
-        self.flat = flat
-        self._engine_handle = None
-
-
-def _two_node_record(mask1: int, mask2: int, d: np.ndarray) -> bytes:
-    """One cluster of two nodes, node 0 at the origin and node 1 at (d[c], 0, 0) in conformer c."""
-    C = len(d)
-    xyz = np.zeros((2, 3, C), dtype=np.float32)
-    xyz[1, 0, :] = d
-    head = struct.pack("<HHHH", 2, C, 1, 0) + bytes([mask1, mask2]) + bytes([2])
-    head += b"\0" * (-len(head) % 4)
-    rec = head + xyz.tobytes()
-    return rec + b"\0" * (-len(rec) % 16)
-
-
-def _subset_pairs(flat, a: int):
-    """Distinct non-empty node subsets of model cluster `a` by ligand type mask (graph_match.py:148-150), one mask each, and
-    every unordered pair of them (the same subset twice included: two ligand nodes of one type)."""
-    nodes = int(flat.cluster_nodes[a])
-    subs = {}
-    for mask in range(1, 128):
-        sub = 0
-        for m in range(flat.num_nodes):
-            if (nodes >> m) & 1 and (mask >> int(flat.node_type[m])) & 1:
-                sub |= 1 << m
-        if sub and sub not in subs:
-            subs[sub] = mask
-    masks = list(subs.values())
-    return [(masks[i], masks[j]) for i in range(len(masks)) for j in range(i, len(masks))]
-
-
-def _single_cluster_model(flat, a: int):
-    """The model reduced to cluster `a` (all nodes and edges kept, so node indices stand): the two-node ligand then has one
-    level with one candidate, and its score is the mean over conformers of max(0, S[0][a])."""
-    return dataclasses.replace(
-        flat,
-        cluster_nodes=flat.cluster_nodes[a:a + 1].copy(),
-        cluster_typemask=flat.cluster_typemask[a:a + 1].copy(),
-        cluster_center=flat.cluster_center[a:a + 1].copy(),
-        cluster_size=flat.cluster_size[a:a + 1].copy(),
-        cluster_type=tuple(flat.cluster_type[a:a + 1]),
-    )
-
-
-def _sweep_library(pairs, dmax: float, n_conf: int, delta: float):
-    """For every mask pair, ligands whose conformers step through [0, dmax] in `delta` increments."""
-    from pharmaconet_amd import PackedLibrary
-
-    per = int(np.ceil(dmax / (delta * n_conf)))
-    recs, dist = [], []
-    for m1, m2 in pairs:
-        for j in range(per):
-            d = ((j * n_conf + np.arange(n_conf)) * delta).astype(np.float32)
-            recs.append(_two_node_record(m1, m2, d))
-            dist.append(d)
-    return PackedLibrary.from_records(recs), np.array(dist)
 
 
 def _gpu(model, lib, monkeypatch=None, flags=None):
@@ -95,10 +33,6 @@ def _gpu(model, lib, monkeypatch=None, flags=None):
     if flags is not None:
         monkeypatch.delenv("PMX_TREE_FLAGS")
     return out + (stats,)
-
-
-def _table_range(flat) -> float:
-    return float(np.nanmax(flat.edge_mean.astype(np.float64) + 7.0 * flat.edge_std.astype(np.float64)))
 
 
 @pytest.mark.parametrize("name,n_conf,delta", [("model_6oim_like", 8, 0.011), ("model_6oim_like", 1, 0.0173),
