@@ -1083,6 +1083,118 @@ int pmx_shape_starts(const pmx_shape_ref *ref, const pmx_library *lib /* NULL in
                      double *trans_out_dev /* [n][3] */, double *frame_dev /* [n][16] */, int32_t *status_dev, void *stream);
 
 /*
+ * Colour overlap (pmx_colour.hip): the two shape calls above compare untyped spheres - "shape only". These calls add the typed term, the
+ * "colour" of ligand-based screening: does a posed hit put its pharmacophore features - the typed nodes every library record carries - where
+ * a known binder has features of the same type? pmx_pose_colour judges a pose where it stands, pmx_combo_overlay moves a row by shape and
+ * colour together. No direction is compared - no donor / acceptor vector, no ring normal - and no hydrogens: a feature is a point with a
+ * set of types. The overlaps are first-order as the shape term's. The reference has no counterpart; the specification is this comment,
+ * and tests/colour_ref.py and tests/combo_ref.py restate it in NumPy.
+ *
+ * The colour reference: pmx_colour_ref_create copies 1 <= f <= PMX_MAX_LIGAND_NODES features of the known ligand - float32 positions
+ * xyz[f][3] in the pocket's frame, type masks typemask[f] (bit t is type t; every mask < 128; a mask of 0 is allowed: such a feature pairs
+ * with nothing) - with the type weights weights[PMX_NUM_TYPES] (finite, >= 0) and one radius (finite, > 0) to `device`. Anything else is
+ * PMX_ERR_INVALID, checked on the host before anything is copied. The handle keeps the features widened to float64, the weights as doubles,
+ * alpha_c = KAPPA / ((double)radius * (double)radius) and C_BB, the self-overlap of the reference: the C_AA (below) of the reference's own
+ * features and masks taken as a feature-mode row under the identity motion, computed once at create by the kernel of pmx_pose_colour, so the
+ * two are equal bit for bit. The copy and C_BB are finished when the call returns. pmx_colour_ref_self hands C_BB out;
+ * pmx_colour_ref_destroy frees the handle (NULL is allowed).
+ *
+ * The pair term. A posed typed point a with mask ma and a feature (or posed typed point) b with mask mb:
+ *   w = the sum, in ascending type t, of (double)weights[t] over the bits set in ma & mb, from 0.0
+ *   a pair with w == 0 is left out (of every sum, and of every nearest-partner search: such a pair shares no weighted type)
+ *   otherwise V = the pair term of the pmx_pose_shape comment with alpha_a = alpha_b = alpha_c (e = p - y, d2, s, q, k, V in its order),
+ *   and the pair's term is w * V
+ * Arithmetic is float64 with every operation rounded (no fused multiply-add), float32 inputs widened; the posed point is pmx_pose_clash's.
+ * All terms are >= 0 because the weights are: a restatement differs from the device through exp alone.
+ *
+ * pmx_pose_colour. Rows come from one of two sources, never both: node mode (lib, ligands_dev, conformer_dev: the record's nodes at
+ * that conformer with the record's type masks) or feature mode (lib NULL; feat_off_dev [n + 1], feat_xyz_dev [.][3], feat_mask_dev [.]:
+ * typed points of the caller's, row i holding points feat_off[i] .. feat_off[i + 1]). The status rules are pmx_pose_clash's, with two more:
+ * a row of more than PMX_MAX_LIGAND_NODES typed points gets PMX_LIGAND_UNSUPPORTED, a row with a mask >= 128 PMX_LIGAND_KEY_INVALID (a
+ * record of an uploaded library has no such mask: pmx_library_upload neutralises a record that has one, and its rows are
+ * PMX_LIGAND_UNSUPPORTED).
+ * Per typed point a of the row (lane a):
+ *   cross_a    the sum of w * V over the features in ascending b
+ *   cross_a^t  for each type t, the sum of weights[t] * V over the features in ascending b whose pair with a shares t (and has w != 0)
+ *   self_a     the sum of w * V over all points a' of the row in ascending a', a itself included
+ *   near2_a    the smallest d2 to a feature whose pair with a has w != 0; node_feature[a] the lowest b that attains it, -1 if there is none
+ * Per feature b < f (lane b): feat_near2_b, the smallest d2 (from e = p - y, as above) over the row's points whose pair with b has
+ * w != 0; feat_node[b] the lowest a that attains it, -1 if there is none.
+ * Row sums: lane a holds point a (a row has at most 64), the 64 lanes are summed by the fixed butterfly of pmx_pose_shape:
+ *   C_AB = the sum of cross_a     C_AA = the sum of self_a     C_AB^t = the sum of cross_a^t     S = the sum of near2_a over the matched
+ *   points, those with node_feature[a] >= 0
+ * The C_AB^t add up to C_AB only up to rounding: a pair's w is rounded once as a sum of weights, its parts are rounded one by one.
+ * Outputs, per row:
+ *   summary_dev       double [n][8]   [0] C_AB  [1] C_AA  [2] C_BB (the handle's)
+ *                                     [3] the colour Tanimoto C_AB / ((C_AA + C_BB) - C_AB), and 0 where C_AB == 0
+ *                                     [4] C_AB / C_BB, 0 where C_BB is 0     [5] C_AB / C_AA, 0 where C_AA is 0
+ *                                     [6] sqrt(S / matched points), NaN where none is matched     [7] 0
+ *   type_overlap_dev  double [n][PMX_NUM_TYPES]   C_AB^t
+ *   count_dev         int32 [n][4]    [0] points; [1] points with node_feature[a] >= 0 and near2_a < c2; [2] features with feat_node[b] >= 0
+ *                                     and feat_near2_b < c2; [3] f;   c2 = (double)cover * (double)cover
+ *   node_colour_dev, node_near_dev  double [n][64]: cross_a and sqrt(near2_a) - NaN for a point without a partner, and beyond the row's points
+ *   node_feature_dev  int32 [n][64]   (-1 beyond the row's points)
+ *   feat_near_dev, feat_node_dev    double / int32 [n][64]: sqrt(feat_near2_b) and feat_node[b]; NaN / -1 without a partner and for b >= f
+ *   matched_fp_dev    uint64 [n][PMX_FINGERPRINT_WORDS]: bit b of word 0 is set where feature b is counted in count[2]; the other words are 0.
+ *                     The format pmx_fingerprint_tanimoto and pmx_fingerprint_leaders take: hits can be clustered by which of the
+ *                     binder's interactions they reproduce
+ *   status_dev        int32 [n]
+ * A row that is not OK has NaN in all of summary, type_overlap, node_colour, node_near and feat_near, -1 in node_feature and feat_node,
+ * counts of 0 (all four) and an empty matched_fp.
+ * Exact consequences. (i) The reference's own features, in order, under the identity motion give C_AB == C_AA == C_BB bit for bit and a
+ * Tanimoto of exactly 1.0 (where C_BB > 0). (ii) One point on one feature of a shared weighted type gives exactly w * (8.0 * (q * sqrt(q))),
+ * q = PI / (alpha_c + alpha_c). (iii) A row far from the reference has C_AB == 0 through underflow and Tanimoto exactly 0. (iv) A row
+ * whose types are all zero-weighted, or shared with no feature, has C_AB == 0 and Tanimoto 0.
+ *
+ * pmx_combo_overlay maximises F = O_AB + colour_weight * C_AB over the rigid motion of a row. It takes a pmx_shape_ref and a
+ * pmx_colour_ref on one device and a library on that device, which is always required: the colour points are the record's nodes (ligand
+ * ligands_dev[i], conformer conformer_dev[i]) with the record's masks. The shape points are those same nodes with point_radius (the point
+ * triple NULL) or the point triple - what pmx_atoms_gather writes for the same (ligand, conformer) rows. Both point sets move under the
+ * one motion. The status rules are pmx_shape_overlay's for the shape points and pmx_pose_colour's for the nodes; the nodes' status comes
+ * first.
+ * Evaluation at (R, t): O_AB, c (the centroid of the posed shape points; 0 where there is none), H_shape and g_shape are exactly
+ * pmx_shape_overlay's. For the node a of lane a and a feature b with w != 0: e, d2, k and V are the pair term above, Vw = w * V,
+ * kappa = (2.0 * k) * Vw; in ascending b, cross_a = the sum of Vw, f_a = the sum of kappa * e, w_a = the sum of kappa. C_AB = the butterfly
+ * of the cross_a: pmx_pose_colour's bits. With r = p_a - c the node's block of H_colour and g_colour is the closed form of the shape term,
+ * operation for operation (w_a (rr - r_0 r_0); w_a * -(r_0 r_1); ..; g_0 = r_1 f_2 - r_2 f_1; ..), each value 0.0 + the block's (a lane
+ * has one node), then the butterfly per value. After the butterflies H = H_shape + colour_weight * H_colour and g = g_shape +
+ * colour_weight * g_colour, value by value (the six values of H that are 0 by structure stay 0); F = O_AB + colour_weight * C_AB.
+ * Iteration: pmx_shape_overlay's, on F: follow only when F > 0 at the start (otherwise reason 0, the input's bits); accept when F' > F;
+ * stop with reason 1 when F' - F <= ftol * F. With colour_weight = 0 every decision and every bit of the motion is pmx_shape_overlay's.
+ * colour_weight is finite and >= 0; it is uncalibrated - the Python layer's default only balances the two self-overlaps.
+ * Outputs, per row:
+ *   rot_out_dev, trans_out_dev   double [n][9], [n][3]: the last accepted motion
+ *   energy_dev   double [n][16]  O_AB at the start, O_AB final, O_AA, O_BB, the shape Tanimoto at the start and final; C_AB at the start, C_AB
+ *                                final, C_AA (pmx_pose_colour's, of the nodes posed at the input motion), C_BB, the colour Tanimoto at the
+ *                                start and final (0 where C_AB == 0); combo at the start and final, the sum of the two Tanimotos, between
+ *                                0 and 2; the net rotation angle from the start in rad; |c_final - c_start|
+ *   count_dev    int32 [n][6]    iterations, accepted steps, stop reason, shape points, nodes, f
+ *   status_dev   int32 [n]
+ * A row that is not OK has NaN motions and energies, counts of 0 and a stop reason of -1.
+ * Cross-checks, bit for bit: energy[6] and energy[8] are pmx_pose_colour's summary[0] and summary[1] at the input motion, energy[7] its
+ * summary[0] at rot_out / trans_out; energy[0], [1] and [2] are pmx_pose_shape's as for pmx_shape_overlay; F final is never below F at
+ * the start.
+ * Both calls: n <= PMX_EXPLAIN_MAX (otherwise PMX_ERR_INVALID); n = 0 succeeds and writes nothing; with n > 0 no output may be NULL. cover is
+ * finite and >= 0; ftol and max_iter as pmx_shape_overlay's. Stream-ordered (enqueued, no synchronisation), no allocation, no work buffer,
+ * no atomic: the same bits on every run, and for a row wherever it stands in a call. One wavefront per row.
+ */
+typedef struct pmx_colour_ref pmx_colour_ref;
+int pmx_colour_ref_create(const float *xyz /* [f][3] */, const uint8_t *typemask /* [f] */, uint32_t f, const float weights[PMX_NUM_TYPES], float radius, int device,
+                          pmx_colour_ref **out);
+int pmx_colour_ref_self(const pmx_colour_ref *ref, double *self_out);
+int pmx_colour_ref_destroy(pmx_colour_ref *ref);
+int pmx_pose_colour(const pmx_colour_ref *ref, const pmx_library *lib /* NULL in feature mode */, const uint64_t *ligands_dev, const int32_t *conformer_dev /* node mode: [n] each */,
+                    const uint64_t *feat_off_dev /* [n + 1] */, const float *feat_xyz_dev /* [.][3] */, const uint8_t *feat_mask_dev /* [.] */,
+                    const double *rot_dev /* [n][9] */, const double *trans_dev /* [n][3] */, uint32_t n, float cover, double *summary_dev /* [n][8] */,
+                    double *type_overlap_dev /* [n][PMX_NUM_TYPES] */, int32_t *count_dev /* [n][4] */, double *node_colour_dev /* [n][64] */, double *node_near_dev /* [n][64] */,
+                    int32_t *node_feature_dev /* [n][64] */, double *feat_near_dev /* [n][64] */, int32_t *feat_node_dev /* [n][64] */,
+                    uint64_t *matched_fp_dev /* [n][PMX_FINGERPRINT_WORDS] */, int32_t *status_dev, void *stream);
+int pmx_combo_overlay(const pmx_shape_ref *shape, const pmx_colour_ref *colour, const pmx_library *lib, const uint64_t *ligands_dev, const int32_t *conformer_dev,
+                      const uint64_t *point_off_dev /* NULL: the nodes are the shape points */, const float *points_dev, const float *point_radius_dev, const double *rot_dev,
+                      const double *trans_dev, uint32_t n, float point_radius, double colour_weight, double ftol, int max_iter, double *rot_out_dev /* [n][9] */,
+                      double *trans_out_dev /* [n][3] */, double *energy_dev /* [n][16] */, int32_t *count_dev /* [n][6] */, int32_t *status_dev, void *stream);
+
+/*
  * Retrospective validation (pmx_enrich.hip): does a model, under given type weights, rank known binders above decoys? Per column of scores
  * over one labelled list, and per bootstrap resample of the list, the integers and sums from which the host derives AUROC, enrichment
  * factors and BEDROC. The specification is this comment (the reference has no counterpart); tests/enrichment_ref.py restates it in NumPy.

@@ -300,6 +300,19 @@ SIGNATURES = {
         [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, *([ctypes.c_void_p] * 4),
          ctypes.c_void_p],
     ),
+    "pmx_colour_ref_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "pmx_colour_ref_self": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    "pmx_colour_ref_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "pmx_pose_colour": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+         ctypes.c_float, *([ctypes.c_void_p] * 10), ctypes.c_void_p],
+    ),
+    "pmx_combo_overlay": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_uint32, ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_int, *([ctypes.c_void_p] * 5), ctypes.c_void_p],
+    ),
     "pmx_score_stats_get": (ctypes.c_int, [ctypes.POINTER(ScoreStats)]),
     "pmx_set_profiling": (ctypes.c_int, [ctypes.c_int]),
 }

@@ -16,7 +16,7 @@ REPO = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libpmx.so"
 PACK_LIB = PKG / "libpmx_pack.so"  # the host-only units alone (no HIP / RCCL runtime)
-SOURCES = ("pmx_api.hip", "pmx_screen_debug.hip", "pmx_explain.hip", "pmx_rows.hip", "pmx_fingerprint.hip", "pmx_ligand_fp.hip", "pmx_pocket.hip", "pmx_refine.hip", "pmx_pose_search.hip", "pmx_pose_fit.hip", "pmx_pose_shape.hip", "pmx_shape_overlay.hip", "pmx_atoms.hip", "pmx_topk.hip", "pmx_density.hip", "pmx_pack_device.hip", "pmx_select.hip", "pmx_enrich.hip", "pmx_pack.cpp", "pmx_sdf.cpp", "pmx_perceive.cpp", "pmx_model_tables.cpp", "pmx_error.cpp")
+SOURCES = ("pmx_api.hip", "pmx_screen_debug.hip", "pmx_explain.hip", "pmx_rows.hip", "pmx_fingerprint.hip", "pmx_ligand_fp.hip", "pmx_pocket.hip", "pmx_refine.hip", "pmx_pose_search.hip", "pmx_pose_fit.hip", "pmx_pose_shape.hip", "pmx_shape_overlay.hip", "pmx_colour.hip", "pmx_atoms.hip", "pmx_topk.hip", "pmx_density.hip", "pmx_pack_device.hip", "pmx_select.hip", "pmx_enrich.hip", "pmx_pack.cpp", "pmx_sdf.cpp", "pmx_perceive.cpp", "pmx_model_tables.cpp", "pmx_error.cpp")
 # the host-only units: libpmx_pack.so is these alone (the packer, the readers, the model tables and the error hook)
 HOST_SOURCES = tuple(s for s in SOURCES if s.endswith(".cpp"))
 # every file under csrc/ that a unit of SOURCES #includes, directly or not (tests/test_cabi.py checks the closure): with SOURCES, what the

@@ -134,12 +134,14 @@ __device__ __forceinline__ double wave_sum(double x) {
 }
 
 // Host: the checks the pose calls share - one source of points, the row count, the library's device - and the source itself. `fn` names
-// the caller in the message, `owner` what the rows are judged against (the pocket, the reference) and `device` where that lives.
+// the caller in the message, `owner` what the rows are judged against (the pocket, the reference) and `device` where that lives. `both`:
+// the call also takes a library and points together (pmx_combo_overlay: the record's nodes carry the types, the points the shape) - the
+// source then holds the two, and a copy of it with `points` null is the node-mode source of the same rows.
 inline int pose_source(const char *fn, const char *owner, int device, const pmx_library *lib, const uint64_t *ligands_dev, const int32_t *conformer_dev,
                        const uint64_t *point_off_dev, const float *points_dev, const float *point_radius_dev, const double *rot_dev, const double *trans_dev, uint32_t n,
-                       PoseSource *out) {
+                       PoseSource *out, bool both = false) {
     const bool nodes = lib != nullptr, points = points_dev != nullptr || point_off_dev != nullptr || point_radius_dev != nullptr;
-    if (nodes == points) return pmx_fail(PMX_ERR_INVALID, "%s: %s", fn, nodes ? "a library and points: one source of points per call" : "neither a library nor points");
+    if (nodes == points && !(both && nodes)) return pmx_fail(PMX_ERR_INVALID, "%s: %s", fn, nodes ? "a library and points: one source of points per call" : "neither a library nor points");
     if (n > PMX_EXPLAIN_MAX) return pmx_fail(PMX_ERR_INVALID, "%s: %u rows, at most %d", fn, n, PMX_EXPLAIN_MAX);
     *out = PoseSource{};
     if (nodes) {
@@ -150,6 +152,7 @@ inline int pose_source(const char *fn, const char *owner, int device, const pmx_
     }
     if (n == 0) return PMX_OK;
     if (nodes ? (!ligands_dev || !conformer_dev) : (!point_off_dev || !points_dev)) return pmx_fail(PMX_ERR_INVALID, "%s: null %s", fn, nodes ? "ligands_dev or conformer_dev" : "point_off_dev or points_dev");
+    if (nodes && points && (!point_off_dev || !points_dev)) return pmx_fail(PMX_ERR_INVALID, "%s: null point_off_dev or points_dev", fn);
     if (!rot_dev || !trans_dev) return pmx_fail(PMX_ERR_INVALID, "%s: null rot_dev or trans_dev", fn);
     out->ligands = ligands_dev;
     out->conformer = conformer_dev;

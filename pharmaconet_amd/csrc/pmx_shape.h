@@ -8,6 +8,8 @@
 #include <cstdint>
 
 #include "pmx.h"
+#include "pmx_lm.h"   // hidx
+#include "pmx_pose.h" // the posed point and the butterfly
 
 struct pmx_shape_ref {
     int device = 0;
@@ -43,6 +45,111 @@ __device__ __forceinline__ double pair_term(double d2, double aa, double ab, dou
     const double q = kShapePi / s;
     k = (aa * ab) / s;
     return (8.0 * (q * __builtin_sqrt(q))) * exp(-(k * d2));
+}
+
+// ---- the evaluation pmx_shape_overlay and pmx_combo_overlay (pmx_colour.hip) iterate on: one definition, so that the two have the same bits
+struct ShapeEval {
+    double oab;
+    double c[3];
+    double H[21], g[6];
+};
+
+// O_AB, c, H and g at (R, t). X: the row's unposed points with their alphas; Lref: the reference.
+__device__ __forceinline__ void shape_evaluate(const double4 *X, uint32_t npts, const double4 *Lref, uint32_t m, const double (&R)[9], const double (&t)[3], int lane, ShapeEval &e) {
+    // ---- the centroid of the posed points
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (uint32_t base = 0; base < npts; base += 64) {
+        const uint32_t u = base + (uint32_t)lane;
+        if (u < npts) {
+            const double4 x = X[u];
+            double p0, p1, p2;
+            pose_point(R, t, x.x, x.y, x.z, p0, p1, p2);
+            s0 += p0;
+            s1 += p1;
+            s2 += p2;
+        }
+    }
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    const double c0 = npts ? s0 / (double)npts : 0.0, c1 = npts ? s1 / (double)npts : 0.0, c2 = npts ? s2 / (double)npts : 0.0;
+    e.c[0] = c0;
+    e.c[1] = c1;
+    e.c[2] = c2;
+
+    // ---- pairs, and each point's block. (H(0,3), H(1,4), H(2,5), H(3,4), H(3,5) and H(4,5) are 0 by structure)
+    double sAB = 0.0;
+    double h00 = 0.0, h01 = 0.0, h02 = 0.0, h11 = 0.0, h12 = 0.0, h22 = 0.0, h04 = 0.0, h05 = 0.0, h13 = 0.0, h15 = 0.0, h23 = 0.0, h24 = 0.0, hw = 0.0;
+    double g0 = 0.0, g1 = 0.0, g2 = 0.0, g3 = 0.0, g4 = 0.0, g5 = 0.0;
+    for (uint32_t base = 0; base < npts; base += 64) {
+        const uint32_t u = base + (uint32_t)lane;
+        if (u < npts) {
+            const double4 x = X[u];
+            double4 p;
+            pose_point(R, t, x.x, x.y, x.z, p.x, p.y, p.z);
+            p.w = x.w;
+            double cross = 0.0, f0 = 0.0, f1 = 0.0, f2 = 0.0, w = 0.0;
+            for (uint32_t b = 0; b < m; ++b) {
+                const double4 y = Lref[b];
+                const double e0 = p.x - y.x, e1 = p.y - y.y, e2 = p.z - y.z;
+                const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+                double k;
+                const double V = pair_term(d2, p.w, y.w, k);
+                const double kappa = (2.0 * k) * V;
+                cross = cross + V;
+                f0 = f0 + kappa * e0;
+                f1 = f1 + kappa * e1;
+                f2 = f2 + kappa * e2;
+                w = w + kappa;
+            }
+            sAB = sAB + cross;
+            const double r0 = p.x - c0, r1 = p.y - c1, r2 = p.z - c2;
+            const double rr = (r0 * r0 + r1 * r1) + r2 * r2;
+            h00 += w * (rr - r0 * r0);
+            h01 += w * -(r0 * r1);
+            h02 += w * -(r0 * r2);
+            h11 += w * (rr - r1 * r1);
+            h12 += w * -(r1 * r2);
+            h22 += w * (rr - r2 * r2);
+            h04 += w * -r2;
+            h05 += w * r1;
+            h13 += w * r2;
+            h15 += w * -r0;
+            h23 += w * -r1;
+            h24 += w * r0;
+            hw += w;
+            g0 += r1 * f2 - r2 * f1;
+            g1 += r2 * f0 - r0 * f2;
+            g2 += r0 * f1 - r1 * f0;
+            g3 += f0;
+            g4 += f1;
+            g5 += f2;
+        }
+    }
+
+    // ---- the row
+    e.oab = wave_sum(sAB);
+#pragma unroll
+    for (int k = 0; k < 21; ++k) e.H[k] = 0.0;
+    e.H[hidx(0, 0)] = wave_sum(h00);
+    e.H[hidx(0, 1)] = wave_sum(h01);
+    e.H[hidx(0, 2)] = wave_sum(h02);
+    e.H[hidx(1, 1)] = wave_sum(h11);
+    e.H[hidx(1, 2)] = wave_sum(h12);
+    e.H[hidx(2, 2)] = wave_sum(h22);
+    e.H[hidx(0, 4)] = wave_sum(h04);
+    e.H[hidx(0, 5)] = wave_sum(h05);
+    e.H[hidx(1, 3)] = wave_sum(h13);
+    e.H[hidx(1, 5)] = wave_sum(h15);
+    e.H[hidx(2, 3)] = wave_sum(h23);
+    e.H[hidx(2, 4)] = wave_sum(h24);
+    e.H[hidx(3, 3)] = e.H[hidx(4, 4)] = e.H[hidx(5, 5)] = wave_sum(hw);
+    e.g[0] = wave_sum(g0);
+    e.g[1] = wave_sum(g1);
+    e.g[2] = wave_sum(g2);
+    e.g[3] = wave_sum(g3);
+    e.g[4] = wave_sum(g4);
+    e.g[5] = wave_sum(g5);
 }
 
 } // namespace pmx

@@ -21,14 +21,14 @@ from .atoms import PackedAtoms  # noqa: F401
 from .constants import weights_vector  # noqa: F401
 from .library import PackedLibrary, as_packed_library  # noqa: F401
 # the posed-hit layer (poses.py); every name of it stays importable from here
-from .poses import (Alignment, ClashReport, PoseFit, RefinedPoses, ShapeOverlay, ShapeReport, ShapeStarts, _atomic_numbers, _fingerprint_tensor,  # noqa: F401
+from .poses import (Alignment, ClashReport, ColourReport, ComboOverlay, PoseFit, RefinedPoses, ShapeOverlay, ShapeReport, ShapeStarts, _atomic_numbers, _fingerprint_tensor,  # noqa: F401
                     _heavy_atoms, _PocketHandle, _pose_source, _PoseRows, _ragged, _ratio, _ShapeRefHandle, clashes, device_pocket,
-                    device_shape_ref, fingerprint_leaders, fingerprint_similarity, overlay, overlay_starts, pose_fit, refine, shape)
+                    balanced_colour_weight, colour, colour_of, combo_overlay, combo_overlay_of, device_colour_ref, device_shape_ref, fingerprint_leaders, fingerprint_similarity, overlay, overlay_starts, pose_fit, refine, shape)
 from .validation import ENRICH_TILE, FLOAT64_REFUSED, MAX_BOOTSTRAP, MAX_COLUMNS, POISSON1_CDF64, Enrichment, cutoffs_ppm  # noqa: F401  (the table and the tile of include/pmx.h)
 
 __all__ = ["Alignment", "Attribution", "ClashReport", "DeviceAtoms", "DeviceLibrary", "FittingHits", "Enrichment", "Explanation", "LigandFingerprints", "PanelResult", "PoseFit", "ScreeningResult", "SimilarityResult", "align", "attribute", "clashes",
            "enrichment", "explain", "score_one", "screen", "screen_multi", "similar", "sweep", "topk", "device_model", "last_score_stats", "pose_fit", "ShapeReport", "shape",
-           "device_shape_ref"]
+           "device_shape_ref", "ColourReport", "ComboOverlay", "colour", "colour_of", "combo_overlay", "combo_overlay_of", "device_colour_ref"]
 
 
 FEATURE_FIELDS = ("atom_off", "atomic_num", "nbr_off", "nbr", "feat_off", "feat_type", "feat_flags", "feat_atom_off", "feat_atoms",
@@ -190,6 +190,45 @@ class ScreeningResult:
         pick = np.array([lo + int(np.argmax(value[lo: lo + c])) for lo, c in zip(first, n_conf)], dtype=np.int64)  # (the first among equals)
         return ShapeOverlay(**{f.name: (None if getattr(every, f.name) is None else getattr(every, f.name)[pick]) for f in dataclasses.fields(every)})
 
+    def combo_overlay(self, k: int, reference, atoms=None, starts: int = 4, conformers: str = "best", model=None, library=None, weights: dict[str, float] | None = None,
+                      **kw) -> "ComboOverlay":
+        """`combo_overlay` of this screen's k best ligands (best first) on a known ligand that carries its typed features
+        (`ReferenceLigand.from_library`, or `colour=` a `shape.ColourFeatures`): shape plus colour, the "TanimotoCombo" of ligand-based
+        screening, of a screen's top hits. The typed points are the hits' pharmacophore nodes; the shape points are those nodes, or the
+        heavy atoms with `atoms` (the library's atom store). `conformers` and `starts` as `overlay` has them, `conformers="all"` keeping
+        per hit the conformer of highest final combo, the lower among equals. Further arguments (`colour_weight`, `node_radius`, `ftol`,
+        `max_iter`) as `combo_overlay` takes them."""
+        what = "ScreeningResult.combo_overlay"
+        model, library, weights = self._scored(model, library, weights)
+        if conformers not in ("best", "all"):
+            raise ValueError(f"{what}: conformers is 'best' or 'all'")
+        if starts not in (0, 4):
+            raise ValueError(f"{what}: starts is 0 or 4")
+        if atoms is not None and not _is_store(atoms):
+            raise TypeError(f"{what}: atoms is the library's DeviceAtoms / PackedAtoms")
+        if conformers == "best":
+            if k * max(starts, 1) > _ffi.EXPLAIN_MAX:
+                raise ValueError(f"{what}: {k} hits x {max(starts, 1)} starts exceed {_ffi.EXPLAIN_MAX} rows")
+            al = explain(model, library, self._best(k), weights=weights).poses(model, library, weights=weights)
+            if starts == 0:
+                return combo_overlay_of(al, reference, library, atoms=atoms, **kw)
+            return combo_overlay(reference, library, al.indices, al.conformers, atoms=atoms, starts=starts, **kw)
+        if starts == 0:
+            raise ValueError(f"{what}: conformers='all' has a fitted pose for one conformer only; use starts=4")
+        hits = self._best(k).astype(np.int64)
+        with _resident(library) as dlib:
+            n_conf = np.maximum(_record_counts(dlib, hits, 1), 1)
+        rows = int(n_conf.sum()) * starts
+        if rows > _ffi.EXPLAIN_MAX:
+            raise ValueError(f"{what}: {len(hits)} hits x their conformers x {starts} starts are {rows} rows, more than {_ffi.EXPLAIN_MAX}; lower k or use conformers='best'")
+        idx, conf = np.repeat(hits, n_conf), np.concatenate([np.arange(c) for c in n_conf]) if len(hits) else np.zeros(0, np.int64)
+        every = combo_overlay(reference, library, idx, conf, atoms=atoms, starts=starts, **kw)
+        first = np.concatenate([[0], np.cumsum(n_conf)[:-1]]).astype(np.int64) if len(hits) else np.zeros(0, np.int64)
+        value = np.where(np.isnan(every.combo), -np.inf, every.combo)
+        pick = np.array([lo + int(np.argmax(value[lo: lo + c])) for lo, c in zip(first, n_conf)], dtype=np.int64)  # (the first among equals)
+        take = lambda v: v[pick] if isinstance(v, np.ndarray) else v  # noqa: E731  (colour_weight is one number)
+        return ComboOverlay(**{f.name: take(getattr(every, f.name)) for f in dataclasses.fields(every)})
+
 
     def diverse(self, k: int, pool: int | None = None, threshold: float = 0.7, model=None, library=None, weights: dict[str, float] | None = None) -> "DiverseHits":
         """The k first hits of this screen that are not the same binding mode again: the best `pool` hits (default
@@ -238,7 +277,7 @@ class ScreeningResult:
                            pool=idx.astype(np.uint64), profile=None)
 
     def fitting(self, k: int, pool: int | None = None, max_clashing: int = 0, pocket=None, atoms=None, model=None, library=None,
-                weights: dict[str, float] | None = None, refine: bool = False, search: int = 0, fit: bool = False, shape=None, **kw) -> "FittingHits":
+                weights: dict[str, float] | None = None, refine: bool = False, search: int = 0, fit: bool = False, shape=None, colour=None, **kw) -> "FittingHits":
         """The k first hits of this screen whose pose fits the pocket: the best `pool` hits (default min(len, max(8 k, 1024), 65536)) are
         explained, posed at their best conformer (`Explanation.poses`) and checked against the protein's atoms (`Alignment.clashes`); a hit
         passes with status 0 and at most `max_clashing` clashing points. In rank order; a hit that was not scored, or whose pose is not OK,
@@ -263,7 +302,12 @@ class ScreeningResult:
         the refined one where the refinement was used; nothing else changes.
         With `shape` - a `shape.ReferenceLigand`, the known binder - `FittingHits.shape` is the `ShapeReport` of every posed hit
         (`Alignment.shape`) at the motion finally used, on the points the clash check read (the molecules' atoms with `atoms`, the nodes
-        otherwise; `shape_cover` is its `cover`); nothing else changes."""
+        otherwise; `shape_cover` is its `cover`); nothing else changes.
+        With `colour` - a `shape.ColourFeatures`, or a `ReferenceLigand` that carries one - `FittingHits.colour` is the `ColourReport` of
+        every posed hit's nodes (`colour_of`) at the motion finally used (`colour_cover` is its `cover`); nothing else changes."""
+        colour_kw = {"cover": kw.pop("colour_cover")} if "colour_cover" in kw else {}
+        if colour_kw and colour is None:
+            raise ValueError("colour_cover: an argument of the colour report, which is off (colour=reference)")
         shape_kw = {"cover": kw.pop("shape_cover")} if "shape_cover" in kw else {}
         if shape_kw and shape is None:
             raise ValueError("shape_cover: an argument of the shape report, which is off (shape=reference)")
@@ -320,9 +364,10 @@ class ScreeningResult:
                 if "device" in kw:
                     shape_kw["device"] = kw["device"]
                 sh = al.shape(shape, dlib, atoms=mols, **shape_kw)
+            col = colour_of(al, colour, dlib, **colour_kw) if colour is not None else None
         passing = np.flatnonzero(rep.ok(max_clashing) & (al.status == 0))[:k]
         return FittingHits(indices=al.indices[passing].astype(np.uint64), scores=ex.scores[al.rows[passing]], ranks=al.rows[passing].astype(np.int64), rows=passing,
-                           pool=ex.indices, poses=al, report=rep, refined=refined, fit=pf, shape=sh)
+                           pool=ex.indices, poses=al, report=rep, refined=refined, fit=pf, shape=sh, colour=col)
 
     def similar_to(self, rank: int, k: int = 100, library=None) -> "SimilarityResult":
         """The library's neighbours of this screen's hit at `rank` (0 is the best hit): `similar` with that ligand as the one query,
@@ -1436,6 +1481,7 @@ class FittingHits:
     refined: "RefinedPoses | None" = None  # `fitting(refine=True)`: the refinement of every posed hit; its motion is used where the fit failed
     fit: "PoseFit | None" = None  # `fitting(fit=True)`: the `PoseFit` (free mode) of every posed hit at the motion finally used
     shape: "ShapeReport | None" = None  # `fitting(shape=reference)`: the `ShapeReport` of every posed hit at the motion finally used
+    colour: "ColourReport | None" = None  # `fitting(colour=reference)`: the `ColourReport` of every posed hit's nodes at that motion
 
     def __len__(self) -> int:
         return len(self.indices)

@@ -624,6 +624,25 @@ class PharmacophoreModel:
             raise ValueError(f"{sorted(kw)}: arguments of the refinement, which is off (refine=True)")
         return out
 
+    def scoring_colour(self, ligand, reference, conformer: int | None = None, key=None, weights: dict[str, float] | None = None, cover: float = 2.0) -> dict:
+        """One ligand fitted into the pocket (`scoring_pose`) and its pharmacophore nodes compared with a known ligand's typed features
+        (`engine.colour`; `reference` a `shape.ColourFeatures`, or a `ReferenceLigand` that carries one, in the pocket's frame), the
+        one-ligand form beside `scoring_shape`. Returns `conformer`, `key`, `rotation`, `translation`, `rmsd` of the pose, and `overlap`,
+        `self_overlap`, `reference_overlap`, `tanimoto`, `reference_fraction`, `fit_fraction`, `rms_matched`, `by_type` (a dict keyed by type
+        name), `n_nodes`, `n_matched`, `n_reference_features`, `n_reference_matched`, `node_overlap`, `node_distance`, `node_feature`,
+        `feature_distance`, `feature_node`, `matched_fingerprint` and `status`. Points and types only: no directions."""
+        from .engine import colour
+        from .library import as_packed_library
+
+        pose = self.scoring_pose(ligand, weights=weights, conformer=conformer, key=key)
+        c = pose["conformer"]
+        rep = colour(reference, as_packed_library(ligand), [0], [c], [pose["rotation"]], [pose["translation"]], cover=cover)
+        scalars = ("overlap", "self_overlap", "reference_overlap", "tanimoto", "reference_fraction", "fit_fraction", "rms_matched")
+        counts = ("n_nodes", "n_matched", "n_reference_features", "n_reference_matched", "status")
+        lists = ("node_overlap", "node_distance", "node_feature", "feature_distance", "feature_node", "matched_fingerprint")
+        return dict(conformer=c, key=pose["key"], rotation=pose["rotation"], translation=pose["translation"], rmsd=pose["rmsd"], by_type=rep.by_type(0),
+                    **{f: float(getattr(rep, f)[0]) for f in scalars}, **{f: int(getattr(rep, f)[0]) for f in counts}, **{f: getattr(rep, f)[0] for f in lists})
+
     def scoring_overlay(self, ligand, reference, starts: int = 4, level: str = "atoms", weights: dict[str, float] | None = None, **kw) -> dict:
         """One ligand overlaid on a known ligand (`engine.overlay`; `reference` a `shape.ReferenceLigand` in the pocket's frame), the
         one-ligand form beside `scoring_shape`. With `starts=4` every conformer is run from the four inertial starts - no pharmacophore fit

@@ -1,5 +1,5 @@
 """The posed-hit layer: rows of points under a rigid motion, judged against the pocket (`clashes`, `refine`), a known ligand (`shape`,
-`overlay`) or the model's hotspots (`pose_fit`). `engine.py` re-exports every name of this module."""
+`overlay`, and with its typed features `colour`, `combo_overlay`) or the model's hotspots (`pose_fit`). `engine.py` re-exports every name of this module."""
 
 from __future__ import annotations
 
@@ -909,3 +909,318 @@ def pose_fit(model, library, indices, conformers, rotation, translation, keys=No
                    n_in_place=cn[:, 2].copy(), n_passing=cn[:, 3].copy(), node_fit=cut(nfit, nn), node_best=cut(nbest, nn), node_z2=cut(nz2, nn),
                    node_target=cut(ntgt, nn, np.int64), hotspot_z2=cut(hz2, wm), hotspot_node=cut(hnode, wm, np.int64),
                    occupied_fingerprint=f.host(fp).view(np.uint64).copy(), status=st, device=dev)
+
+
+# ---------------------------------------------------------------------------------------------------------------- colour: the typed term
+@dataclass
+class ColourReport:
+    """What `colour` returns: one row per posed set of typed points against a known ligand's pharmacophore features (definitions:
+    `pmx_pose_colour` in include/pmx.h). Floats are float64. Points and types only - no donor / acceptor direction, no ring normal - and
+    first-order overlaps, as the shape term's.
+
+    overlap[i], self_overlap[i], reference_overlap[i]   C_AB, C_AA, C_BB: the weighted Gaussian overlap of the pairs that share a type
+    tanimoto[i]     C_AB / (C_AA + C_BB - C_AB), 0 where C_AB is 0: exactly 1 for the reference's own features in place
+    reference_fraction[i], fit_fraction[i]   C_AB / C_BB and C_AB / C_AA (0 where the denominator is 0)
+    rms_matched[i]  the root mean square, over the nodes that have a partner of a shared weighted type, of the distance to the nearest
+                    such feature (NaN where no node has one)
+    type_overlap    [n, 7]: the part of C_AB each type carries, in `constants.TYPE_NAMES` order (`by_type(i)` names them); they add up to
+                    `overlap` only up to rounding
+    n_nodes[i], n_matched[i], n_reference_features[i], n_reference_matched[i]   typed points; those with a typed partner nearer than
+                    `cover`; the reference's features; those of them with a typed partner nearer than `cover`
+    node_overlap[i], node_distance[i], node_feature[i]   per node its part of C_AB, the distance to its nearest typed partner (NaN
+                    without one) and that feature (-1 without one)
+    feature_distance[i], feature_node[i]   the mirror image, per reference feature
+    matched_fingerprint   uint64 [n, 4]: bit b says reference feature b is reproduced (counted in n_reference_matched); `similarity` and
+                    `leaders` cluster hits by which of the binder's interactions they reproduce
+    status[i]       0, 1 (PMX_LIGAND_UNSUPPORTED: also a row of more than 64 typed points) or 4 (PMX_LIGAND_KEY_INVALID: not a conformer,
+                    a motion that is not finite, a mask >= 128); such a row has NaN, zero counts, -1 and an empty fingerprint"""
+
+    overlap: np.ndarray
+    self_overlap: np.ndarray
+    reference_overlap: np.ndarray
+    tanimoto: np.ndarray
+    reference_fraction: np.ndarray
+    fit_fraction: np.ndarray
+    rms_matched: np.ndarray
+    type_overlap: np.ndarray
+    n_nodes: np.ndarray
+    n_matched: np.ndarray
+    n_reference_features: np.ndarray
+    n_reference_matched: np.ndarray
+    node_overlap: list
+    node_distance: list
+    node_feature: list
+    feature_distance: list
+    feature_node: list
+    matched_fingerprint: np.ndarray
+    status: np.ndarray
+    device: "int | None" = None  # where `similarity` and `leaders` run
+
+    def __len__(self) -> int:
+        return len(self.status)
+
+    def by_type(self, i: int) -> dict:
+        """Row i's `type_overlap`, keyed by type name."""
+        from .constants import TYPE_NAMES
+
+        return {name: float(self.type_overlap[i, t]) for t, name in enumerate(TYPE_NAMES)}
+
+    def similarity(self, other: "ColourReport | None" = None) -> np.ndarray:
+        """Tanimoto similarity of the matched fingerprints, on the GPU (`fingerprint_similarity`)."""
+        return fingerprint_similarity(self.matched_fingerprint, None if other is None else other.matched_fingerprint, device=self.device)
+
+    def leaders(self, threshold: float = 0.7, max_leaders: int = 2048):
+        """Sphere exclusion over the rows in their order by matched fingerprint (`fingerprint_leaders`): (leaders, leader_of)."""
+        return fingerprint_leaders(self.matched_fingerprint, threshold=threshold, max_leaders=max_leaders, device=self.device)
+
+
+class _ColourRefHandle(_DeviceHandle):
+    _destroy = "pmx_colour_ref_destroy"
+
+    def __init__(self, colour, device: int):
+        handle = ctypes.c_void_p()
+        xyz, mask = np.ascontiguousarray(colour.xyz, dtype=np.float32), np.ascontiguousarray(colour.typemask, dtype=np.uint8)
+        w = (ctypes.c_float * 7)(*[float(v) for v in colour.weights_array()])
+        _ffi.check(_ffi.load().pmx_colour_ref_create(xyz.ctypes.data, mask.ctypes.data, len(mask), w, float(colour.radius), device, ctypes.byref(handle)))
+        super().__init__(handle, device)
+        self.f = len(mask)
+
+    @property
+    def self_overlap(self) -> float:
+        out = ctypes.c_double()
+        _ffi.check(_ffi.load().pmx_colour_ref_self(self.handle, ctypes.byref(out)))
+        return out.value
+
+
+def _colour_of(reference, what: str):
+    """The `shape.ColourFeatures` of `reference`: itself, or the `colour` a `shape.ReferenceLigand` carries."""
+    from .shape import ColourFeatures
+
+    if isinstance(reference, ColourFeatures):
+        return reference
+    colour = getattr(reference, "colour", None)
+    if colour is None:
+        raise ValueError(f"{what}: the reference has no typed features - a shape.ColourFeatures, or a ReferenceLigand with `colour`")
+    return colour
+
+
+def device_colour_ref(reference, device=None) -> _ColourRefHandle:
+    """The device copy of a `shape.ColourFeatures` (or of a `ReferenceLigand`'s `colour`), made once per (features, device) and freed with
+    the object."""
+    colour = _colour_of(reference, "device_colour_ref")
+    return _cached_handle(colour._device, _device_index(device), lambda dev: _ColourRefHandle(colour, dev))
+
+
+def colour(reference, library=None, indices=None, conformers=None, rotation=None, translation=None, features=None, feature_types=None, cover: float = 2.0,
+           device=None) -> ColourReport:
+    """Posed rows against a known ligand's typed features (`pmx_pose_colour`, csrc/pmx_colour.hip): row i is a set of typed points moved by
+    `rotation[i]` and `translation[i]`, `reference` a `shape.ColourFeatures` (or a `ReferenceLigand` that carries one). A pair of a point
+    and a feature counts when the two share a type of weight > 0, by the sum of those weights times the Gaussian overlap of two spheres
+    of the features' radius. The pose is judged where it is: nothing is moved.
+      node mode     `library`, `indices`, `conformers`: the pharmacophore nodes of library ligand indices[i] at conformer conformers[i] with
+                    the record's type masks
+      feature mode  `features`: a list of [k_i, 3] arrays, typed points of the caller's; `feature_types`: a matching list of type names,
+                    ids, or uint8 masks (`shape.type_masks`). A row holds at most 64 (more: status 1); a mask above 127 gives its row status 4
+    Exactly one of the two. At most 65536 rows. Runs on torch's current stream of the device and waits for it."""
+    from .shape import type_masks
+
+    _torch()
+    ref = _colour_of(reference, "colour")
+    if (features is None) != (feature_types is None):
+        raise ValueError("colour: features and feature_types go together")
+    rows = _PoseRows("colour", library, indices, conformers, rotation, translation, features, None)
+    masks = None
+    if features is not None:
+        if len(feature_types) != rows.n:
+            raise ValueError(f"{len(feature_types)} lists of types for {rows.n} feature sets")
+        each = [type_masks(v, check=False) for v in feature_types]  # (a mask above 127 is the row's status, not an error)
+        if any(len(m) != len(np.asarray(p).reshape(-1, 3)) for m, p in zip(each, features)):
+            raise ValueError("a list of types differs in length from its features")
+        masks = np.ascontiguousarray(np.concatenate(each + [np.zeros(1, np.uint8)]))  # (never an empty buffer)
+    if not (np.isfinite(cover) and cover >= 0):
+        raise ValueError("cover must be finite and not negative")
+    with _pose_frame(rows, library, None, device, device_colour_ref, ref) as f:
+        summary, types, count, fp = f.f64(f.m, 8), f.f64(f.m, 7), f.i32(f.m, 4), f.i64(f.m, _FP_WORDS)
+        ncol, nnear, nfeat, fnear, fnode = f.f64(f.m, _MAX_NODES), f.f64(f.m, _MAX_NODES), f.i32(f.m, _MAX_NODES), f.f64(f.m, _MAX_NODES), f.i32(f.m, _MAX_NODES)
+        t_mask = f.up(masks).data_ptr() if masks is not None else None
+        _ffi.check(f.lib.pmx_pose_colour(f.owner.handle, f.library, *f.src[:4], t_mask, *f.motion, f.n, float(cover), summary.data_ptr(), types.data_ptr(), count.data_ptr(),
+                                         ncol.data_ptr(), nnear.data_ptr(), nfeat.data_ptr(), fnear.data_ptr(), fnode.data_ptr(), fp.data_ptr(), f.status.data_ptr(), f.stream))
+    n, st, nf = f.n, f.st, f.owner.f
+    sm, cn = f.host(summary), f.host(count).astype(np.int64)
+    nn = np.where(st == 0, cn[:, 0], 0)
+    cut = lambda t, k, dtype=None: [(r[: k[i]] if np.ndim(k) else r[:k]).astype(dtype or r.dtype).copy() for i, r in enumerate(f.host(t))]  # noqa: E731
+    return ColourReport(overlap=sm[:, 0].copy(), self_overlap=sm[:, 1].copy(), reference_overlap=sm[:, 2].copy(), tanimoto=sm[:, 3].copy(), reference_fraction=sm[:, 4].copy(),
+                        fit_fraction=sm[:, 5].copy(), rms_matched=sm[:, 6].copy(), type_overlap=f.host(types).copy(), n_nodes=cn[:, 0].copy(), n_matched=cn[:, 1].copy(),
+                        n_reference_matched=cn[:, 2].copy(), n_reference_features=cn[:, 3].copy(), node_overlap=cut(ncol, nn), node_distance=cut(nnear, nn),
+                        node_feature=cut(nfeat, nn, np.int64), feature_distance=cut(fnear, nf), feature_node=cut(fnode, nf, np.int64),
+                        matched_fingerprint=f.host(fp).view(np.uint64).copy(), status=st, device=f.dev)
+
+
+@dataclass
+class ComboOverlay(ShapeOverlay):
+    """What `combo_overlay` returns: a `ShapeOverlay` - every field of it as there, the motion now the one that maximises shape and colour
+    together, F = O_AB + colour_weight * C_AB (definitions: `pmx_combo_overlay` in include/pmx.h) - with the colour and combo fields. Rigid
+    only, no directions and no hydrogens, first-order overlaps, a local maximum, and `colour_weight` is uncalibrated.
+
+    colour_overlap_start[i], colour_overlap[i]   C_AB at the start motion and at the overlaid one
+    colour_self_overlap[i], colour_reference_overlap[i]   C_AA and C_BB
+    colour_tanimoto_start[i], colour_tanimoto[i]   C_AB / (C_AA + C_BB - C_AB) before and after, 0 where C_AB is 0
+    combo_start[i], combo[i]   the sum of the shape and the colour Tanimoto, 0 to 2 ("TanimotoCombo"), before and after
+    n_nodes[i], n_reference_features[i]   the row's typed nodes and the reference's features
+    colour_weight   the weight the call ran with
+    start, start_tanimoto   with `starts=4`: the start kept is the one of highest final combo, and `start_tanimoto` holds every start's final combo"""
+
+    colour_overlap_start: "np.ndarray | None" = None
+    colour_overlap: "np.ndarray | None" = None
+    colour_self_overlap: "np.ndarray | None" = None
+    colour_reference_overlap: "np.ndarray | None" = None
+    colour_tanimoto_start: "np.ndarray | None" = None
+    colour_tanimoto: "np.ndarray | None" = None
+    combo_start: "np.ndarray | None" = None
+    combo: "np.ndarray | None" = None
+    n_nodes: "np.ndarray | None" = None
+    n_reference_features: "np.ndarray | None" = None
+    colour_weight: float = 0.0
+
+
+def balanced_colour_weight(reference, device=None) -> float:
+    """O_BB / C_BB of a `ReferenceLigand` that carries its `colour`: the weight at which the reference laid on itself gets equal amounts
+    from the shape and the colour term. A derived default, not a calibrated one; 0 for a reference whose C_BB is 0."""
+    o_bb, c_bb = device_shape_ref(reference, device).self_overlap, device_colour_ref(reference, device).self_overlap
+    return float(o_bb / c_bb) if c_bb > 0 else 0.0
+
+
+def combo_overlay(reference, library, indices, conformers, rotation=None, translation=None, atoms=None, colour_weight="balanced", starts: int = 0, node_radius: float = 1.0,
+                  ftol: float = 1e-6, max_iter: int = 32, device=None, colour=None, points=None, point_radii=None) -> ComboOverlay:
+    """Library rows overlaid on a known ligand by shape and colour together (`pmx_combo_overlay`, csrc/pmx_colour.hip): per row a bounded
+    Levenberg-Marquardt maximisation over the rigid motion of F = O_AB + colour_weight * C_AB. `reference` is a `shape.ReferenceLigand`
+    that carries its `colour` (`ReferenceLigand.from_library`), or one without and `colour` a `shape.ColourFeatures`. The colour points are
+    always the pharmacophore nodes of library ligand indices[i] at conformer conformers[i]; the shape points are those nodes as spheres of
+    `node_radius`, or with `atoms` (the library's atom store) the ligand's heavy atoms with Bondi radii, or `points` / `point_radii` of the
+    caller's, one set per row. Both move under the one motion.
+      colour_weight  "balanced": O_BB / C_BB of the two references (`balanced_colour_weight`) - derived, not calibrated: nobody has
+                     measured which weight ranks known binders best. A number: that weight, finite and >= 0; 0 is `overlay`
+      starts=0       each row is optimised from its given motion
+      starts=4       `rotation` / `translation` are ignored: each hit is run from the four inertial starts of its shape points
+                     (`pmx_shape_starts`) and the start of highest final combo is kept, the lower among equals. At most 16384 hits
+    Rigid only, no directions, no hydrogens, first-order overlaps, and a local maximum. At most 65536 rows. Runs on torch's current
+    stream of the device and waits for it."""
+    torch = _torch()
+    what = "combo_overlay"
+    if library is None:
+        raise ValueError(f"{what}: the library is required - the colour points are its records' nodes")
+    col = _colour_of(reference if colour is None else colour, what)
+    if starts not in (0, 4):
+        raise ValueError(f"{what}: starts is 0 (from the given motions) or 4 (the inertial starts)")
+    if not 0 <= int(max_iter) <= 64:
+        raise ValueError("max_iter: 0 to 64 (PMX_REFINE_MAX_ITER)")
+    if not (np.isfinite(ftol) and ftol >= 0):
+        raise ValueError("ftol must be finite and not negative")
+    if not np.isfinite(node_radius):
+        raise ValueError("node_radius must be finite")
+    if not isinstance(colour_weight, str) and not (np.isfinite(colour_weight) and colour_weight >= 0):
+        raise ValueError("colour_weight must be finite and not negative, or 'balanced'")
+    if isinstance(colour_weight, str) and colour_weight != "balanced":
+        raise ValueError("colour_weight: a number, or 'balanced'")
+    if atoms is not None and (points is not None or not _is_store(atoms)):
+        raise ValueError(f"{what}: atoms is the library's DeviceAtoms / PackedAtoms; points are the alternative to it")
+    if point_radii is not None and points is None:
+        raise ValueError(f"{what}: point_radii go with points")
+    k = max(starts, 1)
+    idx, conf = np.asarray(indices).reshape(-1), np.asarray(conformers).reshape(-1)
+    if starts:
+        hits = len(idx)
+        if hits > 16384:
+            raise ValueError(f"{what}: {hits} hits, at most 16384 with starts=4 (65536 rows)")
+        idx, conf = np.repeat(idx, k), np.repeat(conf, k)
+        points = None if points is None else [p for p in points for _ in range(k)]
+        point_radii = None if point_radii is None else [r for r in point_radii for _ in range(k)]
+        rotation, translation = np.zeros((hits * k, 3, 3)), np.zeros((hits * k, 3))
+    elif rotation is None or translation is None:
+        raise ValueError(f"{what}: starts=0 optimises the given motions - rotation and translation")
+    rows = _PoseRows(what, library, idx, conf, rotation, translation, None, None)
+    n = rows.n
+    p_off = p_flat = p_rad = None
+    if points is not None:
+        if len(points) != n:
+            raise ValueError(f"{len(points)} point sets for {n} rows")
+        p_off, p_flat, pts = _ragged(points, np.float32, 3)
+        if point_radii is not None:
+            if len(point_radii) != n:
+                raise ValueError(f"{len(point_radii)} radius lists for {n} point sets")
+            _, p_rad, rs = _ragged(point_radii, np.float32, None)
+            if any(len(r) != len(p) for r, p in zip(rs, pts)):
+                raise ValueError("a list of radii differs in length from its points")
+    gstatus = None
+    with contextlib.ExitStack() as stack:
+        dlib = stack.enter_context(_resident(library, device))
+        dat = stack.enter_context(_resident_atoms(atoms, dlib.device)) if atoms is not None else None
+        with _pose_frame(rows, dlib, None, device, device_shape_ref, reference) as f:
+            chandle = device_colour_ref(col, f.dev)
+            cw = (float(f.owner.self_overlap / chandle.self_overlap) if chandle.self_overlap > 0 else 0.0) if isinstance(colour_weight, str) else float(colour_weight)
+            rot, trans, energy, count, motion = f.f64(f.m, 3, 3), f.f64(f.m, 3), f.f64(f.m, 16), f.i32(f.m, 6), f.motion
+            triple = (None, None, None)
+            if dat is not None:
+                t_a, t_b = f.up(rows.idx if n else np.zeros(1, np.int64)), f.up(rows.conf if n else np.zeros(1, np.int32))
+                off, pts_dev, rad_dev, gstatus = dat.gather_device(t_a, t_b, n)
+                f.keep += [off, pts_dev, rad_dev, gstatus]
+                triple = (off.data_ptr(), pts_dev.data_ptr(), rad_dev.data_ptr())
+            elif p_off is not None:
+                triple = (f.up(p_off).data_ptr(), f.up(p_flat).data_ptr(), f.up(p_rad).data_ptr() if p_rad is not None else None)
+            if starts:
+                s_rot, s_trans, s_frame, s_status = f.f64(f.m, 9), f.f64(f.m, 3), f.f64(f.m, 16), f.i32(f.m)
+                which = torch.arange(f.m, dtype=torch.int32, device=f.tdev) % k
+                by_points = triple[0] is not None
+                _ffi.check(f.lib.pmx_shape_starts(f.owner.handle, None if by_points else f.library, *((None, None) if by_points else f.src[:2]), triple[0], triple[1],
+                                                  which.data_ptr(), f.n, s_rot.data_ptr(), s_trans.data_ptr(), s_frame.data_ptr(), s_status.data_ptr(), f.stream))
+                f.keep += [which, s_rot, s_trans, s_frame, s_status]
+                motion = (s_rot.data_ptr(), s_trans.data_ptr())
+            if gstatus is not None and n:  # a row the store has no atoms for: a motion of NaN makes the call report it as not OK
+                bad = (gstatus[:n] != 0)[:, None]
+                m_rot = (s_rot if starts else torch.from_numpy(rows.rot.reshape(-1, 9)).to(f.tdev)).masked_fill(bad, float("nan"))
+                m_trans = (s_trans if starts else torch.from_numpy(rows.trans).to(f.tdev)).masked_fill(bad, float("nan"))
+                f.keep += [m_rot, m_trans]
+                motion = (m_rot.data_ptr(), m_trans.data_ptr())
+            _ffi.check(f.lib.pmx_combo_overlay(f.owner.handle, chandle.handle, f.library, *f.src[:2], *triple, *motion, f.n, float(node_radius), cw, float(ftol), int(max_iter),
+                                               rot.data_ptr(), trans.data_ptr(), energy.data_ptr(), count.data_ptr(), f.status.data_ptr(), f.stream))
+            if gstatus is not None:
+                g_host = gstatus  # (read after the wait)
+    st = f.st
+    if gstatus is not None:
+        g = g_host.cpu().numpy()[:n].astype(np.int32)
+        st = np.where(g != 0, g, st).astype(np.int32)
+    en, cn, R, t = f.host(energy), f.host(count).astype(np.int64), f.host(rot), f.host(trans)
+    hits = n // k
+    if starts:
+        each = en[:, 13].reshape(hits, k)
+        best = np.argmax(np.where(np.isnan(each), -np.inf, each), axis=1) if hits else np.zeros(0, np.int64)  # (the first among equals)
+        pick = np.arange(hits) * k + best
+        start, start_value = best.astype(np.int64), each.copy()
+    else:
+        pick, start, start_value = np.arange(n), np.full(n, -1, np.int64), np.zeros((n, 0))
+    return ComboOverlay(rotation=R[pick].copy(), translation=t[pick].copy(), overlap_start=en[pick, 0], overlap=en[pick, 1], self_overlap=en[pick, 2],
+                        reference_overlap=en[pick, 3], tanimoto_start=en[pick, 4], tanimoto=en[pick, 5], angle=en[pick, 14], shift=en[pick, 15], iterations=cn[pick, 0],
+                        accepted=cn[pick, 1], stop=cn[pick, 2], n_points=cn[pick, 3], start=start, start_tanimoto=start_value, status=st[pick],
+                        indices=rows.idx[pick].copy(), conformers=rows.conf[pick].astype(np.int64), colour_overlap_start=en[pick, 6], colour_overlap=en[pick, 7],
+                        colour_self_overlap=en[pick, 8], colour_reference_overlap=en[pick, 9], colour_tanimoto_start=en[pick, 10], colour_tanimoto=en[pick, 11],
+                        combo_start=en[pick, 12], combo=en[pick, 13], n_nodes=cn[pick, 4], n_reference_features=cn[pick, 5], colour_weight=cw)
+
+
+def colour_of(poses, reference, library, **kw) -> ColourReport:
+    """`colour` of posed rows - an `Alignment`, `RefinedPoses`, `ShapeOverlay` or `ComboOverlay` whose rows are ligands of `library` - at
+    their own motions: the rows' pharmacophore nodes compared with a known ligand's typed features. Row i of the report is row i of the
+    poses. Further arguments (`cover`) as `colour` takes them. (A function, not a method: the posed classes keep their set of methods.)"""
+    if poses.indices is None:
+        raise ValueError("colour_of: these rows are points of the caller's, not ligands of a library")
+    return colour(reference, library, poses.indices, poses.conformers, poses.rotation, poses.translation, **kw)
+
+
+def combo_overlay_of(poses, reference, library, atoms=None, **kw) -> ComboOverlay:
+    """`combo_overlay` of posed rows from each row's own motion: how far is this pose from its nearest match with a known ligand in shape
+    and colour together? The nodes carry the types; the shape points are the nodes or - with `atoms`, the library's atom store - the heavy
+    atoms. Further arguments (`colour_weight`, `node_radius`, `ftol`, `max_iter`) as `combo_overlay` takes them."""
+    if poses.indices is None:
+        raise ValueError("combo_overlay_of: these rows are points of the caller's, not ligands of a library")
+    if kw.get("starts", 0):
+        raise ValueError("combo_overlay_of: the local overlay of these poses; `combo_overlay(..., starts=4)` is the one that needs no pose")
+    return combo_overlay(reference, library, poses.indices, poses.conformers, poses.rotation, poses.translation, atoms=atoms, **kw)

@@ -8,6 +8,8 @@ Output: `path,score` CSV, best first, ties in library order (`screening.py:70-75
 `--explain K --clashes PATH [--protein FILE.pdb]` checks the explained hits' poses against the protein's atoms (excluded volumes).
 `--explain K --pose_shape PATH --shape_ref FILE.pdb` compares the explained hits' poses with a known ligand (Gaussian shape overlap).
 `--explain K --overlay_out PATH --shape_ref FILE.pdb` overlays the explained hits on that ligand (a rigid maximisation of the overlap).
+`--explain K --pose_colour PATH --colour_ref FILE.csv` compares the explained hits' typed nodes with that ligand's pharmacophore features.
+`--explain K --combo_out PATH --shape_ref FILE.pdb --colour_ref FILE.csv` overlays the hits by shape and colour together.
 `--explain K --refine_out PATH [--refine_restraint X] [--refine_iter N]` moves those poses out of the protein's atoms (restrained rigid-body refinement).
 `--explain K --pose_fit PATH [--pose_fit_mode key|free]` scores those poses in place: the overlap of the posed pharmacophore nodes with the model's hotspots (with --refine_out also at the refined motion).
 `--explain K --pose_search PATH [--pose_search_modes M] [--pose_min_fraction F] [--pose_search_level nodes|atoms]` poses every explained hit in the conformer and binding mode that fits the pocket.
@@ -26,6 +28,7 @@ from pathlib import Path
 import numpy as np
 
 from .atoms import PackedAtoms, atoms_path
+from .constants import TYPE_NAMES
 from .library import PackedLibrary
 from .pharmacophore_model import PharmacophoreModel
 
@@ -60,6 +63,11 @@ class Screening_ArgParser(argparse.ArgumentParser):
         cfg.add_argument("--overlay_out", type=str, default=None, metavar="PATH", help="with --explain K and --shape_ref: CSV with one row per explained hit: its best conformer overlaid on the known ligand (a rigid, local maximisation of the Gaussian shape overlap; no atom types): the shape Tanimoto before and after, how far the hit moved, and the motion")
         cfg.add_argument("--overlay_starts", type=int, choices=(0, 4), default=4, help="with --overlay_out: 4 runs each hit from the four motions that lay its inertial frame on the known ligand's and keeps the best; 0 starts from the hit's fitted pose")
         cfg.add_argument("--overlay_iter", type=int, default=32, metavar="N", help="with --overlay_out: at most N trial motions per start (0 to 64)")
+        cfg.add_argument("--pose_colour", type=str, default=None, metavar="PATH", help="with --explain K and --colour_ref: CSV with one row per explained hit: the typed (colour) overlap of its posed pharmacophore nodes with a known ligand's features - matched nodes and features, the colour overlap, Tanimoto and fractions, and the overlap each type carries; points and types only, no directions")
+        cfg.add_argument("--colour_ref", type=str, default=None, metavar="FILE.csv", help="with --pose_colour / --combo_out: the known ligand's pharmacophore features in the model's frame, lines type,x,y,z with type one of " + ", ".join(TYPE_NAMES))
+        cfg.add_argument("--colour_cover", type=float, default=2.0, metavar="D", help="with --pose_colour: a node (a feature) counts as matched when its nearest partner of a shared type is closer than D Angstrom")
+        cfg.add_argument("--combo_out", type=str, default=None, metavar="PATH", help="with --explain K, --shape_ref and --colour_ref: CSV with one row per explained hit: its best conformer overlaid on the known ligand by shape and colour together (a rigid, local maximisation of O_AB + W C_AB): the overlay CSV's columns and the colour Tanimoto before and after and the combo, the sum of the two Tanimotos")
+        cfg.add_argument("--combo_weight", type=str, default="balanced", metavar="W|balanced", help="with --combo_out: the weight of the colour overlap against the shape overlap; balanced is O_BB / C_BB of the known ligand (derived, not calibrated)")
         cfg.add_argument("--shape_level", choices=("nodes", "atoms"), default="atoms", help="with --pose_shape / --overlay_out: compare the hit's pharmacophore nodes, or its heavy atoms (where they come from: as --clash_level)")
         cfg.add_argument("--refine_restraint", type=float, default=0.1, metavar="X", help="with --refine_out: the weight of the restraint that holds the pose near its fit (uncalibrated default)")
         cfg.add_argument("--refine_iter", type=int, default=32, metavar="N", help="with --refine_out: at most N trial motions per pose (0 to 64)")
@@ -199,8 +207,28 @@ def main(argv=None) -> None:
         parser.error("--overlay_out needs --shape_ref FILE.pdb, the known ligand")
     if args.overlay_out and not 0 <= args.overlay_iter <= 64:
         parser.error("--overlay_iter takes 0 to 64")
-    if args.shape_ref and not (args.pose_shape or args.overlay_out):
+    if args.shape_ref and not (args.pose_shape or args.overlay_out or args.combo_out):
         parser.error("--shape_ref needs --pose_shape PATH or --overlay_out PATH")
+    if (args.pose_colour or args.combo_out) and args.explain <= 0:
+        parser.error(f"{'--pose_colour' if args.pose_colour else '--combo_out'} needs --explain K")
+    if (args.pose_colour or args.combo_out) and not args.colour_ref:
+        parser.error(f"{'--pose_colour' if args.pose_colour else '--combo_out'} needs --colour_ref FILE.csv, the known ligand's features")
+    if args.combo_out and not args.shape_ref:
+        parser.error("--combo_out needs --shape_ref FILE.pdb, the known ligand")
+    if args.colour_ref and not (args.pose_colour or args.combo_out):
+        parser.error("--colour_ref needs --pose_colour PATH or --combo_out PATH")
+    if args.pose_colour and not (np.isfinite(args.colour_cover) and args.colour_cover >= 0):
+        parser.error("--colour_cover takes a distance that is not negative")
+    if args.combo_out and not 0 <= args.overlay_iter <= 64:
+        parser.error("--overlay_iter takes 0 to 64")
+    combo_weight = "balanced"
+    if args.combo_out and args.combo_weight != "balanced":
+        try:
+            combo_weight = float(args.combo_weight)
+        except ValueError:
+            combo_weight = float("nan")
+        if not (np.isfinite(combo_weight) and combo_weight >= 0):
+            parser.error("--combo_weight takes a number that is not negative, or balanced")
     if args.pose_shape and not (np.isfinite(args.shape_cover) and args.shape_cover >= 0):
         parser.error("--shape_cover takes a distance that is not negative")
     if not (args.clashes or args.refine_out or args.pose_search) and args.protein:
@@ -215,7 +243,7 @@ def main(argv=None) -> None:
     if (args.clashes or args.refine_out) and args.clash_level == "atoms" and packed_without_atoms:
         parser.error(f"--clash_level atoms takes the hits' atoms from {atoms_path(args.library_dir)}, which does not exist (--save_top writes it from a library directory; "
                      "or use --clash_level nodes)")
-    if (args.pose_shape or args.overlay_out) and args.shape_level == "atoms" and packed_without_atoms:
+    if (args.pose_shape or args.overlay_out or args.combo_out) and args.shape_level == "atoms" and packed_without_atoms:
         parser.error(f"--shape_level atoms takes the hits' atoms from {atoms_path(args.library_dir)}, which does not exist (--save_top writes it from a library directory; "
                      "or use --shape_level nodes)")
     if args.pose_search and args.pose_search_level == "atoms" and packed_without_atoms:
@@ -299,7 +327,14 @@ def main(argv=None) -> None:
             pocket = PocketAtoms.from_pdb(Path(args.protein), centers=model.node_centers) if args.protein else model.pocket_atoms()
         except (OSError, ValueError) as e:
             parser.error(f"{'--clashes' if args.clashes else '--refine_out' if args.refine_out else '--pose_search'}: {e}" + ("" if args.protein else " (give it with --protein FILE.pdb)"))
-    if args.pose_shape or args.overlay_out:  # (before the screen: a reference that cannot be read should not cost a pass)
+    if args.pose_colour or args.combo_out:
+        from .shape import ColourFeatures
+
+        try:
+            colour_ref = ColourFeatures.from_csv(Path(args.colour_ref))
+        except (OSError, ValueError) as e:
+            parser.error(f"--colour_ref {args.colour_ref}: {e}")
+    if args.pose_shape or args.overlay_out or args.combo_out:  # (before the screen: a reference that cannot be read should not cost a pass)
         from .shape import ReferenceLigand
 
         try:
@@ -310,7 +345,7 @@ def main(argv=None) -> None:
     packed = Path(args.library_dir).is_file()
     atom_search = bool(args.pose_search) and args.pose_search_level == "atoms"
     if (atom_search or args.save_top or (packed and (args.clashes or args.refine_out) and args.clash_level == "atoms")
-            or (packed and (args.pose_shape or args.overlay_out) and args.shape_level == "atoms")):
+            or (packed and (args.pose_shape or args.overlay_out or args.combo_out) and args.shape_level == "atoms")):
         names, lib, store = load_library(Path(args.library_dir), args.cpus, on_device=True, with_atoms=True)
     else:
         (names, lib), store = load_library(Path(args.library_dir), args.cpus, on_device=True), None
@@ -360,6 +395,11 @@ def main(argv=None) -> None:
         if args.overlay_out:
             write_overlay_csv(Path(args.overlay_out), names, scores, status, model, lib, weight, args.explain, shape_ref, args.shape_level, args.overlay_starts, args.overlay_iter,
                               hit_atoms)
+        if args.pose_colour:
+            write_pose_colour_csv(Path(args.pose_colour), names, scores, status, model, lib, weight, args.explain, colour_ref, args.colour_cover)
+        if args.combo_out:
+            write_combo_csv(Path(args.combo_out), names, scores, status, model, lib, weight, args.explain, shape_ref, colour_ref, combo_weight, args.shape_level,
+                            args.overlay_starts, args.overlay_iter, hit_atoms)
         if args.pose_search:
             write_pose_search_csv(Path(args.pose_search), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_tolerance, args.pose_search_modes,
                                   args.pose_min_fraction, store if atom_search else None)
@@ -767,6 +807,64 @@ def write_overlay_csv(out: Path, names: list[str], scores: np.ndarray, status: n
         for r, row in enumerate(al.rows):
             nums = ",".join(repr(float(v)) for v in (ov.tanimoto_start[r], ov.tanimoto[r], ov.overlap[r], ref_fraction[r], fit_fraction[r], np.degrees(ov.angle[r]), ov.shift[r],
                                                       *ov.rotation[r].reshape(-1), *ov.translation[r]))
+            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{level},{int(ov.start[r])},{int(ov.n_points[r])},{int(ov.iterations[r])},{int(ov.stop[r])},{nums}\n")
+
+
+POSE_COLOUR_HEADER = ("rank,path,conformer,stage,nodes,matched,reference_features,reference_matched,colour_overlap,colour_tanimoto,reference_fraction,fit_fraction,"
+                      + ",".join(TYPE_NAMES))
+
+
+def write_pose_colour_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, reference, cover: float) -> None:
+    """One row per hit of the k best, in the order of the poses CSV, with stage `fit`: the pharmacophore nodes of the hit's best conformer
+    under its fitted pose (`engine.align`) compared with the known ligand's typed features `reference` (`engine.colour`). Nodes and the
+    nodes with a partner of a shared type within `cover`, the reference's features and those reproduced, the colour overlap, its Tanimoto,
+    the fraction of the reference that is reproduced and of the hit that lies on it, and the overlap each type carries. Every float is the
+    `repr` of the float64 the GPU returned."""
+    from .engine import colour_of, explain
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
+    rep = colour_of(al, reference, lib, cover=cover)
+    with open(out, "w") as w:
+        w.write(POSE_COLOUR_HEADER + "\n")
+        for r, row in enumerate(al.rows):
+            nums = ",".join(repr(float(v)) for v in (rep.overlap[r], rep.tanimoto[r], rep.reference_fraction[r], rep.fit_fraction[r], *rep.type_overlap[r]))
+            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},fit,{int(rep.n_nodes[r])},{int(rep.n_matched[r])},{len(reference)},"
+                    f"{int(rep.n_reference_matched[r])},{nums}\n")
+
+
+COMBO_HEADER = OVERLAY_HEADER + ",colour_tanimoto_start,colour_tanimoto,combo"
+
+
+def write_combo_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, reference, colour, colour_weight, level: str, starts: int,
+                    max_iter: int, store: PackedAtoms | None = None) -> None:
+    """One row per hit of the k best, in the order of the poses CSV: the hit's best conformer overlaid on the known ligand by shape and
+    colour together (`engine.combo_overlay`; `reference` its atoms, `colour` its typed features). The columns of the overlay CSV - the
+    shape points at level `nodes` the hit's pharmacophore nodes, at level `atoms` its heavy atoms - and the colour Tanimoto at the start
+    and at the end and the combo at the end, the sum of the two Tanimotos. The typed points are always the hit's nodes."""
+    from .engine import _heavy_atoms, combo_overlay, explain
+
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
+    atoms = _hit_atoms(store, names, order, al.rows) if level == "atoms" else None
+    source = {}
+    if atoms is not None and store is not None:
+        source = dict(atoms=atoms)
+    elif atoms is not None:  # (a directory's hits, read again: their heavy atoms as the caller's points)
+        points, radii = _heavy_atoms(atoms, al.conformers)
+        source = dict(points=points, point_radii=radii)
+    motion = {} if starts else dict(rotation=al.rotation, translation=al.translation)
+    ov = combo_overlay(reference, lib, al.indices, al.conformers, colour=colour, colour_weight=colour_weight, starts=starts, max_iter=max_iter, **motion, **source)
+    with np.errstate(all="ignore"):
+        ref_fraction = ov.overlap / ov.reference_overlap
+        fit_fraction = np.where(ov.self_overlap == 0.0, 0.0, ov.overlap / np.where(ov.self_overlap == 0.0, 1.0, ov.self_overlap))
+    with open(out, "w") as w:
+        w.write(COMBO_HEADER + "\n")
+        for r, row in enumerate(al.rows):
+            nums = ",".join(repr(float(v)) for v in (ov.tanimoto_start[r], ov.tanimoto[r], ov.overlap[r], ref_fraction[r], fit_fraction[r], np.degrees(ov.angle[r]), ov.shift[r],
+                                                      *ov.rotation[r].reshape(-1), *ov.translation[r], ov.colour_tanimoto_start[r], ov.colour_tanimoto[r], ov.combo[r]))
             w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{level},{int(ov.start[r])},{int(ov.n_points[r])},{int(ov.iterations[r])},{int(ov.stop[r])},{nums}\n")
 
 
