@@ -56,6 +56,8 @@ typedef struct pmx_library pmx_library;
  * (src/pmnet/pharmacophore_model.py:191-204) made positional. edge_mean / edge_std are the
  * float32 values of `model_node1.neighbor_edge_dict[model_node2].distance_mean / .distance_std`
  * (src/pmnet/scoring/match_utils.py:35-48) for every ordered node pair, self-loops included.
+ * The matrices need not be symmetric: a term of ligand nodes (u, v) reads edge [m * n_nodes + n], m matched to u and n to v, with u before v
+ * in its cluster's order (self entries) or u in the cluster of the earlier tree level (pair entries), as oracle/pmx_oracle.c node_pair_term.
  * Clusters are listed in `model.node_clusters` order (pharmacophore_model.py:202-204);
  * cluster_typemask is the stored `node_types` set, cluster_center / cluster_size feed the
  * cluster-distance prefilter (src/pmnet/scoring/graph_match.py:263-268).
