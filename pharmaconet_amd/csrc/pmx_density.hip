@@ -16,8 +16,11 @@
 //     32 + neighbour number) - the sequential search gives a voxel to the EARLIEST queue entry that sees it, and among the
 //     children of one entry the neighbour order decides - then a prefix sum over the claims per frontier voxel places the
 //     next level. The member list that comes out is, element for element, the reference's `cluster` list.
-// Component labels are independent of the search order; the order kernel's output is checked against the host search on the
-// fixture maps and on random blobs (tests/test_model_builder.py, -m gpu) and the model state it leads to against the reference's.
+// Component labels are independent of the search order. Both kernels are held, through the C ABI and with seeds the tests choose,
+// to a plain restatement (tests/density_ref.py, itself pinned to the host search by tests/test_density_cpu.py) at every grid size
+// from 1 to 128, at frontier widths beside a wavefront, a workgroup and the scan's chunk sizes, on paths of thousands of levels
+// and on the special float values (tests/test_gpu_density.py, -m gpu); the model state the searches lead to is held to the
+// reference's, with the fall-back to the host search taken away (tests/test_model_builder.py, -m gpu).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

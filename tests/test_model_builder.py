@@ -3,6 +3,7 @@
 `PharmacophoreModel.create` (`pharmacophore_model.py:108-149`, `utils/density_map.py`) on synthetic hotspot
 density maps (several components per map, touching blobs, specks under the 8-voxel floor) and saved its state."""
 
+import contextlib
 from pathlib import Path
 
 import numpy as np
@@ -27,10 +28,37 @@ def load_inputs(name):
     return z["center"], infos
 
 
-def _assert_state_equals_reference(name, device):
+@contextlib.contextmanager
+def only_the_device_search(monkeypatch, infos):
+    """`build_model_state` has two ways back to the host loop - `device_search_agrees` and, in `create(device="auto")`, a caught
+    RuntimeError - and either would leave a broken kernel unseen. Inside this block there is none: the self-check has passed, the
+    host search raises, and on leaving it `voxel_components_device` has been called once, with all hotspot maps."""
+    from pharmaconet_amd import model_builder
+
+    assert model_builder.device_search_agrees(0) is True  # (runs the host search once per process: before it is taken away)
+    calls = []
+    device_search = model_builder.voxel_components_device
+
+    def recorded(masks, device=0):
+        calls.append((list(masks), device))
+        return device_search(masks, device)
+
+    def no_host_search(mask):
+        raise AssertionError("build_model_state(device=0) fell back to the host search")
+
+    with monkeypatch.context() as patch:
+        patch.setattr(model_builder, "voxel_components_device", recorded)
+        patch.setattr(model_builder, "voxel_components", no_host_search)
+        yield
+    assert len(calls) == 1 and calls[0][1] == 0
+    assert len(calls[0][0]) == len(infos) and all(m is info["point_map"] for m, info in zip(calls[0][0], infos))
+
+
+def _assert_state_equals_reference(name, device, monkeypatch=None):
     center, infos = load_inputs(name)
     want = PharmacophoreModel.load(GOLDEN / f"create_{name}.pm").__getstate__()
-    got = build_model_state(want["pdbblock"], center, infos, device=device)
+    with only_the_device_search(monkeypatch, infos) if device is not None else contextlib.nullcontext():
+        got = build_model_state(want["pdbblock"], center, infos, device=device)
     assert got["pdbblock"] == want["pdbblock"]
     # nodes: numbering (component order), float32 centres, radii, edge maps and overlap lists - exact
     assert len(got["nodes"]) == len(want["nodes"])
@@ -57,10 +85,55 @@ def test_state_equals_reference(name):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", CASES)
-def test_state_equals_reference_with_the_searches_on_the_gpu(name):
+def test_state_equals_reference_with_the_searches_on_the_gpu(name, monkeypatch):
     """the voxel searches of `DensityMapGraph` on the device (`csrc/pmx_density.hip`: component labels +
-    breadth-first member order per component), the seeds from CPython's own `set.pop()`: the same state as the reference's."""
-    _assert_state_equals_reference(name, 0)
+    breadth-first member order per component), the seeds from CPython's own `set.pop()`: the same state as the reference's - and
+    built by the device search, not by a fall-back to the host loop (`only_the_device_search`)."""
+    _assert_state_equals_reference(name, 0, monkeypatch)
+
+
+def synthetic_hotspots_24():
+    """(center, hotspot infos) on a 24^3 grid: several components per map, blobs that touch, specks under the 8-voxel floor."""
+    rng = np.random.default_rng(2424)
+    g = np.stack(np.meshgrid(*[np.arange(24)] * 3, indexing="ij"), -1)
+    kinds = ("Hydrophobic", "HBond_pdon", "PiStacking_P", "SaltBridge_pneg", "HBond_ldon", "Hydrophobic", "SaltBridge_lneg", "XBond")
+    infos = []
+    for h, kind in enumerate(kinds):
+        m = np.zeros((24, 24, 24), dtype=np.float32)
+        first = rng.integers(4, 20, size=3)
+        balls = [(first, 2.6), (first + (3, 1, 0), 2.2)]  # two blobs that touch: one component
+        balls += [(rng.integers(2, 22, size=3), rng.uniform(1.5, 3.2)) for _ in range(4 + h % 3)]
+        for c, r in balls:
+            inside = ((g - c) ** 2).sum(-1) <= r * r
+            m[inside] = rng.uniform(0.05, 1.0, size=int(inside.sum())).astype(np.float32)
+        m[rng.random(m.shape) < 0.002] = 0.3  # specks
+        m[0, 0, 0] = m[23, 23, 23] = m[23, 23, 22] = 0.2
+        infos.append(dict(nci_type=kind, hotspot_position=rng.uniform(-5, 5, size=3).astype(np.float32), hotspot_score=float(rng.uniform(0.3, 1.0)),
+                          point_map=m))
+    return np.array([1.5, -2.25, 3.0]), infos
+
+
+def test_synthetic_hotspots_24_hold_what_they_are_named_for():
+    _, infos = synthetic_hotspots_24()
+    sizes = [[len(members) for members, _ in voxel_components(info["point_map"])] for info in infos]
+    assert all(sum(s >= 8 for s in per_map) >= 2 for per_map in sizes)  # several components per map that become nodes
+    assert all(any(s < 8 for s in per_map) for per_map in sizes)  # and specks that do not
+    state = build_model_state(None, *synthetic_hotspots_24(), resolution=1.0, size=24)
+    assert len(state["nodes"]) == sum(s >= 8 for per_map in sizes for s in per_map) >= 20
+    assert sum(len(v) for v in state["node_cluster_dict"].values()) >= 4
+
+
+@pytest.mark.gpu
+def test_state_at_another_geometry_with_the_searches_on_the_gpu(monkeypatch):
+    """A 24^3 grid at 1 A: the state built with the device search equals the one built with the host search, exactly."""
+    center, infos = synthetic_hotspots_24()
+    want = build_model_state("X", center, infos, resolution=1.0, size=24, device=None)
+    with only_the_device_search(monkeypatch, infos):
+        got = build_model_state("X", center, infos, resolution=1.0, size=24, device=0)
+    assert len(want["nodes"]) >= 20
+    for g, w in zip(got["nodes"], want["nodes"]):
+        assert g == w, (g["index"], g, w)
+    assert got == want
 
 
 @pytest.mark.gpu
