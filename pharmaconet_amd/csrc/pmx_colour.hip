@@ -15,8 +15,10 @@
 //   features  lane b walks the row's nodes in ascending a: a per-lane minimum under a strict <
 //   row       the lanes are combined by the fixed butterfly of pmx_pose.h; matched_fp is one ballot
 // combo_kernel
-//   LDS       overlay_kernel's 72 KB (the shape reference, the row's shape points unposed and posed at the input) and the features: 75840
-//             bytes a block, two blocks a CU
+//   LDS       overlay_kernel's 72 KB, staged by the same functions of pmx_shape.h (stage_reference; stage_points for the row's shape
+//             points unposed and posed at the input; O_AA by pmx::self_overlap), and the features: 75840 bytes a block, two blocks a CU.
+//             The kernel's own: the two sources' statuses, the node source's first, and the lane's node with its mask - a mask >= 128
+//             goes through the one ballot the radii go through
 //   evaluate  pmx::shape_evaluate of pmx_shape.h - the evaluation pmx_shape_overlay iterates on - then the colour pairs of the lane's
 //             node: the same closed-form blocks with r = p - c, c the shape points' centroid; after the butterflies H = H_shape + cw *
 //             H_colour and g likewise
@@ -62,12 +64,14 @@ using pmx::PoseSource;
 using pmx::radius_ok;
 using pmx::ShapeEval;
 using pmx::store_motion;
+using pmx::store_not_ok;
+using pmx::tanimoto;
 using pmx::wave_sum;
 
 constexpr int kA = PMX_MAX_LIGAND_ATOMS;
 constexpr int kF = PMX_MAX_LIGAND_NODES; // typed points of a row, features of a reference: a lane each
 constexpr int kT = PMX_NUM_TYPES;
-constexpr int kWaves = 4;
+constexpr int kWaves = pmx::kShapeWaves;
 static_assert(kF == 64, "a lane per typed point and per feature: one trip of the wavefront");
 static_assert(kT == 7, "a type mask is 7 bits: < 128");
 
@@ -134,7 +138,6 @@ __device__ __forceinline__ double scalar(double x) {
     return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 
-__device__ __forceinline__ double tanimoto(double oab, double oaa, double obb) { return oab / ((oaa + obb) - oab); }
 __device__ __forceinline__ double colour_tanimoto(double cab, double caa, double cbb) { return cab == 0.0 ? 0.0 : cab / ((caa + cbb) - cab); }
 
 // ---------------------------------------------------------------------------------------------------------------- pmx_pose_colour
@@ -464,9 +467,8 @@ __global__ __launch_bounds__(64 * kWaves, 2) void combo_kernel(const ComboArgs a
     const uint32_t row = blockIdx.x * kWaves + (uint32_t)wave;
     const bool live = row < a.n;
     const int lane = (int)(threadIdx.x % 64);
-    const double nan = __builtin_nan("");
 
-    for (uint32_t b = threadIdx.x; b < a.m; b += 64 * kWaves) Lref[b] = a.ref[b];
+    pmx::stage_reference(Lref, a.ref, a.m);
     stage_features(a.colour, Lfeat, Lmask);
 
     // ---- the row's shape points - unposed with their alphas, and posed at the input motion - and the lane's node
@@ -488,20 +490,7 @@ __global__ __launch_bounds__(64 * kWaves, 2) void combo_kernel(const ComboArgs a
         nn = nr.npts;
         if (status == PMX_LIGAND_OK && npts > (uint32_t)kA) status = PMX_LIGAND_UNSUPPORTED; // (more points than a molecule of the atom store can have)
         if (status != PMX_LIGAND_OK) npts = nn = 0;
-        bool bad = false;
-        for (uint32_t base = 0; base < npts; base += 64) {
-            const uint32_t u = base + (uint32_t)lane;
-            if (u < npts) {
-                double y0, y1, y2, q0, q1, q2;
-                pose_load(pr, u, y0, y1, y2);
-                pose_point(R0, t0, y0, y1, y2, q0, q1, q2);
-                const float r = pr.radii ? pr.radii[u] : a.radius;
-                bad = bad || !radius_ok(r);
-                const double al = pmx::alpha_of(r);
-                X[u] = make_double4(y0, y1, y2, al);
-                P[u] = make_double4(q0, q1, q2, al);
-            }
-        }
+        bool bad = pmx::stage_points<true>(pr, npts, R0, t0, a.radius, lane, P, X);
         if (nn) {
             const uint8_t *masks = record_masks(a.node_src, row);
             if ((uint32_t)lane < nn) {
@@ -510,7 +499,7 @@ __global__ __launch_bounds__(64 * kWaves, 2) void combo_kernel(const ComboArgs a
                 bad = bad || mk >= 128u;
             }
         }
-        if (__ballot(bad) != 0ull) {
+        if (__ballot(bad) != 0ull) { // (a radius that is none, a mask of more than 7 bits: one ballot)
             status = PMX_LIGAND_KEY_INVALID;
             npts = nn = mk = 0;
         }
@@ -518,31 +507,14 @@ __global__ __launch_bounds__(64 * kWaves, 2) void combo_kernel(const ComboArgs a
     __syncthreads();
     if (!live) return;
 
-    if (status != PMX_LIGAND_OK) { // no motion, no energy, count = {0, 0, -1, 0, 0, 0}
-        if (lane < 9) a.rot_out[(size_t)row * 9 + lane] = nan;
-        if (lane < 3) a.trans_out[(size_t)row * 3 + lane] = nan;
-        if (lane < 16) a.energy[(size_t)row * 16 + lane] = nan;
-        if (lane < 6) a.count[(size_t)row * 6 + lane] = lane == 2 ? -1 : 0;
-        if (lane == 0) a.status[row] = status;
+    if (status != PMX_LIGAND_OK) {
+        store_not_ok<16, 6>(a.rot_out, a.trans_out, a.energy, a.count, a.status, row, lane, status);
         return;
     }
     const uint32_t m = a.m;
 
     // ---- O_AA and C_AA, once, of the points and the nodes posed at the input motion: pmx_pose_shape's and pmx_pose_colour's terms
-    double sAA = 0.0;
-    for (uint32_t base = 0; base < npts; base += 64) {
-        const uint32_t u = base + (uint32_t)lane;
-        if (u < npts) {
-            const double4 p = P[u];
-            double self = 0.0;
-            for (uint32_t v = 0; v < npts; ++v) {
-                const double4 q = P[v];
-                self = self + pair_term(dist2(p, q), p.w, q.w);
-            }
-            sAA = sAA + self;
-        }
-    }
-    const double oaa = scalar(wave_sum(sAA));
+    const double oaa = scalar(wave_sum(pmx::self_overlap(P, npts, lane)));
     double caa;
     {
         double p0 = 0.0, p1 = 0.0, p2 = 0.0;

@@ -1,7 +1,7 @@
-// pmx_lm.h - the bounded Levenberg-Marquardt loop over a row's six rigid degrees of freedom that pmx_pose_refine (pmx_refine.hip) and
-// pmx_shape_overlay (pmx_shape_overlay.hip) run, one wavefront per row, once: the 6x6 solve, Rodrigues, the iteration with its lambda
-// schedule and three stop reasons, the net angle and centroid shift, and how a row's motion and a row that is not OK are written. The two
-// calls differ in the objective alone. The definitions are the comment of include/pmx.h; tests/lm_ref.py restates the loop.
+// pmx_lm.h - the bounded Levenberg-Marquardt loop over a row's six rigid degrees of freedom that pmx_pose_refine (pmx_refine.hip),
+// pmx_shape_overlay (pmx_shape_overlay.hip) and pmx_combo_overlay (pmx_colour.hip) run, one wavefront per row, once: the 6x6 solve,
+// Rodrigues, the iteration with its lambda schedule and three stop reasons, the net angle and centroid shift, and how a row's motion and a
+// row that is not OK are written (store_not_ok by the widths of the call's energy and count rows). The calls differ in the objective alone. The definitions are the comment of include/pmx.h; tests/lm_ref.py restates the loop.
 //
 // An objective supplies
 //   Eval                       what an evaluation leaves: c[3], H[21], g[6] and whatever its value is made of
@@ -184,13 +184,14 @@ __device__ __forceinline__ void store_motion(double *rot_out, double *trans_out,
     if (lane < 3) trans_out[(size_t)row * 3 + lane] = out;
 }
 
-// A row that is not OK: no motion, no energy, count = {0, 0, -1, 0}, and its status.
+// A row that is not OK: no motion, no energy (kEnergy values a row), count = {0, 0, -1, 0, ...} (kCount), and its status.
+template <int kEnergy, int kCount>
 __device__ __forceinline__ void store_not_ok(double *rot_out, double *trans_out, double *energy, int32_t *count, int32_t *status_out, uint32_t row, int lane, int status) {
     const double nan = __builtin_nan("");
     if (lane < 9) rot_out[(size_t)row * 9 + lane] = nan;
     if (lane < 3) trans_out[(size_t)row * 3 + lane] = nan;
-    if (lane < 8) energy[(size_t)row * 8 + lane] = nan;
-    if (lane < 4) count[(size_t)row * 4 + lane] = lane == 2 ? -1 : 0;
+    if (lane < kEnergy) energy[(size_t)row * kEnergy + lane] = nan;
+    if (lane < kCount) count[(size_t)row * kCount + lane] = lane == 2 ? -1 : 0;
     if (lane == 0) status_out[row] = status;
 }
 

@@ -1,7 +1,10 @@
-// pmx_pose.h - what the kernels that pose points against the pocket share (pmx_pocket.hip: pmx_pose_clash; pmx_refine.hip:
-// pmx_pose_refine; pmx_pose_fit.hip takes the row front end, the posed point and the butterfly; pmx_pose_shape.hip those and the host's
-// checks, against a reference ligand instead of the pocket), so that they cannot drift: the pocket itself, where a row's points come from and which status it has (the row front
-// end), the posed point as include/pmx.h gives it, the fixed butterfly, and the host's checks of the arguments the two calls have in common.
+// pmx_pose.h - what the kernels that pose a row's points under a rigid motion share, so that they cannot drift.
+//   the pocket's handle       pmx_pocket.hip (pmx_pose_clash), pmx_refine.hip (pmx_pose_refine); pmx_pose_search.hip takes nothing else
+//   the row front end         PoseSource, pose_motion, pose_row, pose_load: where a row's points come from and which status it has. The
+//                             two pocket calls; pmx_pose_fit.hip; and through pmx_shape.h the calls against a reference ligand -
+//                             pmx_pose_shape.hip, pmx_shape_overlay.hip, pmx_colour.hip
+//   the posed point, the fixed butterfly   pose_point as include/pmx.h gives it, wave_sum: every unit above
+//   the host's checks         pose_source, of the source and motion arguments the calls have in common: all of them but pmx_pose_fit
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -5,11 +5,10 @@
 // definitions are the comment of include/pmx.h; tests/shape_ref.py restates them.
 //
 // shape_kernel - one wavefront per row, kWaves per block.
-//   LDS       the reference (y widened, alpha: 32 bytes an atom, at most 8 KB) staged once by the block; per wavefront its row's posed
-//             points with their alphas (at most 8 KB). One barrier, after the staging; every wavefront of the block reaches it, the ones
-//             beyond the call's last row included. After it the LDS is only read.
+//   LDS       the staging of pmx_shape.h (stage_reference, stage_shape_row without the unposed points): the reference, at most 8 KB, and
+//             per wavefront its row's posed points with their alphas, at most 8 KB - 40 KB a block. The one barrier follows it.
 //   points    a lane per point: point base + lane, base = 0, 64, 128, 192. The lane walks the reference in ascending b - every lane reads
-//             the same address, a broadcast - for cross_a, near2_a and point_ref, then the row's points in ascending a' for self_a.
+//             the same address, a broadcast - for cross_a, near2_a and point_ref, then the row's points for self_a (pmx::self_term).
 //   reference a lane per reference atom b walks the row's points in ascending a: ref_near2_b and ref_point are a per-lane minimum under a
 //             strict <, so no minimum crosses lanes.
 //   row       a lane adds up its points (its atoms) in ascending order; the lanes are combined by the fixed butterfly of pmx_pose.h.
@@ -23,22 +22,21 @@
 #include "pmx.h"
 #include "pmx_device.h"
 #include "pmx_pose.h"  // the row front end, the posed point, the butterfly and the host's checks: shared with pmx_pose_clash
-#include "pmx_shape.h" // the reference's handle, the radius rules and the pair term: shared with pmx_shape_overlay.hip
+#include "pmx_shape.h" // the reference's handle, the radius rules, the pair term, the staging and the self term: shared with the overlays
 
 namespace {
 using pmx::alpha_of;
 using pmx::dist2;
 using pmx::pair_term;
-using pmx::pose_load;
-using pmx::pose_point;
-using pmx::pose_row;
-using pmx::PoseRow;
 using pmx::PoseSource;
 using pmx::radius_ok;
+using pmx::self_term;
+using pmx::ShapeRow;
+using pmx::stage_shape_row;
 using pmx::wave_sum;
 
 constexpr int kA = PMX_MAX_LIGAND_ATOMS;
-constexpr int kWaves = 4;
+constexpr int kWaves = pmx::kShapeWaves;
 static_assert(kA % 64 == 0 && PMX_MAX_LIGAND_NODES <= kA, "a row's points and the reference take whole trips of the lanes; a record's nodes fit");
 
 struct ShapeArgs {
@@ -68,55 +66,22 @@ __global__ __launch_bounds__(64 * kWaves) void shape_kernel(const ShapeArgs a) {
     const int lane = (int)(threadIdx.x % 64);
     const double nan = __builtin_nan(""), inf = __builtin_inf();
 
-    for (uint32_t b = threadIdx.x; b < a.m; b += 64 * kWaves) Lref[b] = a.ref[b];
+    pmx::stage_reference(Lref, a.ref, a.m);
 
-    // ---- the row's points, posed, with their alphas
-    PoseRow pr{};
-    int status = PMX_LIGAND_OK;
-    uint32_t npts = 0;
+    // ---- the row's points, posed, with their alphas (pmx::stage_shape_row; the unposed points are not kept)
+    ShapeRow sr{};
     double4 *P = Lpts[wave];
     if (live) {
         double R[9], t[3];
-        bool finite = true;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            R[k] = a.rot[(size_t)row * 9 + k];
-            finite = finite && std::isfinite(R[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            t[k] = a.trans[(size_t)row * 3 + k];
-            finite = finite && std::isfinite(t[k]);
-        }
-        pr = pose_row(a.src, row, finite);
-        status = pr.status;
-        npts = pr.npts;
-        if (npts > (uint32_t)kA) { // (more points than a molecule of the atom store can have: nothing of the row is staged)
-            status = PMX_LIGAND_UNSUPPORTED;
-            npts = 0;
-        }
-        bool bad = false;
-        for (uint32_t base = 0; base < npts; base += 64) {
-            const uint32_t u = base + (uint32_t)lane;
-            if (u < npts) {
-                double x0, x1, x2, p0, p1, p2;
-                pose_load(pr, u, x0, x1, x2);
-                pose_point(R, t, x0, x1, x2, p0, p1, p2);
-                const float r = pr.radii ? pr.radii[u] : a.radius;
-                bad = bad || !radius_ok(r);
-                P[u] = make_double4(p0, p1, p2, alpha_of(r));
-            }
-        }
-        if (__ballot(bad) != 0ull) {
-            status = PMX_LIGAND_KEY_INVALID;
-            npts = 0;
-        }
+        sr = stage_shape_row<false>(a.src, a.rot, a.trans, row, a.radius, lane, R, t, P, nullptr);
     }
     __syncthreads();
     if (!live) return;
+    const int status = sr.status;
+    const uint32_t npts = sr.npts;
     const bool ok = status == PMX_LIGAND_OK;
-    const uint64_t out_at = pr.out_at;
-    const uint32_t out_len = pr.out_len, m = a.m;
+    const uint64_t out_at = sr.pr.out_at;
+    const uint32_t out_len = sr.pr.out_len, m = a.m;
     const double c2 = (double)a.cover * (double)a.cover;
 
     // ---- a lane per point: against the reference, then against the row itself
@@ -138,11 +103,7 @@ __global__ __launch_bounds__(64 * kWaves) void shape_kernel(const ShapeArgs a) {
                     nb = (int)b;
                 }
             }
-            double self = 0.0;
-            for (uint32_t v = 0; v < npts; ++v) {
-                const double4 q = P[v];
-                self = self + pair_term(dist2(p, q), p.w, q.w);
-            }
+            const double self = self_term(P, npts, p);
             a.point_near[out_at + u] = __builtin_sqrt(near2);
             a.point_ref[out_at + u] = nb;
             sAB = sAB + cross;

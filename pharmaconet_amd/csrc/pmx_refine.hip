@@ -266,7 +266,7 @@ __global__ __launch_bounds__(64 * kWaves) void refine_kernel(const RefineArgs a)
     }
 
     if (status != PMX_LIGAND_OK) {
-        store_not_ok(a.rot_out, a.trans_out, a.energy, a.count, a.status, row, lane, status);
+        store_not_ok<8, 4>(a.rot_out, a.trans_out, a.energy, a.count, a.status, row, lane, status);
         return;
     }
 

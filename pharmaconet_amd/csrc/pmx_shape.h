@@ -1,6 +1,14 @@
-// pmx_shape.h - what the two shape units share (pmx_pose_shape.hip: pmx_pose_shape, which judges a pose where it stands;
-// pmx_shape_overlay.hip: pmx_shape_overlay and pmx_shape_starts, which move it), so that they cannot drift: the reference ligand's handle,
-// the rules for a radius, and the pair term of include/pmx.h with the operations in the header's order.
+// pmx_shape.h - what the kernels that judge a row against a known ligand's Gaussian volume share, so that they cannot drift: shape_kernel
+// (pmx_pose_shape.hip: pmx_pose_shape, which judges a pose where it stands), overlay_kernel (pmx_shape_overlay.hip: pmx_shape_overlay, which
+// moves it) and combo_kernel (pmx_colour.hip: pmx_combo_overlay, which moves it by shape and colour together).
+//   all three        the reference ligand's handle, the rules for a radius, the pair term of include/pmx.h with the operations in the
+//                    header's order, the staging of the reference and of a row's shape points in LDS (stage_reference, stage_points),
+//                    the self term O_AA (self_term; shape_kernel calls it inside its per-point loop) and the shape Tanimoto
+//   shape, overlay   stage_shape_row: motion, pose_row, stage_points and the row's status in one. (combo_kernel's rows have a node source
+//                    too; it merges the two statuses itself and ballots the radii with the masks. Given stage_shape_row and a ballot of
+//                    its own, the compiler reloaded 32 spilled scalars per pair of its colour loop: 8 % of pmx_combo_overlay)
+//   overlay, combo   self_overlap (the lanes' sums of self_term) and shape_evaluate, the evaluation the two iterate on
+// pmx_shape_starts (starts_kernel) takes the handle alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,6 +53,90 @@ __device__ __forceinline__ double pair_term(double d2, double aa, double ab, dou
     const double q = kShapePi / s;
     k = (aa * ab) / s;
     return (8.0 * (q * __builtin_sqrt(q))) * exp(-(k * d2));
+}
+
+__device__ __forceinline__ double tanimoto(double oab, double oaa, double obb) { return oab / ((oaa + obb) - oab); }
+
+// ---- staging: a block of kShapeWaves wavefronts, a row each. The reference (y widened, alpha: 32 bytes an atom, at most 8 KB) is copied by
+// the whole block, a row's points by its wavefront into its own slices. Neither function holds the barrier: the kernel has one
+// __syncthreads() after its staging, which every wavefront of the block reaches - the ones beyond the call's last row and the ones whose
+// row is not OK included. After it the LDS is only read.
+constexpr int kShapeWaves = 4;
+
+__device__ __forceinline__ void stage_reference(double4 *Lref, const double4 *ref, uint32_t m) {
+    for (uint32_t b = threadIdx.x; b < m; b += 64 * kShapeWaves) Lref[b] = ref[b];
+}
+
+struct ShapeRow {
+    int status;
+    uint32_t npts; // 0 unless the status is PMX_LIGAND_OK
+    PoseRow pr;
+};
+
+// The trips of a row's wavefront over its points: point u posed at (R0, t0) with its alpha into P[u] and - kUnposed - as it is, widened,
+// with its alpha into X[u]. `radius` is the call's, for a source without radii of its own. Returns whether the lane met a radius that is
+// none; the caller ballots it. At most PMX_MAX_LIGAND_ATOMS points: the caller has refused a longer row.
+template <bool kUnposed>
+__device__ __forceinline__ bool stage_points(const PoseRow &pr, uint32_t npts, const double (&R0)[9], const double (&t0)[3], float radius, int lane, double4 *P, double4 *X) {
+    bool bad = false;
+    for (uint32_t base = 0; base < npts; base += 64) {
+        const uint32_t u = base + (uint32_t)lane;
+        if (u < npts) {
+            double x0, x1, x2, p0, p1, p2;
+            pose_load(pr, u, x0, x1, x2);
+            pose_point(R0, t0, x0, x1, x2, p0, p1, p2);
+            const float r = pr.radii ? pr.radii[u] : radius;
+            bad = bad || !radius_ok(r);
+            const double al = alpha_of(r);
+            if (kUnposed) X[u] = make_double4(x0, x1, x2, al);
+            P[u] = make_double4(p0, p1, p2, al);
+        }
+    }
+    return bad;
+}
+
+// A row's shape points, from its motion to its status: the motion into (R0, t0), the row opened, its points staged (stage_points). The
+// status is, in this order: a motion that is not finite or pose_row's own; PMX_LIGAND_UNSUPPORTED for more than PMX_MAX_LIGAND_ATOMS
+// points (more than a molecule of the atom store can have: nothing of the row is staged); PMX_LIGAND_KEY_INVALID for a radius that is
+// none. (combo_kernel, whose rows have a node source as well, merges the two sources' statuses itself and ballots the radii with the
+// masks: it calls stage_points.)
+template <bool kUnposed>
+__device__ __forceinline__ ShapeRow stage_shape_row(const PoseSource &src, const double *rot, const double *trans, uint32_t row, float radius, int lane, double (&R0)[9],
+                                                    double (&t0)[3], double4 *P, double4 *X) {
+    ShapeRow s;
+    const bool finite = pose_motion(rot, trans, row, R0, t0);
+    s.pr = pose_row(src, row, finite);
+    s.status = s.pr.status;
+    s.npts = s.pr.npts;
+    if (s.npts > (uint32_t)PMX_MAX_LIGAND_ATOMS) {
+        s.status = PMX_LIGAND_UNSUPPORTED;
+        s.npts = 0;
+    }
+    if (__ballot(stage_points<kUnposed>(s.pr, s.npts, R0, t0, radius, lane, P, X)) != 0ull) {
+        s.status = PMX_LIGAND_KEY_INVALID;
+        s.npts = 0;
+    }
+    return s;
+}
+
+// ---- O_AA of the staged points. self_a: point p against all points of the row in ascending a', itself included.
+__device__ __forceinline__ double self_term(const double4 *P, uint32_t npts, const double4 &p) {
+    double self = 0.0;
+    for (uint32_t v = 0; v < npts; ++v) {
+        const double4 q = P[v];
+        self = self + pair_term(dist2(p, q), p.w, q.w);
+    }
+    return self;
+}
+
+// ... and the lane's sum of it over its points (base + lane, base = 0, 64, ...): O_AA is the butterfly of this, pmx_pose_shape's bits.
+__device__ __forceinline__ double self_overlap(const double4 *P, uint32_t npts, int lane) {
+    double sAA = 0.0;
+    for (uint32_t base = 0; base < npts; base += 64) {
+        const uint32_t u = base + (uint32_t)lane;
+        if (u < npts) sAA = sAA + self_term(P, npts, P[u]);
+    }
+    return sAA;
 }
 
 // ---- the evaluation pmx_shape_overlay and pmx_combo_overlay (pmx_colour.hip) iterate on: one definition, so that the two have the same bits

@@ -4,16 +4,16 @@
 // from a pose. The definitions are the comment of include/pmx.h; tests/overlay_ref.py restates them.
 //
 // overlay_kernel - one wavefront per row, kWaves per block.
-//   LDS       the reference (32 bytes an atom, at most 8 KB) staged once by the block; per wavefront its row's unposed points, widened, with
-//             their alphas (X, at most 8 KB) and the points posed at the input motion (P, at most 8 KB; read once, for O_AA): 72 KB a
-//             block. One barrier, after the staging; every wavefront of the block reaches it. After it the LDS is only read.
-//   evaluate  at a motion (R, t), two passes of the wave over X:
+//   LDS       the staging of pmx_shape.h (stage_reference, stage_shape_row): the reference, at most 8 KB, and per wavefront its row's
+//             unposed points with their alphas (X, at most 8 KB) and the points posed at the input motion (P, at most 8 KB; read once,
+//             for O_AA by pmx::self_overlap) - 72 KB a block. The one barrier follows it.
+//   evaluate  pmx::shape_evaluate of pmx_shape.h at a motion (R, t), two passes of the wave over X:
 //     centroid  a lane per point in trips of 64, posed as pmx_pose_clash poses it; the lanes' sums by the fixed butterfly
 //     pairs     a lane per point walks the reference in ascending b - a broadcast read - for cross, f (3 values) and w: one exp and a
 //               handful of multiply-adds a pair. The point's block of H (15 values that are not 0 by structure) and g (6) is formed once
 //               per point, the closed form in r = p - c
-//   reduce    O_AB, H, g: one butterfly each - the same bits in every lane afterwards
-//   iterate   pmx::lm_run of pmx_lm.h, the loop this call shares with pmx_pose_refine, following O_AB up
+//     reduce    O_AB, H, g: one butterfly each - the same bits in every lane afterwards
+//   iterate   pmx::lm_run of pmx_lm.h, the loop this call shares with pmx_pose_refine and pmx_combo_overlay, following O_AB up
 // H, g and the motions are named by constant indices only: registers, no scratch.
 //
 // starts_kernel - one wavefront per row, no LDS: the lanes' sums of the row's unposed points and of the reference's atoms, the butterfly,
@@ -30,26 +30,22 @@
 #include "pmx_shape.h"
 
 namespace {
-using pmx::alpha_of;
-using pmx::dist2;
-using pmx::hidx;
 using pmx::lm_net_motion;
 using pmx::lm_run;
 using pmx::LmRun;
-using pmx::pair_term;
 using pmx::pose_load;
-using pmx::pose_motion;
-using pmx::pose_point;
 using pmx::pose_row;
 using pmx::PoseRow;
 using pmx::PoseSource;
-using pmx::radius_ok;
+using pmx::ShapeRow;
+using pmx::stage_shape_row;
 using pmx::store_motion;
 using pmx::store_not_ok;
+using pmx::tanimoto;
 using pmx::wave_sum;
 
 constexpr int kA = PMX_MAX_LIGAND_ATOMS;
-constexpr int kWaves = 4;
+constexpr int kWaves = pmx::kShapeWaves;
 static_assert(kA % 64 == 0 && PMX_MAX_LIGAND_NODES <= kA, "a row's points take whole trips of the lanes; a record's nodes fit");
 
 struct OverlayArgs {
@@ -90,8 +86,6 @@ struct Overlap {
     __device__ __forceinline__ double gain(double before, double after) const { return after - before; }
 };
 
-__device__ __forceinline__ double tanimoto(double oab, double oaa, double obb) { return oab / ((oaa + obb) - oab); }
-
 __global__ __launch_bounds__(64 * kWaves) void overlay_kernel(const OverlayArgs a) {
     __shared__ double4 Lref[kA];
     __shared__ double4 Lx[kWaves][kA];
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(64 * kWaves) void overlay_kernel(const OverlayArgs 
     const bool live = row < a.n;
     const int lane = (int)(threadIdx.x % 64);
 
-    for (uint32_t b = threadIdx.x; b < a.m; b += 64 * kWaves) Lref[b] = a.ref[b];
+    pmx::stage_reference(Lref, a.ref, a.m);
 
     // ---- the row's points: unposed with their alphas, and posed at the input motion
     double R0[9], t0[3];
@@ -109,61 +103,21 @@ __global__ __launch_bounds__(64 * kWaves) void overlay_kernel(const OverlayArgs 
     for (int k = 0; k < 9; ++k) R0[k] = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) t0[k] = 0.0;
-    int status = PMX_LIGAND_OK;
-    uint32_t npts = 0;
+    ShapeRow sr{};
     double4 *X = Lx[wave], *P = Lp[wave];
-    if (live) {
-        const bool finite = pose_motion(a.rot, a.trans, row, R0, t0);
-        const PoseRow pr = pose_row(a.src, row, finite);
-        status = pr.status;
-        npts = pr.npts;
-        if (npts > (uint32_t)kA) { // (more points than a molecule of the atom store can have: nothing of the row is staged)
-            status = PMX_LIGAND_UNSUPPORTED;
-            npts = 0;
-        }
-        bool bad = false;
-        for (uint32_t base = 0; base < npts; base += 64) {
-            const uint32_t u = base + (uint32_t)lane;
-            if (u < npts) {
-                double x0, x1, x2, p0, p1, p2;
-                pose_load(pr, u, x0, x1, x2);
-                pose_point(R0, t0, x0, x1, x2, p0, p1, p2);
-                const float r = pr.radii ? pr.radii[u] : a.radius;
-                bad = bad || !radius_ok(r);
-                const double al = alpha_of(r);
-                X[u] = make_double4(x0, x1, x2, al);
-                P[u] = make_double4(p0, p1, p2, al);
-            }
-        }
-        if (__ballot(bad) != 0ull) {
-            status = PMX_LIGAND_KEY_INVALID;
-            npts = 0;
-        }
-    }
+    if (live) sr = stage_shape_row<true>(a.src, a.rot, a.trans, row, a.radius, lane, R0, t0, P, X);
     __syncthreads();
     if (!live) return;
+    const int status = sr.status;
+    const uint32_t npts = sr.npts, m = a.m;
 
     if (status != PMX_LIGAND_OK) {
-        store_not_ok(a.rot_out, a.trans_out, a.energy, a.count, a.status, row, lane, status);
+        store_not_ok<8, 4>(a.rot_out, a.trans_out, a.energy, a.count, a.status, row, lane, status);
         return;
     }
-    const uint32_t m = a.m;
 
     // ---- O_AA, once, of the points posed at the input motion: pmx_pose_shape's terms in its order
-    double sAA = 0.0;
-    for (uint32_t base = 0; base < npts; base += 64) {
-        const uint32_t u = base + (uint32_t)lane;
-        if (u < npts) {
-            const double4 p = P[u];
-            double self = 0.0;
-            for (uint32_t v = 0; v < npts; ++v) {
-                const double4 q = P[v];
-                self = self + pair_term(dist2(p, q), p.w, q.w);
-            }
-            sAA = sAA + self;
-        }
-    }
-    const double oaa = wave_sum(sAA);
+    const double oaa = wave_sum(pmx::self_overlap(P, npts, lane));
 
     // ---- the iteration, from the evaluation at the start. No point, or a row so far away that every term underflows: nothing to follow
     double R[9], t[3];

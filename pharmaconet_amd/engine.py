@@ -163,56 +163,25 @@ class ScreeningResult:
                               final Tanimoto, the lower among equals
         k * conformers * starts may not exceed 65536 rows. Further arguments (`node_radius`, `ftol`, `max_iter`) as `overlay` takes them."""
         model, library, weights = self._scored(model, library, weights)
-        if conformers not in ("best", "all"):
-            raise ValueError("ScreeningResult.overlay: conformers is 'best' or 'all'")
-        if starts not in (0, 4):
-            raise ValueError("ScreeningResult.overlay: starts is 0 or 4")
         source = (lambda idx, conf: dict(atoms=atoms, indices=idx, conformers=conf)) if atoms is not None else (lambda idx, conf: dict(library=library, indices=idx, conformers=conf))
-        if conformers == "best":
-            if k * max(starts, 1) > _ffi.EXPLAIN_MAX:
-                raise ValueError(f"ScreeningResult.overlay: {k} hits x {max(starts, 1)} starts exceed {_ffi.EXPLAIN_MAX} rows")
-            al = explain(model, library, self._best(k), weights=weights).poses(model, library, weights=weights)
-            if starts == 0:
-                return al.overlay(reference, library if atoms is None else None, atoms=atoms, **kw)
-            return overlay(reference, starts=starts, **source(al.indices, al.conformers), **kw)
-        if starts == 0:
-            raise ValueError("ScreeningResult.overlay: conformers='all' has a fitted pose for one conformer only; use starts=4")
-        hits = self._best(k).astype(np.int64)
-        with _resident(library) as dlib:
-            n_conf = np.maximum(_record_counts(dlib, hits, 1), 1)
-        rows = int(n_conf.sum()) * starts
-        if rows > _ffi.EXPLAIN_MAX:
-            raise ValueError(f"ScreeningResult.overlay: {len(hits)} hits x their conformers x {starts} starts are {rows} rows, more than {_ffi.EXPLAIN_MAX}; lower k or use conformers='best'")
-        idx, conf = np.repeat(hits, n_conf), np.concatenate([np.arange(c) for c in n_conf]) if len(hits) else np.zeros(0, np.int64)
-        every = overlay(reference, starts=starts, **source(idx, conf), **kw)
-        first = np.concatenate([[0], np.cumsum(n_conf)[:-1]]).astype(np.int64) if len(hits) else np.zeros(0, np.int64)
-        value = np.where(np.isnan(every.tanimoto), -np.inf, every.tanimoto)
-        pick = np.array([lo + int(np.argmax(value[lo: lo + c])) for lo, c in zip(first, n_conf)], dtype=np.int64)  # (the first among equals)
-        return ShapeOverlay(**{f.name: (None if getattr(every, f.name) is None else getattr(every, f.name)[pick]) for f in dataclasses.fields(every)})
+        return self._overlay_hits("overlay", "tanimoto", k, starts, conformers, model, library, weights,
+                                  lambda al: al.overlay(reference, library if atoms is None else None, atoms=atoms, **kw),
+                                  lambda idx, conf: overlay(reference, starts=starts, **source(idx, conf), **kw))
 
-    def combo_overlay(self, k: int, reference, atoms=None, starts: int = 4, conformers: str = "best", model=None, library=None, weights: dict[str, float] | None = None,
-                      **kw) -> "ComboOverlay":
-        """`combo_overlay` of this screen's k best ligands (best first) on a known ligand that carries its typed features
-        (`ReferenceLigand.from_library`, or `colour=` a `shape.ColourFeatures`): shape plus colour, the "TanimotoCombo" of ligand-based
-        screening, of a screen's top hits. The typed points are the hits' pharmacophore nodes; the shape points are those nodes, or the
-        heavy atoms with `atoms` (the library's atom store). `conformers` and `starts` as `overlay` has them, `conformers="all"` keeping
-        per hit the conformer of highest final combo, the lower among equals. Further arguments (`colour_weight`, `node_radius`, `ftol`,
-        `max_iter`) as `combo_overlay` takes them."""
-        what = "ScreeningResult.combo_overlay"
-        model, library, weights = self._scored(model, library, weights)
+    def _overlay_hits(self, name, field, k, starts, conformers, model, library, weights, from_poses, from_starts):
+        """What `overlay` and `combo_overlay` do with this screen's k best ligands: `from_poses(alignment)` runs the call from the fitted
+        poses (`starts=0`), `from_starts(indices, conformers)` from the inertial starts; with `conformers="all"` the conformer of highest
+        final `field` is kept per hit, the lower among equals. `name` names the method in a message."""
+        what = f"ScreeningResult.{name}"
         if conformers not in ("best", "all"):
             raise ValueError(f"{what}: conformers is 'best' or 'all'")
         if starts not in (0, 4):
             raise ValueError(f"{what}: starts is 0 or 4")
-        if atoms is not None and not _is_store(atoms):
-            raise TypeError(f"{what}: atoms is the library's DeviceAtoms / PackedAtoms")
         if conformers == "best":
             if k * max(starts, 1) > _ffi.EXPLAIN_MAX:
                 raise ValueError(f"{what}: {k} hits x {max(starts, 1)} starts exceed {_ffi.EXPLAIN_MAX} rows")
             al = explain(model, library, self._best(k), weights=weights).poses(model, library, weights=weights)
-            if starts == 0:
-                return combo_overlay_of(al, reference, library, atoms=atoms, **kw)
-            return combo_overlay(reference, library, al.indices, al.conformers, atoms=atoms, starts=starts, **kw)
+            return from_poses(al) if starts == 0 else from_starts(al.indices, al.conformers)
         if starts == 0:
             raise ValueError(f"{what}: conformers='all' has a fitted pose for one conformer only; use starts=4")
         hits = self._best(k).astype(np.int64)
@@ -222,13 +191,27 @@ class ScreeningResult:
         if rows > _ffi.EXPLAIN_MAX:
             raise ValueError(f"{what}: {len(hits)} hits x their conformers x {starts} starts are {rows} rows, more than {_ffi.EXPLAIN_MAX}; lower k or use conformers='best'")
         idx, conf = np.repeat(hits, n_conf), np.concatenate([np.arange(c) for c in n_conf]) if len(hits) else np.zeros(0, np.int64)
-        every = combo_overlay(reference, library, idx, conf, atoms=atoms, starts=starts, **kw)
+        every = from_starts(idx, conf)
         first = np.concatenate([[0], np.cumsum(n_conf)[:-1]]).astype(np.int64) if len(hits) else np.zeros(0, np.int64)
-        value = np.where(np.isnan(every.combo), -np.inf, every.combo)
+        value = np.where(np.isnan(getattr(every, field)), -np.inf, getattr(every, field))
         pick = np.array([lo + int(np.argmax(value[lo: lo + c])) for lo, c in zip(first, n_conf)], dtype=np.int64)  # (the first among equals)
-        take = lambda v: v[pick] if isinstance(v, np.ndarray) else v  # noqa: E731  (colour_weight is one number)
-        return ComboOverlay(**{f.name: take(getattr(every, f.name)) for f in dataclasses.fields(every)})
+        take = lambda v: v[pick] if isinstance(v, np.ndarray) else v  # noqa: E731  (None, or the one number colour_weight)
+        return type(every)(**{f.name: take(getattr(every, f.name)) for f in dataclasses.fields(every)})
 
+    def combo_overlay(self, k: int, reference, atoms=None, starts: int = 4, conformers: str = "best", model=None, library=None, weights: dict[str, float] | None = None,
+                      **kw) -> "ComboOverlay":
+        """`combo_overlay` of this screen's k best ligands (best first) on a known ligand that carries its typed features
+        (`ReferenceLigand.from_library`, or `colour=` a `shape.ColourFeatures`): shape plus colour, the "TanimotoCombo" of ligand-based
+        screening, of a screen's top hits. The typed points are the hits' pharmacophore nodes; the shape points are those nodes, or the
+        heavy atoms with `atoms` (the library's atom store). `conformers` and `starts` as `overlay` has them, `conformers="all"` keeping
+        per hit the conformer of highest final combo, the lower among equals. Further arguments (`colour_weight`, `node_radius`, `ftol`,
+        `max_iter`) as `combo_overlay` takes them."""
+        model, library, weights = self._scored(model, library, weights)
+        if atoms is not None and not _is_store(atoms):
+            raise TypeError("ScreeningResult.combo_overlay: atoms is the library's DeviceAtoms / PackedAtoms")
+        return self._overlay_hits("combo_overlay", "combo", k, starts, conformers, model, library, weights,
+                                  lambda al: combo_overlay_of(al, reference, library, atoms=atoms, **kw),
+                                  lambda idx, conf: combo_overlay(reference, library, idx, conf, atoms=atoms, starts=starts, **kw))
 
     def diverse(self, k: int, pool: int | None = None, threshold: float = 0.7, model=None, library=None, weights: dict[str, float] | None = None) -> "DiverseHits":
         """The k first hits of this screen that are not the same binding mode again: the best `pool` hits (default

@@ -243,9 +243,10 @@ def device_pocket(pocket, device=None) -> _PocketHandle:
 
 class _PoseRows:
     """The rows the pose calls share: motions and one source of points, checked and laid out as `pmx_pose_clash`, `pmx_pose_refine`,
-    `pmx_pose_shape` and `pmx_shape_overlay` take them. `what` names the caller in a message."""
+    `pmx_pose_shape` and `pmx_shape_overlay` take them. `what` names the caller in a message. `both` (`pmx_combo_overlay`): the rows are
+    library ligands - node mode - and may carry a shape source next to their nodes, an atom store or `points` / `point_radii`."""
 
-    def __init__(self, what, library, indices, conformers, rotation, translation, points, point_radii, atoms=None):
+    def __init__(self, what, library, indices, conformers, rotation, translation, points, point_radii, atoms=None, both=False):
         self.rot = np.ascontiguousarray(np.asarray(rotation, dtype=np.float64).reshape(-1, 3, 3))
         self.trans = np.ascontiguousarray(np.asarray(translation, dtype=np.float64).reshape(-1, 3))
         n = self.n = len(self.rot)
@@ -255,9 +256,12 @@ class _PoseRows:
             raise ValueError(f"at most 65536 rows per {what} call (PMX_EXPLAIN_MAX)")
         self.node_mode = library is not None
         self.store = atoms  # a `DeviceAtoms` / `PackedAtoms`: point mode, the points gathered on the device
-        if atoms is not None:
-            if not _is_store(atoms):
-                raise TypeError(f"{what}: atoms is a DeviceAtoms or a PackedAtoms")
+        if atoms is not None and not _is_store(atoms):
+            raise TypeError(f"{what}: atoms is a DeviceAtoms or a PackedAtoms")
+        if both:
+            if not self.node_mode or (atoms is not None and points is not None):
+                raise ValueError(f"{what}: a library, and next to it an atom store or points - at most one of the two")
+        elif atoms is not None:
             if self.node_mode or points is not None or point_radii is not None:
                 raise ValueError(f"{what}: a library, points or an atom store - exactly one source of points")
         elif self.node_mode == (points is not None):
@@ -270,7 +274,7 @@ class _PoseRows:
                 raise ValueError("indices, conformers and the motions differ in length")
             if (self.idx < 0).any():
                 raise ValueError("negative ligand index")
-        else:
+        if points is not None:
             if len(points) != n:
                 raise ValueError(f"{len(points)} point sets for {n} motions")
             self.off, self.flat, pts = _ragged(points, np.float32, 3)
@@ -282,27 +286,25 @@ class _PoseRows:
                     raise ValueError("a list of radii differs in length from its points")
 
     def upload(self, tdev, dat: "DeviceAtoms | None" = None):
-        """The device tensors (kept alive by the caller) and the seven source and motion arguments that follow the pocket and the library.
+        """The device tensors (kept alive by the caller) and the seven source and motion arguments that follow the pocket and the library:
+        ligands and conformers in node mode, offsets, points and radii where the rows have points - in `both` mode all five.
         With an atom store (`dat`, resident on `tdev`) the points are gathered there; a row whose gather status is not OK has no points and
         gets a motion of NaN, so that the call reports it as it reports any row that is not OK (`finish` puts the gather's status in)."""
         torch = _torch()
         n = self.n
         up = lambda a: torch.from_numpy(a).to(tdev)  # noqa: E731
         t_rot, t_trans = up(self.rot.reshape(-1, 9) if n else np.zeros((1, 9))), up(self.trans if n else np.zeros((1, 3)))
+        ligands = points = ()
+        if self.idx is not None:
+            ligands = (up(self.idx if n else np.zeros(1, np.int64)), up(self.conf if n else np.zeros(1, np.int32)))
         if dat is not None:
-            t_a, t_b = up(self.idx if n else np.zeros(1, np.int64)), up(self.conf if n else np.zeros(1, np.int32))
-            off, pts, rad, self.gstatus = dat.gather_device(t_a, t_b, n)
+            *points, self.gstatus = dat.gather_device(*ligands, n)
             t_rot, t_trans = self.not_ok(t_rot, t_trans)
-            self.slots, self._off_dev = max(n * dat.max_atoms, 1), off
-            keep, src = (t_rot, t_trans, t_a, t_b, off, pts, rad), (None, None, off.data_ptr(), pts.data_ptr(), rad.data_ptr())
-            return keep, src, (t_rot.data_ptr(), t_trans.data_ptr())
-        if self.node_mode:
-            t_a, t_b = up(self.idx if n else np.zeros(1, np.int64)), up(self.conf if n else np.zeros(1, np.int32))
-            keep, src = (t_rot, t_trans, t_a, t_b), (t_a.data_ptr(), t_b.data_ptr(), None, None, None)
-        else:
-            t_a, t_b, t_c = up(self.off), up(self.flat), (up(self.rad) if self.rad is not None else None)
-            keep, src = (t_rot, t_trans, t_a, t_b, t_c), (None, None, t_a.data_ptr(), t_b.data_ptr(), t_c.data_ptr() if t_c is not None else None)
-        return keep, src, (t_rot.data_ptr(), t_trans.data_ptr())
+            self.slots, self._off_dev = max(n * dat.max_atoms, 1), points[0]
+        elif self.off is not None:
+            points = (up(self.off), up(self.flat), up(self.rad) if self.rad is not None else None)
+        ptr = lambda ts, k: tuple(None if t is None else t.data_ptr() for t in ts) or (None,) * k  # noqa: E731
+        return (t_rot, t_trans, *ligands, *points), ptr(ligands if self.node_mode else (), 2) + ptr(points, 3), (t_rot.data_ptr(), t_trans.data_ptr())
 
     def not_ok(self, *tensors):
         """Store mode, after the gather: the [n, k] float tensors with NaN in the rows the store has no points for. This is the one place
@@ -361,8 +363,8 @@ class _PoseFrame:
 
 @contextlib.contextmanager
 def _pose_frame(rows: _PoseRows, library, atoms, device, owner, owned, per_point: bool = False):
-    """The part the pose calls share, around the one C call that is their own: the library and the atom store made resident, the device
-    they name, the handle `owner(owned, device)` (`device_pocket`, `device_shape_ref`, `device_model`), the rows uploaded; then the
+    """The part the pose calls share, around the one C call that is their own: the library and the atom store made resident (the two
+    together for rows of `both` sources: `f.library` and all of `f.src` are set), the device they name, the handle `owner(owned, device)` (`device_pocket`, `device_shape_ref`, `device_model`), the rows uploaded; then the
     body, which allocates its outputs and enqueues its call on torch's current stream; then the wait, the release of the uploads and the
     rows' statuses. A new pose call is an argument check, its outputs, one `_ffi` call, its result."""
     torch = _torch()
@@ -608,45 +610,18 @@ def overlay(reference, library=None, indices=None, conformers=None, rotation=Non
       max_iter, ftol  at most `max_iter` (<= 64) trial motions per row; a step that raises O_AB by no more than ftol * O_AB ends the row
     Rigid only, shape only (no atom types, no hydrogens), unweighted inertial frames, and a local maximum. At most 65536 rows. Runs on
     torch's current stream of the device and waits for it."""
-    torch = _torch()
-    if starts not in (0, 4):
-        raise ValueError("overlay: starts is 0 (from the given motions) or 4 (the inertial starts)")
-    if not 0 <= int(max_iter) <= 64:
-        raise ValueError("max_iter: 0 to 64 (PMX_REFINE_MAX_ITER)")
-    if not (np.isfinite(ftol) and ftol >= 0):
-        raise ValueError("ftol must be finite and not negative")
-    if not np.isfinite(node_radius):
-        raise ValueError("node_radius must be finite")
-    k = max(starts, 1)
-    if starts:
-        hits = len(points) if points is not None else len(np.asarray(indices).reshape(-1))
-        if hits > 16384:
-            raise ValueError(f"overlay: {hits} hits, at most 16384 with starts=4 (65536 rows)")
-        rep = lambda v: None if v is None else [x for x in v for _ in range(k)]  # noqa: E731
-        points, point_radii = rep(points), rep(point_radii)
-        if indices is not None:
-            indices, conformers = np.repeat(np.asarray(indices).reshape(-1), k), np.repeat(np.asarray(conformers).reshape(-1), k)
-        rotation, translation = np.zeros((hits * k, 3, 3)), np.zeros((hits * k, 3))
-    elif rotation is None or translation is None:
-        raise ValueError("overlay: starts=0 optimises the given motions - rotation and translation")
+    _torch()
+    _overlay_check("overlay", starts, max_iter, ftol, node_radius)
+    hits = 0 if not starts else len(points) if points is not None else len(np.asarray(indices).reshape(-1))
+    indices, conformers, rotation, translation, points, point_radii = _expand_starts("overlay", starts, hits, indices, conformers, rotation, translation, points, point_radii)
     rows = _PoseRows("overlay", library, indices, conformers, rotation, translation, points, point_radii, atoms)
     with _pose_frame(rows, library, atoms, device, device_shape_ref, reference) as f:
-        rot, trans, energy, count, motion = f.f64(f.m, 3, 3), f.f64(f.m, 3), f.f64(f.m, 8), f.i32(f.m, 4), f.motion
-        if starts:
-            s_rot, s_trans, _ = _shape_starts(f, torch.arange(f.m, dtype=torch.int32, device=f.tdev) % k, f.i32(f.m))
-            motion = (s_rot.data_ptr(), s_trans.data_ptr())
-        _ffi.check(f.lib.pmx_shape_overlay(f.owner.handle, f.library, *f.src, *motion, f.n, float(node_radius), float(ftol), int(max_iter), rot.data_ptr(), trans.data_ptr(),
-                                           energy.data_ptr(), count.data_ptr(), f.status.data_ptr(), f.stream))
-    n, st = f.n, f.st
+        rot, trans, energy, count = f.f64(f.m, 3, 3), f.f64(f.m, 3), f.f64(f.m, 8), f.i32(f.m, 4)
+        _ffi.check(f.lib.pmx_shape_overlay(f.owner.handle, f.library, *f.src, *_start_motion(f, starts), f.n, float(node_radius), float(ftol), int(max_iter), rot.data_ptr(),
+                                           trans.data_ptr(), energy.data_ptr(), count.data_ptr(), f.status.data_ptr(), f.stream))
+    st = f.st
     en, cn, R, t = f.host(energy), f.host(count).astype(np.int64), f.host(rot), f.host(trans)
-    hits = n // k
-    if starts:
-        each = en[:, 5].reshape(hits, k)
-        best = np.argmax(np.where(np.isnan(each), -np.inf, each), axis=1) if hits else np.zeros(0, np.int64)  # (the first among equals)
-        pick = np.arange(hits) * k + best
-        start, start_tanimoto = best.astype(np.int64), each.copy()
-    else:
-        pick, start, start_tanimoto = np.arange(n), np.full(n, -1, np.int64), np.zeros((n, 0))
+    pick, start, start_tanimoto = _pick_start(en[:, 5], starts)
     has_rows = rows.node_mode or atoms is not None
     return ShapeOverlay(rotation=R[pick].copy(), translation=t[pick].copy(), overlap_start=en[pick, 0], overlap=en[pick, 1], self_overlap=en[pick, 2],
                         reference_overlap=en[pick, 3], tanimoto_start=en[pick, 4], tanimoto=en[pick, 5], angle=en[pick, 6], shift=en[pick, 7], iterations=cn[pick, 0],
@@ -675,13 +650,60 @@ class ShapeStarts:
 def _shape_starts(f: _PoseFrame, which, status):
     """`pmx_shape_starts` of a frame's rows, enqueued: start `which[i]` (an int32 device tensor) of row i. Returns the device tensors
     (rotation [m, 9], translation [m, 3], frame [m, 16]), NaN in a row the store has no atoms for, whatever its empty point list gave;
-    `status` takes the call's statuses. Behind `overlay_starts` and the inertial leg of `overlay(starts=4)`."""
+    `status` takes the call's statuses. Behind `overlay_starts` and the inertial leg of `overlay(starts=4)` and `combo_overlay(starts=4)`;
+    rows that carry shape points next to their nodes start by those points, so the call gets them alone."""
     rot, trans, frame = f.f64(f.m, 9), f.f64(f.m, 3), f.f64(f.m, 16)
-    _ffi.check(f.lib.pmx_shape_starts(f.owner.handle, f.library, *f.src[:4], which.data_ptr(), f.n, rot.data_ptr(), trans.data_ptr(), frame.data_ptr(), status.data_ptr(),
-                                      f.stream))
+    library, src = (None, (None, None, *f.src[2:4])) if f.src[2] is not None else (f.library, f.src[:4])
+    _ffi.check(f.lib.pmx_shape_starts(f.owner.handle, library, *src, which.data_ptr(), f.n, rot.data_ptr(), trans.data_ptr(), frame.data_ptr(), status.data_ptr(), f.stream))
     out = f.rows.not_ok(rot, trans, frame)
     f.keep += [which, status, *out]
     return out
+
+
+def _start_motion(f: _PoseFrame, starts: int):
+    """The motion arguments an overlay starts from: the frame's own, or - row i being start i % starts of its hit - the inertial ones."""
+    if not starts:
+        return f.motion
+    rot, trans, _ = _shape_starts(f, _torch().arange(f.m, dtype=_torch().int32, device=f.tdev) % starts, f.i32(f.m))
+    return rot.data_ptr(), trans.data_ptr()
+
+
+def _overlay_check(what, starts, max_iter, ftol, node_radius) -> None:
+    """The arguments `overlay` and `combo_overlay` have in common."""
+    if starts not in (0, 4):
+        raise ValueError(f"{what}: starts is 0 (from the given motions) or 4 (the inertial starts)")
+    if not 0 <= int(max_iter) <= 64:
+        raise ValueError("max_iter: 0 to 64 (PMX_REFINE_MAX_ITER)")
+    if not (np.isfinite(ftol) and ftol >= 0):
+        raise ValueError("ftol must be finite and not negative")
+    if not np.isfinite(node_radius):
+        raise ValueError("node_radius must be finite")
+
+
+def _expand_starts(what, starts, hits, indices, conformers, rotation, translation, points, point_radii):
+    """The rows of an overlay from `starts` starts a hit: (indices, conformers, rotation, translation, points, point_radii) with every hit
+    `starts` times in a row under a motion of zeros (the inertial starts replace it); as they are with `starts=0`, which needs motions."""
+    if not starts:
+        if rotation is None or translation is None:
+            raise ValueError(f"{what}: starts=0 optimises the given motions - rotation and translation")
+        return indices, conformers, rotation, translation, points, point_radii
+    if hits > 16384:
+        raise ValueError(f"{what}: {hits} hits, at most 16384 with starts={starts} (65536 rows)")
+    rep = lambda v: None if v is None else [x for x in v for _ in range(starts)]  # noqa: E731
+    if indices is not None:
+        indices, conformers = np.repeat(np.asarray(indices).reshape(-1), starts), np.repeat(np.asarray(conformers).reshape(-1), starts)
+    return indices, conformers, np.zeros((hits * starts, 3, 3)), np.zeros((hits * starts, 3)), rep(points), rep(point_radii)
+
+
+def _pick_start(column: np.ndarray, starts: int):
+    """(pick, start, values) of the rows' final values `column`: per hit the row of its best start - the highest value, the first among
+    equals, NaN below everything -, which start that is, and every start's value [hits, starts]. With `starts=0` every row is its own hit."""
+    n = len(column)
+    if not starts:
+        return np.arange(n), np.full(n, -1, np.int64), np.zeros((n, 0))
+    each = column.reshape(n // starts, starts)
+    best = np.argmax(np.where(np.isnan(each), -np.inf, each), axis=1) if len(each) else np.zeros(0, np.int64)
+    return np.arange(len(each)) * starts + best, best.astype(np.int64), each.copy()
 
 
 def overlay_starts(reference, start, library=None, indices=None, conformers=None, points=None, atoms=None, device=None) -> ShapeStarts:
@@ -1105,19 +1127,12 @@ def combo_overlay(reference, library, indices, conformers, rotation=None, transl
                      (`pmx_shape_starts`) and the start of highest final combo is kept, the lower among equals. At most 16384 hits
     Rigid only, no directions, no hydrogens, first-order overlaps, and a local maximum. At most 65536 rows. Runs on torch's current
     stream of the device and waits for it."""
-    torch = _torch()
+    _torch()
     what = "combo_overlay"
     if library is None:
         raise ValueError(f"{what}: the library is required - the colour points are its records' nodes")
     col = _colour_of(reference if colour is None else colour, what)
-    if starts not in (0, 4):
-        raise ValueError(f"{what}: starts is 0 (from the given motions) or 4 (the inertial starts)")
-    if not 0 <= int(max_iter) <= 64:
-        raise ValueError("max_iter: 0 to 64 (PMX_REFINE_MAX_ITER)")
-    if not (np.isfinite(ftol) and ftol >= 0):
-        raise ValueError("ftol must be finite and not negative")
-    if not np.isfinite(node_radius):
-        raise ValueError("node_radius must be finite")
+    _overlay_check(what, starts, max_iter, ftol, node_radius)
     if not isinstance(colour_weight, str) and not (np.isfinite(colour_weight) and colour_weight >= 0):
         raise ValueError("colour_weight must be finite and not negative, or 'balanced'")
     if isinstance(colour_weight, str) and colour_weight != "balanced":
@@ -1126,78 +1141,18 @@ def combo_overlay(reference, library, indices, conformers, rotation=None, transl
         raise ValueError(f"{what}: atoms is the library's DeviceAtoms / PackedAtoms; points are the alternative to it")
     if point_radii is not None and points is None:
         raise ValueError(f"{what}: point_radii go with points")
-    k = max(starts, 1)
     idx, conf = np.asarray(indices).reshape(-1), np.asarray(conformers).reshape(-1)
-    if starts:
-        hits = len(idx)
-        if hits > 16384:
-            raise ValueError(f"{what}: {hits} hits, at most 16384 with starts=4 (65536 rows)")
-        idx, conf = np.repeat(idx, k), np.repeat(conf, k)
-        points = None if points is None else [p for p in points for _ in range(k)]
-        point_radii = None if point_radii is None else [r for r in point_radii for _ in range(k)]
-        rotation, translation = np.zeros((hits * k, 3, 3)), np.zeros((hits * k, 3))
-    elif rotation is None or translation is None:
-        raise ValueError(f"{what}: starts=0 optimises the given motions - rotation and translation")
-    rows = _PoseRows(what, library, idx, conf, rotation, translation, None, None)
-    n = rows.n
-    p_off = p_flat = p_rad = None
-    if points is not None:
-        if len(points) != n:
-            raise ValueError(f"{len(points)} point sets for {n} rows")
-        p_off, p_flat, pts = _ragged(points, np.float32, 3)
-        if point_radii is not None:
-            if len(point_radii) != n:
-                raise ValueError(f"{len(point_radii)} radius lists for {n} point sets")
-            _, p_rad, rs = _ragged(point_radii, np.float32, None)
-            if any(len(r) != len(p) for r, p in zip(rs, pts)):
-                raise ValueError("a list of radii differs in length from its points")
-    gstatus = None
-    with contextlib.ExitStack() as stack:
-        dlib = stack.enter_context(_resident(library, device))
-        dat = stack.enter_context(_resident_atoms(atoms, dlib.device)) if atoms is not None else None
-        with _pose_frame(rows, dlib, None, device, device_shape_ref, reference) as f:
-            chandle = device_colour_ref(col, f.dev)
-            cw = (float(f.owner.self_overlap / chandle.self_overlap) if chandle.self_overlap > 0 else 0.0) if isinstance(colour_weight, str) else float(colour_weight)
-            rot, trans, energy, count, motion = f.f64(f.m, 3, 3), f.f64(f.m, 3), f.f64(f.m, 16), f.i32(f.m, 6), f.motion
-            triple = (None, None, None)
-            if dat is not None:
-                t_a, t_b = f.up(rows.idx if n else np.zeros(1, np.int64)), f.up(rows.conf if n else np.zeros(1, np.int32))
-                off, pts_dev, rad_dev, gstatus = dat.gather_device(t_a, t_b, n)
-                f.keep += [off, pts_dev, rad_dev, gstatus]
-                triple = (off.data_ptr(), pts_dev.data_ptr(), rad_dev.data_ptr())
-            elif p_off is not None:
-                triple = (f.up(p_off).data_ptr(), f.up(p_flat).data_ptr(), f.up(p_rad).data_ptr() if p_rad is not None else None)
-            if starts:
-                s_rot, s_trans, s_frame, s_status = f.f64(f.m, 9), f.f64(f.m, 3), f.f64(f.m, 16), f.i32(f.m)
-                which = torch.arange(f.m, dtype=torch.int32, device=f.tdev) % k
-                by_points = triple[0] is not None
-                _ffi.check(f.lib.pmx_shape_starts(f.owner.handle, None if by_points else f.library, *((None, None) if by_points else f.src[:2]), triple[0], triple[1],
-                                                  which.data_ptr(), f.n, s_rot.data_ptr(), s_trans.data_ptr(), s_frame.data_ptr(), s_status.data_ptr(), f.stream))
-                f.keep += [which, s_rot, s_trans, s_frame, s_status]
-                motion = (s_rot.data_ptr(), s_trans.data_ptr())
-            if gstatus is not None and n:  # a row the store has no atoms for: a motion of NaN makes the call report it as not OK
-                bad = (gstatus[:n] != 0)[:, None]
-                m_rot = (s_rot if starts else torch.from_numpy(rows.rot.reshape(-1, 9)).to(f.tdev)).masked_fill(bad, float("nan"))
-                m_trans = (s_trans if starts else torch.from_numpy(rows.trans).to(f.tdev)).masked_fill(bad, float("nan"))
-                f.keep += [m_rot, m_trans]
-                motion = (m_rot.data_ptr(), m_trans.data_ptr())
-            _ffi.check(f.lib.pmx_combo_overlay(f.owner.handle, chandle.handle, f.library, *f.src[:2], *triple, *motion, f.n, float(node_radius), cw, float(ftol), int(max_iter),
-                                               rot.data_ptr(), trans.data_ptr(), energy.data_ptr(), count.data_ptr(), f.status.data_ptr(), f.stream))
-            if gstatus is not None:
-                g_host = gstatus  # (read after the wait)
+    idx, conf, rotation, translation, points, point_radii = _expand_starts(what, starts, len(idx), idx, conf, rotation, translation, points, point_radii)
+    rows = _PoseRows(what, library, idx, conf, rotation, translation, points, point_radii, atoms, both=True)
+    with _pose_frame(rows, library, atoms, device, device_shape_ref, reference) as f:
+        chandle = device_colour_ref(col, f.dev)
+        cw = (float(f.owner.self_overlap / chandle.self_overlap) if chandle.self_overlap > 0 else 0.0) if isinstance(colour_weight, str) else float(colour_weight)
+        rot, trans, energy, count = f.f64(f.m, 3, 3), f.f64(f.m, 3), f.f64(f.m, 16), f.i32(f.m, 6)
+        _ffi.check(f.lib.pmx_combo_overlay(f.owner.handle, chandle.handle, f.library, *f.src, *_start_motion(f, starts), f.n, float(node_radius), cw, float(ftol), int(max_iter),
+                                           rot.data_ptr(), trans.data_ptr(), energy.data_ptr(), count.data_ptr(), f.status.data_ptr(), f.stream))
     st = f.st
-    if gstatus is not None:
-        g = g_host.cpu().numpy()[:n].astype(np.int32)
-        st = np.where(g != 0, g, st).astype(np.int32)
     en, cn, R, t = f.host(energy), f.host(count).astype(np.int64), f.host(rot), f.host(trans)
-    hits = n // k
-    if starts:
-        each = en[:, 13].reshape(hits, k)
-        best = np.argmax(np.where(np.isnan(each), -np.inf, each), axis=1) if hits else np.zeros(0, np.int64)  # (the first among equals)
-        pick = np.arange(hits) * k + best
-        start, start_value = best.astype(np.int64), each.copy()
-    else:
-        pick, start, start_value = np.arange(n), np.full(n, -1, np.int64), np.zeros((n, 0))
+    pick, start, start_value = _pick_start(en[:, 13], starts)
     return ComboOverlay(rotation=R[pick].copy(), translation=t[pick].copy(), overlap_start=en[pick, 0], overlap=en[pick, 1], self_overlap=en[pick, 2],
                         reference_overlap=en[pick, 3], tanimoto_start=en[pick, 4], tanimoto=en[pick, 5], angle=en[pick, 14], shift=en[pick, 15], iterations=cn[pick, 0],
                         accepted=cn[pick, 1], stop=cn[pick, 2], n_points=cn[pick, 3], start=start, start_tanimoto=start_value, status=st[pick],

@@ -315,6 +315,38 @@ def test_rows_the_atom_store_has_nothing_for():
     assert np.array_equal(by_points.rotation[0], out.rotation[0]) and by_points.combo[0] == out.combo[0] == out.combo[3]
 
 
+@pytest.mark.parametrize("n", [1, 4, 5])  # a lone row, a full block, a block and a tail
+def test_the_atom_store_is_the_same_atoms_as_points(n):
+    """Rows whose shape points the store gathers on the device, and the same rows with the same atoms and Bondi radii as `points` /
+    `point_radii`: the same bits in every field, from the given motions and from the four starts. A row the store has no atoms for is
+    not OK in the store's call (as points it is an OK row without a point, so it is left out of the comparison)."""
+    from pharmaconet_amd.atoms import PackedAtoms
+    from pharmaconet_amd.engine import combo_overlay
+    from pharmaconet_amd.pocket import atomic_number_radii
+
+    name = "f63"
+    c = combo_cases.case(name)
+    lib, _ = combo_cases.library(name)
+    rng = np.random.default_rng(6)
+    zs = [np.full(9, 6), np.zeros(0, np.int64), np.array([8, 6, 7, 6, 16])]
+    ps = [rng.normal(size=(9, 2, 3)).astype(np.float32) + 2.0, np.zeros((0, 2, 3), np.float32), rng.normal(size=(5, 2, 3)).astype(np.float32) + 2.0]
+    store = PackedAtoms.from_arrays(zs, ps)
+    three = lib.select([3, 5, 7])
+    idx, cf = np.array([0, 1, 2, 0, 2][:n]), np.array([1, 1, 0, 0, 1][:n])  # (ligand 1: no atoms)
+    pts = [ps[i][:, k] for i, k in zip(idx, cf)]
+    rad = [np.asarray(atomic_number_radii(zs[i]), np.float32) for i in idx]
+    bad = idx == 1
+    for starts, motion in ((0, dict(rotation=[EYE] * n, translation=[c["t"][3]] * n)), (4, {})):
+        by_store = combo_overlay(case_ref(name), three, idx, cf, atoms=store, starts=starts, colour_weight=1.0, **motion)
+        by_points = combo_overlay(case_ref(name), three, idx, cf, points=pts, point_radii=rad, starts=starts, colour_weight=1.0, **motion)
+        assert len(by_store) == len(by_points) == n and (by_store.status[~bad] == 0).all() and (by_store.n_points[~bad] == [len(p) for p, b in zip(pts, bad) if not b]).all(), starts
+        for f in FIELDS:
+            assert np.array_equal(getattr(by_store, f)[~bad], getattr(by_points, f)[~bad], equal_nan=True), (starts, f)
+        assert (by_store.status[bad] == 1).all() and (by_store.stop[bad] == -1).all() and (by_store.n_points[bad] == 0).all(), starts
+        assert np.isnan(by_store.rotation[bad]).all() and np.isnan(by_store.translation[bad]).all() and all(np.isnan(getattr(by_store, f)[bad]).all() for f in FLOATS), starts
+        assert by_store.start_tanimoto.shape == (n, starts) and (np.isnan(by_store.start_tanimoto[bad]).all() if starts else True)
+
+
 def test_the_hosts_refusals_and_no_rows():
     import torch
 
