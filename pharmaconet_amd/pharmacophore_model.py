@@ -150,6 +150,55 @@ def _flatten_state(state: dict[str, Any]) -> FlatModel:
     )
 
 
+def _one_packed(ligand, what: str):
+    """`ligand` (anything `library.as_packed_library` accepts) as a packed library of the one ligand that `what`, a one-ligand call, takes."""
+    from .library import as_packed_library
+
+    packed = as_packed_library(ligand)
+    if len(packed) != 1:
+        raise ValueError(f"{what} takes exactly one ligand")
+    return packed
+
+
+def _outside_limits(packed) -> ValueError:
+    n, c, _ = packed.header(0)
+    return ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+
+
+def _row(result, i: int, *groups) -> dict:
+    """Row i of an engine result as a dict: `groups` are (type, "field names") in the order of the keys - `float`, `int` or `bool` for a
+    scalar of that type, None for the row's array as it is."""
+    return {f: getattr(result, f)[i] if cast is None else cast(getattr(result, f)[i]) for cast, names in groups for f in names.split()}
+
+
+def _pose_fields(pose: dict) -> dict:
+    """What every call made of `scoring_pose` hands on from it."""
+    return {f: pose[f] for f in ("conformer", "key", "rotation", "translation", "rmsd")}
+
+
+def _points_of(ligand, conformers, level: str | None = None, packed=None):
+    """(level, the keyword arguments that name the points of one row per conformer of `conformers` for the posed-row calls): the ligand's
+    heavy atoms with Bondi radii ("atoms") where it has them, its record's pharmacophore nodes ("nodes") otherwise - or as `level` says."""
+    if level == "atoms" or (level is None and getattr(ligand, "atom_positions", None) is not None):
+        from .engine import _heavy_atoms
+
+        points, radii = _heavy_atoms([ligand] * len(conformers), conformers)
+        return "atoms", dict(points=points, point_radii=radii)
+    if packed is None:
+        from .library import as_packed_library
+
+        packed = as_packed_library(ligand)
+    return "nodes", dict(library=packed, indices=[0] * len(conformers), conformers=conformers)
+
+
+def _posed(result, row: int, ligand, packed, c: int, ok: bool):
+    """(positions, node_positions) of conformer `c` under the motion of `result`'s row: the molecule's atoms (None for a packed record, which
+    holds nodes, not atoms) and the record's nodes; both None where the row is not `ok`."""
+    atoms = getattr(ligand, "atom_positions", None)  # [n_atoms, C, 3] of a `Ligand` / `LigandFeatures`
+    positions = result.transform(row, np.asarray(atoms, dtype=np.float64)[:, c]) if ok and atoms is not None else None
+    return positions, (result.transform(row, packed.unpack(0)["xyz"][:, :, c].astype(np.float64)) if ok else None)
+
+
 class PharmacophoreModel:
     """Pickle-friendly pharmacophore model (`pharmacophore_model.py:50-58`)."""
 
@@ -375,78 +424,62 @@ class PharmacophoreModel:
         (the key of the leaf that reaches each conformer's maximum), `pairs` (the best conformer's match, readable). Takes what
         `_scoring` takes. With `require` / `exclude` (see `engine.explain`) all of it is over the qualifying leaves: the constrained score."""
         from .engine import explain
-        from .library import as_packed_library
 
-        packed = as_packed_library(ligand)
-        if len(packed) != 1:
-            raise ValueError("scoring_detail takes exactly one ligand")
+        packed = _one_packed(ligand, "scoring_detail")
         ex = explain(self, packed, [0], weights=weights, require=require, exclude=exclude)
         if int(ex.status[0]) != 0:
-            n, c, _ = packed.header(0)
-            raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+            raise _outside_limits(packed)
         cm = ex.conf_max[0]
         n, c, ncl = packed.header(0)
         score = 0 if (ncl == 0 and n == 0 and c > 0) else float(np.mean(cm))  # (graph_match.py:95-96 returns the int 0)
         return dict(score=score, max=float(cm.max()) if cm.size else 0.0, conf_max=cm, best_conformer=int(ex.best_conformer[0]),
                     levels=ex.levels[0], match=ex.match[0], pairs=ex.pairs(0, self, packed))
 
-    def scoring_attribution(self, ligand, weights: dict[str, float] | None = None, conformer: int | None = None, key=None) -> dict:
-        """Which nodes of one ligand carry a leaf's total (`engine.attribute`): by default the explaining leaf of the best conformer, else
-        `conformer` and / or `key` (a model cluster or -1 per tree level). `conformer`, `key`, `levels`, `total`, `node` (share per node of the
-        packed record), `entry`, `fails` and `status` (0, or 4 when the key is not a leaf of the ligand's tree for that conformer: total
-        and node are then NaN, `entry` says which pair stands in the way). Takes what `_scoring` takes."""
-        from .engine import attribute, explain
-        from .library import as_packed_library
-
-        packed = as_packed_library(ligand)
-        if len(packed) != 1:
-            raise ValueError("scoring_attribution takes exactly one ligand")
+    def _leaf(self, packed, weights, conformer, key):
+        """(conformer, key) of a one-ligand call: what the caller gave, else the best conformer and that conformer's explaining leaf (`engine.explain`)."""
         if conformer is None or key is None:
+            from .engine import explain
+
             ex = explain(self, packed, [0], weights=weights)
             if int(ex.status[0]) != 0:
-                n, c, _ = packed.header(0)
-                raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+                raise _outside_limits(packed)
             if conformer is None:
                 conformer = int(ex.best_conformer[0])
             if key is None:
                 if not 0 <= int(conformer) < ex.match[0].shape[0]:
                     raise ValueError(f"the ligand has {ex.match[0].shape[0]} conformers")
                 key = ex.match[0][int(conformer)]
-        at = attribute(self, packed, [0], [int(conformer)], [key], weights=weights)
-        if int(at.status[0]) == 1:
-            n, c, _ = packed.header(0)
-            raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
-        return dict(conformer=int(conformer), key=np.asarray(key, dtype=np.int64), levels=at.levels[0], total=float(at.total[0]), node=at.node[0],
-                    entry=at.entry[0], fails=at.fails[0], status=int(at.status[0]))
+        return int(conformer), key
+
+    def _leaf_call(self, call, ligand, what, weights, conformer, key):
+        """(packed, conformer, key, the one row of `call` - `attribute`, `hotspots` or `align` - at that leaf) for `ligand`."""
+        packed = _one_packed(ligand, what)
+        conformer, key = self._leaf(packed, weights, conformer, key)
+        out = call(self, packed, [0], [conformer], [key], weights=weights)
+        if int(out.status[0]) == 1:
+            raise _outside_limits(packed)
+        return packed, conformer, np.asarray(key, dtype=np.int64), out
+
+    def scoring_attribution(self, ligand, weights: dict[str, float] | None = None, conformer: int | None = None, key=None) -> dict:
+        """Which nodes of one ligand carry a leaf's total (`engine.attribute`): by default the explaining leaf of the best conformer, else
+        `conformer` and / or `key` (a model cluster or -1 per tree level). `conformer`, `key`, `levels`, `total`, `node` (share per node of the
+        packed record), `entry`, `fails` and `status` (0, or 4 when the key is not a leaf of the ligand's tree for that conformer: total
+        and node are then NaN, `entry` says which pair stands in the way). Takes what `_scoring` takes."""
+        from .engine import attribute
+
+        _, conformer, key, at = self._leaf_call(attribute, ligand, "scoring_attribution", weights, conformer, key)
+        return dict(conformer=conformer, key=key, **_row(at, 0, (None, "levels"), (float, "total"), (None, "node entry fails"), (int, "status")))
 
     def scoring_hotspots(self, ligand, weights: dict[str, float] | None = None, conformer: int | None = None, key=None) -> dict:
         """Which model nodes - hotspots of the pocket - carry a leaf's total for one ligand (`engine.hotspots`): by default the explaining leaf
         of the best conformer, else `conformer` and / or `key` (a model cluster or -1 per tree level). `conformer`, `key`, `levels`, `total`,
         `share` (per model node), `terms`, `passes`, `fingerprint` (uint64 [4]), `nodes` (the engaged model nodes) and `status` (0, or 4 when
         the key is not a leaf of the ligand's tree for that conformer: total and share are then NaN). Takes what `_scoring` takes."""
-        from .engine import explain, hotspots
-        from .library import as_packed_library
+        from .engine import hotspots
 
-        packed = as_packed_library(ligand)
-        if len(packed) != 1:
-            raise ValueError("scoring_hotspots takes exactly one ligand")
-        if conformer is None or key is None:
-            ex = explain(self, packed, [0], weights=weights)
-            if int(ex.status[0]) != 0:
-                n, c, _ = packed.header(0)
-                raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
-            if conformer is None:
-                conformer = int(ex.best_conformer[0])
-            if key is None:
-                if not 0 <= int(conformer) < ex.match[0].shape[0]:
-                    raise ValueError(f"the ligand has {ex.match[0].shape[0]} conformers")
-                key = ex.match[0][int(conformer)]
-        hs = hotspots(self, packed, [0], [int(conformer)], [key], weights=weights)
-        if int(hs.status[0]) == 1:
-            n, c, _ = packed.header(0)
-            raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
-        return dict(conformer=int(conformer), key=np.asarray(key, dtype=np.int64), levels=hs.levels[0], total=float(hs.total[0]), share=hs.share[0],
-                    terms=hs.terms[0], passes=hs.passes[0], fingerprint=hs.fingerprint[0], nodes=hs.nodes(0), status=int(hs.status[0]))
+        _, conformer, key, hs = self._leaf_call(hotspots, ligand, "scoring_hotspots", weights, conformer, key)
+        return dict(conformer=conformer, key=key, **_row(hs, 0, (None, "levels"), (float, "total"), (None, "share terms passes fingerprint")), nodes=hs.nodes(0),
+                    status=int(hs.status[0]))
 
     def scoring_pose(self, ligand, weights: dict[str, float] | None = None, conformer: int | None = None, key=None) -> dict:
         """One ligand put into the pocket (`engine.align`): by default its best conformer under the explaining leaf's match, else `conformer`
@@ -454,35 +487,13 @@ class PharmacophoreModel:
         conformer's atom positions after the fit (None when `ligand` is a packed record, which holds nodes, not atoms), `node_positions` [n, 3]
         those of the record's nodes; `rotation`, `translation`, `rmsd`, `rmsd_nodes`, `weight`, `sse`, `scale`, `gap`, `node`, `n_nodes`,
         `n_pairs`, `levels` and `status` as `engine.Alignment` has them, with `conformer` and `key`. Takes what `_scoring` takes."""
-        from .engine import align, explain
-        from .library import as_packed_library
+        from .engine import align
 
-        packed = as_packed_library(ligand)
-        if len(packed) != 1:
-            raise ValueError("scoring_pose takes exactly one ligand")
-        if conformer is None or key is None:
-            ex = explain(self, packed, [0], weights=weights)
-            if int(ex.status[0]) != 0:
-                n, c, _ = packed.header(0)
-                raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
-            if conformer is None:
-                conformer = int(ex.best_conformer[0])
-            if key is None:
-                if not 0 <= int(conformer) < ex.match[0].shape[0]:
-                    raise ValueError(f"the ligand has {ex.match[0].shape[0]} conformers")
-                key = ex.match[0][int(conformer)]
-        al = align(self, packed, [0], [int(conformer)], [key], weights=weights)
-        if int(al.status[0]) == 1:
-            n, c, _ = packed.header(0)
-            raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
-        ok = int(al.status[0]) == 0
-        atoms = getattr(ligand, "atom_positions", None)  # [n_atoms, C, 3] of a `Ligand` / `LigandFeatures`
-        positions = al.transform(0, np.asarray(atoms, dtype=np.float64)[:, int(conformer)]) if ok and atoms is not None else None
-        node_positions = al.transform(0, packed.unpack(0)["xyz"][:, :, int(conformer)].astype(np.float64)) if ok else None
-        return dict(conformer=int(conformer), key=np.asarray(key, dtype=np.int64), positions=positions, node_positions=node_positions,
-                    rotation=al.rotation[0], translation=al.translation[0], rmsd=float(al.rmsd[0]), rmsd_nodes=float(al.rmsd_nodes[0]),
-                    weight=float(al.weight[0]), sse=float(al.sse[0]), scale=float(al.scale[0]), gap=float(al.gap[0]), node=al.node[0],
-                    n_nodes=int(al.n_nodes[0]), n_pairs=int(al.n_pairs[0]), levels=al.levels[0], status=int(al.status[0]))
+        packed, conformer, key, al = self._leaf_call(align, ligand, "scoring_pose", weights, conformer, key)
+        positions, node_positions = _posed(al, 0, ligand, packed, conformer, int(al.status[0]) == 0)
+        return dict(conformer=conformer, key=key, positions=positions, node_positions=node_positions,
+                    **_row(al, 0, (None, "rotation translation"), (float, "rmsd rmsd_nodes weight sse scale gap"), (None, "node"), (int, "n_nodes n_pairs"), (None, "levels"),
+                           (int, "status")))
 
     def scoring_pose_search(self, ligand, modes: int = 4, weights: dict[str, float] | None = None, pocket=None, level: str = "nodes", **kw) -> dict:
         """One ligand put into the pocket in the conformer and binding mode that fits it (`engine.pose_search`), the one-ligand form beside
@@ -495,11 +506,8 @@ class PharmacophoreModel:
         `engine.pose_search`. Takes what `_scoring` takes. With `level="atoms"` the search checks the ligand's heavy atoms instead of its nodes
         (`engine.pose_search(atoms=...)`; `ligand` must then carry its atoms: a `Ligand` / `LigandFeatures`); the result says which `level` it is."""
         from .engine import pose_search
-        from .library import as_packed_library
 
-        packed = as_packed_library(ligand)
-        if len(packed) != 1:
-            raise ValueError("scoring_pose_search takes exactly one ligand")
+        packed = _one_packed(ligand, "scoring_pose_search")
         if level not in ("nodes", "atoms"):
             raise ValueError("level: 'nodes' or 'atoms'")
         if level == "atoms":
@@ -511,17 +519,12 @@ class PharmacophoreModel:
             kw = dict(kw, atoms=PackedAtoms.for_library([mol], packed))
         ps = pose_search(self, packed, self.pocket_atoms() if pocket is None else pocket, [0], modes=modes, weights=weights, **kw)
         if int(ps.status[0]) != 0:
-            n, c, _ = packed.header(0)
-            raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+            raise _outside_limits(packed)
         al, rep, c = ps.alignment(), ps.report(), int(ps.conformer[0])
-        ok = c >= 0
-        atoms = getattr(ligand, "atom_positions", None)
-        positions = al.transform(0, np.asarray(atoms, dtype=np.float64)[:, c]) if ok and atoms is not None else None
-        node_positions = al.transform(0, packed.unpack(0)["xyz"][:, :, c].astype(np.float64)) if ok else None
-        return dict(conformer=c, mode=int(ps.mode[0]), key=ps.key[0], passes=bool(ps.passes[0]), n_candidates=int(ps.n_candidates[0]), n_passing=int(ps.n_passing[0]),
-                    value=float(ps.value[0]), fraction=float(ps.fraction[0]), positions=positions, node_positions=node_positions, rotation=al.rotation[0],
-                    translation=al.translation[0], rmsd=float(al.rmsd[0]), rmsd_nodes=float(al.rmsd_nodes[0]), n_nodes=int(al.n_nodes[0]),
-                    n_clashing=int(rep.n_clashing[0]), overlap=float(rep.overlap[0]), clearance=float(rep.clearance[0]), status=int(al.status[0]), level=ps.level)
+        positions, node_positions = _posed(al, 0, ligand, packed, c, c >= 0)
+        return dict(conformer=c, **_row(ps, 0, (int, "mode"), (None, "key"), (bool, "passes"), (int, "n_candidates n_passing"), (float, "value fraction")),
+                    positions=positions, node_positions=node_positions, **_row(al, 0, (None, "rotation translation"), (float, "rmsd rmsd_nodes"), (int, "n_nodes")),
+                    **_row(rep, 0, (int, "n_clashing"), (float, "overlap clearance")), status=int(al.status[0]), level=ps.level)
 
     def scoring_clash(self, ligand, conformer: int | None = None, key=None, weights: dict[str, float] | None = None, pocket=None, **kw) -> dict:
         """One ligand fitted into the pocket (`scoring_pose`) and its pose checked against the protein's atoms (`engine.clashes`): the ligand's own
@@ -531,27 +534,14 @@ class PharmacophoreModel:
         `n_pairs`, `n_contacts`, `worst` (point, atom), `worst_atom` (its label), `point_penetration`, `point_atom`, `contact_fingerprint`,
         `residues` (the touched residues), `ok` and `status`. Further arguments (`tolerance`, `contact`, `node_radius`) as `engine.clashes`."""
         from .engine import clashes
-        from .library import as_packed_library
-        from .pocket import atomic_number_radii
 
         pocket = self.pocket_atoms() if pocket is None else pocket
         pose = self.scoring_pose(ligand, weights=weights, conformer=conformer, key=key)
-        c = pose["conformer"]
-        atoms = getattr(ligand, "atom_positions", None)
-        if atoms is not None:
-            from .engine import _atomic_numbers
-
-            z = _atomic_numbers(ligand)
-            pos = np.asarray(atoms, dtype=np.float32)
-            rep = clashes(pocket, rotation=[pose["rotation"]], translation=[pose["translation"]], points=[pos[z > 1, c] if 0 <= c < pos.shape[1] else np.zeros((0, 3))],
-                          point_radii=[atomic_number_radii(z[z > 1]) if 0 <= c < pos.shape[1] else np.zeros(0)], **kw)
-        else:
-            rep = clashes(pocket, library=as_packed_library(ligand), indices=[0], conformers=[c], rotation=[pose["rotation"]], translation=[pose["translation"]], **kw)
-        return dict(conformer=c, key=pose["key"], rotation=pose["rotation"], translation=pose["translation"], rmsd=pose["rmsd"],
-                    level="atoms" if atoms is not None else "nodes", clearance=float(rep.clearance[0]), overlap=float(rep.overlap[0]), n_points=int(rep.n_points[0]),
-                    n_clashing=int(rep.n_clashing[0]), n_pairs=int(rep.n_pairs[0]), n_contacts=int(rep.n_contacts[0]), worst=tuple(int(v) for v in rep.worst[0]),
-                    worst_atom=rep.atom_label(0, pocket), point_penetration=rep.point_penetration[0], point_atom=rep.point_atom[0],
-                    contact_fingerprint=rep.contact_fingerprint[0], residues=rep.residues(0, pocket), ok=bool(rep.ok()[0]), status=int(rep.status[0]))
+        level, source = _points_of(ligand, [pose["conformer"]])
+        rep = clashes(pocket, rotation=[pose["rotation"]], translation=[pose["translation"]], **source, **kw)
+        return dict(_pose_fields(pose), level=level, **_row(rep, 0, (float, "clearance overlap"), (int, "n_points n_clashing n_pairs n_contacts")),
+                    worst=tuple(int(v) for v in rep.worst[0]), worst_atom=rep.atom_label(0, pocket), **_row(rep, 0, (None, "point_penetration point_atom contact_fingerprint")),
+                    residues=rep.residues(0, pocket), ok=bool(rep.ok()[0]), status=int(rep.status[0]))
 
     def scoring_refine(self, ligand, conformer: int | None = None, key=None, weights: dict[str, float] | None = None, pocket=None, **kw) -> dict:
         """One ligand fitted into the pocket (`scoring_pose`) and its pose moved out of the protein's atoms (`engine.refine`), the one-ligand
@@ -561,26 +551,30 @@ class PharmacophoreModel:
         `anchor_rmsd`, `angle`, `shift`, `iterations`, `accepted`, `stop`, `n_pairs`, `status`, and `ok`: whether the refined pose passes
         `engine.clashes` at the same tolerance. Further arguments (`restraint`, `max_iter`, `ftol`, `tolerance`, `node_radius`) as
         `engine.refine`."""
-        from .engine import _heavy_atoms, clashes, refine
-        from .library import as_packed_library
+        from .engine import clashes, refine
 
         pocket = self.pocket_atoms() if pocket is None else pocket
         pose = self.scoring_pose(ligand, weights=weights, conformer=conformer, key=key)
-        c = pose["conformer"]
-        atoms = getattr(ligand, "atom_positions", None)
-        if atoms is not None:
-            points, radii = _heavy_atoms([ligand], [c])
-            source = dict(points=points, point_radii=radii)
-        else:
-            source = dict(library=as_packed_library(ligand), indices=[0], conformers=[c])
+        level, source = _points_of(ligand, [pose["conformer"]])
         ref = refine(pocket, rotation=[pose["rotation"]], translation=[pose["translation"]], **source, **kw)
         check = {name: kw[name] for name in ("tolerance", "node_radius", "device") if name in kw}
         rep = clashes(pocket, rotation=ref.rotation, translation=ref.translation, **source, **check)
-        return dict(conformer=c, key=pose["key"], level="atoms" if atoms is not None else "nodes", rotation=pose["rotation"], translation=pose["translation"],
-                    refined_rotation=ref.rotation[0], refined_translation=ref.translation[0], overlap_start=float(ref.overlap_start[0]), overlap=float(ref.overlap[0]),
-                    restraint_energy=float(ref.restraint_energy[0]), anchor_rmsd=float(ref.anchor_rmsd[0]), angle=float(ref.angle[0]), shift=float(ref.shift[0]),
-                    iterations=int(ref.iterations[0]), accepted=int(ref.accepted[0]), stop=int(ref.stop[0]), n_pairs=int(ref.n_pairs[0]), status=int(ref.status[0]),
-                    ok=bool(rep.ok()[0]))
+        return dict(conformer=pose["conformer"], key=pose["key"], level=level, rotation=pose["rotation"], translation=pose["translation"],
+                    refined_rotation=ref.rotation[0], refined_translation=ref.translation[0],
+                    **_row(ref, 0, (float, "overlap_start overlap restraint_energy anchor_rmsd angle shift"), (int, "iterations accepted stop n_pairs status")), ok=bool(rep.ok()[0]))
+
+    def _fitted_and_refined(self, pose, head: dict, one, refine: bool, pocket, source: dict, kw: dict) -> dict:
+        """`head` and `one(rotation, translation)`'s fields at the fitted motion of `pose`; with `refine` the same fields under `refined` at the
+        motion `engine.refine` ends at from there (the points `source` names; `kw` its further arguments), with that motion and `stop`."""
+        from .engine import refine as refine_poses
+
+        out = dict(head, **one(pose["rotation"], pose["translation"]))
+        if refine:
+            ref = refine_poses(self.pocket_atoms() if pocket is None else pocket, rotation=[pose["rotation"]], translation=[pose["translation"]], **source, **kw)
+            out["refined"] = dict(refined_rotation=ref.rotation[0], refined_translation=ref.translation[0], stop=int(ref.stop[0]), **one(ref.rotation[0], ref.translation[0]))
+        elif kw:
+            raise ValueError(f"{sorted(kw)}: arguments of the refinement, which is off (refine=True)")
+        return out
 
     def scoring_shape(self, ligand, reference, conformer: int | None = None, key=None, refine: bool = False, weights: dict[str, float] | None = None, pocket=None,
                       node_radius: float = 1.0, cover: float = 2.0, **kw) -> dict:
@@ -593,36 +587,18 @@ class PharmacophoreModel:
         and `status`. With `refine`, the pose is also moved out of the protein's atoms (`engine.refine` on the same points; `pocket`
         defaults to `pocket_atoms()`, further arguments as `engine.refine`) and `refined` holds the same fields for the refined motion,
         with `refined_rotation`, `refined_translation` and `stop`."""
-        from .engine import _heavy_atoms, refine as refine_poses, shape
-        from .library import as_packed_library
+        from .engine import shape
 
         pose = self.scoring_pose(ligand, weights=weights, conformer=conformer, key=key)
-        c = pose["conformer"]
-        atoms = getattr(ligand, "atom_positions", None)
-        if atoms is not None:
-            points, radii = _heavy_atoms([ligand], [c])
-            source = dict(points=points, point_radii=radii)
-        else:
-            source = dict(library=as_packed_library(ligand), indices=[0], conformers=[c])
+        level, source = _points_of(ligand, [pose["conformer"]])
+        source["node_radius"] = node_radius
 
         def one(rotation, translation):
-            sh = shape(reference, rotation=[rotation], translation=[translation], node_radius=node_radius, cover=cover, **source)
-            return dict(overlap=float(sh.overlap[0]), self_overlap=float(sh.self_overlap[0]), reference_overlap=float(sh.reference_overlap[0]), tanimoto=float(sh.tanimoto[0]),
-                        reference_fraction=float(sh.reference_fraction[0]), fit_fraction=float(sh.fit_fraction[0]), rms_to_reference=float(sh.rms_to_reference[0]),
-                        rms_from_reference=float(sh.rms_from_reference[0]), rmsd_in_order=float(sh.rmsd_in_order[0]), n_points=int(sh.n_points[0]),
-                        n_covered=int(sh.n_covered[0]), n_reference_covered=int(sh.n_reference_covered[0]), point_distance=sh.point_distance[0],
-                        point_reference_atom=sh.point_reference_atom[0], reference_distance=sh.reference_distance[0], reference_point=sh.reference_point[0],
-                        status=int(sh.status[0]))
+            sh = shape(reference, rotation=[rotation], translation=[translation], cover=cover, **source)
+            return _row(sh, 0, (float, "overlap self_overlap reference_overlap tanimoto reference_fraction fit_fraction rms_to_reference rms_from_reference rmsd_in_order"),
+                        (int, "n_points n_covered n_reference_covered"), (None, "point_distance point_reference_atom reference_distance reference_point"), (int, "status"))
 
-        out = dict(conformer=c, key=pose["key"], rotation=pose["rotation"], translation=pose["translation"], rmsd=pose["rmsd"],
-                   level="atoms" if atoms is not None else "nodes", **one(pose["rotation"], pose["translation"]))
-        if refine:
-            ref = refine_poses(self.pocket_atoms() if pocket is None else pocket, rotation=[pose["rotation"]], translation=[pose["translation"]], node_radius=node_radius,
-                               **source, **kw)
-            out["refined"] = dict(refined_rotation=ref.rotation[0], refined_translation=ref.translation[0], stop=int(ref.stop[0]), **one(ref.rotation[0], ref.translation[0]))
-        elif kw:
-            raise ValueError(f"{sorted(kw)}: arguments of the refinement, which is off (refine=True)")
-        return out
+        return self._fitted_and_refined(pose, dict(_pose_fields(pose), level=level), one, refine, pocket, source, kw)
 
     def scoring_colour(self, ligand, reference, conformer: int | None = None, key=None, weights: dict[str, float] | None = None, cover: float = 2.0) -> dict:
         """One ligand fitted into the pocket (`scoring_pose`) and its pharmacophore nodes compared with a known ligand's typed features
@@ -635,13 +611,11 @@ class PharmacophoreModel:
         from .library import as_packed_library
 
         pose = self.scoring_pose(ligand, weights=weights, conformer=conformer, key=key)
-        c = pose["conformer"]
-        rep = colour(reference, as_packed_library(ligand), [0], [c], [pose["rotation"]], [pose["translation"]], cover=cover)
-        scalars = ("overlap", "self_overlap", "reference_overlap", "tanimoto", "reference_fraction", "fit_fraction", "rms_matched")
-        counts = ("n_nodes", "n_matched", "n_reference_features", "n_reference_matched", "status")
-        lists = ("node_overlap", "node_distance", "node_feature", "feature_distance", "feature_node", "matched_fingerprint")
-        return dict(conformer=c, key=pose["key"], rotation=pose["rotation"], translation=pose["translation"], rmsd=pose["rmsd"], by_type=rep.by_type(0),
-                    **{f: float(getattr(rep, f)[0]) for f in scalars}, **{f: int(getattr(rep, f)[0]) for f in counts}, **{f: getattr(rep, f)[0] for f in lists})
+        rep = colour(reference, as_packed_library(ligand), [0], [pose["conformer"]], [pose["rotation"]], [pose["translation"]], cover=cover)
+        return dict(_pose_fields(pose), by_type=rep.by_type(0),
+                    **_row(rep, 0, (float, "overlap self_overlap reference_overlap tanimoto reference_fraction fit_fraction rms_matched"),
+                           (int, "n_nodes n_matched n_reference_features n_reference_matched status"),
+                           (None, "node_overlap node_distance node_feature feature_distance feature_node matched_fingerprint")))
 
     def scoring_overlay(self, ligand, reference, starts: int = 4, level: str = "atoms", weights: dict[str, float] | None = None, **kw) -> dict:
         """One ligand overlaid on a known ligand (`engine.overlay`; `reference` a `shape.ReferenceLigand` in the pocket's frame), the
@@ -652,18 +626,14 @@ class PharmacophoreModel:
         `positions` (all the molecule's atoms, posed; None for a packed record), `node_positions`, `overlap_start`, `overlap`,
         `self_overlap`, `reference_overlap`, `tanimoto_start`, `tanimoto`, `angle`, `shift`, `iterations`, `accepted`, `stop`, `n_points`
         and `status`. Further arguments (`node_radius`, `ftol`, `max_iter`) as `engine.overlay`."""
-        from .engine import _heavy_atoms, overlay
-        from .library import as_packed_library
+        from .engine import overlay
 
         if level not in ("nodes", "atoms"):
             raise ValueError("level: 'nodes' or 'atoms'")
         if starts not in (0, 4):
             raise ValueError("starts: 0 or 4")
-        packed = as_packed_library(ligand)
-        if len(packed) != 1:
-            raise ValueError("scoring_overlay takes exactly one ligand")
-        atoms = getattr(ligand, "atom_positions", None)
-        if level == "atoms" and atoms is None:
+        packed = _one_packed(ligand, "scoring_overlay")
+        if level == "atoms" and getattr(ligand, "atom_positions", None) is None:
             raise ValueError("scoring_overlay(level='atoms'): the ligand has no atoms (a packed record); give the molecule, or level='nodes'")
         if starts:
             conf = list(range(int(packed.header(0)[1])))
@@ -672,22 +642,13 @@ class PharmacophoreModel:
             pose = self.scoring_pose(ligand, weights=weights)
             conf = [pose["conformer"]]
             motion = dict(rotation=[pose["rotation"]], translation=[pose["translation"]])
-        if level == "atoms":
-            points, radii = _heavy_atoms([ligand] * len(conf), conf)
-            source = dict(points=points, point_radii=radii)
-        else:
-            source = dict(library=packed, indices=[0] * len(conf), conformers=conf)
-        ov = overlay(reference, starts=starts, **source, **motion, **kw)
+        ov = overlay(reference, starts=starts, **_points_of(ligand, conf, level, packed)[1], **motion, **kw)
         value = np.where(np.isnan(ov.tanimoto), -np.inf, ov.tanimoto)
         r = int(np.argmax(value))  # (the first among equals)
         c = int(conf[r])
-        ok = int(ov.status[r]) == 0
-        positions = ov.transform(r, np.asarray(atoms, dtype=np.float64)[:, c]) if ok and atoms is not None else None
-        node_positions = ov.transform(r, packed.unpack(0)["xyz"][:, :, c].astype(np.float64)) if ok else None
+        positions, node_positions = _posed(ov, r, ligand, packed, c, int(ov.status[r]) == 0)
         return dict(conformer=c, start=int(ov.start[r]), level=level, rotation=ov.rotation[r], translation=ov.translation[r], positions=positions, node_positions=node_positions,
-                    overlap_start=float(ov.overlap_start[r]), overlap=float(ov.overlap[r]), self_overlap=float(ov.self_overlap[r]), reference_overlap=float(ov.reference_overlap[r]),
-                    tanimoto_start=float(ov.tanimoto_start[r]), tanimoto=float(ov.tanimoto[r]), angle=float(ov.angle[r]), shift=float(ov.shift[r]),
-                    iterations=int(ov.iterations[r]), accepted=int(ov.accepted[r]), stop=int(ov.stop[r]), n_points=int(ov.n_points[r]), status=int(ov.status[r]))
+                    **_row(ov, r, (float, "overlap_start overlap self_overlap reference_overlap tanimoto_start tanimoto angle shift"), (int, "iterations accepted stop n_points status")))
 
     def scoring_pose_fit(self, ligand, conformer: int | None = None, key=None, refine: bool = False, free: bool = False, weights: dict[str, float] | None = None,
                          pocket=None, centers=None, sigmas=None, **kw) -> dict:
@@ -699,7 +660,7 @@ class PharmacophoreModel:
         (`engine.refine` on the record's nodes; `pocket` defaults to `pocket_atoms()`, further arguments as `engine.refine`) and `refined`
         holds the same fields for the refined motion, with `refined_rotation`, `refined_translation` and `stop`: what the refinement cost
         is `fraction` against `refined["fraction"]`."""
-        from .engine import pose_fit, refine as refine_poses
+        from .engine import pose_fit
         from .library import as_packed_library
 
         packed = as_packed_library(ligand)
@@ -708,19 +669,10 @@ class PharmacophoreModel:
 
         def one(rotation, translation):
             pf = pose_fit(self, packed, [0], [c], [rotation], [translation], keys=keys, weights=weights, centers=centers, sigmas=sigmas)
-            return dict(fit=float(pf.fit[0]), ideal=float(pf.ideal[0]), fraction=float(pf.fraction[0]), best_fit=float(pf.best_fit[0]),
-                        best_fraction=float(pf.best_fraction[0]), n_nodes=int(pf.n_nodes[0]), n_pairs=int(pf.n_pairs[0]), n_in_place=int(pf.n_in_place[0]),
-                        n_passing=int(pf.n_passing[0]), node_fit=pf.node_fit[0], node_z2=pf.node_z2[0], node_target=pf.node_target[0], hotspot_z2=pf.hotspot_z2[0],
-                        hotspot_node=pf.hotspot_node[0], occupied=pf.occupied(0), coverage=pf.coverage(0, self, weights), status=int(pf.status[0]))
+            return dict(_row(pf, 0, (float, "fit ideal fraction best_fit best_fraction"), (int, "n_nodes n_pairs n_in_place n_passing"),
+                             (None, "node_fit node_z2 node_target hotspot_z2 hotspot_node")), occupied=pf.occupied(0), coverage=pf.coverage(0, self, weights), status=int(pf.status[0]))
 
-        out = dict(conformer=c, key=pose["key"], rotation=pose["rotation"], translation=pose["translation"], rmsd=pose["rmsd"], **one(pose["rotation"], pose["translation"]))
-        if refine:
-            ref = refine_poses(self.pocket_atoms() if pocket is None else pocket, library=packed, indices=[0], conformers=[c], rotation=[pose["rotation"]],
-                               translation=[pose["translation"]], **kw)
-            out["refined"] = dict(refined_rotation=ref.rotation[0], refined_translation=ref.translation[0], stop=int(ref.stop[0]), **one(ref.rotation[0], ref.translation[0]))
-        elif kw:
-            raise ValueError(f"{sorted(kw)}: arguments of the refinement, which is off (refine=True)")
-        return out
+        return self._fitted_and_refined(pose, _pose_fields(pose), one, refine, pocket, dict(library=packed, indices=[0], conformers=[c]), kw)
 
     def explain(self, library, indices, weights: dict[str, float] | None = None, **kwargs):
         """Per-conformer maxima and explaining matches of library ligands `indices` (`engine.explain`)."""
@@ -733,15 +685,11 @@ class PharmacophoreModel:
         [modes, C] and `match` [modes, C, nl] (mode 0 is `scoring_detail`'s `conf_max` and `match`), `count` [C] the modes found, `best_conformer`,
         `levels`, and `pairs`: per mode found at the best conformer its readable match. Takes what `_scoring` takes."""
         from .engine import explain_modes
-        from .library import as_packed_library
 
-        packed = as_packed_library(ligand)
-        if len(packed) != 1:
-            raise ValueError("scoring_modes takes exactly one ligand")
+        packed = _one_packed(ligand, "scoring_modes")
         ms = explain_modes(self, packed, [0], modes=modes, weights=weights, require=require, exclude=exclude)
         if int(ms.status[0]) != 0:
-            n, c, _ = packed.header(0)
-            raise ValueError(f"ligand outside the structural limits of the GPU engine (nodes={n}, conformers={c}); see include/pmx.h")
+            raise _outside_limits(packed)
         c = int(ms.best_conformer[0])
         found = int(ms.count(0)[c]) if ms.values[0].shape[1] else 0
         return dict(values=ms.values[0], match=ms.match[0], count=ms.count(0), best_conformer=c, levels=ms.levels[0],

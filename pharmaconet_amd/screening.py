@@ -23,6 +23,7 @@ from __future__ import annotations
 import argparse
 import multiprocessing
 import sys
+from functools import cached_property
 from pathlib import Path
 
 import numpy as np
@@ -182,35 +183,402 @@ def write_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarra
         print(f"warning: {int(bad.sum())} ligand(s) outside the engine's structural limits were not scored", file=sys.stderr)
 
 
+def _best_hits(scores: np.ndarray, status: np.ndarray, k: int) -> list[int]:
+    """The k best scored ligands in the order of the main CSV."""
+    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
+    return [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
+
+
+class Hits:
+    """The k explained hits of one run: what every side report of `--explain K` is written from. `main` makes it once, after the screen;
+    each of `order`, `explanation`, `poses`, the hits' atoms, `clash_report` and `refined` is computed on first use and kept, so a run
+    explains, fits, checks and refines its hits once however many reports it writes. `store` is a packed library's atom store (the hits'
+    files are read again without it); `pocket`, `clash_level`, `tolerance`, `restraint` and `max_iter` are the run's one set of arguments
+    of the clash check and the refinement. The level of a shape comparison is the caller's own (`atoms(level)`, `source(level)`)."""
+
+    def __init__(self, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, store: PackedAtoms | None = None, pocket=None,
+                 clash_level: str = "nodes", tolerance: float = 0.5, restraint: float = 0.1, max_iter: int = 32):
+        self.names, self.scores, self.status, self.model, self.lib, self.weights, self.k = names, scores, status, model, lib, weights, k
+        self.store, self.pocket, self.clash_level, self.tolerance, self.restraint, self.max_iter = store, pocket, clash_level, tolerance, restraint, max_iter
+
+    @cached_property
+    def order(self) -> list[int]:
+        """The hits as library indices, in the order of the main CSV: the command line's only ranking."""
+        return _best_hits(self.scores, self.status, self.k)
+
+    @cached_property
+    def paths(self) -> list[str]:
+        return [self.names[i] for i in self.order]
+
+    @cached_property
+    def explanation(self):
+        from .engine import explain
+
+        return explain(self.model, self.lib, self.order, weights=self.weights)
+
+    @cached_property
+    def poses(self):
+        """The fit of every explained hit's best conformer under its explaining match (`engine.align`); `rows` are the explanation's rows."""
+        return self.explanation.poses(self.model, self.lib, weights=self.weights)
+
+    @cached_property
+    def keys(self) -> list:
+        return self.explanation._own_rows(None)[2]
+
+    @cached_property
+    def _atoms(self):
+        if self.store is not None:
+            return self.store
+        from .ligand import Ligand
+
+        return [Ligand.load_from_file(self.paths[int(row)]) for row in self.poses.rows]
+
+    def atoms(self, level: str):
+        """What the posed rows' methods take as `atoms` at `level`: None at `nodes`; at `atoms` the library's store, else the hits' files, read once."""
+        return self._atoms if level == "atoms" else None
+
+    def source(self, level: str) -> dict:
+        """The keyword arguments that name the posed hits' points at `level` for the engine's row calls (`poses._pose_source`)."""
+        from .engine import _pose_source
+
+        return _pose_source(self.poses, "the explained hits", None, self.lib, self.atoms(level))[1]
+
+    @cached_property
+    def clash_report(self):
+        return self.poses.clashes(self.pocket, self.lib, atoms=self.atoms(self.clash_level), tolerance=self.tolerance)
+
+    @cached_property
+    def refined(self):
+        return self.poses.refine(self.pocket, self.lib, atoms=self.atoms(self.clash_level), tolerance=self.tolerance, restraint=self.restraint, max_iter=self.max_iter)
+
+
+# ------------------------------------------------------------------------------------------------------------- row formats
+# From result objects to text lines: nothing here calls the engine. `paths[i]` is the path of the explanation's row i.
+MOTION_COLUMNS = ",".join(f"r{i}{j}" for i in range(3) for j in range(3)) + ",tx,ty,tz"
+EXPLAIN_HEADER = "rank,path,score,best_conformer,conformer_max,matches"
+MODES_HEADER = "rank,path,mode,mode_score,fraction_of_best,matches"
+EXPLAIN_NODES_HEADER = "rank,index,path,conformer,node,node_types,ligand_cluster,model_cluster,node_score,share"
+HOTSPOTS_HEADER = "rank,path,node,type,share,fraction,engaged"
+POSES_HEADER = "rank,path,conformer,rmsd,rmsd_nodes,fitted_nodes," + MOTION_COLUMNS
+POSE_SEARCH_HEADER = "rank,path,conformer,mode,passes,candidates,passing,mode_score,fraction_of_best,clashing,overlap,clearance,rmsd,rmsd_nodes,fitted_nodes," + MOTION_COLUMNS
+CLASHES_HEADER = "rank,path,conformer,level,points,clashing,pairs,clearance,overlap,contacts,worst_point,worst_atom,residues"
+REFINE_HEADER = ("rank,path,conformer,level,pairs_before,overlap_before,pairs_after,overlap_after,clearance_after,clashing_after,anchor_rmsd,angle_deg,shift,iterations,stop,"
+                 + MOTION_COLUMNS)
+POSE_FIT_HEADER = "rank,path,conformer,stage,fitted_nodes,pairs,in_place,passing,fit,ideal,fraction,best_fit,best_fraction,occupied_nodes"
+POSE_SHAPE_HEADER = ("rank,path,conformer,stage,level,points,covered,reference_atoms,reference_covered,overlap,tanimoto,reference_fraction,fit_fraction,rms_to_reference,"
+                     "rms_from_reference")
+OVERLAY_HEADER = "rank,path,conformer,level,start,points,iterations,stop,tanimoto_start,tanimoto,overlap,reference_fraction,fit_fraction,angle_deg,shift," + MOTION_COLUMNS
+POSE_COLOUR_HEADER = ("rank,path,conformer,stage,nodes,matched,reference_features,reference_matched,colour_overlap,colour_tanimoto,reference_fraction,fit_fraction,"
+                      + ",".join(TYPE_NAMES))
+COMBO_HEADER = OVERLAY_HEADER + ",colour_tanimoto_start,colour_tanimoto,combo"
+
+
+def _num(*values) -> str:
+    """Floats as the `repr` of the float64 the GPU returned, joined by commas."""
+    return ",".join(repr(float(v)) for v in values)
+
+
+def _motion(poses, r: int) -> str:
+    """Row r's `MOTION_COLUMNS`: the rotation row by row, then the translation."""
+    return _num(*poses.rotation[r].reshape(-1), *poses.translation[r])
+
+
+def _hit(paths, al, r: int) -> str:
+    """`rank,path,conformer` of row r of posed rows `al`: the rank and the path are those of the explanation's row behind it."""
+    return f"{int(al.rows[r]) + 1},{paths[int(al.rows[r])]},{int(al.conformers[r])}"
+
+
+def _matches(levels, match, types) -> str:
+    """A key as `ligand cluster->model cluster:type` pairs; levels matched to None are left out."""
+    return " ".join(f"{lc}->{int(m)}:{types[int(m)]}" for lc, m in zip(levels, match) if m >= 0)
+
+
+def _write(out: Path, header: str, lines) -> None:
+    with open(out, "w") as w:
+        w.write(header + "\n")
+        w.writelines(line + "\n" for line in lines)
+
+
+def explain_rows(paths, scores, ex, types):
+    """`scores[i]` is the main CSV's score of the explanation's row i; `types` the model's cluster types."""
+    for r, path in enumerate(paths):
+        c = int(ex.best_conformer[r])
+        yield f"{r + 1},{path},{_num(scores[r])},{c},{_num(ex.conf_max[r][c])},{_matches(ex.levels[r], ex.match[r][c], types) if c >= 0 else ''}"
+
+
+def modes_rows(paths, ms, types):
+    for r, path in enumerate(paths):
+        c = int(ms.best_conformer[r])
+        for m in range(int(ms.count(r)[c]) if c >= 0 and ms.values[r].shape[1] else 0):
+            v = float(ms.values[r][m, c])
+            yield f"{r + 1},{path},{m},{_num(v, v / float(ms.values[r][0, c]))},{_matches(ms.levels[r], ms.match[r][m, c], types)}"
+
+
+def explain_nodes_rows(paths, order, ex, at, records):
+    """`order[i]` is the library index of the explanation's row i, `records[r]` the unpacked record behind the attribution's row r."""
+    for r, row in enumerate(at.rows):
+        rec, c = records[r], int(at.conformers[r])
+        matched = {int(lc): int(m) for lc, m in zip(ex.levels[row], ex.match[row][c]) if m >= 0}
+        total = float(at.total[r])
+        for u, share in enumerate(at.node[r]):
+            lc = int(np.searchsorted(rec["cluster_end"], u, side="right"))
+            tm = int(rec["typemask"][u])
+            types = "|".join(TYPE_NAMES[t] for t in range(len(TYPE_NAMES)) if tm >> t & 1)
+            yield f"{int(row) + 1},{order[int(row)]},{paths[int(row)]},{c},{u},{types},{lc},{matched.get(lc, '')},{_num(share, float(share) / total if total > 0 else 0.0)}"
+
+
+def hotspots_rows(paths, hs, node_type):
+    for r, row in enumerate(hs.rows):
+        total = float(hs.total[r])
+        engaged = set(hs.nodes(r).tolist())
+        for m in np.flatnonzero(hs.terms[r] > 0):
+            share = float(hs.share[r][m])
+            yield f"{int(row) + 1},{paths[int(row)]},{int(m)},{TYPE_NAMES[int(node_type[m])]},{_num(share, share / total if total > 0 else 0.0)},{int(int(m) in engaged)}"
+
+
+def poses_rows(paths, al):
+    for r in range(len(al.rows)):
+        yield f"{_hit(paths, al, r)},{_num(al.rmsd[r], al.rmsd_nodes[r])},{int(al.n_nodes[r])},{_motion(al, r)}"
+
+
+def pose_search_rows(paths, ps, al, rep):
+    """`al` and `rep` are the search's own alignment and clash report: one row per hit, in the hits' order."""
+    for r in range(len(ps.conformer)):
+        yield (f"{r + 1},{paths[r]},{int(ps.conformer[r])},{int(ps.mode[r])},{int(ps.passes[r])},{int(ps.n_candidates[r])},{int(ps.n_passing[r])},{_num(ps.value[r], ps.fraction[r])},"
+               f"{int(rep.n_clashing[r])},{_num(rep.overlap[r], rep.clearance[r], al.rmsd[r], al.rmsd_nodes[r])},{int(al.n_nodes[r])},{_motion(al, r)}")
+
+
+def clashes_rows(paths, al, rep, level: str, pocket):
+    for r in range(len(al.rows)):
+        yield (f"{_hit(paths, al, r)},{level},{int(rep.n_points[r])},{int(rep.n_clashing[r])},{int(rep.n_pairs[r])},{_num(rep.clearance[r], rep.overlap[r])},{int(rep.n_contacts[r])},"
+               f"{int(rep.worst[r, 0])},{rep.atom_label(r, pocket)},{';'.join(rep.residues(r, pocket))}")
+
+
+def refine_rows(paths, al, before, ref, after, level: str):
+    for r in range(len(al.rows)):
+        yield (f"{_hit(paths, al, r)},{level},{int(before.n_pairs[r])},{_num(before.overlap[r])},{int(after.n_pairs[r])},{_num(after.overlap[r], after.clearance[r])},"
+               f"{int(after.n_clashing[r])},{_num(ref.anchor_rmsd[r], np.degrees(ref.angle[r]), ref.shift[r])},{int(ref.iterations[r])},{int(ref.stop[r])},{_motion(ref, r)}")
+
+
+def pose_fit_rows(paths, al, stages):
+    """`stages`: (stage name, `PoseFit`) pairs; a hit's rows are together."""
+    for r in range(len(al.rows)):
+        for stage, pf in stages:
+            yield (f"{_hit(paths, al, r)},{stage},{int(pf.n_nodes[r])},{int(pf.n_pairs[r])},{int(pf.n_in_place[r])},{int(pf.n_passing[r])},"
+                   f"{_num(pf.fit[r], pf.ideal[r], pf.fraction[r], pf.best_fit[r], pf.best_fraction[r])},{';'.join(str(int(m)) for m in pf.occupied(r))}")
+
+
+def pose_shape_rows(paths, al, stages, level: str, n_reference: int):
+    """`stages`: (stage name, `ShapeReport`) pairs; a hit's rows are together."""
+    for r in range(len(al.rows)):
+        for stage, sh in stages:
+            yield (f"{_hit(paths, al, r)},{stage},{level},{int(sh.n_points[r])},{int(sh.n_covered[r])},{n_reference},{int(sh.n_reference_covered[r])},"
+                   f"{_num(sh.overlap[r], sh.tanimoto[r], sh.reference_fraction[r], sh.fit_fraction[r], sh.rms_to_reference[r], sh.rms_from_reference[r])}")
+
+
+def overlay_rows(paths, al, ov, level: str, combo: bool = False):
+    """The overlay CSV's rows of a `ShapeOverlay`; with `combo` those of a `ComboOverlay`, which end on its three colour columns."""
+    with np.errstate(all="ignore"):
+        ref_fraction = ov.overlap / ov.reference_overlap
+        fit_fraction = np.where(ov.self_overlap == 0.0, 0.0, ov.overlap / np.where(ov.self_overlap == 0.0, 1.0, ov.self_overlap))
+    for r in range(len(al.rows)):
+        yield (f"{_hit(paths, al, r)},{level},{int(ov.start[r])},{int(ov.n_points[r])},{int(ov.iterations[r])},{int(ov.stop[r])},"
+               f"{_num(ov.tanimoto_start[r], ov.tanimoto[r], ov.overlap[r], ref_fraction[r], fit_fraction[r], np.degrees(ov.angle[r]), ov.shift[r])},{_motion(ov, r)}"
+               + (f",{_num(ov.colour_tanimoto_start[r], ov.colour_tanimoto[r], ov.combo[r])}" if combo else ""))
+
+
+def pose_colour_rows(paths, al, rep, n_reference: int):
+    for r in range(len(al.rows)):
+        yield (f"{_hit(paths, al, r)},fit,{int(rep.n_nodes[r])},{int(rep.n_matched[r])},{n_reference},{int(rep.n_reference_matched[r])},"
+               f"{_num(rep.overlap[r], rep.tanimoto[r], rep.reference_fraction[r], rep.fit_fraction[r], *rep.type_overlap[r])}")
+
+
+# ------------------------------------------------------------------------------------------------------------- the side reports
+def write_explain_csv(out: Path, hits: Hits) -> None:
+    """The k best hits of a screen, in the order of the main CSV, with the best conformer, its maximum and its matched pairs
+    `ligand cluster -> model cluster:type` (ligand clusters as indices of the record's priority-ordered cluster list, model clusters as
+    indices of `model.node_clusters`; levels matched to None are left out): `engine.explain` on those k ligands only."""
+    _write(out, EXPLAIN_HEADER, explain_rows(hits.paths, [hits.scores[i] for i in hits.order], hits.explanation, hits.model.flat.cluster_type))
+
+
+def write_modes_csv(out: Path, hits: Hits, modes: int) -> None:
+    """One row per (hit, mode) of the k best hits, in the order of the explain CSV: the `modes` best leaves of the hit's best conformer
+    (`engine.explain_modes`), best first - the leaf's total, the total as a fraction of mode 0's (the explain CSV's conformer_max), and
+    its matched pairs in the explain CSV's format. Modes the conformer does not have are left out."""
+    from .engine import explain_modes
+
+    ms = explain_modes(hits.model, hits.lib, hits.order, modes=modes, weights=hits.weights)
+    _write(out, MODES_HEADER, modes_rows(hits.paths, ms, hits.model.flat.cluster_type))
+
+
+def _record_of(lib, i: int) -> dict:
+    """Record i of a packed library, or of a device-resident one of any origin (its buffers are read back for that record)."""
+    if isinstance(lib, PackedLibrary):
+        return lib.unpack(i)
+    offsets, data = lib.buffers()
+    lo, hi = (int(x) for x in offsets[i : i + 2].cpu())
+    return PackedLibrary.from_records([data[lo:hi].cpu().numpy().tobytes()]).unpack(0)
+
+
+def write_explain_nodes_csv(out: Path, hits: Hits) -> None:
+    """One row per (hit, node) of the k best hits, in the order of the main CSV: the node's index in the packed record, its types, its
+    ligand cluster, the model cluster that cluster is matched to in the explaining leaf of the hit's best conformer (empty for None and
+    for clusters outside the tree), the node's share of that conformer's maximum (`engine.attribute`) and the share as a fraction of it."""
+    at = hits.explanation.attribution(hits.model, hits.lib, weights=hits.weights)
+    records = [_record_of(hits.lib, hits.order[int(row)]) for row in at.rows]
+    _write(out, EXPLAIN_NODES_HEADER, explain_nodes_rows(hits.paths, hits.order, hits.explanation, at, records))
+
+
+def write_hotspots_csv(out: Path, hits: Hits) -> None:
+    """One row per (hit, model node the hit has terms with) of the k best hits, in the order of the explain CSV: the node's index in the
+    model, its type, its share of the hit's best conformer maximum (`engine.hotspots`), the share as a fraction of it, and 1 where the
+    hit engages the node (the node's bit of the hit's interaction fingerprint)."""
+    hs = hits.explanation.hotspots(hits.model, hits.lib, weights=hits.weights)
+    _write(out, HOTSPOTS_HEADER, hotspots_rows(hits.paths, hs, hits.model.flat.node_type))
+
+
+def write_poses_csv(out: Path, hits: Hits) -> None:
+    """One row per hit of the k best, in the order of the explain CSV: the fit of the hit's best conformer under its explaining match
+    (`engine.align`) - the two RMSDs, the fitted nodes and the motion `x -> R x + t` (R row by row) that poses the conformer in the
+    pocket. Every number is the `repr` of the float64 the GPU returned."""
+    _write(out, POSES_HEADER, poses_rows(hits.paths, hits.poses))
+
+
+def write_pose_search_csv(out: Path, hits: Hits, pocket, tolerance: float, modes: int, min_fraction: float, store: PackedAtoms | None = None) -> None:
+    """One row per hit of the k best, in the order of the poses CSV: the hit posed where `engine.pose_search` puts it - of all its conformers
+    under their `modes` best binding modes the best-scoring one whose fitted pharmacophore nodes do not clash with the protein, else the
+    one of smallest overlap. The conformer and mode (-1 and -1 for a hit without any pose), whether it passes, how many candidates there
+    were and how many passed, the mode's leaf total and its share of the hit's best, the clash check and the fit of the chosen pose, and
+    the motion as the poses CSV has it. Every number is the `repr` of the float64 the GPU returned. With `store`, the library's atom store, the
+    search chooses on the hits' heavy atoms (`--pose_search_level atoms`): the same columns, the clash values then being the atoms'."""
+    from .engine import pose_search
+
+    ps = pose_search(hits.model, hits.lib, pocket, hits.order, modes=modes, weights=hits.weights, min_fraction=min_fraction, tolerance=tolerance, atoms=store)
+    _write(out, POSE_SEARCH_HEADER, pose_search_rows(hits.paths, ps, ps.alignment(), ps.report()))
+
+
+def write_clashes_csv(out: Path, hits: Hits) -> None:
+    """One row per hit of the k best, in the order of the poses CSV: the pose of the hit's best conformer (`engine.align`) checked against the
+    protein's heavy atoms (`engine.clashes`) - at level `nodes` the hit's pharmacophore nodes, at level `atoms` the heavy atoms of the hit's
+    file, read again. Points, clashing points, clashing pairs, the deepest penetration (negative: the clearance), the overlap, the points
+    within contact distance, the worst pair's point and protein atom, and the touched residues joined by `;`."""
+    _write(out, CLASHES_HEADER, clashes_rows(hits.paths, hits.poses, hits.clash_report, hits.clash_level, hits.pocket))
+
+
+def write_refine_csv(out: Path, hits: Hits) -> None:
+    """One row per hit of the k best, in the order of the poses CSV: the pose of the hit's best conformer (`engine.align`) moved out of the
+    protein's heavy atoms (`engine.refine`) - the hit's pharmacophore nodes at level `nodes`, the heavy atoms of its file at level `atoms` -
+    with the check (`engine.clashes`) before and after: clashing pairs and overlap before; pairs, overlap, the deepest penetration and the
+    clashing points after; how far the anchors moved (rmsd), the net rotation in degrees, the centroid's shift, the trial motions taken and
+    why they ended (`RefinedPoses.stop`); the refined rotation, row-major, and translation. A pose that is not OK has nan and stop -1."""
+    after = hits.refined.clashes(hits.pocket, hits.lib, atoms=hits.atoms(hits.clash_level), tolerance=hits.tolerance)
+    _write(out, REFINE_HEADER, refine_rows(hits.paths, hits.poses, hits.clash_report, hits.refined, after, hits.clash_level))
+
+
+def write_pose_fit_csv(out: Path, hits: Hits, mode: str, refined: bool = False) -> None:
+    """One row per hit of the k best, in the order of the poses CSV, with stage `fit`: the pose of the hit's best conformer (`engine.align`)
+    scored in place (`engine.pose_fit`) - in mode `key` over the pairs of the explaining match, in mode `free` over every hotspot of a type
+    the node has. Nodes with a pair, pairs, nodes in place, passing pairs, the fit, its ideal and their ratio, the same over each node's
+    nearest hotspot, and the occupied model nodes joined by `;`. With `refined` a second row per hit, stage `refined`, for the motion the
+    run's refinement (`Hits.refined`) ends at. Every float is the `repr` of the float64 the GPU returned."""
+    keys = hits.keys if mode == "key" else None
+    stages = [("fit", hits.poses)] + ([("refined", hits.refined)] if refined else [])
+    _write(out, POSE_FIT_HEADER, pose_fit_rows(hits.paths, hits.poses, [(stage, p.pose_fit(hits.model, hits.lib, keys=keys, weights=hits.weights)) for stage, p in stages]))
+
+
+def write_pose_shape_csv(out: Path, hits: Hits, reference, level: str, cover: float, refined: bool = False) -> None:
+    """One row per hit of the k best, in the order of the poses CSV, with stage `fit`: the pose of the hit's best conformer (`engine.align`)
+    compared with the known ligand `reference` (`engine.shape`) - at level `nodes` the hit's pharmacophore nodes, at level `atoms` its heavy
+    atoms, from where the clashes CSV takes them. Points and the points within `cover` of a reference atom, the reference's atoms and
+    those within `cover` of a point, the overlap volume, the shape Tanimoto, the fraction of the reference that is filled and of the hit that
+    lies inside it, and the root mean square nearest-atom distance both ways. With `refined` a second row per hit, stage `refined`, for the
+    motion the run's refinement ends at (it moved the points of the clash level; the comparison is at `level`). Every float is the `repr` of
+    the float64 the GPU returned."""
+    stages = [("fit", hits.poses)] + ([("refined", hits.refined)] if refined else [])
+    _write(out, POSE_SHAPE_HEADER, pose_shape_rows(hits.paths, hits.poses, [(stage, p.shape(reference, hits.lib, atoms=hits.atoms(level), cover=cover)) for stage, p in stages],
+                                                   level, len(reference)))
+
+
+def _start_motion(hits: Hits, starts: int) -> dict:
+    """Where an overlay starts: with `starts` 4 from the inertial starts (no motion is given), with 0 from the hits' fitted poses."""
+    return {} if starts else dict(rotation=hits.poses.rotation, translation=hits.poses.translation)
+
+
+def write_overlay_csv(out: Path, hits: Hits, reference, level: str, starts: int, max_iter: int) -> None:
+    """One row per hit of the k best, in the order of the poses CSV: the hit's best conformer overlaid on the known ligand `reference`
+    (`engine.overlay`) - at level `nodes` its pharmacophore nodes, at level `atoms` its heavy atoms, from where the pose-shape CSV takes
+    them. With `starts` 4 the hit is run from the four inertial starts and `start` says which was kept; with 0 it is run from its fitted
+    pose (`engine.align`) and `start` is -1. The shape Tanimoto at the start and at the end, the overlap volume there, the fraction of the
+    reference that is filled and of the hit that lies inside it, the net rotation in degrees and the centroid's shift from the start, and
+    the motion. Every float is the `repr` of the float64 the GPU returned (the two fractions and the degrees are formed from them)."""
+    from .engine import overlay
+
+    ov = overlay(reference, starts=starts, max_iter=max_iter, **_start_motion(hits, starts), **hits.source(level))
+    _write(out, OVERLAY_HEADER, overlay_rows(hits.paths, hits.poses, ov, level))
+
+
+def write_pose_colour_csv(out: Path, hits: Hits, reference, cover: float) -> None:
+    """One row per hit of the k best, in the order of the poses CSV, with stage `fit`: the pharmacophore nodes of the hit's best conformer
+    under its fitted pose (`engine.align`) compared with the known ligand's typed features `reference` (`engine.colour`). Nodes and the
+    nodes with a partner of a shared type within `cover`, the reference's features and those reproduced, the colour overlap, its Tanimoto,
+    the fraction of the reference that is reproduced and of the hit that lies on it, and the overlap each type carries. Every float is the
+    `repr` of the float64 the GPU returned."""
+    from .engine import colour_of
+
+    _write(out, POSE_COLOUR_HEADER, pose_colour_rows(hits.paths, hits.poses, colour_of(hits.poses, reference, hits.lib, cover=cover), len(reference)))
+
+
+def write_combo_csv(out: Path, hits: Hits, reference, colour, colour_weight, level: str, starts: int, max_iter: int) -> None:
+    """One row per hit of the k best, in the order of the poses CSV: the hit's best conformer overlaid on the known ligand by shape and
+    colour together (`engine.combo_overlay`; `reference` its atoms, `colour` its typed features). The columns of the overlay CSV - the
+    shape points at level `nodes` the hit's pharmacophore nodes, at level `atoms` its heavy atoms - and the colour Tanimoto at the start
+    and at the end and the combo at the end, the sum of the two Tanimotos. The typed points are always the hit's nodes."""
+    from .engine import combo_overlay
+
+    al = hits.poses
+    rows = dict(dict(library=hits.lib, indices=al.indices, conformers=al.conformers), **hits.source(level))  # (the records always: their nodes carry the types)
+    ov = combo_overlay(reference, colour=colour, colour_weight=colour_weight, starts=starts, max_iter=max_iter, **_start_motion(hits, starts), **rows)
+    _write(out, COMBO_HEADER, overlay_rows(hits.paths, al, ov, level, combo=True))
+
+
+# (flag, the flag that holds the path, writer, the writer's further arguments from the run `s`: the parsed flags and what `main` read for them) of every
+# side report of the explained hits, in the order their files are written
+SIDE_REPORTS = (
+    ("explain_nodes", "explain_nodes", write_explain_nodes_csv, lambda s: ()),
+    ("poses", "poses", write_poses_csv, lambda s: ()),
+    ("clashes", "clashes", write_clashes_csv, lambda s: ()),
+    ("refine_out", "refine_out", write_refine_csv, lambda s: ()),
+    ("pose_fit", "pose_fit", write_pose_fit_csv, lambda s: (s.pose_fit_mode, bool(s.refine_out))),
+    ("pose_shape", "pose_shape", write_pose_shape_csv, lambda s: (s.shape_reference, s.shape_level, s.shape_cover, bool(s.refine_out))),
+    ("overlay_out", "overlay_out", write_overlay_csv, lambda s: (s.shape_reference, s.shape_level, s.overlay_starts, s.overlay_iter)),
+    ("pose_colour", "pose_colour", write_pose_colour_csv, lambda s: (s.colour_reference, s.colour_cover)),
+    ("combo_out", "combo_out", write_combo_csv, lambda s: (s.shape_reference, s.colour_reference, s.colour_weight, s.shape_level, s.overlay_starts, s.overlay_iter)),
+    ("pose_search", "pose_search", write_pose_search_csv, lambda s: (s.pocket, s.clash_tolerance, s.pose_search_modes, s.pose_min_fraction, s.search_store)),
+    ("hotspots", "hotspots", write_hotspots_csv, lambda s: ()),
+    ("modes", "modes_out", write_modes_csv, lambda s: (s.modes,)),
+)
+
+
+def _asked(args, flag: str) -> bool:
+    """Whether the run asks for the side report behind `flag`: a path that is not empty, or --modes' M (0 included: refused later)."""
+    value = getattr(args, flag)
+    return value is not None and value != ""
+
+
 def main(argv=None) -> None:
     parser = Screening_ArgParser()
     args = parser.parse_args(argv)
-    if args.explain_nodes and args.explain <= 0:
-        parser.error("--explain_nodes needs --explain K")
-    if args.poses and args.explain <= 0:
-        parser.error("--poses needs --explain K")
-    if args.clashes and args.explain <= 0:
-        parser.error("--clashes needs --explain K")
-    if args.refine_out and args.explain <= 0:
-        parser.error("--refine_out needs --explain K")
-    if args.pose_search and args.explain <= 0:
-        parser.error("--pose_search needs --explain K")
-    if args.pose_fit and args.explain <= 0:
-        parser.error("--pose_fit needs --explain K")
-    if args.pose_shape and args.explain <= 0:
-        parser.error("--pose_shape needs --explain K")
+    for flag, *_ in SIDE_REPORTS:
+        if _asked(args, flag) and args.explain <= 0:
+            parser.error(f"--{flag} needs --explain K")
     if args.pose_shape and not args.shape_ref:
         parser.error("--pose_shape needs --shape_ref FILE.pdb, the known ligand")
-    if args.overlay_out and args.explain <= 0:
-        parser.error("--overlay_out needs --explain K")
     if args.overlay_out and not args.shape_ref:
         parser.error("--overlay_out needs --shape_ref FILE.pdb, the known ligand")
     if args.overlay_out and not 0 <= args.overlay_iter <= 64:
         parser.error("--overlay_iter takes 0 to 64")
     if args.shape_ref and not (args.pose_shape or args.overlay_out or args.combo_out):
         parser.error("--shape_ref needs --pose_shape PATH or --overlay_out PATH")
-    if (args.pose_colour or args.combo_out) and args.explain <= 0:
-        parser.error(f"{'--pose_colour' if args.pose_colour else '--combo_out'} needs --explain K")
     if (args.pose_colour or args.combo_out) and not args.colour_ref:
         parser.error(f"{'--pose_colour' if args.pose_colour else '--combo_out'} needs --colour_ref FILE.csv, the known ligand's features")
     if args.combo_out and not args.shape_ref:
@@ -221,13 +589,13 @@ def main(argv=None) -> None:
         parser.error("--colour_cover takes a distance that is not negative")
     if args.combo_out and not 0 <= args.overlay_iter <= 64:
         parser.error("--overlay_iter takes 0 to 64")
-    combo_weight = "balanced"
+    args.colour_weight = "balanced"
     if args.combo_out and args.combo_weight != "balanced":
         try:
-            combo_weight = float(args.combo_weight)
+            args.colour_weight = float(args.combo_weight)
         except ValueError:
-            combo_weight = float("nan")
-        if not (np.isfinite(combo_weight) and combo_weight >= 0):
+            args.colour_weight = float("nan")
+        if not (np.isfinite(args.colour_weight) and args.colour_weight >= 0):
             parser.error("--combo_weight takes a number that is not negative, or balanced")
     if args.pose_shape and not (np.isfinite(args.shape_cover) and args.shape_cover >= 0):
         parser.error("--shape_cover takes a distance that is not negative")
@@ -254,8 +622,6 @@ def main(argv=None) -> None:
         parser.error("--refine_restraint takes a number that is not negative")
     if args.refine_out and not 0 <= args.refine_iter <= 64:
         parser.error("--refine_iter takes 0 to 64")
-    if args.hotspots and args.explain <= 0:
-        parser.error("--hotspots needs --explain K")
     if args.diverse is not None and args.diverse <= 0:
         parser.error("--diverse takes a positive K")
     if args.diverse is not None and not args.diverse_out:
@@ -266,8 +632,6 @@ def main(argv=None) -> None:
         parser.error("--diverse_pool takes 1 to 65536")
     if not 0.0 < args.diverse_threshold <= 1.0:
         parser.error("--diverse_threshold takes a similarity in (0, 1]")
-    if args.modes is not None and args.explain <= 0:
-        parser.error("--modes needs --explain K")
     if args.modes is not None and not 1 <= args.modes <= 8:
         parser.error("--modes takes 1 to 8")
     if args.modes_out and args.modes is None:
@@ -320,25 +684,26 @@ def main(argv=None) -> None:
         Halogen=args.halogen,
         Hydrophobic=args.hydrophobic,
     )
+    args.pocket = args.shape_reference = args.colour_reference = None
     if args.clashes or args.refine_out or args.pose_search:  # (before the screen: a model without a protein should not cost a pass)
         from .pocket import PocketAtoms
 
         try:
-            pocket = PocketAtoms.from_pdb(Path(args.protein), centers=model.node_centers) if args.protein else model.pocket_atoms()
+            args.pocket = PocketAtoms.from_pdb(Path(args.protein), centers=model.node_centers) if args.protein else model.pocket_atoms()
         except (OSError, ValueError) as e:
             parser.error(f"{'--clashes' if args.clashes else '--refine_out' if args.refine_out else '--pose_search'}: {e}" + ("" if args.protein else " (give it with --protein FILE.pdb)"))
     if args.pose_colour or args.combo_out:
         from .shape import ColourFeatures
 
         try:
-            colour_ref = ColourFeatures.from_csv(Path(args.colour_ref))
+            args.colour_reference = ColourFeatures.from_csv(Path(args.colour_ref))
         except (OSError, ValueError) as e:
             parser.error(f"--colour_ref {args.colour_ref}: {e}")
     if args.pose_shape or args.overlay_out or args.combo_out:  # (before the screen: a reference that cannot be read should not cost a pass)
         from .shape import ReferenceLigand
 
         try:
-            shape_ref = ReferenceLigand.from_pdb(Path(args.shape_ref))
+            args.shape_reference = ReferenceLigand.from_pdb(Path(args.shape_ref))
         except (OSError, ValueError) as e:
             parser.error(f"--shape_ref {args.shape_ref}: {e}")
     # the library's atom store: the check of a packed library's atoms, the atom-level search, and what --save_top keeps next to the records
@@ -349,7 +714,7 @@ def main(argv=None) -> None:
         names, lib, store = load_library(Path(args.library_dir), args.cpus, on_device=True, with_atoms=True)
     else:
         (names, lib), store = load_library(Path(args.library_dir), args.cpus, on_device=True), None
-    hit_atoms = store if packed else None  # (a directory's hits are read again, as before; a packed library's atoms come from its store)
+    args.search_store = store if atom_search else None
     if args.actives:  # (before the screen: a name that matches nothing should not cost a pass)
         from .validation import match_actives
 
@@ -373,41 +738,15 @@ def main(argv=None) -> None:
     if args.similar_to:
         write_similar_csv(Path(args.similar_out), names, lib, queries, args.similar_to, args.similar_k)
     if args.explain > 0:
-        out = Path(args.explain_out) if args.explain_out else Path(str(args.out) + ".explain.csv")
-        write_explain_csv(out, names, scores, status, model, lib, weight, args.explain)
-        if args.explain_nodes:
-            write_explain_nodes_csv(Path(args.explain_nodes), names, scores, status, model, lib, weight, args.explain)
-        if args.poses:
-            write_poses_csv(Path(args.poses), names, scores, status, model, lib, weight, args.explain)
-        if args.clashes:
-            write_clashes_csv(Path(args.clashes), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_level, args.clash_tolerance, hit_atoms)
-        if args.refine_out:
-            write_refine_csv(Path(args.refine_out), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_level, args.clash_tolerance,
-                             args.refine_restraint, args.refine_iter, hit_atoms)
-        if args.pose_fit:
-            refine = (dict(pocket=pocket, level=args.clash_level, tolerance=args.clash_tolerance, restraint=args.refine_restraint, max_iter=args.refine_iter, store=hit_atoms)
-                      if args.refine_out else None)
-            write_pose_fit_csv(Path(args.pose_fit), names, scores, status, model, lib, weight, args.explain, args.pose_fit_mode, refine)
-        if args.pose_shape:
-            refine = (dict(pocket=pocket, level=args.clash_level, tolerance=args.clash_tolerance, restraint=args.refine_restraint, max_iter=args.refine_iter, store=hit_atoms)
-                      if args.refine_out else None)
-            write_pose_shape_csv(Path(args.pose_shape), names, scores, status, model, lib, weight, args.explain, shape_ref, args.shape_level, args.shape_cover, hit_atoms, refine)
-        if args.overlay_out:
-            write_overlay_csv(Path(args.overlay_out), names, scores, status, model, lib, weight, args.explain, shape_ref, args.shape_level, args.overlay_starts, args.overlay_iter,
-                              hit_atoms)
-        if args.pose_colour:
-            write_pose_colour_csv(Path(args.pose_colour), names, scores, status, model, lib, weight, args.explain, colour_ref, args.colour_cover)
-        if args.combo_out:
-            write_combo_csv(Path(args.combo_out), names, scores, status, model, lib, weight, args.explain, shape_ref, colour_ref, combo_weight, args.shape_level,
-                            args.overlay_starts, args.overlay_iter, hit_atoms)
-        if args.pose_search:
-            write_pose_search_csv(Path(args.pose_search), names, scores, status, model, lib, weight, args.explain, pocket, args.clash_tolerance, args.pose_search_modes,
-                                  args.pose_min_fraction, store if atom_search else None)
-        if args.hotspots:
-            write_hotspots_csv(Path(args.hotspots), names, scores, status, model, lib, weight, args.explain)
-        if args.modes is not None:
-            out = Path(args.modes_out) if args.modes_out else Path(str(args.out) + ".modes.csv")
-            write_modes_csv(out, names, scores, status, model, lib, weight, args.explain, args.modes)
+        # (a directory's hits are read again; a packed library's atoms come from its store)
+        hits = Hits(names, scores, status, model, lib, weight, args.explain, store=store if packed else None, pocket=args.pocket, clash_level=args.clash_level,
+                    tolerance=args.clash_tolerance, restraint=args.refine_restraint, max_iter=args.refine_iter)
+        write_explain_csv(Path(args.explain_out) if args.explain_out else Path(str(args.out) + ".explain.csv"), hits)
+        if args.modes is not None and not args.modes_out:
+            args.modes_out = str(args.out) + ".modes.csv"
+        for flag, path, writer, further in SIDE_REPORTS:
+            if _asked(args, flag):
+                writer(Path(getattr(args, path)), hits, *further(args))
     if args.diverse is not None:
         write_diverse_csv(Path(args.diverse_out), names, result, args.diverse, args.diverse_pool, args.diverse_threshold)
     if args.constrained_out:
@@ -447,12 +786,6 @@ def write_similar_csv(out: Path, names: list[str], lib, queries: list[int], quer
         w.write("rank,path,similarity," + ",".join(Path(q).stem for q in query_names) + "\n")
         for r, i in enumerate(order):
             w.write(f"{r + 1},{names[int(i)]},{float(fused[r])}," + ",".join(str(float(v)) for v in per_query[:, int(i)]) + "\n")
-
-
-def _best_hits(scores: np.ndarray, status: np.ndarray, k: int) -> list[int]:
-    """The k best scored ligands in the order of the main CSV."""
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    return [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
 
 
 def write_panel_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, panel: list[str], lib, weights, k: int) -> None:
@@ -498,103 +831,7 @@ def write_constrained_csv(out: Path, names: list[str], model, lib, weights, k: i
         w.write("rank,path,constrained_score,score,best_conformer,matches\n")
         for r, i in enumerate(res.indices):
             c = int(ex.best_conformer[r])
-            pairs = [f"{lc}->{int(m)}:{types[int(m)]}" for lc, m in zip(ex.levels[r], ex.match[r][c]) if m >= 0] if c >= 0 else []
-            w.write(f"{r + 1},{names[int(i)]},{float(res.scores[r])},{float(res.unconstrained[r])},{c},{' '.join(pairs)}\n")
-
-
-def write_explain_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int) -> None:
-    """The k best hits of a screen, in the order of the main CSV, with the best conformer, its maximum and its matched pairs
-    `ligand cluster -> model cluster:type` (ligand clusters as indices of the record's priority-ordered cluster list, model clusters as
-    indices of `model.node_clusters`; levels matched to None are left out): `engine.explain` on those k ligands only."""
-    from .engine import explain
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    ex = explain(model, lib, order, weights=weights)
-    types = model.flat.cluster_type
-    with open(out, "w") as w:
-        w.write("rank,path,score,best_conformer,conformer_max,matches\n")
-        for r, i in enumerate(order):
-            c = int(ex.best_conformer[r])
-            pairs = [f"{lc}->{int(m)}:{types[int(m)]}" for lc, m in zip(ex.levels[r], ex.match[r][c]) if m >= 0] if c >= 0 else []
-            w.write(f"{r + 1},{names[i]},{float(scores[i])},{c},{float(ex.conf_max[r][c])},{' '.join(pairs)}\n")
-
-
-def write_modes_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, modes: int) -> None:
-    """One row per (hit, mode) of the k best hits, in the order of the explain CSV: the `modes` best leaves of the hit's best conformer
-    (`engine.explain_modes`), best first - the leaf's total, the total as a fraction of mode 0's (the explain CSV's conformer_max), and
-    its matched pairs in the explain CSV's format. Modes the conformer does not have are left out."""
-    from .engine import explain_modes
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    ms = explain_modes(model, lib, order, modes=modes, weights=weights)
-    types = model.flat.cluster_type
-    with open(out, "w") as w:
-        w.write("rank,path,mode,mode_score,fraction_of_best,matches\n")
-        for r, i in enumerate(order):
-            c = int(ms.best_conformer[r])
-            for m in range(int(ms.count(r)[c]) if c >= 0 and ms.values[r].shape[1] else 0):
-                v = float(ms.values[r][m, c])
-                pairs = [f"{lc}->{int(a)}:{types[int(a)]}" for lc, a in zip(ms.levels[r], ms.match[r][m, c]) if a >= 0]
-                w.write(f"{r + 1},{names[i]},{m},{v},{v / float(ms.values[r][0, c])},{' '.join(pairs)}\n")
-
-
-def _record_of(lib, i: int) -> dict:
-    """Record i of a packed library, or of a device-resident one of any origin (its buffers are read back for that record)."""
-    if isinstance(lib, PackedLibrary):
-        return lib.unpack(i)
-    offsets, data = lib.buffers()
-    lo, hi = (int(x) for x in offsets[i : i + 2].cpu())
-    return PackedLibrary.from_records([data[lo:hi].cpu().numpy().tobytes()]).unpack(0)
-
-
-def write_explain_nodes_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int) -> None:
-    """One row per (hit, node) of the k best hits, in the order of the main CSV: the node's index in the packed record, its types, its
-    ligand cluster, the model cluster that cluster is matched to in the explaining leaf of the hit's best conformer (empty for None and
-    for clusters outside the tree), the node's share of that conformer's maximum (`engine.attribute`) and the share as a fraction of it."""
-    from .constants import TYPE_NAMES
-    from .engine import explain
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    ex = explain(model, lib, order, weights=weights)
-    at = ex.attribution(model, lib, weights=weights)
-    with open(out, "w") as w:
-        w.write("rank,index,path,conformer,node,node_types,ligand_cluster,model_cluster,node_score,share\n")
-        for r, row in enumerate(at.rows):
-            i = order[int(row)]
-            rec = _record_of(lib, i)
-            ends = rec["cluster_end"]
-            matched = {int(lc): int(m) for lc, m in zip(ex.levels[row], ex.match[row][int(at.conformers[r])]) if m >= 0}
-            total = float(at.total[r])
-            for u, share in enumerate(at.node[r]):
-                lc = int(np.searchsorted(ends, u, side="right"))
-                tm = int(rec["typemask"][u])
-                types = "|".join(TYPE_NAMES[t] for t in range(len(TYPE_NAMES)) if tm >> t & 1)
-                frac = float(share) / total if total > 0 else 0.0
-                w.write(f"{int(row) + 1},{i},{names[i]},{int(at.conformers[r])},{u},{types},{lc},{matched.get(lc, '')},{float(share)},{frac}\n")
-
-
-def write_hotspots_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int) -> None:
-    """One row per (hit, model node the hit has terms with) of the k best hits, in the order of the explain CSV: the node's index in the
-    model, its type, its share of the hit's best conformer maximum (`engine.hotspots`), the share as a fraction of it, and 1 where the
-    hit engages the node (the node's bit of the hit's interaction fingerprint)."""
-    from .constants import TYPE_NAMES
-    from .engine import explain
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    hs = explain(model, lib, order, weights=weights).hotspots(model, lib, weights=weights)
-    node_type = model.flat.node_type
-    with open(out, "w") as w:
-        w.write("rank,path,node,type,share,fraction,engaged\n")
-        for r, row in enumerate(hs.rows):
-            total = float(hs.total[r])
-            engaged = set(hs.nodes(r).tolist())
-            for m in np.flatnonzero(hs.terms[r] > 0):
-                share = float(hs.share[r][m])
-                w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(m)},{TYPE_NAMES[int(node_type[m])]},{share},{share / total if total > 0 else 0.0},{int(int(m) in engaged)}\n")
+            w.write(f"{r + 1},{names[int(i)]},{float(res.scores[r])},{float(res.unconstrained[r])},{c},{_matches(ex.levels[r], ex.match[r][c], types) if c >= 0 else ''}\n")
 
 
 def write_diverse_csv(out: Path, names: list[str], result, k: int, pool: int | None, threshold: float) -> None:
@@ -609,264 +846,6 @@ def write_diverse_csv(out: Path, names: list[str], result, k: int, pool: int | N
             w.write(f"{int(pool_rows[row]) + 1},{names[int(dv.indices[r])]},{float(scores[int(dv.indices[r])])},{int(dv.cluster_size[r])},{' '.join(str(int(m)) for m in dv.profile.nodes(int(row)))}\n")
 
 
-def write_poses_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int) -> None:
-    """One row per hit of the k best, in the order of the explain CSV: the fit of the hit's best conformer under its explaining match
-    (`engine.align`) - the two RMSDs, the fitted nodes and the motion `x -> R x + t` (R row by row) that poses the conformer in the
-    pocket. Every number is the `repr` of the float64 the GPU returned."""
-    from .engine import explain
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
-    with open(out, "w") as w:
-        w.write("rank,path,conformer,rmsd,rmsd_nodes,fitted_nodes," + ",".join(f"r{i}{j}" for i in range(3) for j in range(3)) + ",tx,ty,tz\n")
-        for r, row in enumerate(al.rows):
-            nums = [al.rmsd[r], al.rmsd_nodes[r]], [*al.rotation[r].reshape(-1), *al.translation[r]]
-            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{','.join(repr(float(v)) for v in nums[0])},{int(al.n_nodes[r])},"
-                    f"{','.join(repr(float(v)) for v in nums[1])}\n")
-
-
-POSE_SEARCH_HEADER = ("rank,path,conformer,mode,passes,candidates,passing,mode_score,fraction_of_best,clashing,overlap,clearance,rmsd,rmsd_nodes,fitted_nodes,"
-                      + ",".join(f"r{i}{j}" for i in range(3) for j in range(3)) + ",tx,ty,tz")
-
-
-def write_pose_search_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, pocket, tolerance: float, modes: int,
-                          min_fraction: float, store: PackedAtoms | None = None) -> None:
-    """One row per hit of the k best, in the order of the poses CSV: the hit posed where `engine.pose_search` puts it - of all its conformers
-    under their `modes` best binding modes the best-scoring one whose fitted pharmacophore nodes do not clash with the protein, else the
-    one of smallest overlap. The conformer and mode (-1 and -1 for a hit without any pose), whether it passes, how many candidates there
-    were and how many passed, the mode's leaf total and its share of the hit's best, the clash check and the fit of the chosen pose, and
-    the motion as the poses CSV has it. Every number is the `repr` of the float64 the GPU returned. With `store`, the library's atom store, the
-    search chooses on the hits' heavy atoms (`--pose_search_level atoms`): the same columns, the clash values then being the atoms'."""
-    from .engine import pose_search
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    ps = pose_search(model, lib, pocket, order, modes=modes, weights=weights, min_fraction=min_fraction, tolerance=tolerance, atoms=store)
-    al, rep = ps.alignment(), ps.report()
-    with open(out, "w") as w:
-        w.write(POSE_SEARCH_HEADER + "\n")
-        for r in range(len(ps)):
-            nums = [ps.value[r], ps.fraction[r]], [rep.overlap[r], rep.clearance[r], al.rmsd[r], al.rmsd_nodes[r]], [*al.rotation[r].reshape(-1), *al.translation[r]]
-            w.write(f"{r + 1},{names[order[r]]},{int(ps.conformer[r])},{int(ps.mode[r])},{int(ps.passes[r])},{int(ps.n_candidates[r])},{int(ps.n_passing[r])},"
-                    f"{','.join(repr(float(v)) for v in nums[0])},{int(rep.n_clashing[r])},{','.join(repr(float(v)) for v in nums[1])},{int(al.n_nodes[r])},"
-                    f"{','.join(repr(float(v)) for v in nums[2])}\n")
-
-
-def _hit_atoms(store, names: list[str], order: list[int], rows):
-    """What `Alignment.clashes(atoms=...)` takes for the posed hits at level `atoms`: the library's atom store where there is one (a packed
-    library: the rows' atoms are gathered on the GPU), else the hits' files, read again."""
-    if store is not None:
-        return store
-    from .ligand import Ligand
-
-    return [Ligand.load_from_file(names[order[int(row)]]) for row in rows]
-
-
-def write_clashes_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, pocket, level: str, tolerance: float,
-                      store: PackedAtoms | None = None) -> None:
-    """One row per hit of the k best, in the order of the poses CSV: the pose of the hit's best conformer (`engine.align`) checked against the
-    protein's heavy atoms (`engine.clashes`) - at level `nodes` the hit's pharmacophore nodes, at level `atoms` the heavy atoms of the hit's
-    file, read again. Points, clashing points, clashing pairs, the deepest penetration (negative: the clearance), the overlap, the points
-    within contact distance, the worst pair's point and protein atom, and the touched residues joined by `;`."""
-    from .engine import explain
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
-    atoms = _hit_atoms(store, names, order, al.rows) if level == "atoms" else None
-    rep = al.clashes(pocket, lib, atoms=atoms, tolerance=tolerance)
-    with open(out, "w") as w:
-        w.write("rank,path,conformer,level,points,clashing,pairs,clearance,overlap,contacts,worst_point,worst_atom,residues\n")
-        for r, row in enumerate(al.rows):
-            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{level},{int(rep.n_points[r])},{int(rep.n_clashing[r])},{int(rep.n_pairs[r])},"
-                    f"{float(rep.clearance[r])!r},{float(rep.overlap[r])!r},{int(rep.n_contacts[r])},{int(rep.worst[r, 0])},{rep.atom_label(r, pocket)},"
-                    f"{';'.join(rep.residues(r, pocket))}\n")
-
-
-REFINE_HEADER = ("rank,path,conformer,level,pairs_before,overlap_before,pairs_after,overlap_after,clearance_after,clashing_after,anchor_rmsd,angle_deg,shift,iterations,stop,"
-                 "r00,r01,r02,r10,r11,r12,r20,r21,r22,tx,ty,tz")
-
-
-def write_refine_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, pocket, level: str, tolerance: float,
-                     restraint: float, max_iter: int, store: PackedAtoms | None = None) -> None:
-    """One row per hit of the k best, in the order of the poses CSV: the pose of the hit's best conformer (`engine.align`) moved out of the
-    protein's heavy atoms (`engine.refine`) - the hit's pharmacophore nodes at level `nodes`, the heavy atoms of its file at level `atoms` -
-    with the check (`engine.clashes`) before and after: clashing pairs and overlap before; pairs, overlap, the deepest penetration and the
-    clashing points after; how far the anchors moved (rmsd), the net rotation in degrees, the centroid's shift, the trial motions taken and
-    why they ended (`RefinedPoses.stop`); the refined rotation, row-major, and translation. A pose that is not OK has nan and stop -1."""
-    from .engine import explain
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
-    atoms = _hit_atoms(store, names, order, al.rows) if level == "atoms" else None
-    before = al.clashes(pocket, lib, atoms=atoms, tolerance=tolerance)
-    ref = al.refine(pocket, lib, atoms=atoms, tolerance=tolerance, restraint=restraint, max_iter=max_iter)
-    after = ref.clashes(pocket, lib, atoms=atoms, tolerance=tolerance)
-    with open(out, "w") as w:
-        w.write(REFINE_HEADER + "\n")
-        for r, row in enumerate(al.rows):
-            motion = ",".join(repr(float(v)) for v in (*ref.rotation[r].reshape(-1), *ref.translation[r]))
-            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{level},{int(before.n_pairs[r])},{float(before.overlap[r])!r},{int(after.n_pairs[r])},"
-                    f"{float(after.overlap[r])!r},{float(after.clearance[r])!r},{int(after.n_clashing[r])},{float(ref.anchor_rmsd[r])!r},"
-                    f"{float(np.degrees(ref.angle[r]))!r},{float(ref.shift[r])!r},{int(ref.iterations[r])},{int(ref.stop[r])},{motion}\n")
-
-
-POSE_FIT_HEADER = "rank,path,conformer,stage,fitted_nodes,pairs,in_place,passing,fit,ideal,fraction,best_fit,best_fraction,occupied_nodes"
-
-
-def write_pose_fit_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, mode: str, refine: dict | None) -> None:
-    """One row per hit of the k best, in the order of the poses CSV, with stage `fit`: the pose of the hit's best conformer (`engine.align`)
-    scored in place (`engine.pose_fit`) - in mode `key` over the pairs of the explaining match, in mode `free` over every hotspot of a type
-    the node has. Nodes with a pair, pairs, nodes in place, passing pairs, the fit, its ideal and their ratio, the same over each node's
-    nearest hotspot, and the occupied model nodes joined by `;`. With `refine` (the arguments of the refine CSV) a second row per hit, stage
-    `refined`, for the motion `engine.refine` ends at. Every float is the `repr` of the float64 the GPU returned."""
-    from .engine import explain
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    ex = explain(model, lib, order, weights=weights)
-    _, _, keys = ex._own_rows(None)
-    al = ex.poses(model, lib, weights=weights)
-    keys = keys if mode == "key" else None
-    stages = [("fit", al.pose_fit(model, lib, keys=keys, weights=weights))]
-    if refine is not None:
-        atoms = _hit_atoms(refine.get("store"), names, order, al.rows) if refine["level"] == "atoms" else None
-        ref = al.refine(refine["pocket"], lib, atoms=atoms, tolerance=refine["tolerance"], restraint=refine["restraint"], max_iter=refine["max_iter"])
-        stages.append(("refined", ref.pose_fit(model, lib, keys=keys, weights=weights)))
-    with open(out, "w") as w:
-        w.write(POSE_FIT_HEADER + "\n")
-        for r, row in enumerate(al.rows):
-            for stage, pf in stages:
-                nums = ",".join(repr(float(v)) for v in (pf.fit[r], pf.ideal[r], pf.fraction[r], pf.best_fit[r], pf.best_fraction[r]))
-                w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{stage},{int(pf.n_nodes[r])},{int(pf.n_pairs[r])},{int(pf.n_in_place[r])},"
-                        f"{int(pf.n_passing[r])},{nums},{';'.join(str(int(m)) for m in pf.occupied(r))}\n")
-
-
-POSE_SHAPE_HEADER = ("rank,path,conformer,stage,level,points,covered,reference_atoms,reference_covered,overlap,tanimoto,reference_fraction,fit_fraction,rms_to_reference,"
-                     "rms_from_reference")
-
-
-def write_pose_shape_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, reference, level: str, cover: float,
-                         store: PackedAtoms | None = None, refine: dict | None = None) -> None:
-    """One row per hit of the k best, in the order of the poses CSV, with stage `fit`: the pose of the hit's best conformer (`engine.align`)
-    compared with the known ligand `reference` (`engine.shape`) - at level `nodes` the hit's pharmacophore nodes, at level `atoms` its heavy
-    atoms, from where the clashes CSV takes them. Points and the points within `cover` of a reference atom, the reference's atoms and
-    those within `cover` of a point, the overlap volume, the shape Tanimoto, the fraction of the reference that is filled and of the hit that
-    lies inside it, and the root mean square nearest-atom distance both ways. With `refine` (the arguments of the refine CSV) a second row
-    per hit, stage `refined`, for the motion `engine.refine` ends at. Every float is the `repr` of the float64 the GPU returned."""
-    from .engine import explain
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
-    atoms = _hit_atoms(store, names, order, al.rows) if level == "atoms" else None
-    stages = [("fit", al.shape(reference, lib, atoms=atoms, cover=cover))]
-    if refine is not None:
-        moved = _hit_atoms(refine.get("store"), names, order, al.rows) if refine["level"] == "atoms" else None
-        ref = al.refine(refine["pocket"], lib, atoms=moved, tolerance=refine["tolerance"], restraint=refine["restraint"], max_iter=refine["max_iter"])
-        stages.append(("refined", ref.shape(reference, lib, atoms=atoms, cover=cover)))
-    with open(out, "w") as w:
-        w.write(POSE_SHAPE_HEADER + "\n")
-        for r, row in enumerate(al.rows):
-            for stage, sh in stages:
-                nums = ",".join(repr(float(v)) for v in (sh.overlap[r], sh.tanimoto[r], sh.reference_fraction[r], sh.fit_fraction[r], sh.rms_to_reference[r], sh.rms_from_reference[r]))
-                w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{stage},{level},{int(sh.n_points[r])},{int(sh.n_covered[r])},{len(reference)},"
-                        f"{int(sh.n_reference_covered[r])},{nums}\n")
-
-
-OVERLAY_HEADER = ("rank,path,conformer,level,start,points,iterations,stop,tanimoto_start,tanimoto,overlap,reference_fraction,fit_fraction,angle_deg,shift,"
-                  "r00,r01,r02,r10,r11,r12,r20,r21,r22,tx,ty,tz")
-
-
-def write_overlay_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, reference, level: str, starts: int, max_iter: int,
-                      store: PackedAtoms | None = None) -> None:
-    """One row per hit of the k best, in the order of the poses CSV: the hit's best conformer overlaid on the known ligand `reference`
-    (`engine.overlay`) - at level `nodes` its pharmacophore nodes, at level `atoms` its heavy atoms, from where the pose-shape CSV takes
-    them. With `starts` 4 the hit is run from the four inertial starts and `start` says which was kept; with 0 it is run from its fitted
-    pose (`engine.align`) and `start` is -1. The shape Tanimoto at the start and at the end, the overlap volume there, the fraction of the
-    reference that is filled and of the hit that lies inside it, the net rotation in degrees and the centroid's shift from the start, and
-    the motion. Every float is the `repr` of the float64 the GPU returned (the two fractions and the degrees are formed from them)."""
-    from .engine import _pose_source, explain, overlay
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
-    atoms = _hit_atoms(store, names, order, al.rows) if level == "atoms" else None
-    if starts:
-        _, source = _pose_source(al, "--overlay_out", None, lib, atoms)
-        ov = overlay(reference, starts=starts, max_iter=max_iter, **source)
-    else:
-        ov = al.overlay(reference, lib, atoms=atoms, max_iter=max_iter)
-    with np.errstate(all="ignore"):
-        ref_fraction = ov.overlap / ov.reference_overlap
-        fit_fraction = np.where(ov.self_overlap == 0.0, 0.0, ov.overlap / np.where(ov.self_overlap == 0.0, 1.0, ov.self_overlap))
-    with open(out, "w") as w:
-        w.write(OVERLAY_HEADER + "\n")
-        for r, row in enumerate(al.rows):
-            nums = ",".join(repr(float(v)) for v in (ov.tanimoto_start[r], ov.tanimoto[r], ov.overlap[r], ref_fraction[r], fit_fraction[r], np.degrees(ov.angle[r]), ov.shift[r],
-                                                      *ov.rotation[r].reshape(-1), *ov.translation[r]))
-            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{level},{int(ov.start[r])},{int(ov.n_points[r])},{int(ov.iterations[r])},{int(ov.stop[r])},{nums}\n")
-
-
-POSE_COLOUR_HEADER = ("rank,path,conformer,stage,nodes,matched,reference_features,reference_matched,colour_overlap,colour_tanimoto,reference_fraction,fit_fraction,"
-                      + ",".join(TYPE_NAMES))
-
-
-def write_pose_colour_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, reference, cover: float) -> None:
-    """One row per hit of the k best, in the order of the poses CSV, with stage `fit`: the pharmacophore nodes of the hit's best conformer
-    under its fitted pose (`engine.align`) compared with the known ligand's typed features `reference` (`engine.colour`). Nodes and the
-    nodes with a partner of a shared type within `cover`, the reference's features and those reproduced, the colour overlap, its Tanimoto,
-    the fraction of the reference that is reproduced and of the hit that lies on it, and the overlap each type carries. Every float is the
-    `repr` of the float64 the GPU returned."""
-    from .engine import colour_of, explain
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
-    rep = colour_of(al, reference, lib, cover=cover)
-    with open(out, "w") as w:
-        w.write(POSE_COLOUR_HEADER + "\n")
-        for r, row in enumerate(al.rows):
-            nums = ",".join(repr(float(v)) for v in (rep.overlap[r], rep.tanimoto[r], rep.reference_fraction[r], rep.fit_fraction[r], *rep.type_overlap[r]))
-            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},fit,{int(rep.n_nodes[r])},{int(rep.n_matched[r])},{len(reference)},"
-                    f"{int(rep.n_reference_matched[r])},{nums}\n")
-
-
-COMBO_HEADER = OVERLAY_HEADER + ",colour_tanimoto_start,colour_tanimoto,combo"
-
-
-def write_combo_csv(out: Path, names: list[str], scores: np.ndarray, status: np.ndarray, model, lib, weights, k: int, reference, colour, colour_weight, level: str, starts: int,
-                    max_iter: int, store: PackedAtoms | None = None) -> None:
-    """One row per hit of the k best, in the order of the poses CSV: the hit's best conformer overlaid on the known ligand by shape and
-    colour together (`engine.combo_overlay`; `reference` its atoms, `colour` its typed features). The columns of the overlay CSV - the
-    shape points at level `nodes` the hit's pharmacophore nodes, at level `atoms` its heavy atoms - and the colour Tanimoto at the start
-    and at the end and the combo at the end, the sum of the two Tanimotos. The typed points are always the hit's nodes."""
-    from .engine import _heavy_atoms, combo_overlay, explain
-
-    key = np.where(np.asarray(status) != 0, -np.inf, scores.astype(np.float64))
-    order = [int(i) for i in np.lexsort((np.arange(len(scores)), -key))[:k] if status[i] == 0]
-    al = explain(model, lib, order, weights=weights).poses(model, lib, weights=weights)
-    atoms = _hit_atoms(store, names, order, al.rows) if level == "atoms" else None
-    source = {}
-    if atoms is not None and store is not None:
-        source = dict(atoms=atoms)
-    elif atoms is not None:  # (a directory's hits, read again: their heavy atoms as the caller's points)
-        points, radii = _heavy_atoms(atoms, al.conformers)
-        source = dict(points=points, point_radii=radii)
-    motion = {} if starts else dict(rotation=al.rotation, translation=al.translation)
-    ov = combo_overlay(reference, lib, al.indices, al.conformers, colour=colour, colour_weight=colour_weight, starts=starts, max_iter=max_iter, **motion, **source)
-    with np.errstate(all="ignore"):
-        ref_fraction = ov.overlap / ov.reference_overlap
-        fit_fraction = np.where(ov.self_overlap == 0.0, 0.0, ov.overlap / np.where(ov.self_overlap == 0.0, 1.0, ov.self_overlap))
-    with open(out, "w") as w:
-        w.write(COMBO_HEADER + "\n")
-        for r, row in enumerate(al.rows):
-            nums = ",".join(repr(float(v)) for v in (ov.tanimoto_start[r], ov.tanimoto[r], ov.overlap[r], ref_fraction[r], fit_fraction[r], np.degrees(ov.angle[r]), ov.shift[r],
-                                                      *ov.rotation[r].reshape(-1), *ov.translation[r], ov.colour_tanimoto_start[r], ov.colour_tanimoto[r], ov.combo[r]))
-            w.write(f"{int(row) + 1},{names[order[int(row)]]},{int(al.conformers[r])},{level},{int(ov.start[r])},{int(ov.n_points[r])},{int(ov.iterations[r])},{int(ov.stop[r])},{nums}\n")
-
-
 if __name__ == "__main__":
     main()
+

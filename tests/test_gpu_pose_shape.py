@@ -433,12 +433,12 @@ def test_fitting_with_a_reference_changes_no_other_field():
 
 def test_cli_pose_shape_csv(tmp_path):
     from pharmaconet_amd.engine import explain
-    from pharmaconet_amd.screening import POSE_SHAPE_HEADER, main, write_pose_shape_csv
+    from pharmaconet_amd.screening import POSE_SHAPE_HEADER, Hits, main, write_pose_shape_csv
     from test_gpu_clash import pocket_6oim
 
     model, lib, _, _ = load_golden("set_6oim_c8")
     ref, pocket = golden_reference(), pocket_6oim()
-    lib = small_library(lib, 12)  # (the command line is what is tested; every side CSV explains its hits again)
+    lib = small_library(lib, 12)  # (the command line is what is tested)
     libfile = tmp_path / "lib.pmxlib"
     lib.save(libfile)
     args = ["-p", str(GOLDEN / "model_6oim_like.pm"), "-d", str(libfile), "--explain", "5"]
@@ -473,6 +473,6 @@ def test_cli_pose_shape_csv(tmp_path):
     # without the refinement one row per hit: the writer itself, under scores that rank the same five hits in the same order
     scores = np.zeros(len(lib), np.float32)
     scores[idx] = np.arange(len(idx), 0, -1)
-    write_pose_shape_csv(tmp_path / "short.csv", list(names), scores, np.zeros(len(lib), np.int32), model, lib, None, 5, ref, "nodes", 2.5)
+    write_pose_shape_csv(tmp_path / "short.csv", Hits(list(names), scores, np.zeros(len(lib), np.int32), model, lib, None, 5), ref, "nodes", 2.5)
     short = (tmp_path / "short.csv").read_text().splitlines()
     assert len(short) == 6 and short[1:] == rows[1::2]
